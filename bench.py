@@ -2,15 +2,22 @@
 """bench.py -- env steps/s of the batched RMSA step() hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--chunk T] [--mixed] [--only NAME] [--dry-run]
+                    [--full] [--dump-outputs DIR]
 
 One bench "step" = ONE LAUNCH of the persistent step kernel = every environment of the batch advances by `chunk`
 (default 1000) RMSAEnv.step calls (policy -> provision -> release -> next arrival, all statistics).  K timed launches
 follow W >= 1 untimed launches of the same shape (so every environment has made >= 300 steps -- SURVEY 8(d) config 2 --
 and the network is in its steady state before the clock starts); ms_per_step x K = the timed region.
 
+A plain run times the headline only.  --full adds the sub-records below and the same-box CPU baseline (`cpu_baseline`).
+--dump-outputs DIR writes, after the timed launches, what they leave a caller of the headline's `env.run` (the state of the
+batch, read back through the package's accessors) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared
+array for array.
+
 Headline workload at N=1: the batch BASELINE.json's north_star quotes its target on -- RMSA-v0, NSFNET, 320 slots,
 load 50, B = 65 536 environments per GPU, shortest-available-path first fit run on the device, seeds 10 + i, full
-statistics.  Sub-records (N=1 only), each timed the same way with its own roofline block and kernel name:
+statistics.  Sub-records (N=1; all with --full, one with --only NAME), each timed the same way with its own roofline block
+and kernel name:
     rmsa_b4096        BASELINE configs[1] (the same env x 4096)
     phy_us14_b4096    BASELINE configs[2]: QoT-aware RMSA, US14, load 1400, bmfa -- with number_cuts_total / rss_total_metric
                       written every step as the reference's step() does (lead), without them, with the periodic
@@ -71,7 +78,14 @@ def parse_args(argv=None):
                     "ends with its slowest environment: 250-step launches run 3-6 %% below 1000-step ones)")
     ap.add_argument("--mixed", action="store_true", help="configs[4]: NSFNET / JPN12 / US14 topology groups, one per rank (r %% 3)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: ranks report their shard through gloo (launcher test)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also the BASELINE configs[1-3] sub-records and the same-box CPU baseline "
+                    "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed launches, write the state they leave "
+                    "(float64 / float32 .npy files, a fixed seeded sample of the per-link arrays) to DIR")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.only not in (None, "headline", "rmsa_b4096"):
+        ap.error(f"--dump-outputs writes the outputs of the RMSA record: not with --only {args.only}")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -194,7 +208,48 @@ class Clock:
         return elapsed, [a.elapsed_time(b) for a, b in ev]
 
 
-def rmsa_record(clock, topo_name, B, chunk, warm, steps, args, rank, local_rank, key):
+DUMP_MAX_ENVS = 65536          # per-environment arrays: every environment up to this batch, a fixed seeded sample above it
+DUMP_SAMPLE_ENVS = 256         # per-link arrays and the occupancy: a fixed seeded sample of environments
+DUMP_SAMPLE_BYTES = 32 << 20   # ... fewer environments if their per-link arrays would exceed this
+
+
+def dump_outputs(env, out_dir, suffix=""):
+    """--dump-outputs: the timed launches ask for no per-step arrays, so what they leave a caller is the state of the batch:
+    counters, clock, pending request, running services, episodes and link / graph statistics of every environment, the slot
+    occupancy of a sample.  Written as float64 (the occupancy as float32), at most ~45 MB in all."""
+    import numpy as np
+    from optical_rl_gym_amd.batched import COUNTER_NAMES
+    B, E, S = env.batch_size, env.topology.num_links, env.num_spectrum_resources
+    rng = np.random.default_rng(20240101)
+    rows = np.arange(B) if B <= DUMP_MAX_ENVS else np.sort(rng.choice(B, DUMP_MAX_ENVS, replace=False))
+    n = max(1, min(B, DUMP_SAMPLE_ENVS, DUMP_SAMPLE_BYTES // (E * S * 4 + E * 4 * 8)))
+    sample = np.sort(rng.choice(B, n, replace=False))
+    c = env.counters()
+    req = env.requests()
+    ls = env.link_stats()
+    gs = env.graph_stats()
+    words = env.occupancy_words()[sample]
+    free = np.unpackbits(words.view(np.uint8), axis=-1, bitorder="little").reshape(n, E, -1)[:, :, :S]   # 1 = free slot
+    arrays = {
+        "env_index": rows,
+        "counters": np.stack([c[k] for k in COUNTER_NAMES], axis=1)[rows],
+        "current_time": env.current_time()[rows],
+        "pending_request": np.stack([req[k].astype(np.float64) for k in req.dtype.names], axis=1)[rows],
+        "num_running": env.num_running()[rows],
+        "episodes_done": env.episodes_done()[rows],
+        "graph_stats": np.stack([gs[k] for k in ("throughput", "compactness", "last_update")], axis=1)[rows],
+        "reduced_counters": env.reduce_counters()[1],
+        "sample_env_index": sample,
+        "sample_link_stats": np.stack([ls[k] for k in ("utilization", "external_fragmentation", "compactness", "last_update")],
+                                      axis=2)[sample],
+        "sample_available_slots": free.astype(np.float32),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
+
+
+def rmsa_record(clock, topo_name, B, chunk, warm, steps, args, rank, local_rank, key, dump_dir=None, dump_suffix=""):
     import numpy as np
     from conftest import load_topology
     from optical_rl_gym_amd import BatchedRMSAEnv
@@ -207,6 +262,8 @@ def rmsa_record(clock, topo_name, B, chunk, warm, steps, args, rank, local_rank,
     for _ in range(max(1, warm)):
         launch()
     elapsed, kms = clock.timed(launch, steps)
+    if dump_dir:
+        dump_outputs(env, dump_dir, dump_suffix)
     red, vec = env.reduce_counters()
     kernel = env.last_kernel()
     W = env.words_per_link
@@ -513,7 +570,8 @@ def main():
         B = 4096 if only == "rmsa_b4096" else args.batch
         topo_name = MIXED[rank % 3] if args.mixed else TOPOLOGY
         key = "rmsa_b%d" % B
-        rec, vec, elapsed, topo = rmsa_record(clock, topo_name, B, args.chunk, args.warmup, args.steps, args, rank, local_rank, key)
+        rec, vec, elapsed, topo = rmsa_record(clock, topo_name, B, args.chunk, args.warmup, args.steps, args, rank, local_rank, key,
+                                              dump_dir=args.dump_outputs, dump_suffix="" if world == 1 else "_rank%d" % rank)
         # statistics all-reduce (the path's only collective) and the slowest rank's clock
         stats = allreduce_stats(vec, dist, dev)
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -555,7 +613,7 @@ def main():
             out["collective"] = collective
         if elapsed < 1.0:
             out["timed_region_short"] = "timed region below 1 s: raise --steps"
-    if rank == 0 and world == 1 and not args.no_sub_records:
+    if rank == 0 and world == 1 and not args.no_sub_records and (args.full or only is not None):
         jobs = {"rmsa_b4096": lambda: rmsa_record(clock, TOPOLOGY, 4096, args.chunk, 1, 100, args, 0, 0, "rmsa_b4096")[0],
                 "phy_metrics": lambda: phy_record(clock, args, "phy_metrics"),
                 "phy": lambda: phy_record(clock, args, "phy"),
@@ -576,7 +634,7 @@ def main():
                      "phy_gn": "phy_us14_b4096_gn_gate (BASELINE configs[2] as worded)",
                      "deeprmsa": "deeprmsa_b32768 (BASELINE configs[3])"}
             out["sub_records"] = {names[k]: v for k, v in sub.items()}
-        if world == 1 and not args.no_cpu_baseline and only is None:
+        if world == 1 and args.full and not args.no_cpu_baseline and only is None:
             from conftest import load_topology
             out["cpu_baseline"] = cpu_baseline(load_topology(TOPOLOGY))
         print(json.dumps(compact(out)), flush=True)

@@ -1,8 +1,11 @@
+# Kernel-trace statistics of every kernel of the full bench line (headline + sub-records, no CPU baseline).
+# usage (GPU box): bash tools/prof_kernel_trace.sh [output directory, default profile_out/kernel_trace]
 set -e
-mkdir -p gpurun_out/prof
-cd /tmp && export TMPDIR=/tmp
-cd $GRAFT_REPO_ROOT
-timeout -k 10 300 python bench.py --no-cpu-baseline > gpurun_out/bench2.log 2>&1
-tail -2 gpurun_out/bench2.log
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof/kt -- python bench.py --no-cpu-baseline > gpurun_out/prof_kt.log 2>&1
-find gpurun_out/prof -name "*stats*" | head
+cd "$(dirname "$0")/.."
+out=${1:-profile_out/kernel_trace}
+mkdir -p $out
+export TMPDIR=/tmp
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $out/bench.log 2>&1
+tail -2 $out/bench.log
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -- python bench.py --full --no-cpu-baseline > $out/kt.log 2>&1
+find $out -name "*stats*" | head

@@ -2,7 +2,7 @@
 set -e
 mkdir -p gpurun_out/pmc
 export TMPDIR=/tmp
-ARGS="--no-cpu-baseline --steps 500 --warmup 500 $@"
+ARGS="--full --no-cpu-baseline --steps 500 --warmup 500 $@"
 run() { # name counters...
   name=$1; shift
   timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d gpurun_out/pmc/$name -- python bench.py $ARGS > gpurun_out/pmc_$name.log 2>&1 || { tail -5 gpurun_out/pmc_$name.log; return 1; }
