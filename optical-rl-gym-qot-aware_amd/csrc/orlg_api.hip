@@ -51,6 +51,7 @@ struct orlg_env {
     int group_resident_hq[ORLG_GROUP_WAVES + 1];
     int group_resident_df[ORLG_GROUP_WAVES + 1];   // ... of the instantiation with the link statistics deferred
     int group_df_lint, group_df_qtime, group_df_qdesc, group_df_wave_bytes, group_df_wpb;   // its LDS layout (no link-statistics slices)
+    int group_df_lsum;   // ... whose place the links' summaries take (8 bytes per link, group_release_links)
     uint4 *llog;             // its log of link updates [B][E][64] (allocated with the first such launch)
     uint32_t *progress;      // chunked tickets: chunks completed per quad in the current launch (allocated with the first such launch)
     size_t group_lds_bytes;
@@ -329,7 +330,7 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p) {
     if (nblocks > resident[wpb]) nblocks = resident[wpb];
     OrlgParams q = p;
     q.llog = df ? e->llog : nullptr;
-    if (df) { q.g_lint = e->group_df_lint; q.g_qtime = e->group_df_qtime; q.g_qdesc = e->group_df_qdesc; }
+    if (df) { q.g_lint = e->group_df_lint; q.g_qtime = e->group_df_qtime; q.g_qdesc = e->group_df_qdesc; q.g_lstat = e->group_df_lsum; }
     q.g_wave_bytes = wave_bytes;
     q.ticket_base = e->ticket_base;
     q.ticket_stride = p.n_steps <= 16 ? 1u : 0u;
@@ -708,6 +709,7 @@ int orlg_create(const orlg_topology *t, const orlg_rmsa_config *c, int32_t batch
             e->group_df_lint = gd; gd = up16(gd + 4 * p.lint_stride * 4);
             e->group_df_qtime = gd; gd = up16(gd + 4 * Q * 8);
             e->group_df_qdesc = gd; gd = up16(gd + 4 * Q * 4);
+            e->group_df_lsum = gd; gd = up16(gd + 4 * E * 8);
             e->group_df_wave_bytes = gd;
             e->group_df_wpb = 0;
             for (int cand = ORLG_GROUP_WAVES; cand >= 1 && !e->group_df_wpb; cand--)

@@ -70,6 +70,15 @@ ORLG_SEG_REDUCE(seg_add, ORLG_OP_ADD)
 ORLG_SEG_REDUCE(seg_max, ORLG_OP_MAX)
 #undef ORLG_SEG_REDUCE
 
+// A link's summary (DEFER instantiation, LDS only): every integer _update_link_stats consumes, 10 bits each -- free slots, free
+// runs, used runs, first used slot (lmin), end of the last used run (lmax), longest free run, slot 0 free, slot S - 1 free.  With
+// no used slot lmin / lmax are group_link_stats' 0x7fff / 0 and lmin keeps only its low 10 bits: a summary is read at a release
+// only, when the link holds the window (at least one used slot).
+DEV u64 lsum_pack(int freec, int F, int U, int lmin, int lmax, int ml, bool ff, bool lf) {
+    return (u64)((uint32_t)freec | ((uint32_t)F << 10) | ((uint32_t)U << 20)) |
+           ((u64)((uint32_t)(lmin & 0x3ff) | ((uint32_t)lmax << 10) | ((uint32_t)ml << 20) | ((uint32_t)ff << 30) | ((uint32_t)lf << 31)) << 32);
+}
+
 // link statistics of up to ORLG_MAX_HOPS links per row: link_stats_update (orlg_kernels.hip) with 16 / W links per row and
 // pass, one word per lane; nlinks = 0 for a row that does not take part.  links: the row's link indices (bytes, LDS).
 // DEFER: the float64 part of _update_link_stats is not done here.  It is a recurrence PER LINK -- the time-weighted means of
@@ -79,11 +88,15 @@ ORLG_SEG_REDUCE(seg_max, ORLG_OP_MAX)
 // entries in the upper bits of the link's span cache, and group_link_replay works the logs off with ONE LINK PER LANE, sixteen
 // links of an environment at a time, every lane through its own link's events in their order -- the same operations on the
 // same values, so the same bits.
-template <int W, bool LINKF, bool GRAPH, bool DEFER = false>
+// SUM (DEFER): 1 = also write each link's summary (lsum_pack) to lsum[link]; 2 = ONLY that, for links 0 .. nlinks - 1 (links is
+// not read): the summaries of a quad whose state was just loaded, without a log entry, span cache or running sum touched.
+template <int W, bool LINKF, bool GRAPH, bool DEFER = false, int SUM = 0>
 DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, const Tab &tb, int S, int E, const uint8_t *links,
                           int nlinks, double now, int &sum_span, int &sum_gaps, double &comp_cur, int sum_sh, double cur_thr,
-                          double &g_thr, double &g_comp, double &g_lu, uint4 *llog = nullptr, bool *need_replay = nullptr) {
+                          double &g_thr, double &g_comp, double &g_lu, uint4 *llog = nullptr, bool *need_replay = nullptr,
+                          u64 *lsum = nullptr) {
     static_assert(W <= 8, "at least two links per row");
+    static_assert(SUM == 0 || (LINKF && DEFER && (SUM == 1 || !GRAPH)), "summaries belong to the deferred instantiation");
     constexpr int NS = ORLG_GL / W;  // links per row and pass
     const int gl = lane & 15;
     const int sl = gl / W, w = gl - sl * W;
@@ -95,7 +108,7 @@ DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, 
         const bool on = sl < NS && h < nlinks;
         int link = 0;
         uint32_t packed = 0u, ilo = 0u, hi = 0u, ml = 0u;   // ilo = 0x7fff - first used slot (0: none): the minimum taken as a maximum
-        if (on) link = (int)links[h];
+        if (on) link = SUM == 2 ? h : (int)links[h];
         // the link's words sit on consecutive lanes: the neighbours' words arrive by DPP instead of further LDS reads
         u64 x = 0ull;
         if (on) x = occ[__mul24(link, W) + w];
@@ -146,6 +159,8 @@ DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, 
         if (LINKF) ml = seg_max<W>(ml);
         const int freec = (int)(packed & 0x3ff), F = (int)((packed >> 10) & 0x3ff), U = (int)(packed >> 20);
         const bool link_lane = on && w == 0;  // one lane per link carries on
+        if (SUM != 0 && link_lane) lsum[link] = lsum_pack(freec, F, U, lmin, lmax, (int)ml, first_free, last_free);
+        if (SUM == 2) { wave_sync(); continue; }
         int dspan = 0, dgaps = 0;
         if (link_lane) {
             int nspan = U > 1 ? lmax - lmin : 0, ngaps = U > 1 ? U - 1 : 0;
@@ -189,7 +204,7 @@ DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, 
         if (LINKF && !DEFER && link_lane) lst[3 * E + link] = now;
         wave_sync();
     }
-    if (GRAPH && nlinks > 0) {
+    if (GRAPH && SUM != 2 && nlinks > 0) {
         // _update_network_stats (rmsa_env.py:537-560), on every lane of the row
         comp_cur = network_compactness(sum_span, sum_sh, sum_gaps, E);
         if (now > 0) {
@@ -199,6 +214,98 @@ DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, 
         }
         g_lu = now;
     }
+}
+
+// Release of the window [s, s+n) on the row's path (DEFER instantiation): group_apply_window + group_link_stats in ONE pass, lane
+// = hop.  The window was wholly in use, so every integer of the link's statistics follows from its summary and the free runs
+// that border the window -- L slots ending at s - 1, R slots starting at s + n: free slots + n, free runs + 1 - [L > 0] - [R > 0],
+// used runs + [slot s - 1 used] + [slot s + n used] - 1, longest free run max(ml, L + n + R) (a release never shortens it), the
+// first / last used slot move only where the window was one, slot 0 / S - 1 are free once the window held them.  The lane reads
+// the words next to and under the window at once (independent LDS reads), ORs the window into the one or two words it covers,
+// looks further out only where a bordering free run reaches a word's end, then logs the update and refreshes the span cache
+// exactly as group_link_stats would (the same values, so the same bits).
+template <int W>
+DEV void group_release_links(const int lane, u64 *occ, u64 *lsum, int32_t *lint, int S, const uint8_t *links, int hops, int s, int n,
+                             double now, int &sum_span, int &sum_gaps, uint4 *llog, bool &need_replay) {
+    static_assert(ORLG_MAX_HOPS <= ORLG_GL, "one lane per hop");
+    const int gl = lane & 15;
+    int dspan = 0, dgaps = 0;
+    if (gl < hops) {
+        const int link = (int)links[gl];
+        u64 *lw = occ + __mul24(link, W);
+        const int e = s + n;
+        // the words that hold slot s - 1, slot s + n, and the window's first / last slot: independent reads (coinciding ones too)
+        const int ia = s > 0 ? (s - 1) >> 6 : 0, ib = e < S ? e >> 6 : 0, ws = s >> 6, we = (e - 1) >> 6;
+        const u64 xa = lw[ia], xb = lw[ib], xs = lw[ws], xe = lw[we];
+        const u64 sm = lsum[link];
+        // the window's bits (a window wider than 64 slots fills the words between its first and last one)
+        const u64 hm = ~0ull << (s & 63), lm = ~0ull >> (63 - ((e - 1) & 63));
+        if (ws == we) {
+            lw[ws] = xs | (hm & lm);
+        } else {
+            lw[ws] = xs | hm;
+            for (int j = ws + 1; j < we; ++j) lw[j] = ~0ull;
+            lw[we] = xe | lm;
+        }
+        // p = the last used slot below s (none: -1), q = the first slot from s + n on that is not free (none: 64 W; slots >= S
+        // are stored as not free, so q <= S): in the word next to the window, else further out word by word (rarely more than one)
+        int p = -1, q = 64 * W;
+        if (s > 0) {
+            const u64 y = ~xa & (~0ull >> (63 - ((s - 1) & 63)));
+            if (y) p = 64 * ia + 63 - clz64(y);
+            else
+                for (int j = ia - 1; j >= 0; --j) {
+                    const u64 v = ~lw[j];
+                    if (v) { p = 64 * j + 63 - clz64(v); break; }
+                }
+        }
+        if (e < S) {
+            const u64 y = ~xb & (~0ull << (e & 63));
+            if (y) q = 64 * ib + ctz64(y);
+            else
+                for (int j = ib + 1; j < W; ++j) {
+                    const u64 v = ~lw[j];
+                    if (v) { q = 64 * j + ctz64(v); break; }
+                }
+        } else {
+            q = e;
+        }
+        const int L = s - 1 - p, R = q - e;
+        const uint32_t lo32 = (uint32_t)sm, hi32 = (uint32_t)(sm >> 32);
+        const int freec = (int)(lo32 & 0x3ff) + n;
+        const int F = (int)((lo32 >> 10) & 0x3ff) + 1 - (L > 0) - (R > 0);
+        const int U = (int)((lo32 >> 20) & 0x3ff) + (s > 0 && L == 0) + (e < S && R == 0) - 1;
+        int lmin = (int)(hi32 & 0x3ff);   // (a window in use: U >= 1 before, lmin is a slot)
+        int lmax = (int)((hi32 >> 10) & 0x3ff);
+        int ml = (int)((hi32 >> 20) & 0x3ff);
+        const bool ff = ((hi32 >> 30) & 1u) || s == 0, lf = (hi32 >> 31) || e == S;
+        ml = L + n + R > ml ? L + n + R : ml;
+        if (U == 0) { lmin = 0x7fff; lmax = 0; }
+        else {
+            if (lmin == s) lmin = e + R;
+            if (lmax == e) lmax = s - L;
+        }
+        lsum[link] = lsum_pack(freec, F, U, lmin, lmax, ml, ff, lf);
+        // group_link_stats' link lane from here on
+        const int nspan = U > 1 ? lmax - lmin : 0, ngaps = U > 1 ? U - 1 : 0;
+        int old = lint[link];
+        int cnt = (int)((uint32_t)old >> 26);
+        const int max_empty = (F > 1 && !(F == 2 && ff && lf)) ? ml : 0;
+        if (cnt < ORLG_LLOG_CAP - 1) {
+            llog[__mul24(link, ORLG_LLOG_CAP) + cnt] =
+                make_uint4((uint32_t)freec | ((uint32_t)max_empty << 10) | ((uint32_t)(lmax - lmin) << 20), (uint32_t)U,
+                           (uint32_t)__double2loint(now), (uint32_t)__double2hiint(now));
+            cnt += 1;
+        }
+        if (cnt >= ORLG_LLOG_FLUSH) need_replay = true;
+        old &= 0x03ffffff;
+        lint[link] = nspan | (ngaps << 16) | (cnt << 26);
+        dspan = nspan - (old & 0xffff);
+        dgaps = ngaps - (old >> 16);
+    }
+    sum_span += row_add_i32(dspan);
+    sum_gaps += row_add_i32(dgaps);
+    wave_sync();
 }
 
 DEV void group_link_replay(const int lane, double *lst, int32_t *lint, const Tab &tb, int S, int E, const uint4 *llog) {
@@ -289,6 +396,9 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
     // bytes per environment they took of the LDS buy a twelfth wave per CU)
     double *lst = DEFER ? nullptr : reinterpret_cast<double *>(wbase + p.g_lstat) + g * 4 * p.E;
     int32_t *lint = reinterpret_cast<int32_t *>(wbase + p.g_lint) + g * p.lint_stride;
+    // DEFER: the links' summaries (lsum_pack) take the place of the statistics' slices; built whenever a quad's state is loaded,
+    // kept by every provision and release -- LDS only, the state in HBM does not hold them
+    u64 *lsum = DEFER ? reinterpret_cast<u64 *>(wbase + p.g_lstat) + g * p.E : nullptr;
 
     const int E = p.E, S = p.S, K = p.K, N = p.N, NBR = p.NBR, Q = p.Q, NW = p.NW;
     constexpr bool NET = STATS >= 1;
@@ -382,6 +492,9 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
     wave_sync();
     double comp_cur = 1.0;
     if (NET) comp_cur = network_compactness(sum_span, sum_sh, sum_gaps, E);
+    if (DEFER)   // the summaries of all E links, from the occupancy just loaded
+        group_link_stats<W, true, false, true, 2>(lane, occ, nullptr, lint, tb, S, E, nullptr, E, 0.0, sum_span, sum_gaps, comp_cur,
+                                                  0, 0.0, g_thr, g_comp, g_lu, nullptr, nullptr, lsum);
     // release queue: a time-sorted ring in LDS (OrlgParams::qtime) -- q_n entries from slot q_head on; the row keeps the time of
     // its head in a register, so that a step without a due release touches no queue memory
     int q_head = gs->q_head, q_n = n_running < Q ? n_running : Q;   // (n_running also counts services an overflow lost)
@@ -543,8 +656,9 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
         }
         SEC(4);  // statistics at provision
         if (NET)
-            group_link_stats<W, FULL, true, DEFER>(lane, occ, lst, lint, tb, S, E, rec->link, accepted ? hops : 0, current_time, sum_span,
-                                                   sum_gaps, comp_cur, sum_sh, (double)sum_bitrate_running, g_thr, g_comp, g_lu, llog, &need_replay);
+            group_link_stats<W, FULL, true, DEFER, DEFER ? 1 : 0>(lane, occ, lst, lint, tb, S, E, rec->link, accepted ? hops : 0, current_time,
+                                                                 sum_span, sum_gaps, comp_cur, sum_sh, (double)sum_bitrate_running, g_thr,
+                                                                 g_comp, g_lu, llog, &need_replay, lsum);
         SEC(5);  // queue insert
         {
             // ---- _add_release (optical_network_env.py:178-189): the entries that are released later move up one slot (from the
@@ -701,12 +815,21 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
                     sum_sh -= n2 * hops2;
                     released = true;
                 }
-                group_apply_window<W>(lane, occ, rec2->link, rel_now ? hops2 : 0, s0, n2, true);   // (ends with a wave_sync)
-                if (rel_now) next_rel = q_n > 0 ? qtime[q_head] : INF;   // the next entry
-                SEC(11);  // statistics at release
-                if (NET)
-                    group_link_stats<W, FULL, false, DEFER>(lane, occ, lst, lint, tb, S, E, rec2->link, rel_now ? hops2 : 0, current_time,
-                                                            sum_span, sum_gaps, comp_cur, sum_sh, 0.0, g_thr, g_comp, g_lu, llog, &need_replay);
+                if constexpr (DEFER) {
+                    // the window and its links' statistics in one pass, lane = hop (group_release_links; ends with a wave_sync)
+                    if (rel_now) next_rel = q_n > 0 ? qtime[q_head] : INF;   // the next entry
+                    group_release_links<W>(lane, occ, lsum, lint, S, rec2->link, rel_now ? hops2 : 0, s0, n2, current_time, sum_span,
+                                           sum_gaps, llog, need_replay);
+                    SEC(11);  // statistics at release: the log replays only
+                } else {
+                    group_apply_window<W>(lane, occ, rec2->link, rel_now ? hops2 : 0, s0, n2, true);   // (ends with a wave_sync)
+                    if (rel_now) next_rel = q_n > 0 ? qtime[q_head] : INF;   // the next entry
+                    SEC(11);  // statistics at release
+                    if (NET)
+                        group_link_stats<W, FULL, false, DEFER>(lane, occ, lst, lint, tb, S, E, rec2->link, rel_now ? hops2 : 0,
+                                                                current_time, sum_span, sum_gaps, comp_cur, sum_sh, 0.0, g_thr, g_comp,
+                                                                g_lu, llog, &need_replay);
+                }
                 if (DEFER && ballot(need_replay) != 0ull) {   // (a link's log never grows past ORLG_LLOG_FLUSH + 1 entries)
                     SEC(14);  // link replay
                     group_link_replay(lane, lst, lint, tb, S, E, llog);
