@@ -376,6 +376,31 @@ int orlg_phy_load_state(orlg_phy_env *env, const void *buffer);
 int orlg_phy_get_channel_state(orlg_phy_env *env, int32_t env_index, uint32_t *entries, uint8_t *lengths);
 int orlg_phy_channel_state_capacity(orlg_phy_env *env);
 
+/* ---- bit_rate_selection = "continuous" (phy_rmsa_env.py:37-42, 114-134, 979-984).  orlg_phy_config as for orlg_phy_create
+ * with bit_rate_cum = NULL and bit_rates = the integers lower .. higher, one apart (the RMSA convention, orlg_rmsa_config):
+ * every request's bit rate is rng.randint(lower, higher).  Refused: a higher bound that needs more than ORLG_PHY_MAX_CHANNELS
+ * channels at modulation level 1 (higher > 100 * ORLG_PHY_MAX_CHANNELS), and defrag_period > 0.  The handle keeps every
+ * share of a channel in float64 (channel_state tuples and service.channels[i][1]), updated in the reference's order of
+ * operations: use_existing_channels (:1650-1673) sums the residuals with a sequential sum in list order, takes
+ * unassigned -= free * 100, used = free + unassigned / 100, free' = unassigned / -100; the physical heuristics take
+ * used = level + unassigned / 100, free = unassigned / -100 for the last channel; _release_path (:781-845) compares
+ * used == capacity and result[1] == channel[1] exactly.  The int16 channels_used output of such a handle holds 0.
+ * 1 for a continuous handle, 0 for a discrete one. */
+int orlg_phy_continuous(orlg_phy_env *env);
+/* orlg_phy_step plus float64 shares.  act_share: EXTERNAL on a continuous handle, [B][ORLG_PHY_MAX_CHANNELS][2] the (used,
+ * free) fields of the reference's selected_channels tuples (fields 1 and 2, phy_rmsa_env.py:1305-1308, 1666-1670), read in
+ * place of act_channels' used field; NULL on a discrete handle.  channels_used_f64 / channels_free_f64: optional outputs
+ * [n_steps][B][ORLG_PHY_MAX_CHANNELS], the chosen channels' tuple fields 1 and 2 (0 padded); continuous handles only. */
+int orlg_phy_step_ex(orlg_phy_env *env, int32_t policy, int32_t n_steps, const int32_t *act_path, const int16_t *act_channels,
+                     const double *act_share, int32_t auto_reset, const orlg_phy_step_io *io, double *channels_used_f64,
+                     double *channels_free_f64);
+/* env.channel_state of ONE env as (channel, used, free, capacity) float64 tuples (phy_rmsa_env.py:117-125, 600-602, 640-644,
+ * 823-838): entries [N*N*K][capacity][4] in list order, lengths [N*N*K]; returns capacity.  Either kind of handle. */
+int orlg_phy_get_channel_state_f64(orlg_phy_env *env, int32_t env_index, double *entries, uint8_t *lengths);
+/* orlg_phy_load_state with the snapshot's size: ORLG_ERR_INVALID when it is not orlg_phy_state_size or the snapshot was
+ * saved by a handle of the other bit-rate mode (a continuous state ends in a 16-byte tag) */
+int orlg_phy_load_state_checked(orlg_phy_env *env, const void *buffer, int64_t bytes);
+
 /* ------------------------------------------------------------------------------------------------
  * GN-model GSNR admission check: calculate_osnr (examples/calculate_osnr.py:9-56) for a flattened batch of checks.
  * Check m walks links check_link_off[m]..check_link_off[m+1]; link l has spans link_span_off[l].. and the services

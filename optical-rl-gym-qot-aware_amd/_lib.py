@@ -151,6 +151,11 @@ def load(build_if_missing=True):
         getattr(L, name).argtypes = [vp, vp]
     L.orlg_phy_get_channel_state.argtypes = [vp, i32, vp, vp]
     L.orlg_phy_channel_state_capacity.argtypes = [vp]
+    # bit_rate_selection="continuous": float64 shares (include/orlg.h)
+    L.orlg_phy_continuous.argtypes = [vp]
+    L.orlg_phy_step_ex.argtypes = [vp, i32, i32, vp, vp, vp, i32, C.POINTER(PhyStepIO), vp, vp]
+    L.orlg_phy_get_channel_state_f64.argtypes = [vp, i32, vp, vp]
+    L.orlg_phy_load_state_checked.argtypes = [vp, vp, i64]
     L.orlg_host_log.argtypes = [C.c_double]
     L.orlg_host_log.restype = C.c_double
     _lib = L
@@ -170,6 +175,7 @@ EXPORTED_SYMBOLS = [
     "orlg_phy_get_occupancy", "orlg_phy_reduce_counters", "orlg_phy_get_channel_state",
     "orlg_phy_channel_state_capacity", "orlg_gn_osnr", "orlg_state_size", "orlg_save_state", "orlg_load_state",
     "orlg_phy_state_size", "orlg_phy_save_state", "orlg_phy_load_state",
+    "orlg_phy_continuous", "orlg_phy_step_ex", "orlg_phy_get_channel_state_f64", "orlg_phy_load_state_checked",
 ]
 
 

@@ -3,10 +3,15 @@
 #include "orlg_host.h"
 #include "orlg_phy_kernels.hip"   // data layout + device helpers
 
+// the last 16 bytes of a continuous handle's saved state ("orlg phy", "cont f64"): a snapshot of the other bit-rate mode is refused
+#define ORLG_PHY_CONT_TAG0 0x796870206772726full
+#define ORLG_PHY_CONT_TAG1 0x34366620746e6f63ull
+
 struct orlg_phy_env {
     OrlgPhyParams p;
     int W, device, waves_per_block, num_paths, num_cu;
-    int resident_blocks[32];   // per kernel variant (phy_launch)
+    int cont;                // bit_rate_selection="continuous": CONT instantiations, float64 shares (p.br_lower, cs_f, svc_f)
+    int resident_blocks[48];   // per kernel variant (phy_launch): 0..31 discrete, 32..47 continuous
     uint32_t ticket_base;
     hipStream_t stream;
     bool own_stream;
@@ -18,6 +23,10 @@ struct orlg_phy_env {
     size_t io_cap[ORLG_PHY_NUM_OUTS];
     int32_t *d_act_path;
     int16_t *d_act_ch;
+    double *d_act_share;     // (continuous handles: staging of the float64 shares of external actions)
+    double *f_buf;           // (continuous handles: the float64 per-step output (used, free) pairs)
+    size_t f_cap;
+    uint64_t *cont_tag;      // (continuous handles: the 16-byte tag at the end of the saved state)
     OrlgErrWord err;         // sticky error word the kernel sets when a queue / channel_state list / work list overflows
     char last_kernel[96];    // name and shape of the kernel behind the last launch (orlg_phy_last_kernel)
 };
@@ -56,7 +65,7 @@ __global__ void orlg_phy_clear_kernel(OrlgPhyParams p, int W, int keep_rng) {
 }
 
 enum { PX_REQUEST, PX_COUNTERS, PX_TIME, PX_RUNNING, PX_EPISODE };
-__global__ void orlg_phy_extract_kernel(OrlgPhyParams p, int what, unsigned char *out) {
+__global__ void orlg_phy_extract_kernel(OrlgPhyParams p, int what, unsigned char *out, int cont) {
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
     const size_t B = p.B;
     if (what == PX_REQUEST) {
@@ -64,7 +73,7 @@ __global__ void orlg_phy_extract_kernel(OrlgPhyParams p, int what, unsigned char
         for (size_t i = tid; i < B; i += nth) {
             const OrlgPhyScalars &s = p.scal[i];
             o[i].service_id = s.req_sid; o[i].src = s.req_src; o[i].dst = s.req_dst;
-            o[i].bit_rate = reinterpret_cast<const int32_t *>(p.tables + p.t_bitrates)[s.req_br];
+            o[i].bit_rate = cont ? p.br_lower + s.req_br : reinterpret_cast<const int32_t *>(p.tables + p.t_bitrates)[s.req_br];
             o[i].arrival_time = s.req_arrival; o[i].holding_time = s.req_holding;
         }
     } else if (what == PX_COUNTERS) {
@@ -157,7 +166,8 @@ static int phy_launch(orlg_phy_env *e, const OrlgPhyParams &p) {
     // admission check, 3 + GN-model admission check alone
     const int df = p.gn_on ? (p.defrag_period > 0 ? 2 : 3) : p.defrag_period > 0 ? 1 : 0;
     const int pol = p.mode == ORLG_MODE_STEP ? p.policy : ORLG_PHY_POLICY_EXTERNAL;   // one instantiation per policy
-    const int variant = df + 4 * (pol + 1);
+    // continuous bit rates: 32 + gn + 2 * (policy + 1) (no defragmentation)
+    const int variant = e->cont ? 32 + (p.gn_on ? 1 : 0) + 2 * (pol + 1) : df + 4 * (pol + 1);
     phy_kernel_t k = pick_phy(e->W, variant);
     if (!k) return fail(ORLG_ERR_INVALID, "no PhyRMSA kernel for W=%d", e->W);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -187,8 +197,12 @@ static int phy_launch(orlg_phy_env *e, const OrlgPhyParams &p) {
     dim3 grid(nblocks), block(ORLG_WAVE * wpb);
     hipLaunchKernelGGL(k, grid, block, e->lds_block_bytes, e->stream, q);
     HIP_TRY(hipGetLastError());
-    snprintf(e->last_kernel, sizeof(e->last_kernel), "orlg_phy_kernel<%d,%s,%d> grid=%d block=%d lds=%zu", e->W,
-             df == 2 ? "true,true" : df == 1 ? "true,false" : df == 3 ? "false,true" : "false,false", pol, nblocks, ORLG_WAVE * wpb, e->lds_block_bytes);
+    if (e->cont)
+        snprintf(e->last_kernel, sizeof(e->last_kernel), "orlg_phy_kernel<%d,false,%s,%d,true> grid=%d block=%d lds=%zu", e->W,
+                 p.gn_on ? "true" : "false", pol, nblocks, ORLG_WAVE * wpb, e->lds_block_bytes);
+    else
+        snprintf(e->last_kernel, sizeof(e->last_kernel), "orlg_phy_kernel<%d,%s,%d> grid=%d block=%d lds=%zu", e->W,
+                 df == 2 ? "true,true" : df == 1 ? "true,false" : df == 3 ? "false,true" : "false,false", pol, nblocks, ORLG_WAVE * wpb, e->lds_block_bytes);
     return ORLG_OK;
 }
 
@@ -199,7 +213,7 @@ static int phy_extract(orlg_phy_env *e, int what, void *out, size_t bytes) {
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->staging), bytes));
         e->staging_bytes = bytes;
     }
-    hipLaunchKernelGGL(orlg_phy_extract_kernel, dim3(256), dim3(256), 0, e->stream, e->p, what, e->staging);
+    hipLaunchKernelGGL(orlg_phy_extract_kernel, dim3(256), dim3(256), 0, e->stream, e->p, what, e->staging, e->cont);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, e->staging, bytes, hipMemcpyDefault, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -218,6 +232,8 @@ int orlg_phy_destroy(orlg_phy_env *e) {
         if (e->io_buf[i]) (void)hipFree(e->io_buf[i]);
     if (e->d_act_path) (void)hipFree(e->d_act_path);
     if (e->d_act_ch) (void)hipFree(e->d_act_ch);
+    if (e->d_act_share) (void)hipFree(e->d_act_share);
+    if (e->f_buf) (void)hipFree(e->f_buf);
     orlg_err_word_destroy(&e->err);
     if (e->own_stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -233,7 +249,20 @@ int orlg_phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t ba
     if (N < 2 || N > 64) return fail(ORLG_ERR_INVALID, "num_nodes %d not in 2..64", N);
     if (E < 1 || E > 255) return fail(ORLG_ERR_INVALID, "num_links %d not in 1..255", E);
     if (C < 1 || C > 320) return fail(ORLG_ERR_INVALID, "num_channels %d not in 1..320", C);
-    if (NBR < 1 || NBR > 64) return fail(ORLG_ERR_INVALID, "num_bit_rates %d not in 1..64", NBR);
+    // bit_rate_cum == NULL: bit_rate_selection="continuous" (as orlg_create) -- bit_rates = lower .. higher, one apart
+    const bool cont = c->bit_rate_cum == nullptr;
+    if (cont) {
+        if (!c->bit_rates || NBR < 1) return fail(ORLG_ERR_INVALID, "continuous bit rates: null bit_rates or num_bit_rates %d < 1", NBR);
+        for (int b = 1; b < NBR; b++)
+            if (c->bit_rates[b] != c->bit_rates[0] + b) return fail(ORLG_ERR_INVALID, "continuous bit rates must be lower .. higher, one apart");
+        const int lo = c->bit_rates[0], hi = c->bit_rates[NBR - 1];
+        if (lo < 0) return fail(ORLG_ERR_INVALID, "continuous bit rates: lower bound %d < 0", lo);
+        // the largest request must fit ORLG_PHY_MAX_CH channels of modulation level 1 (100 Gb/s each)
+        if (hi > 100 * ORLG_PHY_MAX_CH) return fail(ORLG_ERR_INVALID, "continuous bit rates: higher bound %d needs more than %d channels", hi, ORLG_PHY_MAX_CH);
+        if (c->defrag_period > 0) return fail(ORLG_ERR_INVALID, "continuous bit rates with the periodic defragmentation are not supported");
+    } else if (NBR < 1 || NBR > 64) {
+        return fail(ORLG_ERR_INVALID, "num_bit_rates %d not in 1..64", NBR);
+    }
     if (K < 1 || K > ORLG_PHY_MAX_K) return fail(ORLG_ERR_INVALID, "k_paths %d not in 1..%d", K, ORLG_PHY_MAX_K);
     if (c->k_table < K) return fail(ORLG_ERR_INVALID, "QoT tables have %d k-path columns, topology has k=%d", c->k_table, K);
     if (t->num_paths < 1 || t->num_paths >= 65536) return fail(ORLG_ERR_INVALID, "num_paths out of range");
@@ -262,7 +291,8 @@ int orlg_phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t ba
     orlg_phy_env *e = new orlg_phy_env();
     memset(&e->p, 0, sizeof(e->p));
     e->W = W; e->device = device; e->own_stream = true; e->staging = nullptr; e->staging_bytes = 0;
-    e->d_act_path = nullptr; e->d_act_ch = nullptr; e->num_paths = t->num_paths;
+    e->d_act_path = nullptr; e->d_act_ch = nullptr; e->d_act_share = nullptr; e->cont_tag = nullptr;
+    e->f_buf = nullptr; e->f_cap = 0; e->cont = cont ? 1 : 0; e->num_paths = t->num_paths;
     e->err.host = nullptr; e->err.dev = nullptr; e->last_kernel[0] = 0;
     memset(e->resident_blocks, 0, sizeof(e->resident_blocks)); e->num_cu = 0; e->ticket_base = 0;
     for (int i = 0; i < ORLG_PHY_NUM_OUTS; i++) { e->io_buf[i] = nullptr; e->io_cap[i] = 0; }
@@ -315,6 +345,7 @@ int orlg_phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t ba
     p.l_nbi = off; off = up16(off + ORLG_PHY_NB * 2);
     p.l_scratch = off; off = up16(off + 256 + W * 64 * 8);
     p.l_wsc = off; off = up16(off + (int)sizeof(PhyWaveScalars));
+    p.br_lower = cont ? c->bit_rates[0] : 0;
     p.l_wave_bytes = off;
 
     int rc = ORLG_OK;
@@ -344,8 +375,10 @@ int orlg_phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t ba
             }
         }
         p.t_recs = put(recs.data(), recs.size() * sizeof(OrlgPathRec));
-        p.t_bitrates = put(c->bit_rates, (size_t)NBR * 4);
-        p.t_brcum = put(c->bit_rate_cum, (size_t)NBR * 8);
+        // (continuous: the kernel computes lower + r -- no bit-rate table, no cumulative weights in LDS)
+        const double no_cum = 0.0;
+        p.t_bitrates = put(c->bit_rates, (size_t)(cont ? 1 : NBR) * 4);
+        p.t_brcum = put(cont ? &no_cum : c->bit_rate_cum, (size_t)(cont ? 1 : NBR) * 8);
         p.t_srccum = put(c->src_cum, (size_t)N * 8);
         p.t_dstcum = put(c->dst_cum, (size_t)N * N * 8);
         p.t_pairrow = put(c->pair_table_row, (size_t)N * N * 4);
@@ -504,6 +537,16 @@ int orlg_phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t ba
     TRY(alloc(reinterpret_cast<void **>(&p.cs), (size_t)batch * N * N * K * p.cs_len * 4));
     TRY(alloc(reinterpret_cast<void **>(&p.cs_n), (size_t)batch * N * N * K));
     TRY(alloc(reinterpret_cast<void **>(&p.ticket), 16));
+    if (cont) {   // the float64 shares: parallel to the channel_state entries and to the service records
+        TRY(alloc(reinterpret_cast<void **>(&p.cs_f), (size_t)batch * N * N * K * p.cs_len * 2 * sizeof(double)));
+        TRY(alloc(reinterpret_cast<void **>(&p.svc_f), (size_t)batch * Q * ORLG_PHY_MAX_CH * sizeof(double)));
+        TRY(alloc(reinterpret_cast<void **>(&e->cont_tag), 16));
+        const uint64_t tag[2] = {ORLG_PHY_CONT_TAG0, ORLG_PHY_CONT_TAG1};
+        hipError_t er = hipMemset(p.cs_f, 0, (size_t)batch * N * N * K * p.cs_len * 2 * sizeof(double));
+        if (er == hipSuccess) er = hipMemset(p.svc_f, 0, (size_t)batch * Q * ORLG_PHY_MAX_CH * sizeof(double));
+        if (er == hipSuccess) er = hipMemcpy(e->cont_tag, tag, 16, hipMemcpyHostToDevice);
+        if (er != hipSuccess) { orlg_phy_destroy(e); return fail(ORLG_ERR_HIP, "continuous share arrays: %s", hipGetErrorString(er)); }
+    }
     {
         hipError_t er = hipMemset(p.ticket, 0, 16);
         if (er != hipSuccess) { orlg_phy_destroy(e); return fail(ORLG_ERR_HIP, "hipMemset: %s", hipGetErrorString(er)); }
@@ -642,16 +685,31 @@ int orlg_phy_reset(orlg_phy_env *e, int32_t only_episode_counters) {
     return phy_launch(e, p);
 }
 
-int orlg_phy_step(orlg_phy_env *e, int32_t policy, int32_t n_steps, const int32_t *act_path, const int16_t *act_channels,
-                  int32_t auto_reset, const orlg_phy_step_io *io) {
+int orlg_phy_step_ex(orlg_phy_env *e, int32_t policy, int32_t n_steps, const int32_t *act_path, const int16_t *act_channels,
+                     const double *act_share, int32_t auto_reset, const orlg_phy_step_io *io, double *channels_used_f64,
+                     double *channels_free_f64) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     if (n_steps < 1) return fail(ORLG_ERR_INVALID, "n_steps must be >= 1");
     if (policy < ORLG_PHY_POLICY_EXTERNAL || policy > ORLG_PHY_POLICY_FAFF_RSS) return fail(ORLG_ERR_INVALID, "unknown PhyRMSA policy %d", policy);
     if (policy == ORLG_PHY_POLICY_EXTERNAL && (!act_path || !act_channels || n_steps != 1))
         return fail(ORLG_ERR_INVALID, "external actions need path and channel arrays and n_steps == 1");
+    const bool cont = e->cont != 0;
+    if (cont && policy == ORLG_PHY_POLICY_EXTERNAL && !act_share)
+        return fail(ORLG_ERR_INVALID, "a continuous handle's external actions need their float64 shares (act_share, orlg_phy_step_ex)");
+    if (!cont && (act_share || channels_used_f64 || channels_free_f64))
+        return fail(ORLG_ERR_INVALID, "float64 shares belong to handles with continuous bit rates");
     HIP_TRY(hipSetDevice(e->device));
     OrlgPhyParams p = e->p;
     p.mode = ORLG_MODE_STEP; p.n_steps = n_steps; p.policy = policy; p.auto_reset = auto_reset;
+    if (cont && policy == ORLG_PHY_POLICY_EXTERNAL) {
+        if (orlg_is_device_ptr(act_share)) {
+            p.act_share = act_share;
+        } else {
+            if (!e->d_act_share) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_act_share), (size_t)p.B * ORLG_PHY_MAX_CH * 2 * 8));
+            HIP_TRY(hipMemcpyAsync(e->d_act_share, act_share, (size_t)p.B * ORLG_PHY_MAX_CH * 2 * 8, hipMemcpyDefault, e->stream));
+            p.act_share = e->d_act_share;
+        }
+    }
     if (policy == ORLG_PHY_POLICY_EXTERNAL) {
         if (orlg_is_device_ptr(act_path) && orlg_is_device_ptr(act_channels)) {
             p.act_path = act_path; p.act_channels = act_channels;
@@ -693,6 +751,20 @@ int orlg_phy_step(orlg_phy_env *e, int32_t policy, int32_t n_steps, const int32_
             staged[i] = true;
         }
     }
+    // the float64 shares (continuous handles): device pointers in place, host arrays through a launch-local buffer
+    // the float64 shares (continuous handles): the kernel writes (used, free) pairs, split into the two outputs afterwards
+    double *user_f[2] = {channels_used_f64, channels_free_f64};
+    if (cont) p.out_share = nullptr;
+    if (channels_used_f64 || channels_free_f64) {
+        const size_t fbytes = cnt * ORLG_PHY_MAX_CH * 2 * sizeof(double);
+        if (fbytes > e->f_cap) {
+            if (e->f_buf) HIP_TRY(hipFree(e->f_buf));
+            e->f_buf = nullptr; e->f_cap = 0;
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->f_buf), fbytes));
+            e->f_cap = fbytes;
+        }
+        p.out_share = e->f_buf;
+    }
     int rc = phy_launch(e, p);
     if (rc) return rc;
     bool any = false;
@@ -701,9 +773,21 @@ int orlg_phy_step(orlg_phy_env *e, int32_t policy, int32_t n_steps, const int32_
             HIP_TRY(hipMemcpyAsync(slots[i].user, e->io_buf[i], cnt * slots[i].elem, hipMemcpyDeviceToHost, e->stream));
             any = true;
         }
+    for (int i = 0; i < 2; i++)
+        if (user_f[i]) {   // (host or device destination)
+            HIP_TRY(hipMemcpy2DAsync(user_f[i], sizeof(double), e->f_buf + i, 2 * sizeof(double), sizeof(double),
+                                     cnt * ORLG_PHY_MAX_CH, hipMemcpyDefault, e->stream));
+            any = true;
+        }
     if (any) return phy_sync_check(e);
     return ORLG_OK;
 }
+
+int orlg_phy_step(orlg_phy_env *e, int32_t policy, int32_t n_steps, const int32_t *act_path, const int16_t *act_channels,
+                  int32_t auto_reset, const orlg_phy_step_io *io) {
+    return orlg_phy_step_ex(e, policy, n_steps, act_path, act_channels, nullptr, auto_reset, io, nullptr, nullptr);
+}
+int orlg_phy_continuous(orlg_phy_env *e) { return e ? e->cont : ORLG_ERR_INVALID; }
 
 int orlg_phy_synchronize(orlg_phy_env *e) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
@@ -757,7 +841,12 @@ static std::vector<StatePart> phy_state_parts(orlg_phy_env *e) {
     std::vector<StatePart> parts = {{p.occ, B * p.NW * 8}, {p.qtime, B * p.Q * 8}, {p.qrec, B * p.Q * sizeof(OrlgPhySvc)}, {p.mt, B * ORLG_MT_N * 4},
             {p.scal, B * sizeof(OrlgPhyScalars)}, {p.cs, B * lists * p.cs_len * 4}, {p.cs_n, B * lists},
             {p.ring_iat, B * ORLG_RING * 8}, {p.ring_ht, B * ORLG_RING * 8}, {p.ring_req, B * ORLG_RING * 4}};
-    if (p.qsum) { parts.push_back({p.qsum, B * p.Q * sizeof(uint64_t)}); parts.push_back({p.qseq, B * p.Q * sizeof(uint32_t)}); }
+    if (p.defrag_period > 0) { parts.push_back({p.qsum, B * p.Q * sizeof(uint64_t)}); parts.push_back({p.qseq, B * p.Q * sizeof(uint32_t)}); }
+    if (e->cont) {   // (a discrete state stays as it was; the tag comes last)
+        parts.push_back({p.cs_f, B * lists * p.cs_len * 2 * sizeof(double)});
+        parts.push_back({p.svc_f, B * p.Q * ORLG_PHY_MAX_CH * sizeof(double)});
+        parts.push_back({e->cont_tag, 16});
+    }
     return parts;
 }
 int64_t orlg_phy_state_size(orlg_phy_env *e) {
@@ -780,7 +869,40 @@ int orlg_phy_load_state(orlg_phy_env *e, const void *buffer) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     return ORLG_OK;
 }
+int orlg_phy_load_state_checked(orlg_phy_env *e, const void *buffer, int64_t bytes) {
+    if (!e || !buffer) return fail(ORLG_ERR_INVALID, "null argument");
+    const int64_t n = orlg_phy_state_size(e);
+    if (bytes != n) return fail(ORLG_ERR_INVALID, "snapshot of %lld bytes, this handle's state has %lld", (long long)bytes, (long long)n);
+    uint64_t tail[2] = {0ull, 0ull};
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpy(tail, static_cast<const unsigned char *>(buffer) + (n - 16), 16, hipMemcpyDefault));
+    const bool tagged = tail[0] == ORLG_PHY_CONT_TAG0 && tail[1] == ORLG_PHY_CONT_TAG1;
+    if (tagged != (e->cont != 0))
+        return fail(ORLG_ERR_INVALID, "snapshot saved by a handle with %s bit rates", tagged ? "continuous" : "discrete");
+    return orlg_phy_load_state(e, buffer);
+}
 int orlg_phy_channel_state_capacity(orlg_phy_env *e) { return e ? e->p.cs_len : ORLG_ERR_INVALID; }
+int orlg_phy_get_channel_state_f64(orlg_phy_env *e, int32_t env_index, double *entries, uint8_t *lengths) {
+    if (!e || !entries || !lengths) return fail(ORLG_ERR_INVALID, "null argument");
+    if (env_index < 0 || env_index >= e->p.B) return fail(ORLG_ERR_INVALID, "env_index %d out of range", env_index);
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t lists = (size_t)e->p.N * e->p.N * e->p.K, n = lists * e->p.cs_len;
+    std::vector<uint32_t> packed(n);
+    const bool cont = e->cont != 0;
+    std::vector<double> shares(cont ? 2 * n : 0);
+    HIP_TRY(hipMemcpyAsync(packed.data(), e->p.cs + (size_t)env_index * n, n * 4, hipMemcpyDefault, e->stream));
+    if (cont) HIP_TRY(hipMemcpyAsync(shares.data(), e->p.cs_f + (size_t)env_index * n * 2, n * 16, hipMemcpyDefault, e->stream));
+    HIP_TRY(hipMemcpyAsync(lengths, e->p.cs_n + (size_t)env_index * lists, lists, hipMemcpyDefault, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t x = packed[i];
+        entries[4 * i] = (double)(x & 0x1ffu);
+        entries[4 * i + 1] = cont ? shares[2 * i] : (double)((x >> 9) & 0x1fu);
+        entries[4 * i + 2] = cont ? shares[2 * i + 1] : (double)((x >> 14) & 0x1fu);
+        entries[4 * i + 3] = (double)((x >> 19) & 0x1fu);
+    }
+    return e->p.cs_len;
+}
 int orlg_phy_get_channel_state(orlg_phy_env *e, int32_t env_index, uint32_t *entries, uint8_t *lengths) {
     if (!e || !entries || !lengths) return fail(ORLG_ERR_INVALID, "null argument");
     if (env_index < 0 || env_index >= e->p.B) return fail(ORLG_ERR_INVALID, "env_index %d out of range", env_index);

@@ -89,19 +89,35 @@ struct OrlgPhyParams {
     OrlgPhyScalars *scal;   // [B]
     uint32_t *cs;           // [B][N*N*K][cs_len] channel_state lists (virtual layer), list order = array order
     uint8_t *cs_n;          // [B][N*N*K] list lengths
-    OrlgPhyCand *cand;      // [B][cand_cap] defragmentation work list (only with defrag_period > 0)
+    // bit_rate_selection="continuous" (the CONT instantiations) shares the fields of the periodic defragmentation, which such a
+    // handle does not have (refused at create time): the discrete kernels' arguments keep their layout, and so their code.
+    // The bit rate is br_lower + r (r: the ring entry's draw); channel shares are float64 (phy_rmsa_env.py:1305-1308, 1666-1670,
+    // 823-838) in arrays parallel to the packed channel_state entries and service records
+    union {
+        OrlgPhyCand *cand;      // [B][cand_cap] defragmentation work list (only with defrag_period > 0)
+        double *out_share;      // CONT: per-step output [n_steps][B][ORLG_PHY_MAX_CH][2] the chosen channels' (used, free), or nullptr
+    };
     // side arrays of the service records for the periodic defragmentation (only with defrag_period > 0, kept by the DF
     // instantiations at every site that writes a record): its scans walk 8 + 4 bytes per running service instead of 48
-    uint64_t *qsum;         // [B][Q] svc_summary: gid | flags << 14 | nch << 16 | ch[0] << 20 | ch[1] << 35 (15-bit channel entries)
-    uint32_t *qseq;         // [B][Q] the record's seq (list order of topology.graph["running_services"])
-    const uint64_t *lvl_mask;   // [num_rows*K][32][W] channels of one modulation level on (table row, k-path), as bit masks
+    union {
+        uint64_t *qsum;     // [B][Q] svc_summary: gid | flags << 14 | nch << 16 | ch[0] << 20 | ch[1] << 35 (15-bit channel entries)
+        double *cs_f;       // CONT: [B][N*N*K][cs_len][2] (used, free) of every channel_state entry, parallel to cs
+    };
+    union {
+        uint32_t *qseq;     // [B][Q] the record's seq (list order of topology.graph["running_services"])
+        double *svc_f;      // CONT: [B][Q][ORLG_PHY_MAX_CH] service.channels[i][1] (used), parallel to qrec
+    };
+    union {
+        const uint64_t *lvl_mask;   // [num_rows*K][32][W] channels of one modulation level on (table row, k-path), as bit masks
+        const double *act_share;    // CONT, external actions: [B][ORLG_PHY_MAX_CH][2] (used, free) of every chosen channel
+    };
     uint32_t *ticket;       // work queue counter; environment = ticket - ticket_base
     uint32_t ticket_base, ticket_stride;
     // shared tables
     const unsigned char *tables;   // blob staged into LDS
     int32_t tab_bytes, t_pair, t_recs, t_bitrates, t_brcum, t_srccum, t_dstcum, t_pairrow, t_adjoff, t_adj, t_sqrt,
         t_plen, t_pathpair, t_masks;
-    int32_t use_masks, pad_masks;   // E <= 32: link sets as 32-bit masks (OrlgPathMasks) instead of the adjacency CSR
+    int32_t use_masks, br_lower;    // E <= 32: link sets as 32-bit masks (OrlgPathMasks) instead of the adjacency CSR; CONT: lower bound
     // cut metric through per-node free degrees (orlg_phy_config::path_node_weights), networks of at most 16 nodes of at most
     // 15 links each: D[channel] = 16 nibbles (nibble v = links at node v that are free on the channel) in the wave's LDS next
     // to the occupancy (l_nv), rebuilt from the occupancy at the start of every launch that evaluates the cut metric
@@ -627,6 +643,35 @@ DEV bool cs_append(CsList &l, uint32_t v, int lane) {  // list.append
     if (lane == l.n) l.e = v;
     l.n += 1;
     return true;
+}
+// continuous bit rates: the float64 (used, free) of a list's entries, lane i = entry i next to CsList::e (whose used / free
+// fields stay 0: channel, capacity and the valid bit are all the packed word keeps).  Every csf_* call comes before the
+// cs_* call it pairs with (they take the list length as it was).
+struct CsShares { double u, f; };
+DEV CsShares csf_load(const double *csf, int key, int lane, int n, int cs_len) {
+    CsShares s;
+    s.u = 0.0; s.f = 0.0;
+    if (lane < n) {
+        const double *q = csf + ((size_t)key * cs_len + lane) * 2;
+        s.u = q[0]; s.f = q[1];
+    }
+    return s;
+}
+DEV void csf_store(double *csf, int key, const CsShares &s, int n, int cs_len, int lane) {
+    if (lane < n) {
+        double *q = csf + ((size_t)key * cs_len + lane) * 2;
+        q[0] = s.u; q[1] = s.f;
+    }
+}
+DEV void csf_remove(CsShares &s, int q, int n, int lane) {
+    const double nu = __shfl_down(s.u, 1), nf = __shfl_down(s.f, 1);
+    if (lane >= q) {
+        s.u = lane + 1 < n ? nu : 0.0;
+        s.f = lane + 1 < n ? nf : 0.0;
+    }
+}
+DEV void csf_append(CsShares &s, double u, double f, int n, int cap, int lane) {
+    if (n < cap && lane == n) { s.u = u; s.f = f; }
 }
 
 
@@ -1762,7 +1807,9 @@ DEV void nb_first_due(const NearBuffer &nb, double time, int lane, int &victim, 
 // policy turns the per-policy choices inside the channel loops (level as a sort key or not, which metric, first row or best
 // row) into straight-line code: a wave of this kernel is bound by its own instruction latency, and every wave-uniform branch
 // inside an unrolled word loop is a fetch bubble paid W times per candidate path.
-template <int W, bool DF, bool GN, int POL>
+// CONT: bit_rate_selection="continuous" -- arrivals from refill_requests_cont_t, the virtual layer's shares in float64
+// (OrlgPhyParams::cs_f / svc_f) in the reference's order of operations; no defragmentation (refused at create time).
+template <int W, bool DF, bool GN, int POL, bool CONT = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_phy_kernel(const OrlgPhyParams p) {
     // the policy sorts channels by the RSS metric (floating point) instead of an integer key
     constexpr bool RSSP = POL == ORLG_PHY_POLICY_BMFA_RSS_METRIC || POL == ORLG_PHY_POLICY_FAFF_RSS;
@@ -1827,6 +1874,9 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
     uint32_t *gcs = p.cs + (size_t)env * N * N * K * p.cs_len;
     uint8_t *gcs_n = p.cs_n + (size_t)env * N * N * K;
     u64 *gnv = p.use_nv ? reinterpret_cast<u64 *>(wb + p.l_nv) : nullptr;   // node-degree vectors of the cut metric
+    static_assert(!(CONT && DF), "continuous bit rates without the periodic defragmentation");
+    double *gcsf = CONT ? p.cs_f + (size_t)env * N * N * K * p.cs_len * 2 : nullptr;   // (used, free) of the channel_state entries
+    double *gsvf = CONT ? p.svc_f + (size_t)env * Q * ORLG_PHY_MAX_CH : nullptr;      // service.channels[i][1] of the records
 
     SEC(1);  // state load
     // ------------------------------------------------------------------ HBM -> LDS
@@ -1930,9 +1980,12 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
             }
             const int base = tb.pair_base[req_src * N + req_dst];
             const int row = tb.pair_row[req_src * N + req_dst];
-            const int demand = tb.bit_rates[req_br];
+            const int demand = CONT ? p.br_lower + req_br : tb.bit_rates[req_br];
             constexpr int policy = POL;
             int a_path = -2, nsel = 0;
+            // continuous: the selection's float64 (used, free) shares, lane i = selected channel i (in registers: a per-wave LDS
+            // array would cost the node-degree vectors their room on chip)
+            double sh_u = 0.0, sh_f = 0.0;
             // requested now, used after the virtual-layer check as well: the modulation levels of the lane's channels on the K
             // candidate paths (one or two words per channel) and the paths' node records (lane 2 i, 2 i + 1: path i)
             uint32_t lvk[W];   // (a fifth path's levels are read where they are needed: K = 5 pays a wait, K <= 4 no registers)
@@ -1959,6 +2012,10 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                     const int c = raw & 0x1ff, u = (raw >> 9) & 0x1f;
                     int cap = (idp >= 0 && idp < K && c < C) ? (int)p.mod_t[(size_t)(row * K + idp) * p.cpad + c] : 0;
                     sel_ch[lane] = c; sel_cap[lane] = cap; sel_used[lane] = u ? u : cap;
+                    if constexpr (CONT) {   // the tuple's (used, free) in float64 (act_share)
+                        const double *as = kp->act_share + ((size_t)env * ORLG_PHY_MAX_CH + lane) * 2;
+                        sh_u = as[0]; sh_f = as[1];
+                    }
                 }
                 wave_sync();
             } else {
@@ -1968,7 +2025,34 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                 const bool with_metric = bmfa || faff;
                 const bool groom = bmfa ? (p.grooming != 0) : true;
                 bool served = false;
-                if (groom) {
+                if (CONT && groom) {
+                    // use_existing_channels (:1650-1673) on float64 shares: sum() is a sequential sum in list order from 0, the
+                    // running unassigned_bitrate is a float once a share is taken off (it is not reset between k-paths)
+                    double unassigned = (double)demand;
+                    for (int idp = 0; idp < K && !served; ++idp) {
+                        const int key = (req_src * N + req_dst) * K + idp;
+                        const CsList l = cs_load(gcs, gcs_n, key, lane, p.cs_len);
+                        const CsShares s = csf_load(gcsf, key, lane, l.n, p.cs_len);
+                        double sum = 0.0;
+                        for (int i = 0; i < l.n; ++i) sum += readlane_d(s.f, i);
+                        if (sum >= unassigned / 100.0) {
+                            for (int i = 0; i < l.n && nsel < ORLG_PHY_MAX_CH; ++i) {
+                                const double f = readlane_d(s.f, i);
+                                if (f > 0.0) {
+                                    const uint32_t en = cs_get(l, i);
+                                    unassigned -= f * 100.0;
+                                    const bool last = unassigned <= 0.0;
+                                    const double take = last ? f + unassigned / 100.0 : f, rest = last ? unassigned / -100.0 : 0.0;
+                                    if (lane == 0) { sel_ch[nsel] = cs_ch(en); sel_cap[nsel] = cs_cap(en); sel_used[nsel] = 0; }
+                                    if (lane == nsel) { sh_u = take; sh_f = rest; }
+                                    nsel += 1;
+                                    if (last) { a_path = idp + 20; served = true; break; }
+                                }
+                            }
+                        }
+                    }
+                    if (!served) nsel = 0;
+                } else if (groom) {
                     // use_existing_channels (:1650-1673): residual capacity on channels this (src, dst, k-path) already lights
                     int unassigned = demand;
                     for (int idp = 0; idp < K && !served; ++idp) {
@@ -2062,6 +2146,10 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                                 unassigned -= level * 100;
                                 const int used = unassigned <= 0 ? level + unassigned / 100 : level;
                                 if (lane == 0) { sel_ch[nsel] = c0; sel_cap[nsel] = level; sel_used[nsel] = used; }
+                                if (CONT && lane == nsel) {   // (channel, level + unassigned / 100, unassigned / -100, level): :1305-1308
+                                    sh_u = unassigned <= 0 ? (double)level + (double)unassigned / 100.0 : (double)level;
+                                    sh_f = unassigned <= 0 ? (double)unassigned / -100.0 : 0.0;
+                                }
                                 nsel += 1;
                                 if (unassigned <= 0) { covered = true; break; }
                                 h = phy_keys_best<W>(key);
@@ -2140,6 +2228,10 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                                 unassigned -= level * 100;
                                 const int used = unassigned <= 0 ? level + unassigned / 100 : level;
                                 if (lane == 0) { sel_ch[nsel] = c0; sel_cap[nsel] = level; sel_used[nsel] = used; }
+                                if (CONT && lane == nsel) {   // (channel, level + unassigned / 100, unassigned / -100, level): :1305-1308
+                                    sh_u = unassigned <= 0 ? (double)level + (double)unassigned / 100.0 : (double)level;
+                                    sh_f = unassigned <= 0 ? (double)unassigned / -100.0 : 0.0;
+                                }
                                 nsel += 1;
                                 if (unassigned <= 0) { covered = true; break; }
                             }
@@ -2163,23 +2255,41 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                 const int key = (req_src * N + req_dst) * K + idp;
                 CsList l = cs_load(gcs, gcs_n, key, lane, p.cs_len);
                 bool ok = true;
+                CsShares s{0.0, 0.0};
+                if constexpr (CONT) s = csf_load(gcsf, key, lane, l.n, p.cs_len);
                 for (int ci = 0; ci < nsel && ok; ++ci) {
                     const int q = cs_find(l, sel_ch[ci], lane);
                     if (q < 0) { ok = false; break; }
                     const uint32_t en = cs_get(l, q);
+                    if constexpr (CONT) {   // (t[0], t[1] + channel[1], t[2] - channel[1], t[3]) when t[2] >= channel[1] (:640-644)
+                        const double eu = readlane_d(s.u, q), ef = readlane_d(s.f, q), take = readlane_d(sh_u, ci);
+                        if (!(ef >= take)) { ok = false; break; }
+                        csf_remove(s, q, l.n, lane);
+                        cs_remove(l, q, lane);
+                        csf_append(s, eu + take, ef - take, l.n, l.cap, lane);
+                        cs_append(l, cs_pack(cs_ch(en), 0, 0, cs_cap(en)), lane);
+                        continue;
+                    }
                     const int take = sel_used[ci];
                     if (cs_free(en) < take) { ok = false; break; }  // the reference raises here
                     cs_remove(l, q, lane);
                     cs_append(l, cs_pack(cs_ch(en), cs_used(en) + take, cs_free(en) - take, cs_cap(en)), lane);
                 }
                 if (ok) {
+                    if constexpr (CONT) csf_store(gcsf, key, s, l.n, p.cs_len, lane);
                     cs_store(gcs, gcs_n, key, l, lane);
                     if (lane == 0) { ws->c[1] += 1; ws->c[3] += 1; ws->c[5] += demand; ws->c[7] += demand; }
                     accepted = true;
                     if (n_running < Q) {
                         if (lane == 0) gq[n_running] = ws->req_arrival + ws->req_holding;
                         {
-                            const uint32_t hw_v = lane < nsel ? (uint32_t)(sel_ch[lane] | (sel_used[lane] << 9) | (1 << 14)) : 0xffffu;
+                            uint32_t hw_v = lane < nsel ? (uint32_t)(sel_ch[lane] | (sel_used[lane] << 9) | (1 << 14)) : 0xffffu;
+                            if constexpr (CONT) {   // the share in svc_f; partial = channel[1] != channel[3] (_release_path :784)
+                                if (lane < nsel) {
+                                    hw_v = (uint32_t)(sel_ch[lane] | ((sh_u != (double)sel_cap[lane] ? 1 : 0) << 14));
+                                    gsvf[(size_t)n_running * ORLG_PHY_MAX_CH + lane] = sh_u;
+                                }
+                            }
                             rec_store(grec + n_running, &ws->req_arrival, (uint32_t)next_seq, gid, nsel, 1 | (dirbit ? 2 : 0), hw_v, lane);
                             if (DF && gsum) svc_side_store(gsum, gseq, n_running, gid, 1 | (dirbit ? 2 : 0), nsel, hw_v, (uint32_t)next_seq, lane);
                         }
@@ -2214,10 +2324,14 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                 const bool ch_ok = lane < nsel && my_ch >= 0 && my_ch < C;
                 const double my_gsnr = ch_ok ? p.gsnr_t[(size_t)(row * K + a_path) * p.cpad + my_ch] : 0.0;
                 const int my_used = lane < nsel ? sel_used[lane] : 0, my_cap = lane < nsel ? sel_cap[lane] : 0;
-                const bool any_partial_p = ballot(lane < nsel && my_used != my_cap) != 0ull;
+                // continuous: a channel joins channel_state when its free share is not 0 (channel[2] != 0, :600)
+                const double my_uf = CONT && lane < nsel ? sh_u : 0.0, my_ff = CONT && lane < nsel ? sh_f : 0.0;
+                const bool any_partial_p = ballot(lane < nsel && (CONT ? my_ff != 0.0 : my_used != my_cap)) != 0ull;
                 CsList csl;
                 csl.e = 0u; csl.n = 0; csl.cap = p.cs_len;
                 if (any_partial_p) csl = cs_load(gcs, gcs_n, cs_key_p, lane, p.cs_len);
+                CsShares csfl{0.0, 0.0};
+                if (CONT && any_partial_p) csfl = csf_load(gcsf, cs_key_p, lane, csl.n, p.cs_len);
                 // is_path_free_on_channels (:1019-1027): lanes = (channel, hop) pairs
                 // (the heuristics pick among the channels that are free on the path right now: only external actions need the look)
                 bool pass = true;
@@ -2296,10 +2410,19 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                         bool overflow = false;
                         for (int ci = 0; ci < nsel; ++ci) {
                             const int cap = sel_cap[ci], used = sel_used[ci];
+                            if constexpr (CONT) {
+                                const double ff = readlane_d(my_ff, ci);
+                                if (ff != 0.0) {
+                                    csf_append(csfl, readlane_d(my_uf, ci), ff, csl.n, csl.cap, lane);
+                                    if (!cs_append(csl, cs_pack(sel_ch[ci], 0, 0, cap), lane)) overflow = true;
+                                }
+                                continue;
+                            }
                             if (used != cap) {
                                 if (!cs_append(csl, cs_pack(sel_ch[ci], used, cap - used, cap), lane)) overflow = true;
                             }
                         }
+                        if constexpr (CONT) csf_store(gcsf, cs_key_p, csfl, csl.n, p.cs_len, lane);
                         cs_store(gcs, gcs_n, cs_key_p, csl, lane);
                         if (overflow && lane == 0) ws->q_overflow |= 4;
                     }
@@ -2308,7 +2431,13 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                     if (n_running < Q) {
                         if (lane == 0) gq[n_running] = ws->req_arrival + ws->req_holding;
                         {
-                            const uint32_t hw_p = lane < nsel ? (uint32_t)(my_ch | (my_used << 9) | ((my_used != my_cap ? 1 : 0) << 14)) : 0xffffu;
+                            uint32_t hw_p = lane < nsel ? (uint32_t)(my_ch | (my_used << 9) | ((my_used != my_cap ? 1 : 0) << 14)) : 0xffffu;
+                            if constexpr (CONT) {
+                                if (lane < nsel) {
+                                    hw_p = (uint32_t)(my_ch | ((my_uf != (double)my_cap ? 1 : 0) << 14));
+                                    gsvf[(size_t)n_running * ORLG_PHY_MAX_CH + lane] = my_uf;
+                                }
+                            }
                             rec_store(grec + n_running, &ws->req_arrival, (uint32_t)next_seq, gid, nsel, dirbit ? 2 : 0, hw_p, lane);
                             if (DF && gsum) svc_side_store(gsum, gseq, n_running, gid, dirbit ? 2 : 0, nsel, hw_p, (uint32_t)next_seq, lane);
                         }
@@ -2369,7 +2498,8 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                 }
                 if (om & (1 << ORLG_PHY_OUT_CH_USED)) {
                     auto oc = ORLG_GPTR(int16_t, tb.outs[ORLG_PHY_OUT_CH_USED]) + o * ORLG_PHY_MAX_CH;
-                    if (lane < ORLG_PHY_MAX_CH) oc[lane] = lane < nsel ? (int16_t)sel_used[lane] : (int16_t)0;
+                    // (continuous: the shares are not whole units -- 0 here, the float64 output carries them)
+                    if (lane < ORLG_PHY_MAX_CH) oc[lane] = lane < nsel && !CONT ? (int16_t)sel_used[lane] : (int16_t)0;
                 }
                 if (lane == 0) {
                     if (om & (1 << ORLG_PHY_OUT_PATH)) ORLG_GPTR(int32_t, tb.outs[ORLG_PHY_OUT_PATH])[o] = a_path;
@@ -2394,12 +2524,19 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                     wave_sync();
                 }
             }
+            if constexpr (CONT) {   // the chosen channels' float64 (used, free): selected_channels[i][1], [i][2]
+                if (p.out_share && lane < ORLG_PHY_MAX_CH) {
+                    double *os = p.out_share + (((size_t)t * p.B + env) * ORLG_PHY_MAX_CH + lane) * 2;
+                    os[0] = lane < nsel ? sh_u : 0.0;
+                    os[1] = lane < nsel ? sh_f : 0.0;
+                }
+            }
             new_service = 0;
         } else if (p.mode == ORLG_MODE_EPISODE_RESET) {
             // reset(only_episode_counters=True) (phy_rmsa_env.py:426-472)
             eproc = new_service ? 1 : 0;
             if (lane == 0) {
-                ws->c[2] = new_service ? 1 : 0; ws->c[3] = 0; ws->c[6] = new_service ? tb.bit_rates[req_br] : 0; ws->c[7] = 0;
+                ws->c[2] = new_service ? 1 : 0; ws->c[3] = 0; ws->c[6] = new_service ? (CONT ? p.br_lower + req_br : tb.bit_rates[req_br]) : 0; ws->c[7] = 0;
                 ws->total_path_length = 0.0; ws->total_gsnr = 0.0; ws->total_path_index = 0; ws->total_mod = 0;
                 ws->channels_accepted = 0; ws->physical_accepted = 0;
                 ws->counted_moves = 0; ws->counted_moves_groom = 0; ws->counted_defrag_cycles = 0;
@@ -2430,7 +2567,11 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                 if (lane < 156 - 128) l_mt[lane + 128] = m2;
                 wave_sync();
                 int idx_s = mt_idx;
-                const int got = refill_requests(mt_lds, kq->ring_iat + (size_t)env * ORLG_RING, kq->ring_ht + (size_t)env * ORLG_RING,
+                const int got = CONT   // rng.randint(lower, higher) (phy_rmsa_env.py:127-129): the ring entry holds r, the rate is lower + r
+                    ? refill_requests_cont_t<false>(mt_lds, kq->ring_iat + (size_t)env * ORLG_RING, kq->ring_ht + (size_t)env * ORLG_RING,
+                                                    kq->ring_req + (size_t)env * ORLG_RING, tb.src_cum, tb.dst_cum, &idx_s, N, NBR,
+                                                    p.arrival_lambda, p.holding_lambda)
+                    : refill_requests(mt_lds, kq->ring_iat + (size_t)env * ORLG_RING, kq->ring_ht + (size_t)env * ORLG_RING,
                                                 kq->ring_req + (size_t)env * ORLG_RING, tb.src_cum, tb.dst_cum, tb.br_cum, &idx_s, N, NBR,
                                                 p.arrival_lambda, p.holding_lambda, env);
                 m0 = l_mt[lane]; m1 = l_mt[lane + 64];
@@ -2464,7 +2605,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
             new_service = 1;
             eproc += 1;
             if (lane == 0) {
-                const int br_val = tb.bit_rates[bri];
+                const int br_val = CONT ? p.br_lower + bri : tb.bit_rates[bri];
                 ws->c[0] += 1; ws->c[2] += 1; ws->c[4] += br_val; ws->c[6] += br_val;
                 ws->req_arrival = at; ws->req_holding = ht;
             }
@@ -2527,10 +2668,17 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                 }
                 uint32_t cvl = 0u;
                 if (gnv && lane < 4) cvl = reinterpret_cast<const uint32_t *>(p.nvrec + 2 * sv_gid)[lane];
+                double mine_f = 0.0, last_f = 0.0;   // continuous: the victim's shares (lane i: channel i), the last record's
+                if constexpr (CONT) {
+                    if (lane < sv_nch) mine_f = gsvf[(size_t)victim * ORLG_PHY_MAX_CH + lane];
+                    if (move_last && lane < ORLG_PHY_MAX_CH) last_f = gsvf[(size_t)(n_running - 1) * ORLG_PHY_MAX_CH + lane];
+                }
                 CsList l;
                 l.e = 0u; l.n = 0; l.cap = p.cs_len;
+                CsShares s{0.0, 0.0};
                 if (any_partial) {
                     l = cs_load(gcs, gcs_n, key, lane, p.cs_len);
+                    if constexpr (CONT) s = csf_load(gcsf, key, lane, l.n, p.cs_len);
                     for (int ci = 0; ci < sv_nch; ++ci) {
                         const int raw = __builtin_amdgcn_readlane(raw_l, ci);
                         if (!(raw & (1 << 14))) continue;
@@ -2538,6 +2686,20 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                         const int q = cs_find(l, ch, lane);
                         if (q < 0) continue;  // cannot happen for states produced by this kernel
                         const uint32_t en = cs_get(l, q);
+                        if constexpr (CONT) {   // result[1] == channel[1]: dark; else (r0, r1 - c1, r2 + c1, r3) appended (:823-838)
+                            const double eu = readlane_d(s.u, q), ef = readlane_d(s.f, q), mf = readlane_d(mine_f, ci);
+                            csf_remove(s, q, l.n, lane);
+                            cs_remove(l, q, lane);
+                            if (eu == mf) {
+#pragma unroll
+                                for (int w = 0; w < W; ++w)
+                                    if ((ch >> 6) == w) freemask[w] |= 1ull << (ch & 63);
+                            } else {
+                                csf_append(s, eu - mf, ef + mf, l.n, l.cap, lane);
+                                cs_append(l, cs_pack(ch, 0, 0, cs_cap(en)), lane);
+                            }
+                            continue;
+                        }
                         cs_remove(l, q, lane);
                         if (cs_used(en) == mine) {  // last user of the channel: it goes dark
 #pragma unroll
@@ -2573,10 +2735,12 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                         if (freemask[w] != 0ull && ((freemask[w] >> lane) & 1ull)) nv_update(gnv, cv_rel, 64 * w + lane, true);
                 }
                 // the stores: the rewritten channel_state list ...
+                if (CONT && any_partial) csf_store(gcsf, key, s, l.n, p.cs_len, lane);
                 if (any_partial) cs_store(gcs, gcs_n, key, l, lane);
                 // ... and the swap-remove: the last live entry takes the victim's place (its near-buffer entry follows it) ...
                 n_running -= 1;
                 if (move_last) {
+                    if (CONT && lane < ORLG_PHY_MAX_CH) gsvf[(size_t)victim * ORLG_PHY_MAX_CH + lane] = last_f;
                     if (lane < 12) reinterpret_cast<uint32_t *>(grec + victim)[lane] = lastv;
                     else if (lane < 14) reinterpret_cast<uint32_t *>(gq + victim)[lane - 12] = lastv;
                     else if (DF && gsum && lane < 16) reinterpret_cast<uint32_t *>(gsum + victim)[lane - 14] = lastv;
@@ -2629,7 +2793,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                 eproc = 1;
                 if (lane == 0) {
                     ws->episodes_done += 1;
-                    ws->c[2] = 1; ws->c[3] = 0; ws->c[6] = tb.bit_rates[req_br]; ws->c[7] = 0;
+                    ws->c[2] = 1; ws->c[3] = 0; ws->c[6] = CONT ? p.br_lower + req_br : tb.bit_rates[req_br]; ws->c[7] = 0;
                     ws->total_path_length = 0.0; ws->total_gsnr = 0.0; ws->total_path_index = 0; ws->total_mod = 0;
                     ws->channels_accepted = 0; ws->physical_accepted = 0;
                     ws->counted_moves = 0; ws->counted_moves_groom = 0; ws->counted_defrag_cycles = 0;

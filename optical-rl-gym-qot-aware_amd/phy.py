@@ -37,6 +37,40 @@ def _pairs_from_connections_detail(cd):
     return np.ascontiguousarray(cd[:, :2], dtype=np.int32)
 
 
+# the last 16 bytes of a continuous handle's saved state (orlg_phy_api.hip, ORLG_PHY_CONT_TAG0 / 1)
+_CONT_STATE_TAG = np.array([0x796870206772726F, 0x34366620746E6F63], "<u8").view(np.uint8)
+
+
+def _integral_bound(name, v):
+    """rng.randint(lower, higher) takes integral values only (Python 3.10 accepts integral floats such as the reference's
+    defaults 25.0 / 100.0)."""
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be an integral number, got {v!r}") from None
+    if not np.isfinite(f) or f != int(f):
+        raise ValueError(f"{name} must be an integral number, got {v!r}")
+    return int(f)
+
+
+def continuous_bit_rate_bounds(bit_rate_selection, bit_rate_lower_bound, bit_rate_higher_bound, defrag_period):
+    """The checks of ``phy_rmsa_env.py:79-86`` on the bit-rate kwargs, without a device: None for ``"discrete"``, else the
+    integral (lower, higher) of ``rng.randint``."""
+    if bit_rate_selection not in ("discrete", "continuous"):
+        raise ValueError(f"bit_rate_selection must be 'discrete' or 'continuous', got {bit_rate_selection!r}")
+    if bit_rate_selection == "discrete":
+        return None
+    lo = _integral_bound("bit_rate_lower_bound", bit_rate_lower_bound)
+    hi = _integral_bound("bit_rate_higher_bound", bit_rate_higher_bound)
+    if lo < 0 or hi < lo:
+        raise ValueError(f"continuous bit rates need 0 <= bit_rate_lower_bound <= bit_rate_higher_bound, got {lo}..{hi}")
+    if hi > 100 * _lib.PHY_MAX_CHANNELS:
+        raise ValueError(f"bit_rate_higher_bound {hi} needs more than {_lib.PHY_MAX_CHANNELS} channels of 100 Gb/s")
+    if defrag_period:
+        raise ValueError("the periodic defragmentation (defrag_period) is not supported with continuous bit rates")
+    return lo, hi
+
+
 def encode_channels(selected_channels, out_row):
     """The reference's ``selected_channels`` tuples ``(channel, used, free, capacity, virtual)`` (``phy_rmsa_env.py:
     1364-1366``) -> one ``act_channels`` row: channel | used << 9 (``used`` in 100 Gb/s units; bare ints = whole channel)."""
@@ -49,6 +83,14 @@ def encode_channels(selected_channels, out_row):
     return out_row
 
 
+def encode_shares(selected_channels, out_row):
+    """Continuous bit rates: the tuples' float64 (used, free) fields -> one ``act_share`` row [14, 2] (0 padded)."""
+    out_row[:] = 0.0
+    for q, c in enumerate(selected_channels):
+        out_row[q, 0], out_row[q, 1] = float(c[1]), float(c[2])
+    return out_row
+
+
 class BatchedPhyRMSAEnv:
     def __init__(self, topology, batch_size: int, *, modulation_level, connections_detail, gsnr,
                  episode_length: int = 1000, load: float = 10, mean_service_holding_time: float = 10800.0,
@@ -58,9 +100,19 @@ class BatchedPhyRMSAEnv:
                  number_spectrum_channels_s_band: int = 108, l_band: bool = True, s_band: bool = True,
                  defrag_period=None, number_moves=None, metric: str = "cut", grooming: bool = False,
                  queue_capacity: int = 0, channel_state_capacity: int = 0, defrag_capacity: int = 0, device: int = 0,
-                 gn_gate=None, **_ignored):
+                 gn_gate=None, bit_rate_selection: str = "discrete", bit_rate_lower_bound=25.0,
+                 bit_rate_higher_bound=100.0, **_ignored):
         if defrag_period and number_moves is None:
             raise ValueError("defrag_period needs number_moves (the reference compares against it, phy_rmsa_env.py:358)")
+        # bit_rate_selection="continuous" (phy_rmsa_env.py:79-86, 114-134): rng.randint(lower, higher) per request, checked
+        # before the library is loaded
+        bounds = continuous_bit_rate_bounds(bit_rate_selection, bit_rate_lower_bound, bit_rate_higher_bound, defrag_period)
+        self.bit_rate_selection = bit_rate_selection
+        self.continuous = bounds is not None
+        if self.continuous:
+            self.bit_rate_lower_bound, self.bit_rate_higher_bound = bounds
+            bit_rates = range(bounds[0], bounds[1] + 1)
+            bit_rate_probabilities = None
         self.L = _lib.load()
         self.topology = FrozenTopology.from_graph(topology)
         t = self.topology
@@ -113,7 +165,7 @@ class BatchedPhyRMSAEnv:
         cc.arrival_lambda = 1 / self.mean_service_inter_arrival_time
         cc.holding_lambda = 1 / self.mean_service_holding_time
         cc.bit_rates = keep(self.bit_rates, np.int32)
-        cc.bit_rate_cum = keep(br_cum, np.float64)
+        cc.bit_rate_cum = None if self.continuous else keep(br_cum, np.float64)   # NULL: continuous (include/orlg.h)
         cc.src_cum = keep(src_cum, np.float64)
         cc.dst_cum = keep(dst_cum, np.float64)
         cc.pair_table_row = keep(t.pair_table_rows(pairs), np.int32)
@@ -191,16 +243,31 @@ class BatchedPhyRMSAEnv:
         else:
             _lib.check(self.L.orlg_phy_reseed(self.h, None, int(41 if seed is None else seed)))
 
-    def run(self, policy: str, n_steps: int = 1, *, act_path=None, act_channels=None, auto_reset: bool = False,
-            outputs: Sequence[str] = (), out=None):
+    def run(self, policy: str, n_steps: int = 1, *, act_path=None, act_channels=None, act_share=None,
+            auto_reset: bool = False, outputs: Sequence[str] = (), out=None):
         """``n_steps`` x (policy -> PhyRMSAEnv.step).  ``policy='external'``: ``act_path`` [B] int32 (-2 = blocked,
         0..k-1 physical, 20 + k-path virtual layer) and ``act_channels`` [B, 14] int16 (-1 padded; entry = channel |
         used << 9, see :func:`encode_channels`).  Returns the requested per-step arrays [n_steps, B(, ...)]; ``out`` may
-        supply preallocated numpy arrays or torch tensors by name (device tensors are written without staging)."""
+        supply preallocated numpy arrays or torch tensors by name (device tensors are written without staging).
+
+        Continuous bit rates: external actions also need ``act_share`` [B, 14, 2] float64, the (used, free) fields of the
+        tuples (:func:`encode_shares`); the outputs ``channels_used_f64`` / ``channels_free_f64`` [n_steps, B, 14] hold the
+        chosen channels' float64 shares (``channels_used`` is 0 on such a handle)."""
         B = self.batch_size
         io = _lib.PhyStepIO()
         res = {}
         names = list(outputs) + [k for k in (out or {}) if k not in outputs]
+        fptr = {}
+        for name in [n for n in names if n in ("channels_used_f64", "channels_free_f64")]:
+            if not self.continuous:
+                raise KeyError(f"step output {name!r} belongs to handles with continuous bit rates")
+            shape = (n_steps, B, _lib.PHY_MAX_CHANNELS)
+            if out is not None and name in out:
+                res[name] = _check_buffer(f"out[{name!r}]", out[name], shape, np.float64)
+            else:
+                res[name] = np.zeros(shape, np.float64)
+            fptr[name] = _ptr(res[name])
+        names = [n for n in names if n not in fptr]
         for name in names:
             if name not in _lib.PHY_STEP_IO_DTYPES:
                 raise KeyError(f"unknown step output {name!r}")
@@ -233,8 +300,23 @@ class BatchedPhyRMSAEnv:
             _check_buffer("act_path", act_path, (B,), np.int32)
             _check_buffer("act_channels", act_channels, (B, _lib.PHY_MAX_CHANNELS), np.int16)
             ap, ac = _ptr(act_path), _ptr(act_channels)
-        _lib.check(self.L.orlg_phy_step(self.h, _lib.PHY_POLICIES[policy], int(n_steps), ap, ac,
-                                        1 if auto_reset else 0, C.byref(io)))
+        if not self.continuous:
+            if act_share is not None:
+                raise ValueError("act_share belongs to handles with continuous bit rates")
+            _lib.check(self.L.orlg_phy_step(self.h, _lib.PHY_POLICIES[policy], int(n_steps), ap, ac,
+                                            1 if auto_reset else 0, C.byref(io)))
+            return res
+        sp = None
+        if policy == "external":
+            if act_share is None:
+                raise ValueError("policy 'external' with continuous bit rates needs act_share (the tuples' float64 used, free)")
+            if not hasattr(act_share, "data_ptr"):
+                act_share = np.ascontiguousarray(act_share, np.float64)
+            _check_buffer("act_share", act_share, (B, _lib.PHY_MAX_CHANNELS, 2), np.float64)
+            sp = _ptr(act_share)
+        _lib.check(self.L.orlg_phy_step_ex(self.h, _lib.PHY_POLICIES[policy], int(n_steps), ap, ac, sp,
+                                           1 if auto_reset else 0, C.byref(io), fptr.get("channels_used_f64"),
+                                           fptr.get("channels_free_f64")))
         return res
 
     def requests(self):
@@ -292,6 +374,16 @@ class BatchedPhyRMSAEnv:
         if rc < 0:
             _lib.check(rc)
         out = {}
+        if self.continuous:   # float64 (used, free): the reference's tuples hold floats in this mode
+            ent = np.zeros((lists, cap, 4), np.float64)
+            rc = self.L.orlg_phy_get_channel_state_f64(self.h, int(env_index), _ptr(ent), _ptr(n))
+            if rc < 0:
+                _lib.check(rc)
+            for key in np.nonzero(n)[0]:
+                s, rem = divmod(int(key), t.num_nodes * t.k_paths)
+                d, k = divmod(rem, t.k_paths)
+                out[(s, d, k)] = [(int(x[0]), float(x[1]), float(x[2]), int(x[3])) for x in ent[key, :n[key]]]
+            return out
         for key in np.nonzero(n)[0]:
             e = ent[key, :n[key]].astype(np.int64)
             s, rem = divmod(int(key), t.num_nodes * t.k_paths)
@@ -310,6 +402,10 @@ class BatchedPhyRMSAEnv:
 
     def load_state(self, buf):
         buf = np.ascontiguousarray(buf, np.uint8)
+        tagged = buf.size >= 16 and np.array_equal(buf[-16:], _CONT_STATE_TAG)
+        if self.continuous or tagged:   # a snapshot of the other bit-rate mode is refused (ORLG_ERR_INVALID)
+            _lib.check(self.L.orlg_phy_load_state_checked(self.h, _ptr(buf), C.c_int64(buf.size)))
+            return
         assert buf.size == self.L.orlg_phy_state_size(self.h), "snapshot of a differently configured batch"
         _lib.check(self.L.orlg_phy_load_state(self.h, _ptr(buf)))
 

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from .envs import RMSAEnv as _RMSAView
-from .phy import PHY_DEFAULT_BIT_RATES, BatchedPhyRMSAEnv, encode_channels
+from .phy import PHY_DEFAULT_BIT_RATES, BatchedPhyRMSAEnv, encode_channels, encode_shares
 from .topology import Path, Service
 
 
@@ -55,7 +55,8 @@ class PhyRMSAEnv:
                  reset: bool = True, channel_width: float = 12.5, number_spectrum_channels: int = 80,
                  number_spectrum_channels_s_band: int = 108, l_band: bool = True, s_band: bool = True,
                  modulation_level=None, connections_detail=None, gsnr=None, defrag_period=None, number_moves=None,
-                 metric: str = "cut", grooming: bool = True, device: int = 0, **_ignored):
+                 metric: str = "cut", grooming: bool = True, device: int = 0, bit_rate_lower_bound=25.0,
+                 bit_rate_higher_bound=100.0, **_ignored):
         self._batched = BatchedPhyRMSAEnv(
             topology, 1, modulation_level=modulation_level, connections_detail=connections_detail, gsnr=gsnr,
             episode_length=episode_length, load=load, mean_service_holding_time=mean_service_holding_time,
@@ -63,7 +64,9 @@ class PhyRMSAEnv:
             node_request_probabilities=node_request_probabilities, seed=seed, allow_rejection=allow_rejection,
             number_spectrum_channels=number_spectrum_channels,
             number_spectrum_channels_s_band=number_spectrum_channels_s_band, l_band=l_band, s_band=s_band,
-            defrag_period=defrag_period, number_moves=number_moves, metric=metric, grooming=grooming, device=device)
+            defrag_period=defrag_period, number_moves=number_moves, metric=metric, grooming=grooming, device=device,
+            bit_rate_selection=bit_rate_selection, bit_rate_lower_bound=bit_rate_lower_bound,
+            bit_rate_higher_bound=bit_rate_higher_bound)
         b = self._batched
         ft = b.topology
         self._ft = ft
@@ -83,6 +86,9 @@ class PhyRMSAEnv:
         self.number_spectrum_channels_s_band = number_spectrum_channels_s_band
         self.allow_rejection = allow_rejection
         self.bit_rates = list(b.bit_rates)
+        self.bit_rate_selection = bit_rate_selection
+        if b.continuous:   # (the reference keeps no bit-rate histograms in this mode, phy_rmsa_env.py:130-134)
+            self.bit_rate_lower_bound, self.bit_rate_higher_bound = b.bit_rate_lower_bound, b.bit_rate_higher_bound
         self.channel_state = _ChannelState(self)
         self.services_accepted_virtual = 0
         # BVT counters per band and node pair (phy_rmsa_env.py:153-156: 1 = C band, 0 = L band, 2 = S band), kept on the host
@@ -198,7 +204,12 @@ class PhyRMSAEnv:
         encode_channels(channels, ac[0])
         if path > 10:
             self.services_accepted_virtual += 1
-        r = self._batched.run("external", 1, act_path=ap, act_channels=ac,
+        # continuous bit rates: the tuples' float64 (used, free) go with the action (include/orlg.h orlg_phy_step_ex)
+        sh = None
+        if self._batched.continuous:
+            sh = np.zeros((1, _lib.PHY_MAX_CHANNELS, 2))
+            encode_shares(channels, sh[0])
+        r = self._batched.run("external", 1, act_path=ap, act_channels=ac, act_share=sh,
                               outputs=("accepted", "done", "number_cuts_total", "rss_total_metric", "defrag_counters"))
         served.accepted = bool(r["accepted"][0, 0])
         if served.accepted and path <= 10:

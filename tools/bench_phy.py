@@ -23,6 +23,8 @@ def main():
     ap.add_argument("--moves", type=int, default=10, help="number_moves with --defrag")
     ap.add_argument("--period", type=int, default=10, help="defrag_period with --defrag")
     ap.add_argument("--queue", type=int, default=0, help="queue_capacity (0 = from the load)")
+    ap.add_argument("--continuous", type=int, nargs=2, metavar=("LOWER", "HIGHER"), default=None,
+                    help='bit_rate_selection="continuous" with rng.randint(LOWER, HIGHER) bit rates (phy_rmsa_env.py:114-129)')
     ap.add_argument("--topology", default="us14_3-paths_6-modulations",
                     help="another fixture (e.g. spn_3-paths_6-modulations: 30 nodes / 56 links, the structural limits of DESIGN 6) runs "
                          "with SYNTHETIC QoT tables (levels 1..6 at random): a timing, not a reference workload")
@@ -43,7 +45,9 @@ def main():
     env = BatchedPhyRMSAEnv(topo, args.batch, modulation_level=mod, connections_detail=pairs, gsnr=gsnr, load=args.load,
                             mean_service_holding_time=25, episode_length=200, seed=10, grooming=args.grooming,
                             defrag_period=args.period if args.defrag else None, number_moves=args.moves if args.defrag else None,
-                            metric=args.metric, queue_capacity=args.queue)
+                            metric=args.metric, queue_capacity=args.queue,
+                            **(dict(bit_rate_selection="continuous", bit_rate_lower_bound=args.continuous[0],
+                                    bit_rate_higher_bound=args.continuous[1]) if args.continuous else {}))
     outs = ("number_cuts_total", "rss_total_metric") if args.metrics else ()
 
     def run(k):
@@ -62,6 +66,7 @@ def main():
     st = env.episode_stats()
     print(json.dumps({"metric": f"env steps/s, PhyRMSA {args.topology} {args.policy}", "kernel": env.last_kernel(), "node_vectors": bool(env.node_vectors), "value": args.batch * args.steps / dt,
                       "grooming": args.grooming, "defrag": args.defrag, "defrag_metric": args.metric,
+                      "continuous": args.continuous,
                       "queue_overflow": int(st["queue_overflow"].max()),
                       "batch": args.batch, "steps": args.steps, "load": args.load, "metrics_every_step": args.metrics,
                       "ms_per_step": dt * 1e3 / args.steps, "mean_running": float(env.num_running().mean()),
