@@ -236,6 +236,34 @@ int orlg_load_state(orlg_env *env, const void *buffer);
  * out[8] = total episodes done, out[9] = B.  The caller all-reduces this vector (RCCL, SUM). */
 int orlg_reduce_counters(orlg_env *env, int64_t *out /* [16], host or device */);
 
+/* ---- load sweeps in one handle: per-environment traffic, per-load statistics.  The reference's experiment scripts run one
+ * process per load (tests/test_rmsa_threads_us.py:57-60, 132-149: range(1200, 1701, 80)); here the environments of ONE handle
+ * carry their own arrival and holding rates, and the counters come back summed per group (= per load).
+ * arrival_lambda / holding_lambda: [B] host arrays, every entry finite and positive; environment i replays
+ * RMSAEnv(load=load_i, seed=seed_i) from its first request.  group: [B] host array, group[i] in 0 .. num_groups-1, or NULL =
+ * one group; num_groups 1..256.  Everything a handle sizes "from the load" -- queue_capacity = 0 in both configs,
+ * channel_state_capacity = 0, and with the queue the defragmentation work list -- is sized from the LARGEST offered load
+ * (arrival_lambda[i] / holding_lambda[i]) of the batch.  The rates are configuration like the scalars of the configs: not part
+ * of the saved state, kept by orlg_reseed and both resets. */
+typedef struct orlg_traffic {
+    const double *arrival_lambda;
+    const double *holding_lambda;
+    const int32_t *group;
+    int32_t num_groups;
+} orlg_traffic;
+/* orlg_create with per-environment traffic; the scalar lambdas of cfg are ignored.  traffic == NULL is orlg_create. */
+int orlg_create_traffic(const orlg_topology *topo, const orlg_rmsa_config *cfg, int32_t batch, const uint64_t *seeds,
+                        uint64_t base_seed, int32_t device, const orlg_traffic *traffic, orlg_env **out);
+/* read-back of the rates and groups, [B] host arrays each, any pointer may be NULL (a handle without orlg_traffic: the config's
+ * scalars and group 0) */
+int orlg_get_traffic(orlg_env *env, double *arrival_lambda, double *holding_lambda, int32_t *group);
+int orlg_num_groups(orlg_env *env);
+/* orlg_reduce_counters per group: out[g][0..9] as orlg_reduce_counters over the environments of group g (out[g][9] = their
+ * number), out[g][10] = sum of (services_processed - services_accepted)^2, out[g][11] = the same of the episode counters (with
+ * the sums, the variance of the blocked services over the seeds of a load without reading B records), the rest 0.  Integers
+ * only: the result does not depend on the order of accumulation.  Reports a sticky ORLG_ERR_QUEUE_FULL like orlg_reduce_counters. */
+int orlg_reduce_counters_grouped(orlg_env *env, int64_t *out /* [num_groups][16], host or device */);
+
 /* ------------------------------------------------------------------------------------------------
  * QoT-aware environment: PhyRMSAEnv (optical_rl_gym/envs/phy_rmsa_env.py), physical layer + virtual ("grooming")
  * layer + periodic defragmentation.  Allocation is per CHANNEL (L+C+S bands = 268
@@ -400,6 +428,14 @@ int orlg_phy_get_channel_state_f64(orlg_phy_env *env, int32_t env_index, double 
 /* orlg_phy_load_state with the snapshot's size: ORLG_ERR_INVALID when it is not orlg_phy_state_size or the snapshot was
  * saved by a handle of the other bit-rate mode (a continuous state ends in a 16-byte tag) */
 int orlg_phy_load_state_checked(orlg_phy_env *env, const void *buffer, int64_t bytes);
+
+/* ---- load sweeps in one handle (orlg_traffic, above): the twins of orlg_create_traffic / orlg_get_traffic /
+ * orlg_reduce_counters_grouped; episodes_done comes from the episode statistics */
+int orlg_phy_create_traffic(const orlg_topology *topo, const orlg_phy_config *cfg, int32_t batch, const uint64_t *seeds,
+                            uint64_t base_seed, int32_t device, const orlg_traffic *traffic, orlg_phy_env **out);
+int orlg_phy_get_traffic(orlg_phy_env *env, double *arrival_lambda, double *holding_lambda, int32_t *group);
+int orlg_phy_num_groups(orlg_phy_env *env);
+int orlg_phy_reduce_counters_grouped(orlg_phy_env *env, int64_t *out /* [num_groups][16], host or device */);
 
 /* ------------------------------------------------------------------------------------------------
  * GN-model GSNR admission check: calculate_osnr (examples/calculate_osnr.py:9-56) for a flattened batch of checks.

@@ -52,6 +52,11 @@ STEP_IO_DTYPES = {"act_path": "int32", "act_slot": "int32", "accepted": "uint8",
                   "network_compactness_difference": "float64", "avg_link_compactness": "float64",
                   "avg_link_utilization": "float64"}
 
+class Traffic(C.Structure):   # include/orlg.h orlg_traffic
+    _fields_ = [("arrival_lambda", C.c_void_p), ("holding_lambda", C.c_void_p), ("group", C.c_void_p),
+                ("num_groups", C.c_int32)]
+
+
 class PhyConfig(C.Structure):
     _fields_ = [("num_channels", C.c_int32), ("episode_length", C.c_int32), ("num_bit_rates", C.c_int32),
                 ("k_table", C.c_int32), ("num_table_rows", C.c_int32), ("queue_capacity", C.c_int32),
@@ -156,6 +161,17 @@ def load(build_if_missing=True):
     L.orlg_phy_step_ex.argtypes = [vp, i32, i32, vp, vp, vp, i32, C.POINTER(PhyStepIO), vp, vp]
     L.orlg_phy_get_channel_state_f64.argtypes = [vp, i32, vp, vp]
     L.orlg_phy_load_state_checked.argtypes = [vp, vp, i64]
+    # per-environment traffic, per-group statistics (include/orlg.h orlg_traffic)
+    L.orlg_create_traffic.argtypes = [C.POINTER(Topology), C.POINTER(RmsaConfig), i32, vp, u64, i32, C.POINTER(Traffic),
+                                      C.POINTER(vp)]
+    L.orlg_phy_create_traffic.argtypes = [C.POINTER(Topology), C.POINTER(PhyConfig), i32, vp, u64, i32, C.POINTER(Traffic),
+                                          C.POINTER(vp)]
+    for name in ("orlg_get_traffic", "orlg_phy_get_traffic"):
+        getattr(L, name).argtypes = [vp, vp, vp, vp]
+    for name in ("orlg_num_groups", "orlg_phy_num_groups"):
+        getattr(L, name).argtypes = [vp]
+    for name in ("orlg_reduce_counters_grouped", "orlg_phy_reduce_counters_grouped"):
+        getattr(L, name).argtypes = [vp, vp]
     L.orlg_host_log.argtypes = [C.c_double]
     L.orlg_host_log.restype = C.c_double
     _lib = L
@@ -176,6 +192,8 @@ EXPORTED_SYMBOLS = [
     "orlg_phy_channel_state_capacity", "orlg_gn_osnr", "orlg_state_size", "orlg_save_state", "orlg_load_state",
     "orlg_phy_state_size", "orlg_phy_save_state", "orlg_phy_load_state",
     "orlg_phy_continuous", "orlg_phy_step_ex", "orlg_phy_get_channel_state_f64", "orlg_phy_load_state_checked",
+    "orlg_create_traffic", "orlg_get_traffic", "orlg_num_groups", "orlg_reduce_counters_grouped",
+    "orlg_phy_create_traffic", "orlg_phy_get_traffic", "orlg_phy_num_groups", "orlg_phy_reduce_counters_grouped",
 ]
 
 

@@ -11,7 +11,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, traffic as _traffic
 from .topology import FrozenTopology, selection_tables
 
 DEFAULT_BIT_RATES = (200, 250, 300, 350, 400, 450, 500, 550, 600, 650, 700, 750, 800, 850, 900, 950, 1000, 1050,
@@ -39,6 +39,55 @@ def _dtype_name(a):
     return str(a.dtype).replace("torch.", "")
 
 
+class SweepTraffic:
+    """``load=`` / ``mean_service_holding_time=`` / ``groups=`` of a batched constructor.  Scalars without groups: the
+    handle is created as ever (``orlg_create`` / ``orlg_phy_create``).  Length-B array-likes, or ``groups=`` (also next to a
+    scalar load): the handle is created with ``orlg_traffic`` (include/orlg.h) and the environments carry their own rates.
+    ``groups=`` and ``load=`` are independent: a group is any set of environments whose counters are summed together; the
+    per-load Monitor tree and summary (monitor.py) need every group to be ONE load and refuse anything else.
+    Shapes and values of a per-environment call are checked here, before the library is loaded."""
+
+    def __init__(self, batch_size, load, mean_service_holding_time, groups=None, num_groups=None):
+        self.batch_size = int(batch_size)
+        self.per_env = np.ndim(load) > 0 or np.ndim(mean_service_holding_time) > 0 or groups is not None
+        self._group_given = groups is not None
+        if not self.per_env and num_groups not in (None, 1):
+            raise ValueError("num_groups without groups")
+        if self.per_env:
+            self.arrival_lambda, self.holding_lambda = _traffic.per_env_rates(batch_size, load, mean_service_holding_time)
+            self.loads = np.broadcast_to(np.asarray(load, np.float64), (self.batch_size,)).copy()
+            self.groups, self.num_groups = _traffic.check_groups(batch_size, groups, num_groups)
+        else:   # a scalar call: nothing is checked or computed here, the library sees what it always saw
+            self.arrival_lambda = self.holding_lambda = None
+            self.loads = np.full(max(self.batch_size, 0), float(load), np.float64)
+            self.groups, self.num_groups = np.zeros(max(self.batch_size, 0), np.int32), 1
+
+    def _need_rates(self):
+        if not self.per_env:
+            raise RuntimeError("a handle with scalar rates has no orlg_traffic")
+
+    def largest(self):
+        """Index of the environment with the largest offered load (what the library sizes its capacities from)."""
+        self._need_rates()
+        return int(np.argmax(self.arrival_lambda / self.holding_lambda))
+
+    def struct(self):
+        """The ``orlg_traffic`` of the handle (the arrays stay referenced by this object)."""
+        self._need_rates()
+        t = _lib.Traffic()
+        t.arrival_lambda = self.arrival_lambda.ctypes.data_as(C.c_void_p)
+        t.holding_lambda = self.holding_lambda.ctypes.data_as(C.c_void_p)
+        t.group = self.groups.ctypes.data_as(C.c_void_p) if self._group_given else None
+        t.num_groups = self.num_groups
+        return t
+
+
+def _grouped_counters(call, h, num_groups):
+    a = np.zeros((num_groups, 16), np.int64)
+    _lib.check(call(h, _ptr(a)))
+    return a
+
+
 def _check_buffer(name, a, shape, dtype):
     """A caller-supplied array the library reads or writes through a raw pointer: shape, dtype and layout must be exactly
     what the C ABI expects (a wrong dtype would be reinterpreted, a short array overrun)."""
@@ -61,7 +110,8 @@ class BatchedRMSAEnv:
                  bit_rate_probabilities=None, node_request_probabilities=None, seed: Optional[int] = None,
                  seeds=None, allow_rejection: bool = False, channel_width: float = 12.5, j: int = 1,
                  reward_mode: int = 0, stats_level: str = "full", queue_capacity: int = 0, device: int = 0,
-                 step_kernel: str = "auto", bit_rate_lower_bound=25, bit_rate_higher_bound=100):
+                 step_kernel: str = "auto", bit_rate_lower_bound=25, bit_rate_higher_bound=100, groups=None,
+                 num_groups=None):
         if bit_rate_selection not in ("continuous", "discrete"):   # rmsa_env.py:74
             raise ValueError("bit_rate_selection must be 'continuous' or 'discrete'")
         self.bit_rate_selection = bit_rate_selection
@@ -74,6 +124,8 @@ class BatchedRMSAEnv:
                 raise ValueError("continuous bit rates: at most 256 integer rates (lower .. higher)")
             self.bit_rate_lower_bound, self.bit_rate_higher_bound = lo, hi
             bit_rates, bit_rate_probabilities = list(range(lo, hi + 1)), None
+        # load= / mean_service_holding_time= may be length-B array-likes (a load sweep in one handle, traffic.py)
+        self.traffic = SweepTraffic(batch_size, load, mean_service_holding_time, groups, num_groups)
         self.L = _lib.load()
         self.topology = FrozenTopology.from_graph(topology)
         t = self.topology
@@ -89,7 +141,11 @@ class BatchedRMSAEnv:
         # optical_network_env.py:111-129
         self.load = load
         self.mean_service_holding_time = mean_service_holding_time
-        self.mean_service_inter_arrival_time = 1 / float(load / float(mean_service_holding_time))
+        if self.traffic.per_env:
+            self.mean_service_inter_arrival_time = 1 / self.traffic.arrival_lambda
+        else:
+            self.mean_service_inter_arrival_time = 1 / float(load / float(mean_service_holding_time))
+        self.loads, self.groups, self.num_groups = self.traffic.loads, self.traffic.groups, self.traffic.num_groups
         self.node_request_probabilities, src_cum, dst_cum, br_cum = selection_tables(
             node_request_probabilities, bit_rate_probabilities, t.num_nodes, self.bit_rates)
         self.rand_seed = 41 if seed is None else int(seed)  # optical_network_env.py:266-271
@@ -117,8 +173,12 @@ class BatchedRMSAEnv:
         cc.stats_level = _lib.STATS_LEVELS[stats_level]
         cc.step_kernel = _lib.STEP_KERNELS[step_kernel]
         # rmsa_env.py:646-651: expovariate(1 / mean)
-        cc.arrival_lambda = 1 / self.mean_service_inter_arrival_time
-        cc.holding_lambda = 1 / self.mean_service_holding_time
+        if self.traffic.per_env:   # (ignored by orlg_create_traffic; the pair of the largest load, for the record)
+            cc.arrival_lambda = self.traffic.arrival_lambda[self.traffic.largest()]
+            cc.holding_lambda = self.traffic.holding_lambda[self.traffic.largest()]
+        else:
+            cc.arrival_lambda = 1 / self.mean_service_inter_arrival_time
+            cc.holding_lambda = 1 / self.mean_service_holding_time
         cc.channel_width = self.channel_width
         cc.bit_rates = keep(self.bit_rates, np.int32)
         cc.bit_rate_cum = keep(br_cum, np.float64) if bit_rate_selection == "discrete" else None   # (NULL: rng.randint)
@@ -130,8 +190,13 @@ class BatchedRMSAEnv:
             assert seeds.shape == (self.batch_size,)
             seeds_ptr = seeds.ctypes.data_as(C.c_void_p)
         h = C.c_void_p()
-        _lib.check(self.L.orlg_create(C.byref(ct), C.byref(cc), self.batch_size, seeds_ptr,
-                                      C.c_uint64(self.rand_seed), int(device), C.byref(h)))
+        if self.traffic.per_env:
+            tr = self.traffic.struct()
+            _lib.check(self.L.orlg_create_traffic(C.byref(ct), C.byref(cc), self.batch_size, seeds_ptr,
+                                                  C.c_uint64(self.rand_seed), int(device), C.byref(tr), C.byref(h)))
+        else:
+            _lib.check(self.L.orlg_create(C.byref(ct), C.byref(cc), self.batch_size, seeds_ptr,
+                                          C.c_uint64(self.rand_seed), int(device), C.byref(h)))
         self.h = h
         self.device = int(device)
         self.words_per_link = self.L.orlg_words_per_link(self.h)
@@ -346,9 +411,19 @@ class BatchedRMSAEnv:
         assert buf.size == self.L.orlg_state_size(self.h), "snapshot of a differently configured batch"
         _lib.check(self.L.orlg_load_state(self.h, _ptr(buf)))
 
-    def reduce_counters(self):
+    def traffic_rates(self):
+        """(arrival_lambda [B], holding_lambda [B], group [B]) as the handle holds them."""
+        B = self.batch_size
+        a, h, g = np.zeros(B), np.zeros(B), np.zeros(B, np.int32)
+        _lib.check(self.L.orlg_get_traffic(self.h, _ptr(a), _ptr(h), _ptr(g)))
+        return a, h, g
+
+    def reduce_counters(self, by_group: bool = False):
         """Summed counters of this shard (raises if a release queue overflowed): the vector a
-        multi-GPU job all-reduces."""
+        multi-GPU job all-reduces.  ``by_group=True``: the sums per group of environments instead, [G, 16] int64 --
+        columns 0..9 as the vector, 10 / 11 the sums of (processed - accepted)^2, all-time / episode (include/orlg.h)."""
+        if by_group:
+            return _grouped_counters(self.L.orlg_reduce_counters_grouped, self.h, self.num_groups)
         a = np.zeros(16, np.int64)
         _lib.check(self.L.orlg_reduce_counters(self.h, _ptr(a)))
         d = {n: int(a[i]) for i, n in enumerate(COUNTER_NAMES)}
@@ -364,6 +439,10 @@ class BatchedDeepRMSAEnv(BatchedRMSAEnv):
                  mean_service_holding_time: float = 25.0, mean_service_inter_arrival_time: float = 0.1,
                  num_spectrum_resources: int = 100, node_request_probabilities=None, seed=None, seeds=None,
                  allow_rejection: bool = False, **extra):
+        # (either mean may be a length-B array-like: a load sweep, as BatchedRMSAEnv)
+        if np.ndim(mean_service_holding_time) > 0 or np.ndim(mean_service_inter_arrival_time) > 0:
+            mean_service_holding_time = np.asarray(mean_service_holding_time, np.float64)
+            mean_service_inter_arrival_time = np.asarray(mean_service_inter_arrival_time, np.float64)
         super().__init__(topology, batch_size, episode_length=episode_length,
                          load=mean_service_holding_time / mean_service_inter_arrival_time,
                          mean_service_holding_time=mean_service_holding_time,

@@ -69,6 +69,7 @@ struct orlg_env {
     size_t d_actions_cap;
     OrlgErrWord err;         // sticky error word the kernels set on a release-queue overflow
     char last_kernel[96];    // name and shape of the kernel behind the last step / reset launch (orlg_last_kernel)
+    OrlgTrafficState traffic;   // per-environment rates and groups (orlg_create_traffic)
 };
 
 // wait for the handle's stream, then report an overflow a kernel flagged (ORLG_ERR_QUEUE_FULL is sticky until a full reset)
@@ -94,6 +95,51 @@ static int dev_upload(orlg_env *e, T **out, const T *host, size_t count) {
     int rc = dev_alloc(e, out, count);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return ORLG_OK;
+}
+
+// ---------------------------------------------------------------------------------------- per-environment traffic
+int orlg_traffic_check(OrlgTrafficState *ts, const orlg_traffic *tr, int batch, double *arrival, double *holding) {
+    if (!tr) return ORLG_OK;
+    if (!tr->arrival_lambda || !tr->holding_lambda) return fail(ORLG_ERR_INVALID, "traffic: null rate array");
+    if (tr->num_groups < 1 || tr->num_groups > 256) return fail(ORLG_ERR_INVALID, "traffic: num_groups %d not in 1..256", tr->num_groups);
+    double best = -1.0;
+    for (int i = 0; i < batch; i++) {
+        const double a = tr->arrival_lambda[i], h = tr->holding_lambda[i];
+        if (!std::isfinite(a) || !std::isfinite(h) || !(a > 0) || !(h > 0))
+            return fail(ORLG_ERR_INVALID, "traffic: environment %d has arrival_lambda %g, holding_lambda %g: rates must be finite and positive", i, a, h);
+        if (tr->group && (tr->group[i] < 0 || tr->group[i] >= tr->num_groups))
+            return fail(ORLG_ERR_INVALID, "traffic: group[%d] = %d not in 0..%d", i, tr->group[i], tr->num_groups - 1);
+        if (a / h > best) { best = a / h; *arrival = a; *holding = h; }
+    }
+    ts->arrival.assign(tr->arrival_lambda, tr->arrival_lambda + batch);
+    ts->holding.assign(tr->holding_lambda, tr->holding_lambda + batch);
+    if (tr->group) ts->group.assign(tr->group, tr->group + batch);
+    ts->num_groups = tr->num_groups;
+    return ORLG_OK;
+}
+int orlg_traffic_upload(OrlgTrafficState *ts, int batch, std::vector<void *> *bufs) {
+    if (!ts->arrival.empty()) {
+        std::vector<OrlgRates> r((size_t)batch);
+        for (int i = 0; i < batch; i++) { r[i].arrival_lambda = ts->arrival[i]; r[i].holding_lambda = ts->holding[i]; }
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ts->d_rates), r.size() * sizeof(OrlgRates)));
+        bufs->push_back(ts->d_rates);
+        HIP_TRY(hipMemcpy(ts->d_rates, r.data(), r.size() * sizeof(OrlgRates), hipMemcpyHostToDevice));
+    }
+    if (!ts->group.empty()) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ts->d_group), (size_t)batch * sizeof(int32_t)));
+        bufs->push_back(ts->d_group);
+        HIP_TRY(hipMemcpy(ts->d_group, ts->group.data(), (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    return ORLG_OK;
+}
+int orlg_traffic_get(const OrlgTrafficState *ts, int batch, double arrival_lambda, double holding_lambda, double *arrival,
+                     double *holding, int32_t *group) {
+    for (int i = 0; i < batch; i++) {
+        if (arrival) arrival[i] = ts->arrival.empty() ? arrival_lambda : ts->arrival[i];
+        if (holding) holding[i] = ts->holding.empty() ? holding_lambda : ts->holding[i];
+        if (group) group[i] = ts->group.empty() ? 0 : ts->group[i];
+    }
     return ORLG_OK;
 }
 
@@ -291,7 +337,8 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p) {
     // logs the links' updates and works them off one link per lane (group_link_replay)
     const bool df = df_ok;
     int *resident = hq ? e->group_resident_hq : df ? e->group_resident_df : e->group_resident;
-    rmsa_kernel_t k = pick_group(e->W, p.stats_level + (hq ? 4 : df ? 8 : 0));
+    const bool traffic = p.rates != nullptr;   // per-environment rates: the instantiations that read them (+ 16)
+    rmsa_kernel_t k = pick_group(e->W, p.stats_level + (hq ? 4 : df ? 8 : 0) + (traffic ? 16 : 0));
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     if (df && !e->llog) {
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->llog), (size_t)p.B * p.E * 64 * sizeof(uint4)));
@@ -377,7 +424,7 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p) {
     hipLaunchKernelGGL(k, grid, block, lds_bytes, e->stream, q);
     HIP_TRY(hipGetLastError());
     snprintf(e->last_kernel, sizeof(e->last_kernel), "orlg_rmsa_group_kernel<%d,%d%s> grid=%d block=%d lds=%zu chunks=%d", e->W, p.stats_level,
-             hq ? ",true" : df ? ",false,true" : "", nblocks, ORLG_WAVE * wpb, lds_bytes, q.n_chunks);
+             traffic ? (hq ? ",true,false,true" : df ? ",false,true,true" : ",false,false,true") : hq ? ",true" : df ? ",false,true" : "", nblocks, ORLG_WAVE * wpb, lds_bytes, q.n_chunks);
     return ORLG_OK;
 }
 
@@ -510,6 +557,11 @@ int orlg_destroy(orlg_env *e) {
 
 int orlg_create(const orlg_topology *t, const orlg_rmsa_config *c, int32_t batch, const uint64_t *seeds,
                 uint64_t base_seed, int32_t device, orlg_env **out) {
+    return orlg_create_traffic(t, c, batch, seeds, base_seed, device, nullptr, out);
+}
+
+int orlg_create_traffic(const orlg_topology *t, const orlg_rmsa_config *c, int32_t batch, const uint64_t *seeds,
+                        uint64_t base_seed, int32_t device, const orlg_traffic *traffic, orlg_env **out) {
     if (!t || !c || !out) return fail(ORLG_ERR_INVALID, "null argument");
     *out = nullptr;
     const int N = t->num_nodes, E = t->num_links, K = t->k_paths, S = c->num_slots, NBR = c->num_bit_rates;
@@ -530,8 +582,15 @@ int orlg_create(const orlg_topology *t, const orlg_rmsa_config *c, int32_t batch
     if (W == 7) W = 8;  // no W=7 instantiation: pad to 8 words (top word all invalid)
     if (K < 1 || K * W > 64) return fail(ORLG_ERR_INVALID, "k_paths * words_per_link = %d exceeds one wavefront", K * W);
     if (c->j < 1 || c->j > 16) return fail(ORLG_ERR_INVALID, "j %d not in 1..16", c->j);
-    if (!(c->arrival_lambda > 0) || !(c->holding_lambda > 0) || !(c->channel_width > 0))
+    if ((!traffic && (!(c->arrival_lambda > 0) || !(c->holding_lambda > 0))) || !(c->channel_width > 0))
         return fail(ORLG_ERR_INVALID, "arrival_lambda, holding_lambda and channel_width must be positive");
+    // per-environment traffic: the scalars of the config give way to the pair of the largest offered load, which sizes the queue
+    OrlgTrafficState traffic_state;
+    double arrival_lambda = c->arrival_lambda, holding_lambda = c->holding_lambda;
+    {
+        int rc0 = orlg_traffic_check(&traffic_state, traffic, batch, &arrival_lambda, &holding_lambda);
+        if (rc0) return rc0;
+    }
     if (c->stats_level < 0 || c->stats_level > 2) return fail(ORLG_ERR_INVALID, "bad stats_level");
     for (int i = 0; i < N * N; i++) {
         int s = i / N, d = i % N;
@@ -567,13 +626,14 @@ int orlg_create(const orlg_topology *t, const orlg_rmsa_config *c, int32_t batch
     p.B = batch; p.N = N; p.E = E; p.S = S; p.K = K; p.NBR = NBR; p.NW = E * W;
     p.episode_length = c->episode_length; p.reward_mode = c->reward_mode; p.stats_level = c->stats_level; p.j = c->j;
     p.obs_dim = 1 + 2 * N + (2 * c->j + 3) * K;
-    p.arrival_lambda = c->arrival_lambda; p.holding_lambda = c->holding_lambda;
+    p.arrival_lambda = arrival_lambda; p.holding_lambda = holding_lambda;
+    e->traffic = traffic_state;
     // release-queue capacity: offered load in Erlang = arrival_lambda / holding_lambda; the number of
     // services in progress is at most Poisson(load) distributed -> mean + 10 sigma, whole waves (an overflow is
     // detected and reported, never silent)
     int Q = c->queue_capacity;
     if (Q <= 0) {
-        double load = c->arrival_lambda / c->holding_lambda;
+        double load = arrival_lambda / holding_lambda;   // (a sweep: its largest)
         Q = (int)(load + 10.0 * std::sqrt(load));
     }
     Q = ((Q + 15) / 16) * 16;   // 16 slots = one row of the four-environments-per-wave kernel, 128 bytes of times
@@ -751,6 +811,8 @@ int orlg_create(const orlg_topology *t, const orlg_rmsa_config *c, int32_t batch
     TRY(dev_alloc(e, &p.ring_iat, (size_t)batch * ORLG_RING));
     TRY(dev_alloc(e, &p.ring_ht, (size_t)batch * ORLG_RING));
     TRY(dev_alloc(e, &p.ring_req, (size_t)batch * ORLG_RING));
+    TRY(orlg_traffic_upload(&e->traffic, batch, &e->bufs));
+    p.rates = e->traffic.d_rates;
     {
         std::vector<uint32_t> mt((size_t)batch * ORLG_MT_N);
         for (int i = 0; i < batch; i++) orlg_mt_seed(&mt[(size_t)i * ORLG_MT_N], seeds ? seeds[i] : base_seed + (uint64_t)i);
@@ -1093,6 +1155,23 @@ int orlg_reduce_counters(orlg_env *e, int64_t *out) {
     int hflag = 0;
     HIP_TRY(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(out, d, 16 * 8, hipMemcpyDefault, e->stream));
+    SYNC_CHECK(e);
+    if (hflag) return fail(ORLG_ERR_QUEUE_FULL, "a release queue overflowed (capacity %d): raise queue_capacity", e->p.Q);
+    return ORLG_OK;
+}
+
+int orlg_get_traffic(orlg_env *e, double *arrival_lambda, double *holding_lambda, int32_t *group) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    return orlg_traffic_get(&e->traffic, e->p.B, e->p.arrival_lambda, e->p.holding_lambda, arrival_lambda, holding_lambda, group);
+}
+int orlg_num_groups(orlg_env *e) { return e ? e->traffic.num_groups : ORLG_ERR_INVALID; }
+
+int orlg_reduce_counters_grouped(orlg_env *e, int64_t *out) {
+    if (!e || !out) return fail(ORLG_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(e->device));
+    int hflag = 0;
+    int rc = orlg_reduce_grouped(&e->traffic, &e->bufs, e->p.scal, e->p.B, e->num_cu, e->stream, out, &hflag);
+    if (rc) return rc;
     SYNC_CHECK(e);
     if (hflag) return fail(ORLG_ERR_QUEUE_FULL, "a release queue overflowed (capacity %d): raise queue_capacity", e->p.Q);
     return ORLG_OK;

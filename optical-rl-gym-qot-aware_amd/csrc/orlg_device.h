@@ -55,6 +55,11 @@ struct OrlgWaveScalars {
 };
 static_assert(sizeof(OrlgWaveScalars) == 128, "OrlgWaveScalars layout");
 
+// the arrival process of one environment of a handle with per-environment traffic (include/orlg.h orlg_traffic)
+struct __attribute__((aligned(16))) OrlgRates {
+    double arrival_lambda, holding_lambda;
+};
+
 enum { ORLG_MODE_STEP = 0, ORLG_MODE_INIT = 1, ORLG_MODE_EPISODE_RESET = 2 };
 // device-side policy ids (== include/orlg.h ORLG_POLICY_*)
 enum { ORLG_POLICY_EXT = -1, ORLG_POLICY_SP = 0, ORLG_POLICY_SAP = 1, ORLG_POLICY_LLP = 2, ORLG_POLICY_DEEP_SP = 3,
@@ -124,4 +129,7 @@ struct OrlgParams {
     // size (a wave's region = 4 environments), and g_mt = size of the workgroup's MT19937 staging buffer, which sits with its
     // lock word between the tables and the waves' regions
     int32_t g_occ, g_qtime, g_qdesc, g_lstat, g_hist, g_lint, g_env_bytes, g_mt, g_wave_bytes;
+    // per-environment traffic (orlg_create_traffic): [B] pairs (arrival_lambda, holding_lambda) that take the place of the two
+    // scalars above, nullptr = every environment has the scalars.  Read where a refill needs it (orlg_env_rates), never kept
+    const OrlgRates *rates;
 };

@@ -368,7 +368,9 @@ DEV void row_copy8(u64 *dst, const u64 *src, int n, int gl) {
 // half of an environment's footprint there (its capacity, not its live part, sizes the region), and a one-step launch is
 // bound by how many waves a CU keeps resident, not by the queue's latency.  The ring logic is the same code on
 // global pointers; OrlgParams::g_wave_bytes of such a launch ends where the ring's LDS slices would begin.
-template <int W, int STATS, bool HBMQ = false, bool DEFER = false>
+// TRAFFIC: the handle has per-environment traffic (OrlgParams::rates).  A template argument and not a test at run time: the
+// instantiations that serve handles with the two scalars stay, instruction for instruction, what they were without the feature
+template <int W, int STATS, bool HBMQ = false, bool DEFER = false, bool TRAFFIC = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3) / 4) void orlg_rmsa_group_kernel(const OrlgParams p) {
     static_assert(!DEFER || (STATS >= 2 && !HBMQ), "the deferred link statistics belong to long launches with full statistics");
     extern __shared__ __align__(16) unsigned char smem[];
@@ -748,13 +750,15 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
                 l_mt[lane] = m0; l_mt[lane + 64] = m1;
                 if (lane < 156 - 128) l_mt[lane + 128] = m2;
                 wave_sync();
+                double arrival_lambda = p.arrival_lambda, holding_lambda = p.holding_lambda;
+                if constexpr (TRAFFIC) orlg_env_rates(kernarg_params()->rates, env_s, arrival_lambda, holding_lambda);   // (the rates of env_s)
                 const int got = p.br_width > 0   // bit_rate_selection="continuous"
                     ? refill_requests_cont_t<false>(mt_lds, p.ring_iat + (size_t)env_s * ORLG_RING, p.ring_ht + (size_t)env_s * ORLG_RING,
                                                     p.ring_req + (size_t)env_s * ORLG_RING, tb.src_cum, tb.dst_cum, &idx_s, N, p.br_width,
-                                                    p.arrival_lambda, p.holding_lambda)
+                                                    arrival_lambda, holding_lambda)
                     : refill_requests(mt_lds, p.ring_iat + (size_t)env_s * ORLG_RING, p.ring_ht + (size_t)env_s * ORLG_RING,
                                       p.ring_req + (size_t)env_s * ORLG_RING, tb.src_cum, tb.dst_cum, tb.br_cum, &idx_s, N,
-                                      NBR, p.arrival_lambda, p.holding_lambda, env_s);
+                                      NBR, arrival_lambda, holding_lambda, env_s);
                 m0 = l_mt[lane]; m1 = l_mt[lane + 64];
                 if (lane < 156 - 128) m2 = l_mt[lane + 128];
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // this wave's reads of the buffer are done

@@ -43,6 +43,83 @@ struct OrlgErrWord {
 int orlg_err_word_create(OrlgErrWord *w);
 void orlg_err_word_destroy(OrlgErrWord *w);
 
+// ---------------------------------------------------------------------------------------- per-environment traffic
+// What a handle keeps of an orlg_traffic (include/orlg.h): the host arrays for the read-back, the device table of rate pairs
+// the kernels read and the device group index of the grouped reduction.  A handle without traffic has empty arrays, null
+// pointers and one group.
+struct OrlgTrafficState {
+    std::vector<double> arrival, holding;
+    std::vector<int32_t> group;
+    int num_groups = 1;
+    OrlgRates *d_rates = nullptr;
+    int32_t *d_group = nullptr;
+    int64_t *d_grouped = nullptr;   // [num_groups][16] result of the grouped reduction, then its overflow word
+};
+// checks tr (finite positive rates, groups in range) and copies it; *arrival / *holding leave as the pair of the LARGEST offered
+// load arrival_lambda[i] / holding_lambda[i] of the batch: what the handle's capacities are sized from
+int orlg_traffic_check(OrlgTrafficState *ts, const orlg_traffic *tr, int batch, double *arrival, double *holding);
+// device copies (call with the handle's device current); the buffers are pushed to bufs, which the handle frees
+int orlg_traffic_upload(OrlgTrafficState *ts, int batch, std::vector<void *> *bufs);
+int orlg_traffic_get(const OrlgTrafficState *ts, int batch, double arrival_lambda, double holding_lambda, double *arrival,
+                     double *holding, int32_t *group);
+
+// orlg_reduce_counters per group.  Grid-stride over the environments; every workgroup sums into a [num_groups][12] table in LDS
+// (64-bit LDS atomics; at most 256 x 12 x 8 = 24 KB) and then adds its non-zero entries to out[num_groups][16], zeroed on the
+// stream before, with global atomics whose result nobody reads.  Integers only, so the order of the additions does not show.
+// Entries 0..9 as orlg_reduce_counters_kernel, 10 / 11 the squares of the blocked services (all-time / episode).
+// Scal: OrlgEnvScalars or OrlgPhyScalars (c[8], episodes_done, q_overflow).
+#define ORLG_GROUP_COLS 12
+template <typename Scal>
+__global__ __launch_bounds__(256) void orlg_reduce_grouped_kernel(const Scal *scal, const int32_t *group, int B, int G,
+                                                                  unsigned long long *out, int *overflow) {
+    extern __shared__ unsigned long long orlg_group_tab[];
+    for (int i = threadIdx.x; i < G * ORLG_GROUP_COLS; i += 256) orlg_group_tab[i] = 0ull;
+    __syncthreads();
+    int any = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < (size_t)B; i += (size_t)gridDim.x * 256) {
+        int g = group ? group[i] : 0;
+        if (g < 0 || g >= G) g = 0;   // (checked at create time; a table of the wrong handle must not leave the LDS table)
+        unsigned long long *row = orlg_group_tab + g * ORLG_GROUP_COLS;
+        const Scal &s = scal[i];
+        for (int q = 0; q < 8; ++q) atomicAdd(row + q, (unsigned long long)s.c[q]);
+        atomicAdd(row + 8, (unsigned long long)s.episodes_done);
+        atomicAdd(row + 9, 1ull);
+        const long long blocked = s.c[0] - s.c[1], eblocked = s.c[2] - s.c[3];
+        atomicAdd(row + 10, (unsigned long long)(blocked * blocked));
+        atomicAdd(row + 11, (unsigned long long)(eblocked * eblocked));
+        any |= s.q_overflow;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < G * ORLG_GROUP_COLS; i += 256) {
+        const unsigned long long v = orlg_group_tab[i];
+        if (v) atomicAdd(out + (i / ORLG_GROUP_COLS) * 16 + i % ORLG_GROUP_COLS, v);
+    }
+    if (any) atomicOr(overflow, 1);
+}
+// zeroes ts->d_grouped, launches the kernel above and copies [num_groups][16] to out (host or device); *overflow = an environment
+// of the batch has its overflow word set
+template <typename Scal>
+static int orlg_reduce_grouped(OrlgTrafficState *ts, std::vector<void *> *bufs, const Scal *scal, int B, int num_cu,
+                               hipStream_t stream, int64_t *out, int *overflow) {
+    const int G = ts->num_groups;
+    const size_t bytes = (size_t)G * 16 * 8;
+    if (!ts->d_grouped) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ts->d_grouped), bytes + 16));
+        bufs->push_back(ts->d_grouped);
+    }
+    HIP_TRY(hipMemsetAsync(ts->d_grouped, 0, bytes + 16, stream));
+    int nblocks = (B + 255) / 256;
+    const int cap = 4 * (num_cu > 0 ? num_cu : 256);
+    if (nblocks > cap) nblocks = cap;
+    int *d_flag = reinterpret_cast<int *>(ts->d_grouped + (size_t)G * 16);
+    hipLaunchKernelGGL(orlg_reduce_grouped_kernel<Scal>, dim3(nblocks), dim3(256), (size_t)G * ORLG_GROUP_COLS * 8, stream, scal,
+                       ts->d_group, B, G, reinterpret_cast<unsigned long long *>(ts->d_grouped), d_flag);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(overflow, d_flag, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(out, ts->d_grouped, bytes, hipMemcpyDefault, stream));
+    return ORLG_OK;
+}
+
 // ---------------------------------------------------------------------------------------- kernel instantiation units
 // Every unit exports one lookup per word count W; a W the library was not built for resolves to a null (weak) symbol.
 typedef void (*orlg_rmsa_kernel_t)(const OrlgParams);

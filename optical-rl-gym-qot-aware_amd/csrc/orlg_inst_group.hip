@@ -20,6 +20,14 @@ orlg_rmsa_kernel_t ORLG_CAT(orlg_group_kernel_W, ORLG_INST_W)(int stats) {
         case 5: return orlg_rmsa_group_kernel<W, 1, true>;
         case 6: return orlg_rmsa_group_kernel<W, 2, true>;
         case 10: return orlg_rmsa_group_kernel<W, 2, false, true>;   // + 8: full statistics with the link updates deferred (long launches)
+        // + 16: handles with per-environment traffic (OrlgParams::rates)
+        case 16: return orlg_rmsa_group_kernel<W, 0, false, false, true>;
+        case 17: return orlg_rmsa_group_kernel<W, 1, false, false, true>;
+        case 18: return orlg_rmsa_group_kernel<W, 2, false, false, true>;
+        case 20: return orlg_rmsa_group_kernel<W, 0, true, false, true>;
+        case 21: return orlg_rmsa_group_kernel<W, 1, true, false, true>;
+        case 22: return orlg_rmsa_group_kernel<W, 2, true, false, true>;
+        case 26: return orlg_rmsa_group_kernel<W, 2, false, true, true>;
         default: return nullptr;
     }
 }

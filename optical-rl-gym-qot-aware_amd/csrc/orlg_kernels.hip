@@ -557,6 +557,19 @@ DEV KernargParams kernarg_params() {
     return (KernargParams)k;
 }
 
+// (arrival_lambda, holding_lambda) of environment `env` (wave-uniform) of a handle with per-environment traffic; a handle without
+// (rates == nullptr) keeps the two scalars the caller passes in.  The table is written before the handle's first launch and never
+// after, so it is read through the constant address space: the pair arrives by the scalar cache in four SGPRs at the place that
+// uses it -- no vector register, nothing kept across the step
+DEV void orlg_env_rates(const OrlgRates *rates, int env, double &arrival_lambda, double &holding_lambda) {
+    if (rates) {
+        typedef const OrlgRates __attribute__((address_space(4))) *ConstRates;
+        ConstRates r = (ConstRates)(uintptr_t)rates + __builtin_amdgcn_readfirstlane(env);
+        arrival_lambda = r->arrival_lambda;
+        holding_lambda = r->holding_lambda;
+    }
+}
+
 // ---------------------------------------------------------------------------------------- link statistics
 // Rebuild, for a list of links, the integer run statistics of the link's free bitmap and (LINKF) the
 // time-weighted floats of _update_link_stats (rmsa_env.py:562-641).  Maintains the per-link (span, gaps)
@@ -1299,12 +1312,14 @@ DEV void rmsa_body(const OrlgParams &p) {
                 }
                 ring_dirty = true;
                 ring_in_lds = true;
+                double arrival_lambda = p.arrival_lambda, holding_lambda = p.holding_lambda;
+                orlg_env_rates(kernarg_params()->rates, env, arrival_lambda, holding_lambda);   // (a sweep: the environment's own)
                 if (p.br_width > 0)   // bit_rate_selection="continuous"
                     ring_cnt = refill_requests_cont_t<true>(wv.mt, wv.ring_iat, wv.ring_ht, wv.ring_req, tb.src_cum, tb.dst_cum, &mt_idx, N,
-                                                            p.br_width, p.arrival_lambda, p.holding_lambda);
+                                                            p.br_width, arrival_lambda, holding_lambda);
                 else
                     ring_cnt = refill_requests_t<true>(wv.mt, wv.ring_iat, wv.ring_ht, wv.ring_req, tb.src_cum, tb.dst_cum, tb.br_cum,
-                                                       &mt_idx, N, NBR, p.arrival_lambda, p.holding_lambda, env);
+                                                       &mt_idx, N, NBR, arrival_lambda, holding_lambda, env);
                 ring_pos = 0;
                 SEC(7);
             }

@@ -29,6 +29,7 @@ struct orlg_phy_env {
     uint64_t *cont_tag;      // (continuous handles: the 16-byte tag at the end of the saved state)
     OrlgErrWord err;         // sticky error word the kernel sets when a queue / channel_state list / work list overflows
     char last_kernel[96];    // name and shape of the kernel behind the last launch (orlg_phy_last_kernel)
+    OrlgTrafficState traffic;   // per-environment rates and groups (orlg_phy_create_traffic)
 };
 
 static int phy_sync_check(orlg_phy_env *e) {
@@ -242,6 +243,11 @@ int orlg_phy_destroy(orlg_phy_env *e) {
 
 int orlg_phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t batch, const uint64_t *seeds,
                     uint64_t base_seed, int32_t device, orlg_phy_env **out) {
+    return orlg_phy_create_traffic(t, c, batch, seeds, base_seed, device, nullptr, out);
+}
+
+int orlg_phy_create_traffic(const orlg_topology *t, const orlg_phy_config *c, int32_t batch, const uint64_t *seeds,
+                            uint64_t base_seed, int32_t device, const orlg_traffic *traffic, orlg_phy_env **out) {
     if (!t || !c || !out) return fail(ORLG_ERR_INVALID, "null argument");
     *out = nullptr;
     const int N = t->num_nodes, E = t->num_links, K = t->k_paths, C = c->num_channels, NBR = c->num_bit_rates;
@@ -268,7 +274,15 @@ int orlg_phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t ba
     if (t->num_paths < 1 || t->num_paths >= 65536) return fail(ORLG_ERR_INVALID, "num_paths out of range");
     const int W = (C + 63) / 64;
     if (K * W > 64) return fail(ORLG_ERR_INVALID, "k_paths * words_per_link exceeds one wavefront");
-    if (!(c->arrival_lambda > 0) || !(c->holding_lambda > 0)) return fail(ORLG_ERR_INVALID, "lambdas must be positive");
+    if (!traffic && (!(c->arrival_lambda > 0) || !(c->holding_lambda > 0))) return fail(ORLG_ERR_INVALID, "lambdas must be positive");
+    // per-environment traffic: the scalars of the config give way to the pair of the largest offered load, which sizes the
+    // queue, the channel_state lists and with the queue the defragmentation work list
+    OrlgTrafficState traffic_state;
+    double arrival_lambda = c->arrival_lambda, holding_lambda = c->holding_lambda;
+    {
+        int rc0 = orlg_traffic_check(&traffic_state, traffic, batch, &arrival_lambda, &holding_lambda);
+        if (rc0) return rc0;
+    }
     for (int i = 0; i < N * N; i++) {
         int s = i / N, d = i % N;
         if (s == d) continue;
@@ -306,7 +320,8 @@ int orlg_phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t ba
     p.err_flag = e->err.dev;
     p.B = batch; p.N = N; p.E = E; p.C = C; p.K = K; p.NBR = NBR; p.NW = E * W;
     p.episode_length = c->episode_length; p.num_rows = c->num_table_rows; p.cpad = W * 64;
-    p.arrival_lambda = c->arrival_lambda; p.holding_lambda = c->holding_lambda;
+    p.arrival_lambda = arrival_lambda; p.holding_lambda = holding_lambda;
+    e->traffic = traffic_state;
     p.grooming = c->grooming ? 1 : 0;
     p.defrag_period = c->defrag_period > 0 ? c->defrag_period : 0;
     p.number_moves = c->number_moves; p.defrag_metric = c->defrag_metric ? 1 : 0;
@@ -316,7 +331,7 @@ int orlg_phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t ba
         // (pair, path); sized from the mean number of services per ordered pair, overflow is reported, never dropped
         int cl = c->channel_state_capacity;
         if (cl <= 0) {
-            double m = (c->arrival_lambda / c->holding_lambda) / ((double)N * (N - 1));
+            double m = (arrival_lambda / holding_lambda) / ((double)N * (N - 1));   // (a sweep: its largest load)
             cl = (int)(m + 6.0 * std::sqrt(m) + 8.0);
         }
         int pw2 = 8;
@@ -330,7 +345,7 @@ int orlg_phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t ba
     // release queue: at most Poisson(load) services in progress, and never more than the channel-links can hold
     int Q = c->queue_capacity;
     if (Q <= 0) {
-        double load = c->arrival_lambda / c->holding_lambda;
+        double load = arrival_lambda / holding_lambda;
         double q = load + 8.0 * std::sqrt(load) + 32.0;
         double cap = (double)E * C / 2.0 + 64.0;
         Q = (int)(q < cap ? q : cap);
@@ -537,6 +552,16 @@ int orlg_phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t ba
     TRY(alloc(reinterpret_cast<void **>(&p.cs), (size_t)batch * N * N * K * p.cs_len * 4));
     TRY(alloc(reinterpret_cast<void **>(&p.cs_n), (size_t)batch * N * N * K));
     TRY(alloc(reinterpret_cast<void **>(&p.ticket), 16));
+    {
+        // queue and list slots no service has used yet are part of the saved state: zeroed, so that two handles that ran the same
+        // simulation save the same bytes
+        hipError_t er = hipMemset(p.qtime, 0, (size_t)batch * Q * 8);
+        if (er == hipSuccess) er = hipMemset(p.qrec, 0, (size_t)batch * Q * sizeof(OrlgPhySvc));
+        if (er == hipSuccess) er = hipMemset(p.cs, 0, (size_t)batch * N * N * K * p.cs_len * 4);
+        if (er != hipSuccess) { orlg_phy_destroy(e); return fail(ORLG_ERR_HIP, "hipMemset: %s", hipGetErrorString(er)); }
+    }
+    TRY(orlg_traffic_upload(&e->traffic, batch, &e->bufs));
+    p.rates = e->traffic.d_rates;
     if (cont) {   // the float64 shares: parallel to the channel_state entries and to the service records
         TRY(alloc(reinterpret_cast<void **>(&p.cs_f), (size_t)batch * N * N * K * p.cs_len * 2 * sizeof(double)));
         TRY(alloc(reinterpret_cast<void **>(&p.svc_f), (size_t)batch * Q * ORLG_PHY_MAX_CH * sizeof(double)));
@@ -930,6 +955,28 @@ int orlg_phy_reduce_counters(orlg_phy_env *e, int64_t *out) {
     HIP_TRY(hipMemcpyAsync(out, d, 16 * 8, hipMemcpyDefault, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (host[10]) return fail(ORLG_ERR_QUEUE_FULL, "a release queue (capacity %d), channel_state list (capacity %d) or defragmentation work list (capacity %d) overflowed: raise queue_capacity / channel_state_capacity / defrag_capacity", e->p.Q, e->p.cs_len, e->p.cand_cap);
+    return ORLG_OK;
+}
+
+int orlg_phy_get_traffic(orlg_phy_env *e, double *arrival_lambda, double *holding_lambda, int32_t *group) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    return orlg_traffic_get(&e->traffic, e->p.B, e->p.arrival_lambda, e->p.holding_lambda, arrival_lambda, holding_lambda, group);
+}
+int orlg_phy_num_groups(orlg_phy_env *e) { return e ? e->traffic.num_groups : ORLG_ERR_INVALID; }
+
+int orlg_phy_reduce_counters_grouped(orlg_phy_env *e, int64_t *out) {
+    if (!e || !out) return fail(ORLG_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(e->device));
+    if (e->num_cu <= 0) {
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, e->device));
+        e->num_cu = prop.multiProcessorCount;
+    }
+    int hflag = 0;
+    int rc = orlg_reduce_grouped(&e->traffic, &e->bufs, e->p.scal, e->p.B, e->num_cu, e->stream, out, &hflag);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (hflag) return fail(ORLG_ERR_QUEUE_FULL, "a release queue (capacity %d), channel_state list (capacity %d) or defragmentation work list (capacity %d) overflowed: raise queue_capacity / channel_state_capacity / defrag_capacity", e->p.Q, e->p.cs_len, e->p.cand_cap);
     return ORLG_OK;
 }
 

@@ -153,6 +153,9 @@ struct OrlgPhyParams {
     // per-wave LDS layout
     int32_t l_occ, l_nbt, l_nbi, l_scratch, l_wsc, l_wave_bytes, l_shared_bytes, l_outs;
     int32_t l_mtstage;      // the workgroup's MT19937 staging buffer (2496 B, then its lock word), after the tables
+    // per-environment traffic (orlg_phy_create_traffic): [B] pairs that take the place of arrival_lambda / holding_lambda above,
+    // nullptr = every environment has the scalars.  Read where a refill or nb_rebuild needs it (orlg_env_rates), never kept
+    const OrlgRates *rates;
 };
 
 struct PhyWaveScalars {  // LDS
@@ -702,6 +705,15 @@ DEV int nb_collect(NearBuffer &nb, const double *gq, int n_running, double horiz
     }
     wave_sync();
     return cnt;
+}
+// the holding rate that sizes the horizon of nb_rebuild: the handle's scalar, or the environment's own of a handle with
+// per-environment traffic -- fetched from the kernel arguments and the scalar cache at the call, not kept in a register
+DEV double phy_holding_lambda(double holding_lambda, int env) {
+    const OrlgPhyParams __attribute__((address_space(4))) *kq =
+        (const OrlgPhyParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+    double arrival_lambda = 0.0;
+    orlg_env_rates(kq->rates, env, arrival_lambda, holding_lambda);
+    return holding_lambda;
 }
 // returns false when even the services due right now do not fit (reported as a queue overflow)
 DEV bool nb_rebuild(NearBuffer &nb, const double *gq, int n_running, double now, double holding_lambda, int lane) {
@@ -2303,7 +2315,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                                     nb.n += 1;
                                 } else {
                                     wave_sync();
-                                    if (!nb_rebuild(nb, gq, n_running, current_time, p.holding_lambda, lane) && lane == 0) ws->q_overflow |= 8;
+                                    if (!nb_rebuild(nb, gq, n_running, current_time, phy_holding_lambda(p.holding_lambda, env), lane) && lane == 0) ws->q_overflow |= 8;
                                 }
                             }
                         }
@@ -2451,7 +2463,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                                     nb.n += 1;
                                 } else {
                                     wave_sync();
-                                    if (!nb_rebuild(nb, gq, n_running, current_time, p.holding_lambda, lane) && lane == 0) ws->q_overflow |= 8;
+                                    if (!nb_rebuild(nb, gq, n_running, current_time, phy_holding_lambda(p.holding_lambda, env), lane) && lane == 0) ws->q_overflow |= 8;
                                 }
                             }
                         }
@@ -2567,13 +2579,15 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                 if (lane < 156 - 128) l_mt[lane + 128] = m2;
                 wave_sync();
                 int idx_s = mt_idx;
+                double arrival_lambda = p.arrival_lambda, holding_lambda = p.holding_lambda;
+                orlg_env_rates(kq->rates, env, arrival_lambda, holding_lambda);   // (a sweep: the environment's own)
                 const int got = CONT   // rng.randint(lower, higher) (phy_rmsa_env.py:127-129): the ring entry holds r, the rate is lower + r
                     ? refill_requests_cont_t<false>(mt_lds, kq->ring_iat + (size_t)env * ORLG_RING, kq->ring_ht + (size_t)env * ORLG_RING,
                                                     kq->ring_req + (size_t)env * ORLG_RING, tb.src_cum, tb.dst_cum, &idx_s, N, NBR,
-                                                    p.arrival_lambda, p.holding_lambda)
+                                                    arrival_lambda, holding_lambda)
                     : refill_requests(mt_lds, kq->ring_iat + (size_t)env * ORLG_RING, kq->ring_ht + (size_t)env * ORLG_RING,
                                                 kq->ring_req + (size_t)env * ORLG_RING, tb.src_cum, tb.dst_cum, tb.br_cum, &idx_s, N, NBR,
-                                                p.arrival_lambda, p.holding_lambda, env);
+                                                arrival_lambda, holding_lambda, env);
                 m0 = l_mt[lane]; m1 = l_mt[lane + 64];
                 if (lane < 156 - 128) m2 = l_mt[lane + 128];
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // this wave's reads of the buffer are done
@@ -2614,7 +2628,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
             // with the virtual layer the order of simultaneous releases decides who frees a shared channel
             wave_sync();
             if (current_time > nb.horizon) {
-                if (!nb_rebuild(nb, gq, n_running, current_time, p.holding_lambda, lane) && lane == 0) ws->q_overflow |= 8;
+                if (!nb_rebuild(nb, gq, n_running, current_time, phy_holding_lambda(p.holding_lambda, env), lane) && lane == 0) ws->q_overflow |= 8;
             }
             // the scan looks one arrival ahead: the earliest release up to the NEXT arrival's time is this step's victim when it
             // is due now, and otherwise the service the next step will release first -- its record is requested right away

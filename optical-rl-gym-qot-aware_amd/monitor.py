@@ -7,10 +7,13 @@ results produced on the GPU.
 from __future__ import annotations
 
 import json
+import os
 import time
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
+
+from . import traffic as _traffic
 
 RMSA_INFO_KEYWORDS = ("episode_service_blocking_rate", "service_blocking_rate", "episode_bit_rate_blocking_rate",
                       "bit_rate_blocking_rate")
@@ -27,15 +30,69 @@ def write_monitor_csv(path: str, rows: Sequence[Dict], env_id: str, info_keyword
                              for k in ("r", "l", "t") + tuple(info_keywords)) + "\n")
 
 
+def monitor_tree_path(monitor_dir: str, load, episode_length: int, monitor_name: str) -> str:
+    """``{monitor_dir}/logs_{load}_{episode_length}/{monitor_name}.monitor.csv``: the tree of the reference's sweep scripts
+    (``tests/test_rmsa_threads_us.py:149``, ``log_dir = "./.../logs_{}_{}/".format(load, episode_length)``)."""
+    return os.path.join(monitor_dir, f"logs_{load:g}_{int(episode_length)}", f"{monitor_name}.monitor.csv")
+
+
+def write_monitor_tree(monitor_dir: str, monitor_name: str, rows: Sequence[Dict], groups, group_loads, episode_length: int,
+                       env_id: str, info_keywords: Sequence[str], t_start: Optional[float] = None) -> List[str]:
+    """One Monitor CSV per group (= load) of a sweep.  ``rows`` are the rows of :func:`write_monitor_csv` in (episode,
+    environment) order for a batch of ``len(groups)`` environments; a group's file keeps that order -- (episode,
+    environment-of-the-group).  ``group_loads[g]`` names the folder of group ``g``.  Returns the paths by group (groups
+    without environments write nothing and are left out)."""
+    groups = np.asarray(groups)
+    B = groups.shape[0]
+    if B < 1 or len(rows) % B:
+        raise ValueError(f"{len(rows)} rows are not whole episodes of {B} environments")
+    paths = []
+    for g in range(len(group_loads)):
+        members = np.flatnonzero(groups == g)
+        if members.size == 0:
+            continue
+        path = monitor_tree_path(monitor_dir, float(group_loads[g]), episode_length, monitor_name)
+        if path in paths:
+            raise ValueError(f"groups with the same load {group_loads[g]:g} would share {path}")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        mine = [rows[ep * B + int(i)] for ep in range(len(rows) // B) for i in members]
+        write_monitor_csv(path, mine, env_id, info_keywords, t_start=t_start)
+        paths.append(path)
+    return paths
+
+
+def _by_group_summary(env, grouped: Sequence[np.ndarray]):
+    """``by_group`` of the evaluate functions from the grouped reductions taken at the end of every episode."""
+    ep = [_traffic.blocking_summary(a, episode=True) for a in grouped]
+    al = [_traffic.blocking_summary(a, episode=False) for a in grouped]
+    return {"load": _traffic.group_loads(env.loads, env.groups, env.num_groups),
+            "num_envs": np.asarray(grouped[0])[:, 9].copy() if grouped else np.zeros(env.num_groups, np.int64),
+            "episode_service_blocking_rate": np.stack([m for m, _ in ep]),
+            "episode_service_blocking_rate_stderr": np.stack([e for _, e in ep]),
+            "service_blocking_rate": np.stack([m for m, _ in al]),
+            "service_blocking_rate_stderr": np.stack([e for _, e in al]),
+            "counters": np.stack([np.asarray(a) for a in grouped])}
+
+
 def evaluate_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, monitor_path: Optional[str] = None,
                                env_id: str = "RMSA-v0", info_keywords: Sequence[str] = RMSA_INFO_KEYWORDS,
-                               chunk: int = 1000):
+                               chunk: int = 1000, monitor_dir: Optional[str] = None, monitor_name: Optional[str] = None,
+                               by_group: bool = False):
     """Run ``n_eval_episodes`` episodes of ``policy`` on every env of a :class:`BatchedRMSAEnv` with the reference
     loop's semantics: ``env.reset()`` (episode counters only) before every episode, step until ``done``.  Returns
     (episode_rewards [episodes, B], episode_lengths [episodes, B], per-episode info arrays); optionally writes one
-    Monitor CSV with the rows of env 0, then env 1, ... per episode."""
+    Monitor CSV with the rows of env 0, then env 1, ... per episode.
+
+    ``monitor_dir``: one file per group of the handle (a load sweep, ``traffic.load_sweep``) in the reference's tree,
+    ``{monitor_dir}/logs_{load:g}_{episode_length}/{monitor_name}.monitor.csv`` (``monitor_name`` defaults to ``policy``).
+    ``by_group=True`` adds a fourth return value (whatever the output paths): per group its load and, [episodes, G] each, the
+    mean blocking rates with their standard error over the group's seeds, formed from ``reduce_counters(by_group=True)``.
+    Both need every group to be one load (``ValueError`` otherwise)."""
     B = env.batch_size
+    if monitor_dir is not None or by_group:
+        _traffic.group_loads(env.loads, env.groups, env.num_groups)   # (every group one load, before anything runs)
     t0 = time.time()
+    grouped = []
     rewards, lengths = [], []
     infos: Dict[str, List[np.ndarray]] = {k: [] for k in info_keywords}
     rows = []
@@ -56,6 +113,8 @@ def evaluate_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, moni
             active &= ~out["done"][-1].astype(bool)
         assert not active.any(), "episode did not finish on every env"
         c = env.counters()
+        if by_group:
+            grouped.append(env.reduce_counters(by_group=True))
         nxt = env.requests()["bit_rate"].astype(np.int64)
         # the Monitor logs the info of the episode's last step, built before the next request is generated
         proc, eproc = c["services_processed"] - 1, c["episode_services_processed"] - 1
@@ -74,6 +133,12 @@ def evaluate_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, moni
             rows.append(row)
     if monitor_path is not None:
         write_monitor_csv(monitor_path, rows, env_id, info_keywords, t_start=t0)
+    if monitor_dir is not None:
+        write_monitor_tree(monitor_dir, monitor_name or policy, rows, env.groups,
+                           _traffic.group_loads(env.loads, env.groups, env.num_groups), env.episode_length, env_id,
+                           info_keywords, t_start=t0)
+    if by_group:
+        return np.stack(rewards), np.stack(lengths), {k: np.stack(v) for k, v in infos.items()}, _by_group_summary(env, grouped)
     return np.stack(rewards), np.stack(lengths), {k: np.stack(v) for k, v in infos.items()}
 
 
@@ -86,14 +151,19 @@ PHY_INFO_KEYWORDS = ("episode_service_blocking_rate", "service_blocking_rate", "
 
 def evaluate_phy_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, monitor_path: Optional[str] = None,
                                    env_id: str = "PhyRMSA-v0", info_keywords: Sequence[str] = PHY_INFO_KEYWORDS,
-                                   chunk: int = 1000):
+                                   chunk: int = 1000, monitor_dir: Optional[str] = None, monitor_name: Optional[str] = None,
+                                   by_group: bool = False):
     """``evaluate_heuristic(env, heuristic, n_eval_episodes)`` (``utils.py:124-162``) for every env of a
     :class:`BatchedPhyRMSAEnv` with a device policy, and the Monitor CSV of the reference's experiment scripts
     (``tests/test_rmsa_threads_us.py:56-126``): one row per episode with the info dict of the episode's LAST step
     (``phy_rmsa_env.py:319-348``).  ``average_mod_level`` is the true mean (the reference's accumulator wraps at 256 under
-    NumPy >= 2, SURVEY 8c caveat 2).  Returns (episode_rewards [episodes, B], episode_lengths, info arrays)."""
+    NumPy >= 2, SURVEY 8c caveat 2).  Returns (episode_rewards [episodes, B], episode_lengths, info arrays).
+    ``monitor_dir`` / ``monitor_name`` / ``by_group``: the per-load tree and the summary, as :func:`evaluate_heuristic_batched`."""
     B = env.batch_size
+    if monitor_dir is not None or by_group:
+        _traffic.group_loads(env.loads, env.groups, env.num_groups)   # (every group one load, before anything runs)
     t0 = time.time()
+    grouped = []
     rewards, lengths = [], []
     infos: Dict[str, List[np.ndarray]] = {k: [] for k in info_keywords}
     rows = []
@@ -110,6 +180,8 @@ def evaluate_phy_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, 
         ep_r += last["accepted"][0]
         assert last["done"][0].all(), "episode did not finish on every env"
         c = env.counters()
+        if by_group:
+            grouped.append(env.reduce_counters(by_group=True))
         nxt = env.requests()["bit_rate"].astype(np.int64)
         proc, eproc = c["services_processed"] - 1, c["episode_services_processed"] - 1
         req, ereq = c["bit_rate_requested"] - nxt, c["episode_bit_rate_requested"] - nxt
@@ -139,4 +211,10 @@ def evaluate_phy_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, 
             rows.append(row)
     if monitor_path is not None:
         write_monitor_csv(monitor_path, rows, env_id, info_keywords, t_start=t0)
+    if monitor_dir is not None:
+        write_monitor_tree(monitor_dir, monitor_name or policy, rows, env.groups,
+                           _traffic.group_loads(env.loads, env.groups, env.num_groups), env.episode_length, env_id,
+                           info_keywords, t_start=t0)
+    if by_group:
+        return np.stack(rewards), np.stack(lengths), {k: np.stack(v) for k, v in infos.items()}, _by_group_summary(env, grouped)
     return np.stack(rewards), np.stack(lengths), {k: np.stack(v) for k, v in infos.items()}

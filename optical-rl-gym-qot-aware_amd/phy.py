@@ -17,7 +17,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .batched import COUNTER_NAMES, REQUEST_DTYPE, _check_buffer, _ptr
+from .batched import COUNTER_NAMES, REQUEST_DTYPE, SweepTraffic, _check_buffer, _grouped_counters, _ptr
 from .topology import FrozenTopology, selection_tables
 
 PHY_DEFAULT_BIT_RATES = (100, 200, 300, 400, 500, 600)  # phy_rmsa_env.py:38
@@ -101,7 +101,7 @@ class BatchedPhyRMSAEnv:
                  defrag_period=None, number_moves=None, metric: str = "cut", grooming: bool = False,
                  queue_capacity: int = 0, channel_state_capacity: int = 0, defrag_capacity: int = 0, device: int = 0,
                  gn_gate=None, bit_rate_selection: str = "discrete", bit_rate_lower_bound=25.0,
-                 bit_rate_higher_bound=100.0, **_ignored):
+                 bit_rate_higher_bound=100.0, groups=None, num_groups=None, **_ignored):
         if defrag_period and number_moves is None:
             raise ValueError("defrag_period needs number_moves (the reference compares against it, phy_rmsa_env.py:358)")
         # bit_rate_selection="continuous" (phy_rmsa_env.py:79-86, 114-134): rng.randint(lower, higher) per request, checked
@@ -113,6 +113,8 @@ class BatchedPhyRMSAEnv:
             self.bit_rate_lower_bound, self.bit_rate_higher_bound = bounds
             bit_rates = range(bounds[0], bounds[1] + 1)
             bit_rate_probabilities = None
+        # load= / mean_service_holding_time= may be length-B array-likes (a load sweep in one handle, traffic.py)
+        self.traffic = SweepTraffic(batch_size, load, mean_service_holding_time, groups, num_groups)
         self.L = _lib.load()
         self.topology = FrozenTopology.from_graph(topology)
         t = self.topology
@@ -129,7 +131,11 @@ class BatchedPhyRMSAEnv:
         else:
             self.num_channels = number_spectrum_channels
         self.load, self.mean_service_holding_time = load, mean_service_holding_time
-        self.mean_service_inter_arrival_time = 1 / float(load / float(mean_service_holding_time))
+        if self.traffic.per_env:
+            self.mean_service_inter_arrival_time = 1 / self.traffic.arrival_lambda
+        else:
+            self.mean_service_inter_arrival_time = 1 / float(load / float(mean_service_holding_time))
+        self.loads, self.groups, self.num_groups = self.traffic.loads, self.traffic.groups, self.traffic.num_groups
         self.node_request_probabilities, src_cum, dst_cum, br_cum = selection_tables(
             node_request_probabilities, bit_rate_probabilities, t.num_nodes, self.bit_rates)
         self.rand_seed = 41 if seed is None else int(seed)
@@ -162,8 +168,12 @@ class BatchedPhyRMSAEnv:
         cc.defrag_period, cc.number_moves = int(defrag_period or 0), int(number_moves or 0)
         cc.defrag_metric, cc.defrag_capacity = (0 if metric == "cut" else 1), int(defrag_capacity)
         self.defrag_period, self.number_moves, self.metric = defrag_period, number_moves, metric
-        cc.arrival_lambda = 1 / self.mean_service_inter_arrival_time
-        cc.holding_lambda = 1 / self.mean_service_holding_time
+        if self.traffic.per_env:   # (ignored by orlg_phy_create_traffic; the pair of the largest load, for the record)
+            cc.arrival_lambda = self.traffic.arrival_lambda[self.traffic.largest()]
+            cc.holding_lambda = self.traffic.holding_lambda[self.traffic.largest()]
+        else:
+            cc.arrival_lambda = 1 / self.mean_service_inter_arrival_time
+            cc.holding_lambda = 1 / self.mean_service_holding_time
         cc.bit_rates = keep(self.bit_rates, np.int32)
         cc.bit_rate_cum = None if self.continuous else keep(br_cum, np.float64)   # NULL: continuous (include/orlg.h)
         cc.src_cum = keep(src_cum, np.float64)
@@ -199,10 +209,17 @@ class BatchedPhyRMSAEnv:
         seeds_ptr = None
         if seeds is not None:
             seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+            if seeds.shape != (self.batch_size,):
+                raise ValueError(f"seeds: shape {seeds.shape}, expected ({self.batch_size},)")
             seeds_ptr = seeds.ctypes.data_as(C.c_void_p)
         h = C.c_void_p()
-        _lib.check(self.L.orlg_phy_create(C.byref(ct), C.byref(cc), self.batch_size, seeds_ptr,
-                                          C.c_uint64(self.rand_seed), int(device), C.byref(h)))
+        if self.traffic.per_env:
+            tr = self.traffic.struct()
+            _lib.check(self.L.orlg_phy_create_traffic(C.byref(ct), C.byref(cc), self.batch_size, seeds_ptr,
+                                                      C.c_uint64(self.rand_seed), int(device), C.byref(tr), C.byref(h)))
+        else:
+            _lib.check(self.L.orlg_phy_create(C.byref(ct), C.byref(cc), self.batch_size, seeds_ptr,
+                                              C.c_uint64(self.rand_seed), int(device), C.byref(h)))
         self.h = h
         self.words_per_link = self.L.orlg_phy_words_per_link(self.h)
         self.node_vectors = bool(self.L.orlg_phy_node_vectors(self.h))   # cut metric through node-degree vectors (include/orlg.h)
@@ -409,7 +426,17 @@ class BatchedPhyRMSAEnv:
         assert buf.size == self.L.orlg_phy_state_size(self.h), "snapshot of a differently configured batch"
         _lib.check(self.L.orlg_phy_load_state(self.h, _ptr(buf)))
 
-    def reduce_counters(self):
+    def traffic_rates(self):
+        """(arrival_lambda [B], holding_lambda [B], group [B]) as the handle holds them."""
+        B = self.batch_size
+        a, h, g = np.zeros(B), np.zeros(B), np.zeros(B, np.int32)
+        _lib.check(self.L.orlg_phy_get_traffic(self.h, _ptr(a), _ptr(h), _ptr(g)))
+        return a, h, g
+
+    def reduce_counters(self, by_group: bool = False):
+        """As ``BatchedRMSAEnv.reduce_counters``; ``by_group=True`` returns the sums per group, [G, 16] int64."""
+        if by_group:
+            return _grouped_counters(self.L.orlg_phy_reduce_counters_grouped, self.h, self.num_groups)
         a = np.zeros(16, np.int64)
         _lib.check(self.L.orlg_phy_reduce_counters(self.h, _ptr(a)))
         d = {n: int(a[i]) for i, n in enumerate(COUNTER_NAMES)}
