@@ -443,7 +443,13 @@ int orlg_phy_reduce_counters_grouped(orlg_phy_env *env, int64_t *out /* [num_gro
  * running on it link_svc_off[l].. in list order (svc_is_self marks the entry that is the current service itself: the
  * reference adds a stale phi for it, calculate_osnr.py:31-46).  Units: Hz, W, km, 1/m (attenuation_normalized),
  * linear noise figure.  Result: GSNR in dB.  Arrays may be host or device pointers.  Orphaned in the reference
- * (no caller / test): parity is pinned only by tests/golden/osnr_grid.npz.
+ * (no caller / test): parity is pinned only by tests/golden/osnr_grid.npz and, at the edges of the kernel, by the
+ * 50-digit values of tests/golden/osnr_edges.npz.
+ * The caller's contract -- the entry point checks the four sizes only and the kernel follows the offsets as given: every
+ * offset array starts at 0, ascends and ends at the count of the array it indexes; the arrays of one family have one
+ * length; svc_se of an entry that is not the service itself is 1..6; a link's list holds at most one self entry; no other
+ * entry has the center_frequency of a check that walks its link (the routine divides by their distance).  The Python
+ * wrapper gn_osnr() refuses a batch that breaks any of these with ValueError before it loads the library.
  */
 typedef struct orlg_osnr_batch {
     int32_t num_checks, num_links, num_spans, num_services;

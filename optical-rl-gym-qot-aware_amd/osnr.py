@@ -26,8 +26,60 @@ class OsnrBatch(C.Structure):
                [(n, C.c_void_p) for n, _ in FIELDS]
 
 
+def validate_batch(batch):
+    """Raise ``ValueError`` for a batch the kernel must not be given (the caller's contract of ``orlg_gn_osnr`` in
+    ``include/orlg.h``): the device follows the offsets without checking them, and the routine is undefined for an interferer
+    on the service's own frequency (division by ``|f - fc| = 0``), for two own entries in one list and for a spectral
+    efficiency outside the six the modulation-factor table has.  Pure numpy: runs before the library is loaded."""
+    a = {name: np.asarray(batch[name]) for name, _ in FIELDS}
+    for name in a:
+        if a[name].ndim != 1:
+            raise ValueError(f"{name} must be one-dimensional, got shape {a[name].shape}")
+    for fam in (("bandwidth", "center_frequency", "launch_power"), ("span_length_km", "span_attenuation", "span_noise_figure"),
+                ("svc_bandwidth", "svc_center_frequency", "svc_se", "svc_is_self"), ("link_span_off", "link_svc_off")):
+        sizes = {n: a[n].size for n in fam}
+        if len(set(sizes.values())) != 1:
+            raise ValueError("arrays of one family differ in length: " + ", ".join(f"{n}={s}" for n, s in sizes.items()))
+    num_links = a["link_span_off"].size - 1
+    if num_links < 0:
+        raise ValueError("link_span_off and link_svc_off are empty: offset arrays hold one entry more than they have ranges")
+    if a["check_link_off"].size != a["bandwidth"].size + 1:
+        raise ValueError(f"check_link_off has {a['check_link_off'].size} entries for {a['bandwidth'].size} checks: "
+                         "offset arrays hold one entry more than they have ranges")
+    for name, end, what in (("check_link_off", num_links, "links"), ("link_span_off", a["span_length_km"].size, "spans"),
+                            ("link_svc_off", a["svc_bandwidth"].size, "list entries")):
+        off = a[name].astype(np.int64)
+        if off[0] != 0:
+            raise ValueError(f"{name} does not start at 0 (starts at {off[0]})")
+        if np.any(np.diff(off) < 0):
+            raise ValueError(f"{name} does not ascend (at index {int(np.argmax(np.diff(off) < 0)) + 1})")
+        if off[-1] != end:
+            raise ValueError(f"{name} ends at {off[-1]}, not at the number of {what} ({end})")
+    own = a["svc_is_self"] != 0
+    se = a["svc_se"]
+    bad = ~own & ((se < 1) | (se > 6))
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(f"svc_se outside 1..6: svc_se[{i}] = {se[i]}")
+    svc_off = a["link_svc_off"].astype(np.int64)
+    own_before = np.concatenate(([0], np.cumsum(own)))
+    own_per_link = own_before[svc_off[1:]] - own_before[svc_off[:-1]]
+    if np.any(own_per_link > 1):
+        l = int(np.argmax(own_per_link > 1))
+        raise ValueError(f"more than one self entry in the list of link {l} ({int(own_per_link[l])})")
+    link_of_svc = np.repeat(np.arange(num_links), np.diff(svc_off))
+    check_of_link = np.repeat(np.arange(a["bandwidth"].size), np.diff(a["check_link_off"].astype(np.int64)))
+    same = ~own & (a["svc_center_frequency"] == a["center_frequency"][check_of_link[link_of_svc]])
+    if same.any():
+        i = int(np.argmax(same))
+        raise ValueError(f"a non-self entry sits on the center_frequency of its check: svc_center_frequency[{i}] = "
+                         f"{a['svc_center_frequency'][i]} (link {int(link_of_svc[i])}, check {int(check_of_link[link_of_svc[i]])})")
+
+
 def gn_osnr(batch, device: int = 0, stream_ptr=None):
-    """GSNR [dB] per admission check; numpy arrays in, numpy array out (computed on the GPU)."""
+    """GSNR [dB] per admission check; numpy arrays in, numpy array out (computed on the GPU).  A malformed batch
+    (:func:`validate_batch`) raises ``ValueError`` before anything is launched."""
+    validate_batch(batch)
     L = _lib.load()
     L.orlg_gn_osnr.argtypes = [C.POINTER(OsnrBatch), C.c_void_p, C.c_int32, C.c_void_p]
     b = OsnrBatch()

@@ -524,3 +524,53 @@ def gn_osnr(arrays):
     out = np.zeros(b.num_checks)
     L.orc_gn_osnr(C.byref(b), _ptr(out))
     return out
+
+
+def gn_osnr_mp(arrays, checks=None, dps=50):
+    """The same routine in ``mpmath`` at ``dps`` digits, rounded once to float64: what the float64 formula of
+    orlg_oracle_osnr.c would give in exact arithmetic (TEST INFRASTRUCTURE; needs mpmath, which tests import-or-skip).
+
+    Sequential like the routine itself: ``phi`` starts at 0 per check, is recomputed for every list entry that is not the
+    service itself and is added for EVERY entry -- the stale value for the service's own entry -- and survives spans and
+    links.  Every input and every constant (pi and the modulation factors included) is taken at its exact float64 value, so
+    the result is a function of the float64 inputs alone.  ``checks``: indices to evaluate (default all).  The two inverse
+    hyperbolic sines of an interferer depend on the span only through its attenuation; they are kept per (list entry,
+    attenuation) within a link, which changes nothing at ``dps`` digits and spares most of the time."""
+    import mpmath as mp
+    a = {name: np.ascontiguousarray(arrays[name], dtype=dt) for name, dt in OSNR_FIELDS}
+    idx = range(len(a["bandwidth"])) if checks is None else checks
+    out = np.zeros(len(idx))
+    with mp.workdps(dps):
+        f = mp.mpf
+        beta_2, gamma, h_plank, pi = f(21.3e-27), f(1.3e-3), f(6.626e-34), f(3.141592653589793)
+        pmf = [f(1.0), f(1.0), f(2.0 / 3), f(17.0 / 25), f(69.0 / 100), f(13.0 / 21)]
+        for k, m in enumerate(idx):
+            bw, fc, pw = f(float(a["bandwidth"][m])), f(float(a["center_frequency"][m])), f(float(a["launch_power"][m]))
+            acc, phi = f(0), f(0)
+            for l in range(a["check_link_off"][m], a["check_link_off"][m + 1]):
+                i0, i1 = int(a["link_svc_off"][l]), int(a["link_svc_off"][l + 1])
+                sb = [f(float(x)) for x in a["svc_bandwidth"][i0:i1]]
+                df = [f(float(x)) - fc for x in a["svc_center_frequency"][i0:i1]]
+                own = a["svc_is_self"][i0:i1]
+                mod = [None if own[i] else pmf[int(a["svc_se"][i0 + i]) - 1] * (sb[i] / abs(df[i])) * 5 / 3 for i in range(i1 - i0)]
+                asinh_terms = {}
+                for s in range(a["link_span_off"][l], a["link_span_off"][l + 1]):
+                    att, length = f(float(a["span_attenuation"][s])), f(float(a["span_length_km"][s]))
+                    nf = f(float(a["span_noise_figure"][s]))
+                    l_eff_a = 1 / (2 * att)
+                    l_eff = (1 - mp.exp(-2 * att * length * 1e3)) / (2 * att)
+                    ratio = l_eff / (length * 1e3)
+                    sum_phi = mp.asinh(pi ** 2 * beta_2 * bw ** 2 / (4 * att))
+                    for i in range(i1 - i0):
+                        if not own[i]:
+                            key = (i, float(a["span_attenuation"][s]))
+                            if key not in asinh_terms:
+                                c = pi ** 2 * beta_2 * l_eff_a * sb[i]
+                                asinh_terms[key] = mp.asinh(c * (df[i] + sb[i] / 2)) - mp.asinh(c * (df[i] - sb[i] / 2))
+                            phi = asinh_terms[key] - mod[i] * ratio
+                        sum_phi += phi
+                    power_nli_span = (pw / bw) ** 3 * (8 / (27 * pi * beta_2)) * gamma ** 2 * l_eff * sum_phi * bw
+                    power_ase = bw * h_plank * fc * (mp.exp(2 * att * length * 1e3) - 1) * nf
+                    acc += 1 / (pw / (power_ase + power_nli_span))
+            out[k] = float("inf") if acc == 0 else float(10 * mp.log10(1 / acc))
+    return out

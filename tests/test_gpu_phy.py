@@ -508,3 +508,168 @@ def test_phy_large_network_general_paths(policy, defrag, device_log_in_oracle):
         o.close()
     assert tr["accepted"].mean() > 0.5
     env.close()
+
+
+# ---------------------------------------------------------------------- the GN gate against the stand-alone GSNR routine
+def gate_check_as_osnr_batch(topo, tables, gate, avail, src, dst, idp, ch):
+    """One check of the in-step gate as an `orlg_osnr_batch` (include/orlg.h orlg_gn_gate): the links of path `idp` of
+    (src, dst) in path order, per link its equal spans and, as interferers, the channels it has lit other than `ch`, in
+    channel order, at the modulation level the table gives them on this path.  The service itself is in no list."""
+    pairs, mod, _ = tables
+    gid = int(topo.pair_path_base[src * topo.num_nodes + dst]) + idp
+    row = int(topo.pair_table_rows(pairs)[src * topo.num_nodes + dst])
+    cf, bw = np.asarray(gate["channel_center_frequency_hz"]), gate["channel_bandwidth_hz"]
+    b = dict(check_link_off=[0], link_span_off=[0], link_svc_off=[0], bandwidth=[bw], center_frequency=[cf[ch]],
+             launch_power=[gate["launch_power_w"]], span_length_km=[], span_attenuation=[], span_noise_figure=[],
+             svc_bandwidth=[], svc_center_frequency=[], svc_se=[], svc_is_self=[])
+    for link in topo.path_links[topo.path_link_off[gid]:topo.path_link_off[gid + 1]]:
+        ns = int(gate["link_num_spans"][link])
+        b["span_length_km"] += [float(gate["link_span_length_km"][link])] * ns
+        b["span_attenuation"] += [gate["attenuation_normalized"]] * ns
+        b["span_noise_figure"] += [gate["noise_figure"]] * ns
+        lit = np.nonzero(avail[link, :len(cf)] == 0)[0]
+        lit = lit[lit != ch]
+        b["svc_bandwidth"] += [bw] * len(lit)
+        b["svc_center_frequency"] += list(cf[lit])
+        b["svc_se"] += list(np.clip(mod[row, lit, idp].astype(np.int32), 1, 6))
+        b["svc_is_self"] += [0] * len(lit)
+        b["link_span_off"].append(len(b["span_length_km"]))
+        b["link_svc_off"].append(len(b["svc_bandwidth"]))
+    b["check_link_off"].append(len(b["link_span_off"]) - 1)
+    return b
+
+
+def concat_osnr_batches(parts):
+    out = {k: [] for k in parts[0]}
+    for k in ("check_link_off", "link_span_off", "link_svc_off"):
+        out[k] = [0]
+    for p in parts:
+        for k, v in p.items():
+            if k.endswith("_off"):
+                out[k] += [x + out[k][-1] for x in v[1:]]
+            else:
+                out[k] += list(v)
+    return out
+
+
+def replay_gate_checks(policy, n, batch=4):
+    """Run the gated step on the device, replay the oracle next to it step by step for the occupancy BEFORE each step, and
+    return, per step that ran the check, the check as a batch of the stand-alone routine and the GSNR the device's step wrote.
+    The step checks the chosen channels in order and stops at the first that misses its level: the value it reports belongs to
+    that channel, or to the last one."""
+    import oracle as orc
+    from optical_rl_gym_amd import gn_gate_parameters
+    topo, tables = load_topology("us14_3-paths_6-modulations"), load_phy_tables("us14_k3")
+    gate = gn_gate_parameters(topo)
+    kw = dict(load=1400, mean_service_holding_time=25, episode_length=200, seed=10, grooming=False, gn_gate=gate)
+    env = make_env(topo, tables, kw, batch)
+    tr = env.run(policy, n, outputs=("act_path", "channels", "accepted", "gn_gsnr_db"), auto_reset=True)
+    assert env.last_kernel().startswith("orlg_phy_kernel<5,false,true,"), env.last_kernel()
+    env.close()
+    checks, step_values = [], []
+    for i in range(batch):
+        o = phy_oracle_from_kwargs(topo, tables, kw, seed=10 + i)
+        for t in range(n):
+            req, avail = o.request(), o.available_channels()
+            a = o.policy(policy)
+            r = o.step(a)
+            assert a.path == tr["act_path"][t, i] and r.accepted == tr["accepted"][t, i], (i, t)
+            assert np.isnan(r.gn_gsnr_db) == np.isnan(tr["gn_gsnr_db"][t, i]), (i, t)
+            if not np.isnan(r.gn_gsnr_db):
+                assert list(a.ch[:a.n]) == list(tr["channels"][t, i, :a.n]), (i, t)
+                last = None
+                for q in range(a.n):
+                    last = gate_check_as_osnr_batch(topo, tables, gate, avail, req.src, req.dst, a.path, a.ch[q])
+                    if (orc.gn_osnr(last)[0] >= gate["thresholds_db"]).sum() < a.cap[q]:
+                        break
+                # the flattening above is the oracle's own: its stand-alone routine gives the bits its step reported
+                assert orc.gn_osnr(last)[0] == r.gn_gsnr_db, (i, t)
+                checks.append(last)
+                step_values.append(tr["gn_gsnr_db"][t, i])
+            if r.done:
+                o.reset(True)
+        o.close()
+    return checks, np.array(step_values)
+
+
+@pytest.mark.parametrize("policy", ["bmfa", "sapff"])
+def test_gn_gate_equals_the_standalone_routine(policy, device_log_in_oracle):
+    """gn_gsnr<W> inside the step (orlg_phy_kernels.hip) and orlg_gn_osnr (orlg_osnr.hip) state the same arithmetic: for
+    every checked step of 4 environments x 300 steps the stand-alone routine, given the step's path, occupancy and gate
+    parameters as a batch without a self entry, must give the step's gn_gsnr_db to rtol 1e-12."""
+    from optical_rl_gym_amd import gn_osnr
+    checks, step_values = replay_gate_checks(policy, 300)
+    assert len(checks) >= 50
+    entries = [len(c["svc_bandwidth"]) for c in checks]
+    assert max(entries) > 64      # (lists of more than one lane round are among them)
+    got = gn_osnr(concat_osnr_batches(checks))
+    print(f"{policy}: {len(checks)} checks, lists of up to {max(entries)} entries, routine vs step worst relative "
+          f"{np.max(np.abs(got - step_values) / np.abs(step_values)):.2e}")
+    np.testing.assert_allclose(got, step_values, rtol=1e-12, atol=0)
+
+
+def test_gn_gate_against_50_digits(device_log_in_oracle):
+    """A handful of the step's own GSNR values against the routine at 50 digits (the checks with the shortest lists that have
+    an interferer on every link)."""
+    pytest.importorskip("mpmath")
+    import oracle as orc
+    checks, step_values = replay_gate_checks("bmfa", 60)
+    full = [k for k, c in enumerate(checks) if np.all(np.diff(c["link_svc_off"]) > 0)]
+    picked = sorted(full, key=lambda k: len(checks[k]["svc_bandwidth"]))[:4] + full[-4:]
+    assert len(picked) == 8
+    want = orc.gn_osnr_mp(concat_osnr_batches([checks[k] for k in picked]))
+    print("step vs 50 digits, worst relative", np.max(np.abs(step_values[picked] - want) / np.abs(want)))
+    np.testing.assert_allclose(step_values[picked], want, rtol=1e-12, atol=0)
+
+
+# loads and step counts chosen on the oracle alone (CPU): within n steps the gate refuses > 100 and passes > 30 % of the
+# services for both policies, and some environment lights the top channel, so every occupancy word of a link carries
+# interferers.  (At 1400 Erlang and a few hundred steps nothing above channel ~160 is ever lit.)
+GATE_WORD_COUNTS = [(64, (10, 44), 1, 1400, 600), (65, (10, 45), 2, 1400, 600), (128, (20, 88), 2, 4000, 1500),
+                    (129, (20, 89), 3, 4000, 1500), (193, (40, 113), 4, 20000, 1500), (256, (80, 96), 4, 20000, 1500),
+                    (268, (80, 108), 5, 20000, 1500)]
+
+
+@pytest.mark.parametrize("policy", ["bmfa", "sapff"])
+@pytest.mark.parametrize("num_channels,split,words,load,n", GATE_WORD_COUNTS)
+def test_gn_gate_at_every_word_count(num_channels, split, words, load, n, policy, device_log_in_oracle):
+    """The gate's code depends on the occupancy words per link W in four unrolled loops and in the mask of the last word's
+    channels that do not exist: the GN variant of the step kernel against the oracle at W = 1..5, channel counts on and next
+    to the word boundaries, the QoT tables cut to their first C columns.  Decisions, counters and occupancy exactly, the GSNR
+    to rtol 1e-9 as test_gn_gate_in_the_step_vs_oracle states."""
+    from optical_rl_gym_amd import gn_gate_parameters
+    topo, tables = load_topology("us14_3-paths_6-modulations"), load_phy_tables("us14_k3")
+    assert 2 * split[0] + split[1] == num_channels and -(-num_channels // 64) == words
+    tables = (tables[0], np.ascontiguousarray(tables[1][:, :num_channels]), np.ascontiguousarray(tables[2][:, :num_channels]))
+    gate = gn_gate_parameters(topo, num_channels=num_channels)
+    kw = dict(load=load, mean_service_holding_time=25, episode_length=200, seed=10, grooming=False, gn_gate=gate,
+              number_spectrum_channels=split[0], number_spectrum_channels_s_band=split[1])
+    batch = 4
+    env = make_env(topo, tables, kw, batch)
+    assert env.num_channels == num_channels and env.words_per_link == words
+    tr = env.run(policy, n, outputs=("act_path", "channels", "accepted", "gn_gsnr_db", "number_cuts_total"), auto_reset=True)
+    assert env.last_kernel().startswith(f"orlg_phy_kernel<{words},false,true,"), env.last_kernel()
+    cnt, av = env.counters(), env.available_channels()
+    assert env.episode_stats()["queue_overflow"].max() == 0
+    gate_blocks, top = 0, []
+    for i in range(batch):
+        o = phy_oracle_from_kwargs(topo, tables, kw, seed=10 + i)
+        ot = o.run(policy, n, reset_on_done=True)
+        assert np.array_equal(tr["act_path"][:, i], ot["act_path"]), i
+        assert np.array_equal(tr["channels"][:, i, :12].astype(np.int32), ot["channels"]), i
+        assert np.array_equal(tr["accepted"][:, i], ot["accepted"]), i
+        assert np.array_equal(tr["number_cuts_total"][:, i], ot["number_cuts_total"]), i
+        g, og = tr["gn_gsnr_db"][:, i], ot["gn_gsnr_db"]
+        assert np.array_equal(np.isnan(g), np.isnan(og)), i
+        np.testing.assert_allclose(g[~np.isnan(g)], og[~np.isnan(og)], rtol=1e-9, atol=0)
+        assert np.array_equal(av[i], o.available_channels()), i
+        oc = o.counters()
+        for name in oc:
+            assert cnt[name][i] == oc[name], (name, i)
+        gate_blocks += int(((ot["act_path"] >= 0) & (ot["act_path"] < 10) & (ot["accepted"] == 0)).sum())
+        top.append(int(ot["channels"][(ot["accepted"] == 1) & (ot["act_path"] < 10)].max()))
+        o.close()
+    assert gate_blocks > 100               # the gate binds ...
+    assert tr["accepted"].mean() > 0.3     # ... and passes
+    assert max(top) == num_channels - 1 and min(top) >= 64 * (words - 1), top    # the last word is lit in every environment
+    env.close()
