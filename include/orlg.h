@@ -437,6 +437,52 @@ int orlg_phy_get_traffic(orlg_phy_env *env, double *arrival_lambda, double *hold
 int orlg_phy_num_groups(orlg_phy_env *env);
 int orlg_phy_reduce_counters_grouped(orlg_phy_env *env, int64_t *out /* [num_groups][16], host or device */);
 
+/* ---- request traces: a handle that replays caller-supplied requests instead of generating its own (SURVEY section 8(d):
+ * "requests replayed from a pre-generated trace").  Environment i serves request 0, 1, 2, ... of row i; the rest of the step --
+ * policies, provisioning, releases, statistics, outputs -- is the step of a generated handle, on every step kernel.
+ * length: n >= 2 requests per environment.  arrival (absolute arrival time), holding: [B][n] float64, env-major; src, dst,
+ * bit_rate: [B][n] int32, bit_rate the rate's VALUE.  group [B] / num_groups: as in orlg_traffic, group == NULL = one group.
+ * All host arrays, copied before the call returns.  The library checks every entry and refuses the trace with
+ * ORLG_ERR_INVALID -- environment and index in orlg_last_error() -- unless: times are finite, arrivals >= 0 and non-decreasing
+ * per environment, holdings >= 0; src != dst, both below num_nodes (every such pair has its k paths, or the topology is
+ * refused); bit_rate is one of cfg->bit_rates (continuous: inside lower .. higher); n >= 2.
+ * cfg->arrival_lambda / holding_lambda are ignored and there are no seeds: the handle has no generator, orlg_reseed returns
+ * ORLG_ERR_INVALID.  A recorded arrival or holding time comes back from the step with the bits it went in with.
+ * Device footprint: the trace lies on the device in the ring's layout, 20 bytes per request (arrival f64, holding f64,
+ * src | dst << 8 | rate index << 16): 20 * B * n bytes, 1.3 GB at B = 65 536, n = 1001.
+ * Position: a step serves the pending request and draws the next one, every environment exactly one per step, so the position
+ * (requests drawn so far) is one number for the batch.  Creation and a full reset draw request 0: position 1; n requests allow
+ * n - 1 steps.  orlg_step / orlg_phy_step(_ex) whose n_steps would draw past the end returns ORLG_ERR_INVALID before anything
+ * is launched; the state is untouched.  reset(only_episode_counters = 0) rewinds to request 0; reset(1) and auto_reset leave the
+ * position alone.
+ * Saved state: the trace is configuration (as the rates of orlg_traffic), the position is state -- a trace handle's blob ends
+ * (PhyRMSA continuous: before the float64 shares) in 16 bytes, position and length; it loads into a handle created with the
+ * same trace and continues identically.  The blob of a handle without a trace is what it was.
+ * Everything sized "from the load" (queue_capacity = 0, channel_state_capacity = 0, and with them the group kernel's LDS per
+ * environment and the defragmentation work list) is sized from the trace: one host sweep finds the largest number of requests
+ * simultaneously inside [arrival, arrival + holding] over all environments, an upper bound on the running services -- a trace
+ * handle with queue_capacity = 0 never reports ORLG_ERR_QUEUE_FULL for its release queue.  orlg_create_trace clamps that bound
+ * by what the spectrum holds (num_links * num_slots / 2 services); orlg_phy_create_trace does not (services on the virtual
+ * layer share channels).  A bound beyond the queue's limit (4096 / 8192 slots) is refused with ORLG_ERR_INVALID at creation.
+ * orlg_load_state / orlg_phy_load_state check the position's 16 bytes in the caller's buffer first: a snapshot of another
+ * trace length returns ORLG_ERR_INVALID and nothing is loaded. */
+typedef struct orlg_trace {
+    int64_t length;
+    const double *arrival, *holding;
+    const int32_t *src, *dst, *bit_rate;
+    const int32_t *group;
+    int32_t num_groups;
+} orlg_trace;
+int orlg_create_trace(const orlg_topology *topo, const orlg_rmsa_config *cfg, int32_t batch, int32_t device,
+                      const orlg_trace *trace, orlg_env **out);
+int orlg_phy_create_trace(const orlg_topology *topo, const orlg_phy_config *cfg, int32_t batch, int32_t device,
+                          const orlg_trace *trace, orlg_phy_env **out);
+/* requests per environment of the handle's trace (0: the handle generates its traffic) and requests drawn so far */
+int64_t orlg_trace_length(orlg_env *env);
+int64_t orlg_trace_position(orlg_env *env);
+int64_t orlg_phy_trace_length(orlg_phy_env *env);
+int64_t orlg_phy_trace_position(orlg_phy_env *env);
+
 /* ------------------------------------------------------------------------------------------------
  * GN-model GSNR admission check: calculate_osnr (examples/calculate_osnr.py:9-56) for a flattened batch of checks.
  * Check m walks links check_link_off[m]..check_link_off[m+1]; link l has spans link_span_off[l].. and the services

@@ -1,4 +1,4 @@
-from . import _lib, envs, traffic
+from . import _lib, envs, trace, traffic
 from ._lib import OrlgError
 from .batched import DEFAULT_BIT_RATES, BatchedDeepRMSAEnv, BatchedRMSAEnv
 from .envs import (DeepRMSAEnv, PathOnlyFirstFitAction, RMSAEnv, SimpleMatrixObservation, deeprmsa_shortest_available_path_first_fit,
@@ -12,6 +12,7 @@ from .phy_env import (PhyRMSAEnv, phy_aware_bmfa_rmsa, phy_aware_bmfa_rss_rmsa, 
                       sapff_rmsa, use_existing_channels)
 from .registry import ENV_IDS, env_class, make, register_with_gym
 from .sweep import make_sweep
+from .trace import RequestTrace, TraceError, record_trace
 from .topology import FrozenTopology, Modulation, Path, Service, TopologyView, selection_tables
 
 __all__ = ["ENV_IDS", "env_class", "make", "register_with_gym", "FrozenTopology", "Modulation", "Path", "Service", "TopologyView", "selection_tables",
@@ -19,4 +20,4 @@ __all__ = ["ENV_IDS", "env_class", "make", "register_with_gym", "FrozenTopology"
            "RMSAEnv", "DeepRMSAEnv", "SimpleMatrixObservation", "PathOnlyFirstFitAction", "shortest_path_first_fit", "shortest_available_path_first_fit",
            "least_loaded_path_first_fit", "deeprmsa_shortest_path_first_fit",
            "deeprmsa_shortest_available_path_first_fit", "random_policy", "evaluate_heuristic",
-           "traffic", "make_sweep", "write_monitor_tree"]
+           "traffic", "make_sweep", "write_monitor_tree", "trace", "RequestTrace", "TraceError", "record_trace"]

@@ -57,6 +57,11 @@ class Traffic(C.Structure):   # include/orlg.h orlg_traffic
                 ("num_groups", C.c_int32)]
 
 
+class Trace(C.Structure):   # include/orlg.h orlg_trace
+    _fields_ = [("length", C.c_int64), ("arrival", C.c_void_p), ("holding", C.c_void_p), ("src", C.c_void_p),
+                ("dst", C.c_void_p), ("bit_rate", C.c_void_p), ("group", C.c_void_p), ("num_groups", C.c_int32)]
+
+
 class PhyConfig(C.Structure):
     _fields_ = [("num_channels", C.c_int32), ("episode_length", C.c_int32), ("num_bit_rates", C.c_int32),
                 ("k_table", C.c_int32), ("num_table_rows", C.c_int32), ("queue_capacity", C.c_int32),
@@ -172,6 +177,12 @@ def load(build_if_missing=True):
         getattr(L, name).argtypes = [vp]
     for name in ("orlg_reduce_counters_grouped", "orlg_phy_reduce_counters_grouped"):
         getattr(L, name).argtypes = [vp, vp]
+    # request traces (include/orlg.h orlg_trace)
+    L.orlg_create_trace.argtypes = [C.POINTER(Topology), C.POINTER(RmsaConfig), i32, i32, C.POINTER(Trace), C.POINTER(vp)]
+    L.orlg_phy_create_trace.argtypes = [C.POINTER(Topology), C.POINTER(PhyConfig), i32, i32, C.POINTER(Trace), C.POINTER(vp)]
+    for name in ("orlg_trace_length", "orlg_trace_position", "orlg_phy_trace_length", "orlg_phy_trace_position"):
+        getattr(L, name).argtypes = [vp]
+        getattr(L, name).restype = i64
     L.orlg_host_log.argtypes = [C.c_double]
     L.orlg_host_log.restype = C.c_double
     _lib = L
@@ -194,6 +205,8 @@ EXPORTED_SYMBOLS = [
     "orlg_phy_continuous", "orlg_phy_step_ex", "orlg_phy_get_channel_state_f64", "orlg_phy_load_state_checked",
     "orlg_create_traffic", "orlg_get_traffic", "orlg_num_groups", "orlg_reduce_counters_grouped",
     "orlg_phy_create_traffic", "orlg_phy_get_traffic", "orlg_phy_num_groups", "orlg_phy_reduce_counters_grouped",
+    "orlg_create_trace", "orlg_trace_length", "orlg_trace_position",
+    "orlg_phy_create_trace", "orlg_phy_trace_length", "orlg_phy_trace_position",
 ]
 
 

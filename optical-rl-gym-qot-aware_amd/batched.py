@@ -11,7 +11,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from . import _lib, traffic as _traffic
+from . import _lib, trace as _trace, traffic as _traffic
 from .topology import FrozenTopology, selection_tables
 
 DEFAULT_BIT_RATES = (200, 250, 300, 350, 400, 450, 500, 550, 600, 650, 700, 750, 800, 850, 900, 950, 1000, 1050,
@@ -104,14 +104,21 @@ def _check_buffer(name, a, shape, dtype):
 
 
 class BatchedRMSAEnv:
-    def __init__(self, topology, batch_size: int, *, episode_length: int = 1000, load: float = 10,
-                 mean_service_holding_time: float = 10800.0, num_spectrum_resources: int = 100,
+    def __init__(self, topology, batch_size: int, *, episode_length: int = 1000, load: float = None,
+                 mean_service_holding_time: float = None, num_spectrum_resources: int = 100,
                  bit_rate_selection: str = "discrete", bit_rates: Sequence[int] = DEFAULT_BIT_RATES,
                  bit_rate_probabilities=None, node_request_probabilities=None, seed: Optional[int] = None,
                  seeds=None, allow_rejection: bool = False, channel_width: float = 12.5, j: int = 1,
                  reward_mode: int = 0, stats_level: str = "full", queue_capacity: int = 0, device: int = 0,
                  step_kernel: str = "auto", bit_rate_lower_bound=25, bit_rate_higher_bound=100, groups=None,
-                 num_groups=None):
+                 num_groups=None, trace=None):
+        # trace=: the handle replays a RequestTrace (trace.py) instead of generating its traffic; the arguments that describe
+        # generated traffic cannot be passed with it.  groups= stays: it feeds reduce_counters(by_group=True)
+        _trace.check_trace_kwargs(trace, dict(load=load, mean_service_holding_time=mean_service_holding_time, seed=seed,
+                                              seeds=seeds))
+        self.trace = trace
+        load = 10 if load is None else load                                                      # rmsa_env.py:31-32
+        mean_service_holding_time = 10800.0 if mean_service_holding_time is None else mean_service_holding_time
         if bit_rate_selection not in ("continuous", "discrete"):   # rmsa_env.py:74
             raise ValueError("bit_rate_selection must be 'continuous' or 'discrete'")
         self.bit_rate_selection = bit_rate_selection
@@ -125,10 +132,17 @@ class BatchedRMSAEnv:
             self.bit_rate_lower_bound, self.bit_rate_higher_bound = lo, hi
             bit_rates, bit_rate_probabilities = list(range(lo, hi + 1)), None
         # load= / mean_service_holding_time= may be length-B array-likes (a load sweep in one handle, traffic.py)
-        self.traffic = SweepTraffic(batch_size, load, mean_service_holding_time, groups, num_groups)
-        self.L = _lib.load()
+        self.traffic = SweepTraffic(batch_size, load, mean_service_holding_time, None if trace is not None else groups,
+                                    None if trace is not None else num_groups)
         self.topology = FrozenTopology.from_graph(topology)
         t = self.topology
+        if trace is not None:   # checked before the library is loaded: the rules of orlg_create_trace
+            self.trace = trace = trace.for_batch(batch_size)
+            trace.validate(num_nodes=t.num_nodes, **({"bit_rate_bounds": (bit_rates[0], bit_rates[-1])}
+                                                     if bit_rate_selection == "continuous" else {"bit_rates": bit_rates}))
+            self.traffic.groups, self.traffic.num_groups = _trace.trace_groups(batch_size, groups, num_groups)
+            self._trace_groups = groups is not None
+        self.L = _lib.load()
         self.batch_size = int(batch_size)
         self.episode_length = int(episode_length)
         self.num_spectrum_resources = int(num_spectrum_resources)
@@ -190,7 +204,10 @@ class BatchedRMSAEnv:
             assert seeds.shape == (self.batch_size,)
             seeds_ptr = seeds.ctypes.data_as(C.c_void_p)
         h = C.c_void_p()
-        if self.traffic.per_env:
+        if trace is not None:
+            ts = trace.struct(self.groups if self._trace_groups else None, self.num_groups)
+            _lib.check(self.L.orlg_create_trace(C.byref(ct), C.byref(cc), self.batch_size, int(device), C.byref(ts), C.byref(h)))
+        elif self.traffic.per_env:
             tr = self.traffic.struct()
             _lib.check(self.L.orlg_create_traffic(C.byref(ct), C.byref(cc), self.batch_size, seeds_ptr,
                                                   C.c_uint64(self.rand_seed), int(device), C.byref(tr), C.byref(h)))
@@ -244,7 +261,10 @@ class BatchedRMSAEnv:
         draws.  NOT the reference's ``seed()``: there the bit-rate draw stays bound to the generator object of construction time
         (``functools.partial(self.rng.choices, ...)``, ``rmsa_env.py:109-111``), so after ``env.seed(s)`` the reference takes
         inter-arrival time, holding time, source and destination from ``Random(s)`` and the bit rate from the OLD generator
-        (pinned by ``tests/golden/seed_rmsa_nsfnet_s10.npz``); here all five draws come from the new one."""
+        (pinned by ``tests/golden/seed_rmsa_nsfnet_s10.npz``); here all five draws come from the new one.  A handle that
+        replays a trace has no generator: ``ValueError``."""
+        if self.trace is not None:
+            raise ValueError("a handle that replays a trace has no generator to seed")
         if seeds is not None:
             sa = np.ascontiguousarray(seeds, np.uint64)
             if sa.shape != (self.batch_size,):
@@ -252,6 +272,16 @@ class BatchedRMSAEnv:
             _lib.check(self.L.orlg_reseed(self.h, _ptr(sa), 0))
         else:
             _lib.check(self.L.orlg_reseed(self.h, None, int(41 if seed is None else seed)))
+
+    @property
+    def trace_length(self) -> int:
+        """Requests per environment of the handle's trace, 0 for a handle that generates its traffic."""
+        return int(self.L.orlg_trace_length(self.h))
+
+    @property
+    def trace_position(self) -> int:
+        """Requests drawn so far (the same for every environment): 1 after a full reset, + 1 per step."""
+        return int(self.L.orlg_trace_position(self.h))
 
     def run(self, policy: str, n_steps: int = 1, *, actions=None, auto_reset: bool = False,
             outputs: Sequence[str] = (), out: Optional[Dict[str, object]] = None):
@@ -436,9 +466,21 @@ class BatchedDeepRMSAEnv(BatchedRMSAEnv):
     Discrete(k*j + reject), observation = per-path free-block features."""
 
     def __init__(self, topology, batch_size: int, *, j: int = 1, episode_length: int = 1000,
-                 mean_service_holding_time: float = 25.0, mean_service_inter_arrival_time: float = 0.1,
+                 mean_service_holding_time: float = None, mean_service_inter_arrival_time: float = None,
                  num_spectrum_resources: int = 100, node_request_probabilities=None, seed=None, seeds=None,
                  allow_rejection: bool = False, **extra):
+        if extra.get("trace") is not None:   # (the means describe generated traffic)
+            _trace.check_trace_kwargs(extra["trace"], dict(mean_service_holding_time=mean_service_holding_time,
+                                                           mean_service_inter_arrival_time=mean_service_inter_arrival_time,
+                                                           load=extra.get("load"), seed=seed, seeds=seeds))
+            BatchedRMSAEnv.__init__(self, topology, batch_size, episode_length=episode_length,
+                                    num_spectrum_resources=num_spectrum_resources,
+                                    node_request_probabilities=node_request_probabilities, allow_rejection=allow_rejection,
+                                    j=j, reward_mode=1, **extra)
+            return
+        mean_service_holding_time = 25.0 if mean_service_holding_time is None else mean_service_holding_time
+        if mean_service_inter_arrival_time is None:
+            mean_service_inter_arrival_time = 0.1
         # (either mean may be a length-B array-like: a load sweep, as BatchedRMSAEnv)
         if np.ndim(mean_service_holding_time) > 0 or np.ndim(mean_service_inter_arrival_time) > 0:
             mean_service_holding_time = np.asarray(mean_service_holding_time, np.float64)

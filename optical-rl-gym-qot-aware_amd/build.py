@@ -34,6 +34,7 @@ def units():
         u.append((f"orlg_inst_wave_w{w}", "orlg_inst_wave.hip", [f"-DORLG_INST_W={w}"]))
     for w in sorted(PHY_W, reverse=True):
         u.append((f"orlg_inst_phy_w{w}", "orlg_inst_phy.hip", [f"-DORLG_INST_W={w}"]))
+        u.append((f"orlg_inst_phy_trace_w{w}", "orlg_inst_phy_trace.hip", [f"-DORLG_INST_W={w}"]))
     for w in sorted(WAVE_W, reverse=True):
         u.append((f"orlg_inst_group_w{w}", "orlg_inst_group.hip", [f"-DORLG_INST_W={w}"]))
     return u

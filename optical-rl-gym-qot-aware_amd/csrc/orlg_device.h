@@ -132,4 +132,11 @@ struct OrlgParams {
     // per-environment traffic (orlg_create_traffic): [B] pairs (arrival_lambda, holding_lambda) that take the place of the two
     // scalars above, nullptr = every environment has the scalars.  Read where a refill needs it (orlg_env_rates), never kept
     const OrlgRates *rates;
+    // request trace (orlg_create_trace): [B][tr_len] each, 20 bytes per request -- absolute arrival time, holding time,
+    // src | dst << 8 | bit-rate index << 16 (the ring's own layout); nullptr = the environments generate their traffic.  A trace
+    // handle has no generator: OrlgEnvScalars::mt_idx is the index of the next request a refill copies into the ring, and the
+    // ring's first array holds absolute arrival times (refill_requests_trace_as)
+    const double *tr_arrival, *tr_holding;
+    const uint32_t *tr_req;
+    int32_t tr_len, pad_tr;
 };

@@ -370,9 +370,13 @@ DEV void row_copy8(u64 *dst, const u64 *src, int n, int gl) {
 // global pointers; OrlgParams::g_wave_bytes of such a launch ends where the ring's LDS slices would begin.
 // TRAFFIC: the handle has per-environment traffic (OrlgParams::rates).  A template argument and not a test at run time: the
 // instantiations that serve handles with the two scalars stay, instruction for instruction, what they were without the feature
-template <int W, int STATS, bool HBMQ = false, bool DEFER = false, bool TRAFFIC = false>
+// TRACE: the handle replays a request trace (OrlgParams::tr_*): a refill copies the next requests of the row's environment into
+// its ring (refill_requests_trace_as) -- no staging buffer, no lock, no round trip of generator state -- and the ring's first
+// array is the arrival time itself.  A template argument for the same reason as TRAFFIC
+template <int W, int STATS, bool HBMQ = false, bool DEFER = false, bool TRAFFIC = false, bool TRACE = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3) / 4) void orlg_rmsa_group_kernel(const OrlgParams p) {
     static_assert(!DEFER || (STATS >= 2 && !HBMQ), "the deferred link statistics belong to long launches with full statistics");
+    static_assert(!(TRACE && TRAFFIC), "a trace handle has no arrival rates");
     extern __shared__ __align__(16) unsigned char smem[];
     stage_tables(smem, p);
     const int lane = threadIdx.x & 63;
@@ -736,6 +740,18 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
                 const int src_lane = ctz64(m) & 48;
                 const int env_s = __builtin_amdgcn_readlane(env, src_lane);
                 int idx_s = __builtin_amdgcn_readlane(mt_idx, src_lane);
+                if constexpr (TRACE) {
+                    // (idx_s: the environment's cursor into its trace)
+                    const int got = refill_requests_trace_t<false>(p.tr_arrival, p.tr_holding, p.tr_req, p.ring_iat + (size_t)env_s * ORLG_RING,
+                                                                   p.ring_ht + (size_t)env_s * ORLG_RING, p.ring_req + (size_t)env_s * ORLG_RING,
+                                                                   &idx_s, p.tr_len, env_s);
+                    // the ring entries written by other lanes are read back by this wave below (as after refill_requests)
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                    wave_sync();
+                    if ((lane & 48) == src_lane) { ring_cnt = got; ring_pos = 0; mt_idx = idx_s; dry = false; }
+                    continue;
+                }
                 // the MT19937 state travels HBM -> registers -> (lock) LDS -> registers (unlock) -> HBM: the workgroup's staging
                 // buffer is held for the regeneration and the draws only, not for the HBM round trips
                 static_assert(ORLG_MT_N * 4 == 156 * 16, "MT19937 state = 156 rows of 16 bytes");
@@ -781,7 +797,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
                 r_iat = p.ring_iat[ro]; r_ht = p.ring_ht[ro]; rq = p.ring_req[ro];
             }
             if (act) {
-                const double at = current_time + r_iat;
+                const double at = TRACE ? r_iat : current_time + r_iat;   // (a trace's ring holds the arrival time itself)
                 ring_pos += 1; ring_cnt -= 1;
                 current_time = at;
                 req_src = (int)(rq & 0xffu); req_dst = (int)((rq >> 8) & 0xffu); req_br = (int)(rq >> 16);

@@ -63,6 +63,34 @@ int orlg_traffic_upload(OrlgTrafficState *ts, int batch, std::vector<void *> *bu
 int orlg_traffic_get(const OrlgTrafficState *ts, int batch, double arrival_lambda, double holding_lambda, double *arrival,
                      double *holding, int32_t *group);
 
+// ---------------------------------------------------------------------------------------- request traces
+// What a handle keeps of an orlg_trace (include/orlg.h): the device copy in the ring's layout, the length and the position
+// (requests drawn so far -- every environment draws one per step, so the host knows it), and what the capacities are sized from.
+struct OrlgTraceState {
+    int64_t length = 0;           // requests per environment, 0 = the handle generates its traffic
+    int64_t position = 0;         // requests drawn so far
+    int peak = 0;                 // most requests simultaneously inside [arrival, arrival + holding], over all environments
+    int pair_peak = 0;            // ... of one ordered node pair
+    double mean_holding = 0.0;
+    std::vector<uint32_t> req;    // host, until the upload: src | dst << 8 | rate index << 16
+    double *d_arrival = nullptr, *d_holding = nullptr;
+    uint32_t *d_req = nullptr;
+    int64_t *d_tail = nullptr;    // (position, length): the trace handle's part of a saved state
+};
+// checks every entry of tr (the rules of include/orlg.h; bit_rates: the config's table, cont: lower .. higher one apart), packs the
+// requests and sweeps the trace for the peaks.  Groups, if any, go to ts.
+int orlg_trace_check(OrlgTraceState *st, OrlgTrafficState *ts, const orlg_trace *tr, int batch, int N, int NBR,
+                     const int32_t *bit_rates, bool cont);
+// device copies (the handle's device current); buffers are pushed to bufs, which the handle frees
+int orlg_trace_upload(OrlgTraceState *st, const orlg_trace *tr, int batch, std::vector<void *> *bufs);
+// a launch of n_steps more draws: ORLG_ERR_INVALID when it would leave the trace
+int orlg_trace_admit(const OrlgTraceState *st, int n_steps);
+// the position part of a saved state: written to d_tail before a save, read back and checked after a load
+int orlg_trace_tail_store(OrlgTraceState *st, hipStream_t stream);
+int orlg_trace_tail_load(OrlgTraceState *st, hipStream_t stream);
+// the same check on a snapshot that has not been loaded yet (tail: where the 16 bytes lie in the caller's buffer, host or device)
+int orlg_trace_tail_check(const OrlgTraceState *st, const void *tail);
+
 // orlg_reduce_counters per group.  Grid-stride over the environments; every workgroup sums into a [num_groups][12] table in LDS
 // (64-bit LDS atomics; at most 256 x 12 x 8 = 24 KB) and then adds its non-zero entries to out[num_groups][16], zeroed on the
 // stream before, with global atomics whose result nobody reads.  Integers only, so the order of the additions does not show.
@@ -137,6 +165,8 @@ ORLG_FOR_EACH_W(ORLG_DECL_W)
 struct OrlgPhyParams;
 typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
 #define ORLG_FOR_EACH_PHY_W(X) X(1) X(2) X(3) X(4) X(5)
-#define ORLG_DECL_PHY_W(n) orlg_phy_kernel_t orlg_phy_kernel_W##n(int variant) __attribute__((weak));
+#define ORLG_DECL_PHY_W(n)                                                          \
+    orlg_phy_kernel_t orlg_phy_kernel_W##n(int variant) __attribute__((weak));      \
+    orlg_phy_kernel_t orlg_phy_trace_kernel_W##n(int variant) __attribute__((weak));   /* orlg_inst_phy_trace.hip */
 ORLG_FOR_EACH_PHY_W(ORLG_DECL_PHY_W)
 #undef ORLG_DECL_PHY_W

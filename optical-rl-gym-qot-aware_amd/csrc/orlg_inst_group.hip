@@ -28,6 +28,14 @@ orlg_rmsa_kernel_t ORLG_CAT(orlg_group_kernel_W, ORLG_INST_W)(int stats) {
         case 21: return orlg_rmsa_group_kernel<W, 1, true, false, true>;
         case 22: return orlg_rmsa_group_kernel<W, 2, true, false, true>;
         case 26: return orlg_rmsa_group_kernel<W, 2, false, true, true>;
+        // + 32: handles that replay a request trace (OrlgParams::tr_*)
+        case 32: return orlg_rmsa_group_kernel<W, 0, false, false, false, true>;
+        case 33: return orlg_rmsa_group_kernel<W, 1, false, false, false, true>;
+        case 34: return orlg_rmsa_group_kernel<W, 2, false, false, false, true>;
+        case 36: return orlg_rmsa_group_kernel<W, 0, true, false, false, true>;
+        case 37: return orlg_rmsa_group_kernel<W, 1, true, false, false, true>;
+        case 38: return orlg_rmsa_group_kernel<W, 2, true, false, false, true>;
+        case 42: return orlg_rmsa_group_kernel<W, 2, false, true, false, true>;
         default: return nullptr;
     }
 }

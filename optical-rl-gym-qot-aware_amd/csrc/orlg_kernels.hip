@@ -401,6 +401,46 @@ DEV int refill_requests_cont_t(uint32_t *mt, double *ring_iat, double *ring_ht, 
     return r & 0xff;
 }
 
+// A request trace as the ring's second producer (include/orlg.h orlg_create_trace): lane j copies request cursor + j of the
+// environment from the device trace into ring slot j -- three coalesced loads, no MT19937 state, no logarithm.  The ring's first
+// array then holds ABSOLUTE arrival times (the step takes them as they are: a recorded time comes back with its own bits).
+// cursor = requests of the environment copied so far (kept where a generated handle keeps the MT19937 position).  The first
+// refill keeps the stagger of refill_requests_as.  A cursor outside the trace copies nothing (the host refuses a launch that
+// would draw past the end; a state from elsewhere must not make the loads leave the arrays).  Returns the count.
+typedef __attribute__((address_space(1))) const double orlg_glb_cf64;
+typedef __attribute__((address_space(1))) const uint32_t orlg_glb_cu32;
+template <bool RING_LDS>
+__device__ __noinline__ int refill_requests_trace_as(orlg_glb_cf64 *tr_arrival, orlg_glb_cf64 *tr_holding, orlg_glb_cu32 *tr_req,
+                                                     void *ring_iat_v, void *ring_ht_v, void *ring_req_v, int cursor, int length,
+                                                     int env) {
+    const int lane = threadIdx.x & 63;
+    int n = length - cursor;
+    n = n > ORLG_RING ? ORLG_RING : n;
+    if (cursor == 0) { const int cap = 62 - env % 56; n = n > cap ? cap : n; }
+    if (cursor < 0 || n < 0) n = 0;
+    const size_t at = (size_t)env * (size_t)length + (size_t)(cursor > 0 ? cursor : 0) + (size_t)lane;
+    double o_at = 0.0, o_ht = 0.0;
+    uint32_t o_rq = 0u;
+    if (lane < n) { o_at = tr_arrival[at]; o_ht = tr_holding[at]; o_rq = tr_req[at]; }
+    // entries past n are dead and zeroed, as in refill_requests_as
+    if (RING_LDS) {
+        ((orlg_lds_f64 *)ring_iat_v)[lane] = o_at; ((orlg_lds_f64 *)ring_ht_v)[lane] = o_ht; ((orlg_lds_u32 *)ring_req_v)[lane] = o_rq;
+    } else {
+        ((orlg_glb_f64 *)ring_iat_v)[lane] = o_at; ((orlg_glb_f64 *)ring_ht_v)[lane] = o_ht; ((orlg_glb_u32 *)ring_req_v)[lane] = o_rq;
+    }
+    wave_sync();
+    return n;
+}
+// the callers' form: generic pointers in, the cursor advanced through cursor_io
+template <bool RING_LDS>
+DEV int refill_requests_trace_t(const double *tr_arrival, const double *tr_holding, const uint32_t *tr_req, double *ring_iat,
+                                double *ring_ht, uint32_t *ring_req, int *cursor_io, int length, int env) {
+    const int n = refill_requests_trace_as<RING_LDS>((orlg_glb_cf64 *)tr_arrival, (orlg_glb_cf64 *)tr_holding, (orlg_glb_cu32 *)tr_req,
+                                                     ring_iat, ring_ht, ring_req, *cursor_io, length, env);
+    *cursor_io += n;
+    return n;
+}
+
 // ---------------------------------------------------------------------------------------- first fit
 // x[w]: wave-uniform free bitmap of one path (AND over its links).  Lane l of word w owns slot 64w+l
 // and computes the length of the free run starting there.
@@ -1303,7 +1343,17 @@ DEV void rmsa_body(const OrlgParams &p) {
         // ============================================================== _next_service (rmsa_env.py:643-695)
         SEC(7);  // next arrival
         if ((STEPK || p.mode != ORLG_MODE_EPISODE_RESET) && !new_service) {
-            if (ring_cnt == 0) {
+            const bool from_trace = kernarg_params()->tr_arrival != nullptr;   // (wave-uniform: a handle either replays or generates)
+            if (ring_cnt == 0 && from_trace) {
+                SEC(8);  // refill: the next requests of the trace, no generator
+                KernargParams kq = kernarg_params();
+                ring_dirty = true;
+                ring_in_lds = true;
+                ring_cnt = refill_requests_trace_t<true>(kq->tr_arrival, kq->tr_holding, kq->tr_req, wv.ring_iat, wv.ring_ht, wv.ring_req,
+                                                         &mt_idx, kq->tr_len, env);
+                ring_pos = 0;
+                SEC(7);
+            } else if (ring_cnt == 0) {
                 SEC(8);  // refill
                 if (!mt_loaded) {
                     copy_words(wv.mt, kernarg_params()->mt + (size_t)env * ORLG_MT_N, ORLG_MT_N * 4, lane);
@@ -1334,7 +1384,7 @@ DEV void rmsa_body(const OrlgParams &p) {
                 const size_t ro = (size_t)env * ORLG_RING + ring_pos;
                 r_iat = kq->ring_iat[ro]; r_ht = kq->ring_ht[ro]; rq = kq->ring_req[ro];
             }
-            const double at = current_time + r_iat;
+            const double at = from_trace ? r_iat : current_time + r_iat;   // (a trace's ring holds the arrival time itself)
             const double ht = r_ht;
             ring_pos += 1; ring_cnt -= 1;
             current_time = at;

@@ -156,6 +156,11 @@ struct OrlgPhyParams {
     // per-environment traffic (orlg_phy_create_traffic): [B] pairs that take the place of arrival_lambda / holding_lambda above,
     // nullptr = every environment has the scalars.  Read where a refill or nb_rebuild needs it (orlg_env_rates), never kept
     const OrlgRates *rates;
+    // request trace (orlg_phy_create_trace), as OrlgParams::tr_*: [B][tr_len] each, nullptr = generated traffic; the cursor of an
+    // environment lives in OrlgPhyScalars::mt_idx, the ring's first array holds absolute arrival times
+    const double *tr_arrival, *tr_holding;
+    const uint32_t *tr_req;
+    int32_t tr_len, pad_tr;
 };
 
 struct PhyWaveScalars {  // LDS
@@ -1821,7 +1826,9 @@ DEV void nb_first_due(const NearBuffer &nb, double time, int lane, int &victim, 
 // inside an unrolled word loop is a fetch bubble paid W times per candidate path.
 // CONT: bit_rate_selection="continuous" -- arrivals from refill_requests_cont_t, the virtual layer's shares in float64
 // (OrlgPhyParams::cs_f / svc_f) in the reference's order of operations; no defragmentation (refused at create time).
-template <int W, bool DF, bool GN, int POL, bool CONT = false>
+// TRACE: the handle replays a request trace (OrlgPhyParams::tr_*).  A template argument and not a test at run time, as in the
+// group kernel: the instantiations that serve handles without a trace keep their register allocation to the number
+template <int W, bool DF, bool GN, int POL, bool CONT = false, bool TRACE = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_phy_kernel(const OrlgPhyParams p) {
     // the policy sorts channels by the RSS metric (floating point) instead of an integer key
     constexpr bool RSSP = POL == ORLG_PHY_POLICY_BMFA_RSS_METRIC || POL == ORLG_PHY_POLICY_FAFF_RSS;
@@ -2562,7 +2569,21 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
         if (p.mode != ORLG_MODE_EPISODE_RESET && !new_service) {
             // the arrival process does not depend on the network state: requests come from the ring of pre-generated arrivals
             // (five random() draws each, rmsa-style: phy_rmsa_env.py:971-986), refilled 64 at a time when it runs dry
-            if (ring_cnt == 0) {
+            constexpr bool from_trace = TRACE;
+            if (TRACE && ring_cnt == 0) {
+                SEC(8);  // refill: the next requests of the trace -- no staging buffer, no lock, no generator state
+                const OrlgPhyParams __attribute__((address_space(4))) *kq =
+                    (const OrlgPhyParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+                const int got = refill_requests_trace_t<false>(kq->tr_arrival, kq->tr_holding, kq->tr_req, kq->ring_iat + (size_t)env * ORLG_RING,
+                                                               kq->ring_ht + (size_t)env * ORLG_RING, kq->ring_req + (size_t)env * ORLG_RING,
+                                                               &mt_idx, kq->tr_len, env);
+                // the ring entries other lanes wrote are read back below: same CU, the stores only have to be complete
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                wave_sync();
+                ring_cnt = got; ring_pos = 0;
+                SEC(7);
+            } else if (ring_cnt == 0) {
                 SEC(8);  // refill
                 static_assert(ORLG_MT_N * 4 == 156 * 16, "MT19937 state = 156 rows of 16 bytes");
                 const OrlgPhyParams __attribute__((address_space(4))) *kq =
@@ -2611,7 +2632,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
             ring_pos += 1; ring_cnt -= 1;
             if (p.mode == ORLG_MODE_STEP) ring_fetch();   // the entry of the next step
             else pf_ring_ok = false;
-            const double at = current_time + r_iat;
+            const double at = from_trace ? r_iat : current_time + r_iat;   // (a trace's ring holds the arrival time itself)
             current_time = at;
             const int src = (int)(rq & 0xffu), dst = (int)((rq >> 8) & 0xffu), bri = (int)(rq >> 16);
             req_sid = eproc;
@@ -2633,7 +2654,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
             // the scan looks one arrival ahead: the earliest release up to the NEXT arrival's time is this step's victim when it
             // is due now, and otherwise the service the next step will release first -- its record is requested right away
             // (ReleaseAhead; a defragmentation cycle in between drops the look-ahead)
-            const double look_time = have_next ? current_time + next_iat : current_time;
+            const double look_time = have_next ? (from_trace ? next_iat : current_time + next_iat) : current_time;
             int ahead_q = -1;
             for (;;) {
                 int victim, vpos;

@@ -90,13 +90,15 @@ class RMSAEnv:
                             "episode_bit_rate_blocking_rate"]}
     _batched_cls = BatchedRMSAEnv
 
-    def __init__(self, topology=None, episode_length: int = 1000, load: float = 10,
-                 mean_service_holding_time: float = 10800.0, num_spectrum_resources: int = 100,
+    def __init__(self, topology=None, episode_length: int = 1000, load: float = None,
+                 mean_service_holding_time: float = None, num_spectrum_resources: int = 100,
                  bit_rate_selection: str = "discrete", bit_rates: Sequence = DEFAULT_BIT_RATES,
                  bit_rate_probabilities=None, node_request_probabilities=None, bit_rate_lower_bound: float = 25.0,
                  bit_rate_higher_bound: float = 100.0, seed: Optional[int] = None, allow_rejection: bool = False,
                  reset: bool = True, channel_width: float = 12.5, device: int = 0, _batched=None, _index: int = 0,
-                 **_ignored):
+                 trace=None, **_ignored):
+        # (load / mean_service_holding_time: None = the reference's defaults 10 / 10800.0; trace=: a RequestTrace to replay,
+        # which excludes load, mean_service_holding_time and seed -- BatchedRMSAEnv)
         assert bit_rate_selection in ("continuous", "discrete")
         if _batched is None:
             _batched = self._batched_cls(topology, 1, episode_length=episode_length, load=load,
@@ -106,7 +108,8 @@ class RMSAEnv:
                                          bit_rate_lower_bound=bit_rate_lower_bound, bit_rate_higher_bound=bit_rate_higher_bound,
                                          bit_rate_probabilities=bit_rate_probabilities,
                                          node_request_probabilities=node_request_probabilities, seed=seed,
-                                         allow_rejection=allow_rejection, channel_width=channel_width, device=device)
+                                         allow_rejection=allow_rejection, channel_width=channel_width, device=device,
+                                         trace=trace)
         self._init_view(_batched, _index)
 
     # ------------------------------------------------------------------ plumbing
@@ -360,17 +363,18 @@ class DeepRMSAEnv(RMSAEnv):
 
     _batched_cls = BatchedDeepRMSAEnv
 
-    def __init__(self, topology=None, j: int = 1, episode_length: int = 1000, mean_service_holding_time: float = 25.0,
-                 mean_service_inter_arrival_time: float = 0.1, num_spectrum_resources: int = 100,
+    def __init__(self, topology=None, j: int = 1, episode_length: int = 1000, mean_service_holding_time: float = None,
+                 mean_service_inter_arrival_time: float = None, num_spectrum_resources: int = 100,
                  node_request_probabilities=None, seed=None, allow_rejection: bool = False, device: int = 0,
-                 _batched=None, _index: int = 0):
+                 _batched=None, _index: int = 0, trace=None):
+        # (the means: None = the reference's defaults 25.0 / 0.1; trace=: a RequestTrace to replay, which excludes them)
         if _batched is None:
             _batched = BatchedDeepRMSAEnv(topology, 1, j=j, episode_length=episode_length,
                                           mean_service_holding_time=mean_service_holding_time,
                                           mean_service_inter_arrival_time=mean_service_inter_arrival_time,
                                           num_spectrum_resources=num_spectrum_resources,
                                           node_request_probabilities=node_request_probabilities, seed=seed,
-                                          allow_rejection=allow_rejection, device=device)
+                                          allow_rejection=allow_rejection, device=device, trace=trace)
         self._init_view(_batched, _index)
         shape = 1 + 2 * self._ft.num_nodes + (2 * self.j + 3) * self.k_paths
         self.observation_space = _box(-2 ** 30, 2 ** 30, (shape,), np.float64)

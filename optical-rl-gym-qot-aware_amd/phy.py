@@ -16,7 +16,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, trace as _trace
 from .batched import COUNTER_NAMES, REQUEST_DTYPE, SweepTraffic, _check_buffer, _grouped_counters, _ptr
 from .topology import FrozenTopology, selection_tables
 
@@ -93,7 +93,7 @@ def encode_shares(selected_channels, out_row):
 
 class BatchedPhyRMSAEnv:
     def __init__(self, topology, batch_size: int, *, modulation_level, connections_detail, gsnr,
-                 episode_length: int = 1000, load: float = 10, mean_service_holding_time: float = 10800.0,
+                 episode_length: int = 1000, load: float = None, mean_service_holding_time: float = None,
                  bit_rates: Sequence[int] = PHY_DEFAULT_BIT_RATES, bit_rate_probabilities=None,
                  node_request_probabilities=None, seed: Optional[int] = None, seeds=None,
                  allow_rejection: bool = False, number_spectrum_channels: int = 80,
@@ -101,7 +101,13 @@ class BatchedPhyRMSAEnv:
                  defrag_period=None, number_moves=None, metric: str = "cut", grooming: bool = False,
                  queue_capacity: int = 0, channel_state_capacity: int = 0, defrag_capacity: int = 0, device: int = 0,
                  gn_gate=None, bit_rate_selection: str = "discrete", bit_rate_lower_bound=25.0,
-                 bit_rate_higher_bound=100.0, groups=None, num_groups=None, **_ignored):
+                 bit_rate_higher_bound=100.0, groups=None, num_groups=None, trace=None, **_ignored):
+        # trace=: the handle replays a RequestTrace (trace.py); see BatchedRMSAEnv
+        _trace.check_trace_kwargs(trace, dict(load=load, mean_service_holding_time=mean_service_holding_time, seed=seed,
+                                              seeds=seeds))
+        self.trace = trace
+        load = 10 if load is None else load
+        mean_service_holding_time = 10800.0 if mean_service_holding_time is None else mean_service_holding_time
         if defrag_period and number_moves is None:
             raise ValueError("defrag_period needs number_moves (the reference compares against it, phy_rmsa_env.py:358)")
         # bit_rate_selection="continuous" (phy_rmsa_env.py:79-86, 114-134): rng.randint(lower, higher) per request, checked
@@ -114,10 +120,17 @@ class BatchedPhyRMSAEnv:
             bit_rates = range(bounds[0], bounds[1] + 1)
             bit_rate_probabilities = None
         # load= / mean_service_holding_time= may be length-B array-likes (a load sweep in one handle, traffic.py)
-        self.traffic = SweepTraffic(batch_size, load, mean_service_holding_time, groups, num_groups)
-        self.L = _lib.load()
+        self.traffic = SweepTraffic(batch_size, load, mean_service_holding_time, None if trace is not None else groups,
+                                    None if trace is not None else num_groups)
         self.topology = FrozenTopology.from_graph(topology)
         t = self.topology
+        if trace is not None:   # checked before the library is loaded: the rules of orlg_phy_create_trace
+            self.trace = trace = trace.for_batch(batch_size)
+            trace.validate(num_nodes=t.num_nodes, **({"bit_rate_bounds": (bit_rates[0], bit_rates[-1])}
+                                                     if self.continuous else {"bit_rates": list(bit_rates)}))
+            self.traffic.groups, self.traffic.num_groups = _trace.trace_groups(batch_size, groups, num_groups)
+            self._trace_groups = groups is not None
+        self.L = _lib.load()
         self.batch_size = int(batch_size)
         self.episode_length = int(episode_length)
         self.k_paths = t.k_paths
@@ -213,7 +226,10 @@ class BatchedPhyRMSAEnv:
                 raise ValueError(f"seeds: shape {seeds.shape}, expected ({self.batch_size},)")
             seeds_ptr = seeds.ctypes.data_as(C.c_void_p)
         h = C.c_void_p()
-        if self.traffic.per_env:
+        if trace is not None:
+            ts = trace.struct(self.groups if self._trace_groups else None, self.num_groups)
+            _lib.check(self.L.orlg_phy_create_trace(C.byref(ct), C.byref(cc), self.batch_size, int(device), C.byref(ts), C.byref(h)))
+        elif self.traffic.per_env:
             tr = self.traffic.struct()
             _lib.check(self.L.orlg_phy_create_traffic(C.byref(ct), C.byref(cc), self.batch_size, seeds_ptr,
                                                       C.c_uint64(self.rand_seed), int(device), C.byref(tr), C.byref(h)))
@@ -250,8 +266,20 @@ class BatchedPhyRMSAEnv:
         _lib.check(self.L.orlg_phy_last_kernel(self.h, buf, 128))
         return buf.value.decode()
 
+    @property
+    def trace_length(self) -> int:
+        """Requests per environment of the handle's trace, 0 for a handle that generates its traffic."""
+        return int(self.L.orlg_phy_trace_length(self.h))
+
+    @property
+    def trace_position(self) -> int:
+        """Requests drawn so far (the same for every environment): 1 after a full reset, + 1 per step."""
+        return int(self.L.orlg_phy_trace_position(self.h))
+
     def reseed(self, seed=None, seeds=None):
         """A fresh generator for every environment: see ``BatchedRMSAEnv.reseed`` (NOT the reference's ``seed()``)."""
+        if self.trace is not None:
+            raise ValueError("a handle that replays a trace has no generator to seed")
         if seeds is not None:
             sa = np.ascontiguousarray(seeds, np.uint64)
             if sa.shape != (self.batch_size,):

@@ -48,15 +48,16 @@ class PhyRMSAEnv:
     metadata = {"metrics": ["service_blocking_rate", "episode_service_blocking_rate", "bit_rate_blocking_rate",
                             "episode_bit_rate_blocking_rate"]}
 
-    def __init__(self, topology=None, episode_length: int = 1000, load: float = 10,
-                 mean_service_holding_time: float = 10800.0, num_spectrum_resources: int = 100,
+    def __init__(self, topology=None, episode_length: int = 1000, load: float = None,
+                 mean_service_holding_time: float = None, num_spectrum_resources: int = 100,
                  bit_rate_selection: str = "discrete", bit_rates=PHY_DEFAULT_BIT_RATES, bit_rate_probabilities=None,
                  node_request_probabilities=None, seed: Optional[int] = None, allow_rejection: bool = False,
                  reset: bool = True, channel_width: float = 12.5, number_spectrum_channels: int = 80,
                  number_spectrum_channels_s_band: int = 108, l_band: bool = True, s_band: bool = True,
                  modulation_level=None, connections_detail=None, gsnr=None, defrag_period=None, number_moves=None,
                  metric: str = "cut", grooming: bool = True, device: int = 0, bit_rate_lower_bound=25.0,
-                 bit_rate_higher_bound=100.0, **_ignored):
+                 bit_rate_higher_bound=100.0, trace=None, **_ignored):
+        # (load / mean_service_holding_time: None = the reference's defaults 10 / 10800.0; trace=: a RequestTrace to replay)
         self._batched = BatchedPhyRMSAEnv(
             topology, 1, modulation_level=modulation_level, connections_detail=connections_detail, gsnr=gsnr,
             episode_length=episode_length, load=load, mean_service_holding_time=mean_service_holding_time,
@@ -66,7 +67,7 @@ class PhyRMSAEnv:
             number_spectrum_channels_s_band=number_spectrum_channels_s_band, l_band=l_band, s_band=s_band,
             defrag_period=defrag_period, number_moves=number_moves, metric=metric, grooming=grooming, device=device,
             bit_rate_selection=bit_rate_selection, bit_rate_lower_bound=bit_rate_lower_bound,
-            bit_rate_higher_bound=bit_rate_higher_bound)
+            bit_rate_higher_bound=bit_rate_higher_bound, trace=trace)
         b = self._batched
         ft = b.topology
         self._ft = ft
