@@ -210,6 +210,33 @@ int orlg_deeprmsa_observation_f32(orlg_env *env, float *out);
  * The actions of orlg_step may likewise lie in pinned host memory. */
 int orlg_deeprmsa_obs_dim(orlg_env *env);
 
+/* ---- valid-action masks for the whole batch.  One definition throughout: mask[a] = 1 iff the reference's step(a) on the
+ * environment's pending request would accept the service; the explicit rejection, where the action space has one, is always 1.
+ * The quirks are the reference's own.  The entries read state left by either step kernel or by orlg_load_state and write only the
+ * caller's buffers.  Buffers follow orlg_deeprmsa_observation: device memory or pinned host memory is written in place,
+ * asynchronously on the handle's stream; pageable host memory is staged and the call waits.
+ *
+ * allow_rejection (rmsa_env.py:44, 182, 197-202; deeprmsa_env.py:41-43): the action spaces of the handle carry the explicit rejection --
+ * one more column, always 1, in the two byte masks.  Not part of orlg_rmsa_config, whose layout stays: the step itself needs no
+ * flag (an action out of range is rejected either way).  Default 0. */
+int orlg_set_allow_rejection(orlg_env *env, int32_t allow_rejection);
+/* DeepRMSAEnv's Discrete(k*j + reject) (deeprmsa_env.py:41-43, 48-58): action a < k*j = route a / j, block a % j; valid iff
+ * block < len(get_available_blocks(route)[0]) (rmsa_env.py:774-804), i.e. the route has more than `block` free runs of at least
+ * get_number_slots(route) slots.  A block may end at slot S-1: no first-fit bound here.  mask: [B][k*j + reject] uint8. */
+int orlg_deeprmsa_mask_dim(orlg_env *env);
+/* orlg_deeprmsa_observation (obs_f32 == 0: obs is double[B][obs_dim]) or orlg_deeprmsa_observation_f32 (obs_f32 != 0: float) plus
+ * the mask above, out of ONE kernel launch: the block scan behind the observation's start / length features is the mask's.  Either
+ * of obs and mask may be NULL (mask == NULL: exactly the observation entries); both NULL is ORLG_ERR_INVALID. */
+int orlg_deeprmsa_observation_masked(orlg_env *env, void *obs, int32_t obs_f32, uint8_t *mask);
+/* path_ff: [B][k + reject] uint8 or NULL -- PathOnlyFirstFitAction.action(p) (rmsa_env.py:974-1008) finds a slot: some s in
+ * range(0, S - n) has is_path_free(path, s, n), n = get_number_slots(path).  The exclusive bound is the reference's: a path whose
+ * only fit starts at S - n is 0 here.
+ * slots: [B][k][W] uint64 or NULL, the layout of orlg_query_path_masks (bit s of word w = slot 64w+s) -- RMSAEnv.step([p, s])
+ * provisions (rmsa_env.py:233-260, 721-734): s + n <= S and the window is free on every hop.  Start S - n IS valid here (step
+ * accepts it, only the first-fit loops never try it); bits at and beyond S are 0.
+ * Both NULL is ORLG_ERR_INVALID. */
+int orlg_action_masks(orlg_env *env, uint8_t *path_ff, uint64_t *slots);
+
 /* SimpleMatrixObservation.observation() (rmsa_env.py:940-971) for every env: [B][2N + E*S] uint8 */
 int orlg_simple_matrix_observation(orlg_env *env, uint8_t *out);
 int orlg_simple_matrix_obs_dim(orlg_env *env);
@@ -403,6 +430,12 @@ int orlg_phy_load_state(orlg_phy_env *env, const void *buffer);
  * channel | used << 9 | free << 14 | capacity << 19 (100 Gb/s units) in list order, lengths [N*N*K]; returns capacity */
 int orlg_phy_get_channel_state(orlg_phy_env *env, int32_t env_index, uint32_t *entries, uint8_t *lengths);
 int orlg_phy_channel_state_capacity(orlg_phy_env *env);
+
+/* is_channel_free(path_p, c) (phy_rmsa_env.py:1029-1035) for the k candidate paths of every environment's pending request
+ * (k_shortest_paths[source, destination]): out [B][k][W] uint64, bit c of word w = channel 64w+c is
+ * dark on every link of the path; bits at and beyond the channel count are 0.  Not a feasibility mask: modulation levels, the bit
+ * rate and the virtual layer are not looked at.  Buffers as orlg_action_masks. */
+int orlg_phy_channel_masks(orlg_phy_env *env, uint64_t *out /* [B][k][W] */);
 
 /* ---- bit_rate_selection = "continuous" (phy_rmsa_env.py:37-42, 114-134, 979-984).  orlg_phy_config as for orlg_phy_create
  * with bit_rate_cum = NULL and bit_rates = the integers lower .. higher, one apart (the RMSA convention, orlg_rmsa_config):

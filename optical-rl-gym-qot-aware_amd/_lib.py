@@ -138,6 +138,12 @@ def load(build_if_missing=True):
     L.orlg_deeprmsa_observation.argtypes = [vp, vp]
     L.orlg_deeprmsa_observation_f32.argtypes = [vp, vp]
     L.orlg_deeprmsa_obs_dim.argtypes = [vp]
+    # valid-action masks for the whole batch (include/orlg.h)
+    L.orlg_set_allow_rejection.argtypes = [vp, i32]
+    L.orlg_deeprmsa_mask_dim.argtypes = [vp]
+    L.orlg_deeprmsa_observation_masked.argtypes = [vp, vp, i32, vp]
+    L.orlg_action_masks.argtypes = [vp, vp, vp]
+    L.orlg_phy_channel_masks.argtypes = [vp, vp]
     L.orlg_reduce_counters.argtypes = [vp, vp]
     L.orlg_simple_matrix_observation.argtypes = [vp, vp]
     L.orlg_simple_matrix_obs_dim.argtypes = [vp]
@@ -207,6 +213,8 @@ EXPORTED_SYMBOLS = [
     "orlg_phy_create_traffic", "orlg_phy_get_traffic", "orlg_phy_num_groups", "orlg_phy_reduce_counters_grouped",
     "orlg_create_trace", "orlg_trace_length", "orlg_trace_position",
     "orlg_phy_create_trace", "orlg_phy_trace_length", "orlg_phy_trace_position",
+    "orlg_deeprmsa_observation_masked", "orlg_deeprmsa_mask_dim", "orlg_action_masks", "orlg_phy_channel_masks",
+    "orlg_set_allow_rejection",
 ]
 
 

@@ -218,6 +218,10 @@ class BatchedRMSAEnv:
         self.device = int(device)
         self.words_per_link = self.L.orlg_words_per_link(self.h)
         self.obs_dim = self.L.orlg_deeprmsa_obs_dim(self.h)
+        # the explicit rejection is one more column of the action masks (the step kernels need no flag: an action out of range
+        # is a rejection either way)
+        _lib.check(self.L.orlg_set_allow_rejection(self.h, self.reject_action))
+        self.mask_dim = self.L.orlg_deeprmsa_mask_dim(self.h)
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -397,19 +401,65 @@ class BatchedRMSAEnv:
         _lib.check(self.L.orlg_query_path_mask(self.h, int(env_index), int(path_gid), _ptr(m), _ptr(n)))
         return m, int(n[0])
 
-    def observation(self, out=None, dtype=np.float64):
+    def observation(self, out=None, dtype=np.float64, mask_out=None, return_mask=False):
         """DeepRMSAEnv.observation() for every env: [B, obs_dim] float64 (the reference's Box dtype), or float32 -- the
-        float64 vector rounded once, ``obs.astype(np.float32)`` -- with ``dtype=np.float32`` / a float32 ``out`` buffer."""
+        float64 vector rounded once, ``obs.astype(np.float32)`` -- with ``dtype=np.float32`` / a float32 ``out`` buffer.
+
+        ``mask_out=`` (a [B, k*j + reject] uint8 buffer) or ``return_mask=True``: the DeepRMSA action mask leaves the same
+        launch, and the call returns ``(observation, mask)``; see :meth:`action_masks`."""
+        B = self.batch_size
         if out is None:
-            out = np.zeros((self.batch_size, self.obs_dim), dtype)
+            out = np.zeros((B, self.obs_dim), dtype)
         elif _dtype_name(out) == "float32":
             dtype = np.float32
-        if np.dtype(dtype) == np.float32:
-            _check_buffer("out", out, (self.batch_size, self.obs_dim), np.float32)
-            _lib.check(self.L.orlg_deeprmsa_observation_f32(self.h, _ptr(out)))
+        f32 = np.dtype(dtype) == np.float32
+        _check_buffer("out", out, (B, self.obs_dim), np.float32 if f32 else np.float64)
+        if mask_out is None and not return_mask:
+            call = self.L.orlg_deeprmsa_observation_f32 if f32 else self.L.orlg_deeprmsa_observation
+            _lib.check(call(self.h, _ptr(out)))
             return out
-        _check_buffer("out", out, (self.batch_size, self.obs_dim), np.float64)
-        _lib.check(self.L.orlg_deeprmsa_observation(self.h, _ptr(out)))
+        if mask_out is None:
+            mask_out = np.zeros((B, self.mask_dim), np.uint8)
+        else:
+            _check_buffer("mask_out", mask_out, (B, self.mask_dim), np.uint8)
+        _lib.check(self.L.orlg_deeprmsa_observation_masked(self.h, _ptr(out), 1 if f32 else 0, _ptr(mask_out)))
+        return out, mask_out
+
+    MASK_KINDS = ("deeprmsa", "path_ff", "slots")
+
+    def action_mask_shape(self, kind):
+        """(shape, dtype) of ``action_masks(kind)``."""
+        if kind not in self.MASK_KINDS:
+            raise ValueError(f"kind {kind!r}: expected one of {self.MASK_KINDS}")
+        B, k = self.batch_size, self.k_paths
+        if kind == "deeprmsa":
+            return (B, k * self.j + self.reject_action), np.uint8
+        if kind == "path_ff":
+            return (B, k + self.reject_action), np.uint8
+        return (B, k, self.words_per_link), np.uint64
+
+    def action_masks(self, kind="deeprmsa", out=None):
+        """Valid actions of every env's pending request: ``mask[a] = 1`` iff the reference's ``step(a)`` would accept the
+        service.  The explicit rejection, where ``allow_rejection`` gives the action space one, is always 1.
+
+        ``"deeprmsa"``  [B, k*j + reject] uint8: action ``a`` = (route ``a // j``, block ``a % j``) is valid iff the route has
+                        more than ``block`` free runs of at least ``get_number_slots(route)`` slots (``deeprmsa_env.py:48-58``).
+        ``"path_ff"``   [B, k + reject] uint8: ``PathOnlyFirstFitAction.action(p)`` finds a slot -- some ``s`` in
+                        ``range(0, S - n)`` is free (``rmsa_env.py:974-1008``; the bound is exclusive, as in the reference).
+        ``"slots"``     [B, k, W] uint64, bit ``s`` of word ``w`` = slot ``64 w + s``: ``RMSAEnv.step([p, s])`` provisions --
+                        ``s + n <= S`` and the window is free on every hop (start ``S - n`` included).
+        ``out`` may be a numpy array or a torch tensor (device tensors and pinned host tensors are written in place)."""
+        shape, dt = self.action_mask_shape(kind)
+        if out is None:
+            out = np.zeros(shape, dt)
+        else:
+            _check_buffer("out", out, shape, dt)
+        if kind == "deeprmsa":
+            _lib.check(self.L.orlg_deeprmsa_observation_masked(self.h, None, 0, _ptr(out)))
+        elif kind == "path_ff":
+            _lib.check(self.L.orlg_action_masks(self.h, _ptr(out), None))
+        else:
+            _lib.check(self.L.orlg_action_masks(self.h, None, _ptr(out)))
         return out
 
     def simple_matrix_observation(self, out=None):

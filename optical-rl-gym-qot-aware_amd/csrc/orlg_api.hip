@@ -58,6 +58,7 @@ struct orlg_env {
     int num_cu;
     uint32_t ticket_base;
     int num_paths;
+    int allow_rejection;     // the action spaces carry the explicit rejection (orlg_set_allow_rejection): one more mask column
     // owned device buffers
     std::vector<void *> bufs;
     unsigned char *staging;
@@ -440,7 +441,22 @@ static rmsa_kernel_t pick_wave(int W, int kind, int stats) {
 // the wave-per-environment step kernel that only carries the first-fit policies (k <= 8)
 static rmsa_kernel_t pick_rmsa_ff(int W, int stats) { return pick_wave(W, ORLG_KIND_STEP_FF, stats); }
 static rmsa_kernel_t pick_rmsa(int W, int stats, bool step = true) { return pick_wave(W, step ? ORLG_KIND_STEP : ORLG_KIND_RESET, stats); }
-static rmsa_kernel_t pick_obs(int W) { return pick_wave(W, ORLG_KIND_OBS, 0); }
+static orlg_obs_kernel_t pick_obs(int W) {
+    switch (W) {
+#define X(n) case n: return orlg_obs_kernel_W##n ? orlg_obs_kernel_W##n() : nullptr;
+        ORLG_FOR_EACH_W(X)
+#undef X
+        default: return nullptr;
+    }
+}
+static orlg_action_masks_kernel_t pick_action_masks(int W) {
+    switch (W) {
+#define X(n) case n: return orlg_action_masks_kernel_W##n ? orlg_action_masks_kernel_W##n() : nullptr;
+        ORLG_FOR_EACH_W(X)
+#undef X
+        default: return nullptr;
+    }
+}
 static rmsa_kernel_t pick_group(int W, int stats) {
     switch (W) {
 #define X(n) case n: return orlg_group_kernel_W##n ? orlg_group_kernel_W##n(stats) : nullptr;
@@ -1277,24 +1293,65 @@ int orlg_query_path_mask(orlg_env *e, int32_t env_index, int32_t path_gid, uint6
 }
 
 int orlg_deeprmsa_obs_dim(orlg_env *e) { return e ? e->p.obs_dim : ORLG_ERR_INVALID; }
-static int deeprmsa_observation(orlg_env *e, void *out, bool f32) {
-    if (!e || !out) return fail(ORLG_ERR_INVALID, "null argument");
+// A caller's output buffer of one launch: device memory -- or pinned host memory, which the kernel then writes over the bus,
+// asynchronously like a device buffer (no staging copy, no wait: the caller synchronises the stream or an event) -- is written
+// in place; pageable host memory gets a slice of the handle's staging buffer and is copied after the launch.
+struct OutSlot {
+    void *user;
+    size_t bytes, off;
+    void *dev;
+    bool staged;
+};
+static int place_outputs(orlg_env *e, OutSlot *slots, int n) {
+    size_t need = 0;
+    for (int i = 0; i < n; ++i) {
+        OutSlot &s = slots[i];
+        s.dev = s.user ? orlg_device_alias(s.user) : nullptr;
+        s.staged = s.user && !s.dev;
+        s.off = need;
+        if (s.staged) need += (s.bytes + 15) & ~(size_t)15;
+    }
+    if (need) {
+        int rc = ensure_staging(e, need);
+        if (rc) return rc;
+    }
+    for (int i = 0; i < n; ++i)
+        if (slots[i].staged) slots[i].dev = e->staging + slots[i].off;
+    return ORLG_OK;
+}
+static int collect_outputs(orlg_env *e, const OutSlot *slots, int n) {
+    bool any = false;
+    for (int i = 0; i < n; ++i)
+        if (slots[i].staged) {
+            HIP_TRY(hipMemcpyAsync(slots[i].user, slots[i].dev, slots[i].bytes, hipMemcpyDefault, e->stream));
+            any = true;
+        }
+    if (any) HIP_TRY(hipStreamSynchronize(e->stream));
+    return ORLG_OK;
+}
+
+int orlg_set_allow_rejection(orlg_env *e, int32_t allow_rejection) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    e->allow_rejection = allow_rejection ? 1 : 0;
+    return ORLG_OK;
+}
+int orlg_deeprmsa_mask_dim(orlg_env *e) { return e ? e->p.K * e->p.j + e->allow_rejection : ORLG_ERR_INVALID; }
+
+// observation and / or DeepRMSA mask out of ONE launch of orlg_deeprmsa_obs_kernel (mask == nullptr: the kernel writes exactly
+// what it wrote before the mask existed; out == nullptr: the mask alone, the row stays on chip)
+static int deeprmsa_observation(orlg_env *e, void *out, bool f32, uint8_t *mask) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!out && !mask) return fail(ORLG_ERR_INVALID, "null argument: neither an observation nor a mask buffer");
     HIP_TRY(hipSetDevice(e->device));
     OrlgParams p = e->p;
-    size_t bytes = (size_t)p.B * p.obs_dim * (f32 ? 4 : 8);
-    // device memory -- or pinned host memory, which the kernel then writes over the bus, asynchronously like a device buffer
-    // (no staging copy, no wait: the caller synchronises the stream or an event) -- is written in place
-    void *alias = orlg_device_alias(out);
-    const bool dev = alias != nullptr;
+    const int mask_dim = p.K * p.j + e->allow_rejection;
+    OutSlot slots[2] = {{out, (size_t)p.B * p.obs_dim * (f32 ? 4 : 8)}, {mask, (size_t)p.B * mask_dim}};
+    int rc = place_outputs(e, slots, 2);
+    if (rc) return rc;
     p.obs_f32 = f32 ? 1 : 0;
-    if (!dev) {
-        int rc = ensure_staging(e, bytes);
-        if (rc) return rc;
-        p.o_obs = reinterpret_cast<double *>(e->staging);
-    } else {
-        p.o_obs = reinterpret_cast<double *>(alias);
-    }
-    rmsa_kernel_t k = pick_obs(e->W);
+    p.o_obs = reinterpret_cast<double *>(slots[0].dev);
+    orlg_obs_kernel_t k = pick_obs(e->W);
+    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     const int wpb = e->waves_per_block;
     size_t lds = (size_t)p.l_shared_bytes + (size_t)(((p.NW * 8 + 15) & ~15) + ((p.obs_dim * 8 + 15) & ~15)) * wpb;
     if (lds > 160 * 1024) return fail(ORLG_ERR_INVALID, "observation of %d values does not fit the LDS next to the tables", p.obs_dim);
@@ -1302,13 +1359,43 @@ static int deeprmsa_observation(orlg_env *e, void *out, bool f32) {
     int nblocks = (p.B + wpb - 1) / wpb;
     if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;   // a few workgroups per CU, each wave striding over its environments
     dim3 grid(nblocks), block(ORLG_WAVE * wpb);
-    hipLaunchKernelGGL(k, grid, block, lds, e->stream, p);
+    hipLaunchKernelGGL(k, grid, block, lds, e->stream, p, reinterpret_cast<uint8_t *>(slots[1].dev), mask_dim);
     HIP_TRY(hipGetLastError());
-    if (!dev) return copy_out(e, out, e->staging, bytes);
-    return ORLG_OK;
+    return collect_outputs(e, slots, 2);
 }
-int orlg_deeprmsa_observation(orlg_env *e, double *out) { return deeprmsa_observation(e, out, false); }
-int orlg_deeprmsa_observation_f32(orlg_env *e, float *out) { return deeprmsa_observation(e, out, true); }
+int orlg_deeprmsa_observation(orlg_env *e, double *out) {
+    if (!out) return fail(ORLG_ERR_INVALID, "null argument");
+    return deeprmsa_observation(e, out, false, nullptr);
+}
+int orlg_deeprmsa_observation_f32(orlg_env *e, float *out) {
+    if (!out) return fail(ORLG_ERR_INVALID, "null argument");
+    return deeprmsa_observation(e, out, true, nullptr);
+}
+int orlg_deeprmsa_observation_masked(orlg_env *e, void *obs, int32_t obs_f32, uint8_t *mask) {
+    return deeprmsa_observation(e, obs, obs_f32 != 0, mask);
+}
+
+int orlg_action_masks(orlg_env *e, uint8_t *path_ff, uint64_t *slot_masks) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!path_ff && !slot_masks) return fail(ORLG_ERR_INVALID, "null argument: neither a path_ff nor a slots buffer");
+    HIP_TRY(hipSetDevice(e->device));
+    const OrlgParams &p = e->p;
+    const int ff_dim = p.K + e->allow_rejection;
+    OutSlot slots[2] = {{path_ff, (size_t)p.B * ff_dim}, {slot_masks, (size_t)p.B * p.K * e->W * 8}};
+    int rc = place_outputs(e, slots, 2);
+    if (rc) return rc;
+    orlg_action_masks_kernel_t k = pick_action_masks(e->W);
+    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
+    const int wpb = e->waves_per_block;
+    const size_t lds = (size_t)p.l_shared_bytes + (size_t)((p.NW * 8 + 15) & ~15) * wpb;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int nblocks = (p.B + wpb - 1) / wpb;
+    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;   // as the observation: each wave strides over its environments
+    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, reinterpret_cast<uint8_t *>(slots[0].dev), ff_dim,
+                       reinterpret_cast<u64 *>(slots[1].dev));
+    HIP_TRY(hipGetLastError());
+    return collect_outputs(e, slots, 2);
+}
 
 int orlg_simple_matrix_obs_dim(orlg_env *e) { return e ? 2 * e->p.N + e->p.E * e->p.S : ORLG_ERR_INVALID; }
 int orlg_simple_matrix_observation(orlg_env *e, uint8_t *out) {

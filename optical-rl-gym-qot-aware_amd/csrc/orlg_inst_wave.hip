@@ -2,6 +2,7 @@
 // -DORLG_INST_W=<W>: one object per W, so that the library builds in parallel (build.py).
 #include "orlg_host.h"
 #include "orlg_kernels.hip"
+#include "orlg_mask_kernels.hip"
 
 #ifndef ORLG_INST_W
 #error "compile with -DORLG_INST_W=<words per link>"
@@ -22,8 +23,6 @@ static orlg_rmsa_kernel_t pick_stats(int kind, int stats) {
             return stats == 2 ? orlg_rmsa_kernel_ff<W, 2, true> : nullptr;
         case ORLG_KIND_RESET:
             return stats == 0 ? orlg_rmsa_reset_kernel<W, 0> : stats == 1 ? orlg_rmsa_reset_kernel<W, 1> : orlg_rmsa_reset_kernel<W, 2>;
-        case ORLG_KIND_OBS:
-            return orlg_deeprmsa_obs_kernel<W>;
         default:
             return nullptr;
     }
@@ -31,3 +30,5 @@ static orlg_rmsa_kernel_t pick_stats(int kind, int stats) {
 
 orlg_rmsa_kernel_t ORLG_CAT(orlg_wave_kernel_W, ORLG_INST_W)(int kind, int stats) { return pick_stats<ORLG_INST_W>(kind, stats); }
 orlg_masks_kernel_t ORLG_CAT(orlg_masks_kernel_W, ORLG_INST_W)() { return orlg_path_masks_kernel<ORLG_INST_W>; }
+orlg_obs_kernel_t ORLG_CAT(orlg_obs_kernel_W, ORLG_INST_W)() { return orlg_deeprmsa_obs_kernel<ORLG_INST_W>; }
+orlg_action_masks_kernel_t ORLG_CAT(orlg_action_masks_kernel_W, ORLG_INST_W)() { return orlg_action_masks_kernel<ORLG_INST_W>; }

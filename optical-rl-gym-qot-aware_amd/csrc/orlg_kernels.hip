@@ -1549,8 +1549,14 @@ __global__ __launch_bounds__(ORLG_WAVE) void orlg_path_masks_kernel(const OrlgPa
 // device and strides over the environments (the topology tables are staged once per workgroup).  The per-path integers
 // (block starts / lengths, slots needed, free slots, free runs) are found with wave-uniform scans and parked in LDS; then
 // lane i evaluates element i of the vector -- one fp64 division sequence for all elements -- and the row leaves coalesced.
+// mask != nullptr: the DeepRMSA action mask [B][mask_dim] leaves the same launch -- action a < K * J is valid iff block a % J of
+// path a / J exists, i.e. the path has more than a % J free runs of at least get_number_slots slots (deeprmsa_env.py:48-58,
+// rmsa_env.py:774-804), which is what the block scan has just parked: a start >= 0; the column beyond K * J (the explicit
+// rejection) is always valid.  mask == nullptr: the kernel writes what it wrote before the mask existed.  p.o_obs == nullptr
+// (only with a mask): the mask alone.
 template <int W>
-__global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK) void orlg_deeprmsa_obs_kernel(const OrlgParams p) {
+__global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK) void orlg_deeprmsa_obs_kernel(const OrlgParams p, uint8_t *mask,
+                                                                                                int mask_dim) {
     extern __shared__ __align__(16) unsigned char smem[];
     stage_tables(smem, p);
     const Tab tb = make_tab(smem, p);
@@ -1564,6 +1570,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK) void orlg_deep
     const int N = p.N, K = p.K, S = p.S, J = p.j;
     const int PW = 2 * J + 3, head = 1 + 2 * N;
     const uint32_t pw_inv = (65536u + (uint32_t)PW - 1u) / (uint32_t)PW;
+    const uint32_t j_inv = (65536u + (uint32_t)J - 1u) / (uint32_t)J;   // (a / J as r / PW below: a < K * J <= 64 * J, J <= 16)
     const int n_waves = (int)(gridDim.x * (blockDim.x >> 6));
     const bool wide = (p.NW & 1) == 0;
     for (int env = blockIdx.x * (int)(blockDim.x >> 6) + wib; env < p.B; env += n_waves) {
@@ -1655,10 +1662,17 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK) void orlg_deep
             }
         }
         wave_sync();
+        if (mask) {   // lane a = action a: one row of bytes per environment
+            uint8_t *mrow = mask + (size_t)env * mask_dim;
+            for (int a = lane; a < mask_dim; a += 64) {
+                const int route = (int)(((uint32_t)a * j_inv) >> 16), block = a - route * J;
+                mrow[a] = (uint8_t)(route >= K || opa[head + route * PW + 2 * block] >= 0 ? 1 : 0);
+            }
+        }
         double *gout = p.o_obs + (size_t)env * p.obs_dim;
         float *gout32 = reinterpret_cast<float *>(p.o_obs) + (size_t)env * p.obs_dim;   // (obs_f32: the same vector rounded once)
         const int br_val = tb.bit_rates[br];
-        for (int i = lane; i < p.obs_dim; i += 64) {
+        for (int i = p.o_obs ? lane : p.obs_dim; i < p.obs_dim; i += 64) {
             // element i = num / den (one division for every kind of element), optionally followed by (q - 4) / 4
             double num = 0.0, den = 1.0, res;
             bool fixed = false, tail = false;

@@ -916,6 +916,53 @@ int orlg_phy_get_occupancy(orlg_phy_env *e, uint64_t *out) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     return ORLG_OK;
 }
+// is_channel_free (phy_rmsa_env.py:1029-1035) for every channel of every candidate path of every environment's pending request:
+// one thread per (environment, k-path, word) ANDs the free-channel words of the path's links.  Bits at and beyond the channel
+// count are stored as used in the occupancy and so come out 0.  Reads state, writes only `out`.
+__global__ __launch_bounds__(256) void orlg_phy_channel_masks_kernel(const OrlgPhyParams p, int W, uint64_t *out) {
+    const int32_t *pair_base = reinterpret_cast<const int32_t *>(p.tables + p.t_pair);
+    const OrlgPathRec *recs = reinterpret_cast<const OrlgPathRec *>(p.tables + p.t_recs);
+    const size_t per_env = (size_t)p.K * W, total = (size_t)p.B * per_env;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t env = i / per_env;
+        const int r = (int)(i - env * per_env), idp = r / W, w = r - idp * W;
+        const OrlgPhyScalars &s = p.scal[env];
+        const OrlgPathRec rec = recs[pair_base[s.req_src * p.N + s.req_dst] + idp];
+        const uint64_t *occ = p.occ + env * p.NW;
+        uint64_t acc = ~0ull;
+        for (int h = 0; h < rec.hops; ++h) acc &= occ[(int)rec.link[h] * W + w];
+        out[i] = acc;
+    }
+}
+
+int orlg_phy_channel_masks(orlg_phy_env *e, uint64_t *out) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!out) return fail(ORLG_ERR_INVALID, "null argument: no channel-mask buffer");
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t words = (size_t)e->p.B * e->p.K * e->W, bytes = words * 8;
+    // device or pinned host memory is written in place, asynchronously; pageable host memory is staged and the call waits
+    uint64_t *d = reinterpret_cast<uint64_t *>(orlg_device_alias(out));
+    const bool staged = d == nullptr;
+    if (staged) {
+        if (bytes > e->staging_bytes) {
+            if (e->staging) HIP_TRY(hipFree(e->staging));
+            e->staging = nullptr; e->staging_bytes = 0;
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->staging), bytes));
+            e->staging_bytes = bytes;
+        }
+        d = reinterpret_cast<uint64_t *>(e->staging);
+    }
+    size_t nblocks = (words + 255) / 256;
+    const size_t cap = 8 * (size_t)(e->num_cu > 0 ? e->num_cu : 256);
+    if (nblocks > cap) nblocks = cap;
+    hipLaunchKernelGGL(orlg_phy_channel_masks_kernel, dim3((unsigned)nblocks), dim3(256), 0, e->stream, e->p, e->W, d);
+    HIP_TRY(hipGetLastError());
+    if (staged) {
+        HIP_TRY(hipMemcpyAsync(out, d, bytes, hipMemcpyDefault, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    return ORLG_OK;
+}
 typedef OrlgStatePart StatePart;
 static std::vector<StatePart> phy_state_parts(orlg_phy_env *e) {
     const OrlgPhyParams &p = e->p;

@@ -250,6 +250,23 @@ class RMSAEnv:
         ok = np.flatnonzero((values == 1) & (lengths >= slots))[: self.j]
         return starts[ok], lengths[ok]
 
+    def _slot_bits(self):
+        """[k, S] bool: ``step([p, s])`` would provision (``BatchedRMSAEnv.action_masks("slots")`` of this env)."""
+        words = self._batched.action_masks("slots")[self._index]
+        bits = np.unpackbits(words.view(np.uint8), axis=-1, bitorder="little")[:, :self.num_spectrum_resources]
+        return bits.astype(bool)
+
+    def action_masks(self):
+        """Valid actions of ``MultiDiscrete(path, slot)`` for the pending request: bool [k + reject, S + reject], True where
+        ``step([p, s])`` would provision the service (``rmsa_env.py:233-260``).  With ``allow_rejection`` the extra row and
+        column belong to the explicit rejection ``[k, S]``: only their corner is True."""
+        k, S, r = self.k_paths, self.num_spectrum_resources, self.reject_action
+        m = np.zeros((k + r, S + r), bool)
+        m[:k, :S] = self._slot_bits()
+        if r:
+            m[k, S] = True
+        return m
+
     # ------------------------------------------------------------------ gym surface
     def observation(self):
         return {"topology": self.topology, "current_service": self.current_service}
@@ -401,6 +418,11 @@ class DeepRMSAEnv(RMSAEnv):
     def _get_route_block_id(self, action: int) -> Tuple[int, int]:
         return action // self.j, action % self.j
 
+    def action_masks(self):
+        """Valid actions of ``Discrete(k*j + reject)`` for the pending request: bool [k*j + reject], True where ``step(a)``
+        would accept the service (the method maskable-PPO implementations look for)."""
+        return self._batched.action_masks("deeprmsa")[self._index].astype(bool)
+
 
 class SimpleMatrixObservation:
     """``rmsa_env.py:940-971``: observation = one-hot endpoints + the E x S free-slot matrix (built on the device)."""
@@ -450,6 +472,10 @@ class PathOnlyFirstFitAction:
                 if e.is_path_free(path, s, n):
                     return (action, s)
         return (e.topology.graph["k_paths"], e.topology.graph["num_spectrum_resources"])
+
+    def action_masks(self):
+        """Valid paths for the pending request: bool [k + reject], True where ``action(p)`` finds a slot."""
+        return self._inner._batched.action_masks("path_ff")[self._inner._index].astype(bool)
 
     def step(self, action):
         return self.env.step(self.action(action))

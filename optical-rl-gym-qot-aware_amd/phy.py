@@ -407,6 +407,19 @@ class BatchedPhyRMSAEnv:
         bits = np.unpackbits(w.view(np.uint8), axis=-1, bitorder="little")
         return bits.reshape(self.batch_size, E, -1)[:, :, :self.num_channels]
 
+    def channel_masks(self, out=None):
+        """``is_channel_free(path_p, c)`` (``phy_rmsa_env.py:1029-1035``) for the k candidate paths of every env's pending
+        request: [B, k, W] uint64, bit ``c`` of word ``w`` = channel ``64 w + c`` is dark on every link of the path; bits at
+        and beyond the channel count are 0.  ``out`` may be a numpy array or a torch tensor (device and pinned host tensors
+        are written in place).  Modulation levels, the bit rate and the virtual layer are not looked at."""
+        shape = (self.batch_size, self.k_paths, self.words_per_link)
+        if out is None:
+            out = np.zeros(shape, np.uint64)
+        else:
+            _check_buffer("out", out, shape, np.uint64)
+        _lib.check(self.L.orlg_phy_channel_masks(self.h, _ptr(out)))
+        return out
+
     def channel_state(self, env_index: int = 0):
         """``env.channel_state`` of one env (``phy_rmsa_env.py:117-125``): dict (src_id, dst_id, k-path) -> list of
         (channel, used, free, capacity) tuples in list order (100 Gb/s units); empty lists are omitted."""

@@ -129,6 +129,13 @@ class PhyRMSAEnv:
         """``phy_rmsa_env.py:1029-1035``"""
         return bool(self._available()[self._links(path), channel_number].all())
 
+    def channel_masks(self):
+        """bool [k, channels]: ``is_channel_free(path_p, c)`` for the k candidate paths of the pending request (built on the
+        device, ``BatchedPhyRMSAEnv.channel_masks``)."""
+        words = self._batched.channel_masks()[0]
+        bits = np.unpackbits(words.view(np.uint8), axis=-1, bitorder="little")[:, :self._batched.num_channels]
+        return bits.astype(bool)
+
     def is_path_free_on_channels(self, path: Path, selected_channels) -> bool:
         """``phy_rmsa_env.py:1019-1027``"""
         av = self._available()
