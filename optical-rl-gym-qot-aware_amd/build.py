@@ -5,9 +5,9 @@
 hipcc cross-compiles without a GPU.  -ffp-contract=off is REQUIRED: the fp64 statistics and the
 arrival process must perform exactly the reference's IEEE operations (no fused multiply-add).
 
-The library is a set of translation units compiled in parallel into csrc/build/*.o and linked: the host API
-(orlg_api.hip, orlg_phy_api.hip, orlg_osnr.hip) and one object per (kernel family, words per link W) from
-orlg_inst_{wave,group,phy}.hip.  An object is rebuilt when any file its depfile names (or the flags) changed,
+The library is a set of translation units compiled in parallel into csrc/build/*.o and linked: the host side
+(orlg_host.hip: what the APIs share; orlg_api.hip, orlg_phy_api.hip, orlg_osnr.hip: the three APIs) and one object per
+(kernel family, words per link W) from orlg_inst_{wave,group,phy,phy_trace}.hip.  An object is rebuilt when any file its depfile names (or the flags) changed,
 so an edit of one kernel family recompiles that family only.
 """
 import concurrent.futures
@@ -28,7 +28,8 @@ PHY_W = (1, 2, 3, 4, 5)
 
 def units():
     """(object name, source, extra defines)"""
-    u = [("orlg_api", "orlg_api.hip", []), ("orlg_phy_api", "orlg_phy_api.hip", []), ("orlg_osnr", "orlg_osnr.hip", [])]
+    u = [("orlg_host", "orlg_host.hip", []), ("orlg_api", "orlg_api.hip", []), ("orlg_phy_api", "orlg_phy_api.hip", []),
+         ("orlg_osnr", "orlg_osnr.hip", [])]
     # the largest objects first: the pool then finishes with the small ones
     for w in sorted(WAVE_W, reverse=True):
         u.append((f"orlg_inst_wave_w{w}", "orlg_inst_wave.hip", [f"-DORLG_INST_W={w}"]))

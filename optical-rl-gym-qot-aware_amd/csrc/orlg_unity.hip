@@ -4,6 +4,7 @@
 #ifndef ORLG_INST_W
 #define ORLG_INST_W 5
 #endif
+#include "orlg_host.hip"
 #include "orlg_api.hip"
 #include "orlg_phy_api.hip"
 #include "orlg_osnr.hip"

@@ -1,4 +1,5 @@
-"""Checkpoint / resume of the batched state (orlg_save_state / orlg_load_state): a restored batch continues bit for bit."""
+"""Checkpoint / resume of the batched state (orlg_save_state / orlg_load_state): a restored batch continues bit for bit.  Then
+what both kinds of handle share on the host -- reseed, set_stream, save / load, the reductions -- with one body for both."""
 import numpy as np
 import pytest
 
@@ -47,3 +48,104 @@ def test_phy_save_load_resume():
     assert np.array_equal(a.available_channels(), b.available_channels())
     assert a.channel_state(3) == b.channel_state(3)
     a.close(); b.close()
+
+
+# ------------------------------------------------------------------------------------------------ both kinds of handle
+# B = 4; RMSA on NSFNET-320, the QoT-aware handle on US14 (the network the suite has QoT tables for)
+B = 4
+RMSA_KW = dict(num_spectrum_resources=320, load=50, mean_service_holding_time=25, episode_length=1000)
+PHY_KW = dict(episode_length=200, grooming=True, load=1400, mean_service_holding_time=25)
+POLICY = {"rmsa": "sap_ff", "phy": "sapff"}
+OUTS = ("act_path", "accepted", "arrival", "holding")
+
+
+def make(kind, nsfnet, seed=3, **extra):
+    if kind == "rmsa":
+        return make_batched(nsfnet, dict(RMSA_KW, seed=seed), B, **extra)
+    return make_env(load_topology("us14_3-paths_6-modulations"), load_phy_tables("us14_k3"), dict(PHY_KW, seed=seed), B, **extra)
+
+
+def state(env):
+    occ = env.occupancy_words() if hasattr(env, "occupancy_words") else env.available_channels()
+    return dict(env.counters(), current_time=env.current_time(), occupancy=occ)
+
+
+def same(a, b):
+    assert a.keys() == b.keys()
+    for k in a:
+        assert np.ascontiguousarray(a[k]).tobytes() == np.ascontiguousarray(b[k]).tobytes(), k
+
+
+@pytest.mark.parametrize("kind", ["rmsa", "phy"])
+def test_reseed_and_full_reset_equal_a_fresh_handle(nsfnet, kind):
+    env = make(kind, nsfnet, seed=3)
+    env.run(POLICY[kind], 20)
+    env.reseed(77)
+    env.reset(only_episode_counters=False)
+    env.run(POLICY[kind], 50)
+    fresh = make(kind, nsfnet, seed=77)
+    fresh.run(POLICY[kind], 50)
+    same(state(env), state(fresh))
+    env.close(); fresh.close()
+
+
+@pytest.mark.parametrize("kind", ["rmsa", "phy"])
+def test_a_new_stream_between_launches_changes_nothing(nsfnet, kind):
+    env, straight = make(kind, nsfnet), make(kind, nsfnet)
+    env.run(POLICY[kind], 10)
+    env.set_stream(None)          # the handle drops its stream and creates another
+    env.run(POLICY[kind], 40)
+    straight.run(POLICY[kind], 50)
+    same(state(env), state(straight))
+    env.close(); straight.close()
+
+
+@pytest.mark.parametrize("traced", [False, True])
+@pytest.mark.parametrize("kind", ["rmsa", "phy"])
+def test_load_state_rewinds_the_handle(nsfnet, kind, traced):
+    """save_state, 30 steps, load_state, 30 steps: the second 30 are the first 30 -- also for a handle that replays a trace, whose
+    position comes back with the state."""
+    from optical_rl_gym_amd import record_trace
+    from test_gpu_trace import phy as phy_trace_env, rmsa as rmsa_trace_env
+    env = make(kind, nsfnet)
+    if traced:
+        trace = record_trace(env, POLICY[kind], 80, outputs=OUTS)
+        env.close()
+        if kind == "rmsa":
+            env = rmsa_trace_env(nsfnet, B, trace=trace)
+        else:
+            env = phy_trace_env(load_topology("us14_3-paths_6-modulations"), load_phy_tables("us14_k3"),
+                                dict(episode_length=200, grooming=True), B, trace=trace)
+    env.run(POLICY[kind], 10)
+    position = env.trace_position
+    assert position == (11 if traced else 0)
+    snap = env.save_state()
+    first = env.run(POLICY[kind], 30, outputs=OUTS)
+    after = state(env)
+    assert env.trace_position == (41 if traced else 0)
+    env.load_state(snap)
+    assert env.trace_position == position
+    again = env.run(POLICY[kind], 30, outputs=OUTS)
+    for k in OUTS:
+        assert first[k].tobytes() == again[k].tobytes(), k
+    same(after, state(env))
+    env.close()
+
+
+@pytest.mark.parametrize("kind", ["rmsa", "phy"])
+def test_reductions_equal_the_sums_of_the_counters(nsfnet, kind):
+    """reduce_counters is the sum of get_counters over the batch; reduce_counters(by_group=True) with two groups the sum per group."""
+    from optical_rl_gym_amd.batched import COUNTER_NAMES
+    groups = np.array([0, 1, 1, 0], np.int32)
+    env = make(kind, nsfnet, groups=groups, num_groups=2)
+    env.run(POLICY[kind], 50)
+    per_env = env.counters()
+    _, total = env.reduce_counters()
+    grouped = env.reduce_counters(by_group=True)
+    assert grouped.shape == (2, 16)
+    for i, name in enumerate(COUNTER_NAMES):
+        assert total[i] == per_env[name].sum(), name
+        for g in range(2):
+            assert grouped[g, i] == per_env[name][groups == g].sum(), (name, g)
+    assert total[9] == B and list(grouped[:, 9]) == [2, 2]
+    env.close()
