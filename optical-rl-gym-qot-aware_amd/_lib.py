@@ -94,11 +94,58 @@ PHY_STEP_IO_DTYPES = {"act_path": "int32", "n_channels": "int32", "channels": "i
                       "defrag_counters": "int32", "gn_gsnr_db": "float64"}
 PHY_POLICIES = {"external": -1, "bmfa": 0, "bmfa_rss": 1, "sapff": 2, "bmff": 3, "sapbm": 4, "faff": 5, "faff_rss": 6}
 
+def _prototypes():
+    """name -> (restype or None, argtypes or None) of every function include/orlg.h declares; None leaves ctypes' default
+    (an int result; arguments converted as they come).  What works on the handle core both C APIs share exists under both
+    prefixes with one prototype; ``_handle.BatchedHandle`` is written against those."""
+    P, vp, i32, i64, u64 = C.POINTER, C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
+    t = {"orlg_abi_version": (C.c_int, None), "orlg_last_error": (C.c_char_p, None), "orlg_device_count": (C.c_int, None),
+         "orlg_host_log": (C.c_double, [C.c_double]),
+         "orlg_gn_osnr": (None, None)}   # (its argtypes are set next to its struct, osnr.py)
+    for p, config in (("orlg_", RmsaConfig), ("orlg_phy_", PhyConfig)):
+        create = [P(Topology), P(config), i32, vp, u64, i32]
+        t.update({p + "create": (None, create + [P(vp)]),
+                  p + "create_traffic": (None, create + [P(Traffic), P(vp)]),   # per-environment traffic (orlg_traffic)
+                  p + "create_trace": (None, [P(Topology), P(config), i32, i32, P(Trace), P(vp)]),   # request traces (orlg_trace)
+                  p + "destroy": (None, [vp]), p + "set_stream": (None, [vp, vp]), p + "synchronize": (None, [vp]),
+                  p + "last_kernel": (None, [vp, C.c_char_p, i32]), p + "reset": (None, [vp, i32]),
+                  p + "reseed": (None, [vp, vp, u64]), p + "trace_length": (i64, [vp]), p + "trace_position": (i64, [vp]),
+                  p + "words_per_link": (None, [vp]), p + "num_groups": (None, [vp]), p + "state_size": (i64, [vp]),
+                  p + "get_traffic": (None, [vp, vp, vp, vp])})
+        for name in ("get_requests", "get_counters", "get_current_time", "get_num_running", "get_occupancy", "save_state",
+                     "load_state", "reduce_counters", "reduce_counters_grouped"):
+            t[p + name] = (None, [vp, vp])
+    # RMSA / DeepRMSA only
+    t.update({"orlg_step": (None, [vp, i32, i32, vp, i32, P(StepIO)]), "orlg_launch_info": (None, [vp, vp]),
+              "orlg_get_link_stats": (None, [vp, vp, vp, vp, vp]), "orlg_get_graph_stats": (None, [vp, vp, vp, vp]),
+              "orlg_get_bit_rate_hist": (None, [vp, vp, vp, vp, vp]), "orlg_get_episodes_done": (None, [vp, vp]),
+              "orlg_query_path_masks": (None, [vp, i32, vp, vp]), "orlg_query_path_mask": (None, [vp, i32, i32, vp, vp]),
+              "orlg_deeprmsa_observation": (None, [vp, vp]), "orlg_deeprmsa_observation_f32": (None, [vp, vp]),
+              "orlg_deeprmsa_obs_dim": (None, [vp]), "orlg_simple_matrix_observation": (None, [vp, vp]),
+              "orlg_simple_matrix_obs_dim": (None, [vp]),
+              # valid-action masks for the whole batch
+              "orlg_set_allow_rejection": (None, [vp, i32]), "orlg_deeprmsa_mask_dim": (None, [vp]),
+              "orlg_deeprmsa_observation_masked": (None, [vp, vp, i32, vp]), "orlg_action_masks": (None, [vp, vp, vp])})
+    # QoT-aware only
+    t.update({"orlg_phy_step": (None, [vp, i32, i32, vp, vp, i32, P(PhyStepIO)]), "orlg_phy_node_vectors": (None, [vp]),
+              "orlg_phy_get_episode_stats": (None, [vp, vp]), "orlg_phy_channel_masks": (None, [vp, vp]),
+              "orlg_phy_get_channel_state": (None, [vp, i32, vp, vp]), "orlg_phy_channel_state_capacity": (None, [vp]),
+              # bit_rate_selection="continuous": float64 shares
+              "orlg_phy_continuous": (None, [vp]),
+              "orlg_phy_step_ex": (None, [vp, i32, i32, vp, vp, vp, i32, P(PhyStepIO), vp, vp]),
+              "orlg_phy_get_channel_state_f64": (None, [vp, i32, vp, vp]),
+              "orlg_phy_load_state_checked": (None, [vp, vp, i64])})
+    return t
+
+
+PROTOTYPES = _prototypes()
+EXPORTED_SYMBOLS = list(PROTOTYPES)
+
 _lib = None
 
 
 def load(build_if_missing=True):
-    """Load liborlg.so, building it with hipcc first when it is missing or stale."""
+    """Load liborlg.so, building it with hipcc first when it is missing or stale, and give every function its prototype."""
     global _lib
     if _lib is not None:
         return _lib
@@ -109,113 +156,14 @@ def load(build_if_missing=True):
     if not os.path.exists(LIB_PATH):
         raise OrlgError(-2, f"{LIB_PATH} is missing: run python optical-rl-gym-qot-aware_amd/build.py (needs hipcc)")
     L = C.CDLL(LIB_PATH)
-    vp, i32, i64, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
-    L.orlg_abi_version.restype = C.c_int
-    L.orlg_last_error.restype = C.c_char_p
-    L.orlg_device_count.restype = C.c_int
-    L.orlg_create.argtypes = [C.POINTER(Topology), C.POINTER(RmsaConfig), i32, vp, u64, i32, C.POINTER(vp)]
-    L.orlg_destroy.argtypes = [vp]
-    L.orlg_set_stream.argtypes = [vp, vp]
-    L.orlg_synchronize.argtypes = [vp]
-    L.orlg_launch_info.argtypes = [vp, vp]
-    L.orlg_last_kernel.argtypes = [vp, C.c_char_p, i32]
-    L.orlg_phy_last_kernel.argtypes = [vp, C.c_char_p, i32]
-    L.orlg_reset.argtypes = [vp, i32]
-    L.orlg_reseed.argtypes = [vp, vp, C.c_uint64]
-    L.orlg_step.argtypes = [vp, i32, i32, vp, i32, C.POINTER(StepIO)]
-    L.orlg_get_requests.argtypes = [vp, vp]
-    L.orlg_get_counters.argtypes = [vp, vp]
-    L.orlg_get_current_time.argtypes = [vp, vp]
-    L.orlg_get_occupancy.argtypes = [vp, vp]
-    L.orlg_words_per_link.argtypes = [vp]
-    L.orlg_get_link_stats.argtypes = [vp, vp, vp, vp, vp]
-    L.orlg_get_graph_stats.argtypes = [vp, vp, vp, vp]
-    L.orlg_get_bit_rate_hist.argtypes = [vp, vp, vp, vp, vp]
-    L.orlg_get_num_running.argtypes = [vp, vp]
-    L.orlg_get_episodes_done.argtypes = [vp, vp]
-    L.orlg_query_path_masks.argtypes = [vp, i32, vp, vp]
-    L.orlg_query_path_mask.argtypes = [vp, i32, i32, vp, vp]
-    L.orlg_deeprmsa_observation.argtypes = [vp, vp]
-    L.orlg_deeprmsa_observation_f32.argtypes = [vp, vp]
-    L.orlg_deeprmsa_obs_dim.argtypes = [vp]
-    # valid-action masks for the whole batch (include/orlg.h)
-    L.orlg_set_allow_rejection.argtypes = [vp, i32]
-    L.orlg_deeprmsa_mask_dim.argtypes = [vp]
-    L.orlg_deeprmsa_observation_masked.argtypes = [vp, vp, i32, vp]
-    L.orlg_action_masks.argtypes = [vp, vp, vp]
-    L.orlg_phy_channel_masks.argtypes = [vp, vp]
-    L.orlg_reduce_counters.argtypes = [vp, vp]
-    L.orlg_simple_matrix_observation.argtypes = [vp, vp]
-    L.orlg_simple_matrix_obs_dim.argtypes = [vp]
-    L.orlg_phy_create.argtypes = [C.POINTER(Topology), C.POINTER(PhyConfig), i32, vp, u64, i32, C.POINTER(vp)]
-    L.orlg_phy_destroy.argtypes = [vp]
-    L.orlg_phy_set_stream.argtypes = [vp, vp]
-    L.orlg_phy_synchronize.argtypes = [vp]
-    L.orlg_phy_reset.argtypes = [vp, i32]
-    L.orlg_phy_reseed.argtypes = [vp, vp, C.c_uint64]
-    L.orlg_phy_step.argtypes = [vp, i32, i32, vp, vp, i32, C.POINTER(PhyStepIO)]
-    L.orlg_phy_words_per_link.argtypes = [vp]
-    L.orlg_phy_node_vectors.argtypes = [vp]
-    for name in ("orlg_phy_get_requests", "orlg_phy_get_counters", "orlg_phy_get_current_time",
-                 "orlg_phy_get_num_running", "orlg_phy_get_episode_stats", "orlg_phy_get_occupancy",
-                 "orlg_phy_reduce_counters"):
-        getattr(L, name).argtypes = [vp, vp]
-    for name in ("orlg_state_size", "orlg_phy_state_size"):
-        getattr(L, name).argtypes = [vp]
-        getattr(L, name).restype = i64
-    for name in ("orlg_save_state", "orlg_load_state", "orlg_phy_save_state", "orlg_phy_load_state"):
-        getattr(L, name).argtypes = [vp, vp]
-    L.orlg_phy_get_channel_state.argtypes = [vp, i32, vp, vp]
-    L.orlg_phy_channel_state_capacity.argtypes = [vp]
-    # bit_rate_selection="continuous": float64 shares (include/orlg.h)
-    L.orlg_phy_continuous.argtypes = [vp]
-    L.orlg_phy_step_ex.argtypes = [vp, i32, i32, vp, vp, vp, i32, C.POINTER(PhyStepIO), vp, vp]
-    L.orlg_phy_get_channel_state_f64.argtypes = [vp, i32, vp, vp]
-    L.orlg_phy_load_state_checked.argtypes = [vp, vp, i64]
-    # per-environment traffic, per-group statistics (include/orlg.h orlg_traffic)
-    L.orlg_create_traffic.argtypes = [C.POINTER(Topology), C.POINTER(RmsaConfig), i32, vp, u64, i32, C.POINTER(Traffic),
-                                      C.POINTER(vp)]
-    L.orlg_phy_create_traffic.argtypes = [C.POINTER(Topology), C.POINTER(PhyConfig), i32, vp, u64, i32, C.POINTER(Traffic),
-                                          C.POINTER(vp)]
-    for name in ("orlg_get_traffic", "orlg_phy_get_traffic"):
-        getattr(L, name).argtypes = [vp, vp, vp, vp]
-    for name in ("orlg_num_groups", "orlg_phy_num_groups"):
-        getattr(L, name).argtypes = [vp]
-    for name in ("orlg_reduce_counters_grouped", "orlg_phy_reduce_counters_grouped"):
-        getattr(L, name).argtypes = [vp, vp]
-    # request traces (include/orlg.h orlg_trace)
-    L.orlg_create_trace.argtypes = [C.POINTER(Topology), C.POINTER(RmsaConfig), i32, i32, C.POINTER(Trace), C.POINTER(vp)]
-    L.orlg_phy_create_trace.argtypes = [C.POINTER(Topology), C.POINTER(PhyConfig), i32, i32, C.POINTER(Trace), C.POINTER(vp)]
-    for name in ("orlg_trace_length", "orlg_trace_position", "orlg_phy_trace_length", "orlg_phy_trace_position"):
-        getattr(L, name).argtypes = [vp]
-        getattr(L, name).restype = i64
-    L.orlg_host_log.argtypes = [C.c_double]
-    L.orlg_host_log.restype = C.c_double
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        f = getattr(L, name)
+        if restype is not None:
+            f.restype = restype
+        if argtypes is not None:
+            f.argtypes = argtypes
     _lib = L
     return L
-
-
-EXPORTED_SYMBOLS = [
-    "orlg_abi_version", "orlg_last_error", "orlg_device_count", "orlg_create", "orlg_destroy", "orlg_set_stream",
-    "orlg_synchronize", "orlg_launch_info", "orlg_last_kernel", "orlg_phy_last_kernel", "orlg_reset", "orlg_reseed", "orlg_step", "orlg_get_requests", "orlg_get_counters",
-    "orlg_get_current_time", "orlg_get_occupancy", "orlg_words_per_link", "orlg_get_link_stats",
-    "orlg_get_graph_stats", "orlg_get_bit_rate_hist", "orlg_get_num_running", "orlg_get_episodes_done",
-    "orlg_query_path_masks", "orlg_query_path_mask", "orlg_deeprmsa_observation", "orlg_deeprmsa_observation_f32", "orlg_deeprmsa_obs_dim", "orlg_reduce_counters",
-    "orlg_simple_matrix_observation", "orlg_simple_matrix_obs_dim", "orlg_host_log",
-    "orlg_phy_create", "orlg_phy_destroy", "orlg_phy_set_stream", "orlg_phy_synchronize", "orlg_phy_reset", "orlg_phy_reseed",
-    "orlg_phy_step", "orlg_phy_words_per_link", "orlg_phy_node_vectors", "orlg_phy_get_requests", "orlg_phy_get_counters",
-    "orlg_phy_get_current_time", "orlg_phy_get_num_running", "orlg_phy_get_episode_stats",
-    "orlg_phy_get_occupancy", "orlg_phy_reduce_counters", "orlg_phy_get_channel_state",
-    "orlg_phy_channel_state_capacity", "orlg_gn_osnr", "orlg_state_size", "orlg_save_state", "orlg_load_state",
-    "orlg_phy_state_size", "orlg_phy_save_state", "orlg_phy_load_state",
-    "orlg_phy_continuous", "orlg_phy_step_ex", "orlg_phy_get_channel_state_f64", "orlg_phy_load_state_checked",
-    "orlg_create_traffic", "orlg_get_traffic", "orlg_num_groups", "orlg_reduce_counters_grouped",
-    "orlg_phy_create_traffic", "orlg_phy_get_traffic", "orlg_phy_num_groups", "orlg_phy_reduce_counters_grouped",
-    "orlg_create_trace", "orlg_trace_length", "orlg_trace_position",
-    "orlg_phy_create_trace", "orlg_phy_trace_length", "orlg_phy_trace_position",
-    "orlg_deeprmsa_observation_masked", "orlg_deeprmsa_mask_dim", "orlg_action_masks", "orlg_phy_channel_masks",
-    "orlg_set_allow_rejection",
-]
 
 
 def check(rc):

@@ -11,99 +11,19 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from . import _lib, trace as _trace, traffic as _traffic
-from .topology import FrozenTopology, selection_tables
+from . import _lib, trace as _trace
+from ._handle import COUNTER_NAMES, REQUEST_DTYPE, SweepTraffic  # noqa: F401  (their import path: bench.py, tools/, tests)
+from ._handle import BatchedHandle, _check_buffer, _dtype_name, _output_names, _ptr
 
 DEFAULT_BIT_RATES = (200, 250, 300, 350, 400, 450, 500, 550, 600, 650, 700, 750, 800, 850, 900, 950, 1000, 1050,
                      1100, 1150, 1200)  # rmsa_env.py:37-38
 
-COUNTER_NAMES = ("services_processed", "services_accepted", "episode_services_processed",
-                 "episode_services_accepted", "bit_rate_requested", "bit_rate_provisioned",
-                 "episode_bit_rate_requested", "episode_bit_rate_provisioned")
-
-REQUEST_DTYPE = np.dtype([("service_id", np.int32), ("src", np.int32), ("dst", np.int32), ("bit_rate", np.int32),
-                          ("arrival_time", np.float64), ("holding_time", np.float64)])
+_STEP_IO_SHAPES = {"request": (4,)}   # per-step outputs wider than [n_steps, B]
 
 
-def _ptr(a):
-    """Pointer of a numpy array, a torch tensor (host or device) or None."""
-    if a is None:
-        return None
-    if hasattr(a, "data_ptr"):
-        return C.c_void_p(a.data_ptr())
-    return a.ctypes.data_as(C.c_void_p)
+class BatchedRMSAEnv(BatchedHandle):
+    PREFIX = "orlg_"
 
-
-def _dtype_name(a):
-    """'int32', 'float64', ... of a numpy array or a torch tensor."""
-    return str(a.dtype).replace("torch.", "")
-
-
-class SweepTraffic:
-    """``load=`` / ``mean_service_holding_time=`` / ``groups=`` of a batched constructor.  Scalars without groups: the
-    handle is created as ever (``orlg_create`` / ``orlg_phy_create``).  Length-B array-likes, or ``groups=`` (also next to a
-    scalar load): the handle is created with ``orlg_traffic`` (include/orlg.h) and the environments carry their own rates.
-    ``groups=`` and ``load=`` are independent: a group is any set of environments whose counters are summed together; the
-    per-load Monitor tree and summary (monitor.py) need every group to be ONE load and refuse anything else.
-    Shapes and values of a per-environment call are checked here, before the library is loaded."""
-
-    def __init__(self, batch_size, load, mean_service_holding_time, groups=None, num_groups=None):
-        self.batch_size = int(batch_size)
-        self.per_env = np.ndim(load) > 0 or np.ndim(mean_service_holding_time) > 0 or groups is not None
-        self._group_given = groups is not None
-        if not self.per_env and num_groups not in (None, 1):
-            raise ValueError("num_groups without groups")
-        if self.per_env:
-            self.arrival_lambda, self.holding_lambda = _traffic.per_env_rates(batch_size, load, mean_service_holding_time)
-            self.loads = np.broadcast_to(np.asarray(load, np.float64), (self.batch_size,)).copy()
-            self.groups, self.num_groups = _traffic.check_groups(batch_size, groups, num_groups)
-        else:   # a scalar call: nothing is checked or computed here, the library sees what it always saw
-            self.arrival_lambda = self.holding_lambda = None
-            self.loads = np.full(max(self.batch_size, 0), float(load), np.float64)
-            self.groups, self.num_groups = np.zeros(max(self.batch_size, 0), np.int32), 1
-
-    def _need_rates(self):
-        if not self.per_env:
-            raise RuntimeError("a handle with scalar rates has no orlg_traffic")
-
-    def largest(self):
-        """Index of the environment with the largest offered load (what the library sizes its capacities from)."""
-        self._need_rates()
-        return int(np.argmax(self.arrival_lambda / self.holding_lambda))
-
-    def struct(self):
-        """The ``orlg_traffic`` of the handle (the arrays stay referenced by this object)."""
-        self._need_rates()
-        t = _lib.Traffic()
-        t.arrival_lambda = self.arrival_lambda.ctypes.data_as(C.c_void_p)
-        t.holding_lambda = self.holding_lambda.ctypes.data_as(C.c_void_p)
-        t.group = self.groups.ctypes.data_as(C.c_void_p) if self._group_given else None
-        t.num_groups = self.num_groups
-        return t
-
-
-def _grouped_counters(call, h, num_groups):
-    a = np.zeros((num_groups, 16), np.int64)
-    _lib.check(call(h, _ptr(a)))
-    return a
-
-
-def _check_buffer(name, a, shape, dtype):
-    """A caller-supplied array the library reads or writes through a raw pointer: shape, dtype and layout must be exactly
-    what the C ABI expects (a wrong dtype would be reinterpreted, a short array overrun)."""
-    if tuple(a.shape) != tuple(shape):
-        raise ValueError(f"{name}: shape {tuple(a.shape)}, expected {tuple(shape)}")
-    if _dtype_name(a) != str(np.dtype(dtype)):
-        raise TypeError(f"{name}: dtype {_dtype_name(a)}, expected {np.dtype(dtype)}")
-    contiguous = a.is_contiguous() if hasattr(a, "is_contiguous") else a.flags["C_CONTIGUOUS"]
-    if not contiguous:
-        raise ValueError(f"{name}: must be C-contiguous")
-    if not hasattr(a, "data_ptr") and not a.flags["WRITEABLE"] and name.startswith("out"):
-        raise ValueError(f"{name}: read-only array")
-    return a
-
-
-class BatchedRMSAEnv:
     def __init__(self, topology, batch_size: int, *, episode_length: int = 1000, load: float = None,
                  mean_service_holding_time: float = None, num_spectrum_resources: int = 100,
                  bit_rate_selection: str = "discrete", bit_rates: Sequence[int] = DEFAULT_BIT_RATES,
@@ -112,13 +32,7 @@ class BatchedRMSAEnv:
                  reward_mode: int = 0, stats_level: str = "full", queue_capacity: int = 0, device: int = 0,
                  step_kernel: str = "auto", bit_rate_lower_bound=25, bit_rate_higher_bound=100, groups=None,
                  num_groups=None, trace=None):
-        # trace=: the handle replays a RequestTrace (trace.py) instead of generating its traffic; the arguments that describe
-        # generated traffic cannot be passed with it.  groups= stays: it feeds reduce_counters(by_group=True)
-        _trace.check_trace_kwargs(trace, dict(load=load, mean_service_holding_time=mean_service_holding_time, seed=seed,
-                                              seeds=seeds))
-        self.trace = trace
-        load = 10 if load is None else load                                                      # rmsa_env.py:31-32
-        mean_service_holding_time = 10800.0 if mean_service_holding_time is None else mean_service_holding_time
+        load, mean_service_holding_time = self._init_traffic_kwargs(trace, load, mean_service_holding_time, seed, seeds)
         if bit_rate_selection not in ("continuous", "discrete"):   # rmsa_env.py:74
             raise ValueError("bit_rate_selection must be 'continuous' or 'discrete'")
         self.bit_rate_selection = bit_rate_selection
@@ -131,122 +45,28 @@ class BatchedRMSAEnv:
                 raise ValueError("continuous bit rates: at most 256 integer rates (lower .. higher)")
             self.bit_rate_lower_bound, self.bit_rate_higher_bound = lo, hi
             bit_rates, bit_rate_probabilities = list(range(lo, hi + 1)), None
-        # load= / mean_service_holding_time= may be length-B array-likes (a load sweep in one handle, traffic.py)
-        self.traffic = SweepTraffic(batch_size, load, mean_service_holding_time, None if trace is not None else groups,
-                                    None if trace is not None else num_groups)
-        self.topology = FrozenTopology.from_graph(topology)
-        t = self.topology
-        if trace is not None:   # checked before the library is loaded: the rules of orlg_create_trace
-            self.trace = trace = trace.for_batch(batch_size)
-            trace.validate(num_nodes=t.num_nodes, **({"bit_rate_bounds": (bit_rates[0], bit_rates[-1])}
-                                                     if bit_rate_selection == "continuous" else {"bit_rates": bit_rates}))
-            self.traffic.groups, self.traffic.num_groups = _trace.trace_groups(batch_size, groups, num_groups)
-            self._trace_groups = groups is not None
-        self.L = _lib.load()
-        self.batch_size = int(batch_size)
-        self.episode_length = int(episode_length)
+        tables = self._open(topology, batch_size, episode_length, load, mean_service_holding_time, bit_rates,
+                            bit_rate_selection == "continuous", bit_rate_probabilities, node_request_probabilities, seed,
+                            groups, num_groups)
         self.num_spectrum_resources = int(num_spectrum_resources)
-        self.k_paths = t.k_paths
         self.j = int(j)
         self.allow_rejection = bool(allow_rejection)
         self.reject_action = 1 if allow_rejection else 0
         self.channel_width = float(channel_width)
-        self.bit_rates = [int(b) for b in bit_rates]
-        # optical_network_env.py:111-129
-        self.load = load
-        self.mean_service_holding_time = mean_service_holding_time
-        if self.traffic.per_env:
-            self.mean_service_inter_arrival_time = 1 / self.traffic.arrival_lambda
-        else:
-            self.mean_service_inter_arrival_time = 1 / float(load / float(mean_service_holding_time))
-        self.loads, self.groups, self.num_groups = self.traffic.loads, self.traffic.groups, self.traffic.num_groups
-        self.node_request_probabilities, src_cum, dst_cum, br_cum = selection_tables(
-            node_request_probabilities, bit_rate_probabilities, t.num_nodes, self.bit_rates)
-        self.rand_seed = 41 if seed is None else int(seed)  # optical_network_env.py:266-271
         self.stats_level = stats_level
-
-        self._keep = []
-
-        def keep(a, dt):
-            a = np.ascontiguousarray(a, dtype=dt)
-            self._keep.append(a)
-            return a.ctypes.data_as(C.c_void_p)
-
-        ct = _lib.Topology()
-        ct.num_nodes, ct.num_links, ct.k_paths, ct.num_paths = t.num_nodes, t.num_links, t.k_paths, t.num_paths
-        ct.pair_path_base = keep(t.pair_path_base, np.int32)
-        ct.pair_path_count = keep(t.pair_path_count, np.int32)
-        ct.path_hops = keep(t.path_hops, np.int32)
-        ct.path_se = keep(t.path_se, np.int32)
-        ct.path_length = keep(t.path_length, np.float64)
-        ct.path_link_off = keep(t.path_link_off, np.int32)
-        ct.path_links = keep(t.path_links, np.int32)
         cc = _lib.RmsaConfig()
         cc.num_slots, cc.episode_length, cc.num_bit_rates = self.num_spectrum_resources, self.episode_length, len(self.bit_rates)
         cc.j, cc.reward_mode, cc.queue_capacity = self.j, int(reward_mode), int(queue_capacity)
         cc.stats_level = _lib.STATS_LEVELS[stats_level]
         cc.step_kernel = _lib.STEP_KERNELS[step_kernel]
-        # rmsa_env.py:646-651: expovariate(1 / mean)
-        if self.traffic.per_env:   # (ignored by orlg_create_traffic; the pair of the largest load, for the record)
-            cc.arrival_lambda = self.traffic.arrival_lambda[self.traffic.largest()]
-            cc.holding_lambda = self.traffic.holding_lambda[self.traffic.largest()]
-        else:
-            cc.arrival_lambda = 1 / self.mean_service_inter_arrival_time
-            cc.holding_lambda = 1 / self.mean_service_holding_time
         cc.channel_width = self.channel_width
-        cc.bit_rates = keep(self.bit_rates, np.int32)
-        cc.bit_rate_cum = keep(br_cum, np.float64) if bit_rate_selection == "discrete" else None   # (NULL: rng.randint)
-        cc.src_cum = keep(src_cum, np.float64)
-        cc.dst_cum = keep(dst_cum, np.float64)
-        seeds_ptr = None
-        if seeds is not None:
-            seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-            assert seeds.shape == (self.batch_size,)
-            seeds_ptr = seeds.ctypes.data_as(C.c_void_p)
-        h = C.c_void_p()
-        if trace is not None:
-            ts = trace.struct(self.groups if self._trace_groups else None, self.num_groups)
-            _lib.check(self.L.orlg_create_trace(C.byref(ct), C.byref(cc), self.batch_size, int(device), C.byref(ts), C.byref(h)))
-        elif self.traffic.per_env:
-            tr = self.traffic.struct()
-            _lib.check(self.L.orlg_create_traffic(C.byref(ct), C.byref(cc), self.batch_size, seeds_ptr,
-                                                  C.c_uint64(self.rand_seed), int(device), C.byref(tr), C.byref(h)))
-        else:
-            _lib.check(self.L.orlg_create(C.byref(ct), C.byref(cc), self.batch_size, seeds_ptr,
-                                          C.c_uint64(self.rand_seed), int(device), C.byref(h)))
-        self.h = h
-        self.device = int(device)
-        self.words_per_link = self.L.orlg_words_per_link(self.h)
+        self._fill_traffic(cc, *tables)
+        self._create(self._topology_struct(), cc, seeds, device)
         self.obs_dim = self.L.orlg_deeprmsa_obs_dim(self.h)
         # the explicit rejection is one more column of the action masks (the step kernels need no flag: an action out of range
         # is a rejection either way)
         _lib.check(self.L.orlg_set_allow_rejection(self.h, self.reject_action))
         self.mask_dim = self.L.orlg_deeprmsa_mask_dim(self.h)
-
-    # ------------------------------------------------------------------ lifetime
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.orlg_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_ptr):
-        """Run on an existing HIP stream, e.g. ``torch.cuda.current_stream().cuda_stream``."""
-        _lib.check(self.L.orlg_set_stream(self.h, C.c_void_p(stream_ptr) if stream_ptr else None))
-
-    def synchronize(self):
-        _lib.check(self.L.orlg_synchronize(self.h))
-
-    def last_kernel(self) -> str:
-        """Name, template arguments and launch shape of the kernel behind the last ``run`` / ``reset``."""
-        buf = C.create_string_buffer(128)
-        _lib.check(self.L.orlg_last_kernel(self.h, buf, 128))
-        return buf.value.decode()
 
     def launch_info(self):
         """Launch geometry of the step kernel (envs per workgroup, LDS bytes, resident workgroups per CU)."""
@@ -256,37 +76,6 @@ class BatchedRMSAEnv:
                 "workgroups_per_cu": int(a[2]), "words_per_link": int(a[3])}
 
     # ------------------------------------------------------------------ stepping
-    def reset(self, only_episode_counters: bool = True):
-        _lib.check(self.L.orlg_reset(self.h, 1 if only_episode_counters else 0))
-
-    def reseed(self, seed=None, seeds=None):
-        """A fresh ``random.Random`` for every environment -- ``seeds[i]`` if given, else ``seed + i`` (the constructor's
-        convention) -- and nothing else changes: the pending requests stay, the next arrivals are the new generators' first
-        draws.  NOT the reference's ``seed()``: there the bit-rate draw stays bound to the generator object of construction time
-        (``functools.partial(self.rng.choices, ...)``, ``rmsa_env.py:109-111``), so after ``env.seed(s)`` the reference takes
-        inter-arrival time, holding time, source and destination from ``Random(s)`` and the bit rate from the OLD generator
-        (pinned by ``tests/golden/seed_rmsa_nsfnet_s10.npz``); here all five draws come from the new one.  A handle that
-        replays a trace has no generator: ``ValueError``."""
-        if self.trace is not None:
-            raise ValueError("a handle that replays a trace has no generator to seed")
-        if seeds is not None:
-            sa = np.ascontiguousarray(seeds, np.uint64)
-            if sa.shape != (self.batch_size,):
-                raise ValueError(f"seeds: shape {sa.shape}, expected ({self.batch_size},)")
-            _lib.check(self.L.orlg_reseed(self.h, _ptr(sa), 0))
-        else:
-            _lib.check(self.L.orlg_reseed(self.h, None, int(41 if seed is None else seed)))
-
-    @property
-    def trace_length(self) -> int:
-        """Requests per environment of the handle's trace, 0 for a handle that generates its traffic."""
-        return int(self.L.orlg_trace_length(self.h))
-
-    @property
-    def trace_position(self) -> int:
-        """Requests drawn so far (the same for every environment): 1 after a full reset, + 1 per step."""
-        return int(self.L.orlg_trace_position(self.h))
-
     def run(self, policy: str, n_steps: int = 1, *, actions=None, auto_reset: bool = False,
             outputs: Sequence[str] = (), out: Optional[Dict[str, object]] = None):
         """``n_steps`` x (policy -> step) on the device.  ``outputs`` names per-step arrays to return
@@ -294,18 +83,7 @@ class BatchedRMSAEnv:
         preallocated numpy arrays or torch tensors (device tensors are written without staging)."""
         B = self.batch_size
         io = _lib.StepIO()
-        res = {}
-        names = list(outputs) + [k for k in (out or {}) if k not in outputs]
-        for name in names:
-            if name not in _lib.STEP_IO_DTYPES:
-                raise KeyError(f"unknown step output {name!r}")
-            shape = (n_steps, B, 4) if name == "request" else (n_steps, B)
-            if out is not None and name in out:
-                arr = _check_buffer(f"out[{name!r}]", out[name], shape, _lib.STEP_IO_DTYPES[name])
-            else:
-                arr = np.zeros(shape, dtype=_lib.STEP_IO_DTYPES[name])
-            res[name] = arr
-            setattr(io, name, _ptr(arr))
+        res = self._step_outputs(_output_names(outputs, out), n_steps, out, _lib.STEP_IO_DTYPES, _STEP_IO_SHAPES, io)
         ap = None
         if policy in ("external", "deeprmsa_external", "path_ff_external"):
             if actions is None:
@@ -333,26 +111,8 @@ class BatchedRMSAEnv:
         return {k: v[0] for k, v in r.items()}
 
     # ------------------------------------------------------------------ state read-back
-    def requests(self):
-        a = np.zeros(self.batch_size, REQUEST_DTYPE)
-        _lib.check(self.L.orlg_get_requests(self.h, _ptr(a)))
-        return a
-
-    def counters(self):
-        a = np.zeros((self.batch_size, 8), np.int64)
-        _lib.check(self.L.orlg_get_counters(self.h, _ptr(a)))
-        return {n: a[:, i].copy() for i, n in enumerate(COUNTER_NAMES)}
-
-    def current_time(self):
-        a = np.zeros(self.batch_size, np.float64)
-        _lib.check(self.L.orlg_get_current_time(self.h, _ptr(a)))
-        return a
-
     def occupancy_words(self):
-        E, W = self.topology.num_links, self.words_per_link
-        a = np.zeros((self.batch_size, E, W), np.uint64)
-        _lib.check(self.L.orlg_get_occupancy(self.h, _ptr(a)))
-        return a
+        return self._occupancy_words()
 
     def available_slots(self):
         """topology.graph["available_slots"] for every env: [B, E, S] uint8 (1 = free)."""
@@ -377,15 +137,8 @@ class BatchedRMSAEnv:
         _lib.check(self.L.orlg_get_bit_rate_hist(self.h, *[_ptr(a) for a in out]))
         return dict(zip(("requested", "provisioned", "episode_requested", "episode_provisioned"), out))
 
-    def num_running(self):
-        a = np.zeros(self.batch_size, np.int32)
-        _lib.check(self.L.orlg_get_num_running(self.h, _ptr(a)))
-        return a
-
     def episodes_done(self):
-        a = np.zeros(self.batch_size, np.int64)
-        _lib.check(self.L.orlg_get_episodes_done(self.h, _ptr(a)))
-        return a
+        return self._read(self.L.orlg_get_episodes_done, self.batch_size, np.int64)
 
     def path_masks(self, env_index: int = 0):
         """(masks [k, W] uint64, nslots [k]) for the pending request of one env."""
@@ -476,39 +229,6 @@ class BatchedRMSAEnv:
         """PathOnlyFirstFitAction.step for every env: ``paths`` is [B] int32 (k = reject)."""
         r = self.run("path_ff_external", 1, actions=paths, outputs=outputs)
         return {k: v[0] for k, v in r.items()}
-
-    def save_state(self):
-        """Snapshot of the complete simulation state of the batch (a uint8 array): checkpoint / resume, env cloning."""
-        n = self.L.orlg_state_size(self.h)
-        if n < 0:
-            _lib.check(int(n))
-        buf = np.empty(int(n), np.uint8)
-        _lib.check(self.L.orlg_save_state(self.h, _ptr(buf)))
-        return buf
-
-    def load_state(self, buf):
-        buf = np.ascontiguousarray(buf, np.uint8)
-        assert buf.size == self.L.orlg_state_size(self.h), "snapshot of a differently configured batch"
-        _lib.check(self.L.orlg_load_state(self.h, _ptr(buf)))
-
-    def traffic_rates(self):
-        """(arrival_lambda [B], holding_lambda [B], group [B]) as the handle holds them."""
-        B = self.batch_size
-        a, h, g = np.zeros(B), np.zeros(B), np.zeros(B, np.int32)
-        _lib.check(self.L.orlg_get_traffic(self.h, _ptr(a), _ptr(h), _ptr(g)))
-        return a, h, g
-
-    def reduce_counters(self, by_group: bool = False):
-        """Summed counters of this shard (raises if a release queue overflowed): the vector a
-        multi-GPU job all-reduces.  ``by_group=True``: the sums per group of environments instead, [G, 16] int64 --
-        columns 0..9 as the vector, 10 / 11 the sums of (processed - accepted)^2, all-time / episode (include/orlg.h)."""
-        if by_group:
-            return _grouped_counters(self.L.orlg_reduce_counters_grouped, self.h, self.num_groups)
-        a = np.zeros(16, np.int64)
-        _lib.check(self.L.orlg_reduce_counters(self.h, _ptr(a)))
-        d = {n: int(a[i]) for i, n in enumerate(COUNTER_NAMES)}
-        d["episodes_done"], d["num_envs"] = int(a[8]), int(a[9])
-        return d, a
 
 
 class BatchedDeepRMSAEnv(BatchedRMSAEnv):

@@ -19,6 +19,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import traffic as _traffic
 from .batched import DEFAULT_BIT_RATES, BatchedDeepRMSAEnv, BatchedRMSAEnv
 from .topology import FrozenTopology, Path, Service
 
@@ -83,11 +84,41 @@ class _LazyGraph(dict):
         return super().__getitem__(key)
 
 
-class RMSAEnv:
-    """Drop-in for ``RMSAEnv`` (``rmsa_env.py:18``) backed by the device path."""
+class _View:
+    """What the single-environment views share (``RMSAEnv`` here, ``PhyRMSAEnv`` in phy_env.py): the mirror of the pending
+    request and the parts of the gym surface that do not touch the device."""
 
     metadata = {"metrics": ["service_blocking_rate", "episode_service_blocking_rate", "bit_rate_blocking_rate",
                             "episode_bit_rate_blocking_rate"]}
+
+    def _service(self, r):
+        """The ``Service`` of one row of ``requests()``."""
+        nodes = self._ft.nodes
+        return Service(int(r["service_id"]), nodes[r["src"]], int(r["src"]), destination=nodes[r["dst"]],
+                       destination_id=int(r["dst"]), arrival_time=float(r["arrival_time"]),
+                       holding_time=float(r["holding_time"]), bit_rate=int(r["bit_rate"]))
+
+    def observation(self):
+        return {"topology": self.topology, "current_service": self.current_service}
+
+    def reward(self):
+        return 1 if self.current_service.accepted else 0
+
+    def seed(self, seed=None):
+        """``optical_network_env.py:266-271``; see ``BatchedRMSAEnv.reseed`` for why this is refused."""
+        raise NotImplementedError(
+            "seed() after construction is not reproduced: the reference keeps drawing the BIT RATE from the generator object of "
+            "construction time (functools.partial(self.rng.choices, ...)) while the other four draws of a request come from "
+            "Random(seed) -- two generators per environment.  Pass seed= to the constructor, or call reseed() on the batched "
+            "environment for a fresh generator for all draws (not the reference's stream).")
+
+    def render(self, mode="human"):
+        return
+
+
+class RMSAEnv(_View):
+    """Drop-in for ``RMSAEnv`` (``rmsa_env.py:18``) backed by the device path."""
+
     _batched_cls = BatchedRMSAEnv
 
     def __init__(self, topology=None, episode_length: int = 1000, load: float = None,
@@ -184,12 +215,7 @@ class RMSAEnv:
     def _sync(self):
         """Refresh the host mirror of the pending request, the counters and the per-path masks."""
         b, i = self._batched, self._index
-        r = b.requests()[i]
-        nodes = self._ft.nodes
-        self.current_service = Service(int(r["service_id"]), nodes[r["src"]], int(r["src"]),
-                                       destination=nodes[r["dst"]], destination_id=int(r["dst"]),
-                                       arrival_time=float(r["arrival_time"]), holding_time=float(r["holding_time"]),
-                                       bit_rate=int(r["bit_rate"]))
+        self.current_service = self._service(b.requests()[i])
         c = b.counters()
         for name, arr in c.items():
             setattr(self, name, int(arr[i]))
@@ -268,23 +294,6 @@ class RMSAEnv:
         return m
 
     # ------------------------------------------------------------------ gym surface
-    def observation(self):
-        return {"topology": self.topology, "current_service": self.current_service}
-
-    def reward(self):
-        return 1 if self.current_service.accepted else 0
-
-    def seed(self, seed=None):
-        """``optical_network_env.py:266-271``; see ``BatchedRMSAEnv.reseed`` for why this is refused."""
-        raise NotImplementedError(
-            "seed() after construction is not reproduced: the reference keeps drawing the BIT RATE from the generator object of "
-            "construction time (functools.partial(self.rng.choices, ...)) while the other four draws of a request come from "
-            "Random(seed) -- two generators per environment.  Pass seed= to the constructor, or call reseed() on the batched "
-            "environment for a fresh generator for all draws (not the reference's stream).")
-
-    def render(self, mode="human"):
-        return
-
     def reset(self, only_episode_counters: bool = True):
         """``rmsa_env.py:343-457``"""
         if self._batched.batch_size != 1:
@@ -337,24 +346,9 @@ class RMSAEnv:
         division, as in the reference), floats from the device statistics."""
         b, i = self._batched, self._index
         c = {k: int(v[i]) for k, v in b.counters().items()}
-        # the reference builds info BEFORE _next_service() (rmsa_env.py:293-335); the device step already
-        # generated the next request, so take its contribution out of the request-side counters again
-        nxt = b.requests()[i]
-        nxt_rate = int(nxt["bit_rate"])
-        c["services_processed"] -= 1
-        c["episode_services_processed"] -= 1
-        c["bit_rate_requested"] -= nxt_rate
-        c["episode_bit_rate_requested"] -= nxt_rate
-        info = {
-            "service_blocking_rate": (c["services_processed"] - c["services_accepted"]) / c["services_processed"],
-            "episode_service_blocking_rate": (c["episode_services_processed"] - c["episode_services_accepted"])
-            / c["episode_services_processed"],
-            "bit_rate_blocking_rate": (c["bit_rate_requested"] - c["bit_rate_provisioned"]) / c["bit_rate_requested"],
-            "episode_bit_rate_blocking_rate": (c["episode_bit_rate_requested"] - c["episode_bit_rate_provisioned"])
-            / c["episode_bit_rate_requested"],
-            "network_compactness": compactness,
-            "network_compactness_difference": compactness_difference,
-        }
+        nxt_rate = int(b.requests()[i]["bit_rate"])
+        info = dict(_traffic.blocking_rates(c, nxt_rate), network_compactness=compactness,
+                    network_compactness_difference=compactness_difference)
         # np.mean over the links, evaluated on the device at the reference's point in the step
         info["avg_link_compactness"] = avg_link_compactness
         info["avg_link_utilization"] = avg_link_utilization

@@ -74,6 +74,51 @@ def _by_group_summary(env, grouped: Sequence[np.ndarray]):
             "counters": np.stack([np.asarray(a) for a in grouped])}
 
 
+class _Evaluation:
+    """What the two evaluate functions share around their episode loops: the check of the groups, the rows of the Monitor
+    CSV, the three writers and the return value."""
+
+    def __init__(self, env, info_keywords, monitor_dir, by_group):
+        self.env, self.info_keywords, self.by_group = env, info_keywords, by_group
+        if monitor_dir is not None or by_group:
+            _traffic.group_loads(env.loads, env.groups, env.num_groups)   # (every group one load, before anything runs)
+        self.t0 = time.time()
+        self.grouped, self.rewards, self.lengths, self.rows = [], [], [], []
+        self.infos: Dict[str, List[np.ndarray]] = {k: [] for k in info_keywords}
+
+    def end_of_episode(self):
+        """The four blocking rates [B] when an episode has just ended: the Monitor logs the info of the episode's last step,
+        built before the next request is generated.  With ``by_group`` the grouped reduction of this moment is kept too."""
+        env = self.env
+        c = env.counters()
+        if self.by_group:
+            self.grouped.append(env.reduce_counters(by_group=True))
+        return _traffic.blocking_rates(c, env.requests()["bit_rate"].astype(np.int64))
+
+    def add_episode(self, ep_r, ep_l, vals):
+        """One row per environment; integer-valued info columns are written as integers."""
+        t = time.time() - self.t0
+        self.rewards.append(ep_r.copy()); self.lengths.append(ep_l.copy())
+        for k in self.info_keywords:
+            self.infos[k].append(np.asarray(vals[k]))
+        for i in range(self.env.batch_size):
+            row = {"r": float(ep_r[i]), "l": int(ep_l[i]), "t": round(t, 6)}
+            row.update({k: (int(vals[k][i]) if np.issubdtype(np.asarray(vals[k]).dtype, np.integer) else float(vals[k][i]))
+                        for k in self.info_keywords})
+            self.rows.append(row)
+
+    def finish(self, env_id, monitor_path, monitor_dir, monitor_name):
+        env = self.env
+        if monitor_path is not None:
+            write_monitor_csv(monitor_path, self.rows, env_id, self.info_keywords, t_start=self.t0)
+        if monitor_dir is not None:
+            write_monitor_tree(monitor_dir, monitor_name, self.rows, env.groups,
+                               _traffic.group_loads(env.loads, env.groups, env.num_groups), env.episode_length, env_id,
+                               self.info_keywords, t_start=self.t0)
+        out = np.stack(self.rewards), np.stack(self.lengths), {k: np.stack(v) for k, v in self.infos.items()}
+        return out + (_by_group_summary(env, self.grouped),) if self.by_group else out
+
+
 def evaluate_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, monitor_path: Optional[str] = None,
                                env_id: str = "RMSA-v0", info_keywords: Sequence[str] = RMSA_INFO_KEYWORDS,
                                chunk: int = 1000, monitor_dir: Optional[str] = None, monitor_name: Optional[str] = None,
@@ -89,13 +134,7 @@ def evaluate_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, moni
     mean blocking rates with their standard error over the group's seeds, formed from ``reduce_counters(by_group=True)``.
     Both need every group to be one load (``ValueError`` otherwise)."""
     B = env.batch_size
-    if monitor_dir is not None or by_group:
-        _traffic.group_loads(env.loads, env.groups, env.num_groups)   # (every group one load, before anything runs)
-    t0 = time.time()
-    grouped = []
-    rewards, lengths = [], []
-    infos: Dict[str, List[np.ndarray]] = {k: [] for k in info_keywords}
-    rows = []
+    ev = _Evaluation(env, info_keywords, monitor_dir, by_group)
     for _ in range(n_eval_episodes):
         env.reset(only_episode_counters=True)
         ep_r = np.zeros(B)
@@ -112,34 +151,8 @@ def evaluate_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, moni
             left -= n
             active &= ~out["done"][-1].astype(bool)
         assert not active.any(), "episode did not finish on every env"
-        c = env.counters()
-        if by_group:
-            grouped.append(env.reduce_counters(by_group=True))
-        nxt = env.requests()["bit_rate"].astype(np.int64)
-        # the Monitor logs the info of the episode's last step, built before the next request is generated
-        proc, eproc = c["services_processed"] - 1, c["episode_services_processed"] - 1
-        req, ereq = c["bit_rate_requested"] - nxt, c["episode_bit_rate_requested"] - nxt
-        vals = {"service_blocking_rate": (proc - c["services_accepted"]) / proc,
-                "episode_service_blocking_rate": (eproc - c["episode_services_accepted"]) / eproc,
-                "bit_rate_blocking_rate": (req - c["bit_rate_provisioned"]) / req,
-                "episode_bit_rate_blocking_rate": (ereq - c["episode_bit_rate_provisioned"]) / ereq}
-        t = time.time() - t0
-        rewards.append(ep_r.copy()); lengths.append(ep_l.copy())
-        for k in info_keywords:
-            infos[k].append(np.asarray(vals[k]))
-        for i in range(B):
-            row = {"r": float(ep_r[i]), "l": int(ep_l[i]), "t": round(t, 6)}
-            row.update({k: float(vals[k][i]) for k in info_keywords})
-            rows.append(row)
-    if monitor_path is not None:
-        write_monitor_csv(monitor_path, rows, env_id, info_keywords, t_start=t0)
-    if monitor_dir is not None:
-        write_monitor_tree(monitor_dir, monitor_name or policy, rows, env.groups,
-                           _traffic.group_loads(env.loads, env.groups, env.num_groups), env.episode_length, env_id,
-                           info_keywords, t_start=t0)
-    if by_group:
-        return np.stack(rewards), np.stack(lengths), {k: np.stack(v) for k, v in infos.items()}, _by_group_summary(env, grouped)
-    return np.stack(rewards), np.stack(lengths), {k: np.stack(v) for k, v in infos.items()}
+        ev.add_episode(ep_r, ep_l, ev.end_of_episode())
+    return ev.finish(env_id, monitor_path, monitor_dir, monitor_name or policy)
 
 
 # tests/test_rmsa_threads_us.py:66-69 (the Monitor the reference wraps PhyRMSA-v0 in)
@@ -160,13 +173,7 @@ def evaluate_phy_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, 
     NumPy >= 2, SURVEY 8c caveat 2).  Returns (episode_rewards [episodes, B], episode_lengths, info arrays).
     ``monitor_dir`` / ``monitor_name`` / ``by_group``: the per-load tree and the summary, as :func:`evaluate_heuristic_batched`."""
     B = env.batch_size
-    if monitor_dir is not None or by_group:
-        _traffic.group_loads(env.loads, env.groups, env.num_groups)   # (every group one load, before anything runs)
-    t0 = time.time()
-    grouped = []
-    rewards, lengths = [], []
-    infos: Dict[str, List[np.ndarray]] = {k: [] for k in info_keywords}
-    rows = []
+    ev = _Evaluation(env, info_keywords, monitor_dir, by_group)
     last_outs = ("accepted", "done", "number_cuts_total", "rss_total_metric", "defrag_counters")
     for _ in range(n_eval_episodes):
         env.reset(only_episode_counters=True)
@@ -179,42 +186,10 @@ def evaluate_phy_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, 
         last = env.run(policy, 1, outputs=last_outs)
         ep_r += last["accepted"][0]
         assert last["done"][0].all(), "episode did not finish on every env"
-        c = env.counters()
-        if by_group:
-            grouped.append(env.reduce_counters(by_group=True))
-        nxt = env.requests()["bit_rate"].astype(np.int64)
-        proc, eproc = c["services_processed"] - 1, c["episode_services_processed"] - 1
-        req, ereq = c["bit_rate_requested"] - nxt, c["episode_bit_rate_requested"] - nxt
-        st = env.episode_stats()
-        phys, chans = st["physical_services_accepted"], st["channels_accepted"]
+        vals = ev.end_of_episode()
         dc = last["defrag_counters"][0].astype(np.int64)
-        vals = {"service_blocking_rate": (proc - c["services_accepted"]) / proc,
-                "episode_service_blocking_rate": (eproc - c["episode_services_accepted"]) / eproc,
-                "bit_rate_blocking_rate": (req - c["bit_rate_provisioned"]) / req,
-                "episode_bit_rate_blocking_rate": (ereq - c["episode_bit_rate_provisioned"]) / ereq,
-                "number_cuts_total": last["number_cuts_total"][0], "rss_total_metric": last["rss_total_metric"][0],
-                "total_path_length": st["total_path_length"] / (phys + 1),
-                "num_moves": dc[:, 0] / 2 + dc[:, 1], "num_moves_groom": dc[:, 1], "num_defrag_cycle": dc[:, 2],
-                "avrage_gsnr": st["total_gsnr"] / (chans + 1),
-                "average_mod_level": st["total_modulation_level"] / (chans + 1),
-                "average_path_index": st["total_path_index"] / (phys + 1),
-                "path_index": st["total_path_index"], "physical_paths": phys}
-        t = time.time() - t0
-        ep_l = np.full(B, env.episode_length - 1, np.int64)
-        rewards.append(ep_r.copy()); lengths.append(ep_l)
-        for k in info_keywords:
-            infos[k].append(np.asarray(vals[k]))
-        for i in range(B):
-            row = {"r": float(ep_r[i]), "l": int(ep_l[i]), "t": round(t, 6)}
-            row.update({k: (int(vals[k][i]) if np.issubdtype(np.asarray(vals[k]).dtype, np.integer) else float(vals[k][i]))
-                        for k in info_keywords})
-            rows.append(row)
-    if monitor_path is not None:
-        write_monitor_csv(monitor_path, rows, env_id, info_keywords, t_start=t0)
-    if monitor_dir is not None:
-        write_monitor_tree(monitor_dir, monitor_name or policy, rows, env.groups,
-                           _traffic.group_loads(env.loads, env.groups, env.num_groups), env.episode_length, env_id,
-                           info_keywords, t_start=t0)
-    if by_group:
-        return np.stack(rewards), np.stack(lengths), {k: np.stack(v) for k, v in infos.items()}, _by_group_summary(env, grouped)
-    return np.stack(rewards), np.stack(lengths), {k: np.stack(v) for k, v in infos.items()}
+        vals.update({"number_cuts_total": last["number_cuts_total"][0], "rss_total_metric": last["rss_total_metric"][0],
+                     "num_moves": dc[:, 0] / 2 + dc[:, 1], "num_moves_groom": dc[:, 1], "num_defrag_cycle": dc[:, 2]})
+        vals.update(env.info())   # the per-episode ratios of the info dict (phy_rmsa_env.py:339-347)
+        ev.add_episode(ep_r, np.full(B, env.episode_length - 1, np.int64), vals)
+    return ev.finish(env_id, monitor_path, monitor_dir, monitor_name or policy)

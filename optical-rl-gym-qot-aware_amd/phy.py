@@ -12,13 +12,13 @@ switch on the periodic defragmentation (``phy_rmsa_env.py:355-417``), run inside
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _lib, trace as _trace
-from .batched import COUNTER_NAMES, REQUEST_DTYPE, SweepTraffic, _check_buffer, _grouped_counters, _ptr
-from .topology import FrozenTopology, selection_tables
+from . import _lib
+from ._handle import BatchedHandle, _check_buffer, _output_names, _ptr
 
 PHY_DEFAULT_BIT_RATES = (100, 200, 300, 400, 500, 600)  # phy_rmsa_env.py:38
 
@@ -91,7 +91,17 @@ def encode_shares(selected_channels, out_row):
     return out_row
 
 
-class BatchedPhyRMSAEnv:
+# per-step outputs wider than [n_steps, B]; the float64 shares of a continuous handle leave through orlg_phy_step_ex's own
+# arguments, not through the orlg_phy_step_io
+_STEP_IO_SHAPES = {"request": (4,), "channels": (_lib.PHY_MAX_CHANNELS,), "channels_used": (_lib.PHY_MAX_CHANNELS,),
+                   "defrag_counters": (3,), "channels_used_f64": (_lib.PHY_MAX_CHANNELS,),
+                   "channels_free_f64": (_lib.PHY_MAX_CHANNELS,)}
+_F64_OUTPUTS = {"channels_used_f64": "float64", "channels_free_f64": "float64"}
+
+
+class BatchedPhyRMSAEnv(BatchedHandle):
+    PREFIX = "orlg_phy_"
+
     def __init__(self, topology, batch_size: int, *, modulation_level, connections_detail, gsnr,
                  episode_length: int = 1000, load: float = None, mean_service_holding_time: float = None,
                  bit_rates: Sequence[int] = PHY_DEFAULT_BIT_RATES, bit_rate_probabilities=None,
@@ -102,12 +112,7 @@ class BatchedPhyRMSAEnv:
                  queue_capacity: int = 0, channel_state_capacity: int = 0, defrag_capacity: int = 0, device: int = 0,
                  gn_gate=None, bit_rate_selection: str = "discrete", bit_rate_lower_bound=25.0,
                  bit_rate_higher_bound=100.0, groups=None, num_groups=None, trace=None, **_ignored):
-        # trace=: the handle replays a RequestTrace (trace.py); see BatchedRMSAEnv
-        _trace.check_trace_kwargs(trace, dict(load=load, mean_service_holding_time=mean_service_holding_time, seed=seed,
-                                              seeds=seeds))
-        self.trace = trace
-        load = 10 if load is None else load
-        mean_service_holding_time = 10800.0 if mean_service_holding_time is None else mean_service_holding_time
+        load, mean_service_holding_time = self._init_traffic_kwargs(trace, load, mean_service_holding_time, seed, seeds)
         if defrag_period and number_moves is None:
             raise ValueError("defrag_period needs number_moves (the reference compares against it, phy_rmsa_env.py:358)")
         # bit_rate_selection="continuous" (phy_rmsa_env.py:79-86, 114-134): rng.randint(lower, higher) per request, checked
@@ -119,22 +124,9 @@ class BatchedPhyRMSAEnv:
             self.bit_rate_lower_bound, self.bit_rate_higher_bound = bounds
             bit_rates = range(bounds[0], bounds[1] + 1)
             bit_rate_probabilities = None
-        # load= / mean_service_holding_time= may be length-B array-likes (a load sweep in one handle, traffic.py)
-        self.traffic = SweepTraffic(batch_size, load, mean_service_holding_time, None if trace is not None else groups,
-                                    None if trace is not None else num_groups)
-        self.topology = FrozenTopology.from_graph(topology)
+        tables = self._open(topology, batch_size, episode_length, load, mean_service_holding_time, bit_rates,
+                            self.continuous, bit_rate_probabilities, node_request_probabilities, seed, groups, num_groups)
         t = self.topology
-        if trace is not None:   # checked before the library is loaded: the rules of orlg_phy_create_trace
-            self.trace = trace = trace.for_batch(batch_size)
-            trace.validate(num_nodes=t.num_nodes, **({"bit_rate_bounds": (bit_rates[0], bit_rates[-1])}
-                                                     if self.continuous else {"bit_rates": list(bit_rates)}))
-            self.traffic.groups, self.traffic.num_groups = _trace.trace_groups(batch_size, groups, num_groups)
-            self._trace_groups = groups is not None
-        self.L = _lib.load()
-        self.batch_size = int(batch_size)
-        self.episode_length = int(episode_length)
-        self.k_paths = t.k_paths
-        self.bit_rates = [int(b) for b in bit_rates]
         self.allow_rejection = bool(allow_rejection)
         # optical_network_env.py:78-102
         if s_band:
@@ -143,15 +135,6 @@ class BatchedPhyRMSAEnv:
             self.num_channels = 2 * number_spectrum_channels
         else:
             self.num_channels = number_spectrum_channels
-        self.load, self.mean_service_holding_time = load, mean_service_holding_time
-        if self.traffic.per_env:
-            self.mean_service_inter_arrival_time = 1 / self.traffic.arrival_lambda
-        else:
-            self.mean_service_inter_arrival_time = 1 / float(load / float(mean_service_holding_time))
-        self.loads, self.groups, self.num_groups = self.traffic.loads, self.traffic.groups, self.traffic.num_groups
-        self.node_request_probabilities, src_cum, dst_cum, br_cum = selection_tables(
-            node_request_probabilities, bit_rate_probabilities, t.num_nodes, self.bit_rates)
-        self.rand_seed = 41 if seed is None else int(seed)
         mod = np.ascontiguousarray(modulation_level, dtype=np.uint8)
         gs = np.ascontiguousarray(gsnr, dtype=np.float64)
         assert mod.shape == gs.shape and mod.shape[1] >= self.num_channels
@@ -160,19 +143,7 @@ class BatchedPhyRMSAEnv:
         pairs = _pairs_from_connections_detail(connections_detail)
         adj_off, adj_link, adj_weight = t.cut_adjacency()
 
-        self._keep = []
-
-        def keep(a, dt):
-            a = np.ascontiguousarray(a, dtype=dt)
-            self._keep.append(a)
-            return a.ctypes.data_as(C.c_void_p)
-
-        ct = _lib.Topology()
-        ct.num_nodes, ct.num_links, ct.k_paths, ct.num_paths = t.num_nodes, t.num_links, t.k_paths, t.num_paths
-        for name, dt in (("pair_path_base", np.int32), ("pair_path_count", np.int32), ("path_hops", np.int32),
-                         ("path_se", np.int32), ("path_length", np.float64), ("path_link_off", np.int32),
-                         ("path_links", np.int32)):
-            setattr(ct, name, keep(getattr(t, name), dt))
+        keep = self._keep_array
         cc = _lib.PhyConfig()
         cc.num_channels, cc.episode_length, cc.num_bit_rates = self.num_channels, self.episode_length, len(self.bit_rates)
         cc.k_table, cc.num_table_rows, cc.queue_capacity = mod.shape[2], mod.shape[0], int(queue_capacity)
@@ -181,23 +152,13 @@ class BatchedPhyRMSAEnv:
         cc.defrag_period, cc.number_moves = int(defrag_period or 0), int(number_moves or 0)
         cc.defrag_metric, cc.defrag_capacity = (0 if metric == "cut" else 1), int(defrag_capacity)
         self.defrag_period, self.number_moves, self.metric = defrag_period, number_moves, metric
-        if self.traffic.per_env:   # (ignored by orlg_phy_create_traffic; the pair of the largest load, for the record)
-            cc.arrival_lambda = self.traffic.arrival_lambda[self.traffic.largest()]
-            cc.holding_lambda = self.traffic.holding_lambda[self.traffic.largest()]
-        else:
-            cc.arrival_lambda = 1 / self.mean_service_inter_arrival_time
-            cc.holding_lambda = 1 / self.mean_service_holding_time
-        cc.bit_rates = keep(self.bit_rates, np.int32)
-        cc.bit_rate_cum = None if self.continuous else keep(br_cum, np.float64)   # NULL: continuous (include/orlg.h)
-        cc.src_cum = keep(src_cum, np.float64)
-        cc.dst_cum = keep(dst_cum, np.float64)
+        self._fill_traffic(cc, *tables)
         cc.pair_table_row = keep(t.pair_table_rows(pairs), np.int32)
         cc.modulation_level = keep(mod, np.uint8)
         cc.gsnr = keep(gs, np.float64)
         cc.adj_off, cc.adj_link, cc.adj_weight = keep(adj_off, np.int32), keep(adj_link, np.int32), keep(adj_weight, np.int32)
         # the cut metric as byte dot products over per-node free degrees (networks of at most 16 nodes); ORLG_PHY_NODEVEC=0
         # keeps the adjacency-list evaluation (identical results: tests/test_gpu_phy.py runs both)
-        import os
         nv = t.cut_node_tables() if os.environ.get("ORLG_PHY_NODEVEC", "1") != "0" else None
         if nv is not None:
             cc.path_node_weights, cc.node_degree = keep(nv[0], np.uint8), keep(nv[1], np.uint8)
@@ -219,74 +180,8 @@ class BatchedPhyRMSAEnv:
             gg.thresholds_db, gg.num_thresholds = keep(thr, np.float64), len(thr)
             self._keep.append(gg)
             cc.gn_gate = C.cast(C.pointer(gg), C.c_void_p)
-        seeds_ptr = None
-        if seeds is not None:
-            seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-            if seeds.shape != (self.batch_size,):
-                raise ValueError(f"seeds: shape {seeds.shape}, expected ({self.batch_size},)")
-            seeds_ptr = seeds.ctypes.data_as(C.c_void_p)
-        h = C.c_void_p()
-        if trace is not None:
-            ts = trace.struct(self.groups if self._trace_groups else None, self.num_groups)
-            _lib.check(self.L.orlg_phy_create_trace(C.byref(ct), C.byref(cc), self.batch_size, int(device), C.byref(ts), C.byref(h)))
-        elif self.traffic.per_env:
-            tr = self.traffic.struct()
-            _lib.check(self.L.orlg_phy_create_traffic(C.byref(ct), C.byref(cc), self.batch_size, seeds_ptr,
-                                                      C.c_uint64(self.rand_seed), int(device), C.byref(tr), C.byref(h)))
-        else:
-            _lib.check(self.L.orlg_phy_create(C.byref(ct), C.byref(cc), self.batch_size, seeds_ptr,
-                                              C.c_uint64(self.rand_seed), int(device), C.byref(h)))
-        self.h = h
-        self.words_per_link = self.L.orlg_phy_words_per_link(self.h)
+        self._create(self._topology_struct(), cc, seeds, device)
         self.node_vectors = bool(self.L.orlg_phy_node_vectors(self.h))   # cut metric through node-degree vectors (include/orlg.h)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.orlg_phy_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_ptr):
-        _lib.check(self.L.orlg_phy_set_stream(self.h, C.c_void_p(stream_ptr) if stream_ptr else None))
-
-    def synchronize(self):
-        _lib.check(self.L.orlg_phy_synchronize(self.h))
-
-    def reset(self, only_episode_counters: bool = True):
-        _lib.check(self.L.orlg_phy_reset(self.h, 1 if only_episode_counters else 0))
-
-    def last_kernel(self) -> str:
-        """Name, template arguments and launch shape of the kernel behind the last ``run`` / ``reset``."""
-        buf = C.create_string_buffer(128)
-        _lib.check(self.L.orlg_phy_last_kernel(self.h, buf, 128))
-        return buf.value.decode()
-
-    @property
-    def trace_length(self) -> int:
-        """Requests per environment of the handle's trace, 0 for a handle that generates its traffic."""
-        return int(self.L.orlg_phy_trace_length(self.h))
-
-    @property
-    def trace_position(self) -> int:
-        """Requests drawn so far (the same for every environment): 1 after a full reset, + 1 per step."""
-        return int(self.L.orlg_phy_trace_position(self.h))
-
-    def reseed(self, seed=None, seeds=None):
-        """A fresh generator for every environment: see ``BatchedRMSAEnv.reseed`` (NOT the reference's ``seed()``)."""
-        if self.trace is not None:
-            raise ValueError("a handle that replays a trace has no generator to seed")
-        if seeds is not None:
-            sa = np.ascontiguousarray(seeds, np.uint64)
-            if sa.shape != (self.batch_size,):
-                raise ValueError(f"seeds: shape {sa.shape}, expected ({self.batch_size},)")
-            _lib.check(self.L.orlg_phy_reseed(self.h, _ptr(sa), 0))
-        else:
-            _lib.check(self.L.orlg_phy_reseed(self.h, None, int(41 if seed is None else seed)))
 
     def run(self, policy: str, n_steps: int = 1, *, act_path=None, act_channels=None, act_share=None,
             auto_reset: bool = False, outputs: Sequence[str] = (), out=None):
@@ -300,30 +195,14 @@ class BatchedPhyRMSAEnv:
         chosen channels' float64 shares (``channels_used`` is 0 on such a handle)."""
         B = self.batch_size
         io = _lib.PhyStepIO()
-        res = {}
-        names = list(outputs) + [k for k in (out or {}) if k not in outputs]
-        fptr = {}
-        for name in [n for n in names if n in ("channels_used_f64", "channels_free_f64")]:
-            if not self.continuous:
-                raise KeyError(f"step output {name!r} belongs to handles with continuous bit rates")
-            shape = (n_steps, B, _lib.PHY_MAX_CHANNELS)
-            if out is not None and name in out:
-                res[name] = _check_buffer(f"out[{name!r}]", out[name], shape, np.float64)
-            else:
-                res[name] = np.zeros(shape, np.float64)
-            fptr[name] = _ptr(res[name])
-        names = [n for n in names if n not in fptr]
-        for name in names:
-            if name not in _lib.PHY_STEP_IO_DTYPES:
-                raise KeyError(f"unknown step output {name!r}")
-            shape = {"request": (n_steps, B, 4), "channels": (n_steps, B, _lib.PHY_MAX_CHANNELS),
-                     "channels_used": (n_steps, B, _lib.PHY_MAX_CHANNELS),
-                     "defrag_counters": (n_steps, B, 3)}.get(name, (n_steps, B))
-            if out is not None and name in out:
-                res[name] = _check_buffer(f"out[{name!r}]", out[name], shape, _lib.PHY_STEP_IO_DTYPES[name])
-            else:
-                res[name] = np.zeros(shape, dtype=_lib.PHY_STEP_IO_DTYPES[name])
-            setattr(io, name, _ptr(res[name]))
+        names = _output_names(outputs, out)
+        f64 = [n for n in names if n in _F64_OUTPUTS]
+        if f64 and not self.continuous:
+            raise KeyError(f"step output {f64[0]!r} belongs to handles with continuous bit rates")
+        res = self._step_outputs(f64, n_steps, out, _F64_OUTPUTS, _STEP_IO_SHAPES)
+        fptr = {name: _ptr(a) for name, a in res.items()}
+        res.update(self._step_outputs([n for n in names if n not in f64], n_steps, out, _lib.PHY_STEP_IO_DTYPES,
+                                      _STEP_IO_SHAPES, io))
         ap = ac = None
         if policy == "external":
             if act_path is None or act_channels is None:
@@ -364,30 +243,8 @@ class BatchedPhyRMSAEnv:
                                            fptr.get("channels_free_f64")))
         return res
 
-    def requests(self):
-        a = np.zeros(self.batch_size, REQUEST_DTYPE)
-        _lib.check(self.L.orlg_phy_get_requests(self.h, _ptr(a)))
-        return a
-
-    def counters(self):
-        a = np.zeros((self.batch_size, 8), np.int64)
-        _lib.check(self.L.orlg_phy_get_counters(self.h, _ptr(a)))
-        return {n: a[:, i].copy() for i, n in enumerate(COUNTER_NAMES)}
-
-    def current_time(self):
-        a = np.zeros(self.batch_size, np.float64)
-        _lib.check(self.L.orlg_phy_get_current_time(self.h, _ptr(a)))
-        return a
-
-    def num_running(self):
-        a = np.zeros(self.batch_size, np.int32)
-        _lib.check(self.L.orlg_phy_get_num_running(self.h, _ptr(a)))
-        return a
-
     def episode_stats(self):
-        a = np.zeros(self.batch_size, EPISODE_STATS_DTYPE)
-        _lib.check(self.L.orlg_phy_get_episode_stats(self.h, _ptr(a)))
-        return a
+        return self._read(self.L.orlg_phy_get_episode_stats, self.batch_size, EPISODE_STATS_DTYPE)
 
     def info(self):
         """The per-episode ratios of the info dict (``phy_rmsa_env.py:339-347``) for every env."""
@@ -401,11 +258,8 @@ class BatchedPhyRMSAEnv:
 
     def available_channels(self):
         """topology.graph["available_channels"] for every env: [B, E, C] uint8 (1 = free)."""
-        E, W = self.topology.num_links, self.words_per_link
-        w = np.zeros((self.batch_size, E, W), np.uint64)
-        _lib.check(self.L.orlg_phy_get_occupancy(self.h, _ptr(w)))
-        bits = np.unpackbits(w.view(np.uint8), axis=-1, bitorder="little")
-        return bits.reshape(self.batch_size, E, -1)[:, :, :self.num_channels]
+        bits = np.unpackbits(self._occupancy_words().view(np.uint8), axis=-1, bitorder="little")
+        return bits.reshape(self.batch_size, self.topology.num_links, -1)[:, :, :self.num_channels]
 
     def channel_masks(self, out=None):
         """``is_channel_free(path_p, c)`` (``phy_rmsa_env.py:1029-1035``) for the k candidate paths of every env's pending
@@ -449,37 +303,10 @@ class BatchedPhyRMSAEnv:
             out[(s, d, k)] = [(int(x & 0x1ff), int((x >> 9) & 0x1f), int((x >> 14) & 0x1f), int((x >> 19) & 0x1f)) for x in e]
         return out
 
-    def save_state(self):
-        """Snapshot of the complete simulation state of the batch (a uint8 array): checkpoint / resume, env cloning."""
-        n = self.L.orlg_phy_state_size(self.h)
-        if n < 0:
-            _lib.check(int(n))
-        buf = np.empty(int(n), np.uint8)
-        _lib.check(self.L.orlg_phy_save_state(self.h, _ptr(buf)))
-        return buf
-
     def load_state(self, buf):
         buf = np.ascontiguousarray(buf, np.uint8)
         tagged = buf.size >= 16 and np.array_equal(buf[-16:], _CONT_STATE_TAG)
         if self.continuous or tagged:   # a snapshot of the other bit-rate mode is refused (ORLG_ERR_INVALID)
             _lib.check(self.L.orlg_phy_load_state_checked(self.h, _ptr(buf), C.c_int64(buf.size)))
             return
-        assert buf.size == self.L.orlg_phy_state_size(self.h), "snapshot of a differently configured batch"
-        _lib.check(self.L.orlg_phy_load_state(self.h, _ptr(buf)))
-
-    def traffic_rates(self):
-        """(arrival_lambda [B], holding_lambda [B], group [B]) as the handle holds them."""
-        B = self.batch_size
-        a, h, g = np.zeros(B), np.zeros(B), np.zeros(B, np.int32)
-        _lib.check(self.L.orlg_phy_get_traffic(self.h, _ptr(a), _ptr(h), _ptr(g)))
-        return a, h, g
-
-    def reduce_counters(self, by_group: bool = False):
-        """As ``BatchedRMSAEnv.reduce_counters``; ``by_group=True`` returns the sums per group, [G, 16] int64."""
-        if by_group:
-            return _grouped_counters(self.L.orlg_phy_reduce_counters_grouped, self.h, self.num_groups)
-        a = np.zeros(16, np.int64)
-        _lib.check(self.L.orlg_phy_reduce_counters(self.h, _ptr(a)))
-        d = {n: int(a[i]) for i, n in enumerate(COUNTER_NAMES)}
-        d["episodes_done"], d["num_envs"] = int(a[8]), int(a[9])
-        return d, a
+        super().load_state(buf)

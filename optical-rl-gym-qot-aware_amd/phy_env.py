@@ -15,8 +15,8 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import _lib
-from .envs import RMSAEnv as _RMSAView
+from . import _lib, traffic as _traffic
+from .envs import RMSAEnv as _RMSAView, _View
 from .phy import PHY_DEFAULT_BIT_RATES, BatchedPhyRMSAEnv, encode_channels, encode_shares
 from .topology import Path, Service
 
@@ -44,10 +44,7 @@ class _ChannelState:
         return list(self._env._channel_lists().get((s, d, k), []))
 
 
-class PhyRMSAEnv:
-    metadata = {"metrics": ["service_blocking_rate", "episode_service_blocking_rate", "bit_rate_blocking_rate",
-                            "episode_bit_rate_blocking_rate"]}
-
+class PhyRMSAEnv(_View):
     def __init__(self, topology=None, episode_length: int = 1000, load: float = None,
                  mean_service_holding_time: float = None, num_spectrum_resources: int = 100,
                  bit_rate_selection: str = "discrete", bit_rates=PHY_DEFAULT_BIT_RATES, bit_rate_probabilities=None,
@@ -100,11 +97,7 @@ class PhyRMSAEnv:
     # ------------------------------------------------------------------ plumbing
     def _sync(self):
         b = self._batched
-        r = b.requests()[0]
-        nodes = self._ft.nodes
-        self.current_service = Service(int(r["service_id"]), nodes[r["src"]], int(r["src"]), destination=nodes[r["dst"]],
-                                       destination_id=int(r["dst"]), arrival_time=float(r["arrival_time"]),
-                                       holding_time=float(r["holding_time"]), bit_rate=int(r["bit_rate"]))
+        self.current_service = self._service(b.requests()[0])
         for name, arr in b.counters().items():
             setattr(self, name, int(arr[0]))
         self.current_time = float(b.current_time()[0])
@@ -181,23 +174,6 @@ class PhyRMSAEnv:
         return rss(after) - rss(col)
 
     # ------------------------------------------------------------------ gym surface
-    def observation(self):
-        return {"topology": self.topology, "current_service": self.current_service}
-
-    def reward(self):
-        return 1 if self.current_service.accepted else 0
-
-    def render(self, mode="human"):
-        return
-
-    def seed(self, seed=None):
-        """``optical_network_env.py:266-271``; see ``BatchedRMSAEnv.reseed`` for why this is refused."""
-        raise NotImplementedError(
-            "seed() after construction is not reproduced: the reference keeps drawing the BIT RATE from the generator object of "
-            "construction time (functools.partial(self.rng.choices, ...)) while the other four draws of a request come from "
-            "Random(seed) -- two generators per environment.  Pass seed= to the constructor, or call reseed() on the batched "
-            "environment for a fresh generator for all draws (not the reference's stream).")
-
     def reset(self, only_episode_counters: bool = True):
         self._batched.reset(only_episode_counters)
         self._sync()
@@ -231,20 +207,11 @@ class PhyRMSAEnv:
                     self.bvts[band][served.source_id][served.destination_id] += 1
         b = self._batched
         c = {k: int(v[0]) for k, v in b.counters().items()}
-        nxt = int(b.requests()[0]["bit_rate"])
-        c["services_processed"] -= 1          # info is built before _next_service (phy_rmsa_env.py:319-351)
-        c["episode_services_processed"] -= 1
-        c["bit_rate_requested"] -= nxt
-        c["episode_bit_rate_requested"] -= nxt
         st = b.episode_stats()[0]
         phys, chans = int(st["physical_services_accepted"]), int(st["channels_accepted"])
         info = {
-            "service_blocking_rate": (c["services_processed"] - c["services_accepted"]) / c["services_processed"],
-            "episode_service_blocking_rate": (c["episode_services_processed"] - c["episode_services_accepted"])
-            / c["episode_services_processed"],
-            "bit_rate_blocking_rate": (c["bit_rate_requested"] - c["bit_rate_provisioned"]) / c["bit_rate_requested"],
-            "episode_bit_rate_blocking_rate": (c["episode_bit_rate_requested"] - c["episode_bit_rate_provisioned"])
-            / c["episode_bit_rate_requested"],
+            # info is built before _next_service (phy_rmsa_env.py:319-351)
+            **_traffic.blocking_rates(c, int(b.requests()[0]["bit_rate"])),
             "number_cuts_total": float(r["number_cuts_total"][0, 0]),
             "rss_total_metric": float(r["rss_total_metric"][0, 0]),
             "total_path_length": float(st["total_path_length"]) / (phys + 1),
@@ -409,44 +376,21 @@ def phy_aware_faff_rss_rmsa(env) -> Tuple[int, list]:
     return _faff(env, _rss_metric)
 
 
-def phy_aware_bmfa_rss_rmsa(env) -> Tuple[int, list]:
-    """``phy_rmsa_env.py:1441-1505``: as bmfa with the RSS metric (``calculate_r_spatial``)."""
+def _bmfa(env, metric):
     v = _with_virtual_layer(env, False)
     if v:
         return v
-    rows = _free_channel_rows(env, _rss_metric)
+    rows = _free_channel_rows(env, metric)
     return _take_channels(env, [sorted(r, key=lambda x: (-x[0], -x[1])) for r in rows], _pick_level_metric)
+
+
+def phy_aware_bmfa_rss_rmsa(env) -> Tuple[int, list]:
+    """``phy_rmsa_env.py:1441-1505``: as bmfa with the RSS metric (``calculate_r_spatial``)."""
+    return _bmfa(env, _rss_metric)
 
 
 def phy_aware_bmfa_rmsa(env) -> Tuple[int, list]:
     """Best-modulation, fragmentation-aware (cut metric) channel selection, ``phy_rmsa_env.py:1375-1438`` with
     the virtual layer first when ``env.grooming``: per path the free channels sorted by (level desc, cut metric desc);
     the row with the best head wins; channels are taken in order until the bit rate is covered (the last one partially)."""
-    v = _with_virtual_layer(env, False)
-    if v:
-        return v
-    table_id = _table_id(env)
-    rows = []
-    for idp, path in enumerate(env.k_shortest_paths[env.current_service.source, env.current_service.destination]):
-        links = [env.topology[path.node_list[i]][path.node_list[i + 1]]["index"] for i in range(len(path.node_list) - 1)]
-        row = []
-        for ch in range(env.topology.graph["num_channel_resources"]):
-            if env.is_channel_free(path, ch):
-                level = int(env.modulation_level[table_id][ch][idp])
-                row.append((level, env.calculate_r_cut(ch, links, False, path, True), ch, idp))
-        rows.append(sorted(row, key=lambda x: (-x[0], -x[1])))
-    while True:
-        best, head = None, (float("-inf"), float("-inf"))
-        for i, row in enumerate(rows):
-            if row and (row[0][0], row[0][1]) > head:
-                best, head = i, (row[0][0], row[0][1])
-        if best is None:
-            return (-2, [])
-        unassigned, selected = env.current_service.bit_rate, []
-        for level, _, ch, idp in rows[best]:
-            unassigned -= level * 100
-            if unassigned <= 0:
-                selected.append((ch, level + unassigned / 100, unassigned / -100, level, False))
-                return (idp, selected)
-            selected.append((ch, level, 0, level, False))
-        rows.pop(best)
+    return _bmfa(env, _cut_metric)

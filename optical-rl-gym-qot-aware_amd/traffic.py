@@ -101,6 +101,21 @@ def group_loads(loads, groups, num_groups):
     return out
 
 
+def blocking_rates(counters, pending_bit_rate):
+    """The four blocking rates of the info dict from the counters of ``counters()`` as they stand after a step.  The
+    reference builds info BEFORE ``_next_service()`` (``rmsa_env.py:293-335``, ``phy_rmsa_env.py:319-351``); the device step
+    has already generated the next request, so the pending request (one service, ``pending_bit_rate``) is taken out of the
+    request-side counters again.  Python ints give the reference's own int / int true divisions, int64 arrays the same
+    element by element."""
+    c = counters
+    proc, eproc = c["services_processed"] - 1, c["episode_services_processed"] - 1
+    req, ereq = c["bit_rate_requested"] - pending_bit_rate, c["episode_bit_rate_requested"] - pending_bit_rate
+    return {"service_blocking_rate": (proc - c["services_accepted"]) / proc,
+            "episode_service_blocking_rate": (eproc - c["episode_services_accepted"]) / eproc,
+            "bit_rate_blocking_rate": (req - c["bit_rate_provisioned"]) / req,
+            "episode_bit_rate_blocking_rate": (ereq - c["episode_bit_rate_provisioned"]) / ereq}
+
+
 def blocking_summary(grouped, episode=True):
     """Mean service blocking rate per group and its standard error over the group's environments, from one result of
     ``reduce_counters(by_group=True)`` ([G, 16] int64) taken when an episode has just ended -- every environment of a handle

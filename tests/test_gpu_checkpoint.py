@@ -3,9 +3,9 @@ what both kinds of handle share on the host -- reseed, set_stream, save / load, 
 import numpy as np
 import pytest
 
-from conftest import load_golden, load_phy_tables, load_topology
+from conftest import load_golden, load_phy_tables, load_topology, oracle_env_from_kwargs, phy_oracle_from_kwargs
 from test_gpu_phy import make_env
-from test_gpu_rmsa import make_batched
+from test_gpu_rmsa import device_log_in_oracle, make_batched  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -59,10 +59,10 @@ POLICY = {"rmsa": "sap_ff", "phy": "sapff"}
 OUTS = ("act_path", "accepted", "arrival", "holding")
 
 
-def make(kind, nsfnet, seed=3, **extra):
+def make(kind, nsfnet, seed=3, batch=B, **extra):
     if kind == "rmsa":
-        return make_batched(nsfnet, dict(RMSA_KW, seed=seed), B, **extra)
-    return make_env(load_topology("us14_3-paths_6-modulations"), load_phy_tables("us14_k3"), dict(PHY_KW, seed=seed), B, **extra)
+        return make_batched(nsfnet, dict(RMSA_KW, seed=seed), batch, **extra)
+    return make_env(load_topology("us14_3-paths_6-modulations"), load_phy_tables("us14_k3"), dict(PHY_KW, seed=seed), batch, **extra)
 
 
 def state(env):
@@ -148,4 +148,40 @@ def test_reductions_equal_the_sums_of_the_counters(nsfnet, kind):
         for g in range(2):
             assert grouped[g, i] == per_env[name][groups == g].sum(), (name, g)
     assert total[9] == B and list(grouped[:, 9]) == [2, 2]
+    env.close()
+
+
+@pytest.mark.parametrize("kind", ["rmsa", "phy"])
+def test_shared_read_backs_equal_the_oracle(nsfnet, kind, device_log_in_oracle):
+    """What the handle base reads back for both kinds -- pending requests, counters, time, services in progress, traffic, trace
+    length, last kernel, device -- after 20 steps of a device policy on 3 environments, against one oracle per environment."""
+    batch, seed, n = 3, 3, 20
+    env = make(kind, nsfnet, seed=seed, batch=batch)
+    env.run(POLICY[kind], n)
+    req, cnt, now, nrun = env.requests(), env.counters(), env.current_time(), env.num_running()
+    assert req.shape == now.shape == nrun.shape == (batch,)
+    for i in range(batch):
+        if kind == "rmsa":
+            o = oracle_env_from_kwargs(nsfnet, RMSA_KW, seed=seed + i)
+        else:
+            o = phy_oracle_from_kwargs(load_topology("us14_3-paths_6-modulations"), load_phy_tables("us14_k3"), PHY_KW, seed=seed + i)
+        o.run(POLICY[kind], n)
+        r = o.request()
+        assert (req[i]["service_id"], req[i]["src"], req[i]["dst"], req[i]["bit_rate"]) == (r.service_id, r.src, r.dst, r.bit_rate), i
+        assert (req[i]["arrival_time"], req[i]["holding_time"]) == (r.arrival_time, r.holding_time), i
+        oc = o.counters()
+        assert set(oc) == set(cnt)
+        for name in oc:
+            assert cnt[name][i] == oc[name], (name, i)
+        assert now[i] == o.current_time() and nrun[i] == o.num_running(), i
+        o.close()
+    # the constructor's rates (optical_network_env.py:127-129, rmsa_env.py:646-651), one group
+    kw = RMSA_KW if kind == "rmsa" else PHY_KW
+    holding = kw["mean_service_holding_time"]
+    arrival_lambda, holding_lambda, group = env.traffic_rates()
+    assert arrival_lambda.tolist() == [1 / (1 / float(kw["load"] / float(holding)))] * batch
+    assert holding_lambda.tolist() == [1 / holding] * batch and group.tolist() == [0] * batch
+    assert env.trace_length == 0
+    assert env.last_kernel()
+    assert env.device == 0
     env.close()
