@@ -70,6 +70,39 @@ ORLG_SEG_REDUCE(seg_add, ORLG_OP_ADD)
 ORLG_SEG_REDUCE(seg_max, ORLG_OP_MAX)
 #undef ORLG_SEG_REDUCE
 
+// path_word_rec (orlg_kernels.hip) with the hop words FOUR TO A WAIT: the record's link bytes are all in registers, so the reads of
+// a group of four hops are issued back to back and ANDed in after one round trip, where the other form waits for every hop's
+// word before it votes on the next (three waves per SIMD do not hide that chain here; the wave kernel, at four, keeps its own
+// form).  A hop past the path's end reads the word of the path's first link -- a valid address on every lane, link 0 on an
+// inactive one -- and a select puts ~0 in its place.  Inactive lanes return 0 with se = hops = 0, as there.
+template <int W>
+DEV u64 group_path_word_rec(const u64 *occ, const OrlgPathRec *recs, int gid, int w, bool active, int &se, int &hops_out) {
+    uint4 r = make_uint4(0u, 0u, 0u, 0u);
+    if (active) r = *reinterpret_cast<const uint4 *>(recs + gid);
+    const uint32_t q[4] = {r.x, r.y, r.z, r.w};
+    const int hops = (int)(r.x & 0xffu);
+    se = (int)((r.x >> 8) & 0xffu);
+    hops_out = hops;
+    const int first = __mul24((int)((r.x >> 16) & 0xffu), W) + w;
+    u64 acc = active ? ~0ull : 0ull;
+#pragma unroll
+    for (int h0 = 0; h0 < ORLG_MAX_HOPS; h0 += 4) {
+        if (ballot(h0 < hops) == 0ull) break;
+        u64 v[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int h = h0 + k;
+            if (h < ORLG_MAX_HOPS) {
+                const int link = (int)((q[(h + 2) >> 2] >> (8 * ((h + 2) & 3))) & 0xffu);
+                v[k] = occ[h < hops ? __mul24(link, W) + w : first];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc &= h0 + k < hops ? v[k] : ~0ull;
+    }
+    return acc;
+}
+
 // A link's summary (DEFER instantiation, LDS only): every integer _update_link_stats consumes, 10 bits each -- free slots, free
 // runs, used runs, first used slot (lmin), end of the last used run (lmax), longest free run, slot 0 free, slot S - 1 free.  With
 // no used slot lmin / lmax are group_link_stats' 0x7fff / 0 and lmin keeps only its low 10 bits: a summary is read at a release
@@ -90,12 +123,17 @@ DEV u64 lsum_pack(int freec, int F, int U, int lmin, int lmax, int ml, bool ff, 
 // same values, so the same bits.
 // SUM (DEFER): 1 = also write each link's summary (lsum_pack) to lsum[link]; 2 = ONLY that, for links 0 .. nlinks - 1 (links is
 // not read): the summaries of a quad whose state was just loaded, without a log entry, span cache or running sum touched.
-template <int W, bool LINKF, bool GRAPH, bool DEFER = false, int SUM = 0>
+// APPLY: the pass of a provision clears the window [win_s, win_s + win_n) on its links itself (the lane layout is
+// group_apply_window's: a link's word w on one lane, and a path never repeats a link, so no word is touched twice in a launch of
+// the pass): the word is cleared in the register it was read into, stored back where the window reaches it, and everything
+// after -- the neighbours' DPP reads included -- sees the cleared words.  No write pass of its own, no second read.
+template <int W, bool LINKF, bool GRAPH, bool DEFER = false, int SUM = 0, bool APPLY = false>
 DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, const Tab &tb, int S, int E, const uint8_t *links,
                           int nlinks, double now, int &sum_span, int &sum_gaps, double &comp_cur, int sum_sh, double cur_thr,
                           double &g_thr, double &g_comp, double &g_lu, uint4 *llog = nullptr, bool *need_replay = nullptr,
-                          u64 *lsum = nullptr) {
+                          u64 *lsum = nullptr, int win_s = 0, int win_n = 0) {
     static_assert(W <= 8, "at least two links per row");
+    static_assert(!APPLY || SUM != 2, "the summary rebuild changes no occupancy");
     static_assert(SUM == 0 || (LINKF && DEFER && (SUM == 1 || !GRAPH)), "summaries belong to the deferred instantiation");
     constexpr int NS = ORLG_GL / W;  // links per row and pass
     const int gl = lane & 15;
@@ -112,6 +150,11 @@ DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, 
         // the link's words sit on consecutive lanes: the neighbours' words arrive by DPP instead of further LDS reads
         u64 x = 0ull;
         if (on) x = occ[__mul24(link, W) + w];
+        if (APPLY && on) {
+            const u64 m = window_mask(win_s, win_n, w);
+            x &= ~m;
+            if (m) occ[__mul24(link, W) + w] = x;
+        }
         const u64 prev = lane_prev_u64(x);
         int e = 0;  // free slots that continue a run reaching this word's end into the next words
         if (LINKF) {
@@ -531,6 +574,8 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
     }
     wave_sync();
     double next_rel = q_n > 0 ? qtime[q_head] : INF;
+    // ... and the head's descriptor with it: a release starts from a register, the path record one round trip earlier
+    uint32_t next_desc = q_n > 0 ? qdesc[q_head] : 0u;
     const int cidx = gl & 7;
     int req_base = tb.pair_base[req_src * N + req_dst];  // first path record of the pending request's node pair
 
@@ -585,7 +630,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
                 const int pp = p0 + ps;
                 const bool on = ps < PP && pp < kmax && a_ok;
                 int se_pp, hops_pp;
-                const u64 x = path_word_rec<W>(occ, tb.recs, base + path0 + pp, w, on, se_pp, hops_pp);
+                const u64 x = group_path_word_rec<W>(occ, tb.recs, base + path0 + pp, w, on, se_pp, hops_pp);
                 int n = 1;
                 if (on) n = tb.nslots[req_br * ORLG_NSLOT_STRIDE + se_pp];
                 u64 r = run_starts<W>(x, n, w);
@@ -652,7 +697,8 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
         }
         const int br_val = tb.bit_rates[req_br];
         // ---- _provision_path (rmsa_env.py:462-513)
-        group_apply_window<W>(lane, occ, rec->link, accepted ? hops : 0, a_slot, n, false);
+        // (with network statistics the statistics pass below clears the window as it reads the links' words)
+        if (!NET) group_apply_window<W>(lane, occ, rec->link, accepted ? hops : 0, a_slot, n, false);
         if (accepted) {
             sum_sh += n * hops;
             n_running += 1;
@@ -662,9 +708,10 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
         }
         SEC(4);  // statistics at provision
         if (NET)
-            group_link_stats<W, FULL, true, DEFER, DEFER ? 1 : 0>(lane, occ, lst, lint, tb, S, E, rec->link, accepted ? hops : 0, current_time,
-                                                                 sum_span, sum_gaps, comp_cur, sum_sh, (double)sum_bitrate_running, g_thr,
-                                                                 g_comp, g_lu, llog, &need_replay, lsum);
+            group_link_stats<W, FULL, true, DEFER, DEFER ? 1 : 0, true>(lane, occ, lst, lint, tb, S, E, rec->link, accepted ? hops : 0,
+                                                                          current_time, sum_span, sum_gaps, comp_cur, sum_sh,
+                                                                          (double)sum_bitrate_running, g_thr, g_comp, g_lu, llog,
+                                                                          &need_replay, lsum, a_slot, n);
         SEC(5);  // queue insert
         {
             // ---- _add_release (optical_network_env.py:178-189): the entries that are released later move up one slot (from the
@@ -695,12 +742,14 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
             if (ins) {
                 int pr = q_head + r;
                 pr -= pr >= Q ? Q : 0;
+                const uint32_t desc = (uint32_t)gid | ((uint32_t)a_slot << 14) | ((uint32_t)req_br << 24);
                 if (gl == 0) {
                     qtime[pr] = rel;
-                    qdesc[pr] = (uint32_t)gid | ((uint32_t)a_slot << 14) | ((uint32_t)req_br << 24);
+                    qdesc[pr] = desc;
                 }
                 q_n += 1;
-                next_rel = rel < next_rel ? rel : next_rel;
+                // the new head only if strictly earlier (then r = 0): an entry with the head's time goes behind it
+                if (rel < next_rel) { next_rel = rel; next_desc = desc; }
             }
             wave_sync();
         }
@@ -819,8 +868,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
                 if (ballot(rel_now) == 0ull) break;
                 SEC(10);  // release apply
                 // ---- _release_path (rmsa_env.py:515-535)
-                uint32_t d = 0;
-                if (rel_now) d = qdesc[q_head];
+                const uint32_t d = rel_now ? next_desc : 0u;   // (the head's descriptor came with its time)
                 const int gid2 = (int)(d & 0x3fff), s0 = (int)((d >> 14) & 0x3ff), bri2 = (int)(d >> 24);
                 const OrlgPathRec *rec2 = tb.recs + gid2;
                 const int hops2 = rec2->hops;
@@ -837,13 +885,19 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
                 }
                 if constexpr (DEFER) {
                     // the window and its links' statistics in one pass, lane = hop (group_release_links; ends with a wave_sync)
-                    if (rel_now) next_rel = q_n > 0 ? qtime[q_head] : INF;   // the next entry
+                    if (rel_now) {   // the next entry
+                        next_rel = q_n > 0 ? qtime[q_head] : INF;
+                        next_desc = q_n > 0 ? qdesc[q_head] : 0u;
+                    }
                     group_release_links<W>(lane, occ, lsum, lint, S, rec2->link, rel_now ? hops2 : 0, s0, n2, current_time, sum_span,
                                            sum_gaps, llog, need_replay);
                     SEC(11);  // statistics at release: the log replays only
                 } else {
                     group_apply_window<W>(lane, occ, rec2->link, rel_now ? hops2 : 0, s0, n2, true);   // (ends with a wave_sync)
-                    if (rel_now) next_rel = q_n > 0 ? qtime[q_head] : INF;   // the next entry
+                    if (rel_now) {   // the next entry
+                        next_rel = q_n > 0 ? qtime[q_head] : INF;
+                        next_desc = q_n > 0 ? qdesc[q_head] : 0u;
+                    }
                     SEC(11);  // statistics at release
                     if (NET)
                         group_link_stats<W, FULL, false, DEFER>(lane, occ, lst, lint, tb, S, E, rec2->link, rel_now ? hops2 : 0,
