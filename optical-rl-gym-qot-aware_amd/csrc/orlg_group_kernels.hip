@@ -453,6 +453,10 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
     constexpr bool NET = STATS >= 1;
     constexpr bool FULL = STATS >= 2;
     const double INF = __longlong_as_double((long long)ORLG_INF_BITS);
+    // the network compactness after a step's releases is read by two per-step outputs only (a provision's statistics pass
+    // computes its own, and the state that leaves does not hold it): a launch that asks for neither leaves the two float64
+    // divisions out.  Wave-uniform: a scalar branch
+    const bool out_comp = (p.out_mask & ((1 << ORLG_OUT_COMPACT) | (1 << ORLG_OUT_COMPACT_DIFF))) != 0;
     SEC_DECL_G
 
     // ------------------------------------------------------------------ work queue over quads of environments
@@ -911,7 +915,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
                     SEC(11);
                 }
             }
-            if (NET && released) comp_cur = network_compactness(sum_span, sum_sh, sum_gaps, E);
+            if (NET && out_comp && released) comp_cur = network_compactness(sum_span, sum_sh, sum_gaps, E);
         }
 
         if (DEFER && ballot(need_replay) != 0ull) {   // a link's log is filling up: every row works its logs off
