@@ -140,3 +140,9 @@ struct OrlgParams {
     const uint32_t *tr_req;
     int32_t tr_len, pad_tr;
 };
+
+// A kernel's parameter struct T in the kernarg segment: fields are fetched through the scalar cache where they are used
+template <typename T>
+__device__ __forceinline__ const T __attribute__((address_space(4))) *kernarg_as() {
+    return (const T __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+}

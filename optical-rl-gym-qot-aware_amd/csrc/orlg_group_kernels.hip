@@ -14,7 +14,7 @@
 // one ballot shifted to the row's 16 bits.  The state format in HBM is the wave-per-environment kernel's: either kernel
 // can continue a batch the other one stepped, and the reset kernel is shared.  The MT19937 state and the ring of pre-generated
 // arrivals stay in HBM: a row reads its next arrival one step ahead, and a refill (every ~62 steps per environment) is done
-// by the whole wave for one environment at a time through a per-wave LDS staging buffer (refill_requests, unchanged).
+// by the whole wave for one environment at a time through the workgroup's LDS staging buffer (refill_requests, orlg_requests.h).
 // The wave's LDS region is array-major (four occupancy bitmaps, then four link-statistics blocks, ...: OrlgParams::g_occ ...),
 // as four consecutive environments lie in the HBM arrays: a quad's state moves as linear copies by all 64 lanes.
 //
@@ -22,6 +22,7 @@
 // (its two heuristics and the agent's (path, block) action), load balancing (llp_ff) and external (path, slot) actions.  Reference: the same lines of rmsa_env.py as orlg_kernels.hip cites.
 #pragma once
 #include "orlg_kernels.hip"
+#include "orlg_requests.h"
 
 #define ORLG_GL 16  // lanes per environment (one DPP row)
 #define ORLG_GE 4   // environments per wave
@@ -35,16 +36,6 @@ DEV int row_min_i32(int v) {
 }
 // votes of the lane's own row (16 bits)
 DEV uint32_t row_ballot(bool p, int lane) { return (uint32_t)(ballot(p) >> (lane & 48)) & 0xffffu; }
-// row minimum of (time, slot), ties to the lower slot: the minimum time first, then the lowest slot among the lanes that hold it
-DEV void row_min_time_slot(double &t, int &q) {
-    double m = t, o;
-    o = ORLG_DPP_F64(dpp_xor1, m); m = o < m ? o : m;
-    o = ORLG_DPP_F64(dpp_xor2, m); m = o < m ? o : m;
-    o = ORLG_DPP_F64(dpp_half_mirror, m); m = o < m ? o : m;
-    o = ORLG_DPP_F64(dpp_row_mirror, m); m = o < m ? o : m;
-    q = row_min_i32(t == m ? q : 0x7fffffff);
-    t = m;
-}
 
 // Reductions over the W consecutive lanes that hold one link's words (W is not a power of two in general: 16 / W links share a
 // row): the link's FIRST lane ends with the link's result (the other lanes hold partial results nobody reads).  Sums and
@@ -373,13 +364,6 @@ DEV void group_apply_window(int lane, u64 *occ, const uint8_t *links, int hops, 
     wave_sync();
 }
 
-// rows copy their environment's arrays between HBM and LDS: 16 lanes x 16 bytes per instruction and row
-DEV void row_copy16(void *dst, const void *src, int bytes, int gl) {
-    const int n16 = bytes >> 4;
-    const uint4 *s16 = reinterpret_cast<const uint4 *>(src);
-    uint4 *d16 = reinterpret_cast<uint4 *>(dst);
-    for (int i = gl; i < n16; i += ORLG_GL) d16[i] = s16[i];
-}
 // A quad's slices of one array between HBM and LDS: `bytes` (a multiple of 8) from a wave-uniform source by all 64 lanes, 16
 // bytes per lane and pass (the quad's first environment is a multiple of four: 32-byte aligned for every array copied this way)
 DEV void quad_copy(void *dst, const void *src, int bytes, int lane) {
@@ -402,9 +386,6 @@ DEV void quad_copy(void *dst, const void *src, int bytes, int lane) {
         }
     }
     if ((bytes & 8) && lane == 0) reinterpret_cast<u64 *>(dst)[2 * n16] = reinterpret_cast<const u64 *>(src)[2 * n16];
-}
-DEV void row_copy8(u64 *dst, const u64 *src, int n, int gl) {
-    for (int i = gl; i < n; i += ORLG_GL) dst[i] = src[i];
 }
 
 // HBMQ: launches of very few steps (the agent-driven loop) leave the release queue where it is, in HBM: staged in LDS it is
@@ -795,18 +776,16 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
                 int idx_s = __builtin_amdgcn_readlane(mt_idx, src_lane);
                 if constexpr (TRACE) {
                     // (idx_s: the environment's cursor into its trace)
-                    const int got = refill_requests_trace_t<false>(p.tr_arrival, p.tr_holding, p.tr_req, p.ring_iat + (size_t)env_s * ORLG_RING,
-                                                                   p.ring_ht + (size_t)env_s * ORLG_RING, p.ring_req + (size_t)env_s * ORLG_RING,
-                                                                   &idx_s, p.tr_len, env_s);
-                    // the ring entries written by other lanes are read back by this wave below (as after refill_requests)
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                    wave_sync();
+                    const int got = refill_requests_trace<false>(p.tr_arrival, p.tr_holding, p.tr_req, p.ring_iat + (size_t)env_s * ORLG_RING,
+                                                                 p.ring_ht + (size_t)env_s * ORLG_RING, p.ring_req + (size_t)env_s * ORLG_RING,
+                                                                 &idx_s, p.tr_len, env_s);
+                    ring_visible();
                     if ((lane & 48) == src_lane) { ring_cnt = got; ring_pos = 0; mt_idx = idx_s; dry = false; }
                     continue;
                 }
                 // the MT19937 state travels HBM -> registers -> (lock) LDS -> registers (unlock) -> HBM: the workgroup's staging
                 // buffer is held for the regeneration and the draws only, not for the HBM round trips
+                // (the sequence is written out here and in orlg_phy_kernels.hip: as one shared function it changed 99 kernels' registers, orlg_requests.h)
                 static_assert(ORLG_MT_N * 4 == 156 * 16, "MT19937 state = 156 rows of 16 bytes");
                 const uint4 *g_mt = reinterpret_cast<const uint4 *>(p.mt + (size_t)env_s * ORLG_MT_N);
                 uint4 *l_mt = reinterpret_cast<uint4 *>(mt_lds);
@@ -822,12 +801,12 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
                 double arrival_lambda = p.arrival_lambda, holding_lambda = p.holding_lambda;
                 if constexpr (TRAFFIC) orlg_env_rates(kernarg_params()->rates, env_s, arrival_lambda, holding_lambda);   // (the rates of env_s)
                 const int got = p.br_width > 0   // bit_rate_selection="continuous"
-                    ? refill_requests_cont_t<false>(mt_lds, p.ring_iat + (size_t)env_s * ORLG_RING, p.ring_ht + (size_t)env_s * ORLG_RING,
-                                                    p.ring_req + (size_t)env_s * ORLG_RING, tb.src_cum, tb.dst_cum, &idx_s, N, p.br_width,
-                                                    arrival_lambda, holding_lambda)
-                    : refill_requests(mt_lds, p.ring_iat + (size_t)env_s * ORLG_RING, p.ring_ht + (size_t)env_s * ORLG_RING,
-                                      p.ring_req + (size_t)env_s * ORLG_RING, tb.src_cum, tb.dst_cum, tb.br_cum, &idx_s, N,
-                                      NBR, arrival_lambda, holding_lambda, env_s);
+                    ? refill_requests_cont<false>(mt_lds, p.ring_iat + (size_t)env_s * ORLG_RING, p.ring_ht + (size_t)env_s * ORLG_RING,
+                                                  p.ring_req + (size_t)env_s * ORLG_RING, tb.src_cum, tb.dst_cum, &idx_s, N, p.br_width,
+                                                  arrival_lambda, holding_lambda)
+                    : refill_requests<false>(mt_lds, p.ring_iat + (size_t)env_s * ORLG_RING, p.ring_ht + (size_t)env_s * ORLG_RING,
+                                             p.ring_req + (size_t)env_s * ORLG_RING, tb.src_cum, tb.dst_cum, tb.br_cum, &idx_s, N,
+                                             NBR, arrival_lambda, holding_lambda, env_s);
                 m0 = l_mt[lane]; m1 = l_mt[lane + 64];
                 if (lane < 156 - 128) m2 = l_mt[lane + 128];
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // this wave's reads of the buffer are done
@@ -835,11 +814,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3)
                 uint4 *o_mt = reinterpret_cast<uint4 *>(p.mt + (size_t)env_s * ORLG_MT_N);
                 o_mt[lane] = m0; o_mt[lane + 64] = m1;
                 if (lane < 156 - 128) o_mt[lane + 128] = m2;
-                // the ring entries written by other lanes are read back by this wave below: the stores have to be complete (same
-                // CU: the vector cache is write-through and coherent for its own CU's stores, no L2 write-back / invalidate needed)
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                wave_sync();
+                ring_visible();
                 if ((lane & 48) == src_lane) { ring_cnt = got; ring_pos = 0; mt_idx = idx_s; dry = false; }
             }
             SEC(7);

@@ -163,283 +163,8 @@ DEV void copy_words(void *dst, const void *src, int bytes, int lane) {
     for (int i = (n16 << 2) + lane; i < (bytes >> 2); i += 64) d4[i] = s4[i];
 }
 
-// ---------------------------------------------------------------------------------------- MT19937
-// Regenerate all 624 words in place (CPython _randommodule.c genrand_uint32).  Sub-round r handles
-// kk = 64r + lane; mt[kk+1] is still old (same or later sub-round), mt[kk+397] is old for kk < 227 and
-// mt[kk-227] is already new for kk >= 227, exactly as in the sequential loop.
-template <typename MT /* pointer to the 624 state words: generic or LDS-qualified */>
-DEV void mt_regenerate(MT mt, int lane) {
-    for (int r = 0; r < 10; ++r) {
-        int kk = 64 * r + lane;
-        uint32_t v = 0;
-        if (kk < ORLG_MT_N) {
-            int k1 = kk + 1 == ORLG_MT_N ? 0 : kk + 1;
-            int ks = kk < ORLG_MT_N - ORLG_MT_M ? kk + ORLG_MT_M : kk - (ORLG_MT_N - ORLG_MT_M);
-            uint32_t y = (mt[kk] & 0x80000000u) | (mt[k1] & 0x7fffffffu);
-            v = mt[ks] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-        }
-        wave_sync();
-        if (kk < ORLG_MT_N) mt[kk] = v;
-        wave_sync();
-    }
-}
-
-// Five consecutive random.random() values, returned wave-uniform.
-DEV void draw5(Wave &wv, int &idx, double (&u)[5]) {
-    const int lane = wv.lane;
-    int avail = ORLG_MT_N - idx;
-    uint32_t w = 0;
-    if (avail >= 10) {
-        if (lane < 10) w = wv.mt[idx + lane];
-        idx += 10;
-    } else {
-        if (lane < avail) w = wv.mt[idx + lane];
-        mt_regenerate(wv.mt, lane);
-        if (lane >= avail && lane < 10) w = wv.mt[lane - avail];
-        idx = 10 - avail;
-    }
-    w ^= (w >> 11);
-    w ^= (w << 7) & 0x9d2c5680u;
-    w ^= (w << 15) & 0xefc60000u;
-    w ^= (w >> 18);
-    uint32_t nb = (uint32_t)__shfl_down((int)w, 1);
-    double d = ((double)(w >> 5) * 67108864.0 + (double)(nb >> 6)) * (1.0 / 9007199254740992.0);
-#pragma unroll
-    for (int q = 0; q < 5; ++q) u[q] = readlane_d(d, 2 * q);
-}
-
-// random.choices(population, weights)[0] with cumulative weights: bisect_right(cum, u*total, 0, n-1)
-// = number of cum[0..n-2] that are <= x (cum is non-decreasing).
-DEV int choice_cum(const double *cum, int n, double u, int lane) {
-    double total = cum[n - 1] + 0.0;
-    double x = u * total;
-    double c = lane < n - 1 ? cum[lane] : 0.0;
-    return popc64(ballot(lane < n - 1 && c <= x));
-}
-
-// Pre-generate arrivals, one per lane (_next_service's five random() draws each: inter-arrival, holding time, source,
-// destination, bit rate -- rmsa_env.py:646-659, optical_network_env.py:197-206).  The arrival process does not depend
-// on the network state, so lane j produces request j of the RNG stream: words [idx + 10 j, idx + 10 j + 10).  At most
-// one MT19937 regeneration happens inside a refill (n is capped accordingly), exactly where the sequential
-// generator would do it.  Returns the number of requests written to the ring.
-// (Out of line, so its pointers carry their address space in the signature: through generic pointers every access of the
-// MT19937 state and the tables in LDS was a flat instruction.  RING_LDS: the ring lives in LDS (wave-per-environment kernel)
-// or in HBM (the other two).  Returns count | new index << 8.)
-typedef __attribute__((address_space(3))) uint32_t orlg_lds_u32;
-typedef __attribute__((address_space(3))) double orlg_lds_f64;
-typedef __attribute__((address_space(3))) const double orlg_lds_cf64;
-typedef __attribute__((address_space(1))) uint32_t orlg_glb_u32;
-typedef __attribute__((address_space(1))) double orlg_glb_f64;
-template <bool RING_LDS>
-__device__ __noinline__ int refill_requests_as(orlg_lds_u32 *mt, void *ring_iat_v, void *ring_ht_v, void *ring_req_v,
-                                               orlg_lds_cf64 *src_cum, orlg_lds_cf64 *dst_cum, orlg_lds_cf64 *br_cum, int idx,
-                                               int N, int NBR, double lam_arrival, double lam_holding, int env) {
-    // out of line on purpose: it runs once per ~62 steps and must not add register pressure to the step loop
-    const int lane = threadIdx.x & 63;
-    const double ylam_arrival = recip_refine(lam_arrival), ylam_holding = recip_refine(lam_holding);
-    int n = (2 * ORLG_MT_N - idx) / 10;
-    n = n > ORLG_RING ? ORLG_RING : n;
-    // A freshly seeded generator (idx == 624: every environment's first refill) hands out 62 - env % 56 requests instead of 62.
-    // The request stream is the same whatever a refill's size; what changes is WHEN the environments run dry: batches stepped
-    // one launch per step (agent-driven) otherwise refill all at once every 62nd launch, one after the other behind the
-    // workgroup's staging-buffer lock.
-#ifndef ORLG_EXP_NO_STAGGER   // (experiment: every environment refills in the same launch, the other 61 of 62 launches none)
-    if (idx == ORLG_MT_N) { const int cap = 62 - env % 56; n = n > cap ? cap : n; }
-#endif
-    uint32_t w[10];
-    const int g0 = idx + 10 * lane;
-#pragma unroll
-    for (int k = 0; k < 10; ++k) w[k] = (lane < n && g0 + k < ORLG_MT_N) ? mt[g0 + k] : 0u;
-    if (idx + 10 * n > ORLG_MT_N) {
-        mt_regenerate(mt, lane);
-#pragma unroll
-        for (int k = 0; k < 10; ++k)
-            if (lane < n && g0 + k >= ORLG_MT_N) w[k] = mt[g0 + k - ORLG_MT_N];
-        idx = idx + 10 * n - ORLG_MT_N;
-    } else {
-        idx += 10 * n;
-    }
-    double u[5];
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-        uint32_t a = w[2 * q], b = w[2 * q + 1];
-        a ^= (a >> 11); a ^= (a << 7) & 0x9d2c5680u; a ^= (a << 15) & 0xefc60000u; a ^= (a >> 18);
-        b ^= (b >> 11); b ^= (b << 7) & 0x9d2c5680u; b ^= (b << 15) & 0xefc60000u; b ^= (b >> 18);
-        u[q] = ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
-    }
-    const double iat = div_by(-orlg_log(1.0 - u[0]), lam_arrival, ylam_arrival);
-    const double ht = div_by(-orlg_log(1.0 - u[1]), lam_holding, ylam_holding);
-    // random.choices: bisect_right(cum, u * total, 0, n - 1) = #{i < n - 1 : cum[i] <= x}
-    int src = 0, dst = 0, bri = 0;
-    {
-        const double x = u[2] * (src_cum[N - 1] + 0.0);
-        for (int i = 0; i < N - 1; ++i) src += src_cum[i] <= x ? 1 : 0;
-    }
-    {
-        orlg_lds_cf64 *row = dst_cum + src * N;
-        const double x = u[3] * (row[N - 1] + 0.0);
-        for (int i = 0; i < N - 1; ++i) dst += row[i] <= x ? 1 : 0;
-    }
-    {
-        const double x = u[4] * (br_cum[NBR - 1] + 0.0);
-        for (int i = 0; i < NBR - 1; ++i) bri += br_cum[i] <= x ? 1 : 0;
-    }
-    // entries past n are dead; they are zeroed so that a snapshot of the state does not depend on what the ring held before
-    const double o_iat = lane < n ? iat : 0.0, o_ht = lane < n ? ht : 0.0;
-    const uint32_t o_rq = lane < n ? ((uint32_t)src | ((uint32_t)dst << 8) | ((uint32_t)bri << 16)) : 0u;
-    if (RING_LDS) {
-        ((orlg_lds_f64 *)ring_iat_v)[lane] = o_iat; ((orlg_lds_f64 *)ring_ht_v)[lane] = o_ht; ((orlg_lds_u32 *)ring_req_v)[lane] = o_rq;
-    } else {
-        ((orlg_glb_f64 *)ring_iat_v)[lane] = o_iat; ((orlg_glb_f64 *)ring_ht_v)[lane] = o_ht; ((orlg_glb_u32 *)ring_req_v)[lane] = o_rq;
-    }
-    wave_sync();
-    return n | (idx << 8);
-}
-// the callers' form: generic pointers in, the new MT19937 index through idx_io
-template <bool RING_LDS>
-DEV int refill_requests_t(uint32_t *mt, double *ring_iat, double *ring_ht, uint32_t *ring_req, const double *src_cum,
-                          const double *dst_cum, const double *br_cum, int *idx_io, int N, int NBR, double lam_arrival,
-                          double lam_holding, int env) {
-    const int r = refill_requests_as<RING_LDS>((orlg_lds_u32 *)mt, ring_iat, ring_ht, ring_req, (orlg_lds_cf64 *)src_cum,
-                                               (orlg_lds_cf64 *)dst_cum, (orlg_lds_cf64 *)br_cum, *idx_io, N, NBR, lam_arrival,
-                                               lam_holding, env);
-    *idx_io = r >> 8;
-    return r & 0xff;
-}
-DEV int refill_requests(uint32_t *mt, double *ring_iat, double *ring_ht, uint32_t *ring_req, const double *src_cum,
-                        const double *dst_cum, const double *br_cum, int *idx_io, int N, int NBR, double lam_arrival,
-                        double lam_holding, int env) {   // ring in HBM
-    return refill_requests_t<false>(mt, ring_iat, ring_ht, ring_req, src_cum, dst_cum, br_cum, idx_io, N, NBR, lam_arrival, lam_holding, env);
-}
-
-// bit_rate_selection="continuous" (rmsa_env.py:95-101, 655-659): the bit rate is rng.randint(lower, higher) = lower +
-// _randbelow(width), CPython's _randbelow_with_getrandbits: k = width.bit_length(); r = getrandbits(k) -- one MT19937 word
-// shifted right by 32 - k -- until r < width.  A request then consumes eight words for its four random() values and a
-// VARIABLE number for the bit rate, so request j no longer starts at a known word.  Two phases: (1) one walk over the word
-// stream, wave-uniform, that only looks at the bit-rate words -- where every request starts and which r it accepts (~25
-// instructions per request); (2) lane j computes request j from its eight words like the discrete generator.  A refill
-// stays inside the state's current 624 words; the request that straddles a regeneration is generated alone, word by word.
-// The ring entry holds r (the index into the table of the width bit rates lower .. higher).  Returns count | new index << 8.
-template <bool RING_LDS>
-__device__ __noinline__ int refill_requests_cont_as(orlg_lds_u32 *mt, void *ring_iat_v, void *ring_ht_v, void *ring_req_v,
-                                                    orlg_lds_cf64 *src_cum, orlg_lds_cf64 *dst_cum, int idx, int N, int width,
-                                                    double lam_arrival, double lam_holding) {
-    const int lane = threadIdx.x & 63;
-    const double ylam_arrival = recip_refine(lam_arrival), ylam_holding = recip_refine(lam_holding);
-    const int sh = 32 - (32 - __builtin_clz((unsigned)width));   // 32 - k, k = width.bit_length()
-    auto temper = [](uint32_t y) { y ^= (y >> 11); y ^= (y << 7) & 0x9d2c5680u; y ^= (y << 15) & 0xefc60000u; y ^= (y >> 18); return y; };
-    if (idx >= ORLG_MT_N) { mt_regenerate(mt, lane); idx = 0; }
-    // phase 1: the requests that lie inside [idx, 624)
-    int n = 0, my_off = 0, my_r = 0, off = idx;
-    for (; n < ORLG_RING; ++n) {
-        int w = off + 8;
-        if (w >= ORLG_MT_N) break;
-        int r = 0;
-        bool got = false;
-        while (w < ORLG_MT_N) {
-            r = (int)(temper(mt[w]) >> sh);
-            w += 1;
-            if (r < width) { got = true; break; }
-        }
-        if (!got) break;          // its bit-rate draws run past the state's end
-        if (lane == n) { my_off = off; my_r = r; }
-        off = w;
-    }
-    double u[4];
-    if (n == 0) {
-        // the straddler: word by word through the regeneration, every lane the same values
-        uint32_t wq[8];
-        int r = 0;
-        for (int k = 0;; ++k) {
-            if (off >= ORLG_MT_N) { mt_regenerate(mt, lane); off = 0; }
-            const uint32_t y = temper(mt[off]);
-            off += 1;
-            if (k < 8) { wq[k] = y; continue; }
-            r = (int)(y >> sh);
-            if (r < width) break;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) u[q] = ((double)(wq[2 * q] >> 5) * 67108864.0 + (double)(wq[2 * q + 1] >> 6)) * (1.0 / 9007199254740992.0);
-        my_r = r;
-        n = 1;
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t a = lane < n ? temper(mt[my_off + 2 * q]) : 0u, b = lane < n ? temper(mt[my_off + 2 * q + 1]) : 0u;
-            u[q] = ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
-        }
-    }
-    idx = off;
-    const double iat = div_by(-orlg_log(1.0 - u[0]), lam_arrival, ylam_arrival);
-    const double ht = div_by(-orlg_log(1.0 - u[1]), lam_holding, ylam_holding);
-    int src = 0, dst = 0;
-    {
-        const double x = u[2] * (src_cum[N - 1] + 0.0);
-        for (int i = 0; i < N - 1; ++i) src += src_cum[i] <= x ? 1 : 0;
-    }
-    {
-        orlg_lds_cf64 *row = dst_cum + src * N;
-        const double x = u[3] * (row[N - 1] + 0.0);
-        for (int i = 0; i < N - 1; ++i) dst += row[i] <= x ? 1 : 0;
-    }
-    const double o_iat = lane < n ? iat : 0.0, o_ht = lane < n ? ht : 0.0;
-    const uint32_t o_rq = lane < n ? ((uint32_t)src | ((uint32_t)dst << 8) | ((uint32_t)my_r << 16)) : 0u;
-    if (RING_LDS) {
-        ((orlg_lds_f64 *)ring_iat_v)[lane] = o_iat; ((orlg_lds_f64 *)ring_ht_v)[lane] = o_ht; ((orlg_lds_u32 *)ring_req_v)[lane] = o_rq;
-    } else {
-        ((orlg_glb_f64 *)ring_iat_v)[lane] = o_iat; ((orlg_glb_f64 *)ring_ht_v)[lane] = o_ht; ((orlg_glb_u32 *)ring_req_v)[lane] = o_rq;
-    }
-    wave_sync();
-    return n | (idx << 8);
-}
-template <bool RING_LDS>
-DEV int refill_requests_cont_t(uint32_t *mt, double *ring_iat, double *ring_ht, uint32_t *ring_req, const double *src_cum,
-                               const double *dst_cum, int *idx_io, int N, int width, double lam_arrival, double lam_holding) {
-    const int r = refill_requests_cont_as<RING_LDS>((orlg_lds_u32 *)mt, ring_iat, ring_ht, ring_req, (orlg_lds_cf64 *)src_cum,
-                                                    (orlg_lds_cf64 *)dst_cum, *idx_io, N, width, lam_arrival, lam_holding);
-    *idx_io = r >> 8;
-    return r & 0xff;
-}
-
-// A request trace as the ring's second producer (include/orlg.h orlg_create_trace): lane j copies request cursor + j of the
-// environment from the device trace into ring slot j -- three coalesced loads, no MT19937 state, no logarithm.  The ring's first
-// array then holds ABSOLUTE arrival times (the step takes them as they are: a recorded time comes back with its own bits).
-// cursor = requests of the environment copied so far (kept where a generated handle keeps the MT19937 position).  The first
-// refill keeps the stagger of refill_requests_as.  A cursor outside the trace copies nothing (the host refuses a launch that
-// would draw past the end; a state from elsewhere must not make the loads leave the arrays).  Returns the count.
-typedef __attribute__((address_space(1))) const double orlg_glb_cf64;
-typedef __attribute__((address_space(1))) const uint32_t orlg_glb_cu32;
-template <bool RING_LDS>
-__device__ __noinline__ int refill_requests_trace_as(orlg_glb_cf64 *tr_arrival, orlg_glb_cf64 *tr_holding, orlg_glb_cu32 *tr_req,
-                                                     void *ring_iat_v, void *ring_ht_v, void *ring_req_v, int cursor, int length,
-                                                     int env) {
-    const int lane = threadIdx.x & 63;
-    int n = length - cursor;
-    n = n > ORLG_RING ? ORLG_RING : n;
-    if (cursor == 0) { const int cap = 62 - env % 56; n = n > cap ? cap : n; }
-    if (cursor < 0 || n < 0) n = 0;
-    const size_t at = (size_t)env * (size_t)length + (size_t)(cursor > 0 ? cursor : 0) + (size_t)lane;
-    double o_at = 0.0, o_ht = 0.0;
-    uint32_t o_rq = 0u;
-    if (lane < n) { o_at = tr_arrival[at]; o_ht = tr_holding[at]; o_rq = tr_req[at]; }
-    // entries past n are dead and zeroed, as in refill_requests_as
-    if (RING_LDS) {
-        ((orlg_lds_f64 *)ring_iat_v)[lane] = o_at; ((orlg_lds_f64 *)ring_ht_v)[lane] = o_ht; ((orlg_lds_u32 *)ring_req_v)[lane] = o_rq;
-    } else {
-        ((orlg_glb_f64 *)ring_iat_v)[lane] = o_at; ((orlg_glb_f64 *)ring_ht_v)[lane] = o_ht; ((orlg_glb_u32 *)ring_req_v)[lane] = o_rq;
-    }
-    wave_sync();
-    return n;
-}
-// the callers' form: generic pointers in, the cursor advanced through cursor_io
-template <bool RING_LDS>
-DEV int refill_requests_trace_t(const double *tr_arrival, const double *tr_holding, const uint32_t *tr_req, double *ring_iat,
-                                double *ring_ht, uint32_t *ring_req, int *cursor_io, int length, int env) {
-    const int n = refill_requests_trace_as<RING_LDS>((orlg_glb_cf64 *)tr_arrival, (orlg_glb_cf64 *)tr_holding, (orlg_glb_cu32 *)tr_req,
-                                                     ring_iat, ring_ht, ring_req, *cursor_io, length, env);
-    *cursor_io += n;
-    return n;
-}
+// ---------------------------------------------------------------------------------------- arrivals
+#include "orlg_requests.h"   // mt_regenerate, the ring's three producers, ring_store, ring_visible
 
 // ---------------------------------------------------------------------------------------- first fit
 // x[w]: wave-uniform free bitmap of one path (AND over its links).  Lane l of word w owns slot 64w+l
@@ -588,13 +313,13 @@ DEV double network_compactness(int sum_span, int sum_slots_hops, int sum_gaps, i
     return 1.0;
 }
 
-// kernel parameters re-read from the kernarg segment through an opaque pointer: lets the compiler drop
-// rarely used pointers from SGPRs across the step loop instead of spilling them
+// the RMSA kernels re-read their parameters through an OPAQUE pointer: lets the compiler drop rarely used pointers from SGPRs
+// across the step loop instead of spilling them
 typedef const OrlgParams __attribute__((address_space(4))) *KernargParams;
 DEV KernargParams kernarg_params() {
-    auto k = __builtin_amdgcn_kernarg_segment_ptr();
+    auto k = kernarg_as<OrlgParams>();
     asm volatile("" : "+s"(k));
-    return (KernargParams)k;
+    return k;
 }
 
 // (arrival_lambda, holding_lambda) of environment `env` (wave-uniform) of a handle with per-environment traffic; a handle without
@@ -683,10 +408,6 @@ DEV double wave_add_f64(double v) {   // the association order differs from a se
     return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
 }
 
-DEV u64 lane_next_u64(u64 v) {
-    const uint32_t lo = (uint32_t)lane_next_i32((int)(uint32_t)v), hi = (uint32_t)lane_next_i32((int)(uint32_t)(v >> 32));
-    return ((u64)hi << 32) | lo;
-}
 DEV int wave_min_i32(int v) {
     int o = dpp_xor1(v); v = o < v ? o : v;
     o = dpp_xor2(v); v = o < v ? o : v;
@@ -1349,8 +1070,8 @@ DEV void rmsa_body(const OrlgParams &p) {
                 KernargParams kq = kernarg_params();
                 ring_dirty = true;
                 ring_in_lds = true;
-                ring_cnt = refill_requests_trace_t<true>(kq->tr_arrival, kq->tr_holding, kq->tr_req, wv.ring_iat, wv.ring_ht, wv.ring_req,
-                                                         &mt_idx, kq->tr_len, env);
+                ring_cnt = refill_requests_trace<true>(kq->tr_arrival, kq->tr_holding, kq->tr_req, wv.ring_iat, wv.ring_ht, wv.ring_req,
+                                                       &mt_idx, kq->tr_len, env);
                 ring_pos = 0;
                 SEC(7);
             } else if (ring_cnt == 0) {
@@ -1365,11 +1086,11 @@ DEV void rmsa_body(const OrlgParams &p) {
                 double arrival_lambda = p.arrival_lambda, holding_lambda = p.holding_lambda;
                 orlg_env_rates(kernarg_params()->rates, env, arrival_lambda, holding_lambda);   // (a sweep: the environment's own)
                 if (p.br_width > 0)   // bit_rate_selection="continuous"
-                    ring_cnt = refill_requests_cont_t<true>(wv.mt, wv.ring_iat, wv.ring_ht, wv.ring_req, tb.src_cum, tb.dst_cum, &mt_idx, N,
-                                                            p.br_width, arrival_lambda, holding_lambda);
+                    ring_cnt = refill_requests_cont<true>(wv.mt, wv.ring_iat, wv.ring_ht, wv.ring_req, tb.src_cum, tb.dst_cum, &mt_idx, N,
+                                                          p.br_width, arrival_lambda, holding_lambda);
                 else
-                    ring_cnt = refill_requests_t<true>(wv.mt, wv.ring_iat, wv.ring_ht, wv.ring_req, tb.src_cum, tb.dst_cum, tb.br_cum,
-                                                       &mt_idx, N, NBR, arrival_lambda, holding_lambda, env);
+                    ring_cnt = refill_requests<true>(wv.mt, wv.ring_iat, wv.ring_ht, wv.ring_req, tb.src_cum, tb.dst_cum, tb.br_cum,
+                                                     &mt_idx, N, NBR, arrival_lambda, holding_lambda, env);
                 ring_pos = 0;
                 SEC(7);
             }

@@ -17,6 +17,7 @@
 // Lanes are channels: lane l of word w owns channel 64w + l.
 #pragma once
 #include "orlg_kernels.hip"
+#include "orlg_requests.h"
 
 #define ORLG_PHY_MAX_CH 14
 #define ORLG_PHY_MAX_K 5
@@ -714,8 +715,7 @@ DEV int nb_collect(NearBuffer &nb, const double *gq, int n_running, double horiz
 // the holding rate that sizes the horizon of nb_rebuild: the handle's scalar, or the environment's own of a handle with
 // per-environment traffic -- fetched from the kernel arguments and the scalar cache at the call, not kept in a register
 DEV double phy_holding_lambda(double holding_lambda, int env) {
-    const OrlgPhyParams __attribute__((address_space(4))) *kq =
-        (const OrlgPhyParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+    const auto kq = kernarg_as<OrlgPhyParams>();
     double arrival_lambda = 0.0;
     orlg_env_rates(kq->rates, env, arrival_lambda, holding_lambda);
     return holding_lambda;
@@ -836,8 +836,7 @@ DEV void mc_after(const u64 *occ, MetricCache &mc, int ch, int lane) {
         if (mc.defer) {
             if (mc.nlog < ORLG_RLOG_CAP) {
                 if (lane == 0) {
-                    const OrlgPhyParams __attribute__((address_space(4))) *kq =
-                        (const OrlgPhyParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+                    const auto kq = kernarg_as<OrlgPhyParams>();
                     const size_t at = (size_t)mc.env * ORLG_RLOG_CAP + mc.nlog;
                     kq->rlog_val[at] = t; kq->rlog_key[at] = (uint32_t)ch | ((uint32_t)mc.stamp << 16);
                 }
@@ -855,8 +854,7 @@ template <int W>
 DEV void mc_flush(MetricCache &mc, const double *terms_now /* LDS [W*64] */, u64 *ormask /* LDS [W] */, int C, int cpad, int lane,
                   uint64_t out_rss, size_t B) {
     constexpr int SL = ORLG_RLOG_CAP / 64;
-    const OrlgPhyParams __attribute__((address_space(4))) *kq =
-        (const OrlgPhyParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+    const auto kq = kernarg_as<OrlgPhyParams>();
     const uint32_t *lkey = kq->rlog_key + (size_t)mc.env * ORLG_RLOG_CAP;
     const double *lval = kq->rlog_val + (size_t)mc.env * ORLG_RLOG_CAP;
     double *lt0 = kq->rlog_t0 + (size_t)mc.env * cpad;
@@ -1880,8 +1878,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
         }
     }
     if (!p.ticket_stride && lane == 0) {
-        const OrlgPhyParams __attribute__((address_space(4))) *kq =
-            (const OrlgPhyParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+        const auto kq = kernarg_as<OrlgPhyParams>();
         nxt_tk = atomicAdd(kq->ticket, 1u);
     }
     OrlgPhySvc *grec = p.qrec + (size_t)env * Q;
@@ -1973,8 +1970,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
         pf_ring_ok = ring_cnt > 0;
         pf_next_ok = ring_cnt > 1;
         if (pf_ring_ok) {
-            const OrlgPhyParams __attribute__((address_space(4))) *kq =
-                (const OrlgPhyParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+            const auto kq = kernarg_as<OrlgPhyParams>();
             const size_t ro = (size_t)env * ORLG_RING + ring_pos;
             const uint32_t *src = lane < 2 ? reinterpret_cast<const uint32_t *>(kq->ring_iat + ro) + lane
                                 : lane < 4 ? reinterpret_cast<const uint32_t *>(kq->ring_ht + ro) + (lane - 2)
@@ -2020,8 +2016,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
             }
 
             if (policy == ORLG_PHY_POLICY_EXTERNAL) {
-                const OrlgPhyParams __attribute__((address_space(4))) *kp =
-                    (const OrlgPhyParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+                const auto kp = kernarg_as<OrlgPhyParams>();
                 a_path = uni(kp->act_path[env]);
                 const int16_t *ac = kp->act_channels + (size_t)env * ORLG_PHY_MAX_CH;
                 int raw = lane < ORLG_PHY_MAX_CH ? (int)ac[lane] : -1;
@@ -2572,22 +2567,17 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
             constexpr bool from_trace = TRACE;
             if (TRACE && ring_cnt == 0) {
                 SEC(8);  // refill: the next requests of the trace -- no staging buffer, no lock, no generator state
-                const OrlgPhyParams __attribute__((address_space(4))) *kq =
-                    (const OrlgPhyParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
-                const int got = refill_requests_trace_t<false>(kq->tr_arrival, kq->tr_holding, kq->tr_req, kq->ring_iat + (size_t)env * ORLG_RING,
-                                                               kq->ring_ht + (size_t)env * ORLG_RING, kq->ring_req + (size_t)env * ORLG_RING,
-                                                               &mt_idx, kq->tr_len, env);
-                // the ring entries other lanes wrote are read back below: same CU, the stores only have to be complete
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                wave_sync();
+                const auto kq = kernarg_as<OrlgPhyParams>();
+                const int got = refill_requests_trace<false>(kq->tr_arrival, kq->tr_holding, kq->tr_req, kq->ring_iat + (size_t)env * ORLG_RING,
+                                                             kq->ring_ht + (size_t)env * ORLG_RING, kq->ring_req + (size_t)env * ORLG_RING,
+                                                             &mt_idx, kq->tr_len, env);
+                ring_visible();
                 ring_cnt = got; ring_pos = 0;
                 SEC(7);
             } else if (ring_cnt == 0) {
-                SEC(8);  // refill
+                SEC(8);  // refill (the sequence of orlg_group_kernels.hip, written out in both: orlg_requests.h says why)
                 static_assert(ORLG_MT_N * 4 == 156 * 16, "MT19937 state = 156 rows of 16 bytes");
-                const OrlgPhyParams __attribute__((address_space(4))) *kq =
-                    (const OrlgPhyParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+                const auto kq = kernarg_as<OrlgPhyParams>();
                 const uint4 *g_mt = reinterpret_cast<const uint4 *>(kq->mt + (size_t)env * ORLG_MT_N);
                 uint4 *l_mt = reinterpret_cast<uint4 *>(mt_lds);
                 uint4 m0 = g_mt[lane], m1 = g_mt[lane + 64], m2 = make_uint4(0u, 0u, 0u, 0u);
@@ -2603,12 +2593,12 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                 double arrival_lambda = p.arrival_lambda, holding_lambda = p.holding_lambda;
                 orlg_env_rates(kq->rates, env, arrival_lambda, holding_lambda);   // (a sweep: the environment's own)
                 const int got = CONT   // rng.randint(lower, higher) (phy_rmsa_env.py:127-129): the ring entry holds r, the rate is lower + r
-                    ? refill_requests_cont_t<false>(mt_lds, kq->ring_iat + (size_t)env * ORLG_RING, kq->ring_ht + (size_t)env * ORLG_RING,
-                                                    kq->ring_req + (size_t)env * ORLG_RING, tb.src_cum, tb.dst_cum, &idx_s, N, NBR,
-                                                    arrival_lambda, holding_lambda)
-                    : refill_requests(mt_lds, kq->ring_iat + (size_t)env * ORLG_RING, kq->ring_ht + (size_t)env * ORLG_RING,
-                                                kq->ring_req + (size_t)env * ORLG_RING, tb.src_cum, tb.dst_cum, tb.br_cum, &idx_s, N, NBR,
-                                                arrival_lambda, holding_lambda, env);
+                    ? refill_requests_cont<false>(mt_lds, kq->ring_iat + (size_t)env * ORLG_RING, kq->ring_ht + (size_t)env * ORLG_RING,
+                                                  kq->ring_req + (size_t)env * ORLG_RING, tb.src_cum, tb.dst_cum, &idx_s, N, NBR,
+                                                  arrival_lambda, holding_lambda)
+                    : refill_requests<false>(mt_lds, kq->ring_iat + (size_t)env * ORLG_RING, kq->ring_ht + (size_t)env * ORLG_RING,
+                                             kq->ring_req + (size_t)env * ORLG_RING, tb.src_cum, tb.dst_cum, tb.br_cum, &idx_s, N, NBR,
+                                             arrival_lambda, holding_lambda, env);
                 m0 = l_mt[lane]; m1 = l_mt[lane + 64];
                 if (lane < 156 - 128) m2 = l_mt[lane + 128];
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // this wave's reads of the buffer are done
@@ -2616,10 +2606,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
                 uint4 *o_mt = reinterpret_cast<uint4 *>(kq->mt + (size_t)env * ORLG_MT_N);
                 o_mt[lane] = m0; o_mt[lane + 64] = m1;
                 if (lane < 156 - 128) o_mt[lane + 128] = m2;
-                // the ring entries other lanes wrote are read back below: same CU, the stores only have to be complete
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                wave_sync();
+                ring_visible();
                 mt_idx = idx_s; ring_cnt = got; ring_pos = 0;
                 SEC(7);
             }
@@ -2848,8 +2835,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_p
     // ------------------------------------------------------------------ LDS -> HBM
     wave_sync();
     {
-        const OrlgPhyParams __attribute__((address_space(4))) *kp =
-            (const OrlgPhyParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+        const auto kp = kernarg_as<OrlgPhyParams>();
         u64 *g = kp->occ + (size_t)env * NW;
         for (int i = lane; i < NW; i += 64) g[i] = occ[i];
         OrlgPhyScalars *go = kp->scal + env;

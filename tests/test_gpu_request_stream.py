@@ -1,0 +1,158 @@
+"""The request stream itself: what the arrival ring's producers (csrc/orlg_requests.h) hand to the three step kernels, held
+per step to the C oracle bit for bit -- arrival, holding, source, destination, bit rate -- for every producer (MT19937 with
+discrete and with continuous bit rates, per-environment rates, a trace) and both places a ring is read from (LDS / the
+prefetch in a long launch, HBM in one-step launches).
+
+B = 60: the first refill of environments 0, 55 and 56 hands out 62, 7 and 62 requests (both ends of the stagger and its wrap),
+and 60 is fifteen full quads of the group kernel.  One launch of 200 steps (every environment refills and regenerates its
+generator at least three times), then 70 one-step launches (every environment refills at least once more).
+
+Continuous bit rates are 100..350 in every case (width 251 of 256: not a power of two, the rejection loop runs), not 100..600:
+the RMSA handle and the RMSA oracle take at most 256 rates (ORC_MAX_BIT_RATES), and the QoT-aware oracle has no continuous
+mode.  A request is the same function of the generator in both environments (five draws in the same order, next_service of
+orlg_oracle.c and orlg_oracle_phy.c), so the continuous QoT-aware stream is held to the RMSA oracle's on the same nodes and
+rates; width 501 stays with the reference's traces in tests/test_gpu_phy_continuous.py (times to rtol 1e-12)."""
+import functools
+
+import numpy as np
+import pytest
+
+from conftest import load_phy_tables, load_topology, oracle_env_from_kwargs, phy_oracle_from_kwargs
+from test_gpu_rmsa import device_log_in_oracle  # noqa: F401
+from test_gpu_sweep import RMSA_OUTS
+from test_gpu_trace import one_step_launches, phy, rmsa, same_bytes
+
+pytestmark = pytest.mark.gpu
+
+B, CHECKED = 60, (0, 1, 3, 54, 55, 56, 59)
+LONG, SINGLE = 200, 70
+N = LONG + SINGLE
+POLICY = "sap_ff"
+STREAM = ("request", "arrival", "holding")
+CONT = dict(bit_rate_selection="continuous", bit_rate_lower_bound=100, bit_rate_higher_bound=350)
+LOADS = np.where(np.arange(B) % 2 == 0, 50.0, 120.0)   # two loads inside every quad
+RMSA_KW = dict(num_spectrum_resources=64, mean_service_holding_time=25, episode_length=1000, seed=10)
+VARIANTS = {"discrete": dict(load=50), "continuous": dict(load=50, **CONT), "traffic": dict(load=LOADS)}
+
+PHY_B = 8
+PHY_POLICY = "bmfa"
+PHY_KW = dict(load=900, mean_service_holding_time=25, episode_length=1000, seed=3, grooming=False)
+PHY_OUTS = ("act_path", "n_channels", "channels", "accepted", "done") + STREAM
+
+
+def scheduled(env, run_long, run_single, outs):
+    """The schedule on a fresh handle; the handle is closed."""
+    long = run_long(outs)
+    state_long = env.save_state().copy()
+    single = run_single(outs)
+    r = dict(outs={k: np.concatenate([long[k], single[k]]) for k in outs}, long={k: long[k] for k in outs},
+             state_long=state_long, state_end=env.save_state().copy(), pending=env.requests())
+    env.close()
+    return r
+
+
+def trace_of(r):
+    """The N served requests of a run and the pending one."""
+    from optical_rl_gym_amd import RequestTrace
+    o, p = r["outs"], r["pending"]
+    return RequestTrace(np.concatenate([o["arrival"], p["arrival_time"][None]]), np.concatenate([o["holding"], p["holding_time"][None]]),
+                        np.concatenate([o["request"][:, :, 1], p["src"][None]]), np.concatenate([o["request"][:, :, 2], p["dst"][None]]),
+                        np.concatenate([o["request"][:, :, 3], p["bit_rate"][None]]), batch_size=p.shape[0], layout="step")
+
+
+@functools.lru_cache(maxsize=None)
+def rmsa_run(kernel, variant):
+    topo = load_topology("nsfnet_chen_5-paths_6-modulations")
+    if variant == "trace":   # recorded from the discrete run
+        env = rmsa(topo, B, trace=trace_of(rmsa_run("wave", "discrete")), step_kernel=kernel,
+                   **{k: v for k, v in RMSA_KW.items() if k != "seed"})
+    else:
+        env = rmsa(topo, B, step_kernel=kernel, **dict(RMSA_KW, **VARIANTS[variant]))
+    return scheduled(env, lambda outs: env.run(POLICY, LONG, outputs=outs), lambda outs: one_step_launches(env, POLICY, SINGLE, outs),
+                     RMSA_OUTS)
+
+
+@functools.lru_cache(maxsize=None)
+def rmsa_oracle_stream(variant, i):
+    """Environment i's N requests from the oracle (call with the device's logarithm in the oracle)."""
+    topo = load_topology("nsfnet_chen_5-paths_6-modulations")
+    kw = dict(RMSA_KW, **VARIANTS[variant], seed=RMSA_KW["seed"] + i)
+    kw["load"] = float(np.broadcast_to(kw["load"], (B,))[i])
+    o = oracle_env_from_kwargs(topo, kw)
+    ot = o.run(POLICY, N, fields=("src", "dst", "bit_rate", "arrival", "holding"))
+    o.close()
+    return ot
+
+
+def check_stream(tr, i, ot):
+    for q, g in ((1, "src"), (2, "dst"), (3, "bit_rate")):
+        assert np.array_equal(tr["request"][:, i, q], ot[g]), (g, i)
+    for f in ("arrival", "holding"):
+        bad = np.nonzero(tr[f][:, i] != ot[f])[0]
+        assert bad.size == 0, (f, i, bad[:4], tr[f][bad[:4], i], ot[f][bad[:4]])
+
+
+@pytest.mark.parametrize("variant", ["discrete", "continuous", "traffic", "trace"])
+@pytest.mark.parametrize("kernel", ["wave", "group"])
+def test_rmsa_stream_vs_oracle(kernel, variant, device_log_in_oracle):
+    tr = rmsa_run(kernel, variant)["outs"]
+    assert tr["arrival"].shape == (N, B)
+    for i in CHECKED:
+        check_stream(tr, i, rmsa_oracle_stream("discrete" if variant == "trace" else variant, i))
+    if variant == "continuous":
+        assert tr["request"][..., 3].min() >= 100 and tr["request"][..., 3].max() <= 350
+    if variant == "traffic":   # the two loads are two arrival processes
+        assert tr["arrival"][-1, 0::2].min() > tr["arrival"][-1, 1::2].max()
+
+
+@pytest.mark.parametrize("variant", ["discrete", "continuous", "traffic", "trace"])
+def test_wave_and_group_agree(variant):
+    w, g = rmsa_run("wave", variant), rmsa_run("group", variant)
+    same_bytes(w["long"], g["long"], "after the long launch")
+    assert w["state_long"].tobytes() == g["state_long"].tobytes()
+    same_bytes(w["outs"], g["outs"], "at the end")
+    assert w["state_end"].tobytes() == g["state_end"].tobytes()
+
+
+@pytest.mark.parametrize("kernel", ["wave", "group"])
+def test_trace_equals_the_run_it_was_recorded_from(kernel):
+    same_bytes(rmsa_run(kernel, "discrete")["outs"], rmsa_run(kernel, "trace")["outs"])
+
+
+# ------------------------------------------------------------------------------------------------ QoT-aware
+@functools.lru_cache(maxsize=None)
+def phy_run(variant):
+    topo, tables = load_topology("jpn12_3-paths_6-modulations"), load_phy_tables("jpn12_k3")
+    if variant == "trace":
+        kw = {k: v for k, v in PHY_KW.items() if k not in ("load", "mean_service_holding_time", "seed")}
+        env = phy(topo, tables, kw, PHY_B, trace=trace_of(phy_run("discrete")))
+    else:
+        env = phy(topo, tables, dict(PHY_KW, **(CONT if variant == "continuous" else {})), PHY_B)
+    return scheduled(env, lambda outs: env.run(PHY_POLICY, LONG, outputs=outs), lambda outs: one_step_launches(env, PHY_POLICY, SINGLE, outs),
+                     PHY_OUTS)
+
+
+@functools.lru_cache(maxsize=None)
+def phy_oracle_stream(variant, i):
+    topo, tables = load_topology("jpn12_3-paths_6-modulations"), load_phy_tables("jpn12_k3")
+    fields = ("src", "dst", "bit_rate", "arrival", "holding")
+    if variant == "continuous":   # (the RMSA oracle: see the module's docstring)
+        o = oracle_env_from_kwargs(topo, dict(PHY_KW, **CONT, seed=PHY_KW["seed"] + i))
+        ot = o.run(POLICY, N, fields=fields)
+    else:
+        o = phy_oracle_from_kwargs(topo, tables, dict(PHY_KW, seed=PHY_KW["seed"] + i))
+        ot = o.run(PHY_POLICY, N, fields=fields)
+    o.close()
+    return ot
+
+
+@pytest.mark.parametrize("variant", ["discrete", "continuous", "trace"])
+def test_phy_stream_vs_oracle(variant, device_log_in_oracle):
+    tr = phy_run(variant)["outs"]
+    assert tr["arrival"].shape == (N, PHY_B)
+    for i in range(PHY_B):
+        check_stream(tr, i, phy_oracle_stream("discrete" if variant == "trace" else variant, i))
+    if variant == "continuous":
+        assert tr["request"][..., 3].min() >= 100 and tr["request"][..., 3].max() <= 350
+    if variant == "trace":
+        same_bytes(phy_run("discrete")["outs"], phy_run("trace")["outs"])
