@@ -127,53 +127,10 @@ __global__ void orlg_overflow_kernel(const OrlgEnvScalars *scal, int B, int *out
     if (any) atomicOr(out, 1);
 }
 
-// ---------------------------------------------------------------------------------------- kernel dispatch
-// the kernels live in per-W objects (orlg_inst_wave.hip / orlg_inst_group.hip); a W the library was not built for is a null symbol
+// ---------------------------------------------------------------------------------------- launches
+// the kernels live in per-W objects (orlg_inst_wave.hip / orlg_inst_group.hip), found by key: orlg_pick (orlg_variants.h)
 typedef orlg_rmsa_kernel_t rmsa_kernel_t;
 typedef orlg_masks_kernel_t masks_kernel_t;
-static rmsa_kernel_t pick_wave(int W, int kind, int stats) {
-    switch (W) {
-#define X(n) case n: return orlg_wave_kernel_W##n ? orlg_wave_kernel_W##n(kind, stats) : nullptr;
-        ORLG_FOR_EACH_W(X)
-#undef X
-        default: return nullptr;
-    }
-}
-// the wave-per-environment step kernel that only carries the first-fit policies (k <= 8)
-static rmsa_kernel_t pick_rmsa_ff(int W, int stats) { return pick_wave(W, ORLG_KIND_STEP_FF, stats); }
-static rmsa_kernel_t pick_rmsa(int W, int stats, bool step = true) { return pick_wave(W, step ? ORLG_KIND_STEP : ORLG_KIND_RESET, stats); }
-static orlg_obs_kernel_t pick_obs(int W) {
-    switch (W) {
-#define X(n) case n: return orlg_obs_kernel_W##n ? orlg_obs_kernel_W##n() : nullptr;
-        ORLG_FOR_EACH_W(X)
-#undef X
-        default: return nullptr;
-    }
-}
-static orlg_action_masks_kernel_t pick_action_masks(int W) {
-    switch (W) {
-#define X(n) case n: return orlg_action_masks_kernel_W##n ? orlg_action_masks_kernel_W##n() : nullptr;
-        ORLG_FOR_EACH_W(X)
-#undef X
-        default: return nullptr;
-    }
-}
-static rmsa_kernel_t pick_group(int W, int stats) {
-    switch (W) {
-#define X(n) case n: return orlg_group_kernel_W##n ? orlg_group_kernel_W##n(stats) : nullptr;
-        ORLG_FOR_EACH_W(X)
-#undef X
-        default: return nullptr;
-    }
-}
-static masks_kernel_t pick_masks(int W) {
-    switch (W) {
-#define X(n) case n: return orlg_masks_kernel_W##n ? orlg_masks_kernel_W##n() : nullptr;
-        ORLG_FOR_EACH_W(X)
-#undef X
-        default: return nullptr;
-    }
-}
 
 // the step kernel with four environments per wave: first-fit policies and external (path, slot) actions
 static int launch_rmsa_group(orlg_env *e, const OrlgParams &p) {
@@ -188,16 +145,16 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p) {
     // logs the links' updates and works them off one link per lane (group_link_replay)
     const bool df = df_ok;
     int *resident = hq ? e->group_resident_hq : df ? e->group_resident_df : e->group_resident;
-    const bool traffic = p.rates != nullptr;   // per-environment rates: the instantiations that read them (+ 16)
-    const bool trace = p.tr_arrival != nullptr;   // a request trace: the instantiations that replay it (+ 32)
-    rmsa_kernel_t k = pick_group(e->W, p.stats_level + (hq ? 4 : df ? 8 : 0) + (trace ? 32 : traffic ? 16 : 0));
+    const bool trace = p.tr_arrival != nullptr;   // a request trace: the instantiations that replay it
+    const bool traffic = !trace && p.rates != nullptr;   // per-environment rates: the instantiations that read them
+    const OrlgGroupKey key = {p.stats_level, hq, df, traffic, trace};
+    rmsa_kernel_t k = orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     if (df && !e->llog) {
         int rc = orlg_handle_alloc(e, &e->llog, (size_t)p.B * p.E * ORLG_LLOG_CAP);
         if (rc) return rc;
     }
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)((size_t)p.l_shared_bytes + p.g_mt + 16 + (size_t)wpb_max * wave_bytes)));
+    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), (size_t)p.l_shared_bytes + p.g_mt + 16 + (size_t)wpb_max * wave_bytes)) return rc;
     const int n_quads = (p.B + 3) / 4;
     // Waves per workgroup: as many as the LDS holds when the batch keeps every CU busy for several rounds (more resident waves
     // per SIMD hide more latency); fewer when that would leave CUs idle or the last round mostly empty.  A round of w waves per
@@ -220,11 +177,7 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p) {
         if (v >= 1 && v <= wpb_max) wpb = v;
     }
     const size_t lds_bytes = (size_t)p.l_shared_bytes + p.g_mt + 16 + (size_t)wpb * wave_bytes;
-    if (resident[wpb] <= 0) {
-        int nb = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(k), ORLG_WAVE * wpb, lds_bytes));
-        resident[wpb] = (nb > 0 ? nb : 1) * e->num_cu;
-    }
+    if (int rc = orlg_handle_resident(e, reinterpret_cast<const void *>(k), ORLG_WAVE * wpb, lds_bytes, &resident[wpb])) return rc;
     int nblocks = (n_quads + wpb - 1) / wpb;
     if (nblocks > resident[wpb]) nblocks = resident[wpb];
     OrlgParams q = p;
@@ -275,9 +228,7 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p) {
     dim3 grid(nblocks), block(ORLG_WAVE * wpb);
     hipLaunchKernelGGL(k, grid, block, lds_bytes, e->stream, q);
     HIP_TRY(hipGetLastError());
-    snprintf(e->last_kernel, sizeof(e->last_kernel), "orlg_rmsa_group_kernel<%d,%d%s> grid=%d block=%d lds=%zu chunks=%d", e->W, p.stats_level,
-             trace ? (hq ? ",true,false,false,true" : df ? ",false,true,false,true" : ",false,false,false,true")
-                   : traffic ? (hq ? ",true,false,true" : df ? ",false,true,true" : ",false,false,true") : hq ? ",true" : df ? ",false,true" : "", nblocks, ORLG_WAVE * wpb, lds_bytes, q.n_chunks);
+    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * wpb, lds_bytes, q.n_chunks);
     return ORLG_OK;
 }
 
@@ -291,24 +242,27 @@ static bool group_kernel_serves(const orlg_env *e, const OrlgParams &p) {
     return p.B > e->resident_blocks * e->waves_per_block;
 }
 
+// the plain wave-per-environment step kernel
+static rmsa_kernel_t step_kernel(int W, int stats) { return orlg_pick(W, OrlgWaveKey{ORLG_WAVE_KERNEL(orlg_rmsa_kernel), stats, false}); }
+
 static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
     const bool ff = p.mode == ORLG_MODE_STEP && p.K <= 8 && (p.policy == ORLG_POLICY_SP || p.policy == ORLG_POLICY_SAP);
     // long launches with full statistics whose outputs do not read the link statistics step by step: the instantiation that logs the
     // links' updates and works them off one link per lane (link_replay) -- as launch_rmsa_group
     const bool df = p.mode == ORLG_MODE_STEP && p.stats_level >= 2 && p.n_steps >= 16 && !getenv("ORLG_NO_DEFER") &&
                     !(p.out_mask & ((1 << ORLG_OUT_AVG_LINK_COMPACT) | (1 << ORLG_OUT_AVG_LINK_UTIL)));
-    rmsa_kernel_t k = df ? pick_wave(e->W, ff ? ORLG_KIND_STEP_FF_DF : ORLG_KIND_STEP_DF, p.stats_level)
-                         : ff ? pick_rmsa_ff(e->W, p.stats_level) : pick_rmsa(e->W, p.stats_level, p.mode == ORLG_MODE_STEP);
+    const OrlgWaveKey key = {ff ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel_ff)
+                                : p.mode == ORLG_MODE_STEP ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel) : ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel),
+                             p.stats_level, df};
+    rmsa_kernel_t k = orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)e->lds_block_bytes));
+    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), e->lds_block_bytes)) return rc;
     const int wpb = e->waves_per_block;
     if (e->resident_blocks <= 0) {
-        int nb = 0;
-        rmsa_kernel_t ks = pick_rmsa(e->W, p.stats_level, true);  // the grid is sized for the step kernel (any grid is correct)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_block_bytes));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(ks), ORLG_WAVE * wpb, e->lds_block_bytes));
-        e->resident_blocks = (nb > 0 ? nb : 1) * e->num_cu;
+        const void *ks = reinterpret_cast<const void *>(step_kernel(e->W, p.stats_level));  // the grid is sized for the step kernel (any grid is correct)
+        int rc = orlg_kernel_lds(ks, e->lds_block_bytes);
+        if (!rc) rc = orlg_handle_resident(e, ks, ORLG_WAVE * wpb, e->lds_block_bytes, &e->resident_blocks);
+        if (rc) return rc;
     }
     if (group_kernel_serves(e, p)) return launch_rmsa_group(e, p);
     int nblocks = (p.B + wpb - 1) / wpb;
@@ -325,9 +279,7 @@ static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
     dim3 grid(nblocks), block(ORLG_WAVE * wpb);
     hipLaunchKernelGGL(k, grid, block, e->lds_block_bytes, e->stream, q);
     HIP_TRY(hipGetLastError());
-    snprintf(e->last_kernel, sizeof(e->last_kernel), "%s<%d,%d%s> grid=%d block=%d lds=%zu",
-             ff ? "orlg_rmsa_kernel_ff" : (p.mode == ORLG_MODE_STEP ? "orlg_rmsa_kernel" : "orlg_rmsa_reset_kernel"), e->W, p.stats_level,
-             df ? ",true" : "", nblocks, ORLG_WAVE * wpb, e->lds_block_bytes);
+    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * wpb, e->lds_block_bytes);
     return ORLG_OK;
 }
 
@@ -626,7 +578,7 @@ static int rmsa_create(const orlg_topology *t, const orlg_rmsa_config *c, int32_
 int orlg_launch_info(orlg_env *e, int32_t *out) {
     if (!e || !out) return fail(ORLG_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(e->device));
-    rmsa_kernel_t k = pick_rmsa(e->W, e->p.stats_level);
+    rmsa_kernel_t k = step_kernel(e->W, e->p.stats_level);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)e->lds_block_bytes));
     int nb = 0;
@@ -802,7 +754,7 @@ static int query_masks(orlg_env *e, int32_t env_index, int gid0, int count, uint
     size_t mbytes = (size_t)count * e->W * 8, nbytes = (size_t)count * 4;
     int rc = orlg_handle_staging(e, mbytes + nbytes + 64);
     if (rc) return rc;
-    masks_kernel_t k = pick_masks(e->W);
+    masks_kernel_t k = orlg_pick_masks(e->W);
     u64 *dm = reinterpret_cast<u64 *>(e->staging.bytes());
     int32_t *dn = reinterpret_cast<int32_t *>(e->staging.bytes() + ((mbytes + 15) & ~(size_t)15));
     size_t lds = (size_t)e->p.l_shared_bytes + (size_t)e->p.NW * 8;
@@ -884,7 +836,7 @@ static int deeprmsa_observation(orlg_env *e, void *out, bool f32, uint8_t *mask)
     if (rc) return rc;
     p.obs_f32 = f32 ? 1 : 0;
     p.o_obs = reinterpret_cast<double *>(slots[0].dev);
-    orlg_obs_kernel_t k = pick_obs(e->W);
+    orlg_obs_kernel_t k = orlg_pick_obs(e->W);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     const int wpb = e->waves_per_block;
     size_t lds = (size_t)p.l_shared_bytes + (size_t)(((p.NW * 8 + 15) & ~15) + ((p.obs_dim * 8 + 15) & ~15)) * wpb;
@@ -918,7 +870,7 @@ int orlg_action_masks(orlg_env *e, uint8_t *path_ff, uint64_t *slot_masks) {
     OutSlot slots[2] = {{path_ff, (size_t)p.B * ff_dim}, {slot_masks, (size_t)p.B * p.K * e->W * 8}};
     int rc = place_outputs(e, slots, 2);
     if (rc) return rc;
-    orlg_action_masks_kernel_t k = pick_action_masks(e->W);
+    orlg_action_masks_kernel_t k = orlg_pick_action_masks(e->W);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     const int wpb = e->waves_per_block;
     const size_t lds = (size_t)p.l_shared_bytes + (size_t)((p.NW * 8 + 15) & ~15) * wpb;

@@ -1,7 +1,7 @@
 // orlg_host.h -- the host side that the translation units of liborlg.so share (orlg_host.hip defines it; orlg_api.hip,
 // orlg_phy_api.hip and orlg_osnr.hip use it): errors, the handle core of both C APIs with the functions that work on it, the
-// helper kernels that differ only in the scalar record, and the declarations of the per-shape kernel instantiation units
-// (orlg_inst_*.hip, one object per word count W so that the library builds in parallel: build.py).
+// helper kernels that differ only in the scalar record, and what a launch of a step kernel does around the launch itself.  The
+// kernel instantiations, their keys and names: orlg_variants.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +16,7 @@
 
 #include "../../include/orlg.h"
 #include "orlg_device.h"
+#include "orlg_variants.h"
 
 // ---------------------------------------------------------------------------------------- errors
 // thread-local message of the last failure (orlg_last_error)
@@ -169,6 +170,18 @@ int orlg_handle_set_stream(OrlgHandle *h, void *hip_stream);
 // wait for the handle's stream, then report an overflow a kernel flagged (ORLG_ERR_QUEUE_FULL is sticky until a full reset)
 int orlg_handle_sync_check(OrlgHandle *h);
 int orlg_handle_last_kernel(const OrlgHandle *h, char *buf, int32_t cap);
+// Around a launch.  lds: let `kernel` use `bytes` of dynamic LDS.  resident: the workgroups of `kernel` (`block` threads, `lds`
+// bytes) the device holds at a time = the largest grid of a work queue, asked once and kept in *resident (0 = not asked yet).
+// launched: last_kernel = `name grid= block= lds=`, then ` chunks=` where there are any; the name is the key's (orlg_kernel_name).
+int orlg_kernel_lds(const void *kernel, size_t bytes);
+int orlg_handle_resident(OrlgHandle *h, const void *kernel, int block, size_t lds, int *resident);
+void orlg_handle_note_launch(OrlgHandle *h, const char *name, int grid, int block, size_t lds, int chunks);
+template <typename Key>
+static void orlg_handle_launched(OrlgHandle *h, const Key &key, int grid, int block, size_t lds, int chunks = 0) {
+    char name[64];
+    orlg_kernel_name(name, sizeof(name), h->W, key);
+    orlg_handle_note_launch(h, name, grid, block, lds, chunks);
+}
 // allocate `bytes` (16 when that is 0) and remember them in bufs; then copy `bytes` from host, or zero them, or neither
 int orlg_handle_alloc_bytes(OrlgHandle *h, void **out, size_t bytes, const void *host, bool zero);
 template <typename T>
@@ -307,30 +320,3 @@ static int orlg_reduce_grouped(OrlgHandle *h, const Scal *scal, int B, int64_t *
     HIP_TRY(hipMemcpyAsync(out, ts->d_grouped, bytes, hipMemcpyDefault, h->stream));
     return ORLG_OK;
 }
-
-// ---------------------------------------------------------------------------------------- kernel instantiation units
-// Every unit exports one lookup per word count W; a W the library was not built for resolves to a null (weak) symbol.
-typedef void (*orlg_rmsa_kernel_t)(const OrlgParams);
-typedef void (*orlg_masks_kernel_t)(const OrlgParams, int, int, int, uint64_t *, int32_t *);
-enum { ORLG_KIND_STEP = 0, ORLG_KIND_STEP_FF = 1, ORLG_KIND_RESET = 2, ORLG_KIND_GROUP = 4,
-       ORLG_KIND_STEP_DF = 5, ORLG_KIND_STEP_FF_DF = 6 };   // _DF: full statistics with the links' float64 part deferred (link_replay)
-#define ORLG_FOR_EACH_W(X) X(1) X(2) X(3) X(4) X(5) X(6) X(8)
-typedef void (*orlg_obs_kernel_t)(const OrlgParams, uint8_t *, int);                      // orlg_deeprmsa_obs_kernel
-typedef void (*orlg_action_masks_kernel_t)(const OrlgParams, uint8_t *, int, uint64_t *);   // orlg_action_masks_kernel
-#define ORLG_DECL_W(n)                                                                           \
-    orlg_rmsa_kernel_t orlg_wave_kernel_W##n(int kind, int stats) __attribute__((weak));          \
-    orlg_masks_kernel_t orlg_masks_kernel_W##n() __attribute__((weak));                           \
-    orlg_obs_kernel_t orlg_obs_kernel_W##n() __attribute__((weak));                               \
-    orlg_action_masks_kernel_t orlg_action_masks_kernel_W##n() __attribute__((weak));             \
-    orlg_rmsa_kernel_t orlg_group_kernel_W##n(int stats) __attribute__((weak));
-ORLG_FOR_EACH_W(ORLG_DECL_W)
-#undef ORLG_DECL_W
-
-struct OrlgPhyParams;
-typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
-#define ORLG_FOR_EACH_PHY_W(X) X(1) X(2) X(3) X(4) X(5)
-#define ORLG_DECL_PHY_W(n)                                                          \
-    orlg_phy_kernel_t orlg_phy_kernel_W##n(int variant) __attribute__((weak));      \
-    orlg_phy_kernel_t orlg_phy_trace_kernel_W##n(int variant) __attribute__((weak));   /* orlg_inst_phy_trace.hip */
-ORLG_FOR_EACH_PHY_W(ORLG_DECL_PHY_W)
-#undef ORLG_DECL_PHY_W

@@ -87,6 +87,23 @@ int orlg_handle_last_kernel(const OrlgHandle *h, char *buf, int32_t cap) {
     return ORLG_OK;
 }
 
+int orlg_kernel_lds(const void *kernel, size_t bytes) {
+    HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return ORLG_OK;
+}
+int orlg_handle_resident(OrlgHandle *h, const void *kernel, int block, size_t lds, int *resident) {
+    if (*resident > 0) return ORLG_OK;
+    int nb = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, lds));
+    *resident = (nb > 0 ? nb : 1) * h->num_cu;
+    return ORLG_OK;
+}
+void orlg_handle_note_launch(OrlgHandle *h, const char *name, int grid, int block, size_t lds, int chunks) {
+    char tail[24] = "";
+    if (chunks > 0) snprintf(tail, sizeof(tail), " chunks=%d", chunks);
+    snprintf(h->last_kernel, sizeof(h->last_kernel), "%s grid=%d block=%d lds=%zu%s", name, grid, block, lds, tail);
+}
+
 int orlg_handle_alloc_bytes(OrlgHandle *h, void **out, size_t bytes, const void *host, bool zero) {
     HIP_TRY(hipMalloc(out, bytes ? bytes : 16));
     h->bufs.push_back(*out);

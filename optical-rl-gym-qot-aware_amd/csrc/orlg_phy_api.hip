@@ -11,7 +11,7 @@
 struct orlg_phy_env : OrlgHandle {
     OrlgPhyParams p = {};
     int cont = 0;                    // bit_rate_selection="continuous": CONT instantiations, float64 shares (p.br_lower, cs_f, svc_f)
-    int resident_blocks[48] = {};    // per kernel variant (phy_launch): 0..31 discrete, 32..47 continuous
+    int resident_blocks[sizeof(ORLG_PHY_KEY_LIST) / sizeof(ORLG_PHY_KEY_LIST[0])] = {};   // per kernel instantiation (phy_launch)
     uint64_t *cont_tag = nullptr;    // (continuous handles: the 16-byte tag at the end of the saved state)
 };
 // OrlgHandle::extra: external actions from host memory (path, channels, float64 shares of continuous handles) and the float64
@@ -19,15 +19,6 @@ struct orlg_phy_env : OrlgHandle {
 enum { X_ACT_PATH, X_ACT_CH, X_ACT_SHARE, X_F64 };
 
 typedef orlg_phy_kernel_t phy_kernel_t;
-static phy_kernel_t pick_phy(int W, int variant, bool trace) {
-    switch (W) {
-#define X(n) case n: return trace ? (orlg_phy_trace_kernel_W##n ? orlg_phy_trace_kernel_W##n(variant) : nullptr) \
-                                  : (orlg_phy_kernel_W##n ? orlg_phy_kernel_W##n(variant) : nullptr);
-        ORLG_FOR_EACH_PHY_W(X)
-#undef X
-        default: return nullptr;
-    }
-}
 
 __global__ void orlg_phy_clear_kernel(OrlgPhyParams p, int W, int keep_rng) {
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
@@ -110,26 +101,20 @@ __global__ void orlg_gn_tables_kernel(const OrlgPhyParams p, double *A, double *
 }
 
 static int phy_launch(orlg_phy_env *e, const OrlgPhyParams &p) {
-    // kernel variant (orlg_inst_phy.hip): 0 the step proper, 1 + periodic defragmentation, 2 + defragmentation and GN-model
-    // admission check, 3 + GN-model admission check alone
-    const int df = p.gn_on ? (p.defrag_period > 0 ? 2 : 3) : p.defrag_period > 0 ? 1 : 0;
-    const int pol = p.mode == ORLG_MODE_STEP ? p.policy : ORLG_PHY_POLICY_EXTERNAL;   // one instantiation per policy
-    // continuous bit rates: 32 + gn + 2 * (policy + 1) (no defragmentation)
-    const int variant = e->cont ? 32 + (p.gn_on ? 1 : 0) + 2 * (pol + 1) : df + 4 * (pol + 1);
-    const bool trace = p.tr_arrival != nullptr;   // a request trace: the TRACE instantiations (same variants, their own objects)
-    phy_kernel_t k = pick_phy(e->W, variant, trace);
+    // the step proper, + periodic defragmentation, + the GN-model admission check, or both (continuous bit rates: no
+    // defragmentation); one instantiation per policy; a request trace: the TRACE instantiations (same keys, their own objects)
+    const int pol = p.mode == ORLG_MODE_STEP ? p.policy : ORLG_PHY_POLICY_EXTERNAL;
+    const OrlgPhyKey key = {!e->cont && p.defrag_period > 0, p.gn_on != 0, pol, e->cont != 0, p.tr_arrival != nullptr};
+    const int index = orlg_key_index(ORLG_PHY_KEY_LIST, key);
+    phy_kernel_t k = index < 0 ? nullptr : orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no PhyRMSA kernel for W=%d", e->W);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)e->lds_block_bytes));
+    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), e->lds_block_bytes)) return rc;
     const int wpb = e->waves_per_block;
-    // the instantiations differ in registers and scratch: the resident workgroups (= the grid of the work queue) per variant
-    if (e->resident_blocks[variant] <= 0) {
-        int nb = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(k), ORLG_WAVE * wpb, e->lds_block_bytes));
-        e->resident_blocks[variant] = (nb > 0 ? nb : 1) * e->num_cu;
-    }
+    // the instantiations differ in registers and scratch: the resident workgroups (= the grid of the work queue) per instantiation
+    int *resident = &e->resident_blocks[index];
+    if (int rc = orlg_handle_resident(e, reinterpret_cast<const void *>(k), ORLG_WAVE * wpb, e->lds_block_bytes, resident)) return rc;
     int nblocks = (p.B + wpb - 1) / wpb;
-    if (nblocks > e->resident_blocks[variant]) nblocks = e->resident_blocks[variant];
+    if (nblocks > *resident) nblocks = *resident;
     OrlgPhyParams q = p;
     // the node-degree vectors are rebuilt from the occupancy by every launch that evaluates the cut metric, and only by those
     q.use_nv = (p.use_nv && p.mode == ORLG_MODE_STEP &&
@@ -141,16 +126,7 @@ static int phy_launch(orlg_phy_env *e, const OrlgPhyParams &p) {
     dim3 grid(nblocks), block(ORLG_WAVE * wpb);
     hipLaunchKernelGGL(k, grid, block, e->lds_block_bytes, e->stream, q);
     HIP_TRY(hipGetLastError());
-    if (trace)
-        snprintf(e->last_kernel, sizeof(e->last_kernel), "orlg_phy_kernel<%d,%s,%d,%s,true> grid=%d block=%d lds=%zu", e->W,
-                 e->cont ? (p.gn_on ? "false,true" : "false,false") : df == 2 ? "true,true" : df == 1 ? "true,false" : df == 3 ? "false,true" : "false,false",
-                 pol, e->cont ? "true" : "false", nblocks, ORLG_WAVE * wpb, e->lds_block_bytes);
-    else if (e->cont)
-        snprintf(e->last_kernel, sizeof(e->last_kernel), "orlg_phy_kernel<%d,false,%s,%d,true> grid=%d block=%d lds=%zu", e->W,
-                 p.gn_on ? "true" : "false", pol, nblocks, ORLG_WAVE * wpb, e->lds_block_bytes);
-    else
-        snprintf(e->last_kernel, sizeof(e->last_kernel), "orlg_phy_kernel<%d,%s,%d> grid=%d block=%d lds=%zu", e->W,
-                 df == 2 ? "true,true" : df == 1 ? "true,false" : df == 3 ? "false,true" : "false,false", pol, nblocks, ORLG_WAVE * wpb, e->lds_block_bytes);
+    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * wpb, e->lds_block_bytes);
     return ORLG_OK;
 }
 

@@ -1,0 +1,157 @@
+// orlg_variants.h -- which instantiations of the step kernels liborlg.so holds, written once.  Per kernel family: a key (the
+// template parameters after W, under the kernels' own names), the list of the legal keys, and from them the lookups the
+// instantiation units export (orlg_inst_*.hip expand the list), the name a launch reports (last_kernel) and a dense index.
+// Plain C++: no HIP, no device code -- orlg_host.h includes it, and so can a host program that only links the library.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+
+#include "../../include/orlg.h"   // ORLG_PHY_POLICY_*
+
+// ---------------------------------------------------------------------------------------- keys
+// wave-per-environment kernels (orlg_kernels.hip): template <int W, int STATS, bool DEFER = false>; the reset kernel has no DEFER
+#define ORLG_WAVE_KERNELS(X) X(orlg_rmsa_kernel) X(orlg_rmsa_kernel_ff) X(orlg_rmsa_reset_kernel)
+#define ORLG_WAVE_KERNEL(name) ORLG_IS_##name
+enum OrlgWaveKernel {
+#define X(name) ORLG_WAVE_KERNEL(name),
+    ORLG_WAVE_KERNELS(X)
+#undef X
+};
+struct OrlgWaveKey { OrlgWaveKernel kernel; int STATS; bool DEFER; };
+// orlg_rmsa_group_kernel (orlg_group_kernels.hip)
+struct OrlgGroupKey { int STATS; bool HBMQ, DEFER, TRAFFIC, TRACE; };
+// orlg_phy_kernel (orlg_phy_kernels.hip)
+struct OrlgPhyKey { bool DF, GN; int POL; bool CONT, TRACE; };
+
+inline bool operator==(const OrlgWaveKey &a, const OrlgWaveKey &b) { return a.kernel == b.kernel && a.STATS == b.STATS && a.DEFER == b.DEFER; }
+inline bool operator==(const OrlgGroupKey &a, const OrlgGroupKey &b) {
+    return a.STATS == b.STATS && a.HBMQ == b.HBMQ && a.DEFER == b.DEFER && a.TRAFFIC == b.TRAFFIC && a.TRACE == b.TRACE;
+}
+inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
+    return a.DF == b.DF && a.GN == b.GN && a.POL == b.POL && a.CONT == b.CONT && a.TRACE == b.TRACE;
+}
+
+// ---------------------------------------------------------------------------------------- the legal keys
+// X(kernel, STATS[, DEFER]).  DEFER: full statistics with the links' float64 part deferred (link_replay); _ff: the first-fit
+// policies only (k <= 8).  (A list's order is the order of the kernels in the unit's code object: levels 1, 2, 0 as they have
+// always lain there, so that a build can be compared with its predecessor byte by byte.)
+#define ORLG_WAVE_KEYS(X)                                                                    \
+    X(orlg_rmsa_kernel, 1) X(orlg_rmsa_kernel, 2) X(orlg_rmsa_kernel, 0)                     \
+    X(orlg_rmsa_kernel_ff, 1) X(orlg_rmsa_kernel_ff, 2) X(orlg_rmsa_kernel_ff, 0)            \
+    X(orlg_rmsa_kernel, 2, true) X(orlg_rmsa_kernel_ff, 2, true)                             \
+    X(orlg_rmsa_reset_kernel, 1) X(orlg_rmsa_reset_kernel, 2) X(orlg_rmsa_reset_kernel, 0)
+
+// X(STATS, HBMQ, DEFER, TRAFFIC, TRACE).  Per kind of handle: every statistics level, the same with the release queue left in HBM
+// (launches of very few steps), and full statistics with the link updates deferred (long launches).  The kinds: plain, with
+// per-environment traffic (OrlgParams::rates), replaying a request trace (OrlgParams::tr_*)
+#define ORLG_GROUP_KEYS_OF(X, TRAFFIC, TRACE)                                                                     \
+    X(0, false, false, TRAFFIC, TRACE) X(1, false, false, TRAFFIC, TRACE) X(2, false, false, TRAFFIC, TRACE)      \
+    X(0, true, false, TRAFFIC, TRACE) X(1, true, false, TRAFFIC, TRACE) X(2, true, false, TRAFFIC, TRACE)         \
+    X(2, false, true, TRAFFIC, TRACE)
+#define ORLG_GROUP_KEYS(X) ORLG_GROUP_KEYS_OF(X, false, false) ORLG_GROUP_KEYS_OF(X, true, false) ORLG_GROUP_KEYS_OF(X, false, true)
+
+// X(DF, GN, POL, CONT, TRACE), one instantiation per policy (-1 external actions .. 6).  Discrete bit rates: the step kernel
+// proper, + periodic defragmentation, + defragmentation and the GN-model admission check, + the check alone (a handle without
+// defrag_period does not carry the defragmentation's registers).  bit_rate_selection="continuous": the step kernel proper and
+// + the check (no defragmentation: refused at create time).  TRACE: handles that replay a request trace (OrlgPhyParams::tr_*),
+// the same keys again.
+#define ORLG_PHY_KEYS_DISCRETE(X, POL, TRACE) \
+    X(false, false, POL, false, TRACE) X(true, false, POL, false, TRACE) X(true, true, POL, false, TRACE) X(false, true, POL, false, TRACE)
+#define ORLG_PHY_KEYS_CONT(X, POL, TRACE) X(false, false, POL, true, TRACE) X(false, true, POL, true, TRACE)
+#ifdef ORLG_PHY_FEW_POLICIES   // (instrumented single-unit builds of tools/: external actions and bmfa, discrete only)
+#define ORLG_PHY_KEYS_OF(X, TRACE) \
+    ORLG_PHY_KEYS_DISCRETE(X, ORLG_PHY_POLICY_EXTERNAL, TRACE) ORLG_PHY_KEYS_DISCRETE(X, ORLG_PHY_POLICY_BMFA_CUT, TRACE)
+#else
+#define ORLG_PHY_KEYS_OF(X, TRACE)                                                                                      \
+    ORLG_PHY_KEYS_DISCRETE(X, ORLG_PHY_POLICY_EXTERNAL, TRACE) ORLG_PHY_KEYS_DISCRETE(X, ORLG_PHY_POLICY_BMFA_CUT, TRACE)    \
+    ORLG_PHY_KEYS_DISCRETE(X, ORLG_PHY_POLICY_BMFA_RSS_METRIC, TRACE) ORLG_PHY_KEYS_DISCRETE(X, ORLG_PHY_POLICY_SAPFF, TRACE) \
+    ORLG_PHY_KEYS_DISCRETE(X, ORLG_PHY_POLICY_BMFF, TRACE) ORLG_PHY_KEYS_DISCRETE(X, ORLG_PHY_POLICY_SAPBM, TRACE)           \
+    ORLG_PHY_KEYS_DISCRETE(X, ORLG_PHY_POLICY_FAFF, TRACE) ORLG_PHY_KEYS_DISCRETE(X, ORLG_PHY_POLICY_FAFF_RSS, TRACE)        \
+    ORLG_PHY_KEYS_CONT(X, ORLG_PHY_POLICY_EXTERNAL, TRACE) ORLG_PHY_KEYS_CONT(X, ORLG_PHY_POLICY_BMFA_CUT, TRACE)            \
+    ORLG_PHY_KEYS_CONT(X, ORLG_PHY_POLICY_BMFA_RSS_METRIC, TRACE) ORLG_PHY_KEYS_CONT(X, ORLG_PHY_POLICY_SAPFF, TRACE)        \
+    ORLG_PHY_KEYS_CONT(X, ORLG_PHY_POLICY_BMFF, TRACE) ORLG_PHY_KEYS_CONT(X, ORLG_PHY_POLICY_SAPBM, TRACE)                   \
+    ORLG_PHY_KEYS_CONT(X, ORLG_PHY_POLICY_FAFF, TRACE) ORLG_PHY_KEYS_CONT(X, ORLG_PHY_POLICY_FAFF_RSS, TRACE)
+#endif
+#define ORLG_PHY_KEYS(X) ORLG_PHY_KEYS_OF(X, false) ORLG_PHY_KEYS_OF(X, true)
+
+// the lists as arrays; a key's position is its dense index (orlg_phy_env::resident_blocks), -1 for a key that is not legal
+#define ORLG_WAVE_KEY_ENTRY(name, ...) OrlgWaveKey{ORLG_WAVE_KERNEL(name), __VA_ARGS__},
+#define ORLG_GROUP_KEY_ENTRY(...) OrlgGroupKey{__VA_ARGS__},
+#define ORLG_PHY_KEY_ENTRY(...) OrlgPhyKey{__VA_ARGS__},
+inline constexpr OrlgWaveKey ORLG_WAVE_KEY_LIST[] = {ORLG_WAVE_KEYS(ORLG_WAVE_KEY_ENTRY)};
+inline constexpr OrlgGroupKey ORLG_GROUP_KEY_LIST[] = {ORLG_GROUP_KEYS(ORLG_GROUP_KEY_ENTRY)};
+inline constexpr OrlgPhyKey ORLG_PHY_KEY_LIST[] = {ORLG_PHY_KEYS(ORLG_PHY_KEY_ENTRY)};
+template <typename Key, size_t N>
+static int orlg_key_index(const Key (&list)[N], const Key &key) {
+    for (size_t i = 0; i < N; i++)
+        if (list[i] == key) return (int)i;
+    return -1;
+}
+
+// ---------------------------------------------------------------------------------------- names
+// "kernel<W,arg,...>" as the compiler names the instantiation, spaces left out; trailing arguments that equal their default are
+// dropped.  kind: 'i' an int, 'b' a bool, 'd' a bool whose default is false.
+struct OrlgArg { int value; char kind; };
+inline void orlg_format_kernel(char *buf, size_t cap, const char *kernel, int W, const OrlgArg *args, int n) {
+    while (n > 0 && args[n - 1].kind == 'd' && !args[n - 1].value) --n;
+    size_t at = (size_t)snprintf(buf, cap, "%s<%d", kernel, W);
+    for (int i = 0; i < n && at < cap; i++)
+        at += (size_t)(args[i].kind == 'i' ? snprintf(buf + at, cap - at, ",%d", args[i].value)
+                                           : snprintf(buf + at, cap - at, ",%s", args[i].value ? "true" : "false"));
+    if (at < cap) snprintf(buf + at, cap - at, ">");
+}
+inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgWaveKey &k) {
+#define X(name) #name,
+    static const char *const names[] = {ORLG_WAVE_KERNELS(X)};
+#undef X
+    const OrlgArg args[] = {{k.STATS, 'i'}, {k.DEFER, 'd'}};
+    orlg_format_kernel(buf, cap, names[k.kernel], W, args, k.kernel == ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel) ? 1 : 2);
+}
+inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgGroupKey &k) {
+    const OrlgArg args[] = {{k.STATS, 'i'}, {k.HBMQ, 'd'}, {k.DEFER, 'd'}, {k.TRAFFIC, 'd'}, {k.TRACE, 'd'}};
+    orlg_format_kernel(buf, cap, "orlg_rmsa_group_kernel", W, args, 5);
+}
+inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgPhyKey &k) {
+    const OrlgArg args[] = {{k.DF, 'b'}, {k.GN, 'b'}, {k.POL, 'i'}, {k.CONT, 'd'}, {k.TRACE, 'd'}};
+    orlg_format_kernel(buf, cap, "orlg_phy_kernel", W, args, 5);
+}
+
+// ---------------------------------------------------------------------------------------- kernel instantiation units
+// Every unit (orlg_inst_*.hip, one object per word count W so that the library builds in parallel: build.py) exports one lookup
+// per W: key -> instantiation, null for a key that is not legal.  A W the library was not built for is a null (weak) symbol.
+struct OrlgParams;
+struct OrlgPhyParams;
+typedef void (*orlg_rmsa_kernel_t)(const OrlgParams);
+typedef void (*orlg_masks_kernel_t)(const OrlgParams, int, int, int, uint64_t *, int32_t *);   // orlg_path_masks_kernel
+typedef void (*orlg_obs_kernel_t)(const OrlgParams, uint8_t *, int);                          // orlg_deeprmsa_obs_kernel
+typedef void (*orlg_action_masks_kernel_t)(const OrlgParams, uint8_t *, int, uint64_t *);     // orlg_action_masks_kernel
+typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
+#define ORLG_FOR_EACH_W(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__) X(6, __VA_ARGS__) X(8, __VA_ARGS__)
+#define ORLG_FOR_EACH_PHY_W(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__)
+#define ORLG_DECL_W(n, ...)                                                                       \
+    orlg_rmsa_kernel_t orlg_wave_kernel_W##n(OrlgWaveKey) __attribute__((weak));                  \
+    orlg_masks_kernel_t orlg_masks_kernel_W##n() __attribute__((weak));                           \
+    orlg_obs_kernel_t orlg_obs_kernel_W##n() __attribute__((weak));                               \
+    orlg_action_masks_kernel_t orlg_action_masks_kernel_W##n() __attribute__((weak));             \
+    orlg_rmsa_kernel_t orlg_group_kernel_W##n(OrlgGroupKey) __attribute__((weak));
+#define ORLG_DECL_PHY_W(n, ...)                                                                   \
+    orlg_phy_kernel_t orlg_phy_kernel_W##n(OrlgPhyKey) __attribute__((weak));                     \
+    orlg_phy_kernel_t orlg_phy_trace_kernel_W##n(OrlgPhyKey) __attribute__((weak));   /* orlg_inst_phy.hip with -DORLG_INST_TRACE=1 */
+ORLG_FOR_EACH_W(ORLG_DECL_W, )
+ORLG_FOR_EACH_PHY_W(ORLG_DECL_PHY_W, )
+#undef ORLG_DECL_W
+#undef ORLG_DECL_PHY_W
+
+// the lookup `lookup`<W> called with the arguments after it, as a function body: null when the library holds no such W
+#define ORLG_PICK_CASE(n, lookup, ...) case n: return lookup##n ? lookup##n(__VA_ARGS__) : nullptr;
+#define ORLG_PICK(FOR_EACH_W, W, lookup, ...) switch (W) { FOR_EACH_W(ORLG_PICK_CASE, lookup, __VA_ARGS__) default: return nullptr; }
+static orlg_rmsa_kernel_t orlg_pick(int W, const OrlgWaveKey &key) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_wave_kernel_W, key) }
+static orlg_rmsa_kernel_t orlg_pick(int W, const OrlgGroupKey &key) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_group_kernel_W, key) }
+static orlg_phy_kernel_t orlg_pick(int W, const OrlgPhyKey &key) {   // the TRACE instantiations are objects of their own
+    if (key.TRACE) { ORLG_PICK(ORLG_FOR_EACH_PHY_W, W, orlg_phy_trace_kernel_W, key) }
+    ORLG_PICK(ORLG_FOR_EACH_PHY_W, W, orlg_phy_kernel_W, key)
+}
+static orlg_masks_kernel_t orlg_pick_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_masks_kernel_W, ) }
+static orlg_obs_kernel_t orlg_pick_obs(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_obs_kernel_W, ) }
+static orlg_action_masks_kernel_t orlg_pick_action_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_action_masks_kernel_W, ) }
