@@ -2,7 +2,7 @@
 // Its own translation unit; the step kernel is instantiated per word count in orlg_inst_phy.hip.  What it has in common with the
 // RMSA API (orlg_api.hip) is the handle core of orlg_host.h.
 #include "orlg_host.h"
-#include "orlg_phy_kernels.hip"   // data layout + device helpers
+#include "orlg_phy_layout.h"
 
 // the last 16 bytes of a continuous handle's saved state ("orlg phy", "cont f64"): a snapshot of the other bit-rate mode is refused
 #define ORLG_PHY_CONT_TAG0 0x796870206772726full
