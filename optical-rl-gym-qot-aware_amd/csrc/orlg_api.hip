@@ -184,6 +184,10 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p) {
     q.llog = df ? e->llog : nullptr;
     if (df) { q.g_lint = e->group_df_lint; q.g_qtime = e->group_df_qtime; q.g_qdesc = e->group_df_qdesc; q.g_lstat = e->group_df_lsum; }
     q.g_wave_bytes = wave_bytes;
+    // the lean body of the DEFER instantiations (orlg_rmsa_group_body): first fit over the first path or all of them, no per-step
+    // output at all, discrete bit rates -- what a heuristic's evaluation or a load sweep launches
+    q.g_lean = df && (p.policy == ORLG_POLICY_SP || p.policy == ORLG_POLICY_SAP) && p.out_mask == 0 && p.br_width == 0 &&
+               !getenv("ORLG_NO_LEAN");
     q.ticket_base = e->ticket_base;
     q.ticket_stride = p.n_steps <= 16 ? 1u : 0u;
     // Tickets in chunks of steps (orlg_rmsa_group_kernel, work queue): when the batch is not a multiple of the resident waves, a
@@ -228,7 +232,7 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p) {
     dim3 grid(nblocks), block(ORLG_WAVE * wpb);
     hipLaunchKernelGGL(k, grid, block, lds_bytes, e->stream, q);
     HIP_TRY(hipGetLastError());
-    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * wpb, lds_bytes, q.n_chunks);
+    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * wpb, lds_bytes, q.n_chunks, q.g_lean ? "lean" : "full");
     return ORLG_OK;
 }
 

@@ -156,7 +156,7 @@ struct OrlgHandle {
     OrlgScratch extra[ORLG_EXTRA_SLOTS];
     OrlgErrWord err = {nullptr, nullptr};   // sticky error word the kernels set on an overflow
     std::string overflow_message;    // what orlg_handle_sync_check reports then (the variant words it, with its capacities)
-    char last_kernel[96] = "";       // name and shape of the kernel behind the last step / reset launch
+    char last_kernel[128] = "";       // name and shape of the kernel behind the last step / reset launch
     OrlgTrafficState traffic;        // per-environment rates and groups (*_create_traffic)
     OrlgTraceState trace;            // request trace and its position (*_create_trace)
     OrlgHandle() = default;
@@ -172,15 +172,17 @@ int orlg_handle_sync_check(OrlgHandle *h);
 int orlg_handle_last_kernel(const OrlgHandle *h, char *buf, int32_t cap);
 // Around a launch.  lds: let `kernel` use `bytes` of dynamic LDS.  resident: the workgroups of `kernel` (`block` threads, `lds`
 // bytes) the device holds at a time = the largest grid of a work queue, asked once and kept in *resident (0 = not asked yet).
-// launched: last_kernel = `name grid= block= lds=`, then ` chunks=` where there are any; the name is the key's (orlg_kernel_name).
+// launched: last_kernel = `name grid= block= lds=`, then ` body=lean` or ` body=full` for the four-environments-per-wave kernel
+// (orlg_rmsa_group_body) and last ` chunks=` where there are any (callers read the end of the string for it); the name is the
+// key's (orlg_kernel_name).
 int orlg_kernel_lds(const void *kernel, size_t bytes);
 int orlg_handle_resident(OrlgHandle *h, const void *kernel, int block, size_t lds, int *resident);
-void orlg_handle_note_launch(OrlgHandle *h, const char *name, int grid, int block, size_t lds, int chunks);
+void orlg_handle_note_launch(OrlgHandle *h, const char *name, int grid, int block, size_t lds, int chunks, const char *body);
 template <typename Key>
-static void orlg_handle_launched(OrlgHandle *h, const Key &key, int grid, int block, size_t lds, int chunks = 0) {
+static void orlg_handle_launched(OrlgHandle *h, const Key &key, int grid, int block, size_t lds, int chunks = 0, const char *body = nullptr) {
     char name[64];
     orlg_kernel_name(name, sizeof(name), h->W, key);
-    orlg_handle_note_launch(h, name, grid, block, lds, chunks);
+    orlg_handle_note_launch(h, name, grid, block, lds, chunks, body);
 }
 // allocate `bytes` (16 when that is 0) and remember them in bufs; then copy `bytes` from host, or zero them, or neither
 int orlg_handle_alloc_bytes(OrlgHandle *h, void **out, size_t bytes, const void *host, bool zero);

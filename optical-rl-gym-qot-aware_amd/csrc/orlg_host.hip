@@ -98,10 +98,11 @@ int orlg_handle_resident(OrlgHandle *h, const void *kernel, int block, size_t ld
     *resident = (nb > 0 ? nb : 1) * h->num_cu;
     return ORLG_OK;
 }
-void orlg_handle_note_launch(OrlgHandle *h, const char *name, int grid, int block, size_t lds, int chunks) {
-    char tail[24] = "";
+void orlg_handle_note_launch(OrlgHandle *h, const char *name, int grid, int block, size_t lds, int chunks, const char *body) {
+    char tail[24] = "", btail[16] = "";
     if (chunks > 0) snprintf(tail, sizeof(tail), " chunks=%d", chunks);
-    snprintf(h->last_kernel, sizeof(h->last_kernel), "%s grid=%d block=%d lds=%zu%s", name, grid, block, lds, tail);
+    if (body) snprintf(btail, sizeof(btail), " body=%s", body);
+    snprintf(h->last_kernel, sizeof(h->last_kernel), "%s grid=%d block=%d lds=%zu%s%s", name, grid, block, lds, btail, tail);
 }
 
 int orlg_handle_alloc_bytes(OrlgHandle *h, void **out, size_t bytes, const void *host, bool zero) {
