@@ -1,9 +1,9 @@
 // orlg_api.hip -- host side of liborlg.so: the C ABI declared in include/orlg.h.
-// Owns the device state of B environments, builds the read-only tables and launches the kernels of orlg_kernels.hip; what it has
+// Owns the device state of B environments, builds the read-only tables and launches the kernels of orlg_kernels.hip, orlg_group_kernels.hip, orlg_query_kernels.hip and orlg_mask_kernels.hip; what it has
 // in common with the QoT-aware API is the handle core of orlg_host.h.  No CPU compute path exists: every entry point that touches
 // environments needs a HIP device.
 #include "orlg_host.h"
-#include "orlg_kernels.hip"   // data layout + device helpers; the step kernels are instantiated in orlg_inst_*.hip
+#include "orlg_wave.h"   // valid_mask, ORLG_INF_BITS for the helper kernels; the step kernels are instantiated in orlg_inst_*.hip
 
 // ---------------------------------------------------------------------------------------- handle
 struct orlg_env : OrlgHandle {
@@ -984,6 +984,7 @@ extern "C" int orlg_debug_layout(const orlg_env *e, int32_t *out, int n) {
     return i;
 }
 #ifdef ORLG_SECTIONS
+#include "orlg_sections.h"   // orlg_sections[]
 extern "C" int orlg_debug_sections(unsigned long long *out, int reset) {
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(orlg_sections), 16 * 8));

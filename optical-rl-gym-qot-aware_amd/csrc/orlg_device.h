@@ -1,6 +1,7 @@
-// orlg_device.h -- device-side data layout shared by the kernels (orlg_kernels.hip) and the host API
-// (orlg_api.hip).  Names follow the reference's domain: links, slots, paths, services, release queue.
+// orlg_device.h -- device-side data layout shared by the kernels (through orlg_wave.h) and the host API
+// (orlg_host.h, orlg_api.hip).  Names follow the reference's domain: links, slots, paths, services, release queue.
 #pragma once
+#include <hip/hip_vector_types.h>   // uint4
 #include <stdint.h>
 
 #define ORLG_WAVE 64
@@ -16,6 +17,7 @@
 #define ORLG_GROUP_WAVES 12    // four-environments-per-wave kernel: waves per workgroup at most (LDS decides how many fit): up to 3 per SIMD
 #endif
 #define ORLG_DIRECT_STEPS 4    // launches of at most this many steps read their ring entries straight from HBM
+#define ORLG_LLOG_CAP 64      // logged updates per (environment, link) between two replays (6-bit count): sizes OrlgParams::llog
 
 // One k-shortest-path record (16 B): Path.hops, Path.best_modulation.spectral_efficiency and the link
 // "index" of every hop (utils.py:27-36, rmsa_env.py:479-483).

@@ -12,7 +12,7 @@
 // The rows diverge (accepted / blocked, number of releases, hops): every loop runs to the longest row and predicates the others.
 // Reductions stay inside a row (full-mask DPP: quad_perm, row_half_mirror, row_mirror, row_shl), row-level votes come from
 // one ballot shifted to the row's 16 bits.  The state format in HBM is the wave-per-environment kernel's: either kernel
-// can continue a batch the other one stepped, and the reset kernel is shared.  The MT19937 state and the ring of pre-generated
+// can continue a batch the other one stepped, and the reset kernel is shared (the host looks it up; this file does not include it).  The MT19937 state and the ring of pre-generated
 // arrivals stay in HBM: a row reads its next arrival one step ahead, and a refill (every ~62 steps per environment) is done
 // by the whole wave for one environment at a time through the workgroup's LDS staging buffer (refill_requests, orlg_requests.h).
 // The wave's LDS region is array-major (four occupancy bitmaps, then four link-statistics blocks, ...: OrlgParams::g_occ ...),
@@ -21,8 +21,9 @@
 // Policies: the first-fit family (shortest path / shortest available path, path-only agent actions), the DeepRMSA block family
 // (its two heuristics and the agent's (path, block) action), load balancing (llp_ff) and external (path, slot) actions.  Reference: the same lines of rmsa_env.py as orlg_kernels.hip cites.
 #pragma once
-#include "orlg_kernels.hip"
+#include "orlg_link_stats.h"   // and through it orlg_wave.h, orlg_rmsa_layout.h, orlg_spectrum.h
 #include "orlg_requests.h"
+#include "orlg_sections.h"
 
 #define ORLG_GL 16  // lanes per environment (one DPP row)
 #define ORLG_GE 4   // environments per wave
@@ -61,7 +62,7 @@ ORLG_SEG_REDUCE(seg_add, ORLG_OP_ADD)
 ORLG_SEG_REDUCE(seg_max, ORLG_OP_MAX)
 #undef ORLG_SEG_REDUCE
 
-// path_word_rec (orlg_kernels.hip) with the hop words FOUR TO A WAIT: the record's link bytes are all in registers, so the reads of
+// path_word_rec (orlg_spectrum.h) with the hop words FOUR TO A WAIT: the record's link bytes are all in registers, so the reads of
 // a group of four hops are issued back to back and ANDed in after one round trip, where the other form waits for every hop's
 // word before it votes on the next (three waves per SIMD do not hide that chain here; the wave kernel, at four, keeps its own
 // form).  A hop past the path's end reads the word of the path's first link -- a valid address on every lane, link 0 on an
@@ -103,7 +104,7 @@ DEV u64 lsum_pack(int freec, int F, int U, int lmin, int lmax, int ml, bool ff, 
            ((u64)((uint32_t)(lmin & 0x3ff) | ((uint32_t)lmax << 10) | ((uint32_t)ml << 20) | ((uint32_t)ff << 30) | ((uint32_t)lf << 31)) << 32);
 }
 
-// link statistics of up to ORLG_MAX_HOPS links per row: link_stats_update (orlg_kernels.hip) with 16 / W links per row and
+// link statistics of up to ORLG_MAX_HOPS links per row: link_stats_update (orlg_link_stats.h) with 16 / W links per row and
 // pass, one word per lane; nlinks = 0 for a row that does not take part.  links: the row's link indices (bytes, LDS).
 // DEFER: the float64 part of _update_link_stats is not done here.  It is a recurrence PER LINK -- the time-weighted means of
 // utilization, external fragmentation and compactness since the link's last update -- of ~100 instructions that every lane of

@@ -1,7 +1,9 @@
-// orlg_inst_wave.hip -- instantiations of the wave-per-environment kernels (orlg_kernels.hip) for ONE word count,
+// orlg_inst_wave.hip -- instantiations of the wave-per-environment kernels (orlg_kernels.hip, and the query and mask kernels of
+// orlg_query_kernels.hip and orlg_mask_kernels.hip, in the order the file always met them) for ONE word count,
 // -DORLG_INST_W=<W>: one object per W, so that the library builds in parallel (build.py).  Which ones: orlg_variants.h.
 #include "orlg_host.h"
 #include "orlg_kernels.hip"
+#include "orlg_query_kernels.hip"
 #include "orlg_mask_kernels.hip"
 
 #ifndef ORLG_INST_W

@@ -10,7 +10,8 @@
 // the grid sized to the device and striding over the batch, the occupancy row copied to LDS.  It reads state and writes only
 // the caller's buffers.  (The DeepRMSA mask leaves orlg_deeprmsa_obs_kernel itself: the block scan is the observation's.)
 #pragma once
-#include "orlg_kernels.hip"
+#include "orlg_rmsa_layout.h"
+#include "orlg_spectrum.h"
 
 // Eight candidate paths per pass: path p0 + g on the 8-lane group g (two groups per DPP row), one word per lane -- the layout
 // run_starts needs (a path's words on consecutive lanes of one row).  path_ff: [B][ff_dim] bytes, ff_dim = K (+ 1: the explicit

@@ -8,7 +8,7 @@
 // moves the result by a few 1e-16 relative (north_star tolerance: 1e-6 relative).  PARITY UNPINNED by the reference
 // (no caller, no test, not importable: SURVEY 0.3 / 8c); checked against tests/golden/osnr_grid.npz and the oracle.
 #include "orlg_host.h"
-#include "orlg_kernels.hip"
+#include "orlg_wave.h"
 
 struct OrlgOsnrDev {
     int32_t num_checks;

@@ -6,6 +6,8 @@
 #pragma once
 #include "orlg_phy_metrics.h"
 #include "orlg_phy_virtual.h"
+#include "orlg_sections.h"
+#include "orlg_spectrum.h"   // path_word
 
 // channel_state list of a running service: (source, destination, k-path) key from its path record and direction flag
 DEV int svc_key(const PhyTab &tb, int N, int K, int gid, int flags) {

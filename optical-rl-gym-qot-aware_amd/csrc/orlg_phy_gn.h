@@ -3,6 +3,7 @@
 // phy_rmsa_env.py: the gate is this project's.  Its tables are built by orlg_gn_tables_kernel (orlg_phy_api.hip).
 #pragma once
 #include "orlg_phy_layout.h"
+#include "orlg_sections.h"
 
 // GN-model GSNR [dB] of channel `ch` on the path `rec` against the live occupancy (include/orlg.h orlg_gn_gate): the
 // arithmetic of examples/calculate_osnr.py:9-56 for a service that is not yet in the links' lists.  Wave-cooperative, result

@@ -16,8 +16,12 @@
 // capacity = level x 100 Gb/s) read from HBM in [row][k-path][channel] order (coalesced over channels).
 // Lanes are channels: lane l of word w owns channel 64w + l.
 #pragma once
+#include "../../include/orlg.h"   // ORLG_PHY_POLICY_*
 #include "orlg_phy_defrag.h"
 #include "orlg_phy_gn.h"
+#include "orlg_requests.h"   // the ring's producers, orlg_env_rates
+#include "orlg_sections.h"
+#include "orlg_spectrum.h"   // path_word
 
 // The step's sections (SEC(n) below) are written out in the kernel.  The forms tried as functions were compared with the parent's
 // code (profiles/README.md, round 9): none gave the parent's instructions in every instantiation, and each piece says so where

@@ -7,7 +7,7 @@
 // per-step outputs (ORLG_PHY_OUT_*); the packers of a channel_state tuple (cs_*: phy_rmsa_env.py:600-602, 640-644) and of a
 // record's head (svc_summary / sum_*); the tables staged into LDS (PhyTab / make_phy_tab).
 #pragma once
-#include "orlg_kernels.hip"
+#include "orlg_wave.h"
 
 #define ORLG_PHY_MAX_CH 14
 #define ORLG_PHY_MAX_K 5

@@ -6,6 +6,7 @@
 // next step's release looked up ahead (ReleaseAhead); a new service's record and its side arrays (rec_store, svc_side_store).
 #pragma once
 #include "orlg_phy_layout.h"
+#include "orlg_requests.h"   // orlg_env_rates
 
 // ---- channel_state lists (virtual layer): one list = up to cs_len packed entries, entry i on lane i
 struct CsList { uint32_t e; int n, cap; };

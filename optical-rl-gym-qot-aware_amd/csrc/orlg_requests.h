@@ -14,11 +14,9 @@
 // of the 147 orlg_rmsa_group_kernel ones (6 up, 1 down; the worst, <3,2,false,false,true>: spilled VGPRs 47 -> 49).  The headline's
 // orlg_rmsa_group_kernel<5,2,false,true> kept 168 VGPRs, 352 B scratch and 94 spilled VGPRs either way.
 //
-// Included by orlg_kernels.hip below its wave helpers and its fp64 division, which this file uses (DEV, wave_sync, recip_refine,
-// div_by).
+// orlg_env_rates: the arrival process of one environment of a handle with per-environment traffic.
 #pragma once
-#include "orlg_device.h"
-#include "orlg_math.h"
+#include "orlg_wave.h"   // DEV, wave_sync, recip_refine, div_by
 
 // The producers are out of line, so their pointers carry their address space in the signature: through generic pointers every
 // access of the MT19937 state and the tables in LDS was a flat instruction.
@@ -70,6 +68,19 @@ DEV void request_times(double u0, double u1, double lam_arrival, double lam_hold
 // more than without it differed from the parent's, among them 10 of the wave units' (7 with more scratch or spills, 3 with less;
 // orlg_rmsa_kernel_ff<2,2,false>: scratch 144 -> 176 B per lane, orlg_rmsa_reset_kernel<4,0>: 32 -> 48 B, spilled VGPRs 7 -> 9).)
 
+// ---------------------------------------------------------------------------------------- per-environment traffic
+// (arrival_lambda, holding_lambda) of environment `env` (wave-uniform) of a handle with per-environment traffic; a handle without
+// (rates == nullptr) keeps the two scalars the caller passes in.  The table is written before the handle's first launch and never
+// after, so it is read through the constant address space: the pair arrives by the scalar cache in four SGPRs at the place that
+// uses it -- no vector register, nothing kept across the step
+DEV void orlg_env_rates(const OrlgRates *rates, int env, double &arrival_lambda, double &holding_lambda) {
+    if (rates) {
+        typedef const OrlgRates __attribute__((address_space(4))) *ConstRates;
+        ConstRates r = (ConstRates)(uintptr_t)rates + __builtin_amdgcn_readfirstlane(env);
+        arrival_lambda = r->arrival_lambda;
+        holding_lambda = r->holding_lambda;
+    }
+}
 // ---------------------------------------------------------------------------------------- the ring
 // Lane j's entry into slot j of the ring's three rows.  RING_LDS: the ring lives in LDS (wave-per-environment kernel) or in HBM
 // (the other two).  A refill of n requests passes zeros in the lanes past n: those entries are dead, and a snapshot of the state
