@@ -3,24 +3,20 @@
 // in common with the QoT-aware API is the handle core of orlg_host.h.  No CPU compute path exists: every entry point that touches
 // environments needs a HIP device.
 #include "orlg_host.h"
+#include "orlg_group_plan.h"
 #include "orlg_wave.h"   // valid_mask, ORLG_INF_BITS for the helper kernels; the step kernels are instantiated in orlg_inst_*.hip
 
 // ---------------------------------------------------------------------------------------- handle
 struct orlg_env : OrlgHandle {
     OrlgParams p = {};
     int resident_blocks = 0;   // workgroups of the step kernel the device keeps resident (grid size of the work queue)
-    // four-environments-per-wave step kernel: workgroup shape, LDS bytes, resident workgroups; group_mode = ORLG_KERNEL_*
-    // (AUTO falls back to WAVE when the shape does not fit the kernel's LDS budget)
-    int group_mode = 0, group_wpb = 0;   // group_wpb: the most waves per workgroup the LDS holds
-    int group_resident[ORLG_GROUP_WAVES + 1] = {};   // resident workgroups by waves per workgroup (0 = not asked yet)
-    int group_wpb_hq = 0, group_wave_bytes_hq = 0;   // the same for launches that leave the release queue in HBM (orlg_rmsa_group_kernel<.., true>)
-    int group_resident_hq[ORLG_GROUP_WAVES + 1] = {};
-    int group_resident_df[ORLG_GROUP_WAVES + 1] = {};   // ... of the instantiation with the link statistics deferred
-    int group_df_lint = 0, group_df_qtime = 0, group_df_qdesc = 0, group_df_wave_bytes = 0, group_df_wpb = 0;   // its LDS layout (no link-statistics slices)
-    int group_df_lsum = 0;   // ... whose place the links' summaries take (8 bytes per link, group_release_links)
-    uint4 *llog = nullptr;          // its log of link updates [B][E][ORLG_LLOG_CAP] (allocated with the first such launch)
+    // four-environments-per-wave step kernel: group_mode = ORLG_KERNEL_* (AUTO falls back to WAVE when the shape does not fit the
+    // kernel's LDS budget); the LDS layout of each kind of instantiation (orlg_group_plan.h) and its resident workgroups
+    int group_mode = 0;
+    OrlgGroupLayout group[3] = {};                          // by OrlgGroupKind
+    int group_resident[3][ORLG_GROUP_WAVES + 1] = {};       // ... by waves per workgroup (0 = not asked yet)
+    uint4 *llog = nullptr;          // DEFER: the log of link updates [B][E][ORLG_LLOG_CAP] (allocated with the first such launch)
     uint32_t *progress = nullptr;   // chunked tickets: chunks completed per quad in the current launch (allocated with the first such launch)
-    size_t group_lds_bytes = 0;
     int allow_rejection = 0;   // the action spaces carry the explicit rejection (orlg_set_allow_rejection): one more mask column
 };
 enum { X_ACTIONS };   // OrlgHandle::extra: external actions from pageable host memory
@@ -132,107 +128,45 @@ __global__ void orlg_overflow_kernel(const OrlgEnvScalars *scal, int B, int *out
 typedef orlg_rmsa_kernel_t rmsa_kernel_t;
 typedef orlg_masks_kernel_t masks_kernel_t;
 
-// the step kernel with four environments per wave: first-fit policies and external (path, slot) actions
-static int launch_rmsa_group(orlg_env *e, const OrlgParams &p) {
-    // launches of very few steps leave the release queue in HBM (the kernel's HBMQ instantiation): without the queue's slices an
-    // environment takes half the LDS, and such a launch is bound by the waves a CU keeps resident
-    const bool hq = p.n_steps <= ORLG_DIRECT_STEPS && e->group_wpb_hq > e->group_wpb;
-    const bool df_ok = !hq && p.stats_level >= 2 && p.n_steps >= 16 && !getenv("ORLG_NO_DEFER") && e->group_df_wpb >= 1 &&
-                       !(p.out_mask & ((1 << ORLG_OUT_AVG_LINK_COMPACT) | (1 << ORLG_OUT_AVG_LINK_UTIL)));
-    const int wave_bytes = hq ? e->group_wave_bytes_hq : df_ok ? e->group_df_wave_bytes : p.g_wave_bytes;
-    const int wpb_max = hq ? e->group_wpb_hq : df_ok ? e->group_df_wpb : e->group_wpb;
-    // long launches with full statistics whose outputs do not read the link statistics step by step: the instantiation that
-    // logs the links' updates and works them off one link per lane (group_link_replay)
-    const bool df = df_ok;
-    int *resident = hq ? e->group_resident_hq : df ? e->group_resident_df : e->group_resident;
+// the tooling environment of a launch
+static OrlgGroupOverrides group_overrides() {
+    const char *wpb = getenv("ORLG_GROUP_WPB"), *chunks = getenv("ORLG_GROUP_CHUNKS");
+    return {getenv("ORLG_NO_DEFER") != nullptr, getenv("ORLG_NO_CHUNKS") != nullptr, getenv("ORLG_NO_LEAN") != nullptr,
+            wpb ? atoi(wpb) : 0, chunks ? atoi(chunks) : 0};
+}
+
+// the step kernel with four environments per wave: first-fit policies and external (path, slot) actions.  What is launched is
+// decided in orlg_group_plan.h; here it is done
+static int launch_rmsa_group(orlg_env *e, const OrlgParams &p, const OrlgGroupOverrides &ov) {
+    const OrlgGroupChoice c = orlg_group_choose(e->group, {p.B, p.n_steps, p.stats_level, p.policy, p.out_mask, p.br_width}, ov, e->num_cu);
+    const OrlgGroupLayout &l = e->group[c.kind];
+    const bool df = c.kind == ORLG_GROUP_DEFER;
     const bool trace = p.tr_arrival != nullptr;   // a request trace: the instantiations that replay it
     const bool traffic = !trace && p.rates != nullptr;   // per-environment rates: the instantiations that read them
-    const OrlgGroupKey key = {p.stats_level, hq, df, traffic, trace};
+    const OrlgGroupKey key = {p.stats_level, c.kind == ORLG_GROUP_HBMQ, df, traffic, trace};
     rmsa_kernel_t k = orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    if (df && !e->llog) {
-        int rc = orlg_handle_alloc(e, &e->llog, (size_t)p.B * p.E * ORLG_LLOG_CAP);
-        if (rc) return rc;
+    if (df && !e->llog)
+        if (int rc = orlg_handle_alloc(e, &e->llog, (size_t)p.B * p.E * ORLG_LLOG_CAP)) return rc;
+    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), orlg_group_lds(l.shared_bytes, l.wpb_max, l.wave_bytes))) return rc;
+    int *resident = &e->group_resident[c.kind][c.wpb];
+    if (int rc = orlg_handle_resident(e, reinterpret_cast<const void *>(k), ORLG_WAVE * c.wpb, c.lds_bytes, resident)) return rc;
+    const OrlgGroupTickets t = orlg_group_tickets(c, p.B, p.n_steps, *resident, ov);
+    if (t.n_chunks > 1) {
+        if (!e->progress)
+            if (int rc = orlg_handle_alloc(e, &e->progress, (size_t)p.B / 4 + 1)) return rc;
+        HIP_TRY(hipMemsetAsync(e->progress, 0, (size_t)t.n_quads * sizeof(uint32_t), e->stream));
     }
-    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), (size_t)p.l_shared_bytes + p.g_mt + 16 + (size_t)wpb_max * wave_bytes)) return rc;
-    const int n_quads = (p.B + 3) / 4;
-    // Waves per workgroup: as many as the LDS holds when the batch keeps every CU busy for several rounds (more resident waves
-    // per SIMD hide more latency); fewer when that would leave CUs idle or the last round mostly empty.  A round of w waves per
-    // CU costs about w + 1.5 (measured: 10 waves per CU step 3 % more environments per second than 8); few rounds count whole.
-    int wpb = wpb_max;
-    // (long launches of batches beyond one round of the full workgroup keep it: their rounds are evened out by tickets in chunks
-    // of steps, below -- the model here would trade resident waves for whole rounds)
-    const bool long_rounds = p.n_steps >= 256 && !hq && n_quads >= wpb_max * e->num_cu && !getenv("ORLG_NO_CHUNKS");
-    if (!long_rounds) {
-        double best = 1e300;
-        for (int w = wpb_max; w >= 1; --w) {
-            const double rounds = (double)n_quads / ((double)e->num_cu * w);
-            // (short launches stride statically over the quads: whole rounds; long ones draw tickets: the last round is partial)
-            const double cost = ((rounds < 3.0 || p.n_steps <= 16) ? std::ceil(rounds) : rounds + 0.5) * (w + 1.5);
-            if (cost < best - 1e-9) { best = cost; wpb = w; }
-        }
-    }
-    if (const char *ov = getenv("ORLG_GROUP_WPB")) {   // tooling override: waves per workgroup
-        const int v = atoi(ov);
-        if (v >= 1 && v <= wpb_max) wpb = v;
-    }
-    const size_t lds_bytes = (size_t)p.l_shared_bytes + p.g_mt + 16 + (size_t)wpb * wave_bytes;
-    if (int rc = orlg_handle_resident(e, reinterpret_cast<const void *>(k), ORLG_WAVE * wpb, lds_bytes, &resident[wpb])) return rc;
-    int nblocks = (n_quads + wpb - 1) / wpb;
-    if (nblocks > resident[wpb]) nblocks = resident[wpb];
     OrlgParams q = p;
     q.llog = df ? e->llog : nullptr;
-    if (df) { q.g_lint = e->group_df_lint; q.g_qtime = e->group_df_qtime; q.g_qdesc = e->group_df_qdesc; q.g_lstat = e->group_df_lsum; }
-    q.g_wave_bytes = wave_bytes;
-    // the lean body of the DEFER instantiations (orlg_rmsa_group_body): first fit over the first path or all of them, no per-step
-    // output at all, discrete bit rates -- what a heuristic's evaluation or a load sweep launches
-    q.g_lean = df && (p.policy == ORLG_POLICY_SP || p.policy == ORLG_POLICY_SAP) && p.out_mask == 0 && p.br_width == 0 &&
-               !getenv("ORLG_NO_LEAN");
-    q.ticket_base = e->ticket_base;
-    q.ticket_stride = p.n_steps <= 16 ? 1u : 0u;
-    // Tickets in chunks of steps (orlg_rmsa_group_kernel, work queue): when the batch is not a multiple of the resident waves, a
-    // launch's last round of whole-launch tickets runs at a fraction of the occupancy for a whole launch's time (B = 65 536 on 3072
-    // wave slots: 5.33 rounds, the last one 1/3 full and nearly as long as a full one).  With k chunks per quad the tail is one
-    // chunk long; a hand-off between waves costs a few microseconds (agent-scope release + acquire) against milliseconds of steps.
-    q.n_chunks = 1; q.chunk_steps = p.n_steps; q.progress = nullptr;
-    {
-        const int slots = nblocks * wpb;
-        int k = 1;
-        if (long_rounds && !q.ticket_stride && n_quads > slots) {   // (exactly one round: 1 116 with chunks against 1 131-1 140 M)
-            // Measured (NSFNET-320, 1000-step launches, M env-steps/s by chunks k = 1 / 2 / 3 / 4; r = quads / slots rounds):
-            //   B = 16 384 (r = 1.33):   853 / 1 090 / 1 131 / 1 178      B = 49 152 (r = 4):    1 151 / 1 250 / 1 212 / 1 240
-            //   B = 24 576 (r = 2):    1 139 / 1 136 / 1 234 / 1 234      B = 65 536 (r = 5.33): 1 206 / 1 259 / 1 249 / 1 235
-            //   B = 131 072 (r = 10.7): 1 282 with k = 1, 1 257 with k = 3: after many rounds the waves' finishing times have
-            //   spread and the last round is short by itself.
-            // A chunk boundary costs a quad ~0.55 % of a 1000-step launch (state store + load, release + acquire); whole rounds
-            // (r = 2, 4) gain as well: waves that start together stay in step -- all in the same refill at the same time -- and
-            // chunks of different quads break that up.  About eight rounds of tickets are enough:
-            k = (int)std::floor(8.0 * slots / n_quads + 0.5);
-            k = k < 1 ? 1 : (k > 4 ? 4 : k);
-            while (k > 1 && p.n_steps / k < 128) --k;   // (a boundary costs the same whatever the chunk's length)
-        }
-        if (const char *ov = getenv("ORLG_GROUP_CHUNKS")) {   // tooling / tests: force the number of chunks (any batch)
-            const int v = atoi(ov);
-            if (v >= 1 && v <= 64 && !q.ticket_stride && !hq) k = v < p.n_steps ? v : p.n_steps;
-        }
-        if (k > 1) {
-            if (!e->progress) {
-                int rc = orlg_handle_alloc(e, &e->progress, (size_t)p.B / 4 + 1);
-                if (rc) return rc;
-            }
-            HIP_TRY(hipMemsetAsync(e->progress, 0, (size_t)n_quads * sizeof(uint32_t), e->stream));
-            q.chunk_steps = (p.n_steps + k - 1) / k;
-            q.n_chunks = (p.n_steps + q.chunk_steps - 1) / q.chunk_steps;
-            q.progress = e->progress;
-        }
-    }
-    // one draw per ticket a wave takes on (the next one is drawn when a ticket is taken up); with chunks every wave draws its first
-    // ticket as well
-    if (!q.ticket_stride) e->ticket_base += (uint32_t)n_quads * (uint32_t)q.n_chunks + (q.n_chunks > 1 ? (uint32_t)(nblocks * wpb) : 0u);
-    dim3 grid(nblocks), block(ORLG_WAVE * wpb);
-    hipLaunchKernelGGL(k, grid, block, lds_bytes, e->stream, q);
+    q.g_lstat = l.lstat; q.g_lint = l.lint; q.g_qtime = l.qtime; q.g_qdesc = l.qdesc; q.g_wave_bytes = l.wave_bytes;
+    q.g_lean = c.lean;
+    q.ticket_base = e->ticket_base; q.ticket_stride = c.ticket_stride;
+    q.n_chunks = t.n_chunks; q.chunk_steps = t.chunk_steps; q.progress = t.n_chunks > 1 ? e->progress : nullptr;
+    e->ticket_base += t.ticket_advance;
+    hipLaunchKernelGGL(k, dim3(t.nblocks), dim3(ORLG_WAVE * c.wpb), c.lds_bytes, e->stream, q);
     HIP_TRY(hipGetLastError());
-    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * wpb, lds_bytes, q.n_chunks, q.g_lean ? "lean" : "full");
+    orlg_handle_launched(e, key, t.nblocks, ORLG_WAVE * c.wpb, c.lds_bytes, t.n_chunks, c.lean ? "lean" : "full");
     return ORLG_OK;
 }
 
@@ -251,10 +185,8 @@ static rmsa_kernel_t step_kernel(int W, int stats) { return orlg_pick(W, OrlgWav
 
 static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
     const bool ff = p.mode == ORLG_MODE_STEP && p.K <= 8 && (p.policy == ORLG_POLICY_SP || p.policy == ORLG_POLICY_SAP);
-    // long launches with full statistics whose outputs do not read the link statistics step by step: the instantiation that logs the
-    // links' updates and works them off one link per lane (link_replay) -- as launch_rmsa_group
-    const bool df = p.mode == ORLG_MODE_STEP && p.stats_level >= 2 && p.n_steps >= 16 && !getenv("ORLG_NO_DEFER") &&
-                    !(p.out_mask & ((1 << ORLG_OUT_AVG_LINK_COMPACT) | (1 << ORLG_OUT_AVG_LINK_UTIL)));
+    const OrlgGroupOverrides ov = group_overrides();
+    const bool df = p.mode == ORLG_MODE_STEP && orlg_defer_link_stats(p.stats_level, p.n_steps, p.out_mask, ov);   // as launch_rmsa_group
     const OrlgWaveKey key = {ff ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel_ff)
                                 : p.mode == ORLG_MODE_STEP ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel) : ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel),
                              p.stats_level, df};
@@ -268,7 +200,7 @@ static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
         if (!rc) rc = orlg_handle_resident(e, ks, ORLG_WAVE * wpb, e->lds_block_bytes, &e->resident_blocks);
         if (rc) return rc;
     }
-    if (group_kernel_serves(e, p)) return launch_rmsa_group(e, p);
+    if (group_kernel_serves(e, p)) return launch_rmsa_group(e, p, ov);
     int nblocks = (p.B + wpb - 1) / wpb;
     if (nblocks > e->resident_blocks) nblocks = e->resident_blocks;
     if (df && !e->llog) {
@@ -480,7 +412,7 @@ static int rmsa_create(const orlg_topology *t, const orlg_rmsa_config *c, int32_
     {
         // pick the workgroup size that keeps the most environments (waves) resident per CU: 160 KiB of LDS, at most
         // 16 waves per CU wanted (4 per SIMD, the kernel's register budget); ties go to the larger workgroup
-        const size_t lds_cu = 160 * 1024;
+        const size_t lds_cu = ORLG_LDS_BYTES;
         int wpb = 0, best_waves = 0;
         const int wave_cap = 16;
         for (int cand = ORLG_MAX_WAVES_PER_BLOCK; cand >= 1; cand >>= 1) {
@@ -497,49 +429,22 @@ static int rmsa_create(const orlg_topology *t, const orlg_rmsa_config *c, int32_
         e->waves_per_block = wpb;
         e->lds_block_bytes = (size_t)p.l_shared_bytes + (size_t)wpb * p.l_wave_bytes;
     }
-    // the four-environments-per-wave kernel: one environment's LDS region (no MT19937 state, no arrival ring, scalars in
-    // registers), four per wave + the wave's MT19937 staging buffer; as many waves per workgroup as the LDS holds
+    // the four-environments-per-wave kernel: the LDS layout of each kind of instantiation; OrlgParams carries the plain one, a launch
+    // the one it chose (launch_rmsa_group)
     {
-        // a wave's region is array-major: the four environments' occupancy bitmaps behind each other, then their link statistics,
-        // span caches, release times, descriptors -- exactly as four consecutive environments lie in the HBM arrays, so a quad's
-        // occupancy / statistics / span cache move as ONE linear copy by all 64 lanes (uniform base + lane offset); g_* = offset of
-        // the array in the wave's region, row g's slice starts g * (slice bytes) further
-        int go = 0;
-        p.g_occ = go; go = up16(go + 4 * p.NW * 8);
-        p.g_lstat = go; if (c->stats_level >= ORLG_STATS_FULL) go = up16(go + 4 * 4 * E * 8);
-        p.g_hist = go;   // (unused: the four-environments-per-wave kernel updates the histograms in HBM)
-        p.g_lint = go; go = up16(go + 4 * p.lint_stride * 4);
-        p.g_qtime = go; go = up16(go + 4 * Q * 8);
-        p.g_qdesc = go; go = up16(go + 4 * Q * 4);
-        p.g_env_bytes = (go + 3) / 4;   // (per environment, for messages)
-        p.g_mt = up16(ORLG_MT_N * 4);   // the workgroup's MT19937 staging buffer (then its lock word), in front of the waves' regions
-        p.g_wave_bytes = go;
-        e->group_wpb = 0;
-        for (int cand = ORLG_GROUP_WAVES; cand >= 1 && !e->group_wpb; cand--)
-            if ((size_t)p.l_shared_bytes + p.g_mt + 16 + (size_t)cand * p.g_wave_bytes <= 160 * 1024) e->group_wpb = cand;
-        e->group_lds_bytes = (size_t)p.l_shared_bytes + p.g_mt + 16 + (size_t)e->group_wpb * p.g_wave_bytes;
-        for (int w = 0; w <= ORLG_GROUP_WAVES; w++) e->group_resident[w] = e->group_resident_hq[w] = e->group_resident_df[w] = 0;
-        {   // the instantiation that defers the link statistics keeps them in HBM: the same arrays without their slices
-            int gd = up16(p.g_occ + 4 * p.NW * 8);
-            e->group_df_lint = gd; gd = up16(gd + 4 * p.lint_stride * 4);
-            e->group_df_qtime = gd; gd = up16(gd + 4 * Q * 8);
-            e->group_df_qdesc = gd; gd = up16(gd + 4 * Q * 4);
-            e->group_df_lsum = gd; gd = up16(gd + 4 * E * 8);
-            e->group_df_wave_bytes = gd;
-            e->group_df_wpb = 0;
-            for (int cand = ORLG_GROUP_WAVES; cand >= 1 && !e->group_df_wpb; cand--)
-                if ((size_t)p.l_shared_bytes + p.g_mt + 16 + (size_t)cand * gd <= 160 * 1024) e->group_df_wpb = cand;
-        }
-        e->group_wave_bytes_hq = p.g_qtime;   // the region ends where the ring's slices would begin (they are the last arrays)
-        e->group_wpb_hq = 0;
-        for (int cand = ORLG_GROUP_WAVES; cand >= 1 && !e->group_wpb_hq; cand--)
-            if ((size_t)p.l_shared_bytes + p.g_mt + 16 + (size_t)cand * e->group_wave_bytes_hq <= 160 * 1024) e->group_wpb_hq = cand;
+        for (int kind = 0; kind < 3; kind++)
+            e->group[kind] = orlg_group_layout((OrlgGroupKind)kind, p.NW, E, Q, p.lint_stride, c->stats_level, p.l_shared_bytes);
+        const OrlgGroupLayout &g = e->group[ORLG_GROUP_PLAIN];
+        p.g_occ = g.occ; p.g_lstat = g.lstat; p.g_lint = g.lint; p.g_qtime = g.qtime; p.g_qdesc = g.qdesc; p.g_wave_bytes = g.wave_bytes;
+        p.g_hist = g.lint;   // (unused: the four-environments-per-wave kernel updates the histograms in HBM)
+        p.g_env_bytes = (g.wave_bytes + 3) / 4;   // (per environment, for messages)
+        p.g_mt = ORLG_GROUP_MT_BYTES;
         e->group_mode = c->step_kernel;
         const char *gm = getenv("ORLG_GROUP_KERNEL");  // tooling override: 0 = WAVE, 1 = GROUP
         if (gm && (gm[0] == '0' || gm[0] == '1')) e->group_mode = gm[0] == '1' ? ORLG_KERNEL_GROUP : ORLG_KERNEL_WAVE;
         if (e->group_mode < ORLG_KERNEL_AUTO || e->group_mode > ORLG_KERNEL_GROUP)
             return fail(ORLG_ERR_INVALID, "step_kernel %d: not one of ORLG_KERNEL_AUTO / WAVE / GROUP", c->step_kernel);
-        if (e->group_wpb < 1) {
+        if (g.wpb_max < 1) {
             if (e->group_mode == ORLG_KERNEL_GROUP)
                 return fail(ORLG_ERR_INVALID, "step_kernel GROUP: four environments (%d B each) do not fit the LDS", p.g_env_bytes);
             e->group_mode = ORLG_KERNEL_WAVE;
@@ -844,7 +749,7 @@ static int deeprmsa_observation(orlg_env *e, void *out, bool f32, uint8_t *mask)
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     const int wpb = e->waves_per_block;
     size_t lds = (size_t)p.l_shared_bytes + (size_t)(((p.NW * 8 + 15) & ~15) + ((p.obs_dim * 8 + 15) & ~15)) * wpb;
-    if (lds > 160 * 1024) return fail(ORLG_ERR_INVALID, "observation of %d values does not fit the LDS next to the tables", p.obs_dim);
+    if (lds > ORLG_LDS_BYTES) return fail(ORLG_ERR_INVALID, "observation of %d values does not fit the LDS next to the tables", p.obs_dim);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int nblocks = (p.B + wpb - 1) / wpb;
     if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;   // a few workgroups per CU, each wave striding over its environments
@@ -980,6 +885,32 @@ extern "C" int orlg_debug_layout(const orlg_env *e, int32_t *out, int n) {
     int i = 0;
 #define X(f) if (i < n) out[i] = e->p.f; i++;
     ORLG_SHAPE_FIELDS(X)
+#undef X
+    return i;
+}
+// what orlg_group_plan.h makes of a shape and a launch, without a device or a handle (tests/test_group_plan.py): in[] in
+// ORLG_GROUP_PLAN_IN order; out[] = the three layouts by OrlgGroupKind, ORLG_GROUP_LAYOUT_OUT each, then ORLG_GROUP_PLAN_OUT
+#define ORLG_GROUP_PLAN_IN(X) X(NW) X(E) X(Q) X(lint_stride) X(stats_level) X(shared_bytes) X(B) X(n_steps) X(policy) X(out_mask) \
+    X(br_width) X(no_defer) X(no_chunks) X(no_lean) X(wpb) X(chunks) X(num_cu) X(resident)
+#define ORLG_GROUP_LAYOUT_OUT(X) X(g, occ) X(g, lstat) X(g, lint) X(g, qtime) X(g, qdesc) X(g, wave_bytes) X(g, wpb_max)
+#define ORLG_GROUP_PLAN_OUT(X) X(c, kind) X(c, wpb) X(c, lds_bytes) X(c, lean) X(c, ticket_stride) X(c, long_rounds) X(t, nblocks) \
+    X(t, n_chunks) X(t, chunk_steps) X(t, ticket_advance)
+extern "C" int orlg_debug_group_plan(const int32_t *in, int32_t n_in, int32_t *out, int32_t n_out) {
+#define X(f) int32_t f;
+    struct { ORLG_GROUP_PLAN_IN(X) } v;
+#undef X
+    if (!in || !out || n_in != (int32_t)(sizeof(v) / sizeof(int32_t))) return fail(ORLG_ERR_INVALID, "orlg_debug_group_plan: %d inputs", n_in);
+    memcpy(&v, in, sizeof(v));
+    OrlgGroupLayout l[3];
+    for (int kind = 0; kind < 3; kind++) l[kind] = orlg_group_layout((OrlgGroupKind)kind, v.NW, v.E, v.Q, v.lint_stride, v.stats_level, v.shared_bytes);
+    const OrlgGroupOverrides ov = {v.no_defer != 0, v.no_chunks != 0, v.no_lean != 0, v.wpb, v.chunks};
+    const OrlgGroupChoice c = orlg_group_choose(l, {v.B, v.n_steps, v.stats_level, v.policy, v.out_mask, v.br_width}, ov, v.num_cu);
+    if (c.wpb < 1 || v.resident < 1 || v.n_steps < 1) return fail(ORLG_ERR_INVALID, "orlg_debug_group_plan: no workgroup to plan for");
+    const OrlgGroupTickets t = orlg_group_tickets(c, v.B, v.n_steps, v.resident, ov);
+    int i = 0;
+#define X(s, f) if (i < n_out) out[i] = (int32_t)s.f; i++;
+    for (const OrlgGroupLayout &g : l) { ORLG_GROUP_LAYOUT_OUT(X) }
+    ORLG_GROUP_PLAN_OUT(X)
 #undef X
     return i;
 }

@@ -2,6 +2,7 @@
 // Its own translation unit; the step kernel is instantiated per word count in orlg_inst_phy.hip.  What it has in common with the
 // RMSA API (orlg_api.hip) is the handle core of orlg_host.h.
 #include "orlg_host.h"
+#include "orlg_lds.h"
 #include "orlg_phy_layout.h"
 
 // the last 16 bytes of a continuous handle's saved state ("orlg phy", "cont f64"): a snapshot of the other bit-rate mode is refused
@@ -407,7 +408,7 @@ static int phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t 
         // D takes 8 bytes per channel and wave; it must not cost a resident workgroup (two of ORLG_MAX_WAVES_PER_BLOCK waves
         // fill the 128-VGPR budget of a CU) -- otherwise the adjacency lists stay
         const int nv_bytes = up16(C * 8);
-        if (2 * ((size_t)p.l_shared_bytes + (size_t)ORLG_MAX_WAVES_PER_BLOCK * (p.l_wave_bytes + nv_bytes)) <= 160 * 1024) {
+        if (2 * ((size_t)p.l_shared_bytes + (size_t)ORLG_MAX_WAVES_PER_BLOCK * (p.l_wave_bytes + nv_bytes)) <= ORLG_LDS_BYTES) {
             p.l_nv = p.l_wave_bytes;
             p.l_wave_bytes += nv_bytes;
         } else {
@@ -416,8 +417,8 @@ static int phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t 
     }
     {
         int wpb = ORLG_MAX_WAVES_PER_BLOCK;
-        while (wpb > 1 && (size_t)p.l_shared_bytes + (size_t)wpb * p.l_wave_bytes > 160 * 1024) wpb >>= 1;
-        if ((size_t)p.l_shared_bytes + (size_t)wpb * p.l_wave_bytes > 160 * 1024)
+        while (wpb > 1 && (size_t)p.l_shared_bytes + (size_t)wpb * p.l_wave_bytes > ORLG_LDS_BYTES) wpb >>= 1;
+        if ((size_t)p.l_shared_bytes + (size_t)wpb * p.l_wave_bytes > ORLG_LDS_BYTES)
             return fail(ORLG_ERR_INVALID, "tables + one environment exceed the 160 KiB LDS");
         e->waves_per_block = wpb;
         e->lds_block_bytes = (size_t)p.l_shared_bytes + (size_t)wpb * p.l_wave_bytes;
