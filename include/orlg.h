@@ -173,6 +173,44 @@ int orlg_step(orlg_env *env, int32_t policy, int32_t n_steps, const int32_t *act
  * also returns ORLG_ERR_QUEUE_FULL if an environment lost a release; otherwise the next orlg_synchronize /
  * orlg_reduce_counters reports it. */
 
+/* ---- GN-model GSNR admission check inside the step (this project's, not the reference's: examples/calculate_osnr.py has no
+ * caller there; opt-in, off by default).  The slot grid: slot width D = slot_width_hz, lower edge of slot 0 =
+ * frequency_start_hz.  A service on the window [s, s + n) (n = get_number_slots, guard slot included) has bandwidth b = n D, centre
+ * f = frequency_start_hz + (s + n / 2) D, launch power launch_power_density_w_hz * b (constant power spectral density) and the
+ * spectral efficiency of its path (path_se).  Link l has link_num_spans[l] equal spans of link_span_length_km[l], every span the
+ * same attenuation_normalized [1/m] and noise_figure (linear).
+ * The check runs once the action is known, in range and its window free, before _provision_path, whoever proposed the action
+ * (a device policy or the caller).  It evaluates calculate_osnr.py:9-56 for the candidate over the links of its path; the
+ * interferers of a link are the running services of that environment whose path contains it.  The candidate is in no list yet
+ * (no entry is the service itself), and windows on a shared link are disjoint, so no interferer is co-centred.  Admitted iff
+ * GSNR_dB >= thresholds_db[SE - 1]; otherwise the step goes on as for a rejection -- not accepted, the rejection's reward, nothing
+ * provisioned, no queue entry -- while act_path / act_slot still show the proposed action.  A policy proposes once: no next
+ * path is tried.  The action masks stay "window free": they do not know the gate.
+ * Served by the wave-per-environment kernel only: a gated handle runs orlg_rmsa_kernel<W,STATS,false,true> at every batch size
+ * and launch length (ORLG_KERNEL_AUTO resolves to WAVE); a handle without a gate runs exactly the kernels it ran before.  The gate
+ * is configuration, not state: orlg_save_state / orlg_load_state do not carry it, gated and ungated handles load each other's
+ * snapshots. */
+typedef struct orlg_rmsa_gn_gate {
+    double launch_power_density_w_hz;   /* W / Hz */
+    double frequency_start_hz;          /* lower edge of slot 0 */
+    double slot_width_hz;               /* channel_width [GHz] * 1e9 */
+    double attenuation_normalized;      /* 1/m */
+    double noise_figure;                /* linear */
+    const int32_t *link_num_spans;      /* [E] >= 1 */
+    const double *link_span_length_km;  /* [E] */
+    const double *thresholds_db;        /* [num_thresholds] by spectral efficiency 1.. */
+    int32_t num_thresholds;
+} orlg_rmsa_gn_gate;
+/* Sets (the arrays are copied) or, with NULL, removes the gate of a handle.  ORLG_ERR_INVALID: a path's spectral efficiency
+ * exceeds num_thresholds; a value is not finite or not positive (thresholds: not finite); the handle was created with
+ * step_kernel = ORLG_KERNEL_GROUP. */
+int orlg_set_gn_gate(orlg_env *env, const orlg_rmsa_gn_gate *gate);
+/* orlg_step plus one more per-step output: gn_gsnr_db [n_steps][B] float64 (host or device memory like the others, may be
+ * NULL) = the GSNR the check compared, NaN where no check ran (policy rejection, action out of range, window not free, or a
+ * handle without a gate).  orlg_step on a gated handle applies the gate all the same. */
+int orlg_step_gn(orlg_env *env, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
+                 const orlg_step_io *io, double *gn_gsnr_db);
+
 /* state read-back (all arrays [B] or [B][...] env-major) */
 int orlg_get_requests(orlg_env *env, orlg_request *out /* [B] */);
 int orlg_get_counters(orlg_env *env, orlg_counters *out /* [B] */);

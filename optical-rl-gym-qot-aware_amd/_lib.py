@@ -81,6 +81,12 @@ class GnGate(C.Structure):
                 ("pad", C.c_int32)]
 
 
+class RmsaGnGate(C.Structure):   # include/orlg.h orlg_rmsa_gn_gate
+    _fields_ = [("launch_power_density_w_hz", C.c_double), ("frequency_start_hz", C.c_double), ("slot_width_hz", C.c_double),
+                ("attenuation_normalized", C.c_double), ("noise_figure", C.c_double), ("link_num_spans", C.c_void_p),
+                ("link_span_length_km", C.c_void_p), ("thresholds_db", C.c_void_p), ("num_thresholds", C.c_int32)]
+
+
 class PhyStepIO(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("act_path", "n_channels", "channels", "accepted", "done", "request",
                                          "arrival", "holding", "number_cuts_total", "rss_total_metric",
@@ -125,7 +131,10 @@ def _prototypes():
               "orlg_simple_matrix_obs_dim": (None, [vp]),
               # valid-action masks for the whole batch
               "orlg_set_allow_rejection": (None, [vp, i32]), "orlg_deeprmsa_mask_dim": (None, [vp]),
-              "orlg_deeprmsa_observation_masked": (None, [vp, vp, i32, vp]), "orlg_action_masks": (None, [vp, vp, vp])})
+              "orlg_deeprmsa_observation_masked": (None, [vp, vp, i32, vp]), "orlg_action_masks": (None, [vp, vp, vp]),
+              # GN-model admission check inside the step
+              "orlg_set_gn_gate": (None, [vp, P(RmsaGnGate)]),
+              "orlg_step_gn": (None, [vp, i32, i32, vp, i32, P(StepIO), vp])})
     # QoT-aware only
     t.update({"orlg_phy_step": (None, [vp, i32, i32, vp, vp, i32, P(PhyStepIO)]), "orlg_phy_node_vectors": (None, [vp]),
               "orlg_phy_get_episode_stats": (None, [vp, vp]), "orlg_phy_channel_masks": (None, [vp, vp]),

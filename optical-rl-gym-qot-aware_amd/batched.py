@@ -11,7 +11,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from . import _lib, trace as _trace
+from . import _lib, osnr as _osnr, trace as _trace
 from ._handle import COUNTER_NAMES, REQUEST_DTYPE, SweepTraffic  # noqa: F401  (their import path: bench.py, tools/, tests)
 from ._handle import BatchedHandle, _check_buffer, _dtype_name, _output_names, _ptr
 
@@ -31,8 +31,11 @@ class BatchedRMSAEnv(BatchedHandle):
                  seeds=None, allow_rejection: bool = False, channel_width: float = 12.5, j: int = 1,
                  reward_mode: int = 0, stats_level: str = "full", queue_capacity: int = 0, device: int = 0,
                  step_kernel: str = "auto", bit_rate_lower_bound=25, bit_rate_higher_bound=100, groups=None,
-                 num_groups=None, trace=None):
+                 num_groups=None, trace=None, gn_gate=None):
         load, mean_service_holding_time = self._init_traffic_kwargs(trace, load, mean_service_holding_time, seed, seeds)
+        # GN-model GSNR admission check inside the step (osnr.rmsa_gn_gate_parameters; not in the reference: include/orlg.h
+        # orlg_rmsa_gn_gate).  Checked before the library is loaded
+        self.gn_gate = None if gn_gate is None else _osnr.check_rmsa_gn_gate(gn_gate, topology, step_kernel)
         if bit_rate_selection not in ("continuous", "discrete"):   # rmsa_env.py:74
             raise ValueError("bit_rate_selection must be 'continuous' or 'discrete'")
         self.bit_rate_selection = bit_rate_selection
@@ -67,6 +70,18 @@ class BatchedRMSAEnv(BatchedHandle):
         # is a rejection either way)
         _lib.check(self.L.orlg_set_allow_rejection(self.h, self.reject_action))
         self.mask_dim = self.L.orlg_deeprmsa_mask_dim(self.h)
+        if self.gn_gate is not None:
+            g, gg = self.gn_gate, _lib.RmsaGnGate()
+            for name in ("launch_power_density_w_hz", "frequency_start_hz", "slot_width_hz", "attenuation_normalized", "noise_figure"):
+                setattr(gg, name, float(g[name]))
+            gg.link_num_spans = self._keep_array(g["link_num_spans"], np.int32)
+            gg.link_span_length_km = self._keep_array(g["link_span_length_km"], np.float64)
+            gg.thresholds_db, gg.num_thresholds = self._keep_array(g["thresholds_db"], np.float64), len(g["thresholds_db"])
+            try:
+                _lib.check(self.L.orlg_set_gn_gate(self.h, C.byref(gg)))
+            except Exception:
+                self.close()
+                raise
 
     def launch_info(self):
         """Launch geometry of the step kernel (envs per workgroup, LDS bytes, resident workgroups per CU)."""
@@ -80,10 +95,16 @@ class BatchedRMSAEnv(BatchedHandle):
             outputs: Sequence[str] = (), out: Optional[Dict[str, object]] = None):
         """``n_steps`` x (policy -> step) on the device.  ``outputs`` names per-step arrays to return
         (see ``_lib.STEP_IO_DTYPES``) as numpy arrays of shape [n_steps, B(, 4)]; ``out`` may supply
-        preallocated numpy arrays or torch tensors (device tensors are written without staging)."""
+        preallocated numpy arrays or torch tensors (device tensors are written without staging).  ``"gn_gsnr_db"``: the GSNR
+        the GN-model admission check compared (``gn_gate=``), NaN where no check ran; it leaves through ``orlg_step_gn``."""
         B = self.batch_size
         io = _lib.StepIO()
-        res = self._step_outputs(_output_names(outputs, out), n_steps, out, _lib.STEP_IO_DTYPES, _STEP_IO_SHAPES, io)
+        names = _output_names(outputs, out)
+        gsnr = None
+        if "gn_gsnr_db" in names:
+            names = [n for n in names if n != "gn_gsnr_db"]
+            gsnr = self._step_outputs(["gn_gsnr_db"], n_steps, out, {"gn_gsnr_db": "float64"}, {})
+        res = self._step_outputs(names, n_steps, out, _lib.STEP_IO_DTYPES, _STEP_IO_SHAPES, io)
         ap = None
         if policy in ("external", "deeprmsa_external", "path_ff_external"):
             if actions is None:
@@ -96,8 +117,13 @@ class BatchedRMSAEnv(BatchedHandle):
                 actions = np.ascontiguousarray(actions, dtype=np.int32)
             _check_buffer("actions", actions, ashape, np.int32)
             ap = _ptr(actions)
-        _lib.check(self.L.orlg_step(self.h, _lib.POLICIES[policy], int(n_steps), ap, 1 if auto_reset else 0,
-                                    C.byref(io)))
+        if gsnr is None:
+            _lib.check(self.L.orlg_step(self.h, _lib.POLICIES[policy], int(n_steps), ap, 1 if auto_reset else 0,
+                                        C.byref(io)))
+        else:
+            _lib.check(self.L.orlg_step_gn(self.h, _lib.POLICIES[policy], int(n_steps), ap, 1 if auto_reset else 0,
+                                           C.byref(io), _ptr(gsnr["gn_gsnr_db"])))
+            res.update(gsnr)
         return res
 
     def step(self, actions, outputs=("reward", "done", "accepted")):
@@ -193,7 +219,8 @@ class BatchedRMSAEnv(BatchedHandle):
 
     def action_masks(self, kind="deeprmsa", out=None):
         """Valid actions of every env's pending request: ``mask[a] = 1`` iff the reference's ``step(a)`` would accept the
-        service.  The explicit rejection, where ``allow_rejection`` gives the action space one, is always 1.
+        service.  The explicit rejection, where ``allow_rejection`` gives the action space one, is always 1.  The masks say
+        "the window is free": they do not know a GN-model admission check (``gn_gate=``), which may still refuse the service.
 
         ``"deeprmsa"``  [B, k*j + reject] uint8: action ``a`` = (route ``a // j``, block ``a % j``) is valid iff the route has
                         more than ``block`` free runs of at least ``get_number_slots(route)`` slots (``deeprmsa_env.py:48-58``).

@@ -18,8 +18,10 @@ struct orlg_env : OrlgHandle {
     uint4 *llog = nullptr;          // DEFER: the log of link updates [B][E][ORLG_LLOG_CAP] (allocated with the first such launch)
     uint32_t *progress = nullptr;   // chunked tickets: chunks completed per quad in the current launch (allocated with the first such launch)
     int allow_rejection = 0;   // the action spaces carry the explicit rejection (orlg_set_allow_rejection): one more mask column
+    std::vector<uint8_t> path_se;   // spectral efficiency of every path record (orlg_set_gn_gate checks the thresholds against it)
+    double *gn_table = nullptr;     // the gate's table on the device (allocated with the first gate; OrlgParams::gn = it or nullptr)
 };
-enum { X_ACTIONS };   // OrlgHandle::extra: external actions from pageable host memory
+enum { X_ACTIONS, X_GSNR };   // OrlgHandle::extra: external actions from / the gn_gsnr_db output for pageable host memory
 
 #define SYNC_CHECK(e) do { int rc_ = orlg_handle_sync_check(e); if (rc_) return rc_; } while (0)
 
@@ -171,7 +173,7 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p, const OrlgGroupOv
 }
 
 static bool group_kernel_serves(const orlg_env *e, const OrlgParams &p) {
-    if (e->group_mode == ORLG_KERNEL_WAVE || p.mode != ORLG_MODE_STEP) return false;
+    if (e->group_mode == ORLG_KERNEL_WAVE || p.mode != ORLG_MODE_STEP || p.gn) return false;   // (a gated handle: the wave kernel's GN instantiations)
     if (e->group_mode == ORLG_KERNEL_GROUP) return true;
     // AUTO: this kernel once the batch exceeds what the wave-per-environment kernel keeps resident (4096 environments on
     // MI355X) -- long launches (B = 65 536: 1140 vs 630 M env-steps/s) and launches of one step alike (B = 32 768, DeepRMSA
@@ -184,12 +186,14 @@ static bool group_kernel_serves(const orlg_env *e, const OrlgParams &p) {
 static rmsa_kernel_t step_kernel(int W, int stats) { return orlg_pick(W, OrlgWaveKey{ORLG_WAVE_KERNEL(orlg_rmsa_kernel), stats, false}); }
 
 static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
-    const bool ff = p.mode == ORLG_MODE_STEP && p.K <= 8 && (p.policy == ORLG_POLICY_SP || p.policy == ORLG_POLICY_SAP);
+    // a step of a handle with a GN-model admission check: the general kernel's GN instantiation, whatever the policy and the length
+    const bool gn = p.mode == ORLG_MODE_STEP && p.gn != nullptr;
+    const bool ff = !gn && p.mode == ORLG_MODE_STEP && p.K <= 8 && (p.policy == ORLG_POLICY_SP || p.policy == ORLG_POLICY_SAP);
     const OrlgGroupOverrides ov = group_overrides();
-    const bool df = p.mode == ORLG_MODE_STEP && orlg_defer_link_stats(p.stats_level, p.n_steps, p.out_mask, ov);   // as launch_rmsa_group
+    const bool df = !gn && p.mode == ORLG_MODE_STEP && orlg_defer_link_stats(p.stats_level, p.n_steps, p.out_mask, ov);   // as launch_rmsa_group
     const OrlgWaveKey key = {ff ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel_ff)
                                 : p.mode == ORLG_MODE_STEP ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel) : ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel),
-                             p.stats_level, df};
+                             p.stats_level, df, gn};
     rmsa_kernel_t k = orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), e->lds_block_bytes)) return rc;
@@ -373,6 +377,7 @@ static int rmsa_create(const orlg_topology *t, const orlg_rmsa_config *c, int32_
             if (t->path_se[g] < 1 || t->path_se[g] >= ORLG_NSLOT_STRIDE)
                 return fail(ORLG_ERR_INVALID, "path %d: spectral efficiency %d not in 1..7", g, t->path_se[g]);
         p.t_recs = blob.put(recs.data(), recs.size() * sizeof(OrlgPathRec));
+        e->path_se.assign(t->path_se, t->path_se + t->num_paths);
         // get_number_slots (rmsa_env.py:708-719): ceil(bit_rate / (SE * channel_width)) + 1
         std::vector<uint16_t> ns((size_t)NBR * ORLG_NSLOT_STRIDE, 0);
         for (int b = 0; b < NBR; b++)
@@ -533,8 +538,10 @@ int orlg_reseed(orlg_env *e, const uint64_t *seeds, uint64_t base_seed) {
 // io slot ids
 enum { IO_PATH, IO_SLOT, IO_ACC, IO_DONE, IO_REWARD, IO_REQ, IO_ARR, IO_HOLD, IO_COMP, IO_CDIFF };
 
-int orlg_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
-              const orlg_step_io *io) {
+}  // extern "C"
+// orlg_step and orlg_step_gn (gsnr: the one output more, nullptr = not asked for)
+static int rmsa_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
+                     const orlg_step_io *io, double *gsnr) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     if (n_steps < 1) return fail(ORLG_ERR_INVALID, "n_steps must be >= 1");
     if (policy < ORLG_POLICY_EXTERNAL || policy > ORLG_POLICY_PATH_FF_EXTERNAL) return fail(ORLG_ERR_INVALID, "unknown policy %d", policy);
@@ -568,13 +575,84 @@ int orlg_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actio
         {io ? io->avg_link_compactness : nullptr, 8},   {io ? io->avg_link_utilization : nullptr, 8}};
     int rc = orlg_handle_place(e, slots, ORLG_NUM_OUTS, cnt, p.outs, &p.out_mask);
     if (rc) return rc;
+    // gn_gsnr_db: device memory (or pinned host memory) is written in place, pageable host memory through a buffer of the handle
+    const bool gsnr_staged = gsnr && !orlg_device_alias(gsnr);
+    p.o_gsnr = gsnr ? static_cast<double *>(orlg_device_alias(gsnr)) : nullptr;
+    if (gsnr_staged) {
+        rc = orlg_scratch_grow(&e->extra[X_GSNR], cnt * sizeof(double));
+        if (rc) return rc;
+        p.o_gsnr = static_cast<double *>(e->extra[X_GSNR].ptr);
+    }
+    if (gsnr && !p.gn) HIP_TRY(hipMemsetAsync(p.o_gsnr, 0xff, cnt * sizeof(double), e->stream));   // no gate, no check: all NaN
     rc = launch_rmsa(e, p);
     if (rc) return rc;
     if (e->trace.length > 0) e->trace.position += n_steps;
     bool any = false;
     rc = orlg_handle_collect(e, slots, ORLG_NUM_OUTS, cnt, p.outs, &any);
     if (rc) return rc;
+    if (gsnr_staged) {
+        HIP_TRY(hipMemcpyAsync(gsnr, p.o_gsnr, cnt * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        any = true;
+    }
     if (any) SYNC_CHECK(e);
+    return ORLG_OK;
+}
+extern "C" {
+int orlg_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io) {
+    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr);
+}
+int orlg_step_gn(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
+                 double *gn_gsnr_db) {
+    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, gn_gsnr_db);
+}
+
+int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    HIP_TRY(hipSetDevice(e->device));
+    if (!g) {
+        e->p.gn = nullptr;
+        return ORLG_OK;
+    }
+    if (e->group_mode == ORLG_KERNEL_GROUP)
+        return fail(ORLG_ERR_INVALID, "gn_gate: the admission check is served by the wave-per-environment kernel, the handle was created with step_kernel GROUP");
+    const int E = e->p.E;
+    if (!g->link_num_spans || !g->link_span_length_km || !g->thresholds_db) return fail(ORLG_ERR_INVALID, "null argument");
+    const struct { const char *name; double v; } scalars[] = {
+        {"launch_power_density_w_hz", g->launch_power_density_w_hz}, {"frequency_start_hz", g->frequency_start_hz},
+        {"slot_width_hz", g->slot_width_hz}, {"attenuation_normalized", g->attenuation_normalized}, {"noise_figure", g->noise_figure}};
+    for (const auto &sc : scalars)
+        if (!std::isfinite(sc.v) || !(sc.v > 0)) return fail(ORLG_ERR_INVALID, "gn_gate: %s must be finite and positive", sc.name);
+    if (g->num_thresholds < 1 || g->num_thresholds > ORLG_GN_LINK0 - ORLG_GN_THR0)
+        return fail(ORLG_ERR_INVALID, "gn_gate: num_thresholds %d not in 1..%d", g->num_thresholds, ORLG_GN_LINK0 - ORLG_GN_THR0);
+    for (int i = 0; i < g->num_thresholds; i++)
+        if (!std::isfinite(g->thresholds_db[i])) return fail(ORLG_ERR_INVALID, "gn_gate: thresholds_db[%d] is not finite", i);
+    for (size_t gid = 0; gid < e->path_se.size(); gid++) {
+        if (e->path_se[gid] > g->num_thresholds)
+            return fail(ORLG_ERR_INVALID, "gn_gate: path %zu has spectral efficiency %d, thresholds_db has %d entries", gid, e->path_se[gid], g->num_thresholds);
+        if (e->path_se[gid] > 6)
+            return fail(ORLG_ERR_INVALID, "gn_gate: path %zu has spectral efficiency %d, the modulation factors of the GN model end at 6", gid, e->path_se[gid]);
+    }
+    std::vector<double> tab(ORLG_GN_LINK0 + 4 * (size_t)E, 0.0);
+    const double att = g->attenuation_normalized;
+    tab[ORLG_GN_DENSITY] = g->launch_power_density_w_hz; tab[ORLG_GN_F0] = g->frequency_start_hz; tab[ORLG_GN_SLOT] = g->slot_width_hz;
+    tab[ORLG_GN_ATT] = att; tab[ORLG_GN_NF] = g->noise_figure; tab[ORLG_GN_LEFF_A] = 1 / (2 * att);
+    for (int i = 0; i < g->num_thresholds; i++) tab[ORLG_GN_THR0 + i] = g->thresholds_db[i];
+    for (int l = 0; l < E; l++) {
+        const double len = g->link_span_length_km[l];
+        if (g->link_num_spans[l] < 1) return fail(ORLG_ERR_INVALID, "gn_gate: link_num_spans[%d] = %d", l, g->link_num_spans[l]);
+        if (!std::isfinite(len) || !(len > 0)) return fail(ORLG_ERR_INVALID, "gn_gate: link_span_length_km[%d] must be finite and positive", l);
+        // per span, as calculate_osnr.py:24-26, 50 writes them
+        const double l_eff = (1 - std::exp(-2 * att * len * 1e3)) / (2 * att);
+        const double e1 = std::exp(2 * att * len * 1e3) - 1;
+        if (!std::isfinite(e1)) return fail(ORLG_ERR_INVALID, "gn_gate: the loss of a span of link %d overflows", l);
+        double *row = &tab[ORLG_GN_LINK0 + 4 * (size_t)l];
+        row[0] = l_eff; row[1] = l_eff / (len * 1e3); row[2] = e1; row[3] = (double)g->link_num_spans[l];
+    }
+    if (!e->gn_table)
+        if (int rc = orlg_handle_alloc(e, &e->gn_table, tab.size())) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));   // (a launch in flight may be reading the table)
+    HIP_TRY(hipMemcpy(e->gn_table, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    e->p.gn = e->gn_table;
     return ORLG_OK;
 }
 

@@ -142,7 +142,14 @@ struct OrlgParams {
     const double *tr_arrival, *tr_holding;
     const uint32_t *tr_req;
     int32_t tr_len, pad_tr;
+    // GN-model admission check of the wave-per-environment kernel (orlg_set_gn_gate, orlg_rmsa_gn.h): the gate's table in HBM
+    // (ORLG_GN_* below), nullptr = no gate; o_gsnr: the per-step output gn_gsnr_db [n_steps][B] of orlg_step_gn, nullptr = not asked for
+    const double *gn;
+    double *o_gsnr;
 };
+// OrlgParams::gn, in doubles: the gate's scalars, the thresholds by spectral efficiency - 1 from ORLG_GN_THR0, then four per link
+// from ORLG_GN_LINK0 -- effective length of a span, its ratio to the span's length, exp(2 att len) - 1, number of spans
+enum { ORLG_GN_DENSITY = 0, ORLG_GN_F0, ORLG_GN_SLOT, ORLG_GN_ATT, ORLG_GN_NF, ORLG_GN_LEFF_A, ORLG_GN_THR0 = 8, ORLG_GN_LINK0 = 16 };
 
 // A kernel's parameter struct T in the kernarg segment: fields are fetched through the scalar cache where they are used
 template <typename T>

@@ -15,6 +15,7 @@
 orlg_rmsa_kernel_t ORLG_CAT(orlg_wave_kernel_W, ORLG_INST_W)(OrlgWaveKey key) {
 #define X(name, ...) if (key == OrlgWaveKey{ORLG_WAVE_KERNEL(name), __VA_ARGS__}) return name<ORLG_INST_W, __VA_ARGS__>;
     ORLG_WAVE_KEYS(X)
+    ORLG_WAVE_GN_KEYS(X)
 #undef X
     return nullptr;
 }

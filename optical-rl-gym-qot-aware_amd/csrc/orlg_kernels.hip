@@ -33,6 +33,7 @@
 #pragma once
 #include "orlg_link_stats.h"   // and through it orlg_wave.h, orlg_rmsa_layout.h, orlg_spectrum.h
 #include "orlg_requests.h"     // mt_regenerate, the ring's three producers, ring_store, ring_visible, orlg_env_rates
+#include "orlg_rmsa_gn.h"      // rmsa_gn_gsnr: the GN-model admission check of the GN instantiations
 #include "orlg_sections.h"
 
 // ---------------------------------------------------------------------------------------- the step kernel
@@ -40,7 +41,9 @@
 // same body without the policy / provisioning part, under its own name so that kernel statistics keep the two apart.
 // FF: an instantiation that only knows the first-fit policies (shortest path / shortest available path, k <= 8): the other
 // policies' code -- and the registers it pins -- is gone from the kernel the headline workload runs.
-template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false>
+// GN: the handle has a GN-model admission check (orlg_set_gn_gate): a window that is free is provisioned only if its GSNR meets the
+// threshold of the path's spectral efficiency (orlg_rmsa_gn.h); every other instantiation holds none of that code.
+template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false, bool GN = false>
 DEV void rmsa_body(const OrlgParams &p) {
     extern __shared__ __align__(16) unsigned char smem[];
 #ifdef ORLG_SHAPE_ASSUME
@@ -286,6 +289,7 @@ DEV void rmsa_body(const OrlgParams &p) {
             SEC(3);  // validate + provision
             const double prev_compact = comp_cur;
             bool accepted = false;
+            double gn_gsnr = __longlong_as_double(0x7ff8000000000000ll);   // GN: the GSNR the check compared, NaN = no check ran
             if (a_path >= 0 && a_path < K && a_slot >= 0 && a_slot < S) {
                 const int n = __builtin_amdgcn_readlane(my_n, a_path);
                 // the device policies only propose windows they found free; agent actions are checked (is_path_free)
@@ -295,6 +299,14 @@ DEV void rmsa_body(const OrlgParams &p) {
 #pragma unroll
                     for (int w = 0; w < W; ++w) x[w] = readlane64(acc, a_path * LS + w);
                     window_ok = window_free<W>(x, a_slot, n, S);
+                }
+                if constexpr (GN) {
+                    if (window_ok) {
+                        const OrlgGnTable gn = ORLG_GPTR(const double, p.gn);
+                        const OrlgPathRec *cand = tb.recs + (base + a_path);
+                        gn_gsnr = rmsa_gn_gsnr(wv, tb, gn, E, Q, q_head, q_n, cand, a_slot, n);
+                        window_ok = gn_gsnr >= gn[ORLG_GN_THR0 + (int)cand->se - 1];
+                    }
                 }
                 if (window_ok) {
                     // ---- _provision_path (rmsa_env.py:462-513)
@@ -384,6 +396,9 @@ DEV void rmsa_body(const OrlgParams &p) {
                     if (FULL && (om & (1 << ORLG_OUT_AVG_LINK_UTIL)))
                         ORLG_GPTR(double, tb.outs[ORLG_OUT_AVG_LINK_UTIL])[o] = np_mean(wv.lst, E);
                 }
+            }
+            if constexpr (GN) {
+                if (lane == 0 && p.o_gsnr) ORLG_GPTR(double, p.o_gsnr)[(size_t)t * p.B + env] = gn_gsnr;
             }
             new_service = 0;
         } else if (p.mode == ORLG_MODE_EPISODE_RESET) {
@@ -570,9 +585,9 @@ DEV void rmsa_body(const OrlgParams &p) {
     SEC_FLUSH;
 }
 
-template <int W, int STATS, bool DEFER = false>
+template <int W, int STATS, bool DEFER = false, bool GN = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel(const OrlgParams p) {
-    rmsa_body<W, STATS, true, false, DEFER>(p);
+    rmsa_body<W, STATS, true, false, DEFER, GN>(p);
 }
 template <int W, int STATS, bool DEFER = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel_ff(const OrlgParams p) {

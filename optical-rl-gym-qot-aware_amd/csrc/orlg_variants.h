@@ -10,7 +10,8 @@
 #include "../../include/orlg.h"   // ORLG_PHY_POLICY_*
 
 // ---------------------------------------------------------------------------------------- keys
-// wave-per-environment kernels (orlg_kernels.hip): template <int W, int STATS, bool DEFER = false>; the reset kernel has no DEFER
+// wave-per-environment kernels (orlg_kernels.hip): template <int W, int STATS, bool DEFER = false, bool GN = false>; the reset kernel
+// has no DEFER, and only orlg_rmsa_kernel has GN (the GN-model admission check, orlg_rmsa_gn.h)
 #define ORLG_WAVE_KERNELS(X) X(orlg_rmsa_kernel) X(orlg_rmsa_kernel_ff) X(orlg_rmsa_reset_kernel)
 #define ORLG_WAVE_KERNEL(name) ORLG_IS_##name
 enum OrlgWaveKernel {
@@ -18,13 +19,13 @@ enum OrlgWaveKernel {
     ORLG_WAVE_KERNELS(X)
 #undef X
 };
-struct OrlgWaveKey { OrlgWaveKernel kernel; int STATS; bool DEFER; };
+struct OrlgWaveKey { OrlgWaveKernel kernel; int STATS; bool DEFER; bool GN = false; };
 // orlg_rmsa_group_kernel (orlg_group_kernels.hip)
 struct OrlgGroupKey { int STATS; bool HBMQ, DEFER, TRAFFIC, TRACE; };
 // orlg_phy_kernel (orlg_phy_kernels.hip)
 struct OrlgPhyKey { bool DF, GN; int POL; bool CONT, TRACE; };
 
-inline bool operator==(const OrlgWaveKey &a, const OrlgWaveKey &b) { return a.kernel == b.kernel && a.STATS == b.STATS && a.DEFER == b.DEFER; }
+inline bool operator==(const OrlgWaveKey &a, const OrlgWaveKey &b) { return a.kernel == b.kernel && a.STATS == b.STATS && a.DEFER == b.DEFER && a.GN == b.GN; }
 inline bool operator==(const OrlgGroupKey &a, const OrlgGroupKey &b) {
     return a.STATS == b.STATS && a.HBMQ == b.HBMQ && a.DEFER == b.DEFER && a.TRAFFIC == b.TRAFFIC && a.TRACE == b.TRACE;
 }
@@ -41,6 +42,11 @@ inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
     X(orlg_rmsa_kernel_ff, 1) X(orlg_rmsa_kernel_ff, 2) X(orlg_rmsa_kernel_ff, 0)            \
     X(orlg_rmsa_kernel, 2, true) X(orlg_rmsa_kernel_ff, 2, true)                             \
     X(orlg_rmsa_reset_kernel, 1) X(orlg_rmsa_reset_kernel, 2) X(orlg_rmsa_reset_kernel, 0)
+// X(kernel, STATS, DEFER, GN): what a handle with a GN-model admission check launches (orlg_set_gn_gate) -- the general step kernel
+// with the check, per statistics level; no _ff and no DEFER variant.  A list of its own: ORLG_WAVE_KEYS stays what a handle without
+// a gate can reach, in number too (tests/test_variant_names.py counts its lookups); an instantiation unit expands both, these
+// last, so that the kernels in front of them lie in the code object where they lay.
+#define ORLG_WAVE_GN_KEYS(X) X(orlg_rmsa_kernel, 1, false, true) X(orlg_rmsa_kernel, 2, false, true) X(orlg_rmsa_kernel, 0, false, true)
 
 // X(STATS, HBMQ, DEFER, TRAFFIC, TRACE).  Per kind of handle: every statistics level, the same with the release queue left in HBM
 // (launches of very few steps), and full statistics with the link updates deferred (long launches).  The kinds: plain, with
@@ -80,6 +86,7 @@ inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
 #define ORLG_GROUP_KEY_ENTRY(...) OrlgGroupKey{__VA_ARGS__},
 #define ORLG_PHY_KEY_ENTRY(...) OrlgPhyKey{__VA_ARGS__},
 inline constexpr OrlgWaveKey ORLG_WAVE_KEY_LIST[] = {ORLG_WAVE_KEYS(ORLG_WAVE_KEY_ENTRY)};
+inline constexpr OrlgWaveKey ORLG_WAVE_GN_KEY_LIST[] = {ORLG_WAVE_GN_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_KEY_LIST[] = {ORLG_GROUP_KEYS(ORLG_GROUP_KEY_ENTRY)};
 inline constexpr OrlgPhyKey ORLG_PHY_KEY_LIST[] = {ORLG_PHY_KEYS(ORLG_PHY_KEY_ENTRY)};
 template <typename Key, size_t N>
@@ -105,8 +112,8 @@ inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgWaveKey &k)
 #define X(name) #name,
     static const char *const names[] = {ORLG_WAVE_KERNELS(X)};
 #undef X
-    const OrlgArg args[] = {{k.STATS, 'i'}, {k.DEFER, 'd'}};
-    orlg_format_kernel(buf, cap, names[k.kernel], W, args, k.kernel == ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel) ? 1 : 2);
+    const OrlgArg args[] = {{k.STATS, 'i'}, {k.DEFER, 'd'}, {k.GN, 'd'}};
+    orlg_format_kernel(buf, cap, names[k.kernel], W, args, k.kernel == ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel) ? 1 : 3);
 }
 inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgGroupKey &k) {
     const OrlgArg args[] = {{k.STATS, 'i'}, {k.HBMQ, 'd'}, {k.DEFER, 'd'}, {k.TRAFFIC, 'd'}, {k.TRACE, 'd'}};

@@ -127,7 +127,8 @@ class RMSAEnv(_View):
                  bit_rate_probabilities=None, node_request_probabilities=None, bit_rate_lower_bound: float = 25.0,
                  bit_rate_higher_bound: float = 100.0, seed: Optional[int] = None, allow_rejection: bool = False,
                  reset: bool = True, channel_width: float = 12.5, device: int = 0, _batched=None, _index: int = 0,
-                 trace=None, **_ignored):
+                 trace=None, gn_gate=None, **_ignored):
+        # (gn_gate=: the GN-model admission check of BatchedRMSAEnv; info["gn_gsnr_db"] exists only with it)
         # (load / mean_service_holding_time: None = the reference's defaults 10 / 10800.0; trace=: a RequestTrace to replay,
         # which excludes load, mean_service_holding_time and seed -- BatchedRMSAEnv)
         assert bit_rate_selection in ("continuous", "discrete")
@@ -140,7 +141,7 @@ class RMSAEnv(_View):
                                          bit_rate_probabilities=bit_rate_probabilities,
                                          node_request_probabilities=node_request_probabilities, seed=seed,
                                          allow_rejection=allow_rejection, channel_width=channel_width, device=device,
-                                         trace=trace)
+                                         trace=trace, gn_gate=gn_gate)
         self._init_view(_batched, _index)
 
     # ------------------------------------------------------------------ plumbing
@@ -312,7 +313,10 @@ class RMSAEnv(_View):
         return self._batched.run("external", 1, actions=np.array([[path, initial_slot]], np.int32),
                                  outputs=("accepted", "done", "reward", "network_compactness",
                                           "network_compactness_difference", "avg_link_compactness",
-                                          "avg_link_utilization"))
+                                          "avg_link_utilization") + self._gate_outputs())
+
+    def _gate_outputs(self):
+        return ("gn_gsnr_db",) if self._batched.gn_gate is not None else ()
 
     def step(self, action):
         """``rmsa_env.py:222-341`` -> (observation, reward, done, info)"""
@@ -334,6 +338,8 @@ class RMSAEnv(_View):
             self.actions_taken[self.k_paths, self.num_spectrum_resources] += 1
         info = self._info(float(r["network_compactness"][0, 0]), float(r["network_compactness_difference"][0, 0]),
                           float(r["avg_link_compactness"][0, 0]), float(r["avg_link_utilization"][0, 0]))
+        if "gn_gsnr_db" in r:   # (a handle with a GN-model admission check: the GSNR it compared, NaN = no check ran)
+            info["gn_gsnr_db"] = float(r["gn_gsnr_db"][0, 0])
         reward = r["reward"][0, 0]
         reward = int(reward) if float(reward).is_integer() else float(reward)
         self._sync()
@@ -377,7 +383,7 @@ class DeepRMSAEnv(RMSAEnv):
     def __init__(self, topology=None, j: int = 1, episode_length: int = 1000, mean_service_holding_time: float = None,
                  mean_service_inter_arrival_time: float = None, num_spectrum_resources: int = 100,
                  node_request_probabilities=None, seed=None, allow_rejection: bool = False, device: int = 0,
-                 _batched=None, _index: int = 0, trace=None):
+                 _batched=None, _index: int = 0, trace=None, gn_gate=None):
         # (the means: None = the reference's defaults 25.0 / 0.1; trace=: a RequestTrace to replay, which excludes them)
         if _batched is None:
             _batched = BatchedDeepRMSAEnv(topology, 1, j=j, episode_length=episode_length,
@@ -385,7 +391,7 @@ class DeepRMSAEnv(RMSAEnv):
                                           mean_service_inter_arrival_time=mean_service_inter_arrival_time,
                                           num_spectrum_resources=num_spectrum_resources,
                                           node_request_probabilities=node_request_probabilities, seed=seed,
-                                          allow_rejection=allow_rejection, device=device, trace=trace)
+                                          allow_rejection=allow_rejection, device=device, trace=trace, gn_gate=gn_gate)
         self._init_view(_batched, _index)
         shape = 1 + 2 * self._ft.num_nodes + (2 * self.j + 3) * self.k_paths
         self.observation_space = _box(-2 ** 30, 2 ** 30, (shape,), np.float64)
@@ -403,7 +409,7 @@ class DeepRMSAEnv(RMSAEnv):
         return self._batched.run("deeprmsa_external", 1, actions=np.array([int(action)], np.int32),
                                  outputs=("accepted", "done", "reward", "network_compactness",
                                           "network_compactness_difference", "avg_link_compactness",
-                                          "avg_link_utilization", "act_path", "act_slot"))
+                                          "avg_link_utilization", "act_path", "act_slot") + self._gate_outputs())
 
     def _resolved_action(self, action, r):
         """``deeprmsa_env.py:48-58``: the (route, first slot of the block) the action stands for, (k, S) for a rejection"""

@@ -131,3 +131,62 @@ def gn_gate_parameters(topology, num_channels=268, *, launch_power_dbm=0.0, chan
         "link_span_length_km": lengths / nspans,
         "thresholds_db": np.asarray(sorted(thr), np.float64),
     }
+
+
+def rmsa_gn_gate_parameters(topology, *, launch_power_dbm_per_50ghz=0.0, frequency_start_hz=191.7e12, channel_width=12.5,
+                            max_span_length_km=80.0, attenuation_db_km=0.2, noise_figure_db=4.5, thresholds_db=None):
+    """Parameters of the GN-model admission check of ``BatchedRMSAEnv(..., gn_gate=...)`` / ``BatchedDeepRMSAEnv``
+    (``include/orlg.h`` ``orlg_rmsa_gn_gate``): a plain dict of numbers / arrays.
+
+    * slot grid: slot width ``channel_width`` GHz, lower edge of slot 0 at ``frequency_start_hz``; a service on the window
+      ``[s, s + n)`` is ``n`` slots wide around ``frequency_start_hz + (s + n / 2) * width``;
+    * launch power: a constant power spectral density, ``launch_power_dbm_per_50ghz`` dBm in every 50 GHz --
+      ``1e-3 * 10 ** (dBm / 10) / 50e9`` W/Hz;
+    * spans, attenuation, noise figure and the default thresholds: the conventions of :func:`gn_gate_parameters`.
+    """
+    from .topology import FrozenTopology
+    t = FrozenTopology.from_graph(topology)
+    lengths = np.array([float(e[4]) for e in t.edges], np.float64)[np.argsort([int(e[2]) for e in t.edges])]
+    nspans = (lengths // max_span_length_km).astype(np.int32) + 1
+    thr = thresholds_db if thresholds_db is not None else [0.5 * (a + b) for a, b in TABLE_THRESHOLDS_DB]
+    return {
+        "launch_power_density_w_hz": 1e-3 * 10 ** (launch_power_dbm_per_50ghz / 10.0) / 50e9,
+        "frequency_start_hz": float(frequency_start_hz),
+        "slot_width_hz": float(channel_width) * 1e9,
+        "attenuation_normalized": attenuation_db_km / (2 * 10 * np.log10(np.e) * 1e3),
+        "noise_figure": 10 ** (noise_figure_db / 10.0),
+        "link_num_spans": nspans,
+        "link_span_length_km": lengths / nspans,
+        "thresholds_db": np.asarray(sorted(thr), np.float64),
+    }
+
+
+RMSA_GN_GATE_SCALARS = ("launch_power_density_w_hz", "frequency_start_hz", "slot_width_hz", "attenuation_normalized", "noise_figure")
+
+
+def check_rmsa_gn_gate(gate, topology, step_kernel="auto"):
+    """The rules of ``orlg_set_gn_gate`` as ``ValueError``s, before the library is loaded: returns the gate as a dict of floats
+    and contiguous arrays."""
+    from .topology import FrozenTopology
+    if step_kernel == "group":
+        raise ValueError("gn_gate: the admission check is served by the wave-per-environment kernel, not by step_kernel='group'")
+    t = FrozenTopology.from_graph(topology)
+    g = {}
+    for name in RMSA_GN_GATE_SCALARS:
+        v = float(gate[name])
+        if not np.isfinite(v) or not v > 0:
+            raise ValueError(f"gn_gate: {name} must be finite and positive, got {v}")
+        g[name] = v
+    g["link_num_spans"] = ns = np.ascontiguousarray(gate["link_num_spans"], np.int32)
+    g["link_span_length_km"] = sl = np.ascontiguousarray(gate["link_span_length_km"], np.float64)
+    g["thresholds_db"] = thr = np.ascontiguousarray(gate["thresholds_db"], np.float64)
+    if ns.shape != (t.num_links,) or sl.shape != (t.num_links,):
+        raise ValueError(f"gn_gate: link_num_spans / link_span_length_km must have shape ({t.num_links},), got {ns.shape} / {sl.shape}")
+    if (ns < 1).any() or not np.isfinite(sl).all() or (sl <= 0).any():
+        raise ValueError("gn_gate: link_num_spans must be >= 1 and link_span_length_km finite and positive")
+    if thr.ndim != 1 or thr.size < 1 or not np.isfinite(thr).all():
+        raise ValueError("gn_gate: thresholds_db must be a non-empty one-dimensional array of finite values")
+    se_max = int(np.max(t.path_se))
+    if se_max > thr.size:
+        raise ValueError(f"gn_gate: a path has spectral efficiency {se_max}, thresholds_db has {thr.size} entries")
+    return g

@@ -1,0 +1,172 @@
+"""The CPU "gated oracle" of the GN-model admission check of the slot-based environments (``include/orlg.h``
+``orlg_rmsa_gn_gate``): the oracle environment stepped one request at a time, with the check restated on the host
+from a shadow list of the running services and evaluated by the oracle's ``calculate_osnr`` (``oracle.gn_osnr``).  Helper module
+of ``test_rmsa_gn_gate_args.py`` and ``test_gpu_rmsa_gn_gate.py``; nothing here touches a GPU.
+
+Per step: read the pending request and the clock; drop the shadow services with ``release <= now``; take the proposal; build the
+one-check batch (interferers per path link, provision order); evaluate it; ``step(p, s)`` if admitted, else ``step(K, S)``; on
+``done`` ``reset(only_episode_counters=True)``.  The shadow holds (release time, link set, centre, bandwidth, SE) of every
+admitted service.
+"""
+import contextlib
+import ctypes as C
+import functools
+
+import numpy as np
+
+import oracle as orc
+from conftest import load_topology, oracle_env_from_kwargs
+
+HOLDING_TIME = 25
+GATE_KWARGS = dict(launch_power_dbm_per_50ghz=6.0)   # (at the default 0 dBm the gate rejects nothing on these networks)
+
+# the cases of the issue: 600 steps each
+CASES = {
+    "nsfnet_s320_l50_sapff": dict(topology="nsfnet_chen_5-paths_6-modulations", S=320, load=50, seed=10, policy="sap_ff"),
+    "nsfnet_s320_l150_sapff": dict(topology="nsfnet_chen_5-paths_6-modulations", S=320, load=150, seed=11, policy="sap_ff"),
+    "nsfnet_s320_l150_llpff": dict(topology="nsfnet_chen_5-paths_6-modulations", S=320, load=150, seed=12, policy="llp_ff"),
+    "nsfnet_s100_l20_spff": dict(topology="nsfnet_chen_5-paths_6-modulations", S=100, load=20, seed=13, policy="sp_ff"),
+    "jpn12_s320_l150_sapff": dict(topology="jpn12_5-paths_6-modulations", S=320, load=150, seed=3, policy="sap_ff"),
+}
+N_STEPS = 600
+EPISODE_LENGTH = 200
+
+
+def case_kwargs(case, **over):
+    """BatchedRMSAEnv / oracle keyword arguments of a case (without the topology)."""
+    c = CASES[case] if isinstance(case, str) else case
+    return dict(dict(num_spectrum_resources=c["S"], load=c["load"], mean_service_holding_time=HOLDING_TIME,
+                     episode_length=EPISODE_LENGTH, seed=c["seed"]), **over)
+
+
+def case_gate(topo, **over):
+    from optical_rl_gym_amd import rmsa_gn_gate_parameters
+    return rmsa_gn_gate_parameters(topo, **dict(GATE_KWARGS, **over))
+
+
+@contextlib.contextmanager
+def device_log_in_oracle():
+    """The oracle's expovariate with the library's host build of the device logarithm (a host function: no GPU needed)."""
+    from optical_rl_gym_amd import _lib
+    orc.set_log_fn(C.cast(_lib.load().orlg_host_log, C.c_void_p).value)
+    try:
+        yield
+    finally:
+        orc.set_log_fn(None)
+
+
+class GatedOracle:
+    """One oracle environment behind the gate."""
+
+    def __init__(self, topo, kw, gate, seed=None, j=1, reward_mode=0):
+        self.topo, self.gate = topo, gate
+        self.o = oracle_env_from_kwargs(topo, kw, seed=seed, j=j, reward_mode=reward_mode)
+        self.K, self.S, self.j = topo.k_paths, int(kw["num_spectrum_resources"]), j
+        self.shadow = []   # provision order: (release, frozenset of links, f, b, se)
+        self.checks = self.rejects = self.max_running = 0
+        self.closest = np.inf
+
+    def close(self):
+        self.o.close()
+
+    # ---- the check
+    def _path(self, p):
+        t, r = self.topo, self.o.request()
+        gid = int(t.pair_path_base[r.src * t.num_nodes + r.dst]) + p
+        links = [int(l) for l in t.path_links[t.path_link_off[gid]:t.path_link_off[gid + 1]]]
+        return links, int(t.path_se[gid])
+
+    def _window(self, s, n):
+        g = self.gate
+        b = n * g["slot_width_hz"]
+        return b, g["frequency_start_hz"] + (s + n / 2) * g["slot_width_hz"]
+
+    def gsnr(self, links, s, n):
+        """GSNR [dB] of a service on [s, s + n) of the path with `links`, against the shadow."""
+        g = self.gate
+        b, f = self._window(s, n)
+        span_off, svc_off, lengths, sb, sf, sse = [0], [0], [], [], [], []
+        for l in links:
+            ns = int(g["link_num_spans"][l])
+            lengths += [float(g["link_span_length_km"][l])] * ns
+            span_off.append(len(lengths))
+            for (_, ls, f_i, b_i, se_i) in self.shadow:
+                if l in ls:
+                    sb.append(b_i); sf.append(f_i); sse.append(se_i)
+            svc_off.append(len(sb))
+        n_sp = len(lengths)
+        batch = dict(check_link_off=[0, len(links)], link_span_off=span_off, link_svc_off=svc_off, bandwidth=[b],
+                     center_frequency=[f], launch_power=[g["launch_power_density_w_hz"] * b], span_length_km=lengths,
+                     span_attenuation=[g["attenuation_normalized"]] * n_sp, span_noise_figure=[g["noise_figure"]] * n_sp,
+                     svc_bandwidth=sb, svc_center_frequency=sf, svc_se=sse, svc_is_self=[0] * len(sb))
+        return float(orc.gn_osnr(batch)[0])
+
+    # ---- proposals
+    def propose(self, policy):
+        """(path, slot) the policy proposes for the pending request, (K, S) for a rejection."""
+        if policy.startswith("deeprmsa"):
+            return self.resolve_deeprmsa(self.o.policy(policy)[0])
+        return self.o.policy(policy)
+
+    def resolve_deeprmsa(self, action):
+        """(route, first slot of the block) of a DeepRMSA action, (K, S) where it is a rejection (deeprmsa_env.py:48-58)."""
+        if 0 <= action < self.K * self.j:
+            route, blk = divmod(int(action), self.j)
+            starts, _ = self.o.available_blocks(route)
+            if blk < len(starts):
+                return route, int(starts[blk])
+        return self.K, self.S
+
+    # ---- one step
+    def step(self, p, s):
+        """Returns dict(act_path, act_slot, accepted, done, gsnr (NaN = no check ran), request)."""
+        o = self.o
+        r, now = o.request(), o.current_time()
+        self.shadow = [e for e in self.shadow if not e[0] <= now]
+        self.max_running = max(self.max_running, len(self.shadow))
+        gsnr, admitted = np.nan, False
+        if 0 <= p < self.K and 0 <= s < self.S:
+            n = o.number_slots(p)
+            if o.is_path_free(p, s, n):
+                links, se = self._path(p)
+                gsnr = self.gsnr(links, s, n)
+                thr = float(self.gate["thresholds_db"][se - 1])
+                self.checks += 1
+                self.closest = min(self.closest, abs(gsnr - thr))
+                admitted = gsnr >= thr
+                if admitted:
+                    b, f = self._window(s, n)
+                    self.shadow.append((r.arrival_time + r.holding_time, frozenset(links), f, b, se))
+                else:
+                    self.rejects += 1
+        res = o.step(p, s) if admitted else o.step(self.K, self.S)
+        assert bool(res.accepted) == admitted
+        out = dict(act_path=p, act_slot=s, accepted=int(admitted), done=int(res.done), gsnr=gsnr, reward=res.reward,
+                   request=(r.service_id, r.src, r.dst, r.bit_rate))
+        if res.done:
+            o.reset(only_episode_counters=True)
+        return out
+
+    def run(self, policy, n_steps):
+        rows = [self.step(*self.propose(policy)) for _ in range(n_steps)]
+        return {k: np.array([row[k] for row in rows]) for k in rows[0]}
+
+
+@functools.lru_cache(maxsize=None)
+def run_case(case, seed=None, n_steps=N_STEPS, gate_items=()):
+    """The gated oracle of a case (seed: the case's own by default), run once per process and shared: (per-step arrays, final
+    state, figures).  The results are read-only by agreement."""
+    c = CASES[case]
+    topo = load_topology(c["topology"])
+    kw = case_kwargs(case)
+    with device_log_in_oracle():
+        go = GatedOracle(topo, kw, case_gate(topo, **dict(gate_items)), seed=seed)
+        tr = go.run(c["policy"], n_steps)
+    o = go.o
+    final = dict(available_slots=o.available_slots(), counters=o.counters(), num_running=o.num_running(),
+                 current_time=o.current_time())
+    figures = dict(checks=go.checks, rejects=go.rejects, max_running=go.max_running, closest=go.closest)
+    go.close()
+    for a in tr.values():
+        a.setflags(write=False)
+    return tr, final, figures
