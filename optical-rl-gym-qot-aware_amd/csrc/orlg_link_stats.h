@@ -15,7 +15,10 @@
 
 // numpy's float64 add.reduce order (pairwise_sum in numpy/core/src/umath/loops_utils.h.src: 8 running
 // accumulators, fixed combination tree, blocks of <= 128) so that np.mean(...) in the info dict is reproduced
-// bit for bit; n <= 255 here (one link per element).
+// bit for bit; n <= 255 here (one link per element).  The elements are summed in link-index order, the reference's list is in
+// the graph's edge order (rmsa_env.py:311-322, topology.edges()): bit for bit when the link list is in graph order
+// (FrozenTopology.links_in_graph_order; every shipped list is), within 2 E 2^-53 relative otherwise -- two orders of summing
+// the same E non-negative terms (tests/test_many_links.py).  The split (n > 128) runs from 129 links on: tests/test_gpu_many_links.py.
 DEV double np_pairwise_block(const double *a, int n) {
     if (n < 8) {
         double res = 0.;

@@ -189,6 +189,16 @@ class FrozenTopology:
         self.path_node_off = np.asarray(node_off, np.int32)
         self.path_nodes = np.asarray(node_ids, np.int32)
 
+    @property
+    def links_in_graph_order(self) -> bool:
+        """True when the link indices ascend along ``edges``, the order in which the reference's graph iterates its links
+        (``topology.edges()``).  The reference takes the per-step link averages (``avg_link_compactness``,
+        ``avg_link_utilization``) as ``np.mean`` over that iteration (``rmsa_env.py:311-322``); the kernels and the oracle sum in
+        link-index order.  True: the averages equal the reference's bit for bit.  False: the same E non-negative terms are summed
+        in another order, and the averages agree to ``2 * E * 2**-53`` relative; nothing else depends on the order."""
+        idx = [e[2] for e in self.edges]
+        return all(a < b for a, b in zip(idx, idx[1:]))
+
     def cut_adjacency(self):
         """Per path: the links adjacent to the path's nodes that are not path links, with weight 1 at the two end
         nodes and 2 at interior nodes -- ``calculate_r_cut(..., modified=True)`` (``phy_rmsa_env.py:1140-1193``)

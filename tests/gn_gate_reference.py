@@ -27,6 +27,11 @@ CASES = {
     "nsfnet_s320_l150_llpff": dict(topology="nsfnet_chen_5-paths_6-modulations", S=320, load=150, seed=12, policy="llp_ff"),
     "nsfnet_s100_l20_spff": dict(topology="nsfnet_chen_5-paths_6-modulations", S=100, load=20, seed=13, policy="sp_ff"),
     "jpn12_s320_l150_sapff": dict(topology="jpn12_5-paths_6-modulations", S=320, load=150, seed=3, policy="sap_ff"),
+    # more than 64 links: a running service's link set is four mask words on the device, selected by link >> 6 (238 and 108
+    # links; the last case runs 8 words per link and candidates of up to 14 hops)
+    "ring34_s100_l60_sapff": dict(topology="ring34_3-paths_6-modulations", S=100, load=60, seed=7, policy="sap_ff"),
+    "ring34_s320_l300_llpff": dict(topology="ring34_3-paths_6-modulations", S=320, load=300, seed=7, policy="llp_ff"),
+    "ring36_s512_l500_sapff": dict(topology="ring36_3-paths_6-modulations", S=512, load=500, seed=7, policy="sap_ff"),
 }
 N_STEPS = 600
 EPISODE_LENGTH = 200
@@ -64,6 +69,7 @@ class GatedOracle:
         self.K, self.S, self.j = topo.k_paths, int(kw["num_spectrum_resources"]), j
         self.shadow = []   # provision order: (release, frozenset of links, f, b, se)
         self.checks = self.rejects = self.max_running = 0
+        self.link_ranges = 0   # most ranges of 64 link ids the shadow's services lay on at a check
         self.closest = np.inf
 
     def close(self):
@@ -132,6 +138,7 @@ class GatedOracle:
                 gsnr = self.gsnr(links, s, n)
                 thr = float(self.gate["thresholds_db"][se - 1])
                 self.checks += 1
+                self.link_ranges = max(self.link_ranges, len({l >> 6 for e in self.shadow for l in e[1]}))
                 self.closest = min(self.closest, abs(gsnr - thr))
                 admitted = gsnr >= thr
                 if admitted:
@@ -165,7 +172,8 @@ def run_case(case, seed=None, n_steps=N_STEPS, gate_items=()):
     o = go.o
     final = dict(available_slots=o.available_slots(), counters=o.counters(), num_running=o.num_running(),
                  current_time=o.current_time())
-    figures = dict(checks=go.checks, rejects=go.rejects, max_running=go.max_running, closest=go.closest)
+    figures = dict(checks=go.checks, rejects=go.rejects, max_running=go.max_running, closest=go.closest,
+                   link_ranges=go.link_ranges)
     go.close()
     for a in tr.values():
         a.setflags(write=False)

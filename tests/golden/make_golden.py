@@ -3,7 +3,7 @@
 
 Run in the build container only (needs /root/reference):
 
-    python tests/golden/make_golden.py [--only topologies|rmsa|deeprmsa|phy|osnr]
+    python tests/golden/make_golden.py [--only link_lists|topologies|rmsa|order|deeprmsa|phy|osnr]
 
 The reference (pure Python) is imported from /root/reference with a tiny in-memory
 ``gym`` stand-in (gym itself is not installed here; the reference only needs the base
@@ -12,7 +12,9 @@ reference is copied: the fixtures are *data* -- frozen topologies (node / link /
 tables read out of the shipped pickles) and per-step input/output vectors.
 
 Outputs
+  topology_txt/ring3?.txt     link lists of our own (circulant graphs of 238 and 108 links; --only link_lists, not in the default run)
   topologies/<name>.json      frozen topology tables (see optical_rl_gym_amd.topology)
+  order_*.npz                 RMSAEnv trace on a link list whose index order is not the graph's edge order
   rmsa_*.npz                  RMSAEnv per-step traces (requests, actions, counters, info floats)
   deeprmsa_*.npz              DeepRMSAEnv traces incl. the observation vector
   phy_*.npz, tables/*.npz     PhyRMSAEnv traces and the QoT tables (uint8 / float64)
@@ -95,14 +97,66 @@ def load_pickled_topology(spec):
     frozen tables).  The historic name of this helper is kept for the call sites below."""
     import contextlib
     import io
-    txt, k = spec
+    import tempfile
+    txt, k, shuffle_seed = (tuple(spec) + (None,))[:3]
     ex = os.path.join(REF, "examples")
     if ex not in sys.path:
         sys.path.insert(0, ex)
     import create_topology as ct   # main-guarded script: importing it only defines get_topology + the modulation table
     name = os.path.splitext(txt)[0].upper()   # the shipped pickles carry the upper-case name (e.g. "NSFNET_CHEN")
-    with contextlib.redirect_stdout(io.StringIO()):   # get_topology prints every path
-        return ct.get_topology(os.path.join(ex, "topologies", txt), name, ct.modulations, k)
+    path = os.path.join(ex, "topologies", txt)
+    if not os.path.exists(path):              # a link list of our own (gen_link_lists): the same generator reads it
+        path = os.path.join(HERE, "topology_txt", txt)
+    with contextlib.ExitStack() as stack:
+        if shuffle_seed is not None:          # the same links, listed (= indexed) in another order than the graph iterates them
+            head, links = read_link_list(path)
+            perm = np.random.default_rng(shuffle_seed).permutation(len(links))
+            tmp = stack.enter_context(tempfile.TemporaryDirectory())
+            path, name = os.path.join(tmp, "shuffled.txt"), name + "_SHUFFLED"
+            write_link_list(path, head, [links[i] for i in perm])
+        stack.enter_context(contextlib.redirect_stdout(io.StringIO()))   # get_topology prints every path
+        return ct.get_topology(path, name, ct.modulations, k)
+
+
+# --------------------------------------------------------------------------- link lists of our own
+def circulant(N, jumps, seed=7):
+    """Links (a, b, km) of the circulant graph C_N(jumps), nodes 1..N, sorted by (a, b) with a < b: a graph built from the list
+    iterates its edges in the order of the list, so link index order == graph order (the shipped lists have that property too)."""
+    rng = np.random.default_rng(seed)
+    e = []
+    for j in jumps:
+        for a in range(N):
+            e.append((a + 1, (a + j) % N + 1, int(rng.integers(60 * j, 400 * j))))
+    return sorted((min(a, b), max(a, b), l) for a, b, l in e)
+
+
+LINK_LISTS = {   # file -> (nodes, jumps): topologies of more than 64 (ring36) and more than 128 (ring34) links
+    "ring34.txt": (34, (1, 2, 3, 4, 5, 6, 7)),   # 238 links
+    "ring36.txt": (36, (1, 2, 3)),               # 108 links
+}
+
+
+def read_link_list(path):
+    with open(path) as f:
+        rows = [ln.split() for ln in f if not ln.startswith("#") and ln.strip()]
+    return int(rows[0][0]), [tuple(int(x) for x in r) for r in rows[2:]]
+
+
+def write_link_list(path, num_nodes, links, comment=None):
+    with open(path, "w") as f:
+        if comment:
+            f.write("# " + comment + "\n")
+        f.write(f"{num_nodes}\n{len(links)}\n")
+        for a, b, l in links:
+            f.write(f"{a} {b} {l}\n")
+
+
+def gen_link_lists():
+    for fname, (N, jumps) in LINK_LISTS.items():
+        links = circulant(N, jumps)
+        write_link_list(os.path.join(HERE, "topology_txt", fname), N, links,
+                        f"circulant C_{N}{tuple(jumps)}, lengths default_rng(7); make_golden.py --only link_lists")
+        print("link list", fname, N, "nodes", len(links), "links")
 
 
 # --------------------------------------------------------------------------- topologies
@@ -112,6 +166,10 @@ TOPOLOGIES = {   # fixture name -> (link-list file, k shortest paths)
     "jpn12_3-paths_6-modulations": ("jpn12.txt", 3),
     "jpn12_5-paths_6-modulations": ("jpn12.txt", 5),
     "spn_3-paths_6-modulations": ("spn.txt", 3),
+    "ring34_3-paths_6-modulations": ("ring34.txt", 3),
+    "ring36_3-paths_6-modulations": ("ring36.txt", 3),
+    # ring34 with its link list permuted by default_rng(7).permutation: index order != graph order (order_ring34_shuffled.npz)
+    "ring34_shuffled_3-paths_6-modulations": ("ring34.txt", 3, 7),
 }
 
 
@@ -151,9 +209,11 @@ def freeze_topology(topo):
     }
 
 
-def gen_topologies():
+def gen_topologies(only_case=None):
     os.makedirs(os.path.join(HERE, "topologies"), exist_ok=True)
     for name, fname in TOPOLOGIES.items():
+        if only_case is not None and name != only_case:
+            continue
         fz = freeze_topology(load_pickled_topology(fname))
         with open(os.path.join(HERE, "topologies", name + ".json"), "w") as f:
             json.dump(fz, f, separators=(",", ":"))
@@ -261,6 +321,8 @@ RMSA_BASE = dict(num_spectrum_resources=320, load=50, mean_service_holding_time=
 DEEPRMSA_NODE_PROBS = [0.01801802, 0.04004004, 0.05305305, 0.01901902, 0.04504505, 0.02402402, 0.06706707,
                        0.08908909, 0.13813814, 0.12212212, 0.07607608, 0.12012012, 0.01901902, 0.16916917]
 
+RING = dict(episode_length=200)
+
 RMSA_CASES = [
     # name, topology, env kwargs override, policy, steps, reset_on_done
     ("rmsa_nsfnet_s10_sapff", "nsfnet_chen_5-paths_6-modulations", dict(seed=10), "sap_ff", 3000, False),
@@ -286,6 +348,20 @@ RMSA_CASES = [
      "llp_ff", 1000, False),
     ("rmsa_spn_s2_sapff", "spn_3-paths_6-modulations", dict(seed=2, load=400, num_spectrum_resources=64),
      "sap_ff", 800, False),
+    # more than 64 / more than 128 links (our own link lists, LINK_LISTS): both branches of numpy's pairwise mean
+    ("rmsa_ring34_s5_sapff", "ring34_3-paths_6-modulations", dict(RING, seed=5, load=60, num_spectrum_resources=100),
+     "sap_ff", 600, True),
+    ("rmsa_ring34_s6_llpff", "ring34_3-paths_6-modulations", dict(RING, seed=6, load=300), "llp_ff", 600, True),
+    ("rmsa_ring36_s5_sapff", "ring36_3-paths_6-modulations", dict(RING, seed=5, load=60, num_spectrum_resources=100),
+     "sap_ff", 600, True),
+    ("rmsa_ring36_s6_llpff", "ring36_3-paths_6-modulations", dict(RING, seed=6, load=300), "llp_ff", 600, True),
+]
+
+# the same links indexed in another order than the graph iterates them: NOT an rmsa_* case (the two per-step link averages
+# differ from the oracle's in the last bits, tests/test_many_links.py)
+ORDER_CASES = [
+    ("order_ring34_shuffled", "ring34_shuffled_3-paths_6-modulations",
+     dict(RING, seed=5, load=60, num_spectrum_resources=100), "sap_ff", 300, True),
 ]
 
 
@@ -296,8 +372,10 @@ def _jsonable(d):
     return out
 
 
-def gen_rmsa():
-    for name, tname, over, policy, steps, reset in RMSA_CASES:
+def gen_rmsa(cases=None, only_case=None):
+    for name, tname, over, policy, steps, reset in (RMSA_CASES if cases is None else cases):
+        if only_case is not None and name != only_case:
+            continue
         kw = dict(RMSA_BASE)
         kw.update(over)
         topo = load_pickled_topology(TOPOLOGIES[tname])
@@ -309,6 +387,10 @@ def gen_rmsa():
         np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
         print(name, "accepted", int(out["services_accepted"][-1]), "/", int(out["services_processed"][-1]),
               "compactness", out["network_compactness"][-1])
+
+
+def gen_order():
+    gen_rmsa(ORDER_CASES)
 
 
 # --------------------------------------------------------------------------- seed() in the middle of a run
@@ -739,16 +821,16 @@ def gen_osnr():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
-    ap.add_argument("--case", default=None, help="with --only phy: one PHY_CASES entry")
+    ap.add_argument("--case", default=None, help="with --only phy | rmsa | topologies: one entry of that table")
     args = ap.parse_args()
     install_gym_stub()
     import optical_rl_gym  # noqa: F401  (registers env ids)
 
-    todo = [args.only] if args.only else ["topologies", "rmsa", "wrappers", "seed", "bookkeeping", "deeprmsa", "phy", "osnr"]
+    todo = [args.only] if args.only else ["topologies", "rmsa", "order", "wrappers", "seed", "bookkeeping", "deeprmsa", "phy", "osnr"]
     for what in todo:
         fn = globals().get("gen_" + what)
-        if what == "phy" and args.case:
-            gen_phy(only_case=args.case)
+        if what in ("phy", "rmsa", "topologies") and args.case:
+            fn(only_case=args.case)
             continue
         if fn is None:
             print("skip", what, "(generator not implemented yet)")

@@ -62,7 +62,11 @@ def test_refusals_before_the_library_loads(topo, monkeypatch):
 @pytest.mark.parametrize("case", list(ref.CASES))
 def test_case_is_meaningful(case):
     """Asserted from the gated oracle alone: the gate refuses between 2 % and 50 % of what it checks, and no GSNR lies within
-    1e-4 dB of its threshold (the device sums the interferers in another order: ~1e-15 relative)."""
+    1e-4 dB of its threshold (the device sums the interferers in another order: ~1e-15 relative).
+
+    The cases of more than 64 links, seed 7, as this test prints them (checks / refused / most running services / closest [dB]):
+    ring34_s100_l60_sapff 407 / 25 / 47 / 0.076; ring34_s320_l300_llpff 460 / 49 / 178 / 0.010;
+    ring36_s512_l500_sapff 347 / 62 / 158 / 0.014."""
     tr, final, fig = ref.run_case(case)
     print(case, fig)
     assert fig["checks"] > 0
@@ -70,6 +74,16 @@ def test_case_is_meaningful(case):
     assert fig["closest"] > 1e-4
     assert int(np.isfinite(tr["gsnr"]).sum()) == fig["checks"]
     assert int(tr["accepted"].sum()) == fig["checks"] - fig["rejects"]
+
+
+def test_ring34_cases_hold_services_on_every_range_of_64_links():
+    """Above 64 links the device keeps a running service's link set in four mask words and selects one by link >> 6: in each
+    ring34 case some check sees running services on links of [0, 64), [64, 128), [128, 192) and [192, 238) at once (ring36, 108
+    links: both of its ranges).  Without that the words beyond the first are not exercised."""
+    for case, c in ref.CASES.items():
+        if c["topology"].startswith("ring"):
+            E = load_topology(c["topology"]).num_links
+            assert E > 64 and ref.run_case(case)[2]["link_ranges"] == (E + 63) // 64, case
 
 
 def test_cases_reach_the_second_chunk_of_lanes():
