@@ -8,14 +8,13 @@ one-check batch (interferers per path link, provision order); evaluate it; ``ste
 ``done`` ``reset(only_episode_counters=True)``.  The shadow holds (release time, link set, centre, bandwidth, SE) of every
 admitted service.
 """
-import contextlib
-import ctypes as C
 import functools
 
 import numpy as np
 
 import oracle as orc
 from conftest import load_topology, oracle_env_from_kwargs
+from gpu_support import device_log_in_oracle
 
 HOLDING_TIME = 25
 GATE_KWARGS = dict(launch_power_dbm_per_50ghz=6.0)   # (at the default 0 dBm the gate rejects nothing on these networks)
@@ -47,17 +46,6 @@ def case_kwargs(case, **over):
 def case_gate(topo, **over):
     from optical_rl_gym_amd import rmsa_gn_gate_parameters
     return rmsa_gn_gate_parameters(topo, **dict(GATE_KWARGS, **over))
-
-
-@contextlib.contextmanager
-def device_log_in_oracle():
-    """The oracle's expovariate with the library's host build of the device logarithm (a host function: no GPU needed)."""
-    from optical_rl_gym_amd import _lib
-    orc.set_log_fn(C.cast(_lib.load().orlg_host_log, C.c_void_p).value)
-    try:
-        yield
-    finally:
-        orc.set_log_fn(None)
 
 
 class GatedOracle:

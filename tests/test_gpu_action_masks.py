@@ -12,7 +12,7 @@ import pytest
 
 from conftest import (DEEPRMSA_NODE_PROBS, deeprmsa_to_rmsa_kwargs, load_golden, load_phy_tables, load_topology,
                       oracle_env_from_kwargs, phy_oracle_from_kwargs)
-from test_gpu_rmsa import device_log_in_oracle  # noqa: F401  (fixture)
+from gpu_support import check_against_oracles, device_log_fixture, phy_env, unpack  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -20,43 +20,6 @@ NSFNET = "nsfnet_chen_5-paths_6-modulations"
 RMSA_NSFNET_320 = dict(num_spectrum_resources=320, load=50, mean_service_holding_time=25, episode_length=1000, seed=10)
 CONFIG4 = dict(mean_service_holding_time=7.5, mean_service_inter_arrival_time=1.0 / 12.0, num_spectrum_resources=320,
                node_request_probabilities=DEEPRMSA_NODE_PROBS, episode_length=50)
-
-
-def unpack(words, n):
-    """[..., W] uint64 -> [..., n] uint8, bit s of word w = element 64 w + s"""
-    return np.unpackbits(np.ascontiguousarray(words).view(np.uint8), axis=-1, bitorder="little")[..., :n]
-
-
-def expected_masks(o, K, J, S, reject):
-    """The three masks of one oracle environment, from the reference's own queries."""
-    deep = np.zeros(K * J + reject, np.uint8)
-    ff = np.zeros(K + reject, np.uint8)
-    slots = np.zeros((K, S), np.uint8)
-    for p in range(K):
-        n = o.number_slots(p)
-        starts, _ = o.available_blocks(p)
-        for b in range(J):
-            deep[p * J + b] = b < len(starts)                                   # deeprmsa_env.py:52-54
-        slots[p] = [o.is_path_free(p, s, n) for s in range(S)]                 # rmsa_env.py:233-260
-        ff[p] = any(slots[p, s] for s in range(0, S - n))                      # rmsa_env.py:974-1008, the bound exclusive
-    if reject:
-        deep[K * J] = ff[K] = 1
-    return deep, ff, slots
-
-
-def check_against_oracles(env, oracles, where):
-    K, J, S, r = env.k_paths, env.j, env.num_spectrum_resources, env.reject_action
-    deep, ff, words = env.action_masks("deeprmsa"), env.action_masks("path_ff"), env.action_masks("slots")
-    assert deep.shape == (len(oracles), K * J + r) and ff.shape == (len(oracles), K + r)
-    assert words.shape == (len(oracles), K, env.words_per_link) and words.dtype == np.uint64
-    bits = unpack(words, 64 * env.words_per_link)
-    assert not bits[..., S:].any(), where                                        # bits at and beyond S are 0
-    for i, o in enumerate(oracles):
-        e_deep, e_ff, e_slots = expected_masks(o, K, J, S, r)
-        assert np.array_equal(deep[i], e_deep), (where, i, deep[i], e_deep)
-        assert np.array_equal(ff[i], e_ff), (where, i, ff[i], e_ff)
-        assert np.array_equal(bits[i, :, :S], e_slots), (where, i, np.nonzero(bits[i, :, :S] != e_slots))
-    return deep, ff, bits[..., :S]
 
 
 def _case(name):
@@ -328,13 +291,6 @@ def test_fused_equals_separate_b32768():
     assert r.returncode == 0 and "fused masks ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
-def _phy_env(topo, tables, kw, batch):
-    from optical_rl_gym_amd import BatchedPhyRMSAEnv
-    pairs, mod, gsnr = tables
-    kw = {k: v for k, v in kw.items() if k not in ("num_spectrum_resources", "bit_rate_selection")}
-    return BatchedPhyRMSAEnv(topo, batch, modulation_level=mod, connections_detail=pairs, gsnr=gsnr, **kw)
-
-
 def _expected_channel_bits(topo, av, src, dst):
     """AND over the links of each candidate path of (src, dst) of available_channels [E, C]"""
     base = int(topo.pair_path_base[src * topo.num_nodes + dst])
@@ -354,7 +310,7 @@ def test_phy_channel_masks_against_the_oracle(case, device_log_in_oracle):
     if "us14" in case:
         assert kw["load"] == 1400
     batch, C = 4, 268
-    env = _phy_env(topo, tables, kw, batch)
+    env = phy_env(topo, tables, kw, batch)
     assert env.num_channels == C
     oracles = [phy_oracle_from_kwargs(topo, tables, kw, seed=kw["seed"] + i) for i in range(batch)]
     lit = 0

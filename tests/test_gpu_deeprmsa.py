@@ -7,36 +7,24 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, deeprmsa_to_rmsa_kwargs, load_golden, load_topology, oracle_env_from_kwargs
-from test_gpu_rmsa import device_log_in_oracle  # noqa: F401  (fixture)
+from gpu_support import device_log_fixture, grid_edges, rmsa_env, step_kernel, write_topology  # noqa: F401
 
-pytestmark = pytest.mark.gpu
+# both step kernels carry the DeepRMSA policies (include/orlg.h ORLG_KERNEL_*): every test runs against each
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("step_kernel")]
 CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "deeprmsa_*.npz")))
 
 
-STEP_KERNEL = "auto"
-
-
-@pytest.fixture(autouse=True, params=["wave", "group"])
-def step_kernel(request):
-    """Both step kernels carry the DeepRMSA policies (include/orlg.h ORLG_KERNEL_*): every test runs against each."""
-    global STEP_KERNEL
-    STEP_KERNEL = request.param
-    yield request.param
-    STEP_KERNEL = "auto"
-
-
-def make_env(topo, meta_kw, batch):
+def make_env(topo, meta_kw, batch, kernel):
     from optical_rl_gym_amd import BatchedDeepRMSAEnv
-    kw = dict(meta_kw)
-    return BatchedDeepRMSAEnv(topo, batch, step_kernel=STEP_KERNEL, **kw)
+    return rmsa_env(topo, batch, kernel, cls=BatchedDeepRMSAEnv, **meta_kw)
 
 
 @pytest.mark.parametrize("case", CASES)
-def test_deeprmsa_golden(case, device_log_in_oracle):
+def test_deeprmsa_golden(case, device_log_in_oracle, step_kernel):
     z, meta = load_golden(case)
     topo = load_topology(meta["topology"])
     n, batch = min(meta["steps"], 500), 4
-    env = make_env(topo, meta["env_kwargs"], batch)
+    env = make_env(topo, meta["env_kwargs"], batch, step_kernel)
     kw, j = deeprmsa_to_rmsa_kwargs(meta["env_kwargs"])
     oracles = [oracle_env_from_kwargs(topo, kw, seed=kw["seed"] + i, j=j, reward_mode=1) for i in range(batch)]
     obs = env.observation()
@@ -73,17 +61,16 @@ def test_deeprmsa_golden(case, device_log_in_oracle):
     env.close()
 
 
-def test_deeprmsa_observation_batch_32768(device_log_in_oracle):
+def test_deeprmsa_observation_batch_32768(device_log_in_oracle, step_kernel):
     """SURVEY 8(d) config 4 / BASELINE configs[3] as written (B = 32 768, NSFNET S=320 j=1, holding 7.5, inter-arrival
     1/12, the DeepRMSA node request probabilities of the reference's tests/test_deeprmsa.py:30-47): observation build for the
     whole batch; spot checks against the oracle and structural properties for every env."""
     topo = load_topology("nsfnet_chen_5-paths_6-modulations")
     from conftest import DEEPRMSA_NODE_PROBS
-    from optical_rl_gym_amd import BatchedDeepRMSAEnv
     kw = dict(j=1, mean_service_holding_time=7.5, mean_service_inter_arrival_time=1.0 / 12.0,
               node_request_probabilities=DEEPRMSA_NODE_PROBS, num_spectrum_resources=320, episode_length=50, seed=100)
     B = 32768
-    env = BatchedDeepRMSAEnv(topo, B, step_kernel=STEP_KERNEL, **kw)
+    env = make_env(topo, kw, B, step_kernel)
     env.run("deeprmsa_sap_ff", 300, auto_reset=True)
     obs = env.observation()
     assert obs.shape == (B, 54)
@@ -110,19 +97,18 @@ def test_deeprmsa_observation_batch_32768(device_log_in_oracle):
 
 
 @pytest.mark.parametrize("slots,j", [(400, 2), (200, 3), (64, 1), (512, 2)])
-def test_deeprmsa_synthetic_shapes(tmp_path, slots, j, device_log_in_oracle):
+def test_deeprmsa_synthetic_shapes(tmp_path, slots, j, device_log_in_oracle, step_kernel):
     """Observation builder and block policies on shapes the golden traces do not have (seven words of slots on the eight-word
     layout, one word, j > 1 with few blocks): device vs oracle, observation and decisions bit for bit."""
     pytest.importorskip("networkx")
-    import test_gpu_edge_cases as ec
     from optical_rl_gym_amd.topology_io import topology_from_txt
     rng = np.random.default_rng(slots + j)
-    edges = ec._grid_edges(3, 3, rng)
-    topo = topology_from_txt(ec._write_topology(tmp_path, "grid9", 9, edges), "grid9", k_paths=3)
+    edges = grid_edges(3, 3, rng)
+    topo = topology_from_txt(write_topology(tmp_path, "grid9", 9, edges), "grid9", k_paths=3)
     meta_kw = dict(j=j, mean_service_holding_time=10.0, mean_service_inter_arrival_time=10.0 / (0.25 * slots),
                    num_spectrum_resources=slots, episode_length=40, seed=slots)
     batch = 3
-    env = make_env(topo, meta_kw, batch)
+    env = make_env(topo, meta_kw, batch, step_kernel)
     kw, jj = deeprmsa_to_rmsa_kwargs(meta_kw)
     oracles = [oracle_env_from_kwargs(topo, kw, seed=kw["seed"] + i, j=jj, reward_mode=1) for i in range(batch)]
     for t in range(120):
@@ -139,11 +125,11 @@ def test_deeprmsa_synthetic_shapes(tmp_path, slots, j, device_log_in_oracle):
     env.close()
 
 
-def test_deeprmsa_float32_observation_into_a_device_buffer():
+def test_deeprmsa_float32_observation_into_a_device_buffer(step_kernel):
     """orlg_deeprmsa_observation_f32 writing straight into a caller's device buffer (a torch tensor: the agent loop of
     bench.py) == the float64 observation rounded once.  In a child process: torch has to create its HIP context before the
     library does, and this test process has long initialised the library."""
-    if STEP_KERNEL != "wave":
+    if step_kernel != "wave":
         pytest.skip("the observation kernel is the same for both step kernels")
     import subprocess, sys, textwrap
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -4,8 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, load_phy_tables, load_topology
-from test_gpu_phy import make_env
-from test_gpu_rmsa import make_batched
+from gpu_support import phy_env, rmsa_env, same_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -13,7 +12,7 @@ pytestmark = pytest.mark.gpu
 def test_rmsa_queue_overflow_is_reported(nsfnet):
     from optical_rl_gym_amd import OrlgError
     kw = dict(num_spectrum_resources=320, load=150, mean_service_holding_time=25, episode_length=1000, seed=1)
-    env = make_batched(nsfnet, kw, 16, queue_capacity=64)   # well over 64 services in progress at this load
+    env = rmsa_env(nsfnet, 16, queue_capacity=64, **kw)   # well over 64 services in progress at this load
     env.run("sap_ff", 3000)
     with pytest.raises(OrlgError) as ei:
         env.reduce_counters()
@@ -27,7 +26,7 @@ def test_overflow_is_returned_by_step_and_synchronize(nsfnet, kernel):
     orlg_synchronize -- not only orlg_reduce_counters; read-back still works and a full reset clears the condition."""
     from optical_rl_gym_amd import OrlgError
     kw = dict(num_spectrum_resources=320, load=150, mean_service_holding_time=25, episode_length=1000, seed=1)
-    env = make_batched(nsfnet, kw, 16, queue_capacity=64, step_kernel=kernel)
+    env = rmsa_env(nsfnet, 16, kernel, queue_capacity=64, **kw)
     with pytest.raises(OrlgError) as ei:
         env.run("sap_ff", 3000, outputs=("accepted",))
     assert ei.value.code == -4
@@ -47,7 +46,7 @@ def test_load_state_recomputes_the_error_word(nsfnet):
     -- clears it, loading the checkpoint of an overflowed batch brings it back (include/orlg.h, orlg_load_state)."""
     from optical_rl_gym_amd import OrlgError
     kw = dict(num_spectrum_resources=320, load=150, mean_service_holding_time=25, episode_length=1000, seed=1)
-    env = make_batched(nsfnet, kw, 16, queue_capacity=64)
+    env = rmsa_env(nsfnet, 16, queue_capacity=64, **kw)
     env.run("sap_ff", 5)
     clean = env.save_state()
     with pytest.raises(OrlgError):
@@ -67,7 +66,7 @@ def test_load_state_recomputes_the_error_word(nsfnet):
 
 def test_wrong_action_arrays_are_refused(nsfnet):
     kw = dict(num_spectrum_resources=320, load=50, mean_service_holding_time=25, episode_length=1000, seed=1)
-    env = make_batched(nsfnet, kw, 8)
+    env = rmsa_env(nsfnet, 8, **kw)
     with pytest.raises(ValueError):
         env.run("external", 1, actions=np.zeros(8, np.int32))
     with pytest.raises(ValueError):
@@ -88,7 +87,7 @@ def test_group_kernel_overflow_and_lds_limit(nsfnet):
     environments do not fit the LDS is refused when that kernel is demanded (AUTO falls back to the wave-per-environment kernel)."""
     from optical_rl_gym_amd import OrlgError
     kw = dict(num_spectrum_resources=320, load=150, mean_service_holding_time=25, episode_length=1000, seed=1)
-    env = make_batched(nsfnet, kw, 16, queue_capacity=64, step_kernel="group")
+    env = rmsa_env(nsfnet, 16, "group", queue_capacity=64, **kw)
     env.run("sap_ff", 3000)
     with pytest.raises(OrlgError) as ei:
         env.reduce_counters()
@@ -96,9 +95,9 @@ def test_group_kernel_overflow_and_lds_limit(nsfnet):
     env.close()
     kw = dict(num_spectrum_resources=320, load=50, mean_service_holding_time=25, episode_length=1000, seed=1)
     with pytest.raises(OrlgError) as ei:
-        make_batched(nsfnet, kw, 8, queue_capacity=4096, step_kernel="group")
+        rmsa_env(nsfnet, 8, "group", queue_capacity=4096, **kw)
     assert ei.value.code == -1 and "LDS" in str(ei.value)
-    env = make_batched(nsfnet, kw, 8, queue_capacity=4096, step_kernel="auto")
+    env = rmsa_env(nsfnet, 8, "auto", queue_capacity=4096, **kw)
     env.run("sap_ff", 50)
     env.close()
 
@@ -109,9 +108,9 @@ def test_rmsa_limits_are_refused(nsfnet):
         kw = dict(num_spectrum_resources=320, load=50, mean_service_holding_time=25, seed=1)
         kw.update(bad)
         with pytest.raises((OrlgError, ZeroDivisionError, ValueError, AssertionError)):
-            make_batched(nsfnet, kw, 4).close()
+            rmsa_env(nsfnet, 4, **kw).close()
     with pytest.raises(OrlgError) as ei:
-        make_batched(nsfnet, dict(num_spectrum_resources=320, load=50, mean_service_holding_time=25, seed=1), 0)
+        rmsa_env(nsfnet, 0, num_spectrum_resources=320, load=50, mean_service_holding_time=25, seed=1)
     assert ei.value.code == -1
 
 
@@ -119,7 +118,7 @@ def test_phy_small_structures_overflow_is_reported():
     from optical_rl_gym_amd import OrlgError
     z, meta = load_golden("phy_us14_s10_sapff")
     topo, tables = load_topology(meta["topology"]), load_phy_tables(meta["tables"])
-    env = make_env(topo, tables, dict(meta["env_kwargs"], load=3000), 4, queue_capacity=256)
+    env = phy_env(topo, tables, dict(meta["env_kwargs"], load=3000), 4, queue_capacity=256)
     env.run("sapff", 1500, auto_reset=True)
     assert env.episode_stats()["queue_overflow"].max() != 0
     with pytest.raises(OrlgError) as ei:
@@ -137,7 +136,7 @@ def test_phy_level_zero_tables_are_refused():
     mod = mod.copy()
     mod[3, 100, 1] = 0
     with pytest.raises(OrlgError) as ei:
-        make_env(topo, (pairs, mod, gsnr), meta["env_kwargs"], 2)
+        phy_env(topo, (pairs, mod, gsnr), meta["env_kwargs"], 2)
     assert ei.value.code == -1 and "modulation level" in str(ei.value)
 
 
@@ -146,7 +145,7 @@ def test_phy_wrong_action_arrays_are_refused():
     BatchedRMSAEnv.run validates its actions -- a float or an out-of-range channel number is refused, not truncated or wrapped."""
     z, meta = load_golden("phy_us14_s10_sapff")
     topo, tables = load_topology(meta["topology"]), load_phy_tables(meta["tables"])
-    env = make_env(topo, tables, meta["env_kwargs"], 4)
+    env = phy_env(topo, tables, meta["env_kwargs"], 4)
     ch = np.full((4, 14), -1, np.int64)
     with pytest.raises(TypeError):
         env.run("external", 1, act_path=np.zeros(4, np.float64), act_channels=ch)
@@ -171,25 +170,19 @@ def _fifty_first_fit_steps(env, policy):
     return dict(env.counters(), occupancy=occ)
 
 
-def _same_state(a, b):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert np.array_equal(a[k], b[k]), k
-
-
 def test_rmsa_create_refused_after_the_handle_exists(nsfnet):
     """A queue_capacity the LDS cannot hold is refused after the handle, its stream and its error word exist: code -1 with the
     message, and the next create of the same shape steps as a handle that had no refusal before it."""
     from optical_rl_gym_amd import OrlgError
     kw = dict(num_spectrum_resources=320, load=50, mean_service_holding_time=25, episode_length=1000, seed=1)
-    env = make_batched(nsfnet, kw, 4)
+    env = rmsa_env(nsfnet, 4, **kw)
     want = _fifty_first_fit_steps(env, "sap_ff")
     env.close()
     with pytest.raises(OrlgError) as ei:
-        make_batched(nsfnet, kw, 4, queue_capacity=5000)
+        rmsa_env(nsfnet, 4, queue_capacity=5000, **kw)
     assert ei.value.code == -1 and "queue_capacity 5008 too large for LDS (max 4096)" in str(ei.value)
-    env = make_batched(nsfnet, kw, 4)
-    _same_state(_fifty_first_fit_steps(env, "sap_ff"), want)
+    env = rmsa_env(nsfnet, 4, **kw)
+    same_bytes(_fifty_first_fit_steps(env, "sap_ff"), want)
     env.close()
 
 
@@ -200,12 +193,12 @@ def test_phy_create_refused_after_the_handle_exists(bad, message):
     from optical_rl_gym_amd import OrlgError
     topo, tables = load_topology("us14_3-paths_6-modulations"), load_phy_tables("us14_k3")
     kw = dict(episode_length=200, load=1400, mean_service_holding_time=25, seed=1)
-    env = make_env(topo, tables, kw, 4)
+    env = phy_env(topo, tables, kw, 4)
     want = _fifty_first_fit_steps(env, "sapff")
     env.close()
     with pytest.raises(OrlgError) as ei:
-        make_env(topo, tables, kw, 4, **bad)
+        phy_env(topo, tables, kw, 4, **bad)
     assert ei.value.code == -1 and message in str(ei.value)
-    env = make_env(topo, tables, kw, 4)
-    _same_state(_fifty_first_fit_steps(env, "sapff"), want)
+    env = phy_env(topo, tables, kw, 4)
+    same_bytes(_fifty_first_fit_steps(env, "sapff"), want)
     env.close()

@@ -9,20 +9,16 @@ launches of one step (the ring, and so the head's descriptor, in HBM) and launch
 B = 10: two rows of the last quad idle and must not touch the last environment's ring or head.  Every case also asserts, from
 its own outputs, that the events it is there for occurred (EVENTS below): they are replayed from `arrival`, `holding` and
 `accepted` exactly as the kernel's ring sees them (release time = arrival + holding, due when <= the next arrival)."""
-import ctypes as C
 import heapq
 import math
-import os
 
 import numpy as np
 import pytest
 
-from conftest import load_topology, oracle_env_from_kwargs
+from gpu_support import against_oracle, device_log_fixture, drive, external_actions, kernel_name, rmsa_env, same_bytes, topology  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-OUTS = ("act_path", "act_slot", "accepted", "reward", "done", "request", "arrival", "holding", "network_compactness",
-        "network_compactness_difference")
 B = 10
 SEED = 23
 NSF, US14 = "nsfnet_chen_5-paths_6-modulations", "us14_3-paths_6-modulations"
@@ -66,13 +62,6 @@ EXT_STEPS = 200
 
 def env_kwargs(S, load):
     return dict(num_spectrum_resources=S, load=load, mean_service_holding_time=25, episode_length=300, seed=SEED)
-
-
-def external_actions(topo, S, n, batch):
-    rng = np.random.default_rng(123)
-    a = np.stack([rng.integers(0, topo.k_paths + 1, (n, batch)), rng.integers(0, S + 1, (n, batch))], axis=-1).astype(np.int32)
-    a[::3, :, 1] //= 8   # a third of the steps aim low, where first-fit neighbours would be: windows at slot 0, occupied ones
-    return a
 
 
 def events_of(topo, S, cols):
@@ -130,88 +119,32 @@ def events_of_batch(topo, S, tr):
     return with_hops(topo, ev, hops)
 
 
-@pytest.fixture()
-def device_log_in_oracle():
-    import oracle as orc
-    from optical_rl_gym_amd import _lib
-    orc.set_log_fn(C.cast(_lib.load().orlg_host_log, C.c_void_p).value)
-    yield
-    orc.set_log_fn(None)
-
-
-def _drive(topo, kw, stats, kernel, policy, launches, env_vars, actions=None):
-    from optical_rl_gym_amd import BatchedRMSAEnv
-    old = {k: os.environ.get(k) for k in ("ORLG_GROUP_CHUNKS", "ORLG_NO_DEFER", "ORLG_NO_CHUNKS")}
-    for k in old:
-        os.environ.pop(k, None)
-    os.environ.update(env_vars)
-    try:
-        env = BatchedRMSAEnv(topo, B, step_kernel=kernel, stats_level=stats, **kw)
-        runs, names, t = [], set(), 0
-        for n in launches:
-            runs.append(env.run(policy, n, outputs=OUTS, auto_reset=True, actions=None if actions is None else actions[t]))
-            names.add(env.last_kernel().split(" ")[0])
-            t += n
-        res = dict(tr={k: np.concatenate([r[k] for r in runs]) for k in OUTS}, names=names, last=env.last_kernel(),
-                   occ=env.available_slots().copy(), state=env.save_state().copy(),
-                   counters={k: v.copy() for k, v in env.counters().items()},
-                   links={k: v.copy() for k, v in env.link_stats().items()})
-        env.close()
-        return res
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-
-
-def _hold(topo, S, load, policy, stats, launches, shows, chunks, actions=None):
-    kw = env_kwargs(S, load)
-    level = {"counters": 0, "network": 1, "full": 2}[stats]
-    W = (S + 63) // 64
-    W = 8 if W == 7 else W
-    grp = _drive(topo, kw, stats, "group", policy, launches, {"ORLG_GROUP_CHUNKS": chunks} if chunks else {}, actions)
+def _hold(name, S, load, policy, stats, launches, shows, chunks, actions=None):
+    topo, kw = topology(name), env_kwargs(S, load)
+    make = lambda kernel: lambda: rmsa_env(topo, B, kernel, stats_level=stats, **kw)
+    grp = drive(make("group"), launches, policy=policy, env_vars={"ORLG_GROUP_CHUNKS": chunks} if chunks else {}, actions=actions)
+    names = set(grp["kernels"])
     # the instantiation each launch shape is there for
     if launches == DEFER and stats == "full":
-        assert grp["names"] == {f"orlg_rmsa_group_kernel<{W},2,false,true>"}, grp["names"]
+        assert names == {kernel_name("group", S, stats, defer=True)}, names
     elif launches == DEFER or launches == EIGHT:
-        assert grp["names"] == {f"orlg_rmsa_group_kernel<{W},{level}>"}, grp["names"]
+        assert names == {kernel_name("group", S, stats)}, names
     else:
-        assert all(n.startswith(f"orlg_rmsa_group_kernel<{W},{level}") for n in grp["names"]), grp["names"]
+        assert all(n.startswith(kernel_name("group", S, stats)[:-1]) for n in names), names
         if S >= 320 and stats == "full":   # (the ring of a small environment fits the LDS in one-step launches too)
-            assert grp["names"] == {f"orlg_rmsa_group_kernel<{W},2,true>"}, grp["names"]
+            assert names == {kernel_name("group", S, stats, hbmq=True)}, names
     if chunks:
-        assert f"chunks={chunks}" in grp["last"], grp["last"]
-    wav = _drive(topo, kw, stats, "wave", policy, launches, {}, actions)
-    for k in OUTS:
-        assert np.array_equal(grp["tr"][k], wav["tr"][k]), k
-    assert np.array_equal(grp["state"], wav["state"])
-    for k in wav["counters"]:
-        assert np.array_equal(grp["counters"][k], wav["counters"][k]), k
-    for k in wav["links"]:
-        assert np.array_equal(grp["links"][k], wav["links"][k]), k
-    assert np.array_equal(grp["occ"], wav["occ"])
+        assert f"chunks={chunks}" in grp["said"][-1], grp["said"][-1]
+    wav = drive(make("wave"), launches, policy=policy, actions=actions)
+    same_bytes(grp["tr"], wav["tr"], "outputs")
+    same_bytes(grp["snap"], wav["snap"], "state")
     if actions is not None:   # in-range actions both accepted and turned down (occupied, or reaching past the last slot)
         inr = (actions[:, :, 0] < topo.k_paths) & (actions[:, :, 1] < S - 16)
         assert (grp["tr"]["accepted"][inr] != 0).any() and (grp["tr"]["accepted"][inr] == 0).any()
     ev = events_of_batch(topo, S, grp["tr"])
     assert set(shows) <= ev, (sorted(set(shows) - ev), sorted(ev))
-    n = sum(launches)
-    for i in (0, 5, B - 1):
-        o = oracle_env_from_kwargs(topo, kw, seed=SEED + i)
-        ot = o.run(policy, n, reset_on_done=True, actions=None if actions is None else np.ascontiguousarray(actions[:, i]))
-        # (the counters level keeps no network statistics: its network_compactness output stays 1.0 in both kernels)
-        for f in ("act_path", "act_slot", "accepted", "arrival", "holding") + (("network_compactness",) if level >= 1 else ()):
-            assert np.array_equal(grp["tr"][f][:, i], ot[f]), (f, i)
-        assert np.array_equal(grp["occ"][i], o.available_slots()), i
-        oc = o.counters()
-        for name in oc:
-            assert grp["counters"][name][i] == oc[name], (name, i)
-        if stats == "full":
-            ols = o.link_stats()
-            for name in ols:
-                assert np.array_equal(grp["links"][name][i], ols[name]), (name, i)
-        o.close()
+    # (the counters level keeps no network statistics: its compactness outputs stay 1.0 / 0.0 in both kernels)
+    against_oracle(name, kw, grp, policy, sum(launches), (0, 5, B - 1), stats, actions=actions)
 
 
 def _id(case):
@@ -223,20 +156,20 @@ def _id(case):
 @pytest.mark.parametrize("case", CASES, ids=_id)
 def test_group_chain_vs_wave_kernel_and_oracle(case, device_log_in_oracle):
     name, S, load, policy, stats, launches, shows = case
-    _hold(load_topology(name), S, load, policy, stats, launches, shows, None)
+    _hold(name, S, load, policy, stats, launches, shows, None)
 
 
 @pytest.mark.parametrize("case", [c for c in CASES if c[5] == DEFER and c[4] == "full"], ids=_id)
 def test_group_chain_in_seven_chunks(case, device_log_in_oracle):
     name, S, load, policy, stats, launches, shows = case
-    _hold(load_topology(name), S, load, policy, stats, launches, shows, "7")
+    _hold(name, S, load, policy, stats, launches, shows, "7")
 
 
 @pytest.mark.parametrize("case", EXT_CASES, ids=lambda c: f"{c[0][:4]}-{c[1]}-{c[2]}-{c[3]}")
 def test_group_chain_external_actions(case, device_log_in_oracle):
     name, S, load, stats, shows = case
-    topo = load_topology(name)
+    topo = topology(name)
     actions = external_actions(topo, S, EXT_STEPS, B)
     # out-of-range paths and slots among the actions (_hold looks for in-range actions accepted and turned down)
     assert (actions[:, :, 0] == topo.k_paths).any() and (actions[:, :, 1] == S).any()
-    _hold(topo, S, load, "external", stats, (1,) * EXT_STEPS, shows, None, actions)
+    _hold(name, S, load, "external", stats, (1,) * EXT_STEPS, shows, None, actions)

@@ -1,5 +1,5 @@
 """Which kernel instantiation every host selection path launches (csrc/orlg_variants.h: a launch builds a key from its
-parameters, the key picks the kernel and words ``last_kernel()``).  The expected names are written out here; after each launch
+parameters, the key picks the kernel and words ``last_kernel()``).  The expected names are spelled by ``gpu_support.kernel_name``, which ``test_gpu_support.py`` holds to the written-out table; after each launch
 the first token of ``last_kernel()`` must be that name and ``services_accepted`` what the C oracle has after the same steps.
 
 RMSA: NSFNET with 320 slots, 8 environments; both step kernels, every statistics level, launches of 1, 8 and 20 steps (the
@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import DEFAULT_BIT_RATES, load_golden, load_phy_tables, load_topology, oracle_env_from_kwargs, phy_oracle_from_kwargs
-from test_gpu_rmsa import device_log_in_oracle  # noqa: F401
+from gpu_support import device_log_fixture, kernel_name, phy_env as make_phy, rmsa_env  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,39 +28,17 @@ KW = dict(num_spectrum_resources=320, mean_service_holding_time=25, episode_leng
 LOADS, SEEDS_PER_LOAD = (20.0, 200.0), 4   # the handle with per-environment traffic
 POLICIES = ("sp_ff", "llp_ff")
 
-# (kernel, policy class) -> handle kind -> statistics level -> names after launches of 1, 8 and 20 steps
-GROUP = {
-    "plain": {
-        "counters": ("orlg_rmsa_group_kernel<5,0,true>", "orlg_rmsa_group_kernel<5,0>", "orlg_rmsa_group_kernel<5,0>"),
-        "network": ("orlg_rmsa_group_kernel<5,1,true>", "orlg_rmsa_group_kernel<5,1>", "orlg_rmsa_group_kernel<5,1>"),
-        "full": ("orlg_rmsa_group_kernel<5,2,true>", "orlg_rmsa_group_kernel<5,2>", "orlg_rmsa_group_kernel<5,2,false,true>")},
-    "traffic": {
-        "counters": ("orlg_rmsa_group_kernel<5,0,true,false,true>", "orlg_rmsa_group_kernel<5,0,false,false,true>",
-                     "orlg_rmsa_group_kernel<5,0,false,false,true>"),
-        "network": ("orlg_rmsa_group_kernel<5,1,true,false,true>", "orlg_rmsa_group_kernel<5,1,false,false,true>",
-                    "orlg_rmsa_group_kernel<5,1,false,false,true>"),
-        "full": ("orlg_rmsa_group_kernel<5,2,true,false,true>", "orlg_rmsa_group_kernel<5,2,false,false,true>",
-                 "orlg_rmsa_group_kernel<5,2,false,true,true>")},
-    "trace": {
-        "counters": ("orlg_rmsa_group_kernel<5,0,true,false,false,true>", "orlg_rmsa_group_kernel<5,0,false,false,false,true>",
-                     "orlg_rmsa_group_kernel<5,0,false,false,false,true>"),
-        "network": ("orlg_rmsa_group_kernel<5,1,true,false,false,true>", "orlg_rmsa_group_kernel<5,1,false,false,false,true>",
-                    "orlg_rmsa_group_kernel<5,1,false,false,false,true>"),
-        "full": ("orlg_rmsa_group_kernel<5,2,true,false,false,true>", "orlg_rmsa_group_kernel<5,2,false,false,false,true>",
-                 "orlg_rmsa_group_kernel<5,2,false,true,false,true>")}}
-# the wave-per-environment kernels read traffic and trace at run time: one set of names for the three kinds of handle
-WAVE_FF = {"counters": ("orlg_rmsa_kernel_ff<5,0>", "orlg_rmsa_kernel_ff<5,0>", "orlg_rmsa_kernel_ff<5,0>"),
-           "network": ("orlg_rmsa_kernel_ff<5,1>", "orlg_rmsa_kernel_ff<5,1>", "orlg_rmsa_kernel_ff<5,1>"),
-           "full": ("orlg_rmsa_kernel_ff<5,2>", "orlg_rmsa_kernel_ff<5,2>", "orlg_rmsa_kernel_ff<5,2,true>")}
-WAVE = {"counters": ("orlg_rmsa_kernel<5,0>", "orlg_rmsa_kernel<5,0>", "orlg_rmsa_kernel<5,0>"),
-        "network": ("orlg_rmsa_kernel<5,1>", "orlg_rmsa_kernel<5,1>", "orlg_rmsa_kernel<5,1>"),
-        "full": ("orlg_rmsa_kernel<5,2>", "orlg_rmsa_kernel<5,2>", "orlg_rmsa_kernel<5,2,true>")}
 
 
 def expected_name(kernel, policy, kind, stats, launch):
+    """After launches of 1, 8 and 20 steps (launch 0, 1, 2).  The group kernel: the release queue in HBM for the one step, the
+    deferred link statistics for the 20 under full statistics; a handle with per-environment traffic or a trace has instantiations
+    of its own.  The wave-per-environment kernels read traffic and trace at run time: one set of names for the three kinds of
+    handle, the first-fit kernel for sp_ff, and the deferred link statistics for the 20 steps under full statistics."""
+    defer = launch == 2 and stats == "full"
     if kernel == "group":
-        return GROUP[kind][stats][launch]
-    return (WAVE_FF if policy == "sp_ff" else WAVE)[stats][launch]
+        return kernel_name("group", 320, stats, hbmq=launch == 0, defer=defer, traffic=kind == "traffic", trace=kind == "trace")
+    return kernel_name("wave", 320, stats, ff=policy == "sp_ff", defer=defer)
 
 
 def env_kwargs(kind, i):
@@ -96,18 +74,17 @@ def oracle_reference(topo, kind, policy):
 
 
 def make_handle(topo, kind, policy, kernel, stats):
-    from optical_rl_gym_amd import BatchedRMSAEnv, RequestTrace, make_sweep
-    extra = dict(step_kernel=kernel, stats_level=stats)
+    from optical_rl_gym_amd import RequestTrace, make_sweep
     if kind == "plain":
-        return BatchedRMSAEnv(topo, B, load=50, seed=10, **KW, **extra)
+        return rmsa_env(topo, B, kernel, stats_level=stats, load=50, seed=10, **KW)
     if kind == "traffic":
-        return make_sweep("rmsa", topo, loads=LOADS, seeds_per_load=SEEDS_PER_LOAD, seed=10, **KW, **extra)
+        return make_sweep("rmsa", topo, loads=LOADS, seeds_per_load=SEEDS_PER_LOAD, seed=10, step_kernel=kernel, stats_level=stats, **KW)
     # the oracle's own request streams of the plain handle (env-major [B][21]), replayed
     _, req = oracle_reference(topo, "plain", policy)
     trace = RequestTrace(req["arrival"], req["holding"], req["src"].astype(np.int32), req["dst"].astype(np.int32),
                          req["bit_rate"].astype(np.int32), batch_size=B, layout="env")
     kw = {k: v for k, v in KW.items() if k != "mean_service_holding_time"}
-    return BatchedRMSAEnv(topo, B, trace=trace, **kw, **extra)
+    return rmsa_env(topo, B, kernel, stats_level=stats, trace=trace, **kw)
 
 
 def test_the_oracle_counts_tell_the_cases_apart(nsfnet, device_log_in_oracle):
@@ -148,13 +125,6 @@ PHY_CASES = [   # (id, defragmentation, GN gate, external actions, expected name
     ("external-defrag", True, False, True, "orlg_phy_kernel<5,true,false,-1>"),
     ("external-gn", False, True, True, "orlg_phy_kernel<5,false,true,-1>"),
     ("external-defrag-gn", True, True, True, "orlg_phy_kernel<5,true,true,-1>")]
-
-
-def make_phy(topo, tables, kw, batch, **extra):
-    from optical_rl_gym_amd import BatchedPhyRMSAEnv
-    pairs, mod, gsnr = tables
-    kw = {k: v for k, v in kw.items() if k not in ("num_spectrum_resources", "allow_rejection")}
-    return BatchedPhyRMSAEnv(topo, batch, modulation_level=mod, connections_detail=pairs, gsnr=gsnr, **kw, **extra)
 
 
 @pytest.fixture(scope="module")

@@ -7,16 +7,13 @@ link ids of 128 and above read back from a byte, ``lint_stride`` 240 against 238
 reset path.  ``last_kernel()`` is asserted wherever a test is about one instantiation.  (The GN-model admission check above 64
 links: the ``ring3*`` cases of ``gn_gate_reference.CASES`` in ``test_gpu_rmsa_gn_gate.py``.)"""
 import ctypes as C
-import functools
-import os
 
 import numpy as np
 import pytest
 
-import gn_gate_reference as ref
-import test_group_plan as gp
-from conftest import load_topology, oracle_env_from_kwargs
-from test_gpu_action_masks import check_against_oracles
+import gpu_support as gs
+from conftest import oracle_env_from_kwargs
+from gpu_support import check_against_oracles, decisions_match, device_log_in_oracle, kernel_name, rmsa_env, snapshot, state_matches, tooling_env, topology
 
 pytestmark = pytest.mark.gpu
 
@@ -34,50 +31,23 @@ def _kw(S, load, seed=SEED):
 
 
 def _env(name, shape, kernel, **extra):
-    from optical_rl_gym_amd import BatchedRMSAEnv
-    return BatchedRMSAEnv(load_topology(name), B, step_kernel=kernel, **_kw(**shape), **extra)
+    return rmsa_env(name, B, kernel, **_kw(**shape), **extra)
 
 
 def _kernel(env):
     return env.last_kernel().split()[0]
 
 
-@functools.lru_cache(maxsize=None)
 def oracle_run(name, S, load, i, policy, launches):
-    """Environment i of the batch on the oracle, `launches` a tuple of step counts: (one trace per launch, the state after the
-    last).  Run once per process and shared; read-only by agreement."""
-    topo = load_topology(name)
-    with ref.device_log_in_oracle():
-        o = oracle_env_from_kwargs(topo, _kw(S, load), seed=SEED + i)
-        traces = [o.run(policy, n, reset_on_done=True) for n in launches]
-    final = dict(available_slots=o.available_slots(), counters=o.counters(), link_stats=o.link_stats(), graph_stats=o.graph_stats(),
-                 current_time=o.current_time(), num_running=o.num_running())
-    o.close()
-    return traces, final
+    return gs.oracle_run(name, tuple(sorted(_kw(S, load).items())), SEED + i, policy, launches)
 
 
 def _decisions_match(tr, i, want, what):
-    for name in DECISIONS:
-        assert np.array_equal(tr[name][:, i], want[name]), (what, i, name)
+    decisions_match(tr, i, want, DECISIONS, what)   # (these launches ask for neither arrival nor holding)
 
 
-def _read_state(env, link_stats=True):
-    st = dict(available_slots=env.available_slots(), counters=env.counters(), current_time=env.current_time(),
-              num_running=env.num_running())
-    if link_stats:
-        st.update(link_stats=env.link_stats(), graph_stats=env.graph_stats())
-    return st
-
-
-def _state_matches(st, i, final, what):
-    assert np.array_equal(st["available_slots"][i], final["available_slots"]), (what, i)
-    for name, v in final["counters"].items():
-        assert st["counters"][name][i] == v, (what, i, name)
-    assert st["current_time"][i] == final["current_time"] and st["num_running"][i] == final["num_running"], (what, i)
-    for group in ("link_stats", "graph_stats"):
-        for name, v in final[group].items() if group in st else ():
-            bad = np.flatnonzero(np.atleast_1d(st[group][name][i] != v))
-            assert bad.size == 0, (what, i, group, name, bad[:6])
+def _read_state(env):
+    return snapshot(env, save_state=False)
 
 
 # ---------------------------------------------------------------------------------------- the per-step link averages
@@ -89,7 +59,7 @@ def test_link_averages_are_exact(name, kernel):
     networks.  Asking for them selects the instantiations that keep the link statistics up to date in place."""
     env = _env(name, LIGHT, kernel)
     tr = env.run("sap_ff", 300, outputs=DECISIONS + LINK_OUTS, auto_reset=True)
-    assert _kernel(env) == ("orlg_rmsa_kernel_ff<2,2>" if kernel == "wave" else "orlg_rmsa_group_kernel<2,2>"), env.last_kernel()
+    assert _kernel(env) == kernel_name(kernel, 2, "full", ff=kernel == "wave"), env.last_kernel()
     st = _read_state(env)
     for i in range(B):
         (want,), final = oracle_run(name, LIGHT["S"], LIGHT["load"], i, "sap_ff", (300,))
@@ -98,7 +68,7 @@ def test_link_averages_are_exact(name, kernel):
             bad = np.flatnonzero(tr[f][:, i] != want[f])
             assert bad.size == 0, (f, i, bad[:4], tr[f][bad[:4], i], want[f][bad[:4]])
         assert len(np.unique(want["avg_link_utilization"])) > 150   # (it moves with every provision and release)
-        _state_matches(st, i, final, name)
+        state_matches(st, i, final, name)
     env.close()
 
 
@@ -123,30 +93,26 @@ def test_deferred_link_statistics_equal_the_ones_kept_in_place(kernel):
     inside the launch (in the first, 300 steps, a link reaches about 35: worked off at its end).  The same launches under
     ORLG_NO_DEFER on a second handle; both against the oracle, and byte for byte against each other."""
     launches = (300, 600)
-    deferred, plain = (("orlg_rmsa_kernel_ff<5,2,true>", "orlg_rmsa_kernel_ff<5,2>") if kernel == "wave"
-                       else ("orlg_rmsa_group_kernel<5,2,false,true>", "orlg_rmsa_group_kernel<5,2>"))
-    topo = load_topology(RING34)
+    deferred, plain = (kernel_name(kernel, 5, "full", ff=kernel == "wave", defer=d) for d in (True, False))
+    topo = topology(RING34)
     a = _env(RING34, HEAVY, kernel)
     for n in launches:
         a.run("sap_ff", n, auto_reset=True)
         assert _kernel(a) == deferred, a.last_kernel()
-    os.environ["ORLG_NO_DEFER"] = "1"
-    try:
+    with tooling_env(ORLG_NO_DEFER="1"):
         b = _env(RING34, HEAVY, kernel)
         for n in launches:
             b.run("sap_ff", n, auto_reset=True)
             assert _kernel(b) == plain, b.last_kernel()
         sb = b.save_state()
-    finally:
-        del os.environ["ORLG_NO_DEFER"]
     sa, sb_state = _read_state(a), _read_state(b)
     full = 0
     for i in range(B):
         (t1, t2), final = oracle_run(RING34, HEAVY["S"], HEAVY["load"], i, "sap_ff", launches)
         entries = _log_entries(topo, t2, t1["current_time"][-1])
         full += entries[:64].max() >= LLOG_FLUSH and entries[64:].max() >= LLOG_FLUSH
-        _state_matches(sa, i, final, "deferred")
-        _state_matches(sb_state, i, final, "in place")
+        state_matches(sa, i, final, "deferred")
+        state_matches(sb_state, i, final, "in place")
     assert full == B, full   # every environment replays inside the second launch, full logs in both passes of link_replay<64>
     assert a.save_state().tobytes() == sb.tobytes()
     a.close()
@@ -156,21 +122,16 @@ def test_deferred_link_statistics_equal_the_ones_kept_in_place(kernel):
 # ---------------------------------------------------------------------------------------- statistics levels, launches of one step
 def _group_plan(env, stats, n_steps):
     """(shape, layouts, kind) of a launch of the group kernel on this handle's shape: orlg_debug_layout into orlg_debug_group_plan"""
-    fields = gp._fields("ORLG_SHAPE_FIELDS")
+    fields = gs._fields("ORLG_SHAPE_FIELDS")
     out = (C.c_int32 * len(fields))()
     env.L.orlg_debug_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
     assert env.L.orlg_debug_layout(env.h, out, len(fields)) == len(fields)
     shape = dict(zip(fields, out))
     args = dict(NW=shape["NW"], E=shape["E"], Q=shape["Q"], lint_stride=shape["lint_stride"], stats_level=stats,
-                shared_bytes=shape["l_shared_bytes"], B=B, n_steps=n_steps, policy=gp.SAP, out_mask=gp.OUT_ACCEPTED, br_width=0,
+                shared_bytes=shape["l_shared_bytes"], B=B, n_steps=n_steps, policy=gs.SAP, out_mask=gs.OUT_ACCEPTED, br_width=0,
                 no_defer=0, no_chunks=0, no_lean=0, wpb=0, chunks=0, num_cu=256, resident=256)
-    n_out = 3 * len(gp.LAYOUT) + len(gp.PLAN)
-    vin, vout = (C.c_int32 * len(gp.IN))(*[args[f] for f in gp.IN]), (C.c_int32 * n_out)()
-    f = env.L.orlg_debug_group_plan
-    f.argtypes = [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32]
-    assert f(vin, len(gp.IN), vout, n_out) == n_out
-    layouts = {k: dict(zip(gp.LAYOUT, vout[j * len(gp.LAYOUT):(j + 1) * len(gp.LAYOUT)])) for j, k in enumerate(gp.KINDS)}
-    return shape, layouts, gp.KINDS[dict(zip(gp.PLAN, vout[3 * len(gp.LAYOUT):]))["kind"]]
+    layouts, p = gs.group_plan(args)
+    return shape, layouts, p["kind"]
 
 
 @pytest.mark.parametrize("kernel", ["wave", "group"])
@@ -189,24 +150,23 @@ def test_statistics_levels_and_launches_of_one_step(stats, kernel):
     for _ in range(300):
         parts.append(short.run("sap_ff", 1, outputs=outs, auto_reset=True))
     ts = {k: np.concatenate([p[k] for p in parts]) for k in outs}
+    assert _kernel(long_run) == kernel_name(kernel, 5, level, ff=kernel == "wave", defer=level == 2), long_run.last_kernel()
     if kernel == "wave":
-        assert _kernel(long_run) == "orlg_rmsa_kernel_ff<5,%d%s>" % (level, ",true" if level == 2 else ""), long_run.last_kernel()
-        assert _kernel(short) == "orlg_rmsa_kernel_ff<5,%d>" % level, short.last_kernel()
+        assert _kernel(short) == kernel_name("wave", 5, level, ff=True), short.last_kernel()
     else:
         shape, layouts, kind = _group_plan(short, level, 1)
         assert (shape["E"], shape["lint_stride"], shape["Q"], shape["NW"]) == (238, 240, 480, 1190)
         assert layouts["PLAIN"]["wpb_max"] >= 1 and (level < 2 or layouts["DEFER"]["wpb_max"] >= 1)   # it fits: nothing to skip
         assert kind == ("HBMQ" if level < 2 else "PLAIN")
-        assert _kernel(short) == "orlg_rmsa_group_kernel<5,%d%s>" % (level, ",true" if kind == "HBMQ" else ""), short.last_kernel()
-        assert _kernel(long_run) == "orlg_rmsa_group_kernel<5,%d%s>" % (level, ",false,true" if level == 2 else ""), long_run.last_kernel()
-    sl, ss = _read_state(long_run, level == 2), _read_state(short, level == 2)
+        assert _kernel(short) == kernel_name("group", 5, level, hbmq=kind == "HBMQ"), short.last_kernel()
+    sl, ss = _read_state(long_run), _read_state(short)
     for i in range(B):
         (want,), final = oracle_run(RING34, HEAVY["S"], HEAVY["load"], i, "sap_ff", (300,))
         for what, tr, st in (("300 steps", tl, sl), ("300 x 1 step", ts, ss)):
             _decisions_match(tr, i, want, (stats, what))
             if level >= 1:
                 assert np.array_equal(tr["network_compactness"][:, i], want["network_compactness"]), (stats, what, i)
-            _state_matches(st, i, final, (stats, what))
+            state_matches(st, i, final, (stats, what), link_stats=level == 2)
     assert long_run.save_state().tobytes() == short.save_state().tobytes()
     long_run.close()
     short.close()
@@ -232,8 +192,8 @@ def test_checkpoint_continues_alike(kernel):
     for i in range(B):
         (want,), final = oracle_run(RING34, LIGHT["S"], LIGHT["load"], i, "sap_ff", (300,))
         _decisions_match({k: np.concatenate([first[k], second[k]]) for k in DECISIONS}, i, want, "checkpoint")
-        _state_matches(sa, i, final, "original")
-        _state_matches(sb, i, final, "restored")
+        state_matches(sa, i, final, "original")
+        state_matches(sb, i, final, "restored")
     a.close()
     b.close()
 
@@ -244,9 +204,9 @@ def test_action_masks_over_links_of_every_range():
     candidate paths of the pending requests run over links of every range of 64 ids, 128 and above among them."""
     env = _env(RING34, LIGHT, "wave")
     env.run("sap_ff", 200, auto_reset=True)
-    topo = load_topology(RING34)
+    topo = topology(RING34)
     oracles, ranges = [], set()
-    with ref.device_log_in_oracle():
+    with device_log_in_oracle():
         for i in range(B):
             o = oracle_env_from_kwargs(topo, _kw(**LIGHT), seed=SEED + i)
             o.run("sap_ff", 200, reset_on_done=True, fields=[])
@@ -270,13 +230,10 @@ def test_group_kernel_chunks_carry_238_links_through_hbm():
     whole = _env(RING34, HEAVY, "group")
     tw = whole.run("sap_ff", 300, outputs=outs, auto_reset=True)
     assert whole.last_kernel().endswith("chunks=1"), whole.last_kernel()
-    os.environ["ORLG_GROUP_CHUNKS"] = "3"
-    try:
+    with tooling_env(ORLG_GROUP_CHUNKS="3"):
         cut = _env(RING34, HEAVY, "group")
         tc = cut.run("sap_ff", 300, outputs=outs, auto_reset=True)
-    finally:
-        del os.environ["ORLG_GROUP_CHUNKS"]
-    assert _kernel(cut) == _kernel(whole) == "orlg_rmsa_group_kernel<5,2,false,true>" and cut.last_kernel().endswith("chunks=3"), cut.last_kernel()
+    assert _kernel(cut) == _kernel(whole) == kernel_name("group", 5, "full", defer=True) and cut.last_kernel().endswith("chunks=3"), cut.last_kernel()
     for name in outs:
         assert tc[name].tobytes() == tw[name].tobytes(), name
     assert cut.save_state().tobytes() == whole.save_state().tobytes()
@@ -284,6 +241,6 @@ def test_group_kernel_chunks_carry_238_links_through_hbm():
     for i in range(B):
         (want,), final = oracle_run(RING34, HEAVY["S"], HEAVY["load"], i, "sap_ff", (300,))
         _decisions_match(tc, i, want, "chunks")
-        _state_matches(st, i, final, "chunks")
+        state_matches(st, i, final, "chunks")
     whole.close()
     cut.close()

@@ -40,7 +40,7 @@ def test_phy_batched_evaluate_matches_reference_episodes(tmp_path):
     import csv
     import optical_rl_gym_amd as pkg
     from conftest import load_phy_tables
-    from test_gpu_phy import make_env
+    from gpu_support import phy_env as make_env
     for case, policy in (("phy_us14_s10_bmfa", "bmfa"), ("phy_us14_s10_bmfa_defrag_cut", "bmfa")):
         z, meta = load_golden(case)
         topo, tables = load_topology(meta["topology"]), load_phy_tables(meta["tables"])

@@ -5,18 +5,11 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, load_phy_tables, load_topology, phy_oracle_from_kwargs
-from test_gpu_rmsa import device_log_in_oracle  # noqa: F401
+from gpu_support import device_log_fixture, phy_env, phy_matches_oracle, phy_matches_reference, snapshot  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 OUTS = ("act_path", "n_channels", "channels", "channels_used", "accepted", "done", "request", "arrival", "holding",
         "number_cuts_total", "rss_total_metric", "defrag_counters")
-
-
-def make_env(topo, tables, kw, batch, **extra):
-    from optical_rl_gym_amd import BatchedPhyRMSAEnv
-    pairs, mod, gsnr = tables
-    kw = {k: v for k, v in kw.items() if k not in ("num_spectrum_resources", "bit_rate_selection")}
-    return BatchedPhyRMSAEnv(topo, batch, modulation_level=mod, connections_detail=pairs, gsnr=gsnr, **kw, **extra)
 
 
 @pytest.mark.parametrize("case,nmax", [("phy_us14_s10_bmfa", 800), ("phy_jpn12_s3_bmfa", 500),
@@ -36,50 +29,19 @@ def test_phy_policy_vs_oracle_and_reference(case, nmax, device_log_in_oracle, ex
     tables = load_phy_tables(meta["tables"])
     kw = meta["env_kwargs"]
     n, batch = min(nmax, meta["steps"]), 4
-    env = make_env(topo, tables, kw, batch)
+    env = phy_env(topo, tables, kw, batch)
     assert env.grooming == kw.get("grooming", False)
     assert env.node_vectors == expect_node_vectors
     policy = meta["policy"]
     tr = env.run(policy, n, outputs=OUTS, auto_reset=True)
-    cnt, now, nrun, av, est = env.counters(), env.current_time(), env.num_running(), env.available_channels(), env.episode_stats()
+    snap = snapshot(env, save_state=False)
     for i in range(batch):
-        o = phy_oracle_from_kwargs(topo, tables, kw, seed=kw["seed"] + i)
-        ot = o.run(policy, n, reset_on_done=True)
-        assert np.array_equal(tr["act_path"][:, i], ot["act_path"]), i
-        assert np.array_equal(tr["n_channels"][:, i], ot["n_channels"]), i
-        assert np.array_equal(tr["channels"][:, i, :12].astype(np.int32), ot["channels"]), i
-        assert np.array_equal(tr["channels_used"][:, i, :12].astype(np.float64), ot["ch_used"]), i
-        assert np.array_equal(tr["accepted"][:, i], ot["accepted"]) and np.array_equal(tr["done"][:, i], ot["done"])
-        assert np.array_equal(tr["request"][:, i, 1], ot["src"]) and np.array_equal(tr["request"][:, i, 3], ot["bit_rate"])
-        for f in ("arrival", "holding", "number_cuts_total", "rss_total_metric"):
-            bad = np.nonzero(tr[f][:, i] != ot[f])[0]
-            assert bad.size == 0, (f, i, bad[:4], tr[f][bad[:4], i], ot[f][bad[:4]])
-        dc = tr["defrag_counters"][:, i].astype(np.int64)
-        assert np.array_equal(dc[:, 1], ot["num_moves_groom"]) and np.array_equal(dc[:, 2], ot["num_defrag_cycle"]), i
-        assert np.array_equal(dc[:, 0] / 2 + dc[:, 1], ot["num_moves"]), i
-        oc = o.counters()
-        for name in oc:
-            assert cnt[name][i] == oc[name], (name, i)
-        assert now[i] == o.current_time() and nrun[i] == o.num_running()
-        assert np.array_equal(av[i], o.available_channels())
+        ot = phy_matches_oracle(topo, tables, kw, env, tr, i, snap, policy, n, seed=kw["seed"] + i)
         # per-episode sums behind the info dict (the run ended right after an optional reset)
-        assert est["physical_services_accepted"][i] == ot["physical_paths"][-1] or ot["done"][-1]
-        assert est["queue_overflow"][i] == 0
-        assert env.channel_state(i) == o.channel_state(), i
-        o.close()
+        assert snap["episode_stats"]["physical_services_accepted"][i] == ot["physical_paths"][-1] or ot["done"][-1]
     # env 0 is the reference's own trace
-    assert np.array_equal(tr["act_path"][:, 0], z["act_path"][:n])
-    assert np.array_equal(tr["channels"][:, 0, :12], z["channels"][:n])
-    assert np.array_equal(tr["channels_used"][:, 0, :12].astype(np.float64), z["ch_used"][:n])
-    assert np.array_equal(tr["accepted"][:, 0], z["accepted"][:n])
-    np.testing.assert_allclose(tr["arrival"][:, 0], z["arrival"][:n], rtol=1e-12)
-    assert np.array_equal(tr["number_cuts_total"][:, 0], z["number_cuts_total"][:n])
-    assert np.array_equal(tr["rss_total_metric"][:, 0], z["rss_total_metric"][:n])
-    assert cnt["services_accepted"][0] == z["services_accepted"][n - 1]
-    if "num_moves" in z.files:
-        dc = tr["defrag_counters"][:, 0].astype(np.int64)
-        assert np.array_equal(dc[:, 0] / 2 + dc[:, 1], z["num_moves"][:n])
-        assert np.array_equal(dc[:, 1], z["num_moves_groom"][:n]) and np.array_equal(dc[:, 2], z["num_defrag_cycle"][:n])
+    phy_matches_reference(z, tr, 0, n)
+    assert snap["counters.services_accepted"][0] == z["services_accepted"][n - 1]
     env.close()
 
 
@@ -97,7 +59,7 @@ def test_phy_info_ratios_match_reference(device_log_in_oracle):
     """Step by step (one launch per step) the info-dict ratios equal the reference's."""
     z, meta = load_golden("phy_us14_s10_bmfa")
     topo, tables = load_topology(meta["topology"]), load_phy_tables(meta["tables"])
-    env = make_env(topo, tables, meta["env_kwargs"], 2)
+    env = phy_env(topo, tables, meta["env_kwargs"], 2)
     for t in range(260):
         r = env.run("bmfa", 1, outputs=("done",))
         info = env.info()
@@ -118,7 +80,7 @@ def test_phy_external_actions(device_log_in_oracle):
     z, meta = load_golden("phy_us14_s10_bmfa")
     topo, tables = load_topology(meta["topology"]), load_phy_tables(meta["tables"])
     kw = meta["env_kwargs"]
-    env = make_env(topo, tables, kw, 3)
+    env = phy_env(topo, tables, kw, 3)
     oracles = [phy_oracle_from_kwargs(topo, tables, kw, seed=kw["seed"] + i) for i in range(3)]
     rng = np.random.default_rng(0)
     for t in range(150):
@@ -158,7 +120,7 @@ def test_phy_external_actions_with_defragmentation(metric, device_log_in_oracle)
     topo, tables = load_topology("us14_3-paths_6-modulations"), load_phy_tables("us14_k3")
     kw = dict(load=1300, mean_service_holding_time=25, episode_length=90, seed=41, grooming=True, defrag_period=6, number_moves=5,
               metric=metric)
-    env = make_env(topo, tables, kw, 3)
+    env = phy_env(topo, tables, kw, 3)
     oracles = [phy_oracle_from_kwargs(topo, tables, kw, seed=41 + i) for i in range(3)]
     policy = "bmfa" if metric == "cut" else "bmfa_rss"
     for t in range(260):
@@ -195,7 +157,7 @@ def test_phy_external_virtual_layer_actions(device_log_in_oracle):
     z, meta = load_golden("phy_us14_s10_sapff")
     topo, tables = load_topology(meta["topology"]), load_phy_tables(meta["tables"])
     kw = meta["env_kwargs"]
-    env = make_env(topo, tables, kw, 2)
+    env = phy_env(topo, tables, kw, 2)
     oracles = [phy_oracle_from_kwargs(topo, tables, kw, seed=kw["seed"] + i) for i in range(2)]
     nvirt = 0
     for t in range(400):
@@ -232,7 +194,7 @@ def test_phy_batch_4096_properties(device_log_in_oracle):
     z, meta = load_golden("phy_us14_s10_bmfa")
     topo, tables = load_topology(meta["topology"]), load_phy_tables(meta["tables"])
     kw = dict(meta["env_kwargs"], seed=100)
-    env = make_env(topo, tables, kw, 4096)
+    env = phy_env(topo, tables, kw, 4096)
     tr = env.run("bmfa", 300, outputs=("accepted", "n_channels", "act_path", "channels", "number_cuts_total", "rss_total_metric"),
                  auto_reset=True)
     cnt = env.counters()
@@ -264,7 +226,7 @@ def test_phy_work_queue_more_envs_than_resident_waves(device_log_in_oracle):
     topo, tables = load_topology(meta["topology"]), load_phy_tables(meta["tables"])
     kw = dict(meta["env_kwargs"], seed=500, load=600)
     B = 9000
-    env = make_env(topo, tables, kw, B)
+    env = phy_env(topo, tables, kw, B)
     env.run("sapff", 80, auto_reset=True)
     for _ in range(3):
         env.run("sapff", 4, auto_reset=True)
@@ -297,7 +259,7 @@ def test_phy_five_paths_synthetic_tables(policy, device_log_in_oracle):
     tables = (pairs, mod, gsnr)
     kw = dict(load=700, mean_service_holding_time=25, episode_length=120, seed=9, grooming=True, defrag_period=8, number_moves=5,
               metric="rss" if policy == "bmfa_rss" else "cut")
-    env = make_env(topo, tables, kw, 3)
+    env = phy_env(topo, tables, kw, 3)
     tr = env.run(policy, 350, outputs=("act_path", "channels", "channels_used", "accepted", "number_cuts_total", "rss_total_metric",
                                        "defrag_counters"), auto_reset=True)
     av, cnt = env.available_channels(), env.counters()
@@ -329,7 +291,7 @@ def test_phy_every_policy_instantiation_vs_oracle(policy, defrag, device_log_in_
     kw = dict(load=1200, mean_service_holding_time=25, episode_length=150, seed=21, grooming=policy in ("bmfa", "bmfa_rss"))
     if defrag:
         kw.update(defrag_period=7, number_moves=6, metric=defrag)
-    env = make_env(topo, tables, kw, 3)
+    env = phy_env(topo, tables, kw, 3)
     outs = ("act_path", "channels", "channels_used", "accepted", "number_cuts_total", "rss_total_metric", "defrag_counters")
     parts = [env.run(policy, n, outputs=outs, auto_reset=True) for n in (130, 1, 200, 69)]
     tr = {k: np.concatenate([q[k] for q in parts]) for k in outs}
@@ -370,7 +332,7 @@ def test_gn_gate_in_the_step_vs_oracle(policy, launch_power_dbm, defrag, device_
     if defrag:   # the instantiation that carries both the defragmentation and the gate
         kw.update(defrag_period=10, number_moves=10, metric=defrag)
     n, batch = 700 if not defrag else 400, 4
-    env = make_env(topo, tables, kw, batch)
+    env = phy_env(topo, tables, kw, batch)
     # a handle without defrag_period runs the gate's own instantiation (it does not carry the defragmentation's registers)
     assert env.last_kernel().startswith("orlg_phy_kernel<5,true,true," if defrag else "orlg_phy_kernel<5,false,true,"), env.last_kernel()
     tr = env.run(policy, n, outputs=("act_path", "channels", "accepted", "gn_gsnr_db", "number_cuts_total"), auto_reset=True)
@@ -412,7 +374,7 @@ def test_gn_gate_batch_4096(device_log_in_oracle):
     gate = gn_gate_parameters(topo)
     kw = dict(load=1400, mean_service_holding_time=25, episode_length=200, seed=10, grooming=False, gn_gate=gate)
     n, batch = 320, 4096
-    env = make_env(topo, tables, kw, batch)
+    env = phy_env(topo, tables, kw, batch)
     tr = env.run("bmfa", n, outputs=("act_path", "channels", "accepted", "gn_gsnr_db", "number_cuts_total"), auto_reset=True)
     assert env.last_kernel().startswith("orlg_phy_kernel<5,false,true,"), env.last_kernel()
     cnt, av = env.counters(), env.available_channels()
@@ -449,7 +411,7 @@ def test_phy_reseed_between_launches_vs_oracle(device_log_in_oracle):
     with the defragmentation running, against the oracle's reseed()."""
     topo, tables = load_topology("us14_3-paths_6-modulations"), load_phy_tables("us14_k3")
     kw = dict(load=1400, mean_service_holding_time=25, episode_length=200, seed=10, grooming=True, defrag_period=10, number_moves=10)
-    env = make_env(topo, tables, kw, 4)
+    env = phy_env(topo, tables, kw, 4)
     outs = ("act_path", "channels", "accepted", "arrival", "request")
     parts = [env.run("bmfa", 130, outputs=outs, auto_reset=True)]
     env.reseed(901)
@@ -485,7 +447,7 @@ def test_phy_large_network_general_paths(policy, defrag, device_log_in_oracle):
     kw = dict(load=2500, mean_service_holding_time=25, episode_length=150, seed=4, grooming=policy != "sapff")
     if defrag:
         kw.update(defrag_period=9, number_moves=7, metric=defrag)
-    env = make_env(topo, tables, kw, 3)
+    env = phy_env(topo, tables, kw, 3)
     assert not env.node_vectors
     outs = ("act_path", "channels", "channels_used", "accepted", "number_cuts_total", "rss_total_metric", "defrag_counters")
     parts = [env.run(policy, k, outputs=outs, auto_reset=True) for k in (180, 2, 120)]
@@ -562,7 +524,7 @@ def replay_gate_checks(policy, n, batch=4):
     topo, tables = load_topology("us14_3-paths_6-modulations"), load_phy_tables("us14_k3")
     gate = gn_gate_parameters(topo)
     kw = dict(load=1400, mean_service_holding_time=25, episode_length=200, seed=10, grooming=False, gn_gate=gate)
-    env = make_env(topo, tables, kw, batch)
+    env = phy_env(topo, tables, kw, batch)
     tr = env.run(policy, n, outputs=("act_path", "channels", "accepted", "gn_gsnr_db"), auto_reset=True)
     assert env.last_kernel().startswith("orlg_phy_kernel<5,false,true,"), env.last_kernel()
     env.close()
@@ -645,7 +607,7 @@ def test_gn_gate_at_every_word_count(num_channels, split, words, load, n, policy
     kw = dict(load=load, mean_service_holding_time=25, episode_length=200, seed=10, grooming=False, gn_gate=gate,
               number_spectrum_channels=split[0], number_spectrum_channels_s_band=split[1])
     batch = 4
-    env = make_env(topo, tables, kw, batch)
+    env = phy_env(topo, tables, kw, batch)
     assert env.num_channels == num_channels and env.words_per_link == words
     tr = env.run(policy, n, outputs=("act_path", "channels", "accepted", "gn_gsnr_db", "number_cuts_total"), auto_reset=True)
     assert env.last_kernel().startswith(f"orlg_phy_kernel<{words},false,true,"), env.last_kernel()

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, load_phy_tables, load_topology
+from gpu_support import PHY_CONTINUOUS_OUTS as OUTS, phy_env as make_env, same_bytes, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -13,18 +14,8 @@ CASES = ["cont_us14_s20_sapff", "cont_us14_s21_bmff", "cont_us14_s22_sapbm", "co
          "cont_us14_s24_bmfa", "cont_us14_s25_bmfa_groom", "cont_us14_s26_bmfa_rss_groom",
          "cont_us14_s27_sapbm_100_600", "cont_us14_s28_faff_rss_100_600",
          "cont_us14_s29_sapff_100_600_load20000", "cont_jpn12_s30_bmff"]
-OUTS = ("act_path", "n_channels", "channels", "channels_used_f64", "channels_free_f64", "accepted", "done", "request",
-        "arrival", "holding", "number_cuts_total", "rss_total_metric")
 COUNTERS = ("services_processed", "services_accepted", "episode_services_processed", "episode_services_accepted",
             "bit_rate_requested", "bit_rate_provisioned")
-
-
-def make_env(topo, tables, kw, batch, seeds=None, **extra):
-    from optical_rl_gym_amd import BatchedPhyRMSAEnv
-    pairs, mod, gsnr = tables
-    kw = {k: v for k, v in kw.items() if k != "num_spectrum_resources"}
-    kw.update(extra)
-    return BatchedPhyRMSAEnv(topo, batch, modulation_level=mod, connections_detail=pairs, gsnr=gsnr, seeds=seeds, **kw)
 
 
 def channel_caps(topo, tables, tr, i):
@@ -44,13 +35,7 @@ def channel_caps(topo, tables, tr, i):
 
 def same_state(a, b, envs):
     """Two handles hold the same simulation (the saved state also carries never-written, uninitialised slots)."""
-    for get in ("counters", "current_time", "num_running", "available_channels", "requests"):
-        x, y = getattr(a, get)(), getattr(b, get)()
-        if isinstance(x, dict):
-            assert all(np.array_equal(x[k], y[k]) for k in x), get
-        else:
-            assert np.array_equal(x, y), get
-    assert np.array_equal(a.episode_stats(), b.episode_stats())
+    same_bytes(snapshot(a, save_state=False), snapshot(b, save_state=False), "state")
     for i in envs:
         assert a.channel_state(i) == b.channel_state(i), i
 
@@ -196,15 +181,13 @@ def test_phy_continuous_split_launches_and_checkpoint():
     t1 = a.run(policy, 300, outputs=OUTS, auto_reset=True)
     snap = a.save_state()
     t2 = a.run(policy, 300, outputs=OUTS, auto_reset=True)
-    for f in OUTS:
-        assert np.array_equal(np.concatenate([t1[f], t2[f]]), tw[f]), f
+    same_bytes({f: np.concatenate([t1[f], t2[f]]) for f in OUTS}, tw, "split launches")
     same_state(a, whole, range(16))
     b = make_env(topo, tables, kw, 16, seeds=np.arange(16) + 999)
     b.load_state(snap)
     t3 = b.run(policy, 300, outputs=OUTS, auto_reset=True)
-    for f in OUTS:
-        assert np.array_equal(t3[f], t2[f]), f
-    assert np.array_equal(b.save_state(), a.save_state())
+    same_bytes(t3, t2, "resumed")
+    assert b.save_state().tobytes() == a.save_state().tobytes()
     assert b.channel_state(3) == a.channel_state(3)
     # across modes: refused either way
     d = make_env(topo, tables, dict(kw, bit_rate_selection="discrete"), 16)
@@ -216,7 +199,7 @@ def test_phy_continuous_split_launches_and_checkpoint():
         b.load_state(d.save_state())
     assert ei.value.code == -1
     # the refused loads left b alone
-    assert np.array_equal(b.save_state(), a.save_state())
+    assert b.save_state().tobytes() == a.save_state().tobytes()
     for e in (whole, a, b, d):
         e.close()
 

@@ -4,8 +4,7 @@ tests).  Seeds are fixed: the configurations are the same on every run."""
 import numpy as np
 import pytest
 
-from test_gpu_rmsa import device_log_in_oracle  # noqa: F401
-import test_gpu_edge_cases as ec
+from gpu_support import compare_with_oracle, device_log_fixture, grid_edges, write_topology  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -17,11 +16,11 @@ def test_random_configuration_vs_oracle(tmp_path, case, kernel, device_log_in_or
     from optical_rl_gym_amd.topology_io import topology_from_txt
     rng = np.random.default_rng(1000 + case)
     rows, cols = int(rng.integers(2, 5)), int(rng.integers(2, 5))
-    edges = ec._grid_edges(rows, cols, rng)
+    edges = grid_edges(rows, cols, rng)
     k, topo = int(rng.integers(1, 7)), None
     while topo is None:
         try:
-            topo = topology_from_txt(ec._write_topology(tmp_path, f"g{case}", rows * cols, edges), f"g{case}", k_paths=k)
+            topo = topology_from_txt(write_topology(tmp_path, f"g{case}", rows * cols, edges), f"g{case}", k_paths=k)
         except ValueError:   # a small grid does not have k simple paths for every pair
             k -= 1
     S = int(rng.choice([64, 100, 128, 200, 320, 400, 512]))
@@ -29,9 +28,5 @@ def test_random_configuration_vs_oracle(tmp_path, case, kernel, device_log_in_or
               mean_service_holding_time=float(rng.uniform(5, 30)), episode_length=int(rng.integers(30, 200)),
               seed=int(rng.integers(1, 10000)))
     policy = str(rng.choice(["sap_ff", "sp_ff", "llp_ff"]))
-    ec.STEP_KERNEL = kernel
-    try:
-        tr = ec._compare(topo, kw, policy, int(rng.integers(150, 400)), int(rng.choice([1, 3, 6])))
-    finally:
-        ec.STEP_KERNEL = "auto"
+    tr = compare_with_oracle(topo, kw, policy, int(rng.integers(150, 400)), int(rng.choice([1, 3, 6])), kernel)
     assert tr["accepted"].shape[0] > 0

@@ -23,19 +23,14 @@ the kernel's ring sees them (release time = arrival + holding, due when <= the n
   chunk    an insert into a ring whose live part spans more than one 16-slot chunk
   wrap     an insert into a ring whose live part wraps past slot Q - 1 (Q = 64: the head laps the ring four times; Q = 256 where
            a one-step launch is to leave the ring in HBM: once)"""
-import ctypes as C
-import os
-
 import numpy as np
 import pytest
 
-from conftest import load_topology, oracle_env_from_kwargs
+from conftest import oracle_env_from_kwargs
+from gpu_support import COMPACTNESS as COMP, RMSA_OUTS as OUTS, against_oracle, device_log_fixture, drive, kernel_name, rmsa_env, same_bytes, topology  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-OUTS = ("act_path", "act_slot", "accepted", "reward", "done", "request", "arrival", "holding", "network_compactness",
-        "network_compactness_difference")
-COMP = ("network_compactness", "network_compactness_difference")
 SEED, N_STEPS, LOAD = 31, 300, 25
 NSF, US14 = "nsfnet_chen_5-paths_6-modulations", "us14_3-paths_6-modulations"
 SHAPES = {"defer": (N_STEPS,), "chunks": (N_STEPS,), "one": (1,) * N_STEPS, "eight": (8,) * 37 + (4,)}
@@ -155,85 +150,31 @@ def edited_trace(tr, pending):
                         batch_size=arrival.shape[1], layout="step")
 
 
-@pytest.fixture()
-def device_log_in_oracle():
-    import oracle as orc
-    from optical_rl_gym_amd import _lib
-    orc.set_log_fn(C.cast(_lib.load().orlg_host_log, C.c_void_p).value)
-    yield
-    orc.set_log_fn(None)
-
-
 def _drive(topo, B, kw, stats, kernel, policy, launches, chunks=None, actions=None, outputs=OUTS, Q=64):
-    from optical_rl_gym_amd import BatchedRMSAEnv
-    names = ("ORLG_GROUP_CHUNKS", "ORLG_NO_DEFER", "ORLG_NO_CHUNKS")
-    old = {k: os.environ.pop(k, None) for k in names}
-    if chunks:
-        os.environ["ORLG_GROUP_CHUNKS"] = chunks
-    try:
-        env = BatchedRMSAEnv(topo, B, step_kernel=kernel, stats_level=stats, queue_capacity=Q, **kw)
-        runs, kernels, t = [], set(), 0
-        for n in launches:
-            runs.append(env.run(policy, n, outputs=outputs, auto_reset=True, actions=None if actions is None else actions[t]))
-            kernels.add(env.last_kernel().split(" ")[0])
-            t += n
-        res = dict(tr={k: np.concatenate([r[k] for r in runs]) for k in outputs}, kernels=kernels, last=env.last_kernel(),
-                   occ=env.available_slots().copy(), state=env.save_state().copy(), pending=env.requests(),
-                   counters={k: v.copy() for k, v in env.counters().items()},
-                   links={k: v.copy() for k, v in env.link_stats().items()})
-        env.close()
-        return res
-    finally:
-        os.environ.pop("ORLG_GROUP_CHUNKS", None)
-        for k, v in old.items():
-            if v is not None:
-                os.environ[k] = v
+    return drive(lambda: rmsa_env(topo, B, kernel, stats_level=stats, queue_capacity=Q, **kw), launches, outputs, policy=policy,
+                 env_vars={"ORLG_GROUP_CHUNKS": chunks} if chunks else {}, actions=actions)
 
 
-def _same(grp, wav, outputs=OUTS):
-    for k in outputs:
-        assert grp["tr"][k].tobytes() == wav["tr"][k].tobytes(), k
-    assert np.array_equal(grp["state"], wav["state"])
-    for k in wav["counters"]:
-        assert np.array_equal(grp["counters"][k], wav["counters"][k]), k
-    for k in wav["links"]:
-        assert grp["links"][k].tobytes() == wav["links"][k].tobytes(), k
-    assert np.array_equal(grp["occ"], wav["occ"])
+def _same(grp, wav):
+    same_bytes(grp["tr"], wav["tr"], "outputs")
+    same_bytes(grp["snap"], wav["snap"], "state")
 
 
 def _instantiation(grp, S, stats, shape, trace):
-    level = {"counters": 0, "network": 1, "full": 2}[stats]
-    W = (S + 63) // 64
-    tail = ",false,true>" if trace else ">"
+    names = set(grp["kernels"])
     if shape in ("defer", "chunks") and stats == "full":
-        want = f"orlg_rmsa_group_kernel<{W},2,false,true{',false,true>' if trace else '>'}"
-        assert grp["kernels"] == {want}, grp["kernels"]
+        assert names == {kernel_name("group", S, stats, defer=True, trace=trace)}, names
     elif shape == "one" and S >= 320 and stats == "full":   # (the ring of a small environment fits the LDS in one-step launches too)
-        want = f"orlg_rmsa_group_kernel<{W},2,true{',false' + tail if trace else '>'}"
-        assert grp["kernels"] == {want}, grp["kernels"]
+        assert names == {kernel_name("group", S, stats, hbmq=True, trace=trace)}, names
     else:
-        assert all(k.startswith(f"orlg_rmsa_group_kernel<{W},{level}") for k in grp["kernels"]), grp["kernels"]
+        assert all(k.startswith(kernel_name("group", S, stats)[:-1]) for k in names), names
     if shape == "chunks":
-        assert "chunks=7" in grp["last"], grp["last"]
+        assert "chunks=7" in grp["said"][-1], grp["said"][-1]
 
 
-def _against_oracle(topo, B, kw, stats, grp, policy, actions=None):
-    level = {"counters": 0, "network": 1, "full": 2}[stats]
-    for i in (0, B // 2, B - 1):
-        o = oracle_env_from_kwargs(topo, kw, seed=SEED + i)
-        ot = o.run(policy, N_STEPS, reset_on_done=True, actions=None if actions is None else np.ascontiguousarray(actions[:, i]))
-        # (the counters level keeps no network statistics: its compactness outputs stay 1.0 / 0.0 in both kernels)
-        for f in ("act_path", "act_slot", "accepted", "arrival", "holding") + (COMP if level >= 1 else ()):
-            assert grp["tr"][f][:, i].tobytes() == np.ascontiguousarray(ot[f]).astype(grp["tr"][f].dtype).tobytes(), (f, i)
-        assert np.array_equal(grp["occ"][i], o.available_slots()), i
-        oc = o.counters()
-        for name in oc:
-            assert grp["counters"][name][i] == oc[name], (name, i)
-        if stats == "full":
-            ols = o.link_stats()
-            for name in ols:
-                assert np.array_equal(grp["links"][name][i], ols[name]), (name, i)
-        o.close()
+def _against_oracle(name, B, kw, stats, grp, policy, actions=None):
+    # (the counters level keeps no network statistics: its compactness outputs stay 1.0 / 0.0 in both kernels)
+    against_oracle(name, kw, grp, policy, N_STEPS, (0, B // 2, B - 1), stats, actions=actions)
 
 
 def _id(case):
@@ -243,7 +184,7 @@ def _id(case):
 @pytest.mark.parametrize("case", CASES, ids=_id)
 def test_release_head_vs_wave_kernel_and_oracle(case, device_log_in_oracle):
     name, S, B, stats, shape = case
-    topo, kw = load_topology(name), env_kwargs(S)
+    topo, kw = topology(name), env_kwargs(S)
     launches, chunks, Q = SHAPES[shape], "7" if shape == "chunks" else None, capacity(S, stats, shape)
     grp = _drive(topo, B, kw, stats, "group", "sap_ff", launches, chunks, Q=Q)
     _instantiation(grp, S, stats, shape, False)
@@ -251,9 +192,9 @@ def test_release_head_vs_wave_kernel_and_oracle(case, device_log_in_oracle):
     _same(grp, wav)
     ev = hazards(grp["tr"], Q)
     assert GENERATED <= ev, sorted(GENERATED - ev)
-    _against_oracle(topo, B, kw, stats, grp, "sap_ff")
+    _against_oracle(name, B, kw, stats, grp, "sap_ff")
     # the same traffic as a trace, with a tie and a drained ring in every environment
-    trace = edited_trace(wav["tr"], wav["pending"])
+    trace = edited_trace(wav["tr"], wav["snap"]["requests"])
     tkw = dict(num_spectrum_resources=S, episode_length=200, trace=trace)
     tg = _drive(topo, B, tkw, stats, "group", "sap_ff", launches, chunks, Q=Q)
     _instantiation(tg, S, stats, shape, True)
@@ -267,7 +208,7 @@ def test_release_head_vs_wave_kernel_and_oracle(case, device_log_in_oracle):
 @pytest.mark.parametrize("case", EXT_CASES, ids=_id)
 def test_release_head_external_actions(case, device_log_in_oracle):
     name, S, B, stats = case
-    topo, kw = load_topology(name), env_kwargs(S)
+    topo, kw = topology(name), env_kwargs(S)
     Q = capacity(S, stats, "one")
     ff = _drive(topo, B, kw, stats, "wave", "sap_ff", (N_STEPS,), Q=Q)
     actions = np.stack([ff["tr"]["act_path"], ff["tr"]["act_slot"]], axis=-1).astype(np.int32)   # (rejections: path K, slot S)
@@ -277,11 +218,11 @@ def test_release_head_external_actions(case, device_log_in_oracle):
     _same(grp, wav)
     for k in ("act_path", "act_slot", "accepted"):
         assert np.array_equal(grp["tr"][k], ff["tr"][k]), k
-    assert np.array_equal(grp["occ"], ff["occ"])
+    assert np.array_equal(grp["snap"]["occupancy"], ff["snap"]["occupancy"])
     ev = hazards(grp["tr"], Q)
     assert GENERATED <= ev, sorted(GENERATED - ev)
-    _against_oracle(topo, B, kw, stats, grp, "sap_ff")            # the oracle choosing for itself ...
-    _against_oracle(topo, B, kw, stats, grp, "external", actions)  # ... and given the same choices
+    _against_oracle(name, B, kw, stats, grp, "sap_ff")            # the oracle choosing for itself ...
+    _against_oracle(name, B, kw, stats, grp, "external", actions)  # ... and given the same choices
 
 
 @pytest.mark.parametrize("shape", ["defer", "eight", "one"])
@@ -289,15 +230,14 @@ def test_compactness_outputs_are_the_oracles_and_cost_no_state(shape, device_log
     """The two compactness outputs alone, all outputs, no outputs: the arrays equal the oracle's bit for bit -- on steps that
     were blocked right after a step with releases too, where the output is the value computed after those releases -- and
     the state the launches leave does not depend on what was asked for."""
-    topo, S, B = load_topology(NSF), 64, 5
+    topo, S, B = topology(NSF), 64, 5
     kw = dict(env_kwargs(S), load=60)   # (S = 64 at 60 Erlang: a fifth of the requests is blocked)
     launches = SHAPES[shape]
     only = _drive(topo, B, kw, "full", "group", "sap_ff", launches, outputs=COMP)
     full = _drive(topo, B, kw, "full", "group", "sap_ff", launches)
     none = _drive(topo, B, kw, "full", "group", "sap_ff", launches, outputs=())
-    assert only["state"].tobytes() == full["state"].tobytes() == none["state"].tobytes()
-    for k in full["links"]:
-        assert only["links"][k].tobytes() == full["links"][k].tobytes() == none["links"][k].tobytes(), k
+    same_bytes(only["snap"], full["snap"], "the compactness outputs alone")
+    same_bytes(none["snap"], full["snap"], "no outputs")
     hit = 0
     for i in range(B):
         o = oracle_env_from_kwargs(topo, kw, seed=SEED + i)

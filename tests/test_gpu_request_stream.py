@@ -18,9 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import load_phy_tables, load_topology, oracle_env_from_kwargs, phy_oracle_from_kwargs
-from test_gpu_rmsa import device_log_in_oracle  # noqa: F401
-from test_gpu_sweep import RMSA_OUTS
-from test_gpu_trace import one_step_launches, phy, rmsa, same_bytes
+from gpu_support import RMSA_OUTS, device_log_fixture, one_step_launches, phy_env as phy, rmsa_env, same_bytes  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -64,10 +62,10 @@ def trace_of(r):
 def rmsa_run(kernel, variant):
     topo = load_topology("nsfnet_chen_5-paths_6-modulations")
     if variant == "trace":   # recorded from the discrete run
-        env = rmsa(topo, B, trace=trace_of(rmsa_run("wave", "discrete")), step_kernel=kernel,
-                   **{k: v for k, v in RMSA_KW.items() if k != "seed"})
+        env = rmsa_env(topo, B, kernel, trace=trace_of(rmsa_run("wave", "discrete")),
+                       **{k: v for k, v in RMSA_KW.items() if k not in ("seed", "mean_service_holding_time")})
     else:
-        env = rmsa(topo, B, step_kernel=kernel, **dict(RMSA_KW, **VARIANTS[variant]))
+        env = rmsa_env(topo, B, kernel, **dict(RMSA_KW, **VARIANTS[variant]))
     return scheduled(env, lambda outs: env.run(POLICY, LONG, outputs=outs), lambda outs: one_step_launches(env, POLICY, SINGLE, outs),
                      RMSA_OUTS)
 

@@ -9,6 +9,7 @@ import pytest
 
 import gn_gate_reference as ref
 from conftest import deeprmsa_to_rmsa_kwargs, load_topology
+from gpu_support import device_log_in_oracle, kernel_name, rmsa_env, snapshot, state_matches
 
 pytestmark = pytest.mark.gpu
 
@@ -30,17 +31,8 @@ def _steps_match(tr, i, want, what, rows=slice(None)):
 
 
 def _state(env):
-    """the read-backs _state_matches compares, fetched once per handle"""
-    return dict(available_slots=env.available_slots(), counters=env.counters(), num_running=env.num_running(),
-                current_time=env.current_time())
-
-
-def _state_matches(state, i, final, what):
-    assert np.array_equal(state["available_slots"][i], final["available_slots"]), what
-    for name, v in final["counters"].items():
-        assert state["counters"][name][i] == v, (what, name)
-    assert state["num_running"][i] == final["num_running"], what
-    assert state["current_time"][i] == final["current_time"], what
+    """the read-backs state_matches compares, fetched once per handle"""
+    return snapshot(env, save_state=False)
 
 
 def _concat(a, b):
@@ -48,13 +40,12 @@ def _concat(a, b):
 
 
 def _gated_env(case, B, stats_level="full", seeds=None, **over):
-    from optical_rl_gym_amd import BatchedRMSAEnv
     c = ref.CASES[case]
     topo = load_topology(c["topology"])
     kw = ref.case_kwargs(case, **over)
     if seeds is not None:
         kw.pop("seed")
-    return BatchedRMSAEnv(topo, B, gn_gate=ref.case_gate(topo), stats_level=stats_level, seeds=seeds, **kw), topo, c
+    return rmsa_env(topo, B, gn_gate=ref.case_gate(topo), stats_level=stats_level, seeds=seeds, **kw), topo, c
 
 
 @pytest.mark.parametrize("case", list(ref.CASES))
@@ -65,13 +56,13 @@ def test_case_against_the_gated_oracle(case):
     tr = _concat(env.run(c["policy"], ref.N_STEPS - 1, outputs=OUTS, auto_reset=True),
                  env.run(c["policy"], 1, outputs=OUTS, auto_reset=True))
     W = env.words_per_link
-    assert env.last_kernel().startswith(f"orlg_rmsa_kernel<{W},2,false,true>"), env.last_kernel()
+    assert env.last_kernel().startswith(kernel_name("wave", W, "full", gn=True)), env.last_kernel()
     want, final, fig = ref.run_case(case)
     assert int(np.isfinite(tr["gn_gsnr_db"][:, 0]).sum()) == fig["checks"]
     state = _state(env)
     for i in range(B):
         _steps_match(tr, i, want, (case, i))
-        _state_matches(state, i, final, (case, i))
+        state_matches(state, i, final, (case, i))
     env.close()
 
 
@@ -81,11 +72,11 @@ def test_statistics_levels_decide_alike():
     for level, stats in enumerate(("counters", "network", "full")):
         env, topo, c = _gated_env(case, 2, stats_level=stats, seeds=[ref.CASES[case]["seed"]] * 2)
         tr = env.run(c["policy"], ref.N_STEPS, outputs=OUTS, auto_reset=True)
-        assert env.last_kernel().startswith(f"orlg_rmsa_kernel<{env.words_per_link},{level},false,true>"), env.last_kernel()
+        assert env.last_kernel().startswith(kernel_name("wave", env.words_per_link, level, gn=True)), env.last_kernel()
         state = _state(env)
         for i in range(2):
             _steps_match(tr, i, want, (stats, i))
-            _state_matches(state, i, final, (stats, i))
+            state_matches(state, i, final, (stats, i))
         env.close()
 
 
@@ -101,7 +92,7 @@ def test_agent_driven_deeprmsa():
     B, n = 2, 150
     env = BatchedDeepRMSAEnv(topo, B, gn_gate=gate, seeds=[21] * B, **{k: v for k, v in dkw.items() if k != "seed"})
     K = topo.k_paths
-    with ref.device_log_in_oracle():
+    with device_log_in_oracle():
         gos = [ref.GatedOracle(topo, okw, gate, seed=21, j=j, reward_mode=1) for _ in range(B)]
         for t in range(n):
             acts = [go.o.policy("deeprmsa_sap_ff")[0] for go in gos]
@@ -109,7 +100,7 @@ def test_agent_driven_deeprmsa():
                 acts[1] = K * j + (t % 3)   # out of range: a rejection, no check
             rows = [go.step(*go.resolve_deeprmsa(a)) for go, a in zip(gos, acts)]
             tr = env.run("deeprmsa_external", 1, actions=np.array(acts, np.int32), outputs=OUTS, auto_reset=True)
-            assert env.last_kernel().startswith(f"orlg_rmsa_kernel<{env.words_per_link},2,false,true>"), env.last_kernel()
+            assert env.last_kernel().startswith(kernel_name("wave", env.words_per_link, "full", gn=True)), env.last_kernel()
             for i, row in enumerate(rows):
                 want = {k: np.array([v]) for k, v in row.items()}
                 _steps_match(tr, i, want, (t, i))
@@ -131,7 +122,7 @@ def test_external_actions_occupied_and_out_of_range():
     K, S = topo.k_paths, c["S"]
     n = 150
     occupied = checked = 0
-    with ref.device_log_in_oracle():
+    with device_log_in_oracle():
         gos = [ref.GatedOracle(topo, ref.case_kwargs(case), ref.case_gate(topo), seed=11) for _ in range(2)]
         for t in range(n):
             acts = []
@@ -186,7 +177,7 @@ def test_work_queue_beyond_the_resident_waves():
         want, final, fig = ref.run_case(case, seed=c["seed"] + i, n_steps=n)
         assert fig["checks"] > 0
         _steps_match(tr, i, want, i)
-        _state_matches(state, i, final, i)
+        state_matches(state, i, final, i)
     env.close()
 
 

@@ -2,19 +2,15 @@
 per group.  Every environment of a mixed handle is held to what a handle (or the oracle, or the reference's trace) of ITS load
 and seed gives: bit for bit against the oracle (device log in the oracle, as tests/test_gpu_rmsa.py), decisions and counters
 exactly and times to rtol 1e-12 against the reference's traces (as tests/test_gpu_phy.py)."""
-import os
-
 import numpy as np
 import pytest
 
-from conftest import (deeprmsa_to_rmsa_kwargs, load_golden, load_phy_tables, load_topology, oracle_env_from_kwargs,
-                      phy_oracle_from_kwargs)
-from test_gpu_rmsa import device_log_in_oracle  # noqa: F401
+from conftest import deeprmsa_to_rmsa_kwargs, load_golden, load_phy_tables, load_topology, oracle_env_from_kwargs
+from gpu_support import (PHY_CONTINUOUS_OUTS as COUTS, RMSA_OUTS, device_log_fixture, everything_matches_oracle,  # noqa: F401
+                         one_step_launches, phy_env, phy_matches_oracle, phy_matches_reference, rmsa_env, same_bytes, snapshot, step_kernel as step_kernel_both, tooling_env)
 
 pytestmark = pytest.mark.gpu
 
-RMSA_OUTS = ("act_path", "act_slot", "accepted", "done", "reward", "request", "arrival", "holding", "network_compactness",
-             "network_compactness_difference")
 PHY_OUTS = ("act_path", "n_channels", "channels", "channels_used", "accepted", "done", "request", "arrival", "holding",
             "number_cuts_total", "rss_total_metric", "defrag_counters")
 RMSA_KW = dict(num_spectrum_resources=320, mean_service_holding_time=25, episode_length=200)
@@ -22,69 +18,9 @@ RMSA_KW = dict(num_spectrum_resources=320, mean_service_holding_time=25, episode
 SWEEP_LOADS, SWEEP_SEEDS = (2.0, 50.0, 120.0, 400.0), 8
 
 
-class env_vars:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        os.environ.update(self.kv)
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def rmsa_sweep(topo, loads=SWEEP_LOADS, seeds_per_load=SWEEP_SEEDS, seed=10, **extra):
     from optical_rl_gym_amd import make_sweep
     return make_sweep("rmsa", topo, loads=loads, seeds_per_load=seeds_per_load, seed=seed, **dict(RMSA_KW, **extra))
-
-
-def check_rmsa_env(topo, kw, tr, i, state, policy, n, reset_on_done, actions=None, j=1, reward_mode=0):
-    """Environment i of the device run against the oracle of its own kwargs: everything bit-identical."""
-    o = oracle_env_from_kwargs(topo, kw, j=j, reward_mode=reward_mode)
-    ot = o.run(policy, n, reset_on_done=reset_on_done, actions=None if actions is None else np.ascontiguousarray(actions[:, i]))
-    for f, g in (("act_path", "act_path"), ("act_slot", "act_slot"), ("accepted", "accepted"), ("done", "done"),
-                 ("reward", "reward"), ("arrival", "arrival"), ("holding", "holding"),
-                 ("network_compactness", "network_compactness"),
-                 ("network_compactness_difference", "network_compactness_difference")):
-        bad = np.nonzero(tr[f][:, i] != ot[g])[0]
-        assert bad.size == 0, (f, i, kw["load"], bad[:4], tr[f][bad[:4], i], ot[g][bad[:4]])
-    for q, g in enumerate(("service_id", "src", "dst", "bit_rate")):
-        assert np.array_equal(tr["request"][:, i, q], ot[g]), (g, i)
-    cnt, occ, ls, gs, hist, req, now, nrun = state
-    for name, v in o.counters().items():
-        assert cnt[name][i] == v, (name, i)
-    assert np.array_equal(occ[i], o.available_slots()), i
-    for name, v in o.link_stats().items():
-        assert np.array_equal(ls[name][i], v), (name, i)
-    for name, v in o.graph_stats().items():
-        assert gs[name][i] == v, (name, i)
-    for name, v in o.bit_rate_hist().items():
-        assert np.array_equal(hist[name][i], v), (name, i)
-    r = o.request()
-    assert (req[i]["service_id"], req[i]["src"], req[i]["dst"], req[i]["bit_rate"], req[i]["arrival_time"], req[i]["holding_time"]) == \
-        (r.service_id, r.src, r.dst, r.bit_rate, r.arrival_time, r.holding_time), i
-    assert now[i] == o.current_time() and nrun[i] == o.num_running(), i
-    o.close()
-    return ot
-
-
-def rmsa_state(env):
-    return (env.counters(), env.available_slots(), env.link_stats(), env.graph_stats(), env.bit_rate_hist(), env.requests(),
-            env.current_time(), env.num_running())
-
-
-def run_stepwise(env, policy, n, outs, actions=None, **kw):
-    cols = {k: [] for k in outs}
-    for t in range(n):
-        r = env.run(policy, 1, outputs=outs, **(dict(kw, actions=actions[t]) if actions is not None else kw))
-        for k in outs:
-            cols[k].append(r[k][0])
-    return {k: np.stack(v) for k, v in cols.items()}
 
 
 # ------------------------------------------------------------------------------------------------ 2. against the oracle: RMSA
@@ -95,19 +31,19 @@ def test_rmsa_sweep_vs_oracle(nsfnet, device_log_in_oracle, kernel, policy, mode
     """4 loads x 8 seeds, every float bit-exact: long launches (the deferred link statistics and the release summaries),
     one launch per step (the release queue stays in HBM) and long launches cut into forced chunks."""
     n = 700 if mode != "steps" else 90
-    with env_vars(**({"ORLG_GROUP_CHUNKS": "3"} if mode == "chunks" else {})):
+    with tooling_env(**({"ORLG_GROUP_CHUNKS": "3"} if mode == "chunks" else {})):
         env = rmsa_sweep(nsfnet, step_kernel=kernel)
         assert env.batch_size == 32 and env.num_groups == 4
         tr = env.run(policy, n, outputs=RMSA_OUTS, auto_reset=True) if mode != "steps" else \
-            run_stepwise(env, policy, n, RMSA_OUTS, auto_reset=True)
+            one_step_launches(env, policy, n, RMSA_OUTS, auto_reset=True)
         if mode == "chunks":
             assert "chunks=3" in env.last_kernel(), env.last_kernel()
         if mode == "steps" and kernel == "group" and policy == "sap_ff":
             assert ",true>" in env.last_kernel(), env.last_kernel()   # the instantiation with the queue in HBM
-    state = rmsa_state(env)
+    state = snapshot(env, save_state=False)
     for i in range(env.batch_size):
         kw = dict(RMSA_KW, load=float(env.loads[i]), seed=10 + i % SWEEP_SEEDS)
-        check_rmsa_env(nsfnet, kw, tr, i, state, policy, n, True)
+        everything_matches_oracle(nsfnet, kw, tr, i, state, policy, n, True)
     if mode == "long":
         g = env.groups
         assert tr["accepted"][:, g == 3].mean() < 0.999, "the highest load must block"
@@ -119,15 +55,10 @@ def test_rmsa_sweep_continuous_bit_rates_vs_oracle(nsfnet, device_log_in_oracle,
     kwx = dict(bit_rate_selection="continuous", bit_rate_lower_bound=25, bit_rate_higher_bound=100)
     env = rmsa_sweep(nsfnet, step_kernel=step_kernel_both, **kwx)
     tr = env.run("sap_ff", 500, outputs=RMSA_OUTS, auto_reset=True)
-    state = rmsa_state(env)
+    state = snapshot(env, save_state=False)
     for i in range(env.batch_size):
-        check_rmsa_env(nsfnet, dict(RMSA_KW, load=float(env.loads[i]), seed=10 + i % SWEEP_SEEDS, **kwx), tr, i, state, "sap_ff", 500, True)
+        everything_matches_oracle(nsfnet, dict(RMSA_KW, load=float(env.loads[i]), seed=10 + i % SWEEP_SEEDS, **kwx), tr, i, state, "sap_ff", 500, True)
     env.close()
-
-
-@pytest.fixture(params=["wave", "group"])
-def step_kernel_both(request):
-    return request.param
 
 
 def test_deeprmsa_sweep_external_actions_vs_oracle(nsfnet, device_log_in_oracle, step_kernel_both):
@@ -141,7 +72,7 @@ def test_deeprmsa_sweep_external_actions_vs_oracle(nsfnet, device_log_in_oracle,
     rng = np.random.default_rng(11)
     actions = rng.integers(0, nsfnet.k_paths, (n, B)).astype(np.int32)
     outs = ("act_path", "act_slot", "accepted", "reward", "done", "arrival", "holding")
-    tr = run_stepwise(env, "deeprmsa_external", n, outs, actions=actions, auto_reset=True)
+    tr = one_step_launches(env, "deeprmsa_external", n, outs, actions=actions, auto_reset=True)
     obs, cnt = env.observation(), env.counters()
     for i in range(B):
         ld = loads[i // 8]
@@ -158,61 +89,6 @@ def test_deeprmsa_sweep_external_actions_vs_oracle(nsfnet, device_log_in_oracle,
 
 
 # ------------------------------------------------------------------------------------------------ 1. + 2. QoT-aware
-def phy_env(topo, tables, kw, batch, **extra):
-    from optical_rl_gym_amd import BatchedPhyRMSAEnv
-    pairs, mod, gsnr = tables
-    kw = {k: v for k, v in kw.items() if k not in ("num_spectrum_resources", "bit_rate_selection")}
-    kw.update(extra)
-    return BatchedPhyRMSAEnv(topo, batch, modulation_level=mod, connections_detail=pairs, gsnr=gsnr, **kw)
-
-
-def check_phy_env(topo, tables, kw, env, tr, i, state, policy, n):
-    """Environment i against the oracle of its own load and seed, as tests/test_gpu_phy.py holds a uniform batch."""
-    cnt, now, nrun, av, est = state
-    o = phy_oracle_from_kwargs(topo, tables, kw)
-    ot = o.run(policy, n, reset_on_done=True)
-    assert np.array_equal(tr["act_path"][:, i], ot["act_path"]), i
-    assert np.array_equal(tr["n_channels"][:, i], ot["n_channels"]), i
-    assert np.array_equal(tr["channels"][:, i, :12].astype(np.int32), ot["channels"]), i
-    assert np.array_equal(tr["channels_used"][:, i, :12].astype(np.float64), ot["ch_used"]), i
-    assert np.array_equal(tr["accepted"][:, i], ot["accepted"]) and np.array_equal(tr["done"][:, i], ot["done"]), i
-    assert np.array_equal(tr["request"][:, i, 1], ot["src"]) and np.array_equal(tr["request"][:, i, 3], ot["bit_rate"]), i
-    for f in ("arrival", "holding", "number_cuts_total", "rss_total_metric"):
-        bad = np.nonzero(tr[f][:, i] != ot[f])[0]
-        assert bad.size == 0, (f, i, kw["load"], bad[:4], tr[f][bad[:4], i], ot[f][bad[:4]])
-    dc = tr["defrag_counters"][:, i].astype(np.int64)
-    assert np.array_equal(dc[:, 1], ot["num_moves_groom"]) and np.array_equal(dc[:, 2], ot["num_defrag_cycle"]), i
-    assert np.array_equal(dc[:, 0] / 2 + dc[:, 1], ot["num_moves"]), i
-    for name, v in o.counters().items():
-        assert cnt[name][i] == v, (name, i)
-    assert now[i] == o.current_time() and nrun[i] == o.num_running(), i
-    assert np.array_equal(av[i], o.available_channels()), i
-    assert est["queue_overflow"][i] == 0
-    assert env.channel_state(i) == o.channel_state(), i
-    o.close()
-
-
-def check_phy_fixture(z, tr, i, n):
-    """Environment i against the reference's own trace for the trace's first n steps."""
-    assert np.array_equal(tr["act_path"][:n, i], z["act_path"][:n]), i
-    assert np.array_equal(tr["channels"][:n, i, :12], z["channels"][:n]), i
-    assert np.array_equal(tr["channels_used"][:n, i, :12].astype(np.float64), z["ch_used"][:n]), i
-    assert np.array_equal(tr["accepted"][:n, i], z["accepted"][:n]), i
-    np.testing.assert_allclose(tr["arrival"][:n, i], z["arrival"][:n], rtol=1e-12)
-    assert np.array_equal(tr["number_cuts_total"][:n, i], z["number_cuts_total"][:n]), i
-    assert np.array_equal(tr["rss_total_metric"][:n, i], z["rss_total_metric"][:n]), i
-    # the all-time counter of the trace, step by step (services_accepted is never reset)
-    assert np.array_equal(np.cumsum(tr["accepted"][:n, i].astype(np.int64)), z["services_accepted"][:n]), i
-    if "num_moves" in z.files:
-        dc = tr["defrag_counters"][:n, i].astype(np.int64)
-        assert np.array_equal(dc[:, 0] / 2 + dc[:, 1], z["num_moves"][:n])
-        assert np.array_equal(dc[:, 1], z["num_moves_groom"][:n]) and np.array_equal(dc[:, 2], z["num_defrag_cycle"][:n])
-
-
-def phy_state(env):
-    return env.counters(), env.current_time(), env.num_running(), env.available_channels(), env.episode_stats()
-
-
 def run_mixed_phy(cases, copies, extra_envs, device_policy=None):
     """One handle: `copies` environments per fixture of `cases` (its seed and load), then extra_envs = [(load, seed)].  Every
     environment is held to the oracle at its load; the fixture environments also to their traces."""
@@ -234,11 +110,11 @@ def run_mixed_phy(cases, copies, extra_envs, device_policy=None):
     groups = [sorted(set(loads)).index(ld) for ld in loads]
     env = phy_env(topo, tables, base, len(envs), load=loads, seeds=seeds, groups=groups)
     tr = env.run(policy, n, outputs=PHY_OUTS, auto_reset=True)
-    state = phy_state(env)
+    state = snapshot(env, save_state=False)
     for i, (ld, sd, z, steps) in enumerate(envs):
-        check_phy_env(topo, tables, dict(base, load=ld, seed=sd), env, tr, i, state, policy, n)
+        phy_matches_oracle(topo, tables, dict(base, load=ld, seed=sd), env, tr, i, state, policy, n)
         if z is not None:
-            check_phy_fixture(z, tr, i, steps)
+            phy_matches_reference(z, tr, i, steps)
     env.close()
 
 
@@ -284,9 +160,9 @@ def test_phy_sweep_vs_oracle(policy, extra, device_log_in_oracle):
     env = phy_env(topo, tables, base, load.size, load=load, seeds=seeds, groups=group)
     n = 400
     tr = env.run(policy, n, outputs=PHY_OUTS, auto_reset=True)
-    state = phy_state(env)
+    state = snapshot(env, save_state=False)
     for i in range(load.size):
-        check_phy_env(topo, tables, dict(base, load=float(load[i]), seed=int(seeds[i])), env, tr, i, state, policy, n)
+        phy_matches_oracle(topo, tables, dict(base, load=float(load[i]), seed=int(seeds[i])), env, tr, i, state, policy, n)
     if "gn_gate" not in extra:   # (the GN gate refuses services whatever the load)
         assert tr["accepted"][:, group == 0].all(), "the lowest load must not block"
     if narrow:
@@ -321,7 +197,6 @@ def test_phy_continuous_mixed_handle_device_against_device():
     """Continuous bit rates have no oracle: a mixed continuous handle holds the fixture's seed at the fixture's load and at a
     second load; each environment equals the same seed on a UNIFORM continuous handle of its load -- device against device:
     every per-step output and every environment's slice of save_state byte for byte."""
-    from test_gpu_phy_continuous import OUTS as COUTS, make_env
     z, meta = load_golden("cont_us14_s20_sapff")
     topo, tables = load_topology(meta["topology"]), load_phy_tables(meta["tables"])
     kw = dict(meta["env_kwargs"])
@@ -329,17 +204,16 @@ def test_phy_continuous_mixed_handle_device_against_device():
     ld1 = 2.5 * ld0
     loads, seeds = [ld0, ld1, ld0, ld1, ld1, ld0], [sd, sd, sd + 1, sd + 1, sd, sd]
     cap = dict(queue_capacity=2048, channel_state_capacity=32)   # the same capacities on every handle
-    mixed = make_env(topo, tables, dict(kw, load=loads), 6, seeds=seeds, **cap)
+    mixed = phy_env(topo, tables, dict(kw, load=loads), 6, seeds=seeds, **cap)
     tm = mixed.run(meta["policy"], n, outputs=COUTS, auto_reset=True)
     sm = continuous_state_slices(mixed, topo, cap["queue_capacity"])
     assert np.array_equal(tm["act_path"][:, 0], z["act_path"][:n]) and np.array_equal(tm["accepted"][:, 0], z["accepted"][:n])
     np.testing.assert_allclose(tm["arrival"][:, 0], z["arrival"][:n], rtol=1e-12, atol=0)
     for ld in (ld0, ld1):
         idx = [i for i in range(6) if loads[i] == ld]
-        uni = make_env(topo, tables, dict(kw, load=ld), len(idx), seeds=[seeds[i] for i in idx], **cap)
+        uni = phy_env(topo, tables, dict(kw, load=ld), len(idx), seeds=[seeds[i] for i in idx], **cap)
         tu = uni.run(meta["policy"], n, outputs=COUTS, auto_reset=True)
-        for f in COUTS:
-            assert np.ascontiguousarray(tm[f][:, idx]).tobytes() == tu[f].tobytes(), (f, ld)
+        same_bytes({f: tm[f][:, idx] for f in COUTS}, tu, ld)
         for get in ("counters", "current_time", "num_running", "available_channels", "requests", "episode_stats"):
             x, y = getattr(mixed, get)(), getattr(uni, get)()
             if isinstance(x, dict):
@@ -357,16 +231,14 @@ def test_phy_continuous_mixed_handle_device_against_device():
 # ------------------------------------------------------------------------------------------------ 3. a uniform array is the scalar
 @pytest.mark.parametrize("kernel", ["wave", "group"])
 def test_uniform_array_is_the_scalar_rmsa(nsfnet, kernel):
-    from optical_rl_gym_amd import BatchedRMSAEnv
     B = 24
-    a = BatchedRMSAEnv(nsfnet, B, load=50, seed=3, step_kernel=kernel, **RMSA_KW)
-    b = BatchedRMSAEnv(nsfnet, B, load=np.full(B, 50.0), seed=3, step_kernel=kernel, **RMSA_KW)
+    a = rmsa_env(nsfnet, B, kernel, load=50, seed=3, **RMSA_KW)
+    b = rmsa_env(nsfnet, B, kernel, load=np.full(B, 50.0), seed=3, **RMSA_KW)
     assert np.array_equal(a.traffic_rates()[0], b.traffic_rates()[0]) and np.array_equal(a.traffic_rates()[1], b.traffic_rates()[1])
     ta = a.run("sap_ff", 1000, outputs=RMSA_OUTS, auto_reset=True)
     tb = b.run("sap_ff", 1000, outputs=RMSA_OUTS, auto_reset=True)
-    for f in RMSA_OUTS:
-        assert ta[f].tobytes() == tb[f].tobytes(), f
-    assert a.save_state().tobytes() == b.save_state().tobytes()
+    same_bytes(ta, tb, "outputs")
+    same_bytes(snapshot(a), snapshot(b), "state")
     a.close(); b.close()
 
 
@@ -377,9 +249,8 @@ def test_uniform_array_is_the_scalar_phy():
     b = phy_env(topo, tables, kw, 8, load=np.full(8, 50.0))
     ta = a.run("bmfa", 1000, outputs=PHY_OUTS, auto_reset=True)
     tb = b.run("bmfa", 1000, outputs=PHY_OUTS, auto_reset=True)
-    for f in PHY_OUTS:
-        assert ta[f].tobytes() == tb[f].tobytes(), f
-    assert a.save_state().tobytes() == b.save_state().tobytes()
+    same_bytes(ta, tb, "outputs")
+    same_bytes(snapshot(a), snapshot(b), "state")
     a.close(); b.close()
 
 
@@ -415,7 +286,7 @@ def test_mixed_loads_kernels_continue_each_other_and_checkpoint(nsfnet):
     chk.reset(only_episode_counters=False)
     t1 = chk.run("sap_ff", 200, outputs=("arrival", "holding"))
     t2 = other.run("sap_ff", 200, outputs=("arrival", "holding"))
-    assert t1["holding"].tobytes() == t2["holding"].tobytes() and t1["arrival"].tobytes() == t2["arrival"].tobytes()
+    same_bytes(t1, t2, "after the reseed")
     for e in (ref, a, g, fresh, other, chk):
         e.close()
 

@@ -1,9 +1,13 @@
 """Request traces on the device (include/orlg.h orlg_create_trace / orlg_phy_create_trace): a handle replays itself byte for
 byte on every step kernel and launch shape; the reference's own streams come back with every float64 equal to the oracle on
 libm; a hand-made stream has the outcome first fit must give; bounds, resets, saved state, capacities and groups."""
+import functools
+
 import numpy as np
 import pytest
+
 from conftest import load_golden, load_phy_tables, load_topology, oracle_env_from_kwargs, phy_oracle_from_kwargs
+from gpu_support import one_step_launches, phy_env as phy, rmsa_env, same_bytes, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -14,8 +18,7 @@ KW = dict(num_spectrum_resources=320, mean_service_holding_time=25, episode_leng
 T = 1500
 
 
-def rmsa(topo, batch, trace=None, cls=None, **kw):
-    from optical_rl_gym_amd import BatchedRMSAEnv
+def rmsa(topo, batch, trace=None, step_kernel="auto", **kw):
     args = dict(KW, **kw)
     if trace is not None:
         args.pop("mean_service_holding_time", None)
@@ -23,35 +26,11 @@ def rmsa(topo, batch, trace=None, cls=None, **kw):
     else:
         args.setdefault("load", 50)
         args.setdefault("seed", 10)
-    return (cls or BatchedRMSAEnv)(topo, batch, **args)
+    return rmsa_env(topo, batch, step_kernel, **args)
 
 
-def snapshot(env):
-    s = {}
-    for get in ("counters", "link_stats", "graph_stats", "bit_rate_hist"):
-        for k, v in getattr(env, get)().items():
-            s[get + "." + k] = v
-    s["occupancy"] = env.occupancy_words()
-    s["num_running"] = env.num_running()
-    s["current_time"] = env.current_time()
-    s["requests"] = env.requests()
-    return s
-
-
-def same_bytes(a, b, what=""):
-    assert a.keys() == b.keys()
-    for k in a:
-        x, y = np.ascontiguousarray(a[k]), np.ascontiguousarray(b[k])
-        assert x.shape == y.shape and x.dtype == y.dtype and x.tobytes() == y.tobytes(), (what, k)
-
-
-def one_step_launches(env, policy, n, outs):
-    cols = {k: [] for k in outs}
-    for _ in range(n):
-        r = env.run(policy, 1, outputs=outs)
-        for k in outs:
-            cols[k].append(r[k][0])
-    return {k: np.stack(v) for k, v in cols.items()}
+# (the read-backs without save_state: a generating handle's blob holds its generator, a replaying one's its position in the trace)
+read_backs = functools.partial(snapshot, save_state=False)
 
 
 # ------------------------------------------------------------------------------------------------ 1. a handle replays itself
@@ -62,7 +41,7 @@ def test_a_handle_replays_itself(nsfnet, kernel, batch, policy, monkeypatch):
     from optical_rl_gym_amd import record_trace
     gen = rmsa(nsfnet, batch, step_kernel=kernel)
     trace = record_trace(gen, policy, T, outputs=ALL_OUTS)
-    want, want_state = trace.outputs, snapshot(gen)
+    want, want_state = trace.outputs, read_backs(gen)
     assert trace.length == T + 1 and trace.batch_size == batch
     if batch > 8:   # every environment has its own stream
         assert len({trace.arrival[i, :8].tobytes() for i in range(batch)}) == batch
@@ -87,7 +66,7 @@ def test_a_handle_replays_itself(nsfnet, kernel, batch, policy, monkeypatch):
             assert rep.last_kernel().startswith("orlg_rmsa_group_kernel") and rep.last_kernel().split(">")[0].endswith(",true"), rep.last_kernel()
         assert rep.trace_position == T + 1
         same_bytes({k: want[k] for k in outs}, got, (shape, "outputs"))
-        same_bytes(want_state, snapshot(rep), (shape, "state"))
+        same_bytes(want_state, read_backs(rep), (shape, "state"))
         rep.close()
     gen.close()
 
@@ -121,7 +100,7 @@ def test_deeprmsa_external_actions_replayed(nsfnet, kernel):
         r = rep.run("deeprmsa_external", 1, actions=actions[t], outputs=outs)
         for k in outs:
             assert r[k][0].tobytes() == want[k][t].tobytes(), (k, t)
-    same_bytes(snapshot(gen), snapshot(rep))
+    same_bytes(read_backs(gen), read_backs(rep))
     gen.close(); rep.close()
 
 
@@ -200,14 +179,6 @@ def test_stream_no_generator_produces(nsfnet, kernel):
 
 
 # ------------------------------------------------------------------------------------------------ 4. QoT-aware
-def phy(topo, tables, kw, batch, **extra):
-    from optical_rl_gym_amd import BatchedPhyRMSAEnv
-    pairs, mod, gsnr = tables
-    kw = {k: v for k, v in kw.items() if k not in ("num_spectrum_resources", "allow_rejection")}
-    kw.update(extra)
-    return BatchedPhyRMSAEnv(topo, batch, modulation_level=mod, connections_detail=pairs, gsnr=gsnr, **kw)
-
-
 PHY_OUTS = ("act_path", "n_channels", "channels", "accepted", "done", "request", "arrival", "holding", "number_cuts_total",
             "rss_total_metric")
 TRAFFIC_KEYS = ("load", "mean_service_holding_time", "seed")
@@ -265,8 +236,7 @@ def test_phy_gn_gate_device_against_device():
     got = rep.run("bmfa", n, outputs=outs, auto_reset=True)
     assert "true" in rep.last_kernel()   # the GN instantiation
     same_bytes(want, got)
-    for get in ("current_time", "num_running", "available_channels", "requests"):
-        assert np.array_equal(getattr(gen, get)(), getattr(rep, get)()), get
+    same_bytes(read_backs(gen), read_backs(rep), "state")
     gen.close(); rep.close()
 
 
@@ -290,7 +260,7 @@ def test_bounds_resets_and_saved_state(nsfnet, kind):
         trace = record_trace(gen, policy, T, outputs=outs)
         want = trace.outputs
         make = lambda: rmsa(nsfnet, B, trace=trace, step_kernel=kind)
-        state = snapshot
+        state = read_backs
     gen.close()
     env = make()
     n = trace.length
@@ -309,8 +279,7 @@ def test_bounds_resets_and_saved_state(nsfnet, kind):
     assert env.trace_position == n
     with pytest.raises(OrlgError):
         env.run(policy, 1)
-    for k in outs:
-        assert np.concatenate([first[k], rest[k]]).tobytes() == want[k].tobytes(), k
+    same_bytes({k: np.concatenate([first[k], rest[k]]) for k in outs}, want, "outputs")
     end = state(env)
     # an episode reset does not rewind, a full reset does: the second pass equals the first
     env.reset(only_episode_counters=True)
@@ -318,8 +287,7 @@ def test_bounds_resets_and_saved_state(nsfnet, kind):
     env.reset(only_episode_counters=False)
     assert env.trace_position == 1
     again = env.run(policy, n - 1, outputs=outs)
-    for k in outs:
-        assert again[k].tobytes() == want[k].tobytes(), k
+    same_bytes(again, want, "second pass")
     with pytest.raises(ValueError):
         env.reseed(5)
     assert env.L.orlg_phy_reseed(env.h, None, 5) == -1 if kind == "phy" else env.L.orlg_reseed(env.h, None, 5) == -1
@@ -328,11 +296,8 @@ def test_bounds_resets_and_saved_state(nsfnet, kind):
     other.load_state(mid)
     assert other.trace_position == 701
     cont = other.run(policy, n - 1 - 700, outputs=outs)
-    for k in outs:
-        assert cont[k].tobytes() == rest[k].tobytes(), k
-    a, b = end, state(other)
-    for k in a:
-        assert np.ascontiguousarray(a[k]).tobytes() == np.ascontiguousarray(b[k]).tobytes(), k
+    same_bytes(cont, rest, "continued")
+    same_bytes(end, state(other), "state")
     assert other.save_state().size == mid.size
     # a snapshot whose position does not fit this handle's trace is refused before anything is copied
     held = other.save_state()

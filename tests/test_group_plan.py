@@ -9,58 +9,11 @@ inside ``rmsa_create`` and ``launch_rmsa_group`` before the header existed; they
 ``test_gpu_kernel_selection``'s docstring (22 336 B and 25 152 B, 6 (5) and 12 waves) and with the 3072 wave slots of the chunk
 rule's measurements."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-from optical_rl_gym_amd import _lib, build
-
-KINDS = ("PLAIN", "HBMQ", "DEFER")   # enum OrlgGroupKind
-SP, SAP, LLP = 0, 1, 2   # ORLG_POLICY_*
-OUT_ACCEPTED, OUT_LINK_COMPACT, OUT_LINK_UTIL = 1 << 2, 1 << 10, 1 << 11   # 1 << ORLG_OUT_*
-NSFNET = dict(NW=110, E=22, lint_stride=24)
-SHARED = {0: 10448, 2: 14320}
-MT_BYTES = 2496   # the workgroup's MT19937 staging buffer; its lock word takes 16 more
-
-
-def _fields(macro):
-    text = open(os.path.join(build.CSRC, "orlg_api.hip")).read()
-    body = re.search(r"#define %s\(X\)((?:[^\n]*\\\n)*[^\n]*)\n" % macro, text).group(1)
-    return re.findall(r"X\((?:\w+, )?(\w+)\)", body)
-
-
-IN, LAYOUT, PLAN = _fields("ORLG_GROUP_PLAN_IN"), _fields("ORLG_GROUP_LAYOUT_OUT"), _fields("ORLG_GROUP_PLAN_OUT")
-
-
-def plan(Q=128, stats=2, B=8, n_steps=1000, policy=SAP, out_mask=0, br_width=0, num_cu=256, resident=256, **overrides):
-    """({kind name: layout}, plan) -- both dicts by field name"""
-    args = dict(NSFNET, Q=Q, stats_level=stats, shared_bytes=SHARED[stats], B=B, n_steps=n_steps, policy=policy, out_mask=out_mask,
-                br_width=br_width, no_defer=0, no_chunks=0, no_lean=0, wpb=0, chunks=0, num_cu=num_cu, resident=resident)
-    assert set(overrides) <= {"no_defer", "no_chunks", "no_lean", "wpb", "chunks"}
-    args.update(overrides)
-    assert sorted(args) == sorted(IN)
-    n_out = 3 * len(LAYOUT) + len(PLAN)
-    vin, out = (C.c_int32 * len(IN))(*[args[f] for f in IN]), (C.c_int32 * n_out)()
-    f = _lib.load().orlg_debug_group_plan
-    f.argtypes = [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32]
-    assert f(vin, len(IN), out, n_out) == n_out
-    layouts = {k: dict(zip(LAYOUT, out[i * len(LAYOUT):(i + 1) * len(LAYOUT)])) for i, k in enumerate(KINDS)}
-    p = dict(zip(PLAN, out[3 * len(LAYOUT):]))
-    p["kind"] = KINDS[p["kind"]]
-    # what holds for every plan: the workgroup's LDS bytes, and how far the launch moves ticket_base
-    chosen, n_quads = layouts[p["kind"]], (B + 3) // 4
-    assert 1 <= p["wpb"] <= chosen["wpb_max"]
-    assert p["lds_bytes"] == SHARED[stats] + MT_BYTES + 16 + p["wpb"] * chosen["wave_bytes"]
-    assert p["ticket_stride"] == (1 if n_steps <= 16 else 0)
-    assert p["nblocks"] == min(-(-n_quads // p["wpb"]), resident)
-    if p["ticket_stride"]:
-        assert p["ticket_advance"] == 0
-    elif p["n_chunks"] == 1:
-        assert p["ticket_advance"] == n_quads
-    else:
-        assert p["ticket_advance"] == n_quads * p["n_chunks"] + p["nblocks"] * p["wpb"]
-    return layouts, p
+from gpu_support import LLP, OUT_ACCEPTED, OUT_LINK_COMPACT, OUT_LINK_UTIL, SAP, SP, plan
+from optical_rl_gym_amd import _lib
 
 
 def test_a_wrong_number_of_inputs_is_refused():

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, load_topology, oracle_env_from_kwargs
-from test_oracle_golden import FLOAT_FIELDS, INT_FIELDS
+from gpu_support import FLOAT_FIELDS, INT_FIELDS
 
 RING34, RING36 = "ring34_3-paths_6-modulations", "ring36_3-paths_6-modulations"
 SHUFFLED = "ring34_shuffled_3-paths_6-modulations"

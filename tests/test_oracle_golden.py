@@ -8,16 +8,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_golden, load_topology, oracle_env_from_kwargs
+from gpu_support import FLOAT_FIELDS, INT_FIELDS
 
 RMSA_CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "rmsa_*.npz")))
-
-INT_FIELDS = ["service_id", "bit_rate", "accepted", "done", "services_processed", "services_accepted",
-              "episode_services_processed", "episode_services_accepted", "bit_rate_requested",
-              "bit_rate_provisioned", "episode_bit_rate_requested", "episode_bit_rate_provisioned", "free_total"]
-FLOAT_FIELDS = ["arrival", "holding", "reward", "network_compactness", "network_compactness_difference",
-                "avg_link_compactness", "avg_link_utilization", "fairness", "current_time", "graph_throughput",
-                "graph_compactness"]
-
 
 def test_python_random_known_answer():
     import oracle as orc

@@ -270,10 +270,10 @@ import sys
 import numpy as np, torch
 torch.zeros(1, device="cuda")
 sys.path[:0] = [%r, %r]
-from test_osnr import edges
+from conftest import GOLDEN
 from optical_rl_gym_amd import _lib, gn_osnr
 from optical_rl_gym_amd.osnr import FIELDS, OsnrBatch
-z = edges()
+z = dict(np.load(GOLDEN + "/osnr_edges.npz", allow_pickle=False))
 want = gn_osnr(z)
 L = _lib.load()
 L.orlg_gn_osnr.argtypes = [C.POINTER(OsnrBatch), C.c_void_p, C.c_int32, C.c_void_p]
