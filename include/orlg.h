@@ -103,8 +103,15 @@ enum {
     ORLG_POLICY_DEEPRMSA_SP_FF = 3,   /* deeprmsa_env.shortest_path_first_fit (allow_rejection=False) */
     ORLG_POLICY_DEEPRMSA_SAP_FF = 4,  /* deeprmsa_env.shortest_available_path_first_fit */
     ORLG_POLICY_DEEPRMSA_EXTERNAL = 5, /* caller supplies Discrete(k*j) actions (deeprmsa_env.py:48-58) */
-    ORLG_POLICY_PATH_FF_EXTERNAL = 6   /* caller supplies the path, first fit the slot: PathOnlyFirstFitAction
+    ORLG_POLICY_PATH_FF_EXTERNAL = 6,  /* caller supplies the path, first fit the slot: PathOnlyFirstFitAction
                                           (rmsa_env.py:974-1008); actions is [B] int32 */
+    ORLG_POLICY_SAP_FF_GN = 7          /* QoT-aware shortest_available_path_first_fit, only on a handle with a GN-model
+                                          admission check (orlg_rmsa_gn_gate; not in the reference): the candidate paths in
+                                          order, the first one that has a first fit AND whose first-fit window passes the check
+                                          is provisioned; paths without a fit are skipped without a check.  No path with a fit
+                                          passes: a refusal like any other of the gate, act_path / act_slot / gn_gsnr_db show
+                                          the first candidate that was checked (what ORLG_POLICY_SAP_FF would have proposed).
+                                          No path has a fit: the policy's rejection.  Each candidate is checked once */
 };
 
 /* Optional per-step outputs of orlg_step(); any pointer may be NULL.  Arrays are [n_steps][B]
@@ -184,8 +191,10 @@ int orlg_step(orlg_env *env, int32_t policy, int32_t n_steps, const int32_t *act
  * interferers of a link are the running services of that environment whose path contains it.  The candidate is in no list yet
  * (no entry is the service itself), and windows on a shared link are disjoint, so no interferer is co-centred.  Admitted iff
  * GSNR_dB >= thresholds_db[SE - 1]; otherwise the step goes on as for a rejection -- not accepted, the rejection's reward, nothing
- * provisioned, no queue entry -- while act_path / act_slot still show the proposed action.  A policy proposes once: no next
- * path is tried.  The action masks stay "window free": they do not know the gate.
+ * provisioned, no queue entry -- while act_path / act_slot still show the proposed action.  The reference's policies propose
+ * once: no next path is tried; ORLG_POLICY_SAP_FF_GN is the first fit that goes on to the next path.  The action masks of
+ * orlg_action_masks and orlg_deeprmsa_observation_masked stay "window free" on every handle; the masks that know the gate are
+ * orlg_gn_action_masks.
  * Served by the wave-per-environment kernel only: a gated handle runs orlg_rmsa_kernel<W,STATS,false,true> at every batch size
  * and launch length (ORLG_KERNEL_AUTO resolves to WAVE); a handle without a gate runs exactly the kernels it ran before.  The gate
  * is configuration, not state: orlg_save_state / orlg_load_state do not carry it, gated and ungated handles load each other's
@@ -274,6 +283,19 @@ int orlg_deeprmsa_observation_masked(orlg_env *env, void *obs, int32_t obs_f32, 
  * accepts it, only the first-fit loops never try it); bits at and beyond S are 0.
  * Both NULL is ORLG_ERR_INVALID. */
 int orlg_action_masks(orlg_env *env, uint8_t *path_ff, uint64_t *slots);
+
+/* The masks that know the GN-model admission check (orlg_rmsa_gn_gate): mask[a] = 1 iff orlg_step(a) on THIS handle would accept
+ * the pending request.  Window, bandwidth, centre frequency, launch power, interferers (the services running now) and threshold
+ * are those of orlg_rmsa_gn_gate; the GSNR values have the bits of what the step compares.
+ * path_ff: [B][k + reject] uint8 or NULL -- the path_ff bit of orlg_action_masks AND the GSNR of the window [s, s + n), s the
+ * path's first fit in range(0, S - n), >= thresholds_db[SE - 1]: the outcome of ORLG_POLICY_PATH_FF_EXTERNAL.
+ * path_ff_gsnr_db: [B][k] float64 or NULL -- that GSNR in dB, NaN where the path has no first fit.
+ * deeprmsa: [B][k*j + reject] uint8 or NULL -- the mask bit of orlg_deeprmsa_observation_masked AND the GSNR of the first n slots
+ * of block a % j of route a / j >= the threshold: the outcome of ORLG_POLICY_DEEPRMSA_EXTERNAL.
+ * deeprmsa_gsnr_db: [B][k*j] float64 or NULL -- that GSNR, NaN where the block does not exist.
+ * The explicit rejection's column (orlg_set_allow_rejection) is always 1 and has no GSNR column.  Any pointer may be NULL; all
+ * NULL, or a handle without a gate, is ORLG_ERR_INVALID.  Buffers as orlg_action_masks. */
+int orlg_gn_action_masks(orlg_env *env, uint8_t *path_ff, double *path_ff_gsnr_db, uint8_t *deeprmsa, double *deeprmsa_gsnr_db);
 
 /* SimpleMatrixObservation.observation() (rmsa_env.py:940-971) for every env: [B][2N + E*S] uint8 */
 int orlg_simple_matrix_observation(orlg_env *env, uint8_t *out);

@@ -12,7 +12,7 @@ ERR_NAMES = {-1: "ORLG_ERR_INVALID", -2: "ORLG_ERR_NO_DEVICE", -3: "ORLG_ERR_HIP
 
 STATS_LEVELS = {"counters": 0, "network": 1, "full": 2}
 POLICIES = {"external": -1, "sp_ff": 0, "sap_ff": 1, "llp_ff": 2, "deeprmsa_sp_ff": 3, "deeprmsa_sap_ff": 4,
-            "deeprmsa_external": 5, "path_ff_external": 6}
+            "deeprmsa_external": 5, "path_ff_external": 6, "sap_ff_gn": 7}
 
 
 class OrlgError(RuntimeError):
@@ -134,7 +134,9 @@ def _prototypes():
               "orlg_deeprmsa_observation_masked": (None, [vp, vp, i32, vp]), "orlg_action_masks": (None, [vp, vp, vp]),
               # GN-model admission check inside the step
               "orlg_set_gn_gate": (None, [vp, P(RmsaGnGate)]),
-              "orlg_step_gn": (None, [vp, i32, i32, vp, i32, P(StepIO), vp])})
+              "orlg_step_gn": (None, [vp, i32, i32, vp, i32, P(StepIO), vp]),
+              # valid-action masks that know the admission check
+              "orlg_gn_action_masks": (None, [vp, vp, vp, vp, vp])})
     # QoT-aware only
     t.update({"orlg_phy_step": (None, [vp, i32, i32, vp, vp, i32, P(PhyStepIO)]), "orlg_phy_node_vectors": (None, [vp]),
               "orlg_phy_get_episode_stats": (None, [vp, vp]), "orlg_phy_channel_masks": (None, [vp, vp]),

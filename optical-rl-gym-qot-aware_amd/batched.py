@@ -204,36 +204,73 @@ class BatchedRMSAEnv(BatchedHandle):
         _lib.check(self.L.orlg_deeprmsa_observation_masked(self.h, _ptr(out), 1 if f32 else 0, _ptr(mask_out)))
         return out, mask_out
 
-    MASK_KINDS = ("deeprmsa", "path_ff", "slots")
+    MASK_KINDS = ("deeprmsa", "path_ff", "slots", "path_ff_gn", "deeprmsa_gn")
+    GN_MASK_KINDS = ("path_ff_gn", "deeprmsa_gn")   # the kinds that know the GN-model admission check (``gn_gate=``)
 
     def action_mask_shape(self, kind):
         """(shape, dtype) of ``action_masks(kind)``."""
         if kind not in self.MASK_KINDS:
             raise ValueError(f"kind {kind!r}: expected one of {self.MASK_KINDS}")
         B, k = self.batch_size, self.k_paths
-        if kind == "deeprmsa":
+        if kind in ("deeprmsa", "deeprmsa_gn"):
             return (B, k * self.j + self.reject_action), np.uint8
-        if kind == "path_ff":
+        if kind in ("path_ff", "path_ff_gn"):
             return (B, k + self.reject_action), np.uint8
         return (B, k, self.words_per_link), np.uint64
 
-    def action_masks(self, kind="deeprmsa", out=None):
-        """Valid actions of every env's pending request: ``mask[a] = 1`` iff the reference's ``step(a)`` would accept the
-        service.  The explicit rejection, where ``allow_rejection`` gives the action space one, is always 1.  The masks say
-        "the window is free": they do not know a GN-model admission check (``gn_gate=``), which may still refuse the service.
+    def action_mask_gsnr_shape(self, kind):
+        """(shape, dtype) of the GSNR rows that go with ``action_masks(kind, gsnr_out=...)``: one column per action, none for
+        the explicit rejection."""
+        if kind not in self.GN_MASK_KINDS:
+            raise ValueError(f"kind {kind!r} has no GSNR rows: expected one of {self.GN_MASK_KINDS}")
+        return (self.batch_size, self.k_paths * (self.j if kind == "deeprmsa_gn" else 1)), np.float64
 
+    def action_masks(self, kind="deeprmsa", out=None, gsnr_out=None):
+        """Valid actions of every env's pending request: ``mask[a] = 1`` iff ``step(a)`` would accept the service.  The explicit
+        rejection, where ``allow_rejection`` gives the action space one, is always 1.
+
+        The first three kinds say "the window is free" -- the reference's ``step(a)`` -- on every handle: they do not know a
+        GN-model admission check (``gn_gate=``), which may still refuse the service.
         ``"deeprmsa"``  [B, k*j + reject] uint8: action ``a`` = (route ``a // j``, block ``a % j``) is valid iff the route has
                         more than ``block`` free runs of at least ``get_number_slots(route)`` slots (``deeprmsa_env.py:48-58``).
         ``"path_ff"``   [B, k + reject] uint8: ``PathOnlyFirstFitAction.action(p)`` finds a slot -- some ``s`` in
                         ``range(0, S - n)`` is free (``rmsa_env.py:974-1008``; the bound is exclusive, as in the reference).
         ``"slots"``     [B, k, W] uint64, bit ``s`` of word ``w`` = slot ``64 w + s``: ``RMSAEnv.step([p, s])`` provisions --
                         ``s + n <= S`` and the window is free on every hop (start ``S - n`` included).
-        ``out`` may be a numpy array or a torch tensor (device tensors and pinned host tensors are written in place)."""
+        The ``_gn`` kinds exist on a handle with ``gn_gate=`` only and say what ITS step does (``orlg_gn_action_masks``):
+        ``"path_ff_gn"``   ``path_ff[p]`` and the GSNR of the path's first-fit window meets the threshold of its spectral
+                           efficiency: the outcome of ``step_path_first_fit(p)``.
+        ``"deeprmsa_gn"``  ``deeprmsa[a]`` and the GSNR of the first ``n`` slots of the block meets the threshold: the outcome of
+                           ``step_deeprmsa(a)``.
+        ``gsnr_out`` (these two kinds only): a float64 buffer [B, k] / [B, k*j], or ``True`` for a new array -- the GSNR in dB the
+        step would compare, NaN where there is no window; the call then returns ``(mask, gsnr)``.
+        ``out`` / ``gsnr_out`` may be numpy arrays or torch tensors (device tensors and pinned host tensors are written in
+        place)."""
         shape, dt = self.action_mask_shape(kind)
+        gn = kind in self.GN_MASK_KINDS
+        if gsnr_out is not None and gsnr_out is not False and not gn:
+            raise ValueError(f"gsnr_out: kind {kind!r} has no GSNR rows, they go with {self.GN_MASK_KINDS}")
+        if gn and self.gn_gate is None:
+            raise ValueError(f"kind {kind!r} needs a handle with a GN-model admission check (gn_gate=)")
         if out is None:
             out = np.zeros(shape, dt)
         else:
             _check_buffer("out", out, shape, dt)
+        if gn:
+            gsnr = None
+            if gsnr_out is True:
+                gsnr = np.zeros(self.action_mask_gsnr_shape(kind)[0], np.float64)
+            elif gsnr_out is not None and gsnr_out is not False:
+                _check_buffer("gsnr_out", gsnr_out, *self.action_mask_gsnr_shape(kind))
+                if not hasattr(gsnr_out, "data_ptr") and not gsnr_out.flags["WRITEABLE"]:
+                    raise ValueError("gsnr_out: read-only array")
+                gsnr = gsnr_out
+            gp = None if gsnr is None else _ptr(gsnr)
+            if kind == "path_ff_gn":
+                _lib.check(self.L.orlg_gn_action_masks(self.h, _ptr(out), gp, None, None))
+            else:
+                _lib.check(self.L.orlg_gn_action_masks(self.h, None, None, _ptr(out), gp))
+            return out if gsnr is None else (out, gsnr)
         if kind == "deeprmsa":
             _lib.check(self.L.orlg_deeprmsa_observation_masked(self.h, None, 0, _ptr(out)))
         elif kind == "path_ff":

@@ -544,7 +544,9 @@ static int rmsa_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t
                      const orlg_step_io *io, double *gsnr) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     if (n_steps < 1) return fail(ORLG_ERR_INVALID, "n_steps must be >= 1");
-    if (policy < ORLG_POLICY_EXTERNAL || policy > ORLG_POLICY_PATH_FF_EXTERNAL) return fail(ORLG_ERR_INVALID, "unknown policy %d", policy);
+    if (policy < ORLG_POLICY_EXTERNAL || policy > ORLG_POLICY_SAP_FF_GN) return fail(ORLG_ERR_INVALID, "unknown policy %d", policy);
+    if (policy == ORLG_POLICY_SAP_FF_GN && !e->p.gn)
+        return fail(ORLG_ERR_INVALID, "policy %d (sap_ff_gn) asks the GN-model admission check: the handle has no gn_gate", policy);
     const bool ext = policy == ORLG_POLICY_EXTERNAL || policy == ORLG_POLICY_DEEPRMSA_EXTERNAL || policy == ORLG_POLICY_PATH_FF_EXTERNAL;
     if (ext && (!actions || n_steps != 1)) return fail(ORLG_ERR_INVALID, "external actions need an action array and n_steps == 1");
     {
@@ -868,6 +870,36 @@ int orlg_action_masks(orlg_env *e, uint8_t *path_ff, uint64_t *slot_masks) {
                        reinterpret_cast<u64 *>(slots[1].dev));
     HIP_TRY(hipGetLastError());
     return collect_outputs(e, slots, 2);
+}
+
+int orlg_gn_action_masks(orlg_env *e, uint8_t *path_ff, double *path_ff_gsnr_db, uint8_t *deeprmsa, double *deeprmsa_gsnr_db) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!path_ff && !path_ff_gsnr_db && !deeprmsa && !deeprmsa_gsnr_db) return fail(ORLG_ERR_INVALID, "null argument: no mask or GSNR buffer");
+    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn action masks: the handle has no gn_gate");
+    HIP_TRY(hipSetDevice(e->device));
+    const OrlgParams &p = e->p;
+    const size_t B = (size_t)p.B, kj = (size_t)p.K * p.j;
+    OutSlot slots[4] = {{path_ff, B * (p.K + e->allow_rejection)}, {path_ff_gsnr_db, B * p.K * sizeof(double)},
+                        {deeprmsa, B * (kj + e->allow_rejection)}, {deeprmsa_gsnr_db, B * kj * sizeof(double)}};
+    int rc = place_outputs(e, slots, 4);
+    if (rc) return rc;
+    orlg_gn_action_masks_kernel_t k = orlg_pick_gn_action_masks(e->W);
+    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
+    // a wave holds its environment's occupancy row and the live descriptors of its release ring (up to Q): as many waves per
+    // workgroup as the LDS takes next to the tables
+    const size_t per_wave = (size_t)((p.NW * 8 + 15) & ~15) + (size_t)((p.Q * 4 + 15) & ~15);
+    int wpb = e->waves_per_block;
+    while (wpb > 1 && (size_t)p.l_shared_bytes + per_wave * wpb > ORLG_LDS_BYTES) --wpb;
+    const size_t lds = (size_t)p.l_shared_bytes + per_wave * wpb;
+    if (lds > ORLG_LDS_BYTES) return fail(ORLG_ERR_INVALID, "gn action masks: a release queue of %d entries does not fit the LDS next to the tables", p.Q);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int nblocks = (p.B + wpb - 1) / wpb;
+    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;   // as orlg_action_masks: each wave strides over its environments
+    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, reinterpret_cast<uint8_t *>(slots[0].dev),
+                       reinterpret_cast<double *>(slots[1].dev), reinterpret_cast<uint8_t *>(slots[2].dev),
+                       reinterpret_cast<double *>(slots[3].dev), e->allow_rejection);
+    HIP_TRY(hipGetLastError());
+    return collect_outputs(e, slots, 4);
 }
 
 int orlg_simple_matrix_obs_dim(orlg_env *e) { return e ? 2 * e->p.N + e->p.E * e->p.S : ORLG_ERR_INVALID; }

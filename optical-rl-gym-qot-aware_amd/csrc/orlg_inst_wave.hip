@@ -1,10 +1,11 @@
 // orlg_inst_wave.hip -- instantiations of the wave-per-environment kernels (orlg_kernels.hip, and the query and mask kernels of
-// orlg_query_kernels.hip and orlg_mask_kernels.hip, in the order the file always met them) for ONE word count,
+// orlg_query_kernels.hip, orlg_mask_kernels.hip and orlg_gn_mask_kernels.hip, in the order the file always met them) for ONE word count,
 // -DORLG_INST_W=<W>: one object per W, so that the library builds in parallel (build.py).  Which ones: orlg_variants.h.
 #include "orlg_host.h"
 #include "orlg_kernels.hip"
 #include "orlg_query_kernels.hip"
 #include "orlg_mask_kernels.hip"
+#include "orlg_gn_mask_kernels.hip"
 
 #ifndef ORLG_INST_W
 #error "compile with -DORLG_INST_W=<words per link>"
@@ -22,3 +23,4 @@ orlg_rmsa_kernel_t ORLG_CAT(orlg_wave_kernel_W, ORLG_INST_W)(OrlgWaveKey key) {
 orlg_masks_kernel_t ORLG_CAT(orlg_masks_kernel_W, ORLG_INST_W)() { return orlg_path_masks_kernel<ORLG_INST_W>; }
 orlg_obs_kernel_t ORLG_CAT(orlg_obs_kernel_W, ORLG_INST_W)() { return orlg_deeprmsa_obs_kernel<ORLG_INST_W>; }
 orlg_action_masks_kernel_t ORLG_CAT(orlg_action_masks_kernel_W, ORLG_INST_W)() { return orlg_action_masks_kernel<ORLG_INST_W>; }
+orlg_gn_action_masks_kernel_t ORLG_CAT(orlg_gn_action_masks_kernel_W, ORLG_INST_W)() { return orlg_gn_action_masks_kernel<ORLG_INST_W>; }

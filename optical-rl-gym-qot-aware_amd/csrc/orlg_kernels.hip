@@ -43,6 +43,20 @@
 // policies' code -- and the registers it pins -- is gone from the kernel the headline workload runs.
 // GN: the handle has a GN-model admission check (orlg_set_gn_gate): a window that is free is provisioned only if its GSNR meets the
 // threshold of the path's spectral efficiency (orlg_rmsa_gn.h); every other instantiation holds none of that code.
+// GN, policy sap_ff_gn: what a step keeps while it goes from a refused candidate to the next -- the candidate paths below `from`
+// have been refused by the admission check in this step (0: none yet; every other policy leaves it 0), (path, slot, gsnr) is the
+// first of them, which a refusal shows; exhausted: no further path has a fit.  Nothing without a gate.
+template <bool GN>
+struct SapRetry {
+    int from = 0, path = 0, slot = 0;
+    double gsnr = 0.0;
+    bool exhausted = false;
+};
+template <>
+struct SapRetry<false> {
+    SapRetry() = default;
+};
+
 template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false, bool GN = false>
 DEV void rmsa_body(const OrlgParams &p) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -190,6 +204,7 @@ DEV void rmsa_body(const OrlgParams &p) {
 
     // the per-link (span, gaps) cache and its sums travel with the state (they are a function of the occupancy)
     int sum_span = gs_sum_span, sum_gaps = gs_sum_gaps;
+    SapRetry<STEPK && GN> sap;
     if (NET) comp_cur = network_compactness(sum_span, sum_sh, sum_gaps, E);
 
     for (int t = 0; t < n_iter; ++t) {
@@ -244,11 +259,13 @@ DEV void rmsa_body(const OrlgParams &p) {
                     int s0 = find_block<W>(x, n, blk, lane, &len);
                     if (s0 >= 0) { a_path = route; a_slot = s0; }
                 }
-            } else if (LS == 8 && (policy == ORLG_POLICY_SP || policy == ORLG_POLICY_SAP)) {
+            } else if (LS == 8 && (policy == ORLG_POLICY_SP || policy == ORLG_POLICY_SAP || (GN && policy == ORLG_POLICY_SAP_GN))) {
+                // (sap_ff_gn proposes what sap_ff proposes, from the first path the check has not refused yet)
                 // first fit on every candidate path at once: the starts of free runs of >= n slots by shift-and-AND doubling over
                 // the path's words (run_starts), then the lowest (path, slot) of the wave
                 const int kmax = policy == ORLG_POLICY_SP ? 1 : K;
-                const bool on = pp < kmax && pw < W;
+                bool on = pp < kmax && pw < W;
+                if constexpr (GN) on = on && pp >= sap.from;
                 int n_l = 1;
                 if (on) n_l = tb.nslots[req_br * ORLG_NSLOT_STRIDE + se_l];
                 u64 r = run_starts<W>(on ? acc : 0ull, n_l, pw);
@@ -259,7 +276,9 @@ DEV void rmsa_body(const OrlgParams &p) {
             } else {
                 int max_free = 0;
                 const int kmax = (policy == ORLG_POLICY_SP || policy == ORLG_POLICY_DEEP_SP) ? 1 : K;
-                for (int idp = 0; idp < kmax; ++idp) {
+                int idp0 = 0;
+                if constexpr (GN) idp0 = sap.from;
+                for (int idp = idp0; idp < kmax; ++idp) {
                     u64 x[W];
 #pragma unroll
                     for (int w = 0; w < W; ++w) x[w] = readlane64(acc, idp * LS + w);
@@ -290,6 +309,10 @@ DEV void rmsa_body(const OrlgParams &p) {
             const double prev_compact = comp_cur;
             bool accepted = false;
             double gn_gsnr = __longlong_as_double(0x7ff8000000000000ll);   // GN: the GSNR the check compared, NaN = no check ran
+            if constexpr (GN) {   // sap_ff_gn: no further path has a fit, the step is the refusal of the first candidate
+                sap.exhausted = sap.from > 0 && a_path == K;
+                if (sap.exhausted) { a_path = sap.path; a_slot = sap.slot; }
+            }
             if (a_path >= 0 && a_path < K && a_slot >= 0 && a_slot < S) {
                 const int n = __builtin_amdgcn_readlane(my_n, a_path);
                 // the device policies only propose windows they found free; agent actions are checked (is_path_free)
@@ -301,11 +324,24 @@ DEV void rmsa_body(const OrlgParams &p) {
                     window_ok = window_free<W>(x, a_slot, n, S);
                 }
                 if constexpr (GN) {
-                    if (window_ok) {
+                    if (sap.exhausted) {
+                        gn_gsnr = sap.gsnr;
+                        window_ok = false;
+                    } else if (window_ok) {
                         const OrlgGnTable gn = ORLG_GPTR(const double, p.gn);
                         const OrlgPathRec *cand = tb.recs + (base + a_path);
                         gn_gsnr = rmsa_gn_gsnr(wv, tb, gn, E, Q, q_head, q_n, cand, a_slot, n);
                         window_ok = gn_gsnr >= gn[ORLG_GN_THR0 + (int)cand->se - 1];
+                        // sap_ff_gn (QoT-aware shortest available path, first fit; not in the reference, include/orlg.h
+                        // ORLG_POLICY_SAP_FF_GN): a refused window is followed by the first fit of the next path that has one --
+                        // the step starts over at its policy, which nothing has changed yet, from the path behind this one.  Each
+                        // candidate is checked once; when the paths end, the refusal shows the first candidate
+                        if (policy == ORLG_POLICY_SAP_GN && !window_ok) {
+                            if (sap.from == 0) { sap.path = a_path; sap.slot = a_slot; sap.gsnr = gn_gsnr; }
+                            sap.from = a_path + 1;
+                            --t;
+                            continue;
+                        }
                     }
                 }
                 if (window_ok) {
@@ -400,6 +436,7 @@ DEV void rmsa_body(const OrlgParams &p) {
             if constexpr (GN) {
                 if (lane == 0 && p.o_gsnr) ORLG_GPTR(double, p.o_gsnr)[(size_t)t * p.B + env] = gn_gsnr;
             }
+            if constexpr (GN) sap.from = 0;
             new_service = 0;
         } else if (p.mode == ORLG_MODE_EPISODE_RESET) {
             // reset(only_episode_counters=True) (rmsa_env.py:343-389)

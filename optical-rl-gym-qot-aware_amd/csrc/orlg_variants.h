@@ -133,6 +133,7 @@ typedef void (*orlg_rmsa_kernel_t)(const OrlgParams);
 typedef void (*orlg_masks_kernel_t)(const OrlgParams, int, int, int, uint64_t *, int32_t *);   // orlg_path_masks_kernel
 typedef void (*orlg_obs_kernel_t)(const OrlgParams, uint8_t *, int);                          // orlg_deeprmsa_obs_kernel
 typedef void (*orlg_action_masks_kernel_t)(const OrlgParams, uint8_t *, int, uint64_t *);     // orlg_action_masks_kernel
+typedef void (*orlg_gn_action_masks_kernel_t)(const OrlgParams, uint8_t *, double *, uint8_t *, double *, int);   // orlg_gn_action_masks_kernel
 typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
 #define ORLG_FOR_EACH_W(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__) X(6, __VA_ARGS__) X(8, __VA_ARGS__)
 #define ORLG_FOR_EACH_PHY_W(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__)
@@ -141,6 +142,7 @@ typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
     orlg_masks_kernel_t orlg_masks_kernel_W##n() __attribute__((weak));                           \
     orlg_obs_kernel_t orlg_obs_kernel_W##n() __attribute__((weak));                               \
     orlg_action_masks_kernel_t orlg_action_masks_kernel_W##n() __attribute__((weak));             \
+    orlg_gn_action_masks_kernel_t orlg_gn_action_masks_kernel_W##n() __attribute__((weak));       \
     orlg_rmsa_kernel_t orlg_group_kernel_W##n(OrlgGroupKey) __attribute__((weak));
 #define ORLG_DECL_PHY_W(n, ...)                                                                   \
     orlg_phy_kernel_t orlg_phy_kernel_W##n(OrlgPhyKey) __attribute__((weak));                     \
@@ -162,3 +164,4 @@ static orlg_phy_kernel_t orlg_pick(int W, const OrlgPhyKey &key) {   // the TRAC
 static orlg_masks_kernel_t orlg_pick_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_masks_kernel_W, ) }
 static orlg_obs_kernel_t orlg_pick_obs(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_obs_kernel_W, ) }
 static orlg_action_masks_kernel_t orlg_pick_action_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_action_masks_kernel_W, ) }
+static orlg_gn_action_masks_kernel_t orlg_pick_gn_action_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_action_masks_kernel_W, ) }

@@ -283,10 +283,15 @@ class RMSAEnv(_View):
         bits = np.unpackbits(words.view(np.uint8), axis=-1, bitorder="little")[:, :self.num_spectrum_resources]
         return bits.astype(bool)
 
-    def action_masks(self):
+    def action_masks(self, gn=False):
         """Valid actions of ``MultiDiscrete(path, slot)`` for the pending request: bool [k + reject, S + reject], True where
         ``step([p, s])`` would provision the service (``rmsa_env.py:233-260``).  With ``allow_rejection`` the extra row and
-        column belong to the explicit rejection ``[k, S]``: only their corner is True."""
+        column belong to the explicit rejection ``[k, S]``: only their corner is True.  "The window is free": a GN-model
+        admission check (``gn_gate=``) may still refuse it, and ``gn=True`` is refused -- a slot matrix that knows the gate
+        would be ``k S`` GSNR evaluations per environment."""
+        if gn:
+            raise ValueError("action_masks(gn=True): there is no slot matrix that knows the GN-model admission check (k * S GSNR "
+                             "evaluations per environment); the gated masks are DeepRMSAEnv's and PathOnlyFirstFitAction's")
         k, S, r = self.k_paths, self.num_spectrum_resources, self.reject_action
         m = np.zeros((k + r, S + r), bool)
         m[:k, :S] = self._slot_bits()
@@ -418,10 +423,11 @@ class DeepRMSAEnv(RMSAEnv):
     def _get_route_block_id(self, action: int) -> Tuple[int, int]:
         return action // self.j, action % self.j
 
-    def action_masks(self):
+    def action_masks(self, gn=False):
         """Valid actions of ``Discrete(k*j + reject)`` for the pending request: bool [k*j + reject], True where ``step(a)``
-        would accept the service (the method maskable-PPO implementations look for)."""
-        return self._batched.action_masks("deeprmsa")[self._index].astype(bool)
+        would accept the service (the method maskable-PPO implementations look for).  ``gn=True`` (a ``gn_gate=`` environment):
+        the mask that knows the GN-model admission check, ``BatchedRMSAEnv.action_masks("deeprmsa_gn")``."""
+        return self._batched.action_masks("deeprmsa_gn" if gn else "deeprmsa")[self._index].astype(bool)
 
 
 class SimpleMatrixObservation:
@@ -473,9 +479,10 @@ class PathOnlyFirstFitAction:
                     return (action, s)
         return (e.topology.graph["k_paths"], e.topology.graph["num_spectrum_resources"])
 
-    def action_masks(self):
-        """Valid paths for the pending request: bool [k + reject], True where ``action(p)`` finds a slot."""
-        return self._inner._batched.action_masks("path_ff")[self._inner._index].astype(bool)
+    def action_masks(self, gn=False):
+        """Valid paths for the pending request: bool [k + reject], True where ``action(p)`` finds a slot.  ``gn=True`` (a
+        ``gn_gate=`` environment): ... and the GN-model admission check admits that window (``"path_ff_gn"``)."""
+        return self._inner._batched.action_masks("path_ff_gn" if gn else "path_ff")[self._inner._index].astype(bool)
 
     def step(self, action):
         return self.env.step(self.action(action))
@@ -504,6 +511,25 @@ def shortest_available_path_first_fit(env: RMSAEnv) -> Tuple[int, int]:
         for s in range(0, S - n):
             if env.is_path_free(path, s, n):
                 return (idp, s)
+    return (k, S)
+
+
+def shortest_available_path_first_fit_gn(env: RMSAEnv) -> Tuple[int, int]:
+    """QoT-aware SAP-FF on a ``gn_gate=`` environment (not in the reference): what the device policy ``"sap_ff_gn"`` proposes.
+    The first path whose first-fit window the admission check admits (``action_masks("path_ff_gn")`` of this environment); if
+    none is admitted, the first path that has a first fit -- the step then refuses it, as the device policy's step is refused;
+    if no path has one, the rejection."""
+    S, k = env.topology.graph["num_spectrum_resources"], env.topology.graph["k_paths"]
+    mask, gsnr = env._batched.action_masks("path_ff_gn", gsnr_out=True)
+    admitted, fits = np.flatnonzero(mask[env._index, :k]), np.flatnonzero(np.isfinite(gsnr[env._index]))
+    if fits.size == 0:
+        return (k, S)
+    idp = int(admitted[0] if admitted.size else fits[0])
+    path = env.k_shortest_paths[env.current_service.source, env.current_service.destination][idp]
+    n = env.get_number_slots(path)
+    for s in range(0, S - n):
+        if env.is_path_free(path, s, n):
+            return (idp, s)
     return (k, S)
 
 
