@@ -258,7 +258,9 @@
                     const uint32_t fs = seg_add<W>((uint32_t)popc64(x));
                     const uint32_t fit = seg_max<W>(r ? (uint32_t)(0x7fff - (64 * w + ctz64(r))) : 0u);
                     const bool head = on && w == 0 && fit != 0u;
-                    const int key = head ? (int)(((1023u - fs) << 4) | (uint32_t)pp) : 0x7fffffff;   // most free slots, then lowest path
+                    // most free slots, then lowest path: six bits of path (k W <= 64 allows k = 64; four bits let a path 16 and
+                    // above spill into the free-slot count)
+                    const int key = head ? (int)(((1023u - fs) << 6) | (uint32_t)pp) : 0x7fffffff;
                     const int bk = row_min_i32(key);
                     const int payload = (head && key == bk) ? ((((pp << 10) | (0x7fff - (int)fit)) << 14) | (n << 4) | hops_pp) : 0x7fffffff;
                     const int bp = row_min_i32(payload);

@@ -9,7 +9,6 @@ import functools
 import numpy as np
 
 import gn_gate_reference as ref
-from conftest import load_topology
 from gpu_support import device_log_in_oracle
 
 N_STEPS = 300
@@ -85,28 +84,34 @@ def _run(go, policy, n_steps):
     return tr, later
 
 
-@functools.lru_cache(maxsize=None)
 def run_case(case, seed=None, j=1, policy=None, n_steps=N_STEPS, gate_items=(), kw_items=()):
-    """One environment of a case of gn_gate_reference.CASES (seed, policy: the case's own by default) on the candidate oracle,
-    run once per process and shared: (per-step arrays -- the gated oracle's and MASK_FIELDS, the masks taken BEFORE the step --,
-    final state, figures).  Read-only by agreement."""
-    c = ref.CASES[case]
-    topo = load_topology(c["topology"])
-    kw = ref.case_kwargs(case, **dict(kw_items))
+    """One environment of a case -- a name of gn_gate_reference.CASES (seed, policy: the case's own by default) or a (topology,
+    kwargs) pair with its `policy` -- on the candidate oracle, run once per process and shared: (per-step arrays -- the gated
+    oracle's and MASK_FIELDS, the masks taken BEFORE the step --, final state, figures).  Read-only by agreement."""
+    return _run_case(ref.cache_key(case), seed, j, policy, n_steps, tuple(gate_items), tuple(kw_items))
+
+
+@functools.lru_cache(maxsize=None)
+def _run_case(key, seed, j, policy, n_steps, gate_items, kw_items):
+    topo, kw, policy = ref.resolve_case(key if isinstance(key, str) else (key[0], dict(key[1])), policy)
+    kw.update(dict(kw_items))
     with device_log_in_oracle():
         go = CandidateOracle(topo, kw, ref.case_gate(topo, **dict(gate_items)), seed=seed, j=j)
-        tr, later = _run(go, policy or c["policy"], n_steps)
+        tr, later = _run(go, policy, n_steps)
     o = go.o
     final = dict(available_slots=o.available_slots(), counters=o.counters(), num_running=o.num_running(),
                  current_time=o.current_time())
     figures = dict(checks=go.checks, rejects=go.rejects, max_running=go.max_running, later_taken=later,
-                   provisions=int(tr["accepted"].sum()))
+                   provisions=int(tr["accepted"].sum()), closest=float(np.min(tr["margin"])))
     go.close()
     for a in tr.values():
         a.setflags(write=False)
     return tr, final, figures
 
 
-def run_batch(case, j=1, policy=None, n_steps=N_STEPS, batch=B, **kw):
-    """run_case for the seeds case seed + 0 .. batch - 1: a list of its results"""
-    return [run_case(case, seed=ref.CASES[case]["seed"] + i, j=j, policy=policy, n_steps=n_steps, **kw) for i in range(batch)]
+def run_batch(case, j=1, policy=None, n_steps=N_STEPS, batch=B, seed=None, **kw):
+    """run_case for the seeds seed + 0 .. batch - 1 (seed: the case's own; a (topology, kwargs) pair's is its kwargs'): a list of
+    its results"""
+    if seed is None:
+        seed = ref.CASES[case]["seed"] if isinstance(case, str) else case[1]["seed"]
+    return [run_case(case, seed=seed + i, j=j, policy=policy, n_steps=n_steps, **kw) for i in range(batch)]

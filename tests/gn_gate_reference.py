@@ -147,16 +147,36 @@ class GatedOracle:
         return {k: np.array([row[k] for row in rows]) for k in rows[0]}
 
 
+def resolve_case(case, policy=None):
+    """(topology, keyword arguments, policy) of a case: a name of CASES, or a (topology, kwargs) pair -- the kwargs as case_kwargs
+    gives them for the names; the pair needs its policy named."""
+    if isinstance(case, str):
+        c = CASES[case]
+        return load_topology(c["topology"]), case_kwargs(case), policy or c["policy"]
+    topo, kw = case
+    assert policy is not None, "a (topology, kwargs) case has no policy of its own"
+    return topo, dict(kw), policy
+
+
+def cache_key(case):
+    """A case as the key of the per-process caches: the name, or (topology, sorted kwargs items); the topology object by identity,
+    so the caller keeps one object per topology."""
+    return case if isinstance(case, str) else (case[0], tuple(sorted(dict(case[1]).items())))
+
+
+def run_case(case, seed=None, n_steps=N_STEPS, gate_items=(), policy=None):
+    """The gated oracle of a case -- a name of CASES or a (topology, kwargs) pair with its `policy` -- (seed: the case's own by
+    default), run once per process and shared: (per-step arrays, final state, figures).  The results are read-only by
+    agreement."""
+    return _run_case(cache_key(case), seed, n_steps, tuple(gate_items), policy)
+
+
 @functools.lru_cache(maxsize=None)
-def run_case(case, seed=None, n_steps=N_STEPS, gate_items=()):
-    """The gated oracle of a case (seed: the case's own by default), run once per process and shared: (per-step arrays, final
-    state, figures).  The results are read-only by agreement."""
-    c = CASES[case]
-    topo = load_topology(c["topology"])
-    kw = case_kwargs(case)
+def _run_case(key, seed, n_steps, gate_items, policy):
+    topo, kw, policy = resolve_case(key if isinstance(key, str) else (key[0], dict(key[1])), policy)
     with device_log_in_oracle():
         go = GatedOracle(topo, kw, case_gate(topo, **dict(gate_items)), seed=seed)
-        tr = go.run(c["policy"], n_steps)
+        tr = go.run(policy, n_steps)
     o = go.o
     final = dict(available_slots=o.available_slots(), counters=o.counters(), num_running=o.num_running(),
                  current_time=o.current_time())

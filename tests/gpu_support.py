@@ -1,6 +1,7 @@
 """Scaffolding of the GPU tests, each piece once: the oracle on the device's logarithm, the step-kernel fixture, handle factories,
 the tooling environment, a launch driver, read-backs and their byte-for-byte comparison, the comparison with the oracle, the
-expected instantiation names, external actions, the group kernel's launch plan, the action masks, synthetic grids.  Test modules
+expected instantiation names, external actions, the group kernel's launch plan, the action masks, synthetic grids, the shapes
+of more than eight candidate paths.  Test modules
 import from here and never from each other.  Importing this module needs no GPU and loads neither the library nor the oracle:
 both are imported inside the functions that use them."""
 import contextlib
@@ -355,15 +356,21 @@ def kernel_name(family, W_or_S, stats, *, hbmq=False, defer=False, traffic=False
 def external_actions(topo, S, n, batch, seed=123, kind="third_low"):
     """Random external actions [n, batch, 2] int32: paths 0 .. K (K: out of range), slots 0 .. S (S: out of range).
     kind "third_low": a third of the steps aim low (slot // 8), where first-fit neighbours would be -- windows at slot 0, occupied
-    ones; "quarter": every slot // 4; "paths": the paths alone, [n, batch] (path_ff_external)."""
+    ones; "quarter": every slot // 4; "paths": the paths alone, [n, batch] (path_ff_external); "high_paths" (k_paths > 8): as
+    "third_low", and five actions of eight have their path redrawn from 8 .. K - 1 -- more than half aim at a path the step
+    kernels lay out W lanes apart -- the others keep paths 0 .. K and the slots keep S: out of range in either component."""
     rng = np.random.default_rng(seed)
     paths = rng.integers(0, topo.k_paths + 1, (n, batch))
     if kind == "paths":
         return paths.astype(np.int32)
     slots = rng.integers(0, S + 1, (n, batch))
     a = np.stack([paths, slots // 4 if kind == "quarter" else slots], axis=-1).astype(np.int32)
-    if kind == "third_low":
+    if kind in ("third_low", "high_paths"):
         a[::3, :, 1] //= 8
+    if kind == "high_paths":
+        assert topo.k_paths > 8
+        high = rng.integers(8, topo.k_paths, (n, batch))
+        a[..., 0] = np.where(rng.random((n, batch)) < 0.625, high, a[..., 0])
     return a
 
 
@@ -482,3 +489,36 @@ def grid_edges(rows, cols, rng):
             if r + 1 < rows and c + 1 < cols and (r + c) % 2 == 0:
                 edges.append((node(r, c), node(r + 1, c + 1), int(rng.integers(80, 500))))
     return edges
+
+
+# ---------------------------------------------------------------------------------------- more than eight candidate paths
+# The shapes of test_many_paths.py (which pins on the CPU what they exercise) and test_gpu_many_paths.py: grid_edges(rows, cols,
+# default_rng(5)) with k candidate paths per pair, S slots = W words per link, E links, load = 0.5 S E / 40 rounded (3x3: 8, where
+# llp_ff takes path 8 most often -- DESIGN 4), the device policy of the step-parity cases.  W = 8 cannot have K > 8 (8 x 9 > 64 lanes).
+MANY_PATHS = {
+    "g3x3_k9_s64": dict(rows=3, cols=3, k=9, S=64, W=1, E=14, load=8, policy="sap_ff"),
+    "g4x4_k32_s100": dict(rows=4, cols=4, k=32, S=100, W=2, E=29, load=36, policy="llp_ff"),
+    "g4x4_k21_s192": dict(rows=4, cols=4, k=21, S=192, W=3, E=29, load=70, policy="sap_ff"),
+    "g4x4_k16_s200": dict(rows=4, cols=4, k=16, S=200, W=4, E=29, load=72, policy="sap_ff"),
+    "g4x4_k12_s320": dict(rows=4, cols=4, k=12, S=320, W=5, E=29, load=116, policy="llp_ff"),
+    "g3x4_k10_s384": dict(rows=3, cols=4, k=10, S=384, W=6, E=20, load=96, policy="llp_ff"),
+}
+MANY_PATHS_SEED = 3   # environment i of a batch: seed 3 + i
+_many_paths = {}
+
+
+def many_paths_topology(name, tmp_path):
+    """The topology of a MANY_PATHS shape, frozen once per process (the link list is written under the first caller's tmp_path)."""
+    if name not in _many_paths:
+        from optical_rl_gym_amd.topology_io import topology_from_txt
+        c = MANY_PATHS[name]
+        edges = grid_edges(c["rows"], c["cols"], np.random.default_rng(5))
+        _many_paths[name] = topology_from_txt(write_topology(tmp_path, name, c["rows"] * c["cols"], edges), name, k_paths=c["k"])
+    return _many_paths[name]
+
+
+def many_paths_kwargs(name, **over):
+    """BatchedRMSAEnv / oracle keyword arguments of a MANY_PATHS shape (without the topology)."""
+    c = MANY_PATHS[name]
+    return dict(dict(num_spectrum_resources=c["S"], load=c["load"], mean_service_holding_time=25, episode_length=200,
+                     seed=MANY_PATHS_SEED), **over)

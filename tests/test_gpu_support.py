@@ -133,3 +133,19 @@ def test_external_actions_are_the_arrays_they_were(args, shape, digest, first):
     assert hashlib.sha256(a.tobytes()).hexdigest()[:16] == digest
     if kind == "third_low":
         assert external_actions(types.SimpleNamespace(k_paths=K), S, n, batch).tobytes() == a.tobytes()   # the defaults
+
+
+@pytest.mark.parametrize("K,S", [(9, 64), (10, 384), (32, 100)])
+def test_external_actions_aimed_at_the_high_paths(K, S):
+    """kind "high_paths": more than half of the actions name a path 8 .. K - 1, both components go out of range, a third of the
+    steps aim low as "third_low" does, and the actions left alone are the ones "third_low" gives."""
+    topo = types.SimpleNamespace(k_paths=K)
+    a, low = external_actions(topo, S, 150, 6, kind="high_paths"), external_actions(topo, S, 150, 6)
+    assert a.shape == (150, 6, 2) and a.dtype == np.int32
+    high = (a[..., 0] >= 8) & (a[..., 0] < K)
+    assert high.mean() > 0.55
+    assert (a[..., 0] == K).any() and (a[..., 1] == S).any() and a.min() == 0 and a[..., 0].max() == K and a[..., 1].max() == S
+    assert np.array_equal(a[..., 1], low[..., 1]) and np.array_equal(a[~high], low[~high])
+    assert (a[..., 0] != low[..., 0]).mean() > 0.4
+    with pytest.raises(AssertionError):
+        external_actions(types.SimpleNamespace(k_paths=8), S, 4, 2, kind="high_paths")
