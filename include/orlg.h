@@ -220,6 +220,50 @@ int orlg_set_gn_gate(orlg_env *env, const orlg_rmsa_gn_gate *gate);
 int orlg_step_gn(orlg_env *env, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
                  const orlg_step_io *io, double *gn_gsnr_db);
 
+/* ---- why a request was refused (not in the reference).  Both definitions look only at the occupancy the step met,
+ * at `accepted` and at whether the GN-model admission check refused; they are the same for every policy and every action.
+ * For the pending request, n = get_number_slots(p) of candidate path p (links l_1..l_h), free(l) = the free slots of link l:
+ * FIT LEVEL of a path, the highest that holds: */
+enum {
+    ORLG_FIT_CAPACITY = 0,     /* some link has fewer than n free slots (n > S included) */
+    ORLG_FIT_CONTIGUITY = 1,   /* every link has >= n free slots, but some link has no run of n */
+    ORLG_FIT_ALIGNMENT = 2,    /* every link on its own has a free run of >= n slots, but the runs do not line up */
+    ORLG_FIT_LAST_WINDOW = 3,  /* [S-n, S) is free on every link and no window below it is: step([p, S-n]) accepts it, the
+                                * reference's first-fit loops (range(0, S - n)) never try it */
+    ORLG_FIT_FIT = 4,          /* some s in range(0, S - n) has [s, s+n) free on every link: the path_ff bit of orlg_action_masks */
+    ORLG_NUM_FIT_LEVELS = 5
+};
+/* BLOCKING CAUSE of a step; L = the highest fit level over ALL k candidate paths, whatever the policy looked at: */
+enum {
+    ORLG_CAUSE_ACCEPTED = 0,     /* the service was accepted (also one the release queue then lost to an overflow) */
+    ORLG_CAUSE_CAPACITY = 1,     /* not accepted, no GN refusal, L = 0 */
+    ORLG_CAUSE_CONTIGUITY = 2,   /* ... L = 1 */
+    ORLG_CAUSE_ALIGNMENT = 3,    /* ... L = 2 */
+    ORLG_CAUSE_LAST_WINDOW = 4,  /* ... L = 3 */
+    ORLG_CAUSE_POLICY = 5,       /* ... L = 4: a first fit existed and the action did not take it (sp_ff off its first path, an
+                                  * agent's wrong, out-of-range or explicit-reject action, a DeepRMSA block that does not exist) */
+    ORLG_CAUSE_GN = 6,           /* not accepted and the GN-model admission check ran on the proposed window: exactly the steps
+                                  * whose gn_gsnr_db is not NaN and that are not accepted; takes precedence over 1..5 */
+    ORLG_NUM_CAUSES = 8          /* (code 7 is unused: its count is always 0) */
+};
+struct orlg_step_diag {   /* (no typedef: the entry point below has the name; say `struct orlg_step_diag`) */
+    uint8_t *block_cause;    /* [n_steps][B] ORLG_CAUSE_* of every step */
+    int32_t *cause_counts;   /* [B][ORLG_NUM_CAUSES] steps of THIS launch per cause; the library zeroes it on the stream before
+                              * the launch (the caller need not clear it); every row sums to n_steps */
+    double *gn_gsnr_db;      /* [n_steps][B] as orlg_step_gn */
+};
+/* orlg_step plus the outputs of `diag`; any of its pointers, or diag itself, may be NULL -- all NULL is exactly orlg_step and
+ * launches the kernel orlg_step launches.  A launch that asks for block_cause or cause_counts runs an instantiation of the step
+ * kernel that holds the classifier (orlg_rmsa_kernel<.., CAUSE> / orlg_rmsa_group_kernel<.., CAUSE>, the plain kind of either):
+ * the same steps, the same state, the same other outputs.  Buffers as the per-step outputs of orlg_step: device memory is
+ * written in place, host memory (pinned or pageable) through a buffer of the handle, and the call then waits. */
+int orlg_step_diag(orlg_env *env, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
+                   const orlg_step_io *io, const struct orlg_step_diag *diag);
+/* The fit level (ORLG_FIT_*) of every candidate path of every pending request: levels [B][k] uint8.  Reads state and writes
+ * only `levels`; looks at windows only on every handle (it does not know a GN-model admission check).  levels == 4 is the
+ * path_ff bit of orlg_action_masks, levels >= 3 is "any bit in its slots mask".  Buffer as orlg_action_masks. */
+int orlg_path_fit_levels(orlg_env *env, uint8_t *levels);
+
 /* state read-back (all arrays [B] or [B][...] env-major) */
 int orlg_get_requests(orlg_env *env, orlg_request *out /* [B] */);
 int orlg_get_counters(orlg_env *env, orlg_counters *out /* [B] */);

@@ -1,5 +1,5 @@
 from . import _lib, envs, trace, traffic
-from ._lib import OrlgError
+from ._lib import BLOCK_CAUSES, FIT_LEVELS, OrlgError
 from .batched import DEFAULT_BIT_RATES, BatchedDeepRMSAEnv, BatchedRMSAEnv
 from .envs import (DeepRMSAEnv, PathOnlyFirstFitAction, RMSAEnv, SimpleMatrixObservation, deeprmsa_shortest_available_path_first_fit,
                    deeprmsa_shortest_path_first_fit, evaluate_heuristic, least_loaded_path_first_fit,
@@ -22,4 +22,4 @@ __all__ = ["ENV_IDS", "env_class", "make", "register_with_gym", "FrozenTopology"
            "shortest_available_path_first_fit_gn",
            "least_loaded_path_first_fit", "deeprmsa_shortest_path_first_fit",
            "deeprmsa_shortest_available_path_first_fit", "random_policy", "evaluate_heuristic",
-           "traffic", "make_sweep", "write_monitor_tree", "trace", "RequestTrace", "TraceError", "record_trace"]
+           "traffic", "make_sweep", "BLOCK_CAUSES", "FIT_LEVELS", "write_monitor_tree", "trace", "RequestTrace", "TraceError", "record_trace"]

@@ -52,6 +52,16 @@ STEP_IO_DTYPES = {"act_path": "int32", "act_slot": "int32", "accepted": "uint8",
                   "network_compactness_difference": "float64", "avg_link_compactness": "float64",
                   "avg_link_utilization": "float64"}
 
+# include/orlg.h ORLG_CAUSE_* / ORLG_FIT_*: why a step refused its request, and how far a candidate path is from fitting it
+BLOCK_CAUSES = ("accepted", "capacity", "contiguity", "alignment", "last_window", "policy", "gn")
+NUM_CAUSES = 8   # ORLG_NUM_CAUSES: the row length of cause_counts (code 7 is unused, always 0)
+FIT_LEVELS = ("capacity", "contiguity", "alignment", "last_window", "fit")
+
+
+class StepDiag(C.Structure):   # include/orlg.h struct orlg_step_diag
+    _fields_ = [("block_cause", C.c_void_p), ("cause_counts", C.c_void_p), ("gn_gsnr_db", C.c_void_p)]
+
+
 class Traffic(C.Structure):   # include/orlg.h orlg_traffic
     _fields_ = [("arrival_lambda", C.c_void_p), ("holding_lambda", C.c_void_p), ("group", C.c_void_p),
                 ("num_groups", C.c_int32)]
@@ -136,7 +146,10 @@ def _prototypes():
               "orlg_set_gn_gate": (None, [vp, P(RmsaGnGate)]),
               "orlg_step_gn": (None, [vp, i32, i32, vp, i32, P(StepIO), vp]),
               # valid-action masks that know the admission check
-              "orlg_gn_action_masks": (None, [vp, vp, vp, vp, vp])})
+              "orlg_gn_action_masks": (None, [vp, vp, vp, vp, vp]),
+              # blocking cause per step, fit level per candidate path
+              "orlg_step_diag": (None, [vp, i32, i32, vp, i32, P(StepIO), P(StepDiag)]),
+              "orlg_path_fit_levels": (None, [vp, vp])})
     # QoT-aware only
     t.update({"orlg_phy_step": (None, [vp, i32, i32, vp, vp, i32, P(PhyStepIO)]), "orlg_phy_node_vectors": (None, [vp]),
               "orlg_phy_get_episode_stats": (None, [vp, vp]), "orlg_phy_channel_masks": (None, [vp, vp]),

@@ -92,11 +92,17 @@ class BatchedRMSAEnv(BatchedHandle):
 
     # ------------------------------------------------------------------ stepping
     def run(self, policy: str, n_steps: int = 1, *, actions=None, auto_reset: bool = False,
-            outputs: Sequence[str] = (), out: Optional[Dict[str, object]] = None):
+            outputs: Sequence[str] = (), out: Optional[Dict[str, object]] = None, cause_counts=None):
         """``n_steps`` x (policy -> step) on the device.  ``outputs`` names per-step arrays to return
         (see ``_lib.STEP_IO_DTYPES``) as numpy arrays of shape [n_steps, B(, 4)]; ``out`` may supply
         preallocated numpy arrays or torch tensors (device tensors are written without staging).  ``"gn_gsnr_db"``: the GSNR
-        the GN-model admission check compared (``gn_gate=``), NaN where no check ran; it leaves through ``orlg_step_gn``."""
+        the GN-model admission check compared (``gn_gate=``), NaN where no check ran; it leaves through ``orlg_step_gn``.
+
+        Why a request was refused (``orlg_step_diag``; codes ``BLOCK_CAUSES``, include/orlg.h ``ORLG_CAUSE_*``):
+        ``"block_cause"`` in ``outputs`` -- [n_steps, B] uint8, the cause of every step; ``cause_counts=True`` or a [B, 8] int32
+        buffer -- ``"block_cause_counts"``, the steps of THIS launch per cause (the library zeroes the buffer; a row sums to
+        ``n_steps``).  Either one makes the launch run the step kernel's instantiation with the classifier: the same steps,
+        state and outputs, some percent slower."""
         B = self.batch_size
         io = _lib.StepIO()
         names = _output_names(outputs, out)
@@ -104,6 +110,16 @@ class BatchedRMSAEnv(BatchedHandle):
         if "gn_gsnr_db" in names:
             names = [n for n in names if n != "gn_gsnr_db"]
             gsnr = self._step_outputs(["gn_gsnr_db"], n_steps, out, {"gn_gsnr_db": "float64"}, {})
+        diag = {}
+        if "block_cause" in names:
+            names = [n for n in names if n != "block_cause"]
+            diag.update(self._step_outputs(["block_cause"], n_steps, out, {"block_cause": "uint8"}, {}))
+        if cause_counts is not None and cause_counts is not False:
+            if cause_counts is True:
+                cause_counts = np.zeros((B, _lib.NUM_CAUSES), np.int32)
+            else:
+                _check_buffer("out[cause_counts]", cause_counts, (B, _lib.NUM_CAUSES), np.int32)
+            diag["block_cause_counts"] = cause_counts
         res = self._step_outputs(names, n_steps, out, _lib.STEP_IO_DTYPES, _STEP_IO_SHAPES, io)
         ap = None
         if policy in ("external", "deeprmsa_external", "path_ff_external"):
@@ -117,7 +133,14 @@ class BatchedRMSAEnv(BatchedHandle):
                 actions = np.ascontiguousarray(actions, dtype=np.int32)
             _check_buffer("actions", actions, ashape, np.int32)
             ap = _ptr(actions)
-        if gsnr is None:
+        if diag:
+            d = _lib.StepDiag(_ptr(diag.get("block_cause")), _ptr(diag.get("block_cause_counts")),
+                              None if gsnr is None else _ptr(gsnr["gn_gsnr_db"]))
+            _lib.check(self.L.orlg_step_diag(self.h, _lib.POLICIES[policy], int(n_steps), ap, 1 if auto_reset else 0,
+                                             C.byref(io), C.byref(d)))
+            res.update(diag)
+            res.update(gsnr or {})
+        elif gsnr is None:
             _lib.check(self.L.orlg_step(self.h, _lib.POLICIES[policy], int(n_steps), ap, 1 if auto_reset else 0,
                                         C.byref(io)))
         else:
@@ -277,6 +300,20 @@ class BatchedRMSAEnv(BatchedHandle):
             _lib.check(self.L.orlg_action_masks(self.h, _ptr(out), None))
         else:
             _lib.check(self.L.orlg_action_masks(self.h, None, _ptr(out)))
+        return out
+
+    def path_fit_levels(self, out=None):
+        """How far every candidate path of every env's pending request is from fitting it: [B, k] uint8, an index into
+        ``FIT_LEVELS`` (include/orlg.h ``ORLG_FIT_*``) -- 4 a first fit exists (the ``"path_ff"`` mask bit), 3 only the window at
+        ``S - n`` that the first-fit loops never try, 2 every link has a run of ``n`` free slots but they do not line up,
+        1 every link has ``n`` free slots but some link no run of them, 0 some link has fewer than ``n`` free slots.  Windows
+        only, on every handle: it does not know a GN-model admission check.  ``out`` as in :meth:`action_masks`."""
+        shape = (self.batch_size, self.k_paths)
+        if out is None:
+            out = np.zeros(shape, np.uint8)
+        else:
+            _check_buffer("out", out, shape, np.uint8)
+        _lib.check(self.L.orlg_path_fit_levels(self.h, _ptr(out)))
         return out
 
     def simple_matrix_observation(self, out=None):

@@ -21,7 +21,8 @@ struct orlg_env : OrlgHandle {
     std::vector<uint8_t> path_se;   // spectral efficiency of every path record (orlg_set_gn_gate checks the thresholds against it)
     double *gn_table = nullptr;     // the gate's table on the device (allocated with the first gate; OrlgParams::gn = it or nullptr)
 };
-enum { X_ACTIONS, X_GSNR };   // OrlgHandle::extra: external actions from / the gn_gsnr_db output for pageable host memory
+enum { X_ACTIONS, X_GSNR, X_CAUSE, X_CAUSE_COUNTS };   // OrlgHandle::extra: external actions from / the gn_gsnr_db, block_cause and cause_counts outputs for host memory
+static_assert(X_CAUSE_COUNTS < ORLG_EXTRA_SLOTS, "OrlgHandle::extra");
 
 #define SYNC_CHECK(e) do { int rc_ = orlg_handle_sync_check(e); if (rc_) return rc_; } while (0)
 
@@ -145,7 +146,8 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p, const OrlgGroupOv
     const bool df = c.kind == ORLG_GROUP_DEFER;
     const bool trace = p.tr_arrival != nullptr;   // a request trace: the instantiations that replay it
     const bool traffic = !trace && p.rates != nullptr;   // per-environment rates: the instantiations that read them
-    const OrlgGroupKey key = {p.stats_level, c.kind == ORLG_GROUP_HBMQ, df, traffic, trace};
+    const bool cause = (p.out_mask & ORLG_OUT_CAUSE_BIT) != 0;   // the blocking cause: the plain kind with the classifier (the plan chose it)
+    const OrlgGroupKey key = {p.stats_level, c.kind == ORLG_GROUP_HBMQ, df, traffic, trace, cause};
     rmsa_kernel_t k = orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     if (df && !e->llog)
@@ -188,12 +190,14 @@ static rmsa_kernel_t step_kernel(int W, int stats) { return orlg_pick(W, OrlgWav
 static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
     // a step of a handle with a GN-model admission check: the general kernel's GN instantiation, whatever the policy and the length
     const bool gn = p.mode == ORLG_MODE_STEP && p.gn != nullptr;
-    const bool ff = !gn && p.mode == ORLG_MODE_STEP && p.K <= 8 && (p.policy == ORLG_POLICY_SP || p.policy == ORLG_POLICY_SAP);
+    // a launch that asks for the blocking cause: the general kernel's CAUSE instantiation, with or without the check
+    const bool cause = p.mode == ORLG_MODE_STEP && (p.out_mask & ORLG_OUT_CAUSE_BIT) != 0;
+    const bool ff = !gn && !cause && p.mode == ORLG_MODE_STEP && p.K <= 8 && (p.policy == ORLG_POLICY_SP || p.policy == ORLG_POLICY_SAP);
     const OrlgGroupOverrides ov = group_overrides();
     const bool df = !gn && p.mode == ORLG_MODE_STEP && orlg_defer_link_stats(p.stats_level, p.n_steps, p.out_mask, ov);   // as launch_rmsa_group
     const OrlgWaveKey key = {ff ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel_ff)
                                 : p.mode == ORLG_MODE_STEP ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel) : ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel),
-                             p.stats_level, df, gn};
+                             p.stats_level, df, gn, cause};
     rmsa_kernel_t k = orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), e->lds_block_bytes)) return rc;
@@ -539,9 +543,27 @@ int orlg_reseed(orlg_env *e, const uint64_t *seeds, uint64_t base_seed) {
 enum { IO_PATH, IO_SLOT, IO_ACC, IO_DONE, IO_REWARD, IO_REQ, IO_ARR, IO_HOLD, IO_COMP, IO_CDIFF };
 
 }  // extern "C"
-// orlg_step and orlg_step_gn (gsnr: the one output more, nullptr = not asked for)
+// An output of a launch that is not one of orlg_step_io's (block_cause, cause_counts): device memory is written in place,
+// host memory through the handle's buffer `slot` (as orlg_handle_place does for the others); null = not asked for
+struct ExtraOut {
+    void *user = nullptr, *dev = nullptr;
+    size_t bytes = 0;
+    bool staged() const { return user && dev != user; }
+};
+static int extra_out(orlg_env *e, ExtraOut *o, void *user, size_t bytes, int slot) {
+    o->user = user; o->bytes = bytes; o->dev = nullptr;
+    if (!user) return ORLG_OK;
+    o->dev = orlg_is_device_ptr(user) ? user : nullptr;
+    if (!o->dev) {
+        int rc = orlg_scratch_grow(&e->extra[slot], bytes);
+        if (rc) return rc;
+        o->dev = e->extra[slot].ptr;
+    }
+    return ORLG_OK;
+}
+// orlg_step, orlg_step_gn and orlg_step_diag (gsnr, cause, counts: the outputs beyond orlg_step_io, nullptr = not asked for)
 static int rmsa_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
-                     const orlg_step_io *io, double *gsnr) {
+                     const orlg_step_io *io, double *gsnr, uint8_t *cause = nullptr, int32_t *counts = nullptr) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     if (n_steps < 1) return fail(ORLG_ERR_INVALID, "n_steps must be >= 1");
     if (policy < ORLG_POLICY_EXTERNAL || policy > ORLG_POLICY_SAP_FF_GN) return fail(ORLG_ERR_INVALID, "unknown policy %d", policy);
@@ -586,12 +608,26 @@ static int rmsa_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t
         p.o_gsnr = static_cast<double *>(e->extra[X_GSNR].ptr);
     }
     if (gsnr && !p.gn) HIP_TRY(hipMemsetAsync(p.o_gsnr, 0xff, cnt * sizeof(double), e->stream));   // no gate, no check: all NaN
+    // block_cause / cause_counts: the launch runs a CAUSE instantiation (ORLG_OUT_CAUSE_BIT); the counts are zeroed on the stream
+    ExtraOut xc, xn;
+    rc = extra_out(e, &xc, cause, cnt, X_CAUSE);
+    if (!rc) rc = extra_out(e, &xn, counts, (size_t)p.B * ORLG_NUM_CAUSES * sizeof(int32_t), X_CAUSE_COUNTS);
+    if (rc) return rc;
+    p.o_cause = static_cast<uint8_t *>(xc.dev);
+    p.o_cause_counts = static_cast<int32_t *>(xn.dev);
+    if (cause || counts) p.out_mask |= ORLG_OUT_CAUSE_BIT;
+    if (counts) HIP_TRY(hipMemsetAsync(xn.dev, 0, xn.bytes, e->stream));
     rc = launch_rmsa(e, p);
     if (rc) return rc;
     if (e->trace.length > 0) e->trace.position += n_steps;
     bool any = false;
     rc = orlg_handle_collect(e, slots, ORLG_NUM_OUTS, cnt, p.outs, &any);
     if (rc) return rc;
+    for (const ExtraOut *x : {&xc, &xn})
+        if (x->staged()) {
+            HIP_TRY(hipMemcpyAsync(x->user, x->dev, x->bytes, hipMemcpyDeviceToHost, e->stream));
+            any = true;
+        }
     if (gsnr_staged) {
         HIP_TRY(hipMemcpyAsync(gsnr, p.o_gsnr, cnt * sizeof(double), hipMemcpyDeviceToHost, e->stream));
         any = true;
@@ -606,6 +642,11 @@ int orlg_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actio
 int orlg_step_gn(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
                  double *gn_gsnr_db) {
     return rmsa_step(e, policy, n_steps, actions, auto_reset, io, gn_gsnr_db);
+}
+int orlg_step_diag(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
+                   const struct orlg_step_diag *diag) {
+    if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr);
+    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts);
 }
 
 int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
@@ -870,6 +911,26 @@ int orlg_action_masks(orlg_env *e, uint8_t *path_ff, uint64_t *slot_masks) {
                        reinterpret_cast<u64 *>(slots[1].dev));
     HIP_TRY(hipGetLastError());
     return collect_outputs(e, slots, 2);
+}
+
+int orlg_path_fit_levels(orlg_env *e, uint8_t *levels) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!levels) return fail(ORLG_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(e->device));
+    const OrlgParams &p = e->p;
+    OutSlot slots[1] = {{levels, (size_t)p.B * p.K}};
+    int rc = place_outputs(e, slots, 1);
+    if (rc) return rc;
+    orlg_fit_levels_kernel_t k = orlg_pick_fit_levels(e->W);
+    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
+    const int wpb = e->waves_per_block;
+    const size_t lds = (size_t)p.l_shared_bytes + (size_t)((p.NW * 8 + 15) & ~15) * wpb;   // as orlg_action_masks: tables + one occupancy row per wave
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int nblocks = (p.B + wpb - 1) / wpb;
+    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;
+    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, reinterpret_cast<uint8_t *>(slots[0].dev));
+    HIP_TRY(hipGetLastError());
+    return collect_outputs(e, slots, 1);
 }
 
 int orlg_gn_action_masks(orlg_env *e, uint8_t *path_ff, double *path_ff_gsnr_db, uint8_t *deeprmsa, double *deeprmsa_gsnr_db) {

@@ -146,7 +146,17 @@ struct OrlgParams {
     // (ORLG_GN_* below), nullptr = no gate; o_gsnr: the per-step output gn_gsnr_db [n_steps][B] of orlg_step_gn, nullptr = not asked for
     const double *gn;
     double *o_gsnr;
+    // blocking cause (include/orlg.h orlg_step_diag; orlg_block_cause.h), written by the CAUSE instantiations of the two step kernels
+    // only: o_cause [n_steps][B] ORLG_CAUSE_* per step, o_cause_counts [B][8] steps of this launch per cause (zeroed on the stream
+    // before the launch); nullptr = not asked for.  A launch that asks for either has ORLG_OUT_CAUSE_BIT in out_mask.  (At the
+    // struct's end: every other field lies in the kernarg segment where it lay)
+    uint8_t *o_cause;
+    int32_t *o_cause_counts;
 };
+// out_mask of a launch that asks for a cause output: not one of outs[], but a per-step output like them -- what looks at
+// out_mask to choose a kernel (the deferred link statistics, the group kernel's HBMQ kind and lean body) keeps such a launch on
+// the plain instantiations, the only ones that exist with the classifier
+enum { ORLG_OUT_CAUSE_BIT = 1 << 30 };
 // OrlgParams::gn, in doubles: the gate's scalars, the thresholds by spectral efficiency - 1 from ORLG_GN_THR0, then four per link
 // from ORLG_GN_LINK0 -- effective length of a span, its ratio to the span's length, exp(2 att len) - 1, number of spans
 enum { ORLG_GN_DENSITY = 0, ORLG_GN_F0, ORLG_GN_SLOT, ORLG_GN_ATT, ORLG_GN_NF, ORLG_GN_LEFF_A, ORLG_GN_THR0 = 8, ORLG_GN_LINK0 = 16 };

@@ -1,6 +1,6 @@
 // orlg_group_body.h -- the TEXT of orlg_rmsa_group_kernel's body (orlg_group_kernels.hip), from the first statement to the last.
 // Not a header to include at file scope: it is included INSIDE a function that has the kernel's template arguments (W, STATS,
-// HBMQ, DEFER, TRAFFIC, TRACE), a constant `LEAN` and the parameters `p` in scope -- once in the kernel itself and once in
+// HBMQ, DEFER, TRAFFIC, TRACE), the constants `LEAN` and `CAUSE` and the parameters `p` in scope -- once in the kernel itself and once in
 // orlg_rmsa_group_body, which gives the DEFER instantiations their second, lean body.  Why the text and not only the function:
 // a kernel whose body arrives through an inlined function compiles to slightly different code than one that holds the text
 // (other spill placement, a few dozen instructions either way), and the instantiations without a lean body are to stay,
@@ -12,6 +12,7 @@
     static_assert(!DEFER || (STATS >= 2 && !HBMQ), "the deferred link statistics belong to long launches with full statistics");
     static_assert(!(TRACE && TRAFFIC), "a trace handle has no arrival rates");
     static_assert(!LEAN || DEFER, "the lean body belongs to the long launches");
+    static_assert(!CAUSE || (!HBMQ && !DEFER), "the blocking cause belongs to the plain kind");
     extern __shared__ __align__(16) unsigned char smem[];
     stage_tables(smem, p);
     const int lane = threadIdx.x & 63;
@@ -173,6 +174,7 @@
     // ... and the head's descriptor with it: a release starts from a register, the path record one round trip earlier
     uint32_t next_desc = q_n > 0 ? qdesc[q_head] : 0u;
     const int cidx = gl & 7;
+    [[maybe_unused]] int cause_cnt = 0;   // CAUSE: lane c of the row counts this ticket's steps with cause c
     int req_base = tb.pair_base[req_src * N + req_dst];  // first path record of the pending request's node pair
 
     const int n_iter = n_chunks > 1 ? (p.n_steps - t0 < p.chunk_steps ? p.n_steps - t0 : p.chunk_steps) : p.n_steps;
@@ -295,6 +297,16 @@
             accepted = in_range && a_slot + n <= S && bad == 0u;
         }
         const int br_val = tb.bit_rates[req_br];
+        // CAUSE: the blocking cause of the rows that are not accepted, on the occupancy the step met (include/orlg.h ORLG_CAUSE_*)
+        [[maybe_unused]] int cause = 0;
+        if constexpr (CAUSE) {
+            const bool refused = act && !accepted;
+            if (ballot(refused) != 0ull) {
+                const int level = group_fit_level<W>(lane, occ, tb, base, K, S, req_br, refused);
+                cause = refused ? ORLG_CAUSE_CAPACITY + level : ORLG_CAUSE_ACCEPTED;
+            }
+            if (act) cause_cnt += gl == cause ? 1 : 0;
+        }
         // ---- _provision_path (rmsa_env.py:462-513)
         // (with network statistics the statistics pass below clears the window as it reads the links' words)
         if (!NET) group_apply_window<W>(lane, occ, rec->link, accepted ? hops : 0, a_slot, n, false);
@@ -375,6 +387,9 @@
                 ORLG_GPTR(double, tb.outs[ORLG_OUT_AVG_LINK_COMPACT])[o] = np_mean(lst + 2 * E, E);
             if (FULL && (om & (1 << ORLG_OUT_AVG_LINK_UTIL)))
                 ORLG_GPTR(double, tb.outs[ORLG_OUT_AVG_LINK_UTIL])[o] = np_mean(lst, E);
+            if constexpr (CAUSE) {
+                if (p.o_cause) ORLG_GPTR(uint8_t, p.o_cause)[o] = (uint8_t)cause;
+            }
         }
         new_service = 0;
 
@@ -547,6 +562,10 @@
         quad_copy(p.occ + (size_t)env0 * NW, wbase + p.g_occ, nact * NW * 8, lane);
         if (FULL && !DEFER) quad_copy(p.lstat + (size_t)env0 * 4 * E, wbase + p.g_lstat, nact * 4 * E * 8, lane);
         if (NET) quad_copy(p.lint + (size_t)env0 * p.lint_stride, wbase + p.g_lint, nact * p.lint_stride * 4, lane);
+    }
+    if constexpr (CAUSE) {
+        // (the chunks of a quad's launch may run on different waves: every ticket adds its counts, atomics without return)
+        if (act && gl < ORLG_NUM_CAUSES && cause_cnt && p.o_cause_counts) atomicAdd(p.o_cause_counts + (size_t)env * ORLG_NUM_CAUSES + gl, cause_cnt);
     }
     if (act) {
         if constexpr (!HBMQ) {

@@ -24,6 +24,7 @@
 #include "orlg_link_stats.h"   // and through it orlg_wave.h, orlg_rmsa_layout.h, orlg_spectrum.h
 #include "orlg_requests.h"
 #include "orlg_sections.h"
+#include "orlg_block_cause.h"  // window_level: the classifier of the CAUSE instantiations (group_fit_level below)
 
 #define ORLG_GL 16  // lanes per environment (one DPP row)
 #define ORLG_GE 4   // environments per wave
@@ -389,6 +390,55 @@ DEV void quad_copy(void *dst, const void *src, int bytes, int lane) {
     if ((bytes & 8) && lane == 0) reinterpret_cast<u64 *>(dst)[2 * n16] = reinterpret_cast<const u64 *>(src)[2 * n16];
 }
 
+// The highest fit level (include/orlg.h ORLG_FIT_*) over the K candidate paths of each row's pending request: wave_fit_levels
+// (orlg_block_cause.h) in this kernel's layout -- 16 / W paths, then 16 / W links, per row and pass, a path's or a link's W words
+// on consecutive lanes.  `need`: the row asks (its step is not accepted); the rows diverge, so every loop runs to the longest
+// row and the others are predicated.  occ: the row's occupancy (LDS); base: the first path record of its request.
+template <int W>
+DEV int group_fit_level(int lane, const u64 *occ, const Tab &tb, int base, int K, int S, int br, bool need) {
+    constexpr int PP = ORLG_GL / W;   // paths, or links, per row and pass
+    const int gl = lane & 15;
+    const int ps = gl / W, w = gl - ps * W;
+    int top = 0;
+    // windows: a first fit below S - n (4), only the window at S - n (3)
+    for (int p0 = 0; p0 < K; p0 += PP) {
+        const int pp = p0 + ps;
+        const bool on = need && ps < PP && pp < K;
+        int se_pp, hops_pp;
+        const u64 x = group_path_word_rec<W>(occ, tb.recs, base + pp, w, on, se_pp, hops_pp);
+        int n = 1;
+        if (on) n = tb.nslots[br * ORLG_NSLOT_STRIDE + se_pp];
+        const int lv = on ? window_level(run_starts<W>(x, n, w), n, S, w) : 0;
+        const int row = row_ballot(lv == 4, lane) ? 4 : (row_ballot(lv == 3, lane) ? 3 : 0);
+        top = row > top ? row : top;
+    }
+    // links, for the rows without a window: per path, some link short of n free slots (0), some link without a run of n (1), else 2
+    const bool more = need && top < 3;
+    if (ballot(more) == 0ull) return top;
+    for (int idp = 0; idp < K; ++idp) {
+        if (ballot(more && top < 2) == 0ull) break;   // every row that asks has its answer: no path scores above 2 here
+        const OrlgPathRec *rec = tb.recs + (base + idp);
+        const int hops = more && top < 2 ? (int)rec->hops : 0;
+        const int n = tb.nslots[br * ORLG_NSLOT_STRIDE + rec->se];
+        uint32_t nocap = 0u, norun = 0u;
+        for (int h0 = 0;; h0 += PP) {
+            if (ballot(h0 < hops) == 0ull) break;
+            const int h = h0 + ps;
+            const bool on = ps < PP && h < hops;
+            u64 x = 0ull;
+            if (on) x = occ[__mul24((int)rec->link[on ? h : 0], W) + w];
+            const uint32_t freec = seg_add<W>((uint32_t)popc64(x));
+            const uint32_t has = seg_max<W>(run_starts<W>(x, n, w) != 0ull ? 1u : 0u);
+            const bool head = on && w == 0;   // the link's first lane holds the link's results
+            nocap |= row_ballot(head && (int)freec < n, lane);
+            norun |= row_ballot(head && has == 0u, lane);
+        }
+        const int lv = nocap ? 0 : (norun ? 1 : 2);
+        if (more && lv > top) top = lv;
+    }
+    return top;
+}
+
 // HBMQ: launches of very few steps (the agent-driven loop) leave the release queue where it is, in HBM: staged in LDS it is
 // half of an environment's footprint there (its capacity, not its live part, sizes the region), and a one-step launch is
 // bound by how many waves a CU keeps resident, not by the queue's latency.  The ring logic is the same code on
@@ -406,12 +456,16 @@ DEV void quad_copy(void *dst, const void *src, int bytes, int lane) {
 // full body performs for such a launch.  Always inlined: a call would cost the ABI's register traffic
 template <int W, int STATS, bool HBMQ, bool DEFER, bool TRAFFIC, bool TRACE, bool LEAN>
 DEV void orlg_rmsa_group_body(const OrlgParams &p) {
+    constexpr bool CAUSE = false;   // (the DEFER instantiations have no classifier: a cause launch runs the plain kind)
 #include "orlg_group_body.h"
 }
 
 // The kernel.  A DEFER instantiation holds the lean body beside the full one and chooses at entry: one wave-uniform test of a
 // kernel argument, a scalar branch.  Every other instantiation is the body's text alone, the code it was.
-template <int W, int STATS, bool HBMQ = false, bool DEFER = false, bool TRAFFIC = false, bool TRACE = false>
+// CAUSE: the launch asks for the blocking cause of its steps (include/orlg.h orlg_step_diag): the rows whose step is not accepted
+// are classified (group_fit_level) before the provision touches the occupancy.  A template argument for the same reason as
+// TRAFFIC; the plain kind only (orlg_group_plan.h keeps such a launch on it)
+template <int W, int STATS, bool HBMQ = false, bool DEFER = false, bool TRAFFIC = false, bool TRACE = false, bool CAUSE = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3) / 4) void orlg_rmsa_group_kernel(const OrlgParams p) {
     if constexpr (DEFER) {
         if (p.g_lean) orlg_rmsa_group_body<W, STATS, HBMQ, DEFER, TRAFFIC, TRACE, true>(p);

@@ -1,5 +1,6 @@
 // orlg_inst_wave.hip -- instantiations of the wave-per-environment kernels (orlg_kernels.hip, and the query and mask kernels of
-// orlg_query_kernels.hip, orlg_mask_kernels.hip and orlg_gn_mask_kernels.hip, in the order the file always met them) for ONE word count,
+// orlg_query_kernels.hip, orlg_mask_kernels.hip and orlg_gn_mask_kernels.hip, in the order the file always met them; orlg_fit_levels_kernel
+// of orlg_block_cause.h last) for ONE word count,
 // -DORLG_INST_W=<W>: one object per W, so that the library builds in parallel (build.py).  Which ones: orlg_variants.h.
 #include "orlg_host.h"
 #include "orlg_kernels.hip"
@@ -17,6 +18,7 @@ orlg_rmsa_kernel_t ORLG_CAT(orlg_wave_kernel_W, ORLG_INST_W)(OrlgWaveKey key) {
 #define X(name, ...) if (key == OrlgWaveKey{ORLG_WAVE_KERNEL(name), __VA_ARGS__}) return name<ORLG_INST_W, __VA_ARGS__>;
     ORLG_WAVE_KEYS(X)
     ORLG_WAVE_GN_KEYS(X)
+    ORLG_WAVE_CAUSE_KEYS(X)
 #undef X
     return nullptr;
 }
@@ -24,3 +26,4 @@ orlg_masks_kernel_t ORLG_CAT(orlg_masks_kernel_W, ORLG_INST_W)() { return orlg_p
 orlg_obs_kernel_t ORLG_CAT(orlg_obs_kernel_W, ORLG_INST_W)() { return orlg_deeprmsa_obs_kernel<ORLG_INST_W>; }
 orlg_action_masks_kernel_t ORLG_CAT(orlg_action_masks_kernel_W, ORLG_INST_W)() { return orlg_action_masks_kernel<ORLG_INST_W>; }
 orlg_gn_action_masks_kernel_t ORLG_CAT(orlg_gn_action_masks_kernel_W, ORLG_INST_W)() { return orlg_gn_action_masks_kernel<ORLG_INST_W>; }
+orlg_fit_levels_kernel_t ORLG_CAT(orlg_fit_levels_kernel_W, ORLG_INST_W)() { return orlg_fit_levels_kernel<ORLG_INST_W>; }

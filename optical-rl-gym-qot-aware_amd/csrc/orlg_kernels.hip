@@ -34,6 +34,7 @@
 #include "orlg_link_stats.h"   // and through it orlg_wave.h, orlg_rmsa_layout.h, orlg_spectrum.h
 #include "orlg_requests.h"     // mt_regenerate, the ring's three producers, ring_store, ring_visible, orlg_env_rates
 #include "orlg_rmsa_gn.h"      // rmsa_gn_gsnr: the GN-model admission check of the GN instantiations
+#include "orlg_block_cause.h"  // wave_fit_levels: the classifier of the CAUSE instantiations
 #include "orlg_sections.h"
 
 // ---------------------------------------------------------------------------------------- the step kernel
@@ -46,6 +47,9 @@
 // GN, policy sap_ff_gn: what a step keeps while it goes from a refused candidate to the next -- the candidate paths below `from`
 // have been refused by the admission check in this step (0: none yet; every other policy leaves it 0), (path, slot, gsnr) is the
 // first of them, which a refusal shows; exhausted: no further path has a fit.  Nothing without a gate.
+// CAUSE: the launch asks for the blocking cause of its steps (include/orlg.h orlg_step_diag, OrlgParams::o_cause /
+// o_cause_counts): a step that is not accepted is classified (orlg_block_cause.h) on the occupancy it met -- a refused step
+// provisions nothing, so that is still the occupancy when the outputs are written; every other instantiation holds none of it.
 template <bool GN>
 struct SapRetry {
     int from = 0, path = 0, slot = 0;
@@ -57,7 +61,7 @@ struct SapRetry<false> {
     SapRetry() = default;
 };
 
-template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false, bool GN = false>
+template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false, bool GN = false, bool CAUSE = false>
 DEV void rmsa_body(const OrlgParams &p) {
     extern __shared__ __align__(16) unsigned char smem[];
 #ifdef ORLG_SHAPE_ASSUME
@@ -205,6 +209,7 @@ DEV void rmsa_body(const OrlgParams &p) {
     // the per-link (span, gaps) cache and its sums travel with the state (they are a function of the occupancy)
     int sum_span = gs_sum_span, sum_gaps = gs_sum_gaps;
     SapRetry<STEPK && GN> sap;
+    [[maybe_unused]] int cause_cnt = 0;   // CAUSE: lane c counts this launch's steps with cause c
     if (NET) comp_cur = network_compactness(sum_span, sum_sh, sum_gaps, E);
 
     for (int t = 0; t < n_iter; ++t) {
@@ -436,6 +441,16 @@ DEV void rmsa_body(const OrlgParams &p) {
             if constexpr (GN) {
                 if (lane == 0 && p.o_gsnr) ORLG_GPTR(double, p.o_gsnr)[(size_t)t * p.B + env] = gn_gsnr;
             }
+            if constexpr (CAUSE) {
+                int cause = ORLG_CAUSE_ACCEPTED;
+                if (!accepted) {
+                    if (GN && gn_gsnr == gn_gsnr) cause = ORLG_CAUSE_GN;   // the check ran (gn_gsnr_db is not NaN) and refused
+                    else cause = ORLG_CAUSE_CAPACITY + wave_fit_levels<W>(wv.occ, tb, base, K, S, req_br, lane, nullptr);
+                }
+                KernargParams kq = kernarg_params();
+                if (lane == 0 && kq->o_cause) ORLG_GPTR(uint8_t, kq->o_cause)[(size_t)t * p.B + env] = (uint8_t)cause;
+                cause_cnt += lane == cause ? 1 : 0;
+            }
             if constexpr (GN) sap.from = 0;
             new_service = 0;
         } else if (p.mode == ORLG_MODE_EPISODE_RESET) {
@@ -587,6 +602,9 @@ DEV void rmsa_body(const OrlgParams &p) {
         copy_words(kp->qtime + (size_t)env * Q, wv.qtime, Q * 8, lane);
         copy_words(kp->qdesc + (size_t)env * Q, wv.qdesc, Q * 4, lane);
         if (mt_loaded) copy_words(kp->mt + (size_t)env * ORLG_MT_N, wv.mt, ORLG_MT_N * 4, lane);
+        if constexpr (CAUSE) {   // (this wave stepped the environment through the whole launch: the row is its own)
+            if (lane < ORLG_NUM_CAUSES && kp->o_cause_counts) ORLG_GPTR(int32_t, kp->o_cause_counts)[(size_t)env * ORLG_NUM_CAUSES + lane] = cause_cnt;
+        }
         if (FULL) copy_words(kp->lstat + (size_t)env * 4 * E, wv.lst, 4 * E * 8, lane);
         copy_words(kp->hist + (size_t)env * 4 * NBR, wv.hist, 4 * NBR * 4, lane);
         if (NET) copy_words(kp->lint + (size_t)env * kp->lint_stride, wv.lint, kp->lint_stride * 4, lane);
@@ -622,9 +640,9 @@ DEV void rmsa_body(const OrlgParams &p) {
     SEC_FLUSH;
 }
 
-template <int W, int STATS, bool DEFER = false, bool GN = false>
+template <int W, int STATS, bool DEFER = false, bool GN = false, bool CAUSE = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel(const OrlgParams p) {
-    rmsa_body<W, STATS, true, false, DEFER, GN>(p);
+    rmsa_body<W, STATS, true, false, DEFER, GN, CAUSE>(p);
 }
 template <int W, int STATS, bool DEFER = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel_ff(const OrlgParams p) {

@@ -10,8 +10,9 @@
 #include "../../include/orlg.h"   // ORLG_PHY_POLICY_*
 
 // ---------------------------------------------------------------------------------------- keys
-// wave-per-environment kernels (orlg_kernels.hip): template <int W, int STATS, bool DEFER = false, bool GN = false>; the reset kernel
-// has no DEFER, and only orlg_rmsa_kernel has GN (the GN-model admission check, orlg_rmsa_gn.h)
+// wave-per-environment kernels (orlg_kernels.hip): template <int W, int STATS, bool DEFER = false, bool GN = false, bool CAUSE = false>;
+// the reset kernel has no DEFER, and only orlg_rmsa_kernel has GN (the GN-model admission check, orlg_rmsa_gn.h) and CAUSE (the
+// blocking cause of every step, orlg_block_cause.h)
 #define ORLG_WAVE_KERNELS(X) X(orlg_rmsa_kernel) X(orlg_rmsa_kernel_ff) X(orlg_rmsa_reset_kernel)
 #define ORLG_WAVE_KERNEL(name) ORLG_IS_##name
 enum OrlgWaveKernel {
@@ -19,15 +20,15 @@ enum OrlgWaveKernel {
     ORLG_WAVE_KERNELS(X)
 #undef X
 };
-struct OrlgWaveKey { OrlgWaveKernel kernel; int STATS; bool DEFER; bool GN = false; };
+struct OrlgWaveKey { OrlgWaveKernel kernel; int STATS; bool DEFER; bool GN = false; bool CAUSE = false; };
 // orlg_rmsa_group_kernel (orlg_group_kernels.hip)
-struct OrlgGroupKey { int STATS; bool HBMQ, DEFER, TRAFFIC, TRACE; };
+struct OrlgGroupKey { int STATS; bool HBMQ, DEFER, TRAFFIC, TRACE; bool CAUSE = false; };
 // orlg_phy_kernel (orlg_phy_kernels.hip)
 struct OrlgPhyKey { bool DF, GN; int POL; bool CONT, TRACE; };
 
-inline bool operator==(const OrlgWaveKey &a, const OrlgWaveKey &b) { return a.kernel == b.kernel && a.STATS == b.STATS && a.DEFER == b.DEFER && a.GN == b.GN; }
+inline bool operator==(const OrlgWaveKey &a, const OrlgWaveKey &b) { return a.kernel == b.kernel && a.STATS == b.STATS && a.DEFER == b.DEFER && a.GN == b.GN && a.CAUSE == b.CAUSE; }
 inline bool operator==(const OrlgGroupKey &a, const OrlgGroupKey &b) {
-    return a.STATS == b.STATS && a.HBMQ == b.HBMQ && a.DEFER == b.DEFER && a.TRAFFIC == b.TRAFFIC && a.TRACE == b.TRACE;
+    return a.STATS == b.STATS && a.HBMQ == b.HBMQ && a.DEFER == b.DEFER && a.TRAFFIC == b.TRAFFIC && a.TRACE == b.TRACE && a.CAUSE == b.CAUSE;
 }
 inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
     return a.DF == b.DF && a.GN == b.GN && a.POL == b.POL && a.CONT == b.CONT && a.TRACE == b.TRACE;
@@ -47,6 +48,13 @@ inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
 // a gate can reach, in number too (tests/test_variant_names.py counts its lookups); an instantiation unit expands both, these
 // last, so that the kernels in front of them lie in the code object where they lay.
 #define ORLG_WAVE_GN_KEYS(X) X(orlg_rmsa_kernel, 1, false, true) X(orlg_rmsa_kernel, 2, false, true) X(orlg_rmsa_kernel, 0, false, true)
+// X(kernel, STATS, DEFER, GN, CAUSE): what a launch that asks for the blocking cause of its steps runs (orlg_step_diag) -- the general
+// step kernel with the classifier, per statistics level, without and with the admission check; no _ff and no DEFER variant
+// (optimisations that leave the same state: such a launch does without them).  A list of its own for the reasons above, expanded
+// after the GN keys.
+#define ORLG_WAVE_CAUSE_KEYS(X)                                                                                             \
+    X(orlg_rmsa_kernel, 1, false, false, true) X(orlg_rmsa_kernel, 2, false, false, true) X(orlg_rmsa_kernel, 0, false, false, true) \
+    X(orlg_rmsa_kernel, 1, false, true, true) X(orlg_rmsa_kernel, 2, false, true, true) X(orlg_rmsa_kernel, 0, false, true, true)
 
 // X(STATS, HBMQ, DEFER, TRAFFIC, TRACE).  Per kind of handle: every statistics level, the same with the release queue left in HBM
 // (launches of very few steps), and full statistics with the link updates deferred (long launches).  The kinds: plain, with
@@ -56,6 +64,13 @@ inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
     X(0, true, false, TRAFFIC, TRACE) X(1, true, false, TRAFFIC, TRACE) X(2, true, false, TRAFFIC, TRACE)         \
     X(2, false, true, TRAFFIC, TRACE)
 #define ORLG_GROUP_KEYS(X) ORLG_GROUP_KEYS_OF(X, false, false) ORLG_GROUP_KEYS_OF(X, true, false) ORLG_GROUP_KEYS_OF(X, false, true)
+// X(STATS, HBMQ, DEFER, TRAFFIC, TRACE, CAUSE): the launches that ask for the blocking cause -- the plain kind of instantiation
+// (queue in LDS, statistics at every step) per statistics level and kind of handle.  HBMQ, DEFER and its lean body are
+// optimisations that leave identical state; orlg_group_plan.h keeps a cause launch off them.  A list of its own, expanded last
+#define ORLG_GROUP_CAUSE_KEYS_OF(X, TRAFFIC, TRACE) \
+    X(0, false, false, TRAFFIC, TRACE, true) X(1, false, false, TRAFFIC, TRACE, true) X(2, false, false, TRAFFIC, TRACE, true)
+#define ORLG_GROUP_CAUSE_KEYS(X) \
+    ORLG_GROUP_CAUSE_KEYS_OF(X, false, false) ORLG_GROUP_CAUSE_KEYS_OF(X, true, false) ORLG_GROUP_CAUSE_KEYS_OF(X, false, true)
 
 // X(DF, GN, POL, CONT, TRACE), one instantiation per policy (-1 external actions .. 6).  Discrete bit rates: the step kernel
 // proper, + periodic defragmentation, + defragmentation and the GN-model admission check, + the check alone (a handle without
@@ -87,7 +102,9 @@ inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
 #define ORLG_PHY_KEY_ENTRY(...) OrlgPhyKey{__VA_ARGS__},
 inline constexpr OrlgWaveKey ORLG_WAVE_KEY_LIST[] = {ORLG_WAVE_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgWaveKey ORLG_WAVE_GN_KEY_LIST[] = {ORLG_WAVE_GN_KEYS(ORLG_WAVE_KEY_ENTRY)};
+inline constexpr OrlgWaveKey ORLG_WAVE_CAUSE_KEY_LIST[] = {ORLG_WAVE_CAUSE_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_KEY_LIST[] = {ORLG_GROUP_KEYS(ORLG_GROUP_KEY_ENTRY)};
+inline constexpr OrlgGroupKey ORLG_GROUP_CAUSE_KEY_LIST[] = {ORLG_GROUP_CAUSE_KEYS(ORLG_GROUP_KEY_ENTRY)};
 inline constexpr OrlgPhyKey ORLG_PHY_KEY_LIST[] = {ORLG_PHY_KEYS(ORLG_PHY_KEY_ENTRY)};
 template <typename Key, size_t N>
 static int orlg_key_index(const Key (&list)[N], const Key &key) {
@@ -112,12 +129,12 @@ inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgWaveKey &k)
 #define X(name) #name,
     static const char *const names[] = {ORLG_WAVE_KERNELS(X)};
 #undef X
-    const OrlgArg args[] = {{k.STATS, 'i'}, {k.DEFER, 'd'}, {k.GN, 'd'}};
-    orlg_format_kernel(buf, cap, names[k.kernel], W, args, k.kernel == ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel) ? 1 : 3);
+    const OrlgArg args[] = {{k.STATS, 'i'}, {k.DEFER, 'd'}, {k.GN, 'd'}, {k.CAUSE, 'd'}};
+    orlg_format_kernel(buf, cap, names[k.kernel], W, args, k.kernel == ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel) ? 1 : 4);
 }
 inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgGroupKey &k) {
-    const OrlgArg args[] = {{k.STATS, 'i'}, {k.HBMQ, 'd'}, {k.DEFER, 'd'}, {k.TRAFFIC, 'd'}, {k.TRACE, 'd'}};
-    orlg_format_kernel(buf, cap, "orlg_rmsa_group_kernel", W, args, 5);
+    const OrlgArg args[] = {{k.STATS, 'i'}, {k.HBMQ, 'd'}, {k.DEFER, 'd'}, {k.TRAFFIC, 'd'}, {k.TRACE, 'd'}, {k.CAUSE, 'd'}};
+    orlg_format_kernel(buf, cap, "orlg_rmsa_group_kernel", W, args, 6);
 }
 inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgPhyKey &k) {
     const OrlgArg args[] = {{k.DF, 'b'}, {k.GN, 'b'}, {k.POL, 'i'}, {k.CONT, 'd'}, {k.TRACE, 'd'}};
@@ -134,6 +151,7 @@ typedef void (*orlg_masks_kernel_t)(const OrlgParams, int, int, int, uint64_t *,
 typedef void (*orlg_obs_kernel_t)(const OrlgParams, uint8_t *, int);                          // orlg_deeprmsa_obs_kernel
 typedef void (*orlg_action_masks_kernel_t)(const OrlgParams, uint8_t *, int, uint64_t *);     // orlg_action_masks_kernel
 typedef void (*orlg_gn_action_masks_kernel_t)(const OrlgParams, uint8_t *, double *, uint8_t *, double *, int);   // orlg_gn_action_masks_kernel
+typedef void (*orlg_fit_levels_kernel_t)(const OrlgParams, uint8_t *);                         // orlg_fit_levels_kernel
 typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
 #define ORLG_FOR_EACH_W(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__) X(6, __VA_ARGS__) X(8, __VA_ARGS__)
 #define ORLG_FOR_EACH_PHY_W(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__)
@@ -143,6 +161,7 @@ typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
     orlg_obs_kernel_t orlg_obs_kernel_W##n() __attribute__((weak));                               \
     orlg_action_masks_kernel_t orlg_action_masks_kernel_W##n() __attribute__((weak));             \
     orlg_gn_action_masks_kernel_t orlg_gn_action_masks_kernel_W##n() __attribute__((weak));       \
+    orlg_fit_levels_kernel_t orlg_fit_levels_kernel_W##n() __attribute__((weak));                 \
     orlg_rmsa_kernel_t orlg_group_kernel_W##n(OrlgGroupKey) __attribute__((weak));
 #define ORLG_DECL_PHY_W(n, ...)                                                                   \
     orlg_phy_kernel_t orlg_phy_kernel_W##n(OrlgPhyKey) __attribute__((weak));                     \
@@ -164,4 +183,5 @@ static orlg_phy_kernel_t orlg_pick(int W, const OrlgPhyKey &key) {   // the TRAC
 static orlg_masks_kernel_t orlg_pick_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_masks_kernel_W, ) }
 static orlg_obs_kernel_t orlg_pick_obs(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_obs_kernel_W, ) }
 static orlg_action_masks_kernel_t orlg_pick_action_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_action_masks_kernel_W, ) }
+static orlg_fit_levels_kernel_t orlg_pick_fit_levels(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_fit_levels_kernel_W, ) }
 static orlg_gn_action_masks_kernel_t orlg_pick_gn_action_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_action_masks_kernel_W, ) }

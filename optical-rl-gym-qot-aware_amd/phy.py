@@ -184,7 +184,7 @@ class BatchedPhyRMSAEnv(BatchedHandle):
         self.node_vectors = bool(self.L.orlg_phy_node_vectors(self.h))   # cut metric through node-degree vectors (include/orlg.h)
 
     def run(self, policy: str, n_steps: int = 1, *, act_path=None, act_channels=None, act_share=None,
-            auto_reset: bool = False, outputs: Sequence[str] = (), out=None):
+            auto_reset: bool = False, outputs: Sequence[str] = (), out=None, cause_counts=None):
         """``n_steps`` x (policy -> PhyRMSAEnv.step).  ``policy='external'``: ``act_path`` [B] int32 (-2 = blocked,
         0..k-1 physical, 20 + k-path virtual layer) and ``act_channels`` [B, 14] int16 (-1 padded; entry = channel |
         used << 9, see :func:`encode_channels`).  Returns the requested per-step arrays [n_steps, B(, ...)]; ``out`` may
@@ -192,7 +192,13 @@ class BatchedPhyRMSAEnv(BatchedHandle):
 
         Continuous bit rates: external actions also need ``act_share`` [B, 14, 2] float64, the (used, free) fields of the
         tuples (:func:`encode_shares`); the outputs ``channels_used_f64`` / ``channels_free_f64`` [n_steps, B, 14] hold the
-        chosen channels' float64 shares (``channels_used`` is 0 on such a handle)."""
+        chosen channels' float64 shares (``channels_used`` is 0 on such a handle).
+
+        ``cause_counts`` / the output ``"block_cause"`` belong to the slot-based environments (``BatchedRMSAEnv.run``): channel
+        allocation is not contiguous here, and the taxonomy of contiguous windows does not apply."""
+        if (cause_counts is not None and cause_counts is not False) or "block_cause" in _output_names(outputs, out):
+            raise ValueError("the blocking cause (block_cause, cause_counts) is defined for BatchedRMSAEnv / BatchedDeepRMSAEnv: "
+                             "the QoT-aware environment allocates non-contiguous channels")
         B = self.batch_size
         io = _lib.PhyStepIO()
         names = _output_names(outputs, out)

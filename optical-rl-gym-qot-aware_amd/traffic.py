@@ -141,3 +141,29 @@ def blocking_summary(grouped, episode=True):
             var = (b2 - b1 * b1 / n) / (n - 1)
             err[g] = np.sqrt(max(var, 0.0) / n) / proc
     return mean, err
+
+
+def blocking_shares_by_group(cause_counts, groups, num_groups=None, loads=None):
+    """Blocking by cause of a load sweep, from the ``"block_cause_counts"`` of one or more launches of a sweep handle
+    (``BatchedRMSAEnv.run(..., cause_counts=True)``; sum the arrays of several launches before the call).
+
+    ``cause_counts`` [B, 8] integers, ``groups`` [B] the group of every environment (the handle's ``groups``).  Returns a dict:
+    ``counts`` [G, 8] int64, the steps per group and cause (columns: ``BLOCK_CAUSES``, include/orlg.h ``ORLG_CAUSE_*``);
+    ``steps`` [G]; ``shares`` [G, 8] float64 = counts / steps, so ``1 - shares[:, 0]`` is the blocking probability and
+    ``shares[:, 1:]`` splits it by cause (NaN for a group without a step); ``loads`` [G] where ``loads`` [B] is given and
+    every group is one load (:func:`group_loads`; ``ValueError`` otherwise)."""
+    c = np.asarray(cause_counts)
+    if c.ndim != 2 or c.shape[1] != 8:
+        raise ValueError(f"cause_counts: shape {c.shape}, expected (B, 8)")
+    if c.dtype.kind not in "iu":
+        raise TypeError(f"cause_counts: dtype {c.dtype}, expected an integer type")
+    g, n = check_groups(c.shape[0], groups, num_groups)
+    counts = np.zeros((n, 8), np.int64)
+    np.add.at(counts, g, c.astype(np.int64))
+    steps = counts.sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        shares = counts / steps[:, None].astype(np.float64)
+    out = dict(counts=counts, steps=steps, shares=shares)
+    if loads is not None:
+        out["loads"] = group_loads(_per_env("loads", loads, c.shape[0]), g, n)
+    return out
