@@ -259,6 +259,34 @@ struct orlg_step_diag {   /* (no typedef: the entry point below has the name; sa
  * written in place, host memory (pinned or pageable) through a buffer of the handle, and the call then waits. */
 int orlg_step_diag(orlg_env *env, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
                    const orlg_step_io *io, const struct orlg_step_diag *diag);
+/* ---- spectrum-assignment rules (not in the reference: its RMSA heuristics, rmsa_env.py:854-937, are first fit only).
+ * Where on a route's path the service starts.  For candidate path p of the pending request: A = the AND of its links' availability
+ * over the S slots, n = get_number_slots(p); a BLOCK is a maximal run of free slots of A (rmsa_env.py:774-804; it may touch slot
+ * S - 1); a WINDOW is a start s in 0 .. S - n INCLUSIVE with [s, s + n) free (step() accepts s = S - n; only the reference's
+ * first-fit loops skip it).  Integer-exact. */
+enum {
+    ORLG_ASSIGN_FIRST = 0,       /* the reference's: the lowest s in range(0, S - n) -- orlg_step / orlg_step_diag, bit for bit */
+    ORLG_ASSIGN_FIRST_FULL = 1,  /* the lowest window (FIRST without the off-by-one) */
+    ORLG_ASSIGN_LAST = 2,        /* the highest window */
+    ORLG_ASSIGN_BEST = 3,        /* the start of the shortest block of >= n slots; ties go to the lowest start */
+    ORLG_ASSIGN_EXACT = 4,       /* the start of the lowest block of exactly n slots; none: FIRST_FULL */
+    ORLG_NUM_ASSIGN_RULES = 5
+};
+/* orlg_step_diag under assignment rule `assign` (the reference has no counterpart; the routes are its own, rmsa_env.py:854-937).
+ * assign == ORLG_ASSIGN_FIRST is orlg_step_diag and launches what that launches.  For every other rule `policy` is read as a ROUTE
+ * and must be one of ORLG_POLICY_SP_FF (path 0 only), ORLG_POLICY_SAP_FF (the first path in order that has a window),
+ * ORLG_POLICY_LLP_FF (of the paths that have a window the one with the most free slots in A; strict >, ties to the first) or
+ * ORLG_POLICY_PATH_FF_EXTERNAL (actions [B] name the path; out of range or without a window: the rejection (k, S)); the rule
+ * picks the slot on that path.  "Has a window" is a fit level >= ORLG_FIT_LAST_WINDOW (orlg_path_fit_levels): an agent's mask for
+ * the path-only action space comes from that query.  ORLG_ERR_INVALID, before anything is launched: another policy with a rule
+ * other than FIRST (ORLG_POLICY_EXTERNAL names its slot, the DeepRMSA policies index blocks, ORLG_POLICY_SAP_FF_GN), a handle with
+ * a gn_gate, an unknown rule.  diag may be NULL; the blocking causes keep their state-based definitions (sap / llp then refuse
+ * with a cause <= ORLG_CAUSE_ALIGNMENT only).  Such a launch runs the ASSIGN instantiation of the handle's step kernel
+ * (orlg_rmsa_kernel<.., ASSIGN> / orlg_rmsa_group_kernel<.., ASSIGN>, the plain kind of either).  The QoT-aware environment
+ * (orlg_phy_*) has no such entry: its channels are not contiguous. */
+int orlg_step_assign(orlg_env *env, int32_t policy, int32_t assign, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
+                     const orlg_step_io *io, const struct orlg_step_diag *diag);
+
 /* The fit level (ORLG_FIT_*) of every candidate path of every pending request: levels [B][k] uint8.  Reads state and writes
  * only `levels`; looks at windows only on every handle (it does not know a GN-model admission check).  levels == 4 is the
  * path_ff bit of orlg_action_masks, levels >= 3 is "any bit in its slots mask".  Buffer as orlg_action_masks. */

@@ -13,6 +13,24 @@ ERR_NAMES = {-1: "ORLG_ERR_INVALID", -2: "ORLG_ERR_NO_DEVICE", -3: "ORLG_ERR_HIP
 STATS_LEVELS = {"counters": 0, "network": 1, "full": 2}
 POLICIES = {"external": -1, "sp_ff": 0, "sap_ff": 1, "llp_ff": 2, "deeprmsa_sp_ff": 3, "deeprmsa_sap_ff": 4,
             "deeprmsa_external": 5, "path_ff_external": 6, "sap_ff_gn": 7}
+# include/orlg.h ORLG_ASSIGN_*: where on a route's path the service starts (not in the reference, whose heuristics are first fit
+# only, rmsa_env.py:854-937).  "first" is the reference's, with its bound range(0, S - n); the others use every window 0 .. S - n
+ASSIGN_RULES = ("first", "first_full", "last", "best", "exact")
+_ASSIGN_SUFFIX = {"first_full": "ff_full", "last": "lf", "best": "bf", "exact": "ef"}
+# policy name -> (route: the ORLG_POLICY_* that orlg_step_assign reads as one, rule): sp / sap / llp x the four rules, and the
+# agent's path x the four rules
+ASSIGN_POLICIES = {f"{route}_{suffix}": (POLICIES[route + "_ff"], ASSIGN_RULES.index(rule))
+                   for route in ("sp", "sap", "llp") for rule, suffix in _ASSIGN_SUFFIX.items()}
+ASSIGN_POLICIES.update({f"path_{suffix}_external": (POLICIES["path_ff_external"], ASSIGN_RULES.index(rule))
+                        for rule, suffix in _ASSIGN_SUFFIX.items()})
+
+
+def policy_ids(policy):
+    """(ORLG_POLICY_*, ORLG_ASSIGN_*) of a policy name: the reference's policies with rule 0, the names of ``ASSIGN_POLICIES``
+    with theirs.  ``KeyError`` for an unknown name."""
+    if policy in ASSIGN_POLICIES:
+        return ASSIGN_POLICIES[policy]
+    return POLICIES[policy], 0
 
 
 class OrlgError(RuntimeError):
@@ -149,7 +167,9 @@ def _prototypes():
               "orlg_gn_action_masks": (None, [vp, vp, vp, vp, vp]),
               # blocking cause per step, fit level per candidate path
               "orlg_step_diag": (None, [vp, i32, i32, vp, i32, P(StepIO), P(StepDiag)]),
-              "orlg_path_fit_levels": (None, [vp, vp])})
+              "orlg_path_fit_levels": (None, [vp, vp]),
+              # spectrum-assignment rules beyond the reference's first fit
+              "orlg_step_assign": (None, [vp, i32, i32, i32, vp, i32, P(StepIO), P(StepDiag)])})
     # QoT-aware only
     t.update({"orlg_phy_step": (None, [vp, i32, i32, vp, vp, i32, P(PhyStepIO)]), "orlg_phy_node_vectors": (None, [vp]),
               "orlg_phy_get_episode_stats": (None, [vp, vp]), "orlg_phy_channel_masks": (None, [vp, vp]),

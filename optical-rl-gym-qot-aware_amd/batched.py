@@ -102,7 +102,20 @@ class BatchedRMSAEnv(BatchedHandle):
         ``"block_cause"`` in ``outputs`` -- [n_steps, B] uint8, the cause of every step; ``cause_counts=True`` or a [B, 8] int32
         buffer -- ``"block_cause_counts"``, the steps of THIS launch per cause (the library zeroes the buffer; a row sums to
         ``n_steps``).  Either one makes the launch run the step kernel's instantiation with the classifier: the same steps,
-        state and outputs, some percent slower."""
+        state and outputs, some percent slower.
+
+        Assignment rules beyond the reference's first fit (``orlg_step_assign``; not in the reference): the policy
+        names of ``_lib.ASSIGN_POLICIES`` -- a route ``sp`` / ``sap`` / ``llp`` (``rmsa_env.py:854-937``) with ``_ff_full`` (the
+        lowest window of 0 .. S - n, the reference's first fit without its off-by-one), ``_lf`` (the highest window), ``_bf``
+        (the shortest free block of >= n slots, ties to the lowest) or ``_ef`` (the lowest block of exactly n slots, else
+        ``_ff_full``), and ``path_{ff_full,lf,bf,ef}_external`` (``actions`` [B] names the path; a path out of range or without
+        a window is the rejection).  They run wherever ``sap_ff`` runs -- sweep and trace handles, both step kernels, with
+        ``block_cause`` / ``cause_counts`` -- except on a handle with ``gn_gate=`` (``ValueError``).  A path has a window iff
+        ``path_fit_levels() >= 3``: that query is the mask of the path-only action spaces."""
+        pid, rule = _lib.policy_ids(policy)
+        if rule and self.gn_gate is not None:
+            raise ValueError(f"policy {policy!r}: an assignment rule other than the reference's first fit does not run on a handle "
+                             "with a GN-model admission check (gn_gate=)")
         B = self.batch_size
         io = _lib.StepIO()
         names = _output_names(outputs, out)
@@ -122,10 +135,10 @@ class BatchedRMSAEnv(BatchedHandle):
             diag["block_cause_counts"] = cause_counts
         res = self._step_outputs(names, n_steps, out, _lib.STEP_IO_DTYPES, _STEP_IO_SHAPES, io)
         ap = None
-        if policy in ("external", "deeprmsa_external", "path_ff_external"):
+        if pid in (_lib.POLICIES["external"], _lib.POLICIES["deeprmsa_external"], _lib.POLICIES["path_ff_external"]):
             if actions is None:
                 raise ValueError(f"policy {policy!r} needs an actions array")
-            ashape = (B, 2) if policy == "external" else (B,)
+            ashape = (B, 2) if pid == _lib.POLICIES["external"] else (B,)
             if not hasattr(actions, "data_ptr"):
                 actions = np.asarray(actions)
                 if actions.dtype.kind not in "iu":
@@ -133,18 +146,20 @@ class BatchedRMSAEnv(BatchedHandle):
                 actions = np.ascontiguousarray(actions, dtype=np.int32)
             _check_buffer("actions", actions, ashape, np.int32)
             ap = _ptr(actions)
-        if diag:
+        if diag or rule:
             d = _lib.StepDiag(_ptr(diag.get("block_cause")), _ptr(diag.get("block_cause_counts")),
                               None if gsnr is None else _ptr(gsnr["gn_gsnr_db"]))
-            _lib.check(self.L.orlg_step_diag(self.h, _lib.POLICIES[policy], int(n_steps), ap, 1 if auto_reset else 0,
-                                             C.byref(io), C.byref(d)))
+            if rule:
+                _lib.check(self.L.orlg_step_assign(self.h, pid, rule, int(n_steps), ap, 1 if auto_reset else 0, C.byref(io),
+                                                   C.byref(d)))
+            else:
+                _lib.check(self.L.orlg_step_diag(self.h, pid, int(n_steps), ap, 1 if auto_reset else 0, C.byref(io), C.byref(d)))
             res.update(diag)
             res.update(gsnr or {})
         elif gsnr is None:
-            _lib.check(self.L.orlg_step(self.h, _lib.POLICIES[policy], int(n_steps), ap, 1 if auto_reset else 0,
-                                        C.byref(io)))
+            _lib.check(self.L.orlg_step(self.h, pid, int(n_steps), ap, 1 if auto_reset else 0, C.byref(io)))
         else:
-            _lib.check(self.L.orlg_step_gn(self.h, _lib.POLICIES[policy], int(n_steps), ap, 1 if auto_reset else 0,
+            _lib.check(self.L.orlg_step_gn(self.h, pid, int(n_steps), ap, 1 if auto_reset else 0,
                                            C.byref(io), _ptr(gsnr["gn_gsnr_db"])))
             res.update(gsnr)
         return res

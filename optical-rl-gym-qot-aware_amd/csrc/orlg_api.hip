@@ -147,7 +147,8 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p, const OrlgGroupOv
     const bool trace = p.tr_arrival != nullptr;   // a request trace: the instantiations that replay it
     const bool traffic = !trace && p.rates != nullptr;   // per-environment rates: the instantiations that read them
     const bool cause = (p.out_mask & ORLG_OUT_CAUSE_BIT) != 0;   // the blocking cause: the plain kind with the classifier (the plan chose it)
-    const OrlgGroupKey key = {p.stats_level, c.kind == ORLG_GROUP_HBMQ, df, traffic, trace, cause};
+    const bool assign = (p.out_mask & ORLG_OUT_ASSIGN_BIT) != 0;   // an assignment rule: the plain kind with the rules (the plan chose it)
+    const OrlgGroupKey key = {p.stats_level, c.kind == ORLG_GROUP_HBMQ, df, traffic, trace, cause, assign};
     rmsa_kernel_t k = orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     if (df && !e->llog)
@@ -192,12 +193,14 @@ static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
     const bool gn = p.mode == ORLG_MODE_STEP && p.gn != nullptr;
     // a launch that asks for the blocking cause: the general kernel's CAUSE instantiation, with or without the check
     const bool cause = p.mode == ORLG_MODE_STEP && (p.out_mask & ORLG_OUT_CAUSE_BIT) != 0;
-    const bool ff = !gn && !cause && p.mode == ORLG_MODE_STEP && p.K <= 8 && (p.policy == ORLG_POLICY_SP || p.policy == ORLG_POLICY_SAP);
+    // a launch under an assignment rule other than the reference's first fit: the general kernel's ASSIGN instantiation (no gate: refused)
+    const bool assign = p.mode == ORLG_MODE_STEP && (p.out_mask & ORLG_OUT_ASSIGN_BIT) != 0;
+    const bool ff = !gn && !cause && !assign && p.mode == ORLG_MODE_STEP && p.K <= 8 && (p.policy == ORLG_POLICY_SP || p.policy == ORLG_POLICY_SAP);
     const OrlgGroupOverrides ov = group_overrides();
     const bool df = !gn && p.mode == ORLG_MODE_STEP && orlg_defer_link_stats(p.stats_level, p.n_steps, p.out_mask, ov);   // as launch_rmsa_group
     const OrlgWaveKey key = {ff ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel_ff)
                                 : p.mode == ORLG_MODE_STEP ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel) : ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel),
-                             p.stats_level, df, gn, cause};
+                             p.stats_level, df, gn, cause, assign};
     rmsa_kernel_t k = orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), e->lds_block_bytes)) return rc;
@@ -561,14 +564,22 @@ static int extra_out(orlg_env *e, ExtraOut *o, void *user, size_t bytes, int slo
     }
     return ORLG_OK;
 }
-// orlg_step, orlg_step_gn and orlg_step_diag (gsnr, cause, counts: the outputs beyond orlg_step_io, nullptr = not asked for)
+// orlg_step, orlg_step_gn, orlg_step_diag and orlg_step_assign (gsnr, cause, counts: the outputs beyond orlg_step_io, nullptr = not
+// asked for; assign: ORLG_ASSIGN_*, 0 = the reference's first fit)
 static int rmsa_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
-                     const orlg_step_io *io, double *gsnr, uint8_t *cause = nullptr, int32_t *counts = nullptr) {
+                     const orlg_step_io *io, double *gsnr, uint8_t *cause = nullptr, int32_t *counts = nullptr, int32_t assign = ORLG_ASSIGN_FIRST) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     if (n_steps < 1) return fail(ORLG_ERR_INVALID, "n_steps must be >= 1");
     if (policy < ORLG_POLICY_EXTERNAL || policy > ORLG_POLICY_SAP_FF_GN) return fail(ORLG_ERR_INVALID, "unknown policy %d", policy);
     if (policy == ORLG_POLICY_SAP_FF_GN && !e->p.gn)
         return fail(ORLG_ERR_INVALID, "policy %d (sap_ff_gn) asks the GN-model admission check: the handle has no gn_gate", policy);
+    // an assignment rule other than the reference's first fit: the policy is a route, the handle has no gate -- before anything is launched
+    if (assign < ORLG_ASSIGN_FIRST || assign >= ORLG_NUM_ASSIGN_RULES) return fail(ORLG_ERR_INVALID, "unknown assignment rule %d", assign);
+    if (assign != ORLG_ASSIGN_FIRST) {
+        if (policy != ORLG_POLICY_SP_FF && policy != ORLG_POLICY_SAP_FF && policy != ORLG_POLICY_LLP_FF && policy != ORLG_POLICY_PATH_FF_EXTERNAL)
+            return fail(ORLG_ERR_INVALID, "assignment rule %d needs a route (sp_ff, sap_ff, llp_ff or path_ff_external): policy %d names its own slot or block", assign, policy);
+        if (e->p.gn) return fail(ORLG_ERR_INVALID, "assignment rule %d on a handle with a gn_gate: the admission check knows the reference's first fit only", assign);
+    }
     const bool ext = policy == ORLG_POLICY_EXTERNAL || policy == ORLG_POLICY_DEEPRMSA_EXTERNAL || policy == ORLG_POLICY_PATH_FF_EXTERNAL;
     if (ext && (!actions || n_steps != 1)) return fail(ORLG_ERR_INVALID, "external actions need an action array and n_steps == 1");
     {
@@ -617,6 +628,8 @@ static int rmsa_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t
     p.o_cause_counts = static_cast<int32_t *>(xn.dev);
     if (cause || counts) p.out_mask |= ORLG_OUT_CAUSE_BIT;
     if (counts) HIP_TRY(hipMemsetAsync(xn.dev, 0, xn.bytes, e->stream));
+    p.assign = assign;
+    if (assign != ORLG_ASSIGN_FIRST) p.out_mask |= ORLG_OUT_ASSIGN_BIT;   // the launch runs an ASSIGN instantiation
     rc = launch_rmsa(e, p);
     if (rc) return rc;
     if (e->trace.length > 0) e->trace.position += n_steps;
@@ -647,6 +660,11 @@ int orlg_step_diag(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *
                    const struct orlg_step_diag *diag) {
     if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr);
     return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts);
+}
+int orlg_step_assign(orlg_env *e, int32_t policy, int32_t assign, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
+                     const orlg_step_io *io, const struct orlg_step_diag *diag) {
+    if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr, nullptr, nullptr, assign);
+    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, assign);
 }
 
 int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {

@@ -152,11 +152,18 @@ struct OrlgParams {
     // struct's end: every other field lies in the kernarg segment where it lay)
     uint8_t *o_cause;
     int32_t *o_cause_counts;
+    // spectrum-assignment rule (include/orlg.h ORLG_ASSIGN_*, orlg_step_assign; orlg_assign.h), read by the ASSIGN instantiations of
+    // the two step kernels only: `policy` is then the route.  0 = the reference's first fit; a launch with another rule has
+    // ORLG_OUT_ASSIGN_BIT in out_mask.  (At the struct's end, as the cause pointers)
+    int32_t assign;
 };
 // out_mask of a launch that asks for a cause output: not one of outs[], but a per-step output like them -- what looks at
 // out_mask to choose a kernel (the deferred link statistics, the group kernel's HBMQ kind and lean body) keeps such a launch on
 // the plain instantiations, the only ones that exist with the classifier
 enum { ORLG_OUT_CAUSE_BIT = 1 << 30 };
+// out_mask of a launch under an assignment rule other than the reference's first fit (OrlgParams::assign): no output at all, the
+// same device -- the ASSIGN instantiations exist of the plain kind only, and what looks at out_mask keeps the launch on them
+enum { ORLG_OUT_ASSIGN_BIT = 1 << 29, ORLG_OUT_PLAIN_BITS = ORLG_OUT_CAUSE_BIT | ORLG_OUT_ASSIGN_BIT };
 // OrlgParams::gn, in doubles: the gate's scalars, the thresholds by spectral efficiency - 1 from ORLG_GN_THR0, then four per link
 // from ORLG_GN_LINK0 -- effective length of a span, its ratio to the span's length, exp(2 att len) - 1, number of spans
 enum { ORLG_GN_DENSITY = 0, ORLG_GN_F0, ORLG_GN_SLOT, ORLG_GN_ATT, ORLG_GN_NF, ORLG_GN_LEFF_A, ORLG_GN_THR0 = 8, ORLG_GN_LINK0 = 16 };

@@ -1,6 +1,6 @@
 // orlg_group_body.h -- the TEXT of orlg_rmsa_group_kernel's body (orlg_group_kernels.hip), from the first statement to the last.
 // Not a header to include at file scope: it is included INSIDE a function that has the kernel's template arguments (W, STATS,
-// HBMQ, DEFER, TRAFFIC, TRACE), the constants `LEAN` and `CAUSE` and the parameters `p` in scope -- once in the kernel itself and once in
+// HBMQ, DEFER, TRAFFIC, TRACE), the constants `LEAN`, `CAUSE` and `ASSIGN` and the parameters `p` in scope -- once in the kernel itself and once in
 // orlg_rmsa_group_body, which gives the DEFER instantiations their second, lean body.  Why the text and not only the function:
 // a kernel whose body arrives through an inlined function compiles to slightly different code than one that holds the text
 // (other spill placement, a few dozen instructions either way), and the instantiations without a lean body are to stay,
@@ -13,6 +13,7 @@
     static_assert(!(TRACE && TRAFFIC), "a trace handle has no arrival rates");
     static_assert(!LEAN || DEFER, "the lean body belongs to the long launches");
     static_assert(!CAUSE || (!HBMQ && !DEFER), "the blocking cause belongs to the plain kind");
+    static_assert(!ASSIGN || (!HBMQ && !DEFER), "the assignment rules belong to the plain kind");
     extern __shared__ __align__(16) unsigned char smem[];
     stage_tables(smem, p);
     const int lane = threadIdx.x & 63;
@@ -193,7 +194,50 @@
         const int base = req_base;
         int a_path = K, a_slot = S;  // rejection (rmsa_env.py:871,913)
         int ff_n = 1, ff_hops = 0;
-        if (!LEAN && policy == ORLG_POLICY_EXT) {
+        if constexpr (ASSIGN) {
+            // An assignment rule other than the reference's first fit (include/orlg.h ORLG_ASSIGN_*, orlg_assign.h): the policy is
+            // the route -- the first path (sp), the first path that has a window (sap), of the paths that have one the path
+            // with the most free slots, ties to the first (llp; rmsa_env.py:854-937), or the agent's path (rmsa_env.py:982-1005) --
+            // and the rule's key decides the slot on it: one maximum over the path's W lanes, one minimum over the row
+            constexpr int PP = ORLG_GL / W;  // candidate paths per pass
+            const int rule = p.assign;
+            const bool given = policy == ORLG_POLICY_PATH_EXT;
+            int path0 = 0;
+            bool a_ok = true;
+            if (given) {
+                const int a = p.actions[env];
+                a_ok = a >= 0 && a < K;
+                path0 = a_ok ? a : 0;
+            }
+            const bool llp = policy == ORLG_POLICY_LLP;
+            const int kmax = (given || policy == ORLG_POLICY_SP) ? 1 : K;
+            const int ps = gl / W, w = gl - ps * W;
+            int found = 0x7fffffff, found_key = 0x7fffffff;
+            for (int p0 = 0; p0 < kmax; p0 += PP) {
+                if (!llp && ballot(act && a_ok && found == 0x7fffffff) == 0ull) break;
+                const int pp = p0 + ps;
+                const bool on = ps < PP && pp < kmax && a_ok;
+                int se_pp, hops_pp;
+                const u64 x = group_path_word_rec<W>(occ, tb.recs, base + path0 + pp, w, on, se_pp, hops_pp) & valid_mask(S, w);
+                int n = 1;
+                if (on) n = tb.nslots[req_br * ORLG_NSLOT_STRIDE + se_pp];
+                const uint32_t sk = seg_max<W>(assign_word_key<W>(x, n, w, rule));   // the path's key, on its first lane
+                const bool head = on && w == 0 && sk != 0u;
+                const int payload = head ? (((((path0 + pp) << 10) | assign_key_slot(sk, rule)) << 14) | (n << 4) | hops_pp) : 0x7fffffff;
+                if (llp) {
+                    // most free slots, then lowest path (as the first-fit form below)
+                    const uint32_t fs = seg_add<W>((uint32_t)popc64(x));
+                    const int key = head ? (int)(((1023u - fs) << 6) | (uint32_t)pp) : 0x7fffffff;
+                    const int bk = row_min_i32(key);
+                    const int bp = row_min_i32(key == bk ? payload : 0x7fffffff);
+                    if (bk < found_key) { found_key = bk; found = bp; }
+                    continue;
+                }
+                const int best = row_min_i32(payload);
+                if (found == 0x7fffffff) found = best;
+            }
+            if (found != 0x7fffffff) { a_path = found >> 24; a_slot = (found >> 14) & 1023; ff_n = (found >> 4) & 1023; ff_hops = found & 15; }
+        } else if (!LEAN && policy == ORLG_POLICY_EXT) {
             a_path = p.actions[2 * env];
             a_slot = p.actions[2 * env + 1];
         } else {

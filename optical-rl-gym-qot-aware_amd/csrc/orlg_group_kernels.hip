@@ -25,6 +25,7 @@
 #include "orlg_requests.h"
 #include "orlg_sections.h"
 #include "orlg_block_cause.h"  // window_level: the classifier of the CAUSE instantiations (group_fit_level below)
+#include "orlg_assign.h"       // assign_word_key: the assignment rules of the ASSIGN instantiations
 
 #define ORLG_GL 16  // lanes per environment (one DPP row)
 #define ORLG_GE 4   // environments per wave
@@ -457,6 +458,7 @@ DEV int group_fit_level(int lane, const u64 *occ, const Tab &tb, int base, int K
 template <int W, int STATS, bool HBMQ, bool DEFER, bool TRAFFIC, bool TRACE, bool LEAN>
 DEV void orlg_rmsa_group_body(const OrlgParams &p) {
     constexpr bool CAUSE = false;   // (the DEFER instantiations have no classifier: a cause launch runs the plain kind)
+    constexpr bool ASSIGN = false;  // (... and no assignment rule but the reference's first fit)
 #include "orlg_group_body.h"
 }
 
@@ -465,7 +467,9 @@ DEV void orlg_rmsa_group_body(const OrlgParams &p) {
 // CAUSE: the launch asks for the blocking cause of its steps (include/orlg.h orlg_step_diag): the rows whose step is not accepted
 // are classified (group_fit_level) before the provision touches the occupancy.  A template argument for the same reason as
 // TRAFFIC; the plain kind only (orlg_group_plan.h keeps such a launch on it)
-template <int W, int STATS, bool HBMQ = false, bool DEFER = false, bool TRAFFIC = false, bool TRACE = false, bool CAUSE = false>
+// ASSIGN: the launch runs an assignment rule other than the reference's first fit (include/orlg.h orlg_step_assign,
+// OrlgParams::assign; orlg_assign.h): the policy section is the rules' own.  A template argument and the plain kind only, as CAUSE
+template <int W, int STATS, bool HBMQ = false, bool DEFER = false, bool TRAFFIC = false, bool TRACE = false, bool CAUSE = false, bool ASSIGN = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3) / 4) void orlg_rmsa_group_kernel(const OrlgParams p) {
     if constexpr (DEFER) {
         if (p.g_lean) orlg_rmsa_group_body<W, STATS, HBMQ, DEFER, TRAFFIC, TRACE, true>(p);

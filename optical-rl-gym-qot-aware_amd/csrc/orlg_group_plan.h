@@ -50,16 +50,17 @@ struct OrlgGroupTickets { int n_quads, nblocks, n_chunks, chunk_steps; uint32_t 
 // logs the links' updates and works them off one link per lane (group_link_replay; link_replay of the wave-per-environment kernel)
 static inline bool orlg_defer_link_stats(int stats_level, int n_steps, int out_mask, const OrlgGroupOverrides &ov) {
     return stats_level >= 2 && n_steps >= 16 && !ov.no_defer &&
-           !(out_mask & ((1 << ORLG_OUT_AVG_LINK_COMPACT) | (1 << ORLG_OUT_AVG_LINK_UTIL) | ORLG_OUT_CAUSE_BIT));
+           !(out_mask & ((1 << ORLG_OUT_AVG_LINK_COMPACT) | (1 << ORLG_OUT_AVG_LINK_UTIL) | ORLG_OUT_PLAIN_BITS));
 }
 
 static inline OrlgGroupChoice orlg_group_choose(const OrlgGroupLayout *layouts, const OrlgGroupLaunch &a, const OrlgGroupOverrides &ov, int num_cu) {
     OrlgGroupChoice c = {};
     // launches of very few steps leave the release queue in HBM (the kernel's HBMQ instantiation): without the queue's slices an
     // environment takes half the LDS, and such a launch is bound by the waves a CU keeps resident
-    // (a launch that asks for a blocking cause, ORLG_OUT_CAUSE_BIT: the plain kind whatever its length -- the classifier's instantiations)
+    // (a launch that asks for a blocking cause, ORLG_OUT_CAUSE_BIT, or runs an assignment rule, ORLG_OUT_ASSIGN_BIT: the plain kind
+    // whatever its length -- the only instantiations with the classifier and with the rules)
     const bool hq = a.n_steps <= ORLG_DIRECT_STEPS && layouts[ORLG_GROUP_HBMQ].wpb_max > layouts[ORLG_GROUP_PLAIN].wpb_max &&
-                    !(a.out_mask & ORLG_OUT_CAUSE_BIT);
+                    !(a.out_mask & ORLG_OUT_PLAIN_BITS);
     const bool df = !hq && orlg_defer_link_stats(a.stats_level, a.n_steps, a.out_mask, ov) && layouts[ORLG_GROUP_DEFER].wpb_max >= 1;
     c.kind = hq ? ORLG_GROUP_HBMQ : df ? ORLG_GROUP_DEFER : ORLG_GROUP_PLAIN;
     const int wpb_max = layouts[c.kind].wpb_max, n_quads = (a.B + 3) / 4;

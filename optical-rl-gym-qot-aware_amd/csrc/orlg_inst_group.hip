@@ -13,6 +13,7 @@ orlg_rmsa_kernel_t ORLG_CAT(orlg_group_kernel_W, ORLG_INST_W)(OrlgGroupKey key) 
 #define X(...) if (key == OrlgGroupKey{__VA_ARGS__}) return orlg_rmsa_group_kernel<ORLG_INST_W, __VA_ARGS__>;
     ORLG_GROUP_KEYS(X)
     ORLG_GROUP_CAUSE_KEYS(X)
+    ORLG_GROUP_ASSIGN_KEYS(X)
 #undef X
     return nullptr;
 }

@@ -19,6 +19,7 @@ orlg_rmsa_kernel_t ORLG_CAT(orlg_wave_kernel_W, ORLG_INST_W)(OrlgWaveKey key) {
     ORLG_WAVE_KEYS(X)
     ORLG_WAVE_GN_KEYS(X)
     ORLG_WAVE_CAUSE_KEYS(X)
+    ORLG_WAVE_ASSIGN_KEYS(X)
 #undef X
     return nullptr;
 }

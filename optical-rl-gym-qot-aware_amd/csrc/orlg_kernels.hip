@@ -35,6 +35,7 @@
 #include "orlg_requests.h"     // mt_regenerate, the ring's three producers, ring_store, ring_visible, orlg_env_rates
 #include "orlg_rmsa_gn.h"      // rmsa_gn_gsnr: the GN-model admission check of the GN instantiations
 #include "orlg_block_cause.h"  // wave_fit_levels: the classifier of the CAUSE instantiations
+#include "orlg_assign.h"       // wave_assign: the assignment rules of the ASSIGN instantiations
 #include "orlg_sections.h"
 
 // ---------------------------------------------------------------------------------------- the step kernel
@@ -50,6 +51,9 @@
 // CAUSE: the launch asks for the blocking cause of its steps (include/orlg.h orlg_step_diag, OrlgParams::o_cause /
 // o_cause_counts): a step that is not accepted is classified (orlg_block_cause.h) on the occupancy it met -- a refused step
 // provisions nothing, so that is still the occupancy when the outputs are written; every other instantiation holds none of it.
+// ASSIGN: the launch runs an assignment rule other than the reference's first fit (include/orlg.h orlg_step_assign,
+// OrlgParams::assign): the policy is read as a route (sp, sap, llp, or the agent's path) and wave_assign (orlg_assign.h) is the
+// whole policy section; it proposes free windows only.  No other instantiation holds any of it.
 template <bool GN>
 struct SapRetry {
     int from = 0, path = 0, slot = 0;
@@ -61,7 +65,7 @@ struct SapRetry<false> {
     SapRetry() = default;
 };
 
-template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false, bool GN = false, bool CAUSE = false>
+template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false>
 DEV void rmsa_body(const OrlgParams &p) {
     extern __shared__ __align__(16) unsigned char smem[];
 #ifdef ORLG_SHAPE_ASSUME
@@ -228,7 +232,12 @@ DEV void rmsa_body(const OrlgParams &p) {
 
             int a_path = K, a_slot = S;  // rejection (rmsa_env.py:871,913)
             const int policy = p.policy;
-            if (FF) {
+            if constexpr (ASSIGN) {
+                KernargParams kq = kernarg_params();
+                const int given = policy == ORLG_POLICY_PATH_EXT ? uni(kq->actions[env]) : 0;
+                const int got = wave_assign<W>(wv.occ, tb, base, K, S, req_br, lane, policy, kq->assign, given);
+                if (got >= 0) { a_path = got >> 10; a_slot = got & 1023; }
+            } else if (FF) {
                 const int kmax = policy == ORLG_POLICY_SP ? 1 : K;
                 const bool on = pp < kmax && pw < W;
                 int n_l = 1;
@@ -322,7 +331,7 @@ DEV void rmsa_body(const OrlgParams &p) {
                 const int n = __builtin_amdgcn_readlane(my_n, a_path);
                 // the device policies only propose windows they found free; agent actions are checked (is_path_free)
                 bool window_ok = true;
-                if (!FF && (policy == ORLG_POLICY_EXT || policy == ORLG_POLICY_PATH_EXT || policy == ORLG_POLICY_DEEP_EXT)) {
+                if (!FF && !ASSIGN && (policy == ORLG_POLICY_EXT || policy == ORLG_POLICY_PATH_EXT || policy == ORLG_POLICY_DEEP_EXT)) {
                     u64 x[W];
 #pragma unroll
                     for (int w = 0; w < W; ++w) x[w] = readlane64(acc, a_path * LS + w);
@@ -640,9 +649,9 @@ DEV void rmsa_body(const OrlgParams &p) {
     SEC_FLUSH;
 }
 
-template <int W, int STATS, bool DEFER = false, bool GN = false, bool CAUSE = false>
+template <int W, int STATS, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel(const OrlgParams p) {
-    rmsa_body<W, STATS, true, false, DEFER, GN, CAUSE>(p);
+    rmsa_body<W, STATS, true, false, DEFER, GN, CAUSE, ASSIGN>(p);
 }
 template <int W, int STATS, bool DEFER = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel_ff(const OrlgParams p) {

@@ -10,9 +10,10 @@
 #include "../../include/orlg.h"   // ORLG_PHY_POLICY_*
 
 // ---------------------------------------------------------------------------------------- keys
-// wave-per-environment kernels (orlg_kernels.hip): template <int W, int STATS, bool DEFER = false, bool GN = false, bool CAUSE = false>;
-// the reset kernel has no DEFER, and only orlg_rmsa_kernel has GN (the GN-model admission check, orlg_rmsa_gn.h) and CAUSE (the
-// blocking cause of every step, orlg_block_cause.h)
+// wave-per-environment kernels (orlg_kernels.hip): template <int W, int STATS, bool DEFER = false, bool GN = false, bool CAUSE = false,
+// bool ASSIGN = false>; the reset kernel has no DEFER, and only orlg_rmsa_kernel has GN (the GN-model admission check,
+// orlg_rmsa_gn.h), CAUSE (the blocking cause of every step, orlg_block_cause.h) and ASSIGN (the spectrum-assignment rules beyond
+// the reference's first fit, orlg_assign.h)
 #define ORLG_WAVE_KERNELS(X) X(orlg_rmsa_kernel) X(orlg_rmsa_kernel_ff) X(orlg_rmsa_reset_kernel)
 #define ORLG_WAVE_KERNEL(name) ORLG_IS_##name
 enum OrlgWaveKernel {
@@ -20,15 +21,15 @@ enum OrlgWaveKernel {
     ORLG_WAVE_KERNELS(X)
 #undef X
 };
-struct OrlgWaveKey { OrlgWaveKernel kernel; int STATS; bool DEFER; bool GN = false; bool CAUSE = false; };
+struct OrlgWaveKey { OrlgWaveKernel kernel; int STATS; bool DEFER; bool GN = false; bool CAUSE = false; bool ASSIGN = false; };
 // orlg_rmsa_group_kernel (orlg_group_kernels.hip)
-struct OrlgGroupKey { int STATS; bool HBMQ, DEFER, TRAFFIC, TRACE; bool CAUSE = false; };
+struct OrlgGroupKey { int STATS; bool HBMQ, DEFER, TRAFFIC, TRACE; bool CAUSE = false; bool ASSIGN = false; };
 // orlg_phy_kernel (orlg_phy_kernels.hip)
 struct OrlgPhyKey { bool DF, GN; int POL; bool CONT, TRACE; };
 
-inline bool operator==(const OrlgWaveKey &a, const OrlgWaveKey &b) { return a.kernel == b.kernel && a.STATS == b.STATS && a.DEFER == b.DEFER && a.GN == b.GN && a.CAUSE == b.CAUSE; }
+inline bool operator==(const OrlgWaveKey &a, const OrlgWaveKey &b) { return a.kernel == b.kernel && a.STATS == b.STATS && a.DEFER == b.DEFER && a.GN == b.GN && a.CAUSE == b.CAUSE && a.ASSIGN == b.ASSIGN; }
 inline bool operator==(const OrlgGroupKey &a, const OrlgGroupKey &b) {
-    return a.STATS == b.STATS && a.HBMQ == b.HBMQ && a.DEFER == b.DEFER && a.TRAFFIC == b.TRAFFIC && a.TRACE == b.TRACE && a.CAUSE == b.CAUSE;
+    return a.STATS == b.STATS && a.HBMQ == b.HBMQ && a.DEFER == b.DEFER && a.TRAFFIC == b.TRAFFIC && a.TRACE == b.TRACE && a.CAUSE == b.CAUSE && a.ASSIGN == b.ASSIGN;
 }
 inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
     return a.DF == b.DF && a.GN == b.GN && a.POL == b.POL && a.CONT == b.CONT && a.TRACE == b.TRACE;
@@ -55,6 +56,12 @@ inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
 #define ORLG_WAVE_CAUSE_KEYS(X)                                                                                             \
     X(orlg_rmsa_kernel, 1, false, false, true) X(orlg_rmsa_kernel, 2, false, false, true) X(orlg_rmsa_kernel, 0, false, false, true) \
     X(orlg_rmsa_kernel, 1, false, true, true) X(orlg_rmsa_kernel, 2, false, true, true) X(orlg_rmsa_kernel, 0, false, true, true)
+// X(kernel, STATS, DEFER, GN, CAUSE, ASSIGN): what a launch under an assignment rule other than the reference's first fit runs
+// (orlg_step_assign) -- the general step kernel with the rules, per statistics level, without and with the classifier; no gate
+// (refused), no _ff and no DEFER variant.  A list of its own for the reasons above, expanded after the CAUSE keys.
+#define ORLG_WAVE_ASSIGN_KEYS(X)                                                                                                          \
+    X(orlg_rmsa_kernel, 1, false, false, false, true) X(orlg_rmsa_kernel, 2, false, false, false, true) X(orlg_rmsa_kernel, 0, false, false, false, true) \
+    X(orlg_rmsa_kernel, 1, false, false, true, true) X(orlg_rmsa_kernel, 2, false, false, true, true) X(orlg_rmsa_kernel, 0, false, false, true, true)
 
 // X(STATS, HBMQ, DEFER, TRAFFIC, TRACE).  Per kind of handle: every statistics level, the same with the release queue left in HBM
 // (launches of very few steps), and full statistics with the link updates deferred (long launches).  The kinds: plain, with
@@ -71,6 +78,14 @@ inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
     X(0, false, false, TRAFFIC, TRACE, true) X(1, false, false, TRAFFIC, TRACE, true) X(2, false, false, TRAFFIC, TRACE, true)
 #define ORLG_GROUP_CAUSE_KEYS(X) \
     ORLG_GROUP_CAUSE_KEYS_OF(X, false, false) ORLG_GROUP_CAUSE_KEYS_OF(X, true, false) ORLG_GROUP_CAUSE_KEYS_OF(X, false, true)
+// X(STATS, HBMQ, DEFER, TRAFFIC, TRACE, CAUSE, ASSIGN): the launches under an assignment rule other than the reference's first fit
+// -- the plain kind per statistics level and kind of handle, without and with the classifier (orlg_group_plan.h keeps such a
+// launch off HBMQ, DEFER and the lean body through ORLG_OUT_ASSIGN_BIT).  A list of its own, expanded after the CAUSE keys
+#define ORLG_GROUP_ASSIGN_KEYS_OF(X, TRAFFIC, TRACE, CAUSE) \
+    X(0, false, false, TRAFFIC, TRACE, CAUSE, true) X(1, false, false, TRAFFIC, TRACE, CAUSE, true) X(2, false, false, TRAFFIC, TRACE, CAUSE, true)
+#define ORLG_GROUP_ASSIGN_KEYS(X)                                                                                                           \
+    ORLG_GROUP_ASSIGN_KEYS_OF(X, false, false, false) ORLG_GROUP_ASSIGN_KEYS_OF(X, true, false, false) ORLG_GROUP_ASSIGN_KEYS_OF(X, false, true, false) \
+    ORLG_GROUP_ASSIGN_KEYS_OF(X, false, false, true) ORLG_GROUP_ASSIGN_KEYS_OF(X, true, false, true) ORLG_GROUP_ASSIGN_KEYS_OF(X, false, true, true)
 
 // X(DF, GN, POL, CONT, TRACE), one instantiation per policy (-1 external actions .. 6).  Discrete bit rates: the step kernel
 // proper, + periodic defragmentation, + defragmentation and the GN-model admission check, + the check alone (a handle without
@@ -103,8 +118,10 @@ inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
 inline constexpr OrlgWaveKey ORLG_WAVE_KEY_LIST[] = {ORLG_WAVE_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgWaveKey ORLG_WAVE_GN_KEY_LIST[] = {ORLG_WAVE_GN_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgWaveKey ORLG_WAVE_CAUSE_KEY_LIST[] = {ORLG_WAVE_CAUSE_KEYS(ORLG_WAVE_KEY_ENTRY)};
+inline constexpr OrlgWaveKey ORLG_WAVE_ASSIGN_KEY_LIST[] = {ORLG_WAVE_ASSIGN_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_KEY_LIST[] = {ORLG_GROUP_KEYS(ORLG_GROUP_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_CAUSE_KEY_LIST[] = {ORLG_GROUP_CAUSE_KEYS(ORLG_GROUP_KEY_ENTRY)};
+inline constexpr OrlgGroupKey ORLG_GROUP_ASSIGN_KEY_LIST[] = {ORLG_GROUP_ASSIGN_KEYS(ORLG_GROUP_KEY_ENTRY)};
 inline constexpr OrlgPhyKey ORLG_PHY_KEY_LIST[] = {ORLG_PHY_KEYS(ORLG_PHY_KEY_ENTRY)};
 template <typename Key, size_t N>
 static int orlg_key_index(const Key (&list)[N], const Key &key) {
@@ -129,12 +146,12 @@ inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgWaveKey &k)
 #define X(name) #name,
     static const char *const names[] = {ORLG_WAVE_KERNELS(X)};
 #undef X
-    const OrlgArg args[] = {{k.STATS, 'i'}, {k.DEFER, 'd'}, {k.GN, 'd'}, {k.CAUSE, 'd'}};
-    orlg_format_kernel(buf, cap, names[k.kernel], W, args, k.kernel == ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel) ? 1 : 4);
+    const OrlgArg args[] = {{k.STATS, 'i'}, {k.DEFER, 'd'}, {k.GN, 'd'}, {k.CAUSE, 'd'}, {k.ASSIGN, 'd'}};
+    orlg_format_kernel(buf, cap, names[k.kernel], W, args, k.kernel == ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel) ? 1 : 5);
 }
 inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgGroupKey &k) {
-    const OrlgArg args[] = {{k.STATS, 'i'}, {k.HBMQ, 'd'}, {k.DEFER, 'd'}, {k.TRAFFIC, 'd'}, {k.TRACE, 'd'}, {k.CAUSE, 'd'}};
-    orlg_format_kernel(buf, cap, "orlg_rmsa_group_kernel", W, args, 6);
+    const OrlgArg args[] = {{k.STATS, 'i'}, {k.HBMQ, 'd'}, {k.DEFER, 'd'}, {k.TRAFFIC, 'd'}, {k.TRACE, 'd'}, {k.CAUSE, 'd'}, {k.ASSIGN, 'd'}};
+    orlg_format_kernel(buf, cap, "orlg_rmsa_group_kernel", W, args, 7);
 }
 inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgPhyKey &k) {
     const OrlgArg args[] = {{k.DF, 'b'}, {k.GN, 'b'}, {k.POL, 'i'}, {k.CONT, 'd'}, {k.TRACE, 'd'}};

@@ -19,7 +19,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import traffic as _traffic
+from . import _lib, traffic as _traffic
 from .batched import DEFAULT_BIT_RATES, BatchedDeepRMSAEnv, BatchedRMSAEnv
 from .topology import FrozenTopology, Path, Service
 
@@ -455,9 +455,19 @@ class SimpleMatrixObservation:
 
 
 class PathOnlyFirstFitAction:
-    """``rmsa_env.py:974-1008``: the agent chooses the path, the slot is the first fit (resolved on the device)."""
+    """``rmsa_env.py:974-1008``: the agent chooses the path, the slot is the first fit (resolved on the device).
 
-    def __init__(self, env):
+    ``assign=`` (not in the reference): another rule of ``ASSIGN_RULES`` picks the slot on the agent's path -- what the device
+    policies ``path_{ff_full,lf,bf,ef}_external`` resolve (``BatchedRMSAEnv.run``); the default ``"first"`` is the reference's."""
+
+    assign, policy = "first", "path_ff_external"   # the reference's wrapper
+
+    def __init__(self, env, assign="first"):
+        if assign not in _lib.ASSIGN_RULES:
+            raise ValueError(f"assign {assign!r}: expected one of {_lib.ASSIGN_RULES}")
+        self.assign = assign
+        # the device policy that resolves the same actions for a whole batch
+        self.policy = "path_ff_external" if assign == "first" else f"path_{_lib._ASSIGN_SUFFIX[assign]}_external"
         self.env = env
         inner = env
         while not isinstance(inner, RMSAEnv):
@@ -471,6 +481,13 @@ class PathOnlyFirstFitAction:
 
     def action(self, action) -> Tuple[int, int]:
         e = self._inner
+        if self.assign != "first":
+            if 0 <= action < e.k_paths:
+                path = e.k_shortest_paths[e.current_service.source, e.current_service.destination][action]
+                s = assignment_slot(e.get_available_slots(path), e.get_number_slots(path), self.assign)
+                if s is not None:
+                    return (action, s)
+            return (e.topology.graph["k_paths"], e.topology.graph["num_spectrum_resources"])
         if action < e.k_paths:
             path = e.k_shortest_paths[e.current_service.source, e.current_service.destination][action]
             n = e.get_number_slots(path)
@@ -481,7 +498,15 @@ class PathOnlyFirstFitAction:
 
     def action_masks(self, gn=False):
         """Valid paths for the pending request: bool [k + reject], True where ``action(p)`` finds a slot.  ``gn=True`` (a
-        ``gn_gate=`` environment): ... and the GN-model admission check admits that window (``"path_ff_gn"``)."""
+        ``gn_gate=`` environment): ... and the GN-model admission check admits that window (``"path_ff_gn"``).  With
+        ``assign=`` another rule: the paths that have a window, ``path_fit_levels() >= 3`` (no mask kernel of its own)."""
+        if self.assign != "first":
+            if gn:
+                raise ValueError("action_masks(gn=True): the assignment rules do not run with a GN-model admission check")
+            e = self._inner
+            m = np.ones(e.k_paths + e.reject_action, bool)
+            m[:e.k_paths] = e._batched.path_fit_levels()[e._index] >= 3
+            return m
         return self._inner._batched.action_masks("path_ff_gn" if gn else "path_ff")[self._inner._index].astype(bool)
 
     def step(self, action):
@@ -531,6 +556,67 @@ def shortest_available_path_first_fit_gn(env: RMSAEnv) -> Tuple[int, int]:
         if env.is_path_free(path, s, n):
             return (idp, s)
     return (k, S)
+
+
+def assignment_slot(available, n, rule):
+    """The start slot of assignment rule ``rule`` (``ASSIGN_RULES``; include/orlg.h ``ORLG_ASSIGN_*``, not in the reference) for a
+    request of ``n`` slots on a path whose availability vector is ``available`` (``get_available_slots``), or None when the path
+    has no window.  A window is a start ``s`` in ``0 .. S - n`` inclusive with ``[s, s + n)`` free; ``"first"`` alone keeps the
+    reference's bound ``range(0, S - n)``.  A block is a maximal free run (``rmsa_env.py:774-804``)."""
+    a = np.asarray(available).astype(bool)
+    S = len(a)
+    starts, values, lengths = RMSAEnv.rle(a)
+    if starts is None:
+        return None
+    ok = np.flatnonzero(values & (lengths >= n))   # the blocks that hold the request
+    if rule == "first":
+        for b in ok:
+            if starts[b] < S - n:
+                return int(starts[b])
+        return None
+    if ok.size == 0:
+        return None
+    if rule == "first_full":
+        return int(starts[ok[0]])
+    if rule == "last":
+        return int(starts[ok[-1]] + lengths[ok[-1]] - n)
+    if rule == "best":
+        return int(starts[ok[np.argmin(lengths[ok])]])   # (argmin: the first of equal lengths, the lowest start)
+    if rule == "exact":
+        same = ok[lengths[ok] == n]
+        return int(starts[same[0] if same.size else ok[0]])
+    raise ValueError(f"rule {rule!r}: expected one of {_lib.ASSIGN_RULES}")
+
+
+def assignment_heuristic(route, rule):
+    """A heuristic ``f(env) -> [path, slot]`` in the drop-in callback shape of ``shortest_available_path_first_fit``: route
+    ``"sp"`` (path 0), ``"sap"`` (the first path that has a window) or ``"llp"`` (of the paths that have a window the one with
+    the most free slots, strict ``>``; ``rmsa_env.py:854-937``) with assignment rule ``rule`` of ``ASSIGN_RULES`` on it.  Not in
+    the reference beyond ``rule="first"``; what the device policies ``{sp,sap,llp}_{ff,ff_full,lf,bf,ef}`` propose, written on
+    the view's own ``get_available_slots`` / ``get_number_slots``."""
+    if route not in ("sp", "sap", "llp"):
+        raise ValueError(f"route {route!r}: expected 'sp', 'sap' or 'llp'")
+    if rule not in _lib.ASSIGN_RULES:
+        raise ValueError(f"rule {rule!r}: expected one of {_lib.ASSIGN_RULES}")
+
+    def heuristic(env):
+        S, k = env.topology.graph["num_spectrum_resources"], env.topology.graph["k_paths"]
+        paths = env.k_shortest_paths[env.current_service.source, env.current_service.destination]
+        best, action = 0, [k, S]
+        for idp, path in enumerate(paths[:1] if route == "sp" else paths):
+            available = env.get_available_slots(path)
+            s = assignment_slot(available, env.get_number_slots(path), rule)
+            if s is None:
+                continue
+            if route != "llp":
+                return [idp, s]
+            free = int(np.sum(available))
+            if free > best:
+                best, action = free, [idp, s]
+        return action
+
+    heuristic.__name__ = f"{route}_{rule}"
+    return heuristic
 
 
 def least_loaded_path_first_fit(env: RMSAEnv) -> Tuple[int, int]:
