@@ -287,6 +287,29 @@ enum {
 int orlg_step_assign(orlg_env *env, int32_t policy, int32_t assign, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
                      const orlg_step_io *io, const struct orlg_step_diag *diag);
 
+/* ---- fragmentation-aware assignment: the window with the fewest cuts (not in the reference for these environments: it has the cut
+ * count on its QoT-aware environment only, calculate_r_cut).  With A, n and WINDOW as above and free_l(t) = link l's
+ * availability at slot t, free_l(-1) = free_l(S) = 0:
+ *     cuts(p, s) = the number of links l of path p with free_l(s - 1) and free_l(s + n) both set
+ * -- the links on which the window [s, s + n) splits one free block into two (Yin et al. 2013); 0 .. hops.  The rule MIN_CUT takes
+ * the window with the fewest cuts, ties to the lowest start.  Integer-exact. */
+/* a route of orlg_step_min_cut that no policy is: of all k paths the one whose MIN_CUT window has the fewest cuts, ties to the lowest
+ * path index (outside the ORLG_POLICY_* values on purpose: no other entry point accepts it) */
+#define ORLG_ROUTE_FEWEST_CUTS 100
+/* orlg_step_diag under the rule MIN_CUT.  `route` is ORLG_POLICY_SP_FF, ORLG_POLICY_SAP_FF, ORLG_POLICY_LLP_FF or
+ * ORLG_POLICY_PATH_FF_EXTERNAL (actions [B] name the path), read exactly as orlg_step_assign reads them for its rules other than
+ * FIRST ("has a window" is the same predicate), or ORLG_ROUTE_FEWEST_CUTS.  No path of the route with a window: the rejection
+ * (k, S).  ORLG_ERR_INVALID, before anything is launched: any other route, a handle with a gn_gate.  diag may be NULL; block_cause
+ * and cause_counts as under orlg_step_assign (sap, llp and fewest-cuts refuse with a cause <= ORLG_CAUSE_ALIGNMENT only).  Runs the
+ * CUT instantiation of the handle's step kernel (orlg_rmsa_kernel<.., ASSIGN, CUT> / orlg_rmsa_group_kernel<.., ASSIGN, CUT>, the
+ * plain kind of either).  orlg_step_assign itself knows ORLG_NUM_ASSIGN_RULES rules and not this one. */
+int orlg_step_min_cut(orlg_env *env, int32_t route, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
+                      const struct orlg_step_diag *diag);
+/* The MIN_CUT window of every candidate path of every pending request: cuts [B][k] int16 (its cut count, -1 = the path has no
+ * window), slots [B][k] int16 (its start, S = no window).  Either may be NULL, not both.  Reads state and writes only its outputs:
+ * an agent's feature and mask for the path-only action space.  Buffers as orlg_action_masks. */
+int orlg_path_min_cuts(orlg_env *env, int16_t *cuts, int16_t *slots);
+
 /* The fit level (ORLG_FIT_*) of every candidate path of every pending request: levels [B][k] uint8.  Reads state and writes
  * only `levels`; looks at windows only on every handle (it does not know a GN-model admission check).  levels == 4 is the
  * path_ff bit of orlg_action_masks, levels >= 3 is "any bit in its slots mask".  Buffer as orlg_action_masks. */

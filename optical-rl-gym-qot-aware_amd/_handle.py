@@ -233,8 +233,8 @@ class BatchedHandle:
 
     def last_kernel(self) -> str:
         """Name, template arguments and launch shape of the kernel behind the last ``run`` / ``reset``."""
-        buf = C.create_string_buffer(128)
-        _lib.check(self._c.last_kernel(self.h, buf, 128))
+        buf = C.create_string_buffer(160)
+        _lib.check(self._c.last_kernel(self.h, buf, 160))
         return buf.value.decode()
 
     # ------------------------------------------------------------------ stepping

@@ -23,6 +23,13 @@ ASSIGN_POLICIES = {f"{route}_{suffix}": (POLICIES[route + "_ff"], ASSIGN_RULES.i
                    for route in ("sp", "sap", "llp") for rule, suffix in _ASSIGN_SUFFIX.items()}
 ASSIGN_POLICIES.update({f"path_{suffix}_external": (POLICIES["path_ff_external"], ASSIGN_RULES.index(rule))
                         for rule, suffix in _ASSIGN_SUFFIX.items()})
+# include/orlg.h orlg_step_min_cut: the window with the fewest cuts (the links on which it splits a free block in two; DESIGN 2.24,
+# not in the reference for these environments).  policy name -> the route orlg_step_min_cut takes: sp / sap / llp and the agent's
+# path as above, and "min_cut" = ORLG_ROUTE_FEWEST_CUTS, of all k paths the one whose fewest-cuts window has the fewest cuts.  A
+# table of its own: ASSIGN_POLICIES, ASSIGN_RULES and policy_ids answer for the names they always answered for
+ROUTE_FEWEST_CUTS = 100
+CUT_POLICIES = {"sp_mc": POLICIES["sp_ff"], "sap_mc": POLICIES["sap_ff"], "llp_mc": POLICIES["llp_ff"], "min_cut": ROUTE_FEWEST_CUTS,
+                "path_mc_external": POLICIES["path_ff_external"]}
 
 
 def policy_ids(policy):
@@ -169,7 +176,10 @@ def _prototypes():
               "orlg_step_diag": (None, [vp, i32, i32, vp, i32, P(StepIO), P(StepDiag)]),
               "orlg_path_fit_levels": (None, [vp, vp]),
               # spectrum-assignment rules beyond the reference's first fit
-              "orlg_step_assign": (None, [vp, i32, i32, i32, vp, i32, P(StepIO), P(StepDiag)])})
+              "orlg_step_assign": (None, [vp, i32, i32, i32, vp, i32, P(StepIO), P(StepDiag)]),
+              # the window with the fewest cuts: the step under it, and every candidate path's such window
+              "orlg_step_min_cut": (None, [vp, i32, i32, vp, i32, P(StepIO), P(StepDiag)]),
+              "orlg_path_min_cuts": (None, [vp, vp, vp])})
     # QoT-aware only
     t.update({"orlg_phy_step": (None, [vp, i32, i32, vp, vp, i32, P(PhyStepIO)]), "orlg_phy_node_vectors": (None, [vp]),
               "orlg_phy_get_episode_stats": (None, [vp, vp]), "orlg_phy_channel_masks": (None, [vp, vp]),

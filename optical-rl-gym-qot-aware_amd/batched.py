@@ -111,9 +111,16 @@ class BatchedRMSAEnv(BatchedHandle):
         ``_ff_full``), and ``path_{ff_full,lf,bf,ef}_external`` (``actions`` [B] names the path; a path out of range or without
         a window is the rejection).  They run wherever ``sap_ff`` runs -- sweep and trace handles, both step kernels, with
         ``block_cause`` / ``cause_counts`` -- except on a handle with ``gn_gate=`` (``ValueError``).  A path has a window iff
-        ``path_fit_levels() >= 3``: that query is the mask of the path-only action spaces."""
-        pid, rule = _lib.policy_ids(policy)
-        if rule and self.gn_gate is not None:
+        ``path_fit_levels() >= 3``: that query is the mask of the path-only action spaces.
+
+        The window with the fewest cuts (``orlg_step_min_cut``; not in the reference for these environments): the
+        names of ``_lib.CUT_POLICIES`` -- ``sp_mc`` / ``sap_mc`` / ``llp_mc`` (the routes above; on the path the window that
+        splits a free block in two on the fewest links, ties to the lowest start), ``min_cut`` (of all k paths the one whose such
+        window has the fewest cuts, ties to the lowest path) and ``path_mc_external`` (``actions`` [B] names the path).  They run
+        where the names above run, with the same exception; :meth:`path_min_cuts` is the matching query."""
+        cut = policy in _lib.CUT_POLICIES
+        pid, rule = (_lib.CUT_POLICIES[policy], 0) if cut else _lib.policy_ids(policy)
+        if (rule or cut) and self.gn_gate is not None:
             raise ValueError(f"policy {policy!r}: an assignment rule other than the reference's first fit does not run on a handle "
                              "with a GN-model admission check (gn_gate=)")
         B = self.batch_size
@@ -146,10 +153,12 @@ class BatchedRMSAEnv(BatchedHandle):
                 actions = np.ascontiguousarray(actions, dtype=np.int32)
             _check_buffer("actions", actions, ashape, np.int32)
             ap = _ptr(actions)
-        if diag or rule:
+        if diag or rule or cut:
             d = _lib.StepDiag(_ptr(diag.get("block_cause")), _ptr(diag.get("block_cause_counts")),
                               None if gsnr is None else _ptr(gsnr["gn_gsnr_db"]))
-            if rule:
+            if cut:
+                _lib.check(self.L.orlg_step_min_cut(self.h, pid, int(n_steps), ap, 1 if auto_reset else 0, C.byref(io), C.byref(d)))
+            elif rule:
                 _lib.check(self.L.orlg_step_assign(self.h, pid, rule, int(n_steps), ap, 1 if auto_reset else 0, C.byref(io),
                                                    C.byref(d)))
             else:
@@ -330,6 +339,23 @@ class BatchedRMSAEnv(BatchedHandle):
             _check_buffer("out", out, shape, np.uint8)
         _lib.check(self.L.orlg_path_fit_levels(self.h, _ptr(out)))
         return out
+
+    def path_min_cuts(self, cuts_out=None, slots_out=None):
+        """The fewest-cuts window of every candidate path of every env's pending request (``orlg_path_min_cuts``):
+        ``(cuts, slots)``, both [B, k] int16 -- the number of the path's links on which the window leaves free slots on both of
+        its sides (it splits a free block in two there), and the window's start; ``-1`` and ``S`` where the path has no window.
+        What the ``_lib.CUT_POLICIES`` propose, as a feature and a mask for the path-only action space.  Reads state only;
+        ``cuts_out`` / ``slots_out`` as ``out`` in :meth:`action_masks`."""
+        shape = (self.batch_size, self.k_paths)
+        res = []
+        for name, buf in (("cuts_out", cuts_out), ("slots_out", slots_out)):
+            if buf is None:
+                buf = np.zeros(shape, np.int16)
+            else:
+                _check_buffer(name, buf, shape, np.int16)
+            res.append(buf)
+        _lib.check(self.L.orlg_path_min_cuts(self.h, _ptr(res[0]), _ptr(res[1])))
+        return res[0], res[1]
 
     def simple_matrix_observation(self, out=None):
         """SimpleMatrixObservation.observation() for every env: [B, 2N + E*S] uint8 (``rmsa_env.py:940-971``)."""

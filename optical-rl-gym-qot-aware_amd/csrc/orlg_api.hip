@@ -148,7 +148,8 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p, const OrlgGroupOv
     const bool traffic = !trace && p.rates != nullptr;   // per-environment rates: the instantiations that read them
     const bool cause = (p.out_mask & ORLG_OUT_CAUSE_BIT) != 0;   // the blocking cause: the plain kind with the classifier (the plan chose it)
     const bool assign = (p.out_mask & ORLG_OUT_ASSIGN_BIT) != 0;   // an assignment rule: the plain kind with the rules (the plan chose it)
-    const OrlgGroupKey key = {p.stats_level, c.kind == ORLG_GROUP_HBMQ, df, traffic, trace, cause, assign};
+    const bool cut = assign && p.assign == ORLG_ASSIGN_MIN_CUT;   // ... the fewest-cuts window: the CUT instantiations
+    const OrlgGroupKey key = {p.stats_level, c.kind == ORLG_GROUP_HBMQ, df, traffic, trace, cause, assign, cut};
     rmsa_kernel_t k = orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     if (df && !e->llog)
@@ -200,7 +201,7 @@ static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
     const bool df = !gn && p.mode == ORLG_MODE_STEP && orlg_defer_link_stats(p.stats_level, p.n_steps, p.out_mask, ov);   // as launch_rmsa_group
     const OrlgWaveKey key = {ff ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel_ff)
                                 : p.mode == ORLG_MODE_STEP ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel) : ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel),
-                             p.stats_level, df, gn, cause, assign};
+                             p.stats_level, df, gn, cause, assign, assign && p.assign == ORLG_ASSIGN_MIN_CUT};
     rmsa_kernel_t k = orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), e->lds_block_bytes)) return rc;
@@ -564,19 +565,23 @@ static int extra_out(orlg_env *e, ExtraOut *o, void *user, size_t bytes, int slo
     }
     return ORLG_OK;
 }
-// orlg_step, orlg_step_gn, orlg_step_diag and orlg_step_assign (gsnr, cause, counts: the outputs beyond orlg_step_io, nullptr = not
-// asked for; assign: ORLG_ASSIGN_*, 0 = the reference's first fit)
+// orlg_step, orlg_step_gn, orlg_step_diag, orlg_step_assign and orlg_step_min_cut (gsnr, cause, counts: the outputs beyond
+// orlg_step_io, nullptr = not asked for; assign: ORLG_ASSIGN_*, 0 = the reference's first fit, or the device's own
+// ORLG_ASSIGN_MIN_CUT, which only orlg_step_min_cut passes, with min_cut_entry -- `policy` may then be the device's ORLG_POLICY_MIN_CUT)
 static int rmsa_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
-                     const orlg_step_io *io, double *gsnr, uint8_t *cause = nullptr, int32_t *counts = nullptr, int32_t assign = ORLG_ASSIGN_FIRST) {
+                     const orlg_step_io *io, double *gsnr, uint8_t *cause = nullptr, int32_t *counts = nullptr, int32_t assign = ORLG_ASSIGN_FIRST,
+                     bool min_cut_entry = false) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     if (n_steps < 1) return fail(ORLG_ERR_INVALID, "n_steps must be >= 1");
-    if (policy < ORLG_POLICY_EXTERNAL || policy > ORLG_POLICY_SAP_FF_GN) return fail(ORLG_ERR_INVALID, "unknown policy %d", policy);
+    const bool cut_route = min_cut_entry && policy == ORLG_POLICY_MIN_CUT;
+    if (!cut_route && (policy < ORLG_POLICY_EXTERNAL || policy > ORLG_POLICY_SAP_FF_GN)) return fail(ORLG_ERR_INVALID, "unknown policy %d", policy);
     if (policy == ORLG_POLICY_SAP_FF_GN && !e->p.gn)
         return fail(ORLG_ERR_INVALID, "policy %d (sap_ff_gn) asks the GN-model admission check: the handle has no gn_gate", policy);
     // an assignment rule other than the reference's first fit: the policy is a route, the handle has no gate -- before anything is launched
-    if (assign < ORLG_ASSIGN_FIRST || assign >= ORLG_NUM_ASSIGN_RULES) return fail(ORLG_ERR_INVALID, "unknown assignment rule %d", assign);
+    // (the public rules; ORLG_ASSIGN_MIN_CUT comes from orlg_step_min_cut alone and is an unknown rule to every other caller)
+    if (assign < ORLG_ASSIGN_FIRST || assign >= (min_cut_entry ? ORLG_ASSIGN_MIN_CUT + 1 : ORLG_NUM_ASSIGN_RULES)) return fail(ORLG_ERR_INVALID, "unknown assignment rule %d", assign);
     if (assign != ORLG_ASSIGN_FIRST) {
-        if (policy != ORLG_POLICY_SP_FF && policy != ORLG_POLICY_SAP_FF && policy != ORLG_POLICY_LLP_FF && policy != ORLG_POLICY_PATH_FF_EXTERNAL)
+        if (!cut_route && policy != ORLG_POLICY_SP_FF && policy != ORLG_POLICY_SAP_FF && policy != ORLG_POLICY_LLP_FF && policy != ORLG_POLICY_PATH_FF_EXTERNAL)
             return fail(ORLG_ERR_INVALID, "assignment rule %d needs a route (sp_ff, sap_ff, llp_ff or path_ff_external): policy %d names its own slot or block", assign, policy);
         if (e->p.gn) return fail(ORLG_ERR_INVALID, "assignment rule %d on a handle with a gn_gate: the admission check knows the reference's first fit only", assign);
     }
@@ -665,6 +670,17 @@ int orlg_step_assign(orlg_env *e, int32_t policy, int32_t assign, int32_t n_step
                      const orlg_step_io *io, const struct orlg_step_diag *diag) {
     if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr, nullptr, nullptr, assign);
     return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, assign);
+}
+int orlg_step_min_cut(orlg_env *e, int32_t route, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
+                      const struct orlg_step_diag *diag) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (route != ORLG_POLICY_SP_FF && route != ORLG_POLICY_SAP_FF && route != ORLG_POLICY_LLP_FF && route != ORLG_POLICY_PATH_FF_EXTERNAL &&
+        route != ORLG_ROUTE_FEWEST_CUTS)
+        return fail(ORLG_ERR_INVALID, "the fewest-cuts window needs a route (sp_ff, sap_ff, llp_ff, path_ff_external or ORLG_ROUTE_FEWEST_CUTS): got %d", route);
+    if (e->p.gn) return fail(ORLG_ERR_INVALID, "the fewest-cuts window on a handle with a gn_gate: the admission check knows the reference's first fit only");
+    const int32_t policy = route == ORLG_ROUTE_FEWEST_CUTS ? (int32_t)ORLG_POLICY_MIN_CUT : route;
+    if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr, nullptr, nullptr, ORLG_ASSIGN_MIN_CUT, true);
+    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, ORLG_ASSIGN_MIN_CUT, true);
 }
 
 int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
@@ -949,6 +965,27 @@ int orlg_path_fit_levels(orlg_env *e, uint8_t *levels) {
     hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, reinterpret_cast<uint8_t *>(slots[0].dev));
     HIP_TRY(hipGetLastError());
     return collect_outputs(e, slots, 1);
+}
+
+int orlg_path_min_cuts(orlg_env *e, int16_t *cuts, int16_t *slots_out) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!cuts && !slots_out) return fail(ORLG_ERR_INVALID, "null argument: neither a cuts nor a slots buffer");
+    HIP_TRY(hipSetDevice(e->device));
+    const OrlgParams &p = e->p;
+    OutSlot slots[2] = {{cuts, (size_t)p.B * p.K * sizeof(int16_t)}, {slots_out, (size_t)p.B * p.K * sizeof(int16_t)}};
+    int rc = place_outputs(e, slots, 2);
+    if (rc) return rc;
+    orlg_min_cuts_kernel_t k = orlg_pick_min_cuts(e->W);
+    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
+    const int wpb = e->waves_per_block;
+    const size_t lds = (size_t)p.l_shared_bytes + (size_t)((p.NW * 8 + 15) & ~15) * wpb;   // as orlg_path_fit_levels
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int nblocks = (p.B + wpb - 1) / wpb;
+    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;
+    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, reinterpret_cast<int16_t *>(slots[0].dev),
+                       reinterpret_cast<int16_t *>(slots[1].dev));
+    HIP_TRY(hipGetLastError());
+    return collect_outputs(e, slots, 2);
 }
 
 int orlg_gn_action_masks(orlg_env *e, uint8_t *path_ff, double *path_ff_gsnr_db, uint8_t *deeprmsa, double *deeprmsa_gsnr_db) {

@@ -66,6 +66,11 @@ enum { ORLG_MODE_STEP = 0, ORLG_MODE_INIT = 1, ORLG_MODE_EPISODE_RESET = 2 };
 // device-side policy ids (== include/orlg.h ORLG_POLICY_*)
 enum { ORLG_POLICY_EXT = -1, ORLG_POLICY_SP = 0, ORLG_POLICY_SAP = 1, ORLG_POLICY_LLP = 2, ORLG_POLICY_DEEP_SP = 3,
        ORLG_POLICY_DEEP_SAP = 4, ORLG_POLICY_DEEP_EXT = 5, ORLG_POLICY_PATH_EXT = 6, ORLG_POLICY_SAP_GN = 7 };
+// device-side only (orlg_step_min_cut, orlg_cut.h; no public policy or rule has these values): the route "fewest cuts" -- of all k
+// paths the one whose MIN_CUT window has the fewest cuts (include/orlg.h ORLG_ROUTE_FEWEST_CUTS is mapped to it) -- and the rule
+// MIN_CUT as a value of OrlgParams::assign, behind the public ORLG_ASSIGN_* (ORLG_NUM_ASSIGN_RULES stays what it is)
+enum { ORLG_POLICY_MIN_CUT = 8 };
+enum { ORLG_ASSIGN_MIN_CUT = 5 };
 // per-step output slots (OrlgParams::outs)
 enum { ORLG_OUT_PATH = 0, ORLG_OUT_SLOT, ORLG_OUT_ACCEPTED, ORLG_OUT_DONE, ORLG_OUT_REWARD, ORLG_OUT_REQUEST,
        ORLG_OUT_ARRIVAL, ORLG_OUT_HOLDING, ORLG_OUT_COMPACT, ORLG_OUT_COMPACT_DIFF, ORLG_OUT_AVG_LINK_COMPACT,
@@ -154,7 +159,8 @@ struct OrlgParams {
     int32_t *o_cause_counts;
     // spectrum-assignment rule (include/orlg.h ORLG_ASSIGN_*, orlg_step_assign; orlg_assign.h), read by the ASSIGN instantiations of
     // the two step kernels only: `policy` is then the route.  0 = the reference's first fit; a launch with another rule has
-    // ORLG_OUT_ASSIGN_BIT in out_mask.  (At the struct's end, as the cause pointers)
+    // ORLG_OUT_ASSIGN_BIT in out_mask; ORLG_ASSIGN_MIN_CUT (above): the fewest-cuts window, orlg_cut.h, the CUT instantiations.
+    // (At the struct's end, as the cause pointers)
     int32_t assign;
 };
 // out_mask of a launch that asks for a cause output: not one of outs[], but a per-step output like them -- what looks at

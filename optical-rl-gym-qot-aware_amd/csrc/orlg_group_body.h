@@ -1,6 +1,6 @@
 // orlg_group_body.h -- the TEXT of orlg_rmsa_group_kernel's body (orlg_group_kernels.hip), from the first statement to the last.
 // Not a header to include at file scope: it is included INSIDE a function that has the kernel's template arguments (W, STATS,
-// HBMQ, DEFER, TRAFFIC, TRACE), the constants `LEAN`, `CAUSE` and `ASSIGN` and the parameters `p` in scope -- once in the kernel itself and once in
+// HBMQ, DEFER, TRAFFIC, TRACE), the constants `LEAN`, `CAUSE`, `ASSIGN` and `CUT` and the parameters `p` in scope -- once in the kernel itself and once in
 // orlg_rmsa_group_body, which gives the DEFER instantiations their second, lean body.  Why the text and not only the function:
 // a kernel whose body arrives through an inlined function compiles to slightly different code than one that holds the text
 // (other spill placement, a few dozen instructions either way), and the instantiations without a lean body are to stay,
@@ -14,6 +14,7 @@
     static_assert(!LEAN || DEFER, "the lean body belongs to the long launches");
     static_assert(!CAUSE || (!HBMQ && !DEFER), "the blocking cause belongs to the plain kind");
     static_assert(!ASSIGN || (!HBMQ && !DEFER), "the assignment rules belong to the plain kind");
+    static_assert(!CUT || ASSIGN, "the fewest-cuts window is an assignment rule");
     extern __shared__ __align__(16) unsigned char smem[];
     stage_tables(smem, p);
     const int lane = threadIdx.x & 63;
@@ -213,7 +214,34 @@
             const int kmax = (given || policy == ORLG_POLICY_SP) ? 1 : K;
             const int ps = gl / W, w = gl - ps * W;
             int found = 0x7fffffff, found_key = 0x7fffffff;
-            for (int p0 = 0; p0 < kmax; p0 += PP) {
+            // CUT: the fewest-cuts window (OrlgParams::assign == ORLG_ASSIGN_MIN_CUT, orlg_step_min_cut; orlg_cut.h) has a hop loop of
+            // its own, which counts per window start the links it would cut; the rules' loop below is compiled out, as this one is
+            // without CUT.  Its route "fewest cuts" (ORLG_POLICY_MIN_CUT) ranks the paths by their window's cuts as llp ranks them
+            // by free slots: row minima of (rank, path), the earlier pass wins a tie
+            [[maybe_unused]] const bool ranked = llp || policy == ORLG_POLICY_MIN_CUT;
+            for (int p0 = 0; CUT && p0 < kmax; p0 += PP) {
+                if (!ranked && ballot(act && a_ok && found == 0x7fffffff) == 0ull) break;
+                const int pp = p0 + ps;
+                const bool on = ps < PP && pp < kmax && a_ok;
+                int hops_pp, n;
+                u64 x;
+                const uint32_t sk = seg_max<W>(cut_word_key<W>(occ, tb.recs, base + path0 + pp, w, on, tb.nslots + req_br * ORLG_NSLOT_STRIDE, S,
+                                                               hops_pp, n, x));   // the path's key, on its first lane
+                const bool head = on && w == 0 && sk != 0u;
+                const int payload = head ? (((((path0 + pp) << 10) | cut_key_slot(sk)) << 14) | (n << 4) | hops_pp) : 0x7fffffff;
+                if (ranked) {
+                    const uint32_t fs = seg_add<W>((uint32_t)popc64(x));
+                    const uint32_t rank = llp ? 1023u - fs : (uint32_t)cut_key_cuts(sk);
+                    const int key = head ? (int)((rank << 6) | (uint32_t)pp) : 0x7fffffff;
+                    const int bk = row_min_i32(key);
+                    const int bp = row_min_i32(key == bk ? payload : 0x7fffffff);
+                    if (bk < found_key) { found_key = bk; found = bp; }
+                    continue;
+                }
+                const int best = row_min_i32(payload);
+                if (found == 0x7fffffff) found = best;
+            }
+            for (int p0 = 0; !CUT && p0 < kmax; p0 += PP) {
                 if (!llp && ballot(act && a_ok && found == 0x7fffffff) == 0ull) break;
                 const int pp = p0 + ps;
                 const bool on = ps < PP && pp < kmax && a_ok;

@@ -26,6 +26,7 @@
 #include "orlg_sections.h"
 #include "orlg_block_cause.h"  // window_level: the classifier of the CAUSE instantiations (group_fit_level below)
 #include "orlg_assign.h"       // assign_word_key: the assignment rules of the ASSIGN instantiations
+#include "orlg_cut.h"          // cut_word_key: the fewest-cuts window of the CUT instantiations
 
 #define ORLG_GL 16  // lanes per environment (one DPP row)
 #define ORLG_GE 4   // environments per wave
@@ -459,6 +460,7 @@ template <int W, int STATS, bool HBMQ, bool DEFER, bool TRAFFIC, bool TRACE, boo
 DEV void orlg_rmsa_group_body(const OrlgParams &p) {
     constexpr bool CAUSE = false;   // (the DEFER instantiations have no classifier: a cause launch runs the plain kind)
     constexpr bool ASSIGN = false;  // (... and no assignment rule but the reference's first fit)
+    constexpr bool CUT = false;
 #include "orlg_group_body.h"
 }
 
@@ -469,7 +471,10 @@ DEV void orlg_rmsa_group_body(const OrlgParams &p) {
 // TRAFFIC; the plain kind only (orlg_group_plan.h keeps such a launch on it)
 // ASSIGN: the launch runs an assignment rule other than the reference's first fit (include/orlg.h orlg_step_assign,
 // OrlgParams::assign; orlg_assign.h): the policy section is the rules' own.  A template argument and the plain kind only, as CAUSE
-template <int W, int STATS, bool HBMQ = false, bool DEFER = false, bool TRAFFIC = false, bool TRACE = false, bool CAUSE = false, bool ASSIGN = false>
+// CUT (with ASSIGN): the launch runs the fewest-cuts window (orlg_step_min_cut; orlg_cut.h): its hop loop stands in the rules' place.
+// A flag of its own so that the ASSIGN instantiations stay the code they were
+template <int W, int STATS, bool HBMQ = false, bool DEFER = false, bool TRAFFIC = false, bool TRACE = false, bool CAUSE = false, bool ASSIGN = false,
+          bool CUT = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3) / 4) void orlg_rmsa_group_kernel(const OrlgParams p) {
     if constexpr (DEFER) {
         if (p.g_lean) orlg_rmsa_group_body<W, STATS, HBMQ, DEFER, TRAFFIC, TRACE, true>(p);

@@ -156,7 +156,7 @@ struct OrlgHandle {
     OrlgScratch extra[ORLG_EXTRA_SLOTS];
     OrlgErrWord err = {nullptr, nullptr};   // sticky error word the kernels set on an overflow
     std::string overflow_message;    // what orlg_handle_sync_check reports then (the variant words it, with its capacities)
-    char last_kernel[128] = "";       // name and shape of the kernel behind the last step / reset launch
+    char last_kernel[160] = "";       // name and shape of the kernel behind the last step / reset launch
     OrlgTrafficState traffic;        // per-environment rates and groups (*_create_traffic)
     OrlgTraceState trace;            // request trace and its position (*_create_trace)
     OrlgHandle() = default;
@@ -180,7 +180,7 @@ int orlg_handle_resident(OrlgHandle *h, const void *kernel, int block, size_t ld
 void orlg_handle_note_launch(OrlgHandle *h, const char *name, int grid, int block, size_t lds, int chunks, const char *body);
 template <typename Key>
 static void orlg_handle_launched(OrlgHandle *h, const Key &key, int grid, int block, size_t lds, int chunks = 0, const char *body = nullptr) {
-    char name[64];
+    char name[96];   // (the longest: the group kernel's nine arguments, 67 characters)
     orlg_kernel_name(name, sizeof(name), h->W, key);
     orlg_handle_note_launch(h, name, grid, block, lds, chunks, body);
 }

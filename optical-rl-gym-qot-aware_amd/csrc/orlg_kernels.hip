@@ -36,6 +36,7 @@
 #include "orlg_rmsa_gn.h"      // rmsa_gn_gsnr: the GN-model admission check of the GN instantiations
 #include "orlg_block_cause.h"  // wave_fit_levels: the classifier of the CAUSE instantiations
 #include "orlg_assign.h"       // wave_assign: the assignment rules of the ASSIGN instantiations
+#include "orlg_cut.h"          // wave_cut_assign: the fewest-cuts window of the CUT instantiations
 #include "orlg_sections.h"
 
 // ---------------------------------------------------------------------------------------- the step kernel
@@ -54,6 +55,9 @@
 // ASSIGN: the launch runs an assignment rule other than the reference's first fit (include/orlg.h orlg_step_assign,
 // OrlgParams::assign): the policy is read as a route (sp, sap, llp, or the agent's path) and wave_assign (orlg_assign.h) is the
 // whole policy section; it proposes free windows only.  No other instantiation holds any of it.
+// CUT (with ASSIGN): the launch runs the fewest-cuts window (orlg_step_min_cut, OrlgParams::assign == ORLG_ASSIGN_MIN_CUT):
+// wave_cut_assign (orlg_cut.h) stands where wave_assign stands.  A flag of its own so that the ASSIGN instantiations stay the code
+// they were.
 template <bool GN>
 struct SapRetry {
     int from = 0, path = 0, slot = 0;
@@ -65,7 +69,7 @@ struct SapRetry<false> {
     SapRetry() = default;
 };
 
-template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false>
+template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false, bool CUT = false>
 DEV void rmsa_body(const OrlgParams &p) {
     extern __shared__ __align__(16) unsigned char smem[];
 #ifdef ORLG_SHAPE_ASSUME
@@ -235,7 +239,10 @@ DEV void rmsa_body(const OrlgParams &p) {
             if constexpr (ASSIGN) {
                 KernargParams kq = kernarg_params();
                 const int given = policy == ORLG_POLICY_PATH_EXT ? uni(kq->actions[env]) : 0;
-                const int got = wave_assign<W>(wv.occ, tb, base, K, S, req_br, lane, policy, kq->assign, given);
+                // (CUT: the fewest-cuts window, with a hop loop of its own, in the rules' place)
+                int got;
+                if constexpr (CUT) got = wave_cut_assign<W>(wv.occ, tb, base, K, S, req_br, lane, policy, given);
+                else got = wave_assign<W>(wv.occ, tb, base, K, S, req_br, lane, policy, kq->assign, given);
                 if (got >= 0) { a_path = got >> 10; a_slot = got & 1023; }
             } else if (FF) {
                 const int kmax = policy == ORLG_POLICY_SP ? 1 : K;
@@ -649,9 +656,10 @@ DEV void rmsa_body(const OrlgParams &p) {
     SEC_FLUSH;
 }
 
-template <int W, int STATS, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false>
+template <int W, int STATS, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false, bool CUT = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel(const OrlgParams p) {
-    rmsa_body<W, STATS, true, false, DEFER, GN, CAUSE, ASSIGN>(p);
+    static_assert(!CUT || ASSIGN, "the fewest-cuts window is an assignment rule");
+    rmsa_body<W, STATS, true, false, DEFER, GN, CAUSE, ASSIGN, CUT>(p);
 }
 template <int W, int STATS, bool DEFER = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel_ff(const OrlgParams p) {

@@ -619,6 +619,57 @@ def assignment_heuristic(route, rule):
     return heuristic
 
 
+def _min_cut_slot(rows, n):
+    """The fewest-cuts window of a request of ``n`` slots on a path whose links have the availability ``rows`` [hops, S]
+    (``topology.graph["available_slots"]`` rows): ``(cuts, start)`` or None when the path has no window.  A window is a start
+    ``s`` in ``0 .. S - n`` inclusive with ``[s, s + n)`` free on every link; its cuts are the links with slot ``s - 1`` and slot
+    ``s + n`` both free (slots -1 and S are not); fewest cuts, then lowest start (include/orlg.h ``orlg_step_min_cut``)."""
+    rows = np.asarray(rows).astype(bool)
+    S = rows.shape[1]
+    both = rows.all(axis=0)
+    best = None
+    for s in range(0, S - n + 1):
+        if not both[s:s + n].all():
+            continue
+        cuts = sum(1 for r in rows if s > 0 and r[s - 1] and s + n < S and r[s + n])
+        if best is None or cuts < best[0]:
+            best = (cuts, s)
+    return best
+
+
+def min_cut_heuristic(route):
+    """A heuristic ``f(env) -> [path, slot]`` for ``RMSA-v0`` in the drop-in callback shape of
+    ``shortest_available_path_first_fit``: the window with the fewest cuts on route ``"sp"`` (path 0), ``"sap"`` (the first path
+    that has a window), ``"llp"`` (of the paths that have a window the one with the most free slots, strict ``>``) or
+    ``"min_cut"`` (of all paths the one whose fewest-cuts window has the fewest cuts, ties to the lowest path).  Not in the
+    reference for this environment (its ``calculate_r_cut`` belongs to the QoT-aware one); what the device policies
+    ``sp_mc`` / ``sap_mc`` / ``llp_mc`` / ``min_cut`` propose, written on what the view exposes: the rows of
+    ``topology.graph["available_slots"]``, the link indices along a path's ``node_list`` and ``get_number_slots``."""
+    if route not in ("sp", "sap", "llp", "min_cut"):
+        raise ValueError(f"route {route!r}: expected 'sp', 'sap', 'llp' or 'min_cut'")
+
+    def heuristic(env):
+        S, k = env.topology.graph["num_spectrum_resources"], env.topology.graph["k_paths"]
+        paths = env.k_shortest_paths[env.current_service.source, env.current_service.destination]
+        avail = env.topology.graph["available_slots"]
+        best, action = None, [k, S]
+        for idp, path in enumerate(paths[:1] if route == "sp" else paths):
+            nodes = path.node_list
+            rows = np.asarray([avail[env.topology[nodes[i]][nodes[i + 1]]["index"]] for i in range(len(nodes) - 1)])
+            got = _min_cut_slot(rows, env.get_number_slots(path))
+            if got is None:
+                continue
+            if route in ("sp", "sap"):
+                return [idp, got[1]]
+            rank = int(rows.all(axis=0).sum()) if route == "llp" else -got[0]
+            if best is None or rank > best:
+                best, action = rank, [idp, got[1]]
+        return action
+
+    heuristic.__name__ = f"{route}_min_cut"
+    return heuristic
+
+
 def least_loaded_path_first_fit(env: RMSAEnv) -> Tuple[int, int]:
     """LLP-FF (``rmsa_env.py:916-937``): among paths with a first fit, the one with most free slots (strict >)."""
     S, k = env.topology.graph["num_spectrum_resources"], env.topology.graph["k_paths"]
