@@ -144,7 +144,8 @@
         group_link_stats<W, true, false, true, 2>(lane, occ, nullptr, lint, tb, S, E, nullptr, E, 0.0, sum_span, sum_gaps, comp_cur,
                                                   0, 0.0, g_thr, g_comp, g_lu, nullptr, nullptr, lsum);
     // release queue: a time-sorted ring in LDS (OrlgParams::qtime) -- q_n entries from slot q_head on; the row keeps the time of
-    // its head in a register, so that a step without a due release touches no queue memory
+    // its head in a register, so that a step without a due release touches no queue memory.  q_head is the head's slot in LDS: it
+    // starts a ticket where the state has it and falls behind by one slot per insert from the head's side (queue insert)
     int q_head = gs->q_head, q_n = n_running < Q ? n_running : Q;   // (n_running also counts services an overflow lost)
     // only the live part of the ring moves between HBM and LDS (a launch of one step would otherwise spend most of its
     // traffic on empty slots); LDS slots outside it are never read
@@ -397,32 +398,56 @@
                                                                           &need_replay, lsum, a_slot, n);
         SEC(5);  // queue insert
         {
-            // ---- _add_release (optical_network_env.py:178-189): the entries that are released later move up one slot (from the
-            // top chunk of 16 down: a chunk's reads precede its writes), the new one takes the slot that opens -- each row its own
+            // ---- _add_release (optical_network_env.py:178-189): the new entry goes behind every entry that is not later, and the
+            // ring makes room from the nearer end -- each row its own.  A row whose entry is not earlier than its middle one scans
+            // from the top: chunks of 16 entries anchored at the last one (entries q_n - 16 .. q_n - 1, then sixteen lower each
+            // time; the partial chunk is the one at the head), the later entries move up one slot.  A row whose entry is earlier
+            // scans from the head upward: the entries that are not later move DOWN one slot, and so does the head (q_head is the
+            // head in LDS; the state that leaves has the conventional one, see the state store).  Either scan runs until it has
+            // found the place: the side is a guess at the shorter way, nothing depends on it.  A chunk's reads precede its
+            // writes.  The ring in HBM (one-step launches) keeps its head where the other kernel and the oracle have it: from
+            // the top only
             const double rel = req_arrival + req_holding;
             bool ins = accepted && (act || !HBMQ);   // (a row past the batch's end must not touch the last environment's ring in HBM)
             if (ins && q_n >= Q) { q_overflow = 1; ins = false; }
-            bool found = !ins;
-            int r = 0, j0 = (q_n - 1) & ~(ORLG_GL - 1);   // q_n == 0: j0 < 0, nothing to move
-            while (ballot(!found && j0 >= 0) != 0ull) {
-                const bool scan = !found && j0 >= 0;
-                const int j = j0 + gl;
-                const bool valid = scan && j < q_n;
+            bool down = false;
+            if constexpr (!HBMQ) {
+                if (ins && q_n > 0) {
+                    int pm = q_head + (q_n >> 1);
+                    pm -= pm >= Q ? Q : 0;
+                    down = rel < qtime[pm];
+                }
+            }
+            // The lanes count from the near end: lane gl of a chunk looks at the gl-th entry of those not looked at yet, from the
+            // top downward or from the head upward.  Sorted: the entries of a chunk that move are its near end
+            bool found = !ins || q_n == 0;
+            int m = q_n;       // how many entries move: all of them, unless the scan finds one that stays
+            int left = q_n;    // entries not looked at yet
+            int j = down ? gl : q_n - 1 - gl;
+            int hd = down ? q_head - 1 : q_head + 1;   // where the head's entry goes if it moves: down, the new head
+            hd = hd < 0 ? Q - 1 : (hd == Q ? 0 : hd);
+            while (ballot(!found) != 0ull) {
+                const bool scan = !found;
+                const bool valid = scan && gl < left;
                 int pos = q_head + j;
                 pos -= pos >= Q ? Q : 0;
                 double tq = 0.0;
                 uint32_t dq = 0u;
                 if (valid) { tq = qtime[pos]; dq = qdesc[pos]; }
-                const bool later = valid && tq > rel;
-                const int pos1 = pos + 1 == Q ? 0 : pos + 1;
-                if (later) { qtime[pos1] = tq; qdesc[pos1] = dq; }
-                const uint32_t le = row_ballot(valid && !later, lane);   // sorted: a prefix of the chunk
+                const bool moves = valid && (tq > rel) != down;   // up: the later ones; down: the ones that are not later
+                int pos1 = hd + j;
+                pos1 -= pos1 >= Q ? Q : 0;
+                if (moves) { qtime[pos1] = tq; qdesc[pos1] = dq; }
+                const uint32_t stay = row_ballot(valid && !moves, lane);
                 if (scan) {
-                    if (le) { r = j0 + __builtin_popcount(le); found = true; }
-                    else j0 -= ORLG_GL;
+                    if (stay) { m = q_n - left + __builtin_ctz(stay); found = true; }
+                    else if (left <= ORLG_GL) found = true;
+                    else { left -= ORLG_GL; j += down ? ORLG_GL : -ORLG_GL; }
                 }
             }
             if (ins) {
+                const int r = down ? m : q_n - m;   // how many entries stay below the new one
+                if (down) q_head = hd;
                 int pr = q_head + r;
                 pr -= pr >= Q ? Q : 0;
                 const uint32_t desc = (uint32_t)gid | ((uint32_t)a_slot << 14) | ((uint32_t)req_br << 24);
@@ -554,7 +579,8 @@
                 const int hops2 = rec2->hops;
                 const int n2 = tb.nslots[bri2 * ORLG_NSLOT_STRIDE + rec2->se];
                 if (rel_now) {
-                    if (gl == 0) { qtime[q_head] = INF; qdesc[q_head] = 0u; }
+                    // (the ring in LDS leaves a popped slot as it is: the state store writes the (+inf, 0) of the slots that left)
+                    if (HBMQ && gl == 0) { qtime[q_head] = INF; qdesc[q_head] = 0u; }
                     q_head = q_head + 1 == Q ? 0 : q_head + 1;
                     q_pops += 1;
                     q_n -= 1;
@@ -640,18 +666,31 @@
         if (act && gl < ORLG_NUM_CAUSES && cause_cnt && p.o_cause_counts) atomicAdd(p.o_cause_counts + (size_t)env * ORLG_NUM_CAUSES + gl, cause_cnt);
     }
     if (act) {
+        int q_headc = q_head;   // the head the state has
         if constexpr (!HBMQ) {
-            // the ring from where its head was at the start (slots popped since then hold (+inf, 0)) to its last entry; the
-            // number of pops, not the head's distance modulo Q, says how far that is: a head that went round the ring has
-            // emptied slots beyond (q_head - q_head0) % Q + q_n whose old entries HBM would otherwise keep
+            // the ring from where its head was at the start to its last entry: (+inf, 0) in the slots popped since then, the live
+            // entries behind them; the number of pops, not the head's distance modulo Q, says how far that is: a head that went
+            // round the ring has emptied slots beyond (q_head - q_head0) % Q + q_n whose old entries HBM would otherwise keep.
+            // HBM has the CONVENTIONAL ring, whose head moves by pops only (q_head0 + q_pops): the ring in LDS is the same
+            // sorted sequence, rotated down by the ticket's downward inserts -- entry i of it goes from q_head + i to
+            // q_headc + i, and a slot of the span that holds no entry is one that was popped
             double *gqt = p.qtime + (size_t)env * Q;
             uint32_t *gqd = p.qdesc + (size_t)env * Q;
+            q_headc = q_head0 + (int)((uint32_t)q_pops % (uint32_t)Q);
+            q_headc -= q_headc >= Q ? Q : 0;
             int span = q_pops + q_n;
             span = span > Q ? Q : span;
             for (int j = gl; j < span; j += ORLG_GL) {
                 int pos = q_head0 + j;
                 pos -= pos >= Q ? Q : 0;
-                gqt[pos] = qtime[pos]; gqd[pos] = qdesc[pos];
+                int i = pos - q_headc;
+                i += i < 0 ? Q : 0;
+                int src = q_head + i;
+                src -= src >= Q ? Q : 0;
+                double tq = INF;
+                uint32_t dq = 0u;
+                if (i < q_n) { tq = qtime[src]; dq = qdesc[src]; }
+                gqt[pos] = tq; gqd[pos] = dq;
             }
         }
         OrlgEnvScalars *go = p.scal + env;
@@ -666,7 +705,7 @@
             go->req_src = req_src; go->req_dst = req_dst; go->req_br = req_br; go->req_sid = req_sid;
             go->mt_idx = mt_idx; go->new_service = new_service; go->q_overflow = q_overflow;
             go->ring_pos = ring_pos; go->ring_cnt = ring_cnt;
-            go->sum_span = sum_span; go->sum_gaps = sum_gaps; go->q_head = q_head;
+            go->sum_span = sum_span; go->sum_gaps = sum_gaps; go->q_head = q_headc;
             if (q_overflow) *p.err_flag = 1;   // reported by the next entry point that waits for the stream
         }
     }
