@@ -572,33 +572,79 @@
                 const bool rel_now = act && next_rel <= current_time;
                 if (ballot(rel_now) == 0ull) break;
                 SEC(10);  // release apply
-                // ---- _release_path (rmsa_env.py:515-535)
-                const uint32_t d = rel_now ? next_desc : 0u;   // (the head's descriptor came with its time)
-                const int gid2 = (int)(d & 0x3fff), s0 = (int)((d >> 14) & 0x3ff), bri2 = (int)(d >> 24);
-                const OrlgPathRec *rec2 = tb.recs + gid2;
-                const int hops2 = rec2->hops;
-                const int n2 = tb.nslots[bri2 * ORLG_NSLOT_STRIDE + rec2->se];
-                if (rel_now) {
-                    // (the ring in LDS leaves a popped slot as it is: the state store writes the (+inf, 0) of the slots that left)
-                    if (HBMQ && gl == 0) { qtime[q_head] = INF; qdesc[q_head] = 0u; }
-                    q_head = q_head + 1 == Q ? 0 : q_head + 1;
-                    q_pops += 1;
-                    q_n -= 1;
-                    n_running -= 1;
-                    sum_bitrate_running -= tb.bit_rates[bri2];
-                    sum_sh -= n2 * hops2;
-                    released = true;
-                }
                 if constexpr (DEFER) {
-                    // the window and its links' statistics in one pass, lane = hop (group_release_links; ends with a wave_sync)
-                    if (rel_now) {   // the next entry
-                        next_rel = q_n > 0 ? qtime[q_head] : INF;
+                    // ---- _release_path (rmsa_env.py:515-535), for the head A and -- in the same pass -- for the entry B behind it
+                    // where B is due as well, both paths have at most 8 hops and they share no link: the two releases then touch
+                    // disjoint occupancy words, summaries, span-cache entries and link logs at one `current_time`, and what joins
+                    // them are integer sums, so the order between them leaves no trace.  Lanes 0..7 of the row take A's hops, lanes
+                    // 8..15 B's.  Anything else -- a shared link, a longer path, a third due service -- waits for the next pass.
+                    const bool up = gl >= 8;
+                    // (slots outside the ring's live part were never written: B is read only where it exists)
+                    double b_rel = INF;
+                    uint32_t b_desc = 0u;
+                    if (rel_now && q_n >= 2) {
+                        const int qb = q_head + 1 == Q ? 0 : q_head + 1;
+                        b_rel = qtime[qb]; b_desc = qdesc[qb];
+                    }
+                    const bool b_due = b_rel <= current_time;
+                    // the lane's service: its descriptor, path record, window and hop count
+                    const bool mine = up ? b_due : rel_now;
+                    const uint32_t d_a = rel_now ? next_desc : 0u;   // (the head's descriptor came with its time)
+                    const uint32_t d = up ? b_desc : d_a;            // (a B that is not due is a real entry: `mine` keeps its lanes off)
+                    const int gid2 = (int)(d & 0x3fff), s0 = (int)((d >> 14) & 0x3ff), bri2 = (int)(d >> 24);
+                    const OrlgPathRec *rec2 = tb.recs + gid2;
+                    const int hops2 = mine ? (int)rec2->hops : 0;
+                    const int n2 = tb.nslots[bri2 * ORLG_NSLOT_STRIDE + rec2->se];
+                    const int br2 = mine ? tb.bit_rates[bri2] : 0;
+                    const int hop = gl & 7;
+                    // the links of each half as bits (link mod 64): exact up to 64 links, beyond them a false conflict costs one
+                    // pass and nothing else
+                    const u64 lbits = half_row_or_u64(hop < hops2 ? 1ull << (rec2->link[hop] & 63) : 0ull);
+                    const u64 obits = ((u64)(uint32_t)row_swap8_i32((int)(uint32_t)(lbits >> 32)) << 32) | (uint32_t)row_swap8_i32((int)(uint32_t)lbits);
+                    const int hops_o = row_swap8_i32(hops2), n_o = row_swap8_i32(n2), br_o = row_swap8_i32(br2);   // the other half's
+                    const bool pair = b_due && hops2 <= 8 && hops_o <= 8 && (lbits & obits) == 0ull;
+                    // A alone: the whole row is A's, as before (lanes 8..15 matter to a path of more than 8 hops only)
+                    const bool a_up = up && !pair;
+                    const int hops_a = up ? hops_o : hops2, n_a = up ? n_o : n2, br_a = up ? br_o : br2;
+                    const int hops_b = up ? hops2 : hops_o, n_b = up ? n2 : n_o, br_b = up ? br2 : br_o;
+                    if (rel_now) {
+                        // (the ring in LDS leaves a popped slot as it is: the state store writes the (+inf, 0) of the slots that left)
+                        const int pops = pair ? 2 : 1;
+                        q_head += pops;
+                        q_head -= q_head >= Q ? Q : 0;
+                        q_pops += pops;
+                        q_n -= pops;
+                        n_running -= pops;
+                        sum_bitrate_running -= br_a + (pair ? br_b : 0);
+                        sum_sh -= n_a * hops_a + (pair ? n_b * hops_b : 0);
+                        released = true;
+                        next_rel = q_n > 0 ? qtime[q_head] : INF;   // the next entry
                         next_desc = q_n > 0 ? qdesc[q_head] : 0u;
                     }
-                    group_release_links<W>(lane, occ, lsum, lint, S, rec2->link, rel_now ? hops2 : 0, s0, n2, current_time, sum_span,
-                                           sum_gaps, llog, need_replay);
+                    // the window and its links' statistics in one pass, lane = hop (group_release_links; ends with a wave_sync)
+                    const uint8_t *links2 = a_up ? (tb.recs + (int)(d_a & 0x3fff))->link : rec2->link;
+                    group_release_links<W>(lane, occ, lsum, lint, S, links2, pair ? hop : gl, a_up ? hops_a : hops2,
+                                           a_up ? (int)((d_a >> 14) & 0x3ff) : s0, a_up ? n_a : n2, current_time, sum_span, sum_gaps, llog,
+                                           need_replay);
                     SEC(11);  // statistics at release: the log replays only
                 } else {
+                    // ---- _release_path (rmsa_env.py:515-535)
+                    const uint32_t d = rel_now ? next_desc : 0u;   // (the head's descriptor came with its time)
+                    const int gid2 = (int)(d & 0x3fff), s0 = (int)((d >> 14) & 0x3ff), bri2 = (int)(d >> 24);
+                    const OrlgPathRec *rec2 = tb.recs + gid2;
+                    const int hops2 = rec2->hops;
+                    const int n2 = tb.nslots[bri2 * ORLG_NSLOT_STRIDE + rec2->se];
+                    if (rel_now) {
+                        // (the ring in LDS leaves a popped slot as it is: the state store writes the (+inf, 0) of the slots that left)
+                        if (HBMQ && gl == 0) { qtime[q_head] = INF; qdesc[q_head] = 0u; }
+                        q_head = q_head + 1 == Q ? 0 : q_head + 1;
+                        q_pops += 1;
+                        q_n -= 1;
+                        n_running -= 1;
+                        sum_bitrate_running -= tb.bit_rates[bri2];
+                        sum_sh -= n2 * hops2;
+                        released = true;
+                    }
                     group_apply_window<W>(lane, occ, rec2->link, rel_now ? hops2 : 0, s0, n2, true);   // (ends with a wave_sync)
                     if (rel_now) {   // the next entry
                         next_rel = q_n > 0 ? qtime[q_head] : INF;

@@ -32,6 +32,16 @@
 #define ORLG_GE 4   // environments per wave
 
 DEV int row_add_i32(int v) { v += dpp_xor1(v); v += dpp_xor2(v); v += dpp_half_mirror(v); v += dpp_row_mirror(v); return v; }
+// the value of the lane eight places away in the row (row_ror:8): a row's two halves trade places
+DEV int row_swap8_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false); }
+// OR over the eight lanes of a half row, on every lane of it
+DEV u64 half_row_or_u64(u64 v) {
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+    lo |= (uint32_t)dpp_xor1((int)lo); hi |= (uint32_t)dpp_xor1((int)hi);
+    lo |= (uint32_t)dpp_xor2((int)lo); hi |= (uint32_t)dpp_xor2((int)hi);
+    lo |= (uint32_t)dpp_half_mirror((int)lo); hi |= (uint32_t)dpp_half_mirror((int)hi);
+    return ((u64)hi << 32) | lo;
+}
 DEV int row_min_i32(int v) {
     int o = dpp_xor1(v); v = o < v ? o : v;
     o = dpp_xor2(v); v = o < v ? o : v;
@@ -262,14 +272,16 @@ DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, 
 // the words next to and under the window at once (independent LDS reads), ORs the window into the one or two words it covers,
 // looks further out only where a bordering free run reaches a word's end, then logs the update and refreshes the span cache
 // exactly as group_link_stats would (the same values, so the same bits).
+// The lane's hop is its own: hop `hop` of a path of `hops` (none: hops = 0), with that path's window.  A row that releases one
+// service has hop = the lane's place in the row; a row that releases two link-disjoint services at once (orlg_group_body.h) gives
+// its lower eight lanes the first one's hops and its upper eight the second one's, and the row sums below cover both.
 template <int W>
-DEV void group_release_links(const int lane, u64 *occ, u64 *lsum, int32_t *lint, int S, const uint8_t *links, int hops, int s, int n,
-                             double now, int &sum_span, int &sum_gaps, uint4 *llog, bool &need_replay) {
+DEV void group_release_links(const int lane, u64 *occ, u64 *lsum, int32_t *lint, int S, const uint8_t *links, int hop, int hops, int s,
+                             int n, double now, int &sum_span, int &sum_gaps, uint4 *llog, bool &need_replay) {
     static_assert(ORLG_MAX_HOPS <= ORLG_GL, "one lane per hop");
-    const int gl = lane & 15;
     int dspan = 0, dgaps = 0;
-    if (gl < hops) {
-        const int link = (int)links[gl];
+    if (hop < hops) {
+        const int link = (int)links[hop];
         u64 *lw = occ + __mul24(link, W);
         const int e = s + n;
         // the words that hold slot s - 1, slot s + n, and the window's first / last slot: independent reads (coinciding ones too)
