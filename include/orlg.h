@@ -310,6 +310,36 @@ int orlg_step_min_cut(orlg_env *env, int32_t route, int32_t n_steps, const int32
  * an agent's feature and mask for the path-only action space.  Buffers as orlg_action_masks. */
 int orlg_path_min_cuts(orlg_env *env, int16_t *cuts, int16_t *slots);
 
+/* ---- most-used assignment and the route that takes the best window over all candidate paths (not in the reference).
+ * With A, n, BLOCK and WINDOW as above (a window start s lies in 0 .. S - n inclusive):
+ *     U[t]        = the number of links of the topology (all E of them, not only a path's) on which slot t is occupied, t in
+ *                   0 .. S - 1; 0 .. E, E <= 255
+ *     usage(p, s) = U[s] + .. + U[s + n - 1]; 0 .. 255 * 512
+ * The rule MOST_USED takes the window with the largest usage, ties to the lowest start.  The route BEST_WINDOW under a rule: every
+ * path that has a window proposes its rule window; the proposal that ranks best by the rule's own order wins, ties to the lowest
+ * path index -- FIRST_FULL: lower start; LAST: higher start; BEST: shorter block, then lower start; EXACT: a block of exactly n
+ * before any other, then lower start; MOST_USED: higher usage, then lower start (n differs per path: the proposals are compared as
+ * they are).  No path with a window: the rejection (k, S).  Integer-exact; U is recomputed from the occupancy a step meets and is
+ * not part of the saved state.  Outside the enums above on purpose: no other entry point accepts these two values. */
+#define ORLG_RULE_MOST_USED 100
+#define ORLG_ROUTE_BEST_WINDOW 101
+/* orlg_step_diag under a route and a rule.  `route`: ORLG_POLICY_SP_FF, ORLG_POLICY_SAP_FF, ORLG_POLICY_LLP_FF,
+ * ORLG_POLICY_PATH_FF_EXTERNAL (actions [B] name the path) -- read as orlg_step_assign reads them -- or ORLG_ROUTE_BEST_WINDOW.
+ * `rule`: ORLG_ASSIGN_FIRST_FULL, ORLG_ASSIGN_LAST, ORLG_ASSIGN_BEST, ORLG_ASSIGN_EXACT or ORLG_RULE_MOST_USED.  A pair that
+ * orlg_step_assign serves (one of its routes, one of its rules) IS orlg_step_assign and launches what that launches; every other
+ * pair runs the USAGE instantiation of the handle's step kernel (orlg_rmsa_kernel<.., ASSIGN, false, USAGE> /
+ * orlg_rmsa_group_kernel<.., ASSIGN, false, USAGE>, the plain kind of either; orlg_usage.h).  ORLG_ERR_INVALID, before anything is
+ * launched: a null handle, any other route or rule (ORLG_ASSIGN_FIRST included), a handle with a gn_gate.  diag may be NULL;
+ * block_cause and cause_counts as under orlg_step_assign (sap, llp and BEST_WINDOW refuse with a cause <= ORLG_CAUSE_ALIGNMENT only). */
+int orlg_step_window(orlg_env *env, int32_t route, int32_t rule, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
+                     const orlg_step_io *io, const struct orlg_step_diag *diag);
+/* U of every environment: usage [B][S] uint8.  Reads state and writes only `usage`.  Buffer as orlg_action_masks. */
+int orlg_slot_usage(orlg_env *env, uint8_t *usage);
+/* The MOST_USED window of every candidate path of every pending request: usage [B][k] int32 (its usage, -1 = the path has no
+ * window), slots [B][k] int16 (its start, S = no window).  Either may be NULL, not both.  Reads state and writes only its
+ * outputs.  Buffers as orlg_action_masks. */
+int orlg_path_most_used(orlg_env *env, int32_t *usage, int16_t *slots);
+
 /* The fit level (ORLG_FIT_*) of every candidate path of every pending request: levels [B][k] uint8.  Reads state and writes
  * only `levels`; looks at windows only on every handle (it does not know a GN-model admission check).  levels == 4 is the
  * path_ff bit of orlg_action_masks, levels >= 3 is "any bit in its slots mask".  Buffer as orlg_action_masks. */

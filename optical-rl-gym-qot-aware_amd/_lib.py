@@ -30,6 +30,16 @@ ASSIGN_POLICIES.update({f"path_{suffix}_external": (POLICIES["path_ff_external"]
 ROUTE_FEWEST_CUTS = 100
 CUT_POLICIES = {"sp_mc": POLICIES["sp_ff"], "sap_mc": POLICIES["sap_ff"], "llp_mc": POLICIES["llp_ff"], "min_cut": ROUTE_FEWEST_CUTS,
                 "path_mc_external": POLICIES["path_ff_external"]}
+# include/orlg.h orlg_step_window: the rule MOST_USED (the window whose slots are occupied on the most links of the whole network)
+# and the route BEST_WINDOW (of all k paths the one whose rule window ranks best by the rule's own order); DESIGN 2.25, not in the
+# reference.  policy name -> (route, rule) as orlg_step_window takes them.  A table of its own, as CUT_POLICIES
+RULE_MOST_USED = 100
+ROUTE_BEST_WINDOW = 101
+WINDOW_POLICIES = {"sp_mu": (POLICIES["sp_ff"], RULE_MOST_USED), "sap_mu": (POLICIES["sap_ff"], RULE_MOST_USED),
+                   "llp_mu": (POLICIES["llp_ff"], RULE_MOST_USED), "path_mu_external": (POLICIES["path_ff_external"], RULE_MOST_USED),
+                   "any_ff_full": (ROUTE_BEST_WINDOW, ASSIGN_RULES.index("first_full")),
+                   "any_lf": (ROUTE_BEST_WINDOW, ASSIGN_RULES.index("last")), "any_bf": (ROUTE_BEST_WINDOW, ASSIGN_RULES.index("best")),
+                   "any_ef": (ROUTE_BEST_WINDOW, ASSIGN_RULES.index("exact")), "any_mu": (ROUTE_BEST_WINDOW, RULE_MOST_USED)}
 
 
 def policy_ids(policy):
@@ -179,7 +189,11 @@ def _prototypes():
               "orlg_step_assign": (None, [vp, i32, i32, i32, vp, i32, P(StepIO), P(StepDiag)]),
               # the window with the fewest cuts: the step under it, and every candidate path's such window
               "orlg_step_min_cut": (None, [vp, i32, i32, vp, i32, P(StepIO), P(StepDiag)]),
-              "orlg_path_min_cuts": (None, [vp, vp, vp])})
+              "orlg_path_min_cuts": (None, [vp, vp, vp]),
+              # most-used windows and the best window over all paths: the step, the slot usage, every path's most-used window
+              "orlg_step_window": (None, [vp, i32, i32, i32, vp, i32, P(StepIO), P(StepDiag)]),
+              "orlg_slot_usage": (None, [vp, vp]),
+              "orlg_path_most_used": (None, [vp, vp, vp])})
     # QoT-aware only
     t.update({"orlg_phy_step": (None, [vp, i32, i32, vp, vp, i32, P(PhyStepIO)]), "orlg_phy_node_vectors": (None, [vp]),
               "orlg_phy_get_episode_stats": (None, [vp, vp]), "orlg_phy_channel_masks": (None, [vp, vp]),

@@ -117,9 +117,17 @@ class BatchedRMSAEnv(BatchedHandle):
         names of ``_lib.CUT_POLICIES`` -- ``sp_mc`` / ``sap_mc`` / ``llp_mc`` (the routes above; on the path the window that
         splits a free block in two on the fewest links, ties to the lowest start), ``min_cut`` (of all k paths the one whose such
         window has the fewest cuts, ties to the lowest path) and ``path_mc_external`` (``actions`` [B] names the path).  They run
-        where the names above run, with the same exception; :meth:`path_min_cuts` is the matching query."""
+        where the names above run, with the same exception; :meth:`path_min_cuts` is the matching query.
+
+        Most-used windows and the best window over all paths (``orlg_step_window``; not in the reference): the names
+        of ``_lib.WINDOW_POLICIES`` -- ``sp_mu`` / ``sap_mu`` / ``llp_mu`` (the routes above; on the path the window whose slots
+        are occupied on the most links of the whole network, ties to the lowest start), ``path_mu_external`` (``actions`` [B]
+        names the path) and ``any_ff_full`` / ``any_lf`` / ``any_bf`` / ``any_ef`` / ``any_mu`` (every path proposes its rule
+        window; the proposal that ranks best by the rule's own order wins, ties to the lowest path).  They run where the names
+        above run, with the same exception; :meth:`slot_usage` and :meth:`path_most_used` are the matching queries."""
         cut = policy in _lib.CUT_POLICIES
-        pid, rule = (_lib.CUT_POLICIES[policy], 0) if cut else _lib.policy_ids(policy)
+        window = policy in _lib.WINDOW_POLICIES
+        pid, rule = (_lib.CUT_POLICIES[policy], 0) if cut else _lib.WINDOW_POLICIES[policy] if window else _lib.policy_ids(policy)
         if (rule or cut) and self.gn_gate is not None:
             raise ValueError(f"policy {policy!r}: an assignment rule other than the reference's first fit does not run on a handle "
                              "with a GN-model admission check (gn_gate=)")
@@ -153,11 +161,13 @@ class BatchedRMSAEnv(BatchedHandle):
                 actions = np.ascontiguousarray(actions, dtype=np.int32)
             _check_buffer("actions", actions, ashape, np.int32)
             ap = _ptr(actions)
-        if diag or rule or cut:
+        if diag or rule or cut:   # (a name of WINDOW_POLICIES has a rule)
             d = _lib.StepDiag(_ptr(diag.get("block_cause")), _ptr(diag.get("block_cause_counts")),
                               None if gsnr is None else _ptr(gsnr["gn_gsnr_db"]))
             if cut:
                 _lib.check(self.L.orlg_step_min_cut(self.h, pid, int(n_steps), ap, 1 if auto_reset else 0, C.byref(io), C.byref(d)))
+            elif window:
+                _lib.check(self.L.orlg_step_window(self.h, pid, rule, int(n_steps), ap, 1 if auto_reset else 0, C.byref(io), C.byref(d)))
             elif rule:
                 _lib.check(self.L.orlg_step_assign(self.h, pid, rule, int(n_steps), ap, 1 if auto_reset else 0, C.byref(io),
                                                    C.byref(d)))
@@ -355,6 +365,34 @@ class BatchedRMSAEnv(BatchedHandle):
                 _check_buffer(name, buf, shape, np.int16)
             res.append(buf)
         _lib.check(self.L.orlg_path_min_cuts(self.h, _ptr(res[0]), _ptr(res[1])))
+        return res[0], res[1]
+
+    def slot_usage(self, out=None):
+        """The slot usage of every env (``orlg_slot_usage``): [B, S] uint8, the number of links of the whole topology
+        on which the slot is occupied -- what the most-used rule sums over a window, as a feature.  Reads state only; ``out`` as
+        in :meth:`action_masks`."""
+        shape = (self.batch_size, self.num_spectrum_resources)
+        if out is None:
+            out = np.zeros(shape, np.uint8)
+        else:
+            _check_buffer("out", out, shape, np.uint8)
+        _lib.check(self.L.orlg_slot_usage(self.h, _ptr(out)))
+        return out
+
+    def path_most_used(self, usage_out=None, slots_out=None):
+        """The most-used window of every candidate path of every env's pending request (``orlg_path_most_used``):
+        ``(usage, slots)`` -- [B, k] int32, the window's usage (the sum of :meth:`slot_usage` over its slots), and [B, k] int16,
+        its start; ``-1`` and ``S`` where the path has no window.  What the ``*_mu`` names of ``_lib.WINDOW_POLICIES`` propose.
+        Reads state only; ``usage_out`` / ``slots_out`` as ``out`` in :meth:`action_masks`."""
+        shape = (self.batch_size, self.k_paths)
+        res = []
+        for name, buf, dt in (("usage_out", usage_out, np.int32), ("slots_out", slots_out, np.int16)):
+            if buf is None:
+                buf = np.zeros(shape, dt)
+            else:
+                _check_buffer(name, buf, shape, dt)
+            res.append(buf)
+        _lib.check(self.L.orlg_path_most_used(self.h, _ptr(res[0]), _ptr(res[1])))
         return res[0], res[1]
 
     def simple_matrix_observation(self, out=None):

@@ -14,6 +14,7 @@ struct orlg_env : OrlgHandle {
     // kernel's LDS budget); the LDS layout of each kind of instantiation (orlg_group_plan.h) and its resident workgroups
     int group_mode = 0;
     OrlgGroupLayout group[3] = {};                          // by OrlgGroupKind
+    int group_usage_resident[ORLG_GROUP_WAVES + 1] = {};    // ... of the USAGE instantiations, which take more LDS (launch_rmsa_group)
     int group_resident[3][ORLG_GROUP_WAVES + 1] = {};       // ... by waves per workgroup (0 = not asked yet)
     uint4 *llog = nullptr;          // DEFER: the log of link updates [B][E][ORLG_LLOG_CAP] (allocated with the first such launch)
     uint32_t *progress = nullptr;   // chunked tickets: chunks completed per quad in the current launch (allocated with the first such launch)
@@ -140,8 +141,13 @@ static OrlgGroupOverrides group_overrides() {
 
 // the step kernel with four environments per wave: first-fit policies and external (path, slot) actions.  What is launched is
 // decided in orlg_group_plan.h; here it is done
+// a launch of orlg_step_window under the rule MOST_USED or the route BEST_WINDOW: the USAGE instantiations (orlg_usage.h)
+static bool usage_launch(const OrlgParams &p) {
+    return (p.out_mask & ORLG_OUT_ASSIGN_BIT) != 0 && (p.assign == ORLG_ASSIGN_MOST_USED || p.policy == ORLG_POLICY_BEST_WINDOW);
+}
+
 static int launch_rmsa_group(orlg_env *e, const OrlgParams &p, const OrlgGroupOverrides &ov) {
-    const OrlgGroupChoice c = orlg_group_choose(e->group, {p.B, p.n_steps, p.stats_level, p.policy, p.out_mask, p.br_width}, ov, e->num_cu);
+    OrlgGroupChoice c = orlg_group_choose(e->group, {p.B, p.n_steps, p.stats_level, p.policy, p.out_mask, p.br_width}, ov, e->num_cu);
     const OrlgGroupLayout &l = e->group[c.kind];
     const bool df = c.kind == ORLG_GROUP_DEFER;
     const bool trace = p.tr_arrival != nullptr;   // a request trace: the instantiations that replay it
@@ -149,13 +155,22 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p, const OrlgGroupOv
     const bool cause = (p.out_mask & ORLG_OUT_CAUSE_BIT) != 0;   // the blocking cause: the plain kind with the classifier (the plan chose it)
     const bool assign = (p.out_mask & ORLG_OUT_ASSIGN_BIT) != 0;   // an assignment rule: the plain kind with the rules (the plan chose it)
     const bool cut = assign && p.assign == ORLG_ASSIGN_MIN_CUT;   // ... the fewest-cuts window: the CUT instantiations
-    const OrlgGroupKey key = {p.stats_level, c.kind == ORLG_GROUP_HBMQ, df, traffic, trace, cause, assign, cut};
+    const bool usage = usage_launch(p);   // ... MOST_USED / BEST_WINDOW: the USAGE instantiations, with their prefix sums behind the wave regions
+    const OrlgGroupKey key = {p.stats_level, c.kind == ORLG_GROUP_HBMQ, df, traffic, trace, cause, assign, cut, usage};
     rmsa_kernel_t k = orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
+    if (usage) {
+        c.wpb = orlg_group_usage_wpb(l, c.wpb, e->W);
+        if (c.wpb < 1)
+            return fail(ORLG_ERR_INVALID, "step_kernel \"group\": one wave's four environments (%d B) and their slot-usage prefix sums (%d B) do not "
+                                          "fit the LDS next to the tables (%d B); use step_kernel \"wave\" or \"auto\" for this policy",
+                        l.wave_bytes, 4 * ORLG_USAGE_BYTES(e->W), l.shared_bytes);
+        c.lds_bytes = orlg_group_lds(l.shared_bytes, c.wpb, l.wave_bytes + 4 * ORLG_USAGE_BYTES(e->W));
+    }
     if (df && !e->llog)
         if (int rc = orlg_handle_alloc(e, &e->llog, (size_t)p.B * p.E * ORLG_LLOG_CAP)) return rc;
-    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), orlg_group_lds(l.shared_bytes, l.wpb_max, l.wave_bytes))) return rc;
-    int *resident = &e->group_resident[c.kind][c.wpb];
+    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), usage ? c.lds_bytes : orlg_group_lds(l.shared_bytes, l.wpb_max, l.wave_bytes))) return rc;
+    int *resident = usage ? &e->group_usage_resident[c.wpb] : &e->group_resident[c.kind][c.wpb];
     if (int rc = orlg_handle_resident(e, reinterpret_cast<const void *>(k), ORLG_WAVE * c.wpb, c.lds_bytes, resident)) return rc;
     const OrlgGroupTickets t = orlg_group_tickets(c, p.B, p.n_steps, *resident, ov);
     if (t.n_chunks > 1) {
@@ -179,6 +194,8 @@ static int launch_rmsa_group(orlg_env *e, const OrlgParams &p, const OrlgGroupOv
 static bool group_kernel_serves(const orlg_env *e, const OrlgParams &p) {
     if (e->group_mode == ORLG_KERNEL_WAVE || p.mode != ORLG_MODE_STEP || p.gn) return false;   // (a gated handle: the wave kernel's GN instantiations)
     if (e->group_mode == ORLG_KERNEL_GROUP) return true;
+    // (a USAGE launch whose prefix sums the LDS does not hold next to one wave's environments: the wave kernel)
+    if (usage_launch(p) && orlg_group_usage_wpb(e->group[ORLG_GROUP_PLAIN], 1, e->W) < 1) return false;
     // AUTO: this kernel once the batch exceeds what the wave-per-environment kernel keeps resident (4096 environments on
     // MI355X) -- long launches (B = 65 536: 1140 vs 630 M env-steps/s) and launches of one step alike (B = 32 768, DeepRMSA
     // shape: 0.145 vs 0.161 ms per step + observation); at or below it the wave-per-environment kernel has the shorter step
@@ -201,7 +218,7 @@ static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
     const bool df = !gn && p.mode == ORLG_MODE_STEP && orlg_defer_link_stats(p.stats_level, p.n_steps, p.out_mask, ov);   // as launch_rmsa_group
     const OrlgWaveKey key = {ff ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel_ff)
                                 : p.mode == ORLG_MODE_STEP ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel) : ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel),
-                             p.stats_level, df, gn, cause, assign, assign && p.assign == ORLG_ASSIGN_MIN_CUT};
+                             p.stats_level, df, gn, cause, assign, assign && p.assign == ORLG_ASSIGN_MIN_CUT, assign && usage_launch(p)};
     rmsa_kernel_t k = orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), e->lds_block_bytes)) return rc;
@@ -213,7 +230,19 @@ static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
         if (rc) return rc;
     }
     if (group_kernel_serves(e, p)) return launch_rmsa_group(e, p, ov);
-    int nblocks = (p.B + wpb - 1) / wpb;
+    // (a USAGE launch: the waves' prefix sums of the slot usage lie behind the wave regions, asked for here and by no other launch;
+    // where the handle's workgroup fills the LDS, such a launch runs with as many waves per workgroup as still fit)
+    int wpu = wpb;
+    size_t lds = e->lds_block_bytes;
+    if (key.USAGE) {
+        const size_t per_wave = (size_t)p.l_wave_bytes + ORLG_USAGE_BYTES(e->W);
+        while (wpu > 1 && (size_t)p.l_shared_bytes + wpu * per_wave > ORLG_LDS_BYTES) --wpu;
+        lds = (size_t)p.l_shared_bytes + wpu * per_wave;
+        if (lds > ORLG_LDS_BYTES)
+            return fail(ORLG_ERR_INVALID, "tables, one environment and its slot-usage prefix sums (%zu B) exceed the 160 KiB LDS", lds);
+        if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), lds)) return rc;
+    }
+    int nblocks = (p.B + wpu - 1) / wpu;
     if (nblocks > e->resident_blocks) nblocks = e->resident_blocks;
     if (df && !e->llog) {
         int rc = orlg_handle_alloc(e, &e->llog, (size_t)p.B * p.E * ORLG_LLOG_CAP);
@@ -224,10 +253,10 @@ static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
     q.ticket_base = e->ticket_base;
     q.ticket_stride = (p.mode != ORLG_MODE_STEP || p.n_steps <= 16) ? 1u : 0u;
     if (!q.ticket_stride) e->ticket_base += (uint32_t)p.B;  // waves * 1 static environment + (B - waves) tickets + one failing draw per wave
-    dim3 grid(nblocks), block(ORLG_WAVE * wpb);
-    hipLaunchKernelGGL(k, grid, block, e->lds_block_bytes, e->stream, q);
+    dim3 grid(nblocks), block(ORLG_WAVE * wpu);
+    hipLaunchKernelGGL(k, grid, block, lds, e->stream, q);
     HIP_TRY(hipGetLastError());
-    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * wpb, e->lds_block_bytes);
+    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * wpu, lds);
     return ORLG_OK;
 }
 
@@ -567,19 +596,21 @@ static int extra_out(orlg_env *e, ExtraOut *o, void *user, size_t bytes, int slo
 }
 // orlg_step, orlg_step_gn, orlg_step_diag, orlg_step_assign and orlg_step_min_cut (gsnr, cause, counts: the outputs beyond
 // orlg_step_io, nullptr = not asked for; assign: ORLG_ASSIGN_*, 0 = the reference's first fit, or the device's own
-// ORLG_ASSIGN_MIN_CUT, which only orlg_step_min_cut passes, with min_cut_entry -- `policy` may then be the device's ORLG_POLICY_MIN_CUT)
+// ORLG_ASSIGN_MIN_CUT, which only orlg_step_min_cut passes, with own_entry = 1 -- `policy` may then be the device's ORLG_POLICY_MIN_CUT;
+// own_entry = 2: orlg_step_window, which has checked its route and rule itself -- the device's ORLG_ASSIGN_MOST_USED and ORLG_POLICY_BEST_WINDOW)
 static int rmsa_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
                      const orlg_step_io *io, double *gsnr, uint8_t *cause = nullptr, int32_t *counts = nullptr, int32_t assign = ORLG_ASSIGN_FIRST,
-                     bool min_cut_entry = false) {
+                     int own_entry = 0) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     if (n_steps < 1) return fail(ORLG_ERR_INVALID, "n_steps must be >= 1");
-    const bool cut_route = min_cut_entry && policy == ORLG_POLICY_MIN_CUT;
+    const bool min_cut_entry = own_entry == 1;
+    const bool cut_route = (min_cut_entry && policy == ORLG_POLICY_MIN_CUT) || (own_entry == 2 && policy == ORLG_POLICY_BEST_WINDOW);
     if (!cut_route && (policy < ORLG_POLICY_EXTERNAL || policy > ORLG_POLICY_SAP_FF_GN)) return fail(ORLG_ERR_INVALID, "unknown policy %d", policy);
     if (policy == ORLG_POLICY_SAP_FF_GN && !e->p.gn)
         return fail(ORLG_ERR_INVALID, "policy %d (sap_ff_gn) asks the GN-model admission check: the handle has no gn_gate", policy);
     // an assignment rule other than the reference's first fit: the policy is a route, the handle has no gate -- before anything is launched
     // (the public rules; ORLG_ASSIGN_MIN_CUT comes from orlg_step_min_cut alone and is an unknown rule to every other caller)
-    if (assign < ORLG_ASSIGN_FIRST || assign >= (min_cut_entry ? ORLG_ASSIGN_MIN_CUT + 1 : ORLG_NUM_ASSIGN_RULES)) return fail(ORLG_ERR_INVALID, "unknown assignment rule %d", assign);
+    if (assign < ORLG_ASSIGN_FIRST || assign >= (own_entry == 2 ? ORLG_ASSIGN_MOST_USED + 1 : min_cut_entry ? ORLG_ASSIGN_MIN_CUT + 1 : ORLG_NUM_ASSIGN_RULES)) return fail(ORLG_ERR_INVALID, "unknown assignment rule %d", assign);
     if (assign != ORLG_ASSIGN_FIRST) {
         if (!cut_route && policy != ORLG_POLICY_SP_FF && policy != ORLG_POLICY_SAP_FF && policy != ORLG_POLICY_LLP_FF && policy != ORLG_POLICY_PATH_FF_EXTERNAL)
             return fail(ORLG_ERR_INVALID, "assignment rule %d needs a route (sp_ff, sap_ff, llp_ff or path_ff_external): policy %d names its own slot or block", assign, policy);
@@ -679,8 +710,24 @@ int orlg_step_min_cut(orlg_env *e, int32_t route, int32_t n_steps, const int32_t
         return fail(ORLG_ERR_INVALID, "the fewest-cuts window needs a route (sp_ff, sap_ff, llp_ff, path_ff_external or ORLG_ROUTE_FEWEST_CUTS): got %d", route);
     if (e->p.gn) return fail(ORLG_ERR_INVALID, "the fewest-cuts window on a handle with a gn_gate: the admission check knows the reference's first fit only");
     const int32_t policy = route == ORLG_ROUTE_FEWEST_CUTS ? (int32_t)ORLG_POLICY_MIN_CUT : route;
-    if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr, nullptr, nullptr, ORLG_ASSIGN_MIN_CUT, true);
-    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, ORLG_ASSIGN_MIN_CUT, true);
+    if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr, nullptr, nullptr, ORLG_ASSIGN_MIN_CUT, 1);
+    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, ORLG_ASSIGN_MIN_CUT, 1);
+}
+int orlg_step_window(orlg_env *e, int32_t route, int32_t rule, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
+                     const struct orlg_step_diag *diag) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    const bool old_route = route == ORLG_POLICY_SP_FF || route == ORLG_POLICY_SAP_FF || route == ORLG_POLICY_LLP_FF || route == ORLG_POLICY_PATH_FF_EXTERNAL;
+    const bool old_rule = rule == ORLG_ASSIGN_FIRST_FULL || rule == ORLG_ASSIGN_LAST || rule == ORLG_ASSIGN_BEST || rule == ORLG_ASSIGN_EXACT;
+    if (!old_route && route != ORLG_ROUTE_BEST_WINDOW)
+        return fail(ORLG_ERR_INVALID, "orlg_step_window needs a route (sp_ff, sap_ff, llp_ff, path_ff_external or ORLG_ROUTE_BEST_WINDOW): got %d", route);
+    if (!old_rule && rule != ORLG_RULE_MOST_USED)
+        return fail(ORLG_ERR_INVALID, "orlg_step_window needs a rule (ORLG_ASSIGN_FIRST_FULL, LAST, BEST, EXACT or ORLG_RULE_MOST_USED): got %d", rule);
+    if (e->p.gn) return fail(ORLG_ERR_INVALID, "orlg_step_window on a handle with a gn_gate: the admission check knows the reference's first fit only");
+    if (old_route && old_rule) return orlg_step_assign(e, route, rule, n_steps, actions, auto_reset, io, diag);   // what that launches
+    const int32_t policy = route == ORLG_ROUTE_BEST_WINDOW ? (int32_t)ORLG_POLICY_BEST_WINDOW : route;
+    const int32_t assign = rule == ORLG_RULE_MOST_USED ? (int32_t)ORLG_ASSIGN_MOST_USED : rule;
+    if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr, nullptr, nullptr, assign, 2);
+    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, assign, 2);
 }
 
 int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
@@ -986,6 +1033,39 @@ int orlg_path_min_cuts(orlg_env *e, int16_t *cuts, int16_t *slots_out) {
                        reinterpret_cast<int16_t *>(slots[1].dev));
     HIP_TRY(hipGetLastError());
     return collect_outputs(e, slots, 2);
+}
+
+// orlg_slot_usage and orlg_path_most_used: one kernel (orlg_usage_kernel), a null array is not written
+static int usage_query(orlg_env *e, uint8_t *slot_usage, int32_t *usage, int16_t *slots_out) {
+    HIP_TRY(hipSetDevice(e->device));
+    const OrlgParams &p = e->p;
+    OutSlot slots[3] = {{slot_usage, (size_t)p.B * p.S}, {usage, (size_t)p.B * p.K * sizeof(int32_t)}, {slots_out, (size_t)p.B * p.K * sizeof(int16_t)}};
+    int rc = place_outputs(e, slots, 3);
+    if (rc) return rc;
+    orlg_usage_kernel_t k = orlg_pick_usage(e->W);
+    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
+    const size_t per_wave = (size_t)((p.NW * 8 + 15) & ~15) + ORLG_USAGE_BYTES(e->W);   // an occupancy row and its prefix sums
+    int wpb = e->waves_per_block;
+    while (wpb > 1 && (size_t)p.l_shared_bytes + per_wave * wpb > ORLG_LDS_BYTES) --wpb;
+    const size_t lds = (size_t)p.l_shared_bytes + per_wave * wpb;
+    if (lds > ORLG_LDS_BYTES) return fail(ORLG_ERR_INVALID, "tables, one occupancy row and its slot-usage prefix sums (%zu B) exceed the 160 KiB LDS", lds);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int nblocks = (p.B + wpb - 1) / wpb;
+    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;
+    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, static_cast<uint8_t *>(slots[0].dev),
+                       reinterpret_cast<int32_t *>(slots[1].dev), reinterpret_cast<int16_t *>(slots[2].dev));
+    HIP_TRY(hipGetLastError());
+    return collect_outputs(e, slots, 3);
+}
+int orlg_slot_usage(orlg_env *e, uint8_t *usage) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!usage) return fail(ORLG_ERR_INVALID, "null argument: usage");
+    return usage_query(e, usage, nullptr, nullptr);
+}
+int orlg_path_most_used(orlg_env *e, int32_t *usage, int16_t *slots_out) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!usage && !slots_out) return fail(ORLG_ERR_INVALID, "null argument: neither a usage nor a slots buffer");
+    return usage_query(e, nullptr, usage, slots_out);
 }
 
 int orlg_gn_action_masks(orlg_env *e, uint8_t *path_ff, double *path_ff_gsnr_db, uint8_t *deeprmsa, double *deeprmsa_gsnr_db) {

@@ -71,6 +71,13 @@ enum { ORLG_POLICY_EXT = -1, ORLG_POLICY_SP = 0, ORLG_POLICY_SAP = 1, ORLG_POLIC
 // MIN_CUT as a value of OrlgParams::assign, behind the public ORLG_ASSIGN_* (ORLG_NUM_ASSIGN_RULES stays what it is)
 enum { ORLG_POLICY_MIN_CUT = 8 };
 enum { ORLG_ASSIGN_MIN_CUT = 5 };
+// device-side only (orlg_step_window, orlg_usage.h): the route "best window" -- of all k paths the one whose rule window ranks best
+// by the rule's own order (include/orlg.h ORLG_ROUTE_BEST_WINDOW is mapped to it) -- and the rule MOST_USED as a value of
+// OrlgParams::assign (include/orlg.h ORLG_RULE_MOST_USED is mapped to it); a launch with either runs the USAGE instantiations
+enum { ORLG_POLICY_BEST_WINDOW = 9 };
+enum { ORLG_ASSIGN_MOST_USED = 6 };
+// LDS an environment's prefix sums of the slot usage take in such a launch: 64 W int32 (orlg_usage.h usage_prefix)
+#define ORLG_USAGE_BYTES(W) (256 * (W))
 // per-step output slots (OrlgParams::outs)
 enum { ORLG_OUT_PATH = 0, ORLG_OUT_SLOT, ORLG_OUT_ACCEPTED, ORLG_OUT_DONE, ORLG_OUT_REWARD, ORLG_OUT_REQUEST,
        ORLG_OUT_ARRIVAL, ORLG_OUT_HOLDING, ORLG_OUT_COMPACT, ORLG_OUT_COMPACT_DIFF, ORLG_OUT_AVG_LINK_COMPACT,

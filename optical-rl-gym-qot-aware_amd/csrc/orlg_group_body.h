@@ -1,6 +1,6 @@
 // orlg_group_body.h -- the TEXT of orlg_rmsa_group_kernel's body (orlg_group_kernels.hip), from the first statement to the last.
 // Not a header to include at file scope: it is included INSIDE a function that has the kernel's template arguments (W, STATS,
-// HBMQ, DEFER, TRAFFIC, TRACE), the constants `LEAN`, `CAUSE`, `ASSIGN` and `CUT` and the parameters `p` in scope -- once in the kernel itself and once in
+// HBMQ, DEFER, TRAFFIC, TRACE), the constants `LEAN`, `CAUSE`, `ASSIGN`, `CUT` and `USAGE` and the parameters `p` in scope -- once in the kernel itself and once in
 // orlg_rmsa_group_body, which gives the DEFER instantiations their second, lean body.  Why the text and not only the function:
 // a kernel whose body arrives through an inlined function compiles to slightly different code than one that holds the text
 // (other spill placement, a few dozen instructions either way), and the instantiations without a lean body are to stay,
@@ -15,6 +15,7 @@
     static_assert(!CAUSE || (!HBMQ && !DEFER), "the blocking cause belongs to the plain kind");
     static_assert(!ASSIGN || (!HBMQ && !DEFER), "the assignment rules belong to the plain kind");
     static_assert(!CUT || ASSIGN, "the fewest-cuts window is an assignment rule");
+    static_assert(!USAGE || (ASSIGN && !CUT), "most-used windows and the best-window route are assignment rules of their own");
     extern __shared__ __align__(16) unsigned char smem[];
     stage_tables(smem, p);
     const int lane = threadIdx.x & 63;
@@ -242,7 +243,43 @@
                 const int best = row_min_i32(payload);
                 if (found == 0x7fffffff) found = best;
             }
-            for (int p0 = 0; !CUT && p0 < kmax; p0 += PP) {
+            // USAGE: orlg_step_window under the rule MOST_USED or the route BEST_WINDOW (orlg_usage.h) -- the rules' loop below with
+            // the rule MOST_USED beside the four (its key reads the prefix sums of the slot usage, which the row computes from the
+            // occupancy this step meets) and with a ranked route that compares the paths' keys themselves: a key is 27 bits, so the
+            // row takes the minimum of the inverted rank first and then, among the paths that hold it, the lowest payload (the path
+            // is its top field).  The other two loops are compiled out, as this one is without USAGE
+            if constexpr (USAGE) {
+                int32_t *uincl = reinterpret_cast<int32_t *>(smem + p.l_shared_bytes + p.g_mt + 16 + (size_t)(blockDim.x >> 6) * p.g_wave_bytes) +
+                                 (wib * ORLG_GE + g) * (ORLG_USAGE_BYTES(W) / 4);
+                if (rule == ORLG_ASSIGN_MOST_USED) {
+                    usage_prefix<W, 1>(occ, uincl, E, S, lane);
+                    wave_sync();
+                }
+                const bool ranked_w = llp || policy == ORLG_POLICY_BEST_WINDOW;
+                for (int p0 = 0; p0 < kmax; p0 += PP) {
+                    if (!ranked_w && ballot(act && a_ok && found == 0x7fffffff) == 0ull) break;
+                    const int pp = p0 + ps;
+                    const bool on = ps < PP && pp < kmax && a_ok;
+                    int se_pp, hops_pp;
+                    const u64 x = group_path_word_rec<W>(occ, tb.recs, base + path0 + pp, w, on, se_pp, hops_pp) & valid_mask(S, w);
+                    int n = 1;
+                    if (on) n = tb.nslots[req_br * ORLG_NSLOT_STRIDE + se_pp];
+                    const uint32_t sk = seg_max<W>(window_word_key<W>(uincl, x, n, w, rule));   // the path's key, on its first lane
+                    const bool head = on && w == 0 && sk != 0u;
+                    const int payload = head ? (((((path0 + pp) << 10) | window_key_slot(sk, rule)) << 14) | (n << 4) | hops_pp) : 0x7fffffff;
+                    if (ranked_w) {
+                        const uint32_t fs = seg_add<W>((uint32_t)popc64(x));
+                        const int inv = head ? (int)(llp ? 1023u - fs : 0x7ffffffeu - sk) : 0x7fffffff;
+                        const int bk = row_min_i32(inv);
+                        const int bp = row_min_i32(inv == bk ? payload : 0x7fffffff);
+                        if (bk < found_key) { found_key = bk; found = bp; }
+                        continue;
+                    }
+                    const int best = row_min_i32(payload);
+                    if (found == 0x7fffffff) found = best;
+                }
+            }
+            for (int p0 = 0; !CUT && !USAGE && p0 < kmax; p0 += PP) {
                 if (!llp && ballot(act && a_ok && found == 0x7fffffff) == 0ull) break;
                 const int pp = p0 + ps;
                 const bool on = ps < PP && pp < kmax && a_ok;

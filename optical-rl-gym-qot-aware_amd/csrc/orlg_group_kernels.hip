@@ -27,6 +27,7 @@
 #include "orlg_block_cause.h"  // window_level: the classifier of the CAUSE instantiations (group_fit_level below)
 #include "orlg_assign.h"       // assign_word_key: the assignment rules of the ASSIGN instantiations
 #include "orlg_cut.h"          // cut_word_key: the fewest-cuts window of the CUT instantiations
+#include "orlg_usage.h"        // usage_prefix, window_word_key: the rule MOST_USED and the route BEST_WINDOW of the USAGE instantiations
 
 #define ORLG_GL 16  // lanes per environment (one DPP row)
 #define ORLG_GE 4   // environments per wave
@@ -473,6 +474,7 @@ DEV void orlg_rmsa_group_body(const OrlgParams &p) {
     constexpr bool CAUSE = false;   // (the DEFER instantiations have no classifier: a cause launch runs the plain kind)
     constexpr bool ASSIGN = false;  // (... and no assignment rule but the reference's first fit)
     constexpr bool CUT = false;
+    constexpr bool USAGE = false;
 #include "orlg_group_body.h"
 }
 
@@ -485,8 +487,11 @@ DEV void orlg_rmsa_group_body(const OrlgParams &p) {
 // OrlgParams::assign; orlg_assign.h): the policy section is the rules' own.  A template argument and the plain kind only, as CAUSE
 // CUT (with ASSIGN): the launch runs the fewest-cuts window (orlg_step_min_cut; orlg_cut.h): its hop loop stands in the rules' place.
 // A flag of its own so that the ASSIGN instantiations stay the code they were
+// USAGE (with ASSIGN, without CUT): the launch is orlg_step_window's under the rule MOST_USED or the route BEST_WINDOW (orlg_usage.h):
+// a policy loop of its own, and the four environments' prefix sums of the slot usage in LDS behind the workgroup's wave regions
+// (4 * ORLG_USAGE_BYTES(W) per wave, asked for by the launch alone)
 template <int W, int STATS, bool HBMQ = false, bool DEFER = false, bool TRAFFIC = false, bool TRACE = false, bool CAUSE = false, bool ASSIGN = false,
-          bool CUT = false>
+          bool CUT = false, bool USAGE = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_GROUP_WAVES, (ORLG_GROUP_WAVES + 3) / 4) void orlg_rmsa_group_kernel(const OrlgParams p) {
     if constexpr (DEFER) {
         if (p.g_lean) orlg_rmsa_group_body<W, STATS, HBMQ, DEFER, TRAFFIC, TRACE, true>(p);

@@ -40,6 +40,14 @@ static inline OrlgGroupLayout orlg_group_layout(OrlgGroupKind kind, int NW, int 
     return l;
 }
 
+// A USAGE launch (orlg_step_window under the rule MOST_USED or the route BEST_WINDOW; orlg_usage.h) keeps the four environments'
+// prefix sums of the slot usage behind the workgroup's wave regions, 4 * ORLG_USAGE_BYTES(W) per wave on top of the layout: the most
+// waves per workgroup, at most `wpb`, that the LDS then holds; 0 = not even one (the launch is refused, or goes to the wave kernel)
+static inline int orlg_group_usage_wpb(const OrlgGroupLayout &l, int wpb, int W) {
+    while (wpb >= 1 && orlg_group_lds(l.shared_bytes, wpb, l.wave_bytes + 4 * ORLG_USAGE_BYTES(W)) > ORLG_LDS_BYTES) --wpb;
+    return wpb;
+}
+
 struct OrlgGroupLaunch { int B, n_steps, stats_level, policy, out_mask, br_width; };
 // the tooling environment: ORLG_NO_DEFER, ORLG_NO_CHUNKS, ORLG_NO_LEAN set; ORLG_GROUP_WPB, ORLG_GROUP_CHUNKS (0 = not set)
 struct OrlgGroupOverrides { bool no_defer, no_chunks, no_lean; int wpb, chunks; };

@@ -15,6 +15,7 @@ orlg_rmsa_kernel_t ORLG_CAT(orlg_group_kernel_W, ORLG_INST_W)(OrlgGroupKey key) 
     ORLG_GROUP_CAUSE_KEYS(X)
     ORLG_GROUP_ASSIGN_KEYS(X)
     ORLG_GROUP_CUT_KEYS(X)
+    ORLG_GROUP_USAGE_KEYS(X)
 #undef X
     return nullptr;
 }

@@ -37,6 +37,7 @@
 #include "orlg_block_cause.h"  // wave_fit_levels: the classifier of the CAUSE instantiations
 #include "orlg_assign.h"       // wave_assign: the assignment rules of the ASSIGN instantiations
 #include "orlg_cut.h"          // wave_cut_assign: the fewest-cuts window of the CUT instantiations
+#include "orlg_usage.h"        // wave_window_assign: the rule MOST_USED and the route BEST_WINDOW of the USAGE instantiations
 #include "orlg_sections.h"
 
 // ---------------------------------------------------------------------------------------- the step kernel
@@ -58,6 +59,10 @@
 // CUT (with ASSIGN): the launch runs the fewest-cuts window (orlg_step_min_cut, OrlgParams::assign == ORLG_ASSIGN_MIN_CUT):
 // wave_cut_assign (orlg_cut.h) stands where wave_assign stands.  A flag of its own so that the ASSIGN instantiations stay the code
 // they were.
+// USAGE (with ASSIGN, without CUT): the launch is orlg_step_window's under the rule MOST_USED or the route BEST_WINDOW
+// (OrlgParams::assign == ORLG_ASSIGN_MOST_USED, OrlgParams::policy == ORLG_POLICY_BEST_WINDOW): wave_window_assign (orlg_usage.h)
+// stands where wave_assign stands, and the environment's prefix sums of the slot usage lie in LDS BEHIND the workgroup's wave
+// regions (ORLG_USAGE_BYTES(W) per wave; the launch asks for them), so that no other launch's layout changes.
 template <bool GN>
 struct SapRetry {
     int from = 0, path = 0, slot = 0;
@@ -69,7 +74,8 @@ struct SapRetry<false> {
     SapRetry() = default;
 };
 
-template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false, bool CUT = false>
+template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false, bool CUT = false,
+          bool USAGE = false>
 DEV void rmsa_body(const OrlgParams &p) {
     extern __shared__ __align__(16) unsigned char smem[];
 #ifdef ORLG_SHAPE_ASSUME
@@ -242,6 +248,10 @@ DEV void rmsa_body(const OrlgParams &p) {
                 // (CUT: the fewest-cuts window, with a hop loop of its own, in the rules' place)
                 int got;
                 if constexpr (CUT) got = wave_cut_assign<W>(wv.occ, tb, base, K, S, req_br, lane, policy, given);
+                else if constexpr (USAGE)
+                    got = wave_window_assign<W>(wv.occ, reinterpret_cast<int32_t *>(smem + p.l_shared_bytes + (size_t)(blockDim.x >> 6) * p.l_wave_bytes +
+                                                                                    (size_t)wib * ORLG_USAGE_BYTES(W)),
+                                                tb, base, K, E, S, req_br, lane, policy, kq->assign, given);
                 else got = wave_assign<W>(wv.occ, tb, base, K, S, req_br, lane, policy, kq->assign, given);
                 if (got >= 0) { a_path = got >> 10; a_slot = got & 1023; }
             } else if (FF) {
@@ -656,10 +666,11 @@ DEV void rmsa_body(const OrlgParams &p) {
     SEC_FLUSH;
 }
 
-template <int W, int STATS, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false, bool CUT = false>
+template <int W, int STATS, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false, bool CUT = false, bool USAGE = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel(const OrlgParams p) {
     static_assert(!CUT || ASSIGN, "the fewest-cuts window is an assignment rule");
-    rmsa_body<W, STATS, true, false, DEFER, GN, CAUSE, ASSIGN, CUT>(p);
+    static_assert(!USAGE || (ASSIGN && !CUT), "most-used windows and the best-window route are assignment rules of their own");
+    rmsa_body<W, STATS, true, false, DEFER, GN, CAUSE, ASSIGN, CUT, USAGE>(p);
 }
 template <int W, int STATS, bool DEFER = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel_ff(const OrlgParams p) {

@@ -13,7 +13,8 @@
 // wave-per-environment kernels (orlg_kernels.hip): template <int W, int STATS, bool DEFER = false, bool GN = false, bool CAUSE = false,
 // bool ASSIGN = false, bool CUT = false>; the reset kernel has no DEFER, and only orlg_rmsa_kernel has GN (the GN-model admission
 // check, orlg_rmsa_gn.h), CAUSE (the blocking cause of every step, orlg_block_cause.h), ASSIGN (the spectrum-assignment rules beyond
-// the reference's first fit, orlg_assign.h) and CUT (ASSIGN with the fewest-cuts window in the rules' place, orlg_cut.h)
+// the reference's first fit, orlg_assign.h), CUT (ASSIGN with the fewest-cuts window in the rules' place, orlg_cut.h) and, after it,
+// USAGE (ASSIGN with the rule MOST_USED and the route BEST_WINDOW, orlg_usage.h)
 #define ORLG_WAVE_KERNELS(X) X(orlg_rmsa_kernel) X(orlg_rmsa_kernel_ff) X(orlg_rmsa_reset_kernel)
 #define ORLG_WAVE_KERNEL(name) ORLG_IS_##name
 enum OrlgWaveKernel {
@@ -21,15 +22,15 @@ enum OrlgWaveKernel {
     ORLG_WAVE_KERNELS(X)
 #undef X
 };
-struct OrlgWaveKey { OrlgWaveKernel kernel; int STATS; bool DEFER; bool GN = false; bool CAUSE = false; bool ASSIGN = false; bool CUT = false; };
+struct OrlgWaveKey { OrlgWaveKernel kernel; int STATS; bool DEFER; bool GN = false; bool CAUSE = false; bool ASSIGN = false; bool CUT = false; bool USAGE = false; };
 // orlg_rmsa_group_kernel (orlg_group_kernels.hip)
-struct OrlgGroupKey { int STATS; bool HBMQ, DEFER, TRAFFIC, TRACE; bool CAUSE = false; bool ASSIGN = false; bool CUT = false; };
+struct OrlgGroupKey { int STATS; bool HBMQ, DEFER, TRAFFIC, TRACE; bool CAUSE = false; bool ASSIGN = false; bool CUT = false; bool USAGE = false; };
 // orlg_phy_kernel (orlg_phy_kernels.hip)
 struct OrlgPhyKey { bool DF, GN; int POL; bool CONT, TRACE; };
 
-inline bool operator==(const OrlgWaveKey &a, const OrlgWaveKey &b) { return a.kernel == b.kernel && a.STATS == b.STATS && a.DEFER == b.DEFER && a.GN == b.GN && a.CAUSE == b.CAUSE && a.ASSIGN == b.ASSIGN && a.CUT == b.CUT; }
+inline bool operator==(const OrlgWaveKey &a, const OrlgWaveKey &b) { return a.kernel == b.kernel && a.STATS == b.STATS && a.DEFER == b.DEFER && a.GN == b.GN && a.CAUSE == b.CAUSE && a.ASSIGN == b.ASSIGN && a.CUT == b.CUT && a.USAGE == b.USAGE; }
 inline bool operator==(const OrlgGroupKey &a, const OrlgGroupKey &b) {
-    return a.STATS == b.STATS && a.HBMQ == b.HBMQ && a.DEFER == b.DEFER && a.TRAFFIC == b.TRAFFIC && a.TRACE == b.TRACE && a.CAUSE == b.CAUSE && a.ASSIGN == b.ASSIGN && a.CUT == b.CUT;
+    return a.STATS == b.STATS && a.HBMQ == b.HBMQ && a.DEFER == b.DEFER && a.TRAFFIC == b.TRAFFIC && a.TRACE == b.TRACE && a.CAUSE == b.CAUSE && a.ASSIGN == b.ASSIGN && a.CUT == b.CUT && a.USAGE == b.USAGE;
 }
 inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
     return a.DF == b.DF && a.GN == b.GN && a.POL == b.POL && a.CONT == b.CONT && a.TRACE == b.TRACE;
@@ -68,6 +69,12 @@ inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
 #define ORLG_WAVE_CUT_KEYS(X)                                                                                                                       \
     X(orlg_rmsa_kernel, 1, false, false, false, true, true) X(orlg_rmsa_kernel, 2, false, false, false, true, true) X(orlg_rmsa_kernel, 0, false, false, false, true, true) \
     X(orlg_rmsa_kernel, 1, false, false, true, true, true) X(orlg_rmsa_kernel, 2, false, false, true, true, true) X(orlg_rmsa_kernel, 0, false, false, true, true, true)
+// X(kernel, STATS, DEFER, GN, CAUSE, ASSIGN, CUT, USAGE): what a launch of orlg_step_window under the rule MOST_USED or the route
+// BEST_WINDOW runs (orlg_usage.h) -- the ASSIGN keys again with USAGE, for the reason the CUT keys have.  A list of
+// its own, expanded last.
+#define ORLG_WAVE_USAGE_KEYS(X)                                                                                                                                   \
+    X(orlg_rmsa_kernel, 1, false, false, false, true, false, true) X(orlg_rmsa_kernel, 2, false, false, false, true, false, true) X(orlg_rmsa_kernel, 0, false, false, false, true, false, true) \
+    X(orlg_rmsa_kernel, 1, false, false, true, true, false, true) X(orlg_rmsa_kernel, 2, false, false, true, true, false, true) X(orlg_rmsa_kernel, 0, false, false, true, true, false, true)
 
 // X(STATS, HBMQ, DEFER, TRAFFIC, TRACE).  Per kind of handle: every statistics level, the same with the release queue left in HBM
 // (launches of very few steps), and full statistics with the link updates deferred (long launches).  The kinds: plain, with
@@ -99,6 +106,13 @@ inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
 #define ORLG_GROUP_CUT_KEYS(X)                                                                                                     \
     ORLG_GROUP_CUT_KEYS_OF(X, false, false, false) ORLG_GROUP_CUT_KEYS_OF(X, true, false, false) ORLG_GROUP_CUT_KEYS_OF(X, false, true, false) \
     ORLG_GROUP_CUT_KEYS_OF(X, false, false, true) ORLG_GROUP_CUT_KEYS_OF(X, true, false, true) ORLG_GROUP_CUT_KEYS_OF(X, false, true, true)
+// X(STATS, HBMQ, DEFER, TRAFFIC, TRACE, CAUSE, ASSIGN, CUT, USAGE): the launches of orlg_step_window under the rule MOST_USED or the
+// route BEST_WINDOW -- the ASSIGN keys again with USAGE (as ORLG_WAVE_USAGE_KEYS).  A list of its own, expanded last
+#define ORLG_GROUP_USAGE_KEYS_OF(X, TRAFFIC, TRACE, CAUSE) \
+    X(0, false, false, TRAFFIC, TRACE, CAUSE, true, false, true) X(1, false, false, TRAFFIC, TRACE, CAUSE, true, false, true) X(2, false, false, TRAFFIC, TRACE, CAUSE, true, false, true)
+#define ORLG_GROUP_USAGE_KEYS(X)                                                                                                         \
+    ORLG_GROUP_USAGE_KEYS_OF(X, false, false, false) ORLG_GROUP_USAGE_KEYS_OF(X, true, false, false) ORLG_GROUP_USAGE_KEYS_OF(X, false, true, false) \
+    ORLG_GROUP_USAGE_KEYS_OF(X, false, false, true) ORLG_GROUP_USAGE_KEYS_OF(X, true, false, true) ORLG_GROUP_USAGE_KEYS_OF(X, false, true, true)
 
 // X(DF, GN, POL, CONT, TRACE), one instantiation per policy (-1 external actions .. 6).  Discrete bit rates: the step kernel
 // proper, + periodic defragmentation, + defragmentation and the GN-model admission check, + the check alone (a handle without
@@ -133,10 +147,12 @@ inline constexpr OrlgWaveKey ORLG_WAVE_GN_KEY_LIST[] = {ORLG_WAVE_GN_KEYS(ORLG_W
 inline constexpr OrlgWaveKey ORLG_WAVE_CAUSE_KEY_LIST[] = {ORLG_WAVE_CAUSE_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgWaveKey ORLG_WAVE_ASSIGN_KEY_LIST[] = {ORLG_WAVE_ASSIGN_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgWaveKey ORLG_WAVE_CUT_KEY_LIST[] = {ORLG_WAVE_CUT_KEYS(ORLG_WAVE_KEY_ENTRY)};
+inline constexpr OrlgWaveKey ORLG_WAVE_USAGE_KEY_LIST[] = {ORLG_WAVE_USAGE_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_KEY_LIST[] = {ORLG_GROUP_KEYS(ORLG_GROUP_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_CAUSE_KEY_LIST[] = {ORLG_GROUP_CAUSE_KEYS(ORLG_GROUP_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_ASSIGN_KEY_LIST[] = {ORLG_GROUP_ASSIGN_KEYS(ORLG_GROUP_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_CUT_KEY_LIST[] = {ORLG_GROUP_CUT_KEYS(ORLG_GROUP_KEY_ENTRY)};
+inline constexpr OrlgGroupKey ORLG_GROUP_USAGE_KEY_LIST[] = {ORLG_GROUP_USAGE_KEYS(ORLG_GROUP_KEY_ENTRY)};
 inline constexpr OrlgPhyKey ORLG_PHY_KEY_LIST[] = {ORLG_PHY_KEYS(ORLG_PHY_KEY_ENTRY)};
 template <typename Key, size_t N>
 static int orlg_key_index(const Key (&list)[N], const Key &key) {
@@ -161,12 +177,12 @@ inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgWaveKey &k)
 #define X(name) #name,
     static const char *const names[] = {ORLG_WAVE_KERNELS(X)};
 #undef X
-    const OrlgArg args[] = {{k.STATS, 'i'}, {k.DEFER, 'd'}, {k.GN, 'd'}, {k.CAUSE, 'd'}, {k.ASSIGN, 'd'}, {k.CUT, 'd'}};
-    orlg_format_kernel(buf, cap, names[k.kernel], W, args, k.kernel == ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel) ? 1 : 6);
+    const OrlgArg args[] = {{k.STATS, 'i'}, {k.DEFER, 'd'}, {k.GN, 'd'}, {k.CAUSE, 'd'}, {k.ASSIGN, 'd'}, {k.CUT, 'd'}, {k.USAGE, 'd'}};
+    orlg_format_kernel(buf, cap, names[k.kernel], W, args, k.kernel == ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel) ? 1 : 7);
 }
 inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgGroupKey &k) {
-    const OrlgArg args[] = {{k.STATS, 'i'}, {k.HBMQ, 'd'}, {k.DEFER, 'd'}, {k.TRAFFIC, 'd'}, {k.TRACE, 'd'}, {k.CAUSE, 'd'}, {k.ASSIGN, 'd'}, {k.CUT, 'd'}};
-    orlg_format_kernel(buf, cap, "orlg_rmsa_group_kernel", W, args, 8);
+    const OrlgArg args[] = {{k.STATS, 'i'}, {k.HBMQ, 'd'}, {k.DEFER, 'd'}, {k.TRAFFIC, 'd'}, {k.TRACE, 'd'}, {k.CAUSE, 'd'}, {k.ASSIGN, 'd'}, {k.CUT, 'd'}, {k.USAGE, 'd'}};
+    orlg_format_kernel(buf, cap, "orlg_rmsa_group_kernel", W, args, 9);
 }
 inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgPhyKey &k) {
     const OrlgArg args[] = {{k.DF, 'b'}, {k.GN, 'b'}, {k.POL, 'i'}, {k.CONT, 'd'}, {k.TRACE, 'd'}};
@@ -185,6 +201,7 @@ typedef void (*orlg_action_masks_kernel_t)(const OrlgParams, uint8_t *, int, uin
 typedef void (*orlg_gn_action_masks_kernel_t)(const OrlgParams, uint8_t *, double *, uint8_t *, double *, int);   // orlg_gn_action_masks_kernel
 typedef void (*orlg_fit_levels_kernel_t)(const OrlgParams, uint8_t *);                         // orlg_fit_levels_kernel
 typedef void (*orlg_min_cuts_kernel_t)(const OrlgParams, int16_t *, int16_t *);                // orlg_min_cuts_kernel
+typedef void (*orlg_usage_kernel_t)(const OrlgParams, uint8_t *, int32_t *, int16_t *);     // orlg_usage_kernel
 typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
 #define ORLG_FOR_EACH_W(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__) X(6, __VA_ARGS__) X(8, __VA_ARGS__)
 #define ORLG_FOR_EACH_PHY_W(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__)
@@ -196,6 +213,7 @@ typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
     orlg_gn_action_masks_kernel_t orlg_gn_action_masks_kernel_W##n() __attribute__((weak));       \
     orlg_fit_levels_kernel_t orlg_fit_levels_kernel_W##n() __attribute__((weak));                 \
     orlg_min_cuts_kernel_t orlg_min_cuts_kernel_W##n() __attribute__((weak));                     \
+    orlg_usage_kernel_t orlg_usage_kernel_W##n() __attribute__((weak));                           \
     orlg_rmsa_kernel_t orlg_group_kernel_W##n(OrlgGroupKey) __attribute__((weak));
 #define ORLG_DECL_PHY_W(n, ...)                                                                   \
     orlg_phy_kernel_t orlg_phy_kernel_W##n(OrlgPhyKey) __attribute__((weak));                     \
@@ -219,4 +237,5 @@ static orlg_obs_kernel_t orlg_pick_obs(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, or
 static orlg_action_masks_kernel_t orlg_pick_action_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_action_masks_kernel_W, ) }
 static orlg_fit_levels_kernel_t orlg_pick_fit_levels(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_fit_levels_kernel_W, ) }
 static orlg_min_cuts_kernel_t orlg_pick_min_cuts(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_min_cuts_kernel_W, ) }
+static orlg_usage_kernel_t orlg_pick_usage(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_usage_kernel_W, ) }
 static orlg_gn_action_masks_kernel_t orlg_pick_gn_action_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_action_masks_kernel_W, ) }

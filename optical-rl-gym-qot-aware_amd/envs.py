@@ -670,6 +670,69 @@ def min_cut_heuristic(route):
     return heuristic
 
 
+_WINDOW_RULES = ("first_full", "last", "best", "exact", "most_used")
+
+
+def _window_proposal(available, usage, n, rule):
+    """The rule window of a request of ``n`` slots on a path with the availability vector ``available`` (``get_available_slots``)
+    and the network's slot usage ``usage`` [S]: ``(rank, start)``, ``rank`` a tuple that is smaller for the better proposal by the
+    rule's own order (include/orlg.h ``orlg_step_window``), or None when the path has no window.  A window is a start ``s`` in
+    ``0 .. S - n`` inclusive with ``[s, s + n)`` free; a block is a maximal free run."""
+    a = np.asarray(available).astype(bool)
+    S = len(a)
+    best = None
+    for s in range(0, S - n + 1):
+        if not a[s:s + n].all():
+            continue
+        lo, hi = s, s + n
+        while lo > 0 and a[lo - 1]:
+            lo -= 1
+        while hi < S and a[hi]:
+            hi += 1
+        rank = {"first_full": (s,), "last": (-s,), "best": (hi - lo, lo), "exact": (int(hi - lo != n), lo),
+                "most_used": (-int(np.sum(usage[s:s + n])), s)}[rule]
+        start = s if rule in ("first_full", "last", "most_used") else lo
+        if best is None or rank < best[0]:
+            best = (rank, start)
+    return best
+
+
+def window_heuristic(route, rule):
+    """A heuristic ``f(env) -> [path, slot]`` for ``RMSA-v0`` in the drop-in callback shape of
+    ``shortest_available_path_first_fit``: rule ``"first_full"``, ``"last"``, ``"best"``, ``"exact"`` or ``"most_used"`` (the
+    window whose slots are occupied on the most links of the whole network, ties to the lowest start) on route ``"sp"`` (path
+    0), ``"sap"`` (the first path that has a window), ``"llp"`` (of the paths that have a window the one with the most free
+    slots, strict ``>``) or ``"any"`` (every path proposes its rule window; the proposal that ranks best by the rule's own order
+    wins, ties to the lowest path).  Not in the reference; what the device policies of ``WINDOW_POLICIES`` and
+    ``{sp,sap,llp}_{ff_full,lf,bf,ef}`` propose, written on what the view exposes: ``get_available_slots``,
+    ``get_number_slots`` and the rows of ``topology.graph["available_slots"]``."""
+    if route not in ("sp", "sap", "llp", "any"):
+        raise ValueError(f"route {route!r}: expected 'sp', 'sap', 'llp' or 'any'")
+    if rule not in _WINDOW_RULES:
+        raise ValueError(f"rule {rule!r}: expected one of {_WINDOW_RULES}")
+
+    def heuristic(env):
+        S, k = env.topology.graph["num_spectrum_resources"], env.topology.graph["k_paths"]
+        paths = env.k_shortest_paths[env.current_service.source, env.current_service.destination]
+        avail = np.asarray(env.topology.graph["available_slots"])
+        usage = avail.shape[0] - avail.astype(np.int64).sum(axis=0)   # links on which the slot is occupied
+        best, action = None, [k, S]
+        for idp, path in enumerate(paths[:1] if route == "sp" else paths):
+            available = env.get_available_slots(path)
+            got = _window_proposal(available, usage, env.get_number_slots(path), rule)
+            if got is None:
+                continue
+            if route in ("sp", "sap"):
+                return [idp, got[1]]
+            rank = (-int(np.sum(available)),) if route == "llp" else got[0]
+            if best is None or rank < best:
+                best, action = rank, [idp, got[1]]
+        return action
+
+    heuristic.__name__ = f"{route}_{rule}_window"
+    return heuristic
+
+
 def least_loaded_path_first_fit(env: RMSAEnv) -> Tuple[int, int]:
     """LLP-FF (``rmsa_env.py:916-937``): among paths with a first fit, the one with most free slots (strict >)."""
     S, k = env.topology.graph["num_spectrum_resources"], env.topology.graph["k_paths"]
