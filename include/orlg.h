@@ -280,7 +280,7 @@ enum {
  * picks the slot on that path.  "Has a window" is a fit level >= ORLG_FIT_LAST_WINDOW (orlg_path_fit_levels): an agent's mask for
  * the path-only action space comes from that query.  ORLG_ERR_INVALID, before anything is launched: another policy with a rule
  * other than FIRST (ORLG_POLICY_EXTERNAL names its slot, the DeepRMSA policies index blocks, ORLG_POLICY_SAP_FF_GN), a handle with
- * a gn_gate, an unknown rule.  diag may be NULL; the blocking causes keep their state-based definitions (sap / llp then refuse
+ * a gn_gate (orlg_step_rule_gn serves it), an unknown rule.  diag may be NULL; the blocking causes keep their state-based definitions (sap / llp then refuse
  * with a cause <= ORLG_CAUSE_ALIGNMENT only).  Such a launch runs the ASSIGN instantiation of the handle's step kernel
  * (orlg_rmsa_kernel<.., ASSIGN> / orlg_rmsa_group_kernel<.., ASSIGN>, the plain kind of either).  The QoT-aware environment
  * (orlg_phy_*) has no such entry: its channels are not contiguous. */
@@ -299,7 +299,7 @@ int orlg_step_assign(orlg_env *env, int32_t policy, int32_t assign, int32_t n_st
 /* orlg_step_diag under the rule MIN_CUT.  `route` is ORLG_POLICY_SP_FF, ORLG_POLICY_SAP_FF, ORLG_POLICY_LLP_FF or
  * ORLG_POLICY_PATH_FF_EXTERNAL (actions [B] name the path), read exactly as orlg_step_assign reads them for its rules other than
  * FIRST ("has a window" is the same predicate), or ORLG_ROUTE_FEWEST_CUTS.  No path of the route with a window: the rejection
- * (k, S).  ORLG_ERR_INVALID, before anything is launched: any other route, a handle with a gn_gate.  diag may be NULL; block_cause
+ * (k, S).  ORLG_ERR_INVALID, before anything is launched: any other route, a handle with a gn_gate (see orlg_step_rule_gn).  diag may be NULL; block_cause
  * and cause_counts as under orlg_step_assign (sap, llp and fewest-cuts refuse with a cause <= ORLG_CAUSE_ALIGNMENT only).  Runs the
  * CUT instantiation of the handle's step kernel (orlg_rmsa_kernel<.., ASSIGN, CUT> / orlg_rmsa_group_kernel<.., ASSIGN, CUT>, the
  * plain kind of either).  orlg_step_assign itself knows ORLG_NUM_ASSIGN_RULES rules and not this one. */
@@ -329,7 +329,7 @@ int orlg_path_min_cuts(orlg_env *env, int16_t *cuts, int16_t *slots);
  * orlg_step_assign serves (one of its routes, one of its rules) IS orlg_step_assign and launches what that launches; every other
  * pair runs the USAGE instantiation of the handle's step kernel (orlg_rmsa_kernel<.., ASSIGN, false, USAGE> /
  * orlg_rmsa_group_kernel<.., ASSIGN, false, USAGE>, the plain kind of either; orlg_usage.h).  ORLG_ERR_INVALID, before anything is
- * launched: a null handle, any other route or rule (ORLG_ASSIGN_FIRST included), a handle with a gn_gate.  diag may be NULL;
+ * launched: a null handle, any other route or rule (ORLG_ASSIGN_FIRST included), a handle with a gn_gate (see orlg_step_rule_gn).  diag may be NULL;
  * block_cause and cause_counts as under orlg_step_assign (sap, llp and BEST_WINDOW refuse with a cause <= ORLG_CAUSE_ALIGNMENT only). */
 int orlg_step_window(orlg_env *env, int32_t route, int32_t rule, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
                      const orlg_step_io *io, const struct orlg_step_diag *diag);
@@ -339,6 +339,39 @@ int orlg_slot_usage(orlg_env *env, uint8_t *usage);
  * window), slots [B][k] int16 (its start, S = no window).  Either may be NULL, not both.  Reads state and writes only its
  * outputs.  Buffers as orlg_action_masks. */
 int orlg_path_most_used(orlg_env *env, int32_t *usage, int16_t *slots);
+
+/* ---- assignment rules behind the GN-model admission check (not in the reference).  On a handle with a gn_gate a route
+ * and a rule propose (path, slot) exactly as orlg_step_assign / orlg_step_min_cut make them propose on a handle without one in the
+ * same state, and the proposal goes through the check described at orlg_rmsa_gn_gate: window, bandwidth, centre frequency,
+ * power, interferers and threshold as there. */
+/* the fewest-cuts window (orlg_step_min_cut's rule MIN_CUT) as a rule of the two entries below; outside the enums on purpose, as
+ * ORLG_RULE_MOST_USED */
+#define ORLG_RULE_FEWEST_CUTS 102
+/* gn_mode of orlg_step_rule_gn */
+#define ORLG_GN_MODE_CHECK 0       /* the check runs once, on the route's proposal; refused: the step is a gate refusal -- not accepted,
+                                    * act_path / act_slot show the proposal, gn_gsnr_db the value compared, cause ORLG_CAUSE_GN */
+#define ORLG_GN_MODE_NEXT_PATH 1   /* route ORLG_POLICY_SAP_FF only: the candidate paths in order; the first path that has a window AND
+                                    * whose rule window is admitted is provisioned.  Paths without a window are skipped without a
+                                    * check, each candidate is checked once.  None admitted: a refusal that shows the FIRST candidate
+                                    * checked (path, slot, GSNR); no path with a window: the rejection (k, S) with NaN.
+                                    * ORLG_POLICY_SAP_FF_GN with the rule's window in the first fit's place */
+/* orlg_step_diag under a route, a rule and the admission check.  `route`: ORLG_POLICY_SP_FF, ORLG_POLICY_SAP_FF, ORLG_POLICY_LLP_FF,
+ * ORLG_POLICY_PATH_FF_EXTERNAL (actions [B] name the path) or ORLG_ROUTE_FEWEST_CUTS; `rule`: ORLG_ASSIGN_FIRST_FULL, ORLG_ASSIGN_LAST,
+ * ORLG_ASSIGN_BEST, ORLG_ASSIGN_EXACT or ORLG_RULE_FEWEST_CUTS; `gn_mode`: ORLG_GN_MODE_*.  ORLG_ERR_INVALID, before anything is
+ * launched: a null handle or one without a gn_gate; an unknown route, rule or mode; ORLG_GN_MODE_NEXT_PATH with a route other than
+ * ORLG_POLICY_SAP_FF; ORLG_ROUTE_FEWEST_CUTS with a rule other than ORLG_RULE_FEWEST_CUTS; ORLG_ASSIGN_FIRST (that is orlg_step_gn
+ * / ORLG_POLICY_SAP_FF_GN); ORLG_RULE_MOST_USED and ORLG_ROUTE_BEST_WINDOW (not served behind a gate).  diag may be NULL; gn_gsnr_db,
+ * block_cause and cause_counts as under orlg_step_diag.  Runs orlg_rmsa_kernel<W, STATS, false, true, CAUSE, true[, true]>, the
+ * wave-per-environment kernel, at every batch size. */
+int orlg_step_rule_gn(orlg_env *env, int32_t route, int32_t rule, int32_t gn_mode, int32_t n_steps, const int32_t *actions,
+                      int32_t auto_reset, const orlg_step_io *io, const struct orlg_step_diag *diag);
+/* The rule's window of every candidate path of every pending request and what the check says to it: slots [B][k] int16 (its start,
+ * S = the path has no window), gsnr_db [B][k] float64 (the GSNR the check would compare, NaN = no window), admitted [B][k] uint8
+ * (1 iff the window exists and is admitted: the outcome of orlg_step_rule_gn(ORLG_POLICY_PATH_FF_EXTERNAL, rule, ORLG_GN_MODE_CHECK)
+ * on that path, with the bits of its gn_gsnr_db).  `rule` as above, or ORLG_ASSIGN_FIRST: the reference's first fit, the path_ff
+ * columns of orlg_gn_action_masks.  Any pointer may be NULL, not all.  ORLG_ERR_INVALID: a handle without a gn_gate, an unknown
+ * rule.  Reads state and writes only its outputs.  Buffers as orlg_action_masks. */
+int orlg_gn_path_windows(orlg_env *env, int32_t rule, int16_t *slots, double *gsnr_db, uint8_t *admitted);
 
 /* The fit level (ORLG_FIT_*) of every candidate path of every pending request: levels [B][k] uint8.  Reads state and writes
  * only `levels`; looks at windows only on every handle (it does not know a GN-model admission check).  levels == 4 is the

@@ -40,6 +40,12 @@ WINDOW_POLICIES = {"sp_mu": (POLICIES["sp_ff"], RULE_MOST_USED), "sap_mu": (POLI
                    "any_ff_full": (ROUTE_BEST_WINDOW, ASSIGN_RULES.index("first_full")),
                    "any_lf": (ROUTE_BEST_WINDOW, ASSIGN_RULES.index("last")), "any_bf": (ROUTE_BEST_WINDOW, ASSIGN_RULES.index("best")),
                    "any_ef": (ROUTE_BEST_WINDOW, ASSIGN_RULES.index("exact")), "any_mu": (ROUTE_BEST_WINDOW, RULE_MOST_USED)}
+# include/orlg.h orlg_step_rule_gn / orlg_gn_path_windows: a route and a rule behind the GN-model admission check.  The
+# fewest-cuts window as a rule of these two entries, the two modes, and the rule names the query takes.  No policy names: the
+# names of ASSIGN_POLICIES and CUT_POLICIES run through them with ``run(..., gn_rule=)``
+RULE_FEWEST_CUTS = 102
+GN_RULE_MODES = {"check": 0, "next_path": 1}
+GN_PATH_WINDOW_RULES = {"first": 0, "first_full": 1, "last": 2, "best": 3, "exact": 4, "min_cut": RULE_FEWEST_CUTS}
 
 
 def policy_ids(policy):
@@ -193,7 +199,10 @@ def _prototypes():
               # most-used windows and the best window over all paths: the step, the slot usage, every path's most-used window
               "orlg_step_window": (None, [vp, i32, i32, i32, vp, i32, P(StepIO), P(StepDiag)]),
               "orlg_slot_usage": (None, [vp, vp]),
-              "orlg_path_most_used": (None, [vp, vp, vp])})
+              "orlg_path_most_used": (None, [vp, vp, vp]),
+              # assignment rules behind the GN-model admission check: the step, every path's rule window and its GSNR
+              "orlg_step_rule_gn": (None, [vp, i32, i32, i32, i32, vp, i32, P(StepIO), P(StepDiag)]),
+              "orlg_gn_path_windows": (None, [vp, i32, vp, vp, vp])})
     # QoT-aware only
     t.update({"orlg_phy_step": (None, [vp, i32, i32, vp, vp, i32, P(PhyStepIO)]), "orlg_phy_node_vectors": (None, [vp]),
               "orlg_phy_get_episode_stats": (None, [vp, vp]), "orlg_phy_channel_masks": (None, [vp, vp]),

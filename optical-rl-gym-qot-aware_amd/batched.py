@@ -92,7 +92,7 @@ class BatchedRMSAEnv(BatchedHandle):
 
     # ------------------------------------------------------------------ stepping
     def run(self, policy: str, n_steps: int = 1, *, actions=None, auto_reset: bool = False,
-            outputs: Sequence[str] = (), out: Optional[Dict[str, object]] = None, cause_counts=None):
+            outputs: Sequence[str] = (), out: Optional[Dict[str, object]] = None, cause_counts=None, gn_rule=None):
         """``n_steps`` x (policy -> step) on the device.  ``outputs`` names per-step arrays to return
         (see ``_lib.STEP_IO_DTYPES``) as numpy arrays of shape [n_steps, B(, 4)]; ``out`` may supply
         preallocated numpy arrays or torch tensors (device tensors are written without staging).  ``"gn_gsnr_db"``: the GSNR
@@ -124,11 +124,40 @@ class BatchedRMSAEnv(BatchedHandle):
         are occupied on the most links of the whole network, ties to the lowest start), ``path_mu_external`` (``actions`` [B]
         names the path) and ``any_ff_full`` / ``any_lf`` / ``any_bf`` / ``any_ef`` / ``any_mu`` (every path proposes its rule
         window; the proposal that ranks best by the rule's own order wins, ties to the lowest path).  They run where the names
-        above run, with the same exception; :meth:`slot_usage` and :meth:`path_most_used` are the matching queries."""
+        above run, with the same exception; :meth:`slot_usage` and :meth:`path_most_used` are the matching queries.
+
+        An assignment rule behind the admission check (``orlg_step_rule_gn``; not in the reference): ``gn_rule=`` on
+        a handle with ``gn_gate=``, with a name of ``_lib.ASSIGN_POLICIES`` or ``_lib.CUT_POLICIES``.  ``"check"``: the route and
+        the rule propose what they propose without a gate, the check runs once on that window, and a refusal is a gate refusal
+        (not accepted, ``act_path`` / ``act_slot`` the proposal, ``gn_gsnr_db`` the value compared, cause ``"gn"``).
+        ``"next_path"`` (the ``sap_*`` names only): the candidate paths in order, the first one whose rule window is admitted is
+        provisioned -- ``sap_ff_gn`` with the rule's window in the first fit's place.  ``None``: everything above, unchanged.  The
+        most-used rule and the ``any_*`` routes stay without a gate.  :meth:`path_rule_windows` is the matching query."""
+        if gn_rule is not None:
+            return self._run_rule_gn(policy, n_steps, actions, auto_reset, outputs, out, cause_counts, gn_rule)
+        return self._run(policy, n_steps, actions, auto_reset, outputs, out, cause_counts)
+
+    def _run_rule_gn(self, policy, n_steps, actions, auto_reset, outputs, out, cause_counts, gn_rule):
+        """``run(..., gn_rule=)``: every refusal before the library is called."""
+        if gn_rule not in _lib.GN_RULE_MODES:
+            raise ValueError(f"gn_rule {gn_rule!r}: expected None or one of {tuple(_lib.GN_RULE_MODES)}")
+        if policy in _lib.WINDOW_POLICIES:
+            raise ValueError(f"policy {policy!r} with gn_rule=: the most-used rule and the any_* routes are not served behind a "
+                             "GN-model admission check")
+        if policy not in _lib.ASSIGN_POLICIES and policy not in _lib.CUT_POLICIES:
+            raise ValueError(f"policy {policy!r} with gn_rule=: expected a name of _lib.ASSIGN_POLICIES or _lib.CUT_POLICIES (a route "
+                             "with an assignment rule other than the reference's first fit)")
+        if self.gn_gate is None:
+            raise ValueError(f"gn_rule={gn_rule!r} needs a handle with a GN-model admission check (gn_gate=)")
+        if gn_rule == "next_path" and not policy.startswith("sap_"):
+            raise ValueError(f"gn_rule='next_path' goes on to the next candidate path: it needs a sap_* name, got {policy!r}")
+        return self._run(policy, n_steps, actions, auto_reset, outputs, out, cause_counts, _lib.GN_RULE_MODES[gn_rule])
+
+    def _run(self, policy, n_steps, actions, auto_reset, outputs, out, cause_counts, gn_mode=None):
         cut = policy in _lib.CUT_POLICIES
         window = policy in _lib.WINDOW_POLICIES
         pid, rule = (_lib.CUT_POLICIES[policy], 0) if cut else _lib.WINDOW_POLICIES[policy] if window else _lib.policy_ids(policy)
-        if (rule or cut) and self.gn_gate is not None:
+        if (rule or cut) and self.gn_gate is not None and gn_mode is None:
             raise ValueError(f"policy {policy!r}: an assignment rule other than the reference's first fit does not run on a handle "
                              "with a GN-model admission check (gn_gate=)")
         B = self.batch_size
@@ -164,7 +193,10 @@ class BatchedRMSAEnv(BatchedHandle):
         if diag or rule or cut:   # (a name of WINDOW_POLICIES has a rule)
             d = _lib.StepDiag(_ptr(diag.get("block_cause")), _ptr(diag.get("block_cause_counts")),
                               None if gsnr is None else _ptr(gsnr["gn_gsnr_db"]))
-            if cut:
+            if gn_mode is not None:
+                _lib.check(self.L.orlg_step_rule_gn(self.h, pid, _lib.RULE_FEWEST_CUTS if cut else rule, gn_mode, int(n_steps), ap,
+                                                    1 if auto_reset else 0, C.byref(io), C.byref(d)))
+            elif cut:
                 _lib.check(self.L.orlg_step_min_cut(self.h, pid, int(n_steps), ap, 1 if auto_reset else 0, C.byref(io), C.byref(d)))
             elif window:
                 _lib.check(self.L.orlg_step_window(self.h, pid, rule, int(n_steps), ap, 1 if auto_reset else 0, C.byref(io), C.byref(d)))
@@ -394,6 +426,30 @@ class BatchedRMSAEnv(BatchedHandle):
             res.append(buf)
         _lib.check(self.L.orlg_path_most_used(self.h, _ptr(res[0]), _ptr(res[1])))
         return res[0], res[1]
+
+    def path_rule_windows(self, rule, slots_out=None, gsnr_out=None, admitted_out=None):
+        """The window an assignment rule proposes on every candidate path of every env's pending request, and what the GN-model
+        admission check says to it (``orlg_gn_path_windows``; a handle with ``gn_gate=`` only): ``(slots, gsnr,
+        admitted)`` -- [B, k] int16 the window's start (``S`` = the path has none), [B, k] float64 the GSNR in dB the step would
+        compare (NaN = no window), [B, k] uint8 1 iff the window exists and is admitted.  ``rule``: ``"first"`` (the reference's
+        first fit: the ``"path_ff_gn"`` mask), ``"first_full"``, ``"last"``, ``"best"``, ``"exact"`` or ``"min_cut"``.  Row ``p`` is
+        the outcome of ``run("path_<rule>_external", actions=p, gn_rule="check")``, with the bits of its ``gn_gsnr_db``: the
+        agent's feature and mask for the path-only action space.  Reads state only; the buffers as ``out`` in
+        :meth:`action_masks`."""
+        if rule not in _lib.GN_PATH_WINDOW_RULES:
+            raise ValueError(f"rule {rule!r}: expected one of {tuple(_lib.GN_PATH_WINDOW_RULES)}")
+        if self.gn_gate is None:
+            raise ValueError("path_rule_windows needs a handle with a GN-model admission check (gn_gate=)")
+        shape = (self.batch_size, self.k_paths)
+        res = []
+        for name, buf, dt in (("slots_out", slots_out, np.int16), ("gsnr_out", gsnr_out, np.float64), ("admitted_out", admitted_out, np.uint8)):
+            if buf is None:
+                buf = np.zeros(shape, dt)
+            else:
+                _check_buffer(name, buf, shape, dt)
+            res.append(buf)
+        _lib.check(self.L.orlg_gn_path_windows(self.h, _lib.GN_PATH_WINDOW_RULES[rule], _ptr(res[0]), _ptr(res[1]), _ptr(res[2])))
+        return res[0], res[1], res[2]
 
     def simple_matrix_observation(self, out=None):
         """SimpleMatrixObservation.observation() for every env: [B, 2N + E*S] uint8 (``rmsa_env.py:940-971``)."""

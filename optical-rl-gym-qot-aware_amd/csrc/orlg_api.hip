@@ -211,7 +211,8 @@ static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
     const bool gn = p.mode == ORLG_MODE_STEP && p.gn != nullptr;
     // a launch that asks for the blocking cause: the general kernel's CAUSE instantiation, with or without the check
     const bool cause = p.mode == ORLG_MODE_STEP && (p.out_mask & ORLG_OUT_CAUSE_BIT) != 0;
-    // a launch under an assignment rule other than the reference's first fit: the general kernel's ASSIGN instantiation (no gate: refused)
+    // a launch under an assignment rule other than the reference's first fit: the general kernel's ASSIGN instantiation (behind a gate:
+    // orlg_step_rule_gn alone, every other entry refuses)
     const bool assign = p.mode == ORLG_MODE_STEP && (p.out_mask & ORLG_OUT_ASSIGN_BIT) != 0;
     const bool ff = !gn && !cause && !assign && p.mode == ORLG_MODE_STEP && p.K <= 8 && (p.policy == ORLG_POLICY_SP || p.policy == ORLG_POLICY_SAP);
     const OrlgGroupOverrides ov = group_overrides();
@@ -219,7 +220,8 @@ static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
     const OrlgWaveKey key = {ff ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel_ff)
                                 : p.mode == ORLG_MODE_STEP ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel) : ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel),
                              p.stats_level, df, gn, cause, assign, assign && p.assign == ORLG_ASSIGN_MIN_CUT, assign && usage_launch(p)};
-    rmsa_kernel_t k = orlg_pick(e->W, key);
+    // (an assignment rule behind the check, orlg_step_rule_gn: the instantiations of orlg_inst_gnrules.hip, with a lookup of their own)
+    rmsa_kernel_t k = gn && assign ? orlg_pick_gn_rules(e->W, key) : orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), e->lds_block_bytes)) return rc;
     const int wpb = e->waves_per_block;
@@ -597,24 +599,28 @@ static int extra_out(orlg_env *e, ExtraOut *o, void *user, size_t bytes, int slo
 // orlg_step, orlg_step_gn, orlg_step_diag, orlg_step_assign and orlg_step_min_cut (gsnr, cause, counts: the outputs beyond
 // orlg_step_io, nullptr = not asked for; assign: ORLG_ASSIGN_*, 0 = the reference's first fit, or the device's own
 // ORLG_ASSIGN_MIN_CUT, which only orlg_step_min_cut passes, with own_entry = 1 -- `policy` may then be the device's ORLG_POLICY_MIN_CUT;
-// own_entry = 2: orlg_step_window, which has checked its route and rule itself -- the device's ORLG_ASSIGN_MOST_USED and ORLG_POLICY_BEST_WINDOW)
+// own_entry = 2: orlg_step_window, which has checked its route and rule itself -- the device's ORLG_ASSIGN_MOST_USED and ORLG_POLICY_BEST_WINDOW;
+// own_entry = 3: orlg_step_rule_gn, which has checked route, rule, mode and the gate itself -- a rule up to ORLG_ASSIGN_MIN_CUT on a
+// gated handle, `policy` a route, the device's ORLG_POLICY_MIN_CUT, or ORLG_POLICY_SAP_GN = route sap that goes on to the next path)
 static int rmsa_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
                      const orlg_step_io *io, double *gsnr, uint8_t *cause = nullptr, int32_t *counts = nullptr, int32_t assign = ORLG_ASSIGN_FIRST,
                      int own_entry = 0) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     if (n_steps < 1) return fail(ORLG_ERR_INVALID, "n_steps must be >= 1");
     const bool min_cut_entry = own_entry == 1;
-    const bool cut_route = (min_cut_entry && policy == ORLG_POLICY_MIN_CUT) || (own_entry == 2 && policy == ORLG_POLICY_BEST_WINDOW);
+    const bool gn_entry = own_entry == 3;
+    const bool cut_route = ((min_cut_entry || gn_entry) && policy == ORLG_POLICY_MIN_CUT) || (own_entry == 2 && policy == ORLG_POLICY_BEST_WINDOW);
     if (!cut_route && (policy < ORLG_POLICY_EXTERNAL || policy > ORLG_POLICY_SAP_FF_GN)) return fail(ORLG_ERR_INVALID, "unknown policy %d", policy);
     if (policy == ORLG_POLICY_SAP_FF_GN && !e->p.gn)
         return fail(ORLG_ERR_INVALID, "policy %d (sap_ff_gn) asks the GN-model admission check: the handle has no gn_gate", policy);
     // an assignment rule other than the reference's first fit: the policy is a route, the handle has no gate -- before anything is launched
     // (the public rules; ORLG_ASSIGN_MIN_CUT comes from orlg_step_min_cut alone and is an unknown rule to every other caller)
-    if (assign < ORLG_ASSIGN_FIRST || assign >= (own_entry == 2 ? ORLG_ASSIGN_MOST_USED + 1 : min_cut_entry ? ORLG_ASSIGN_MIN_CUT + 1 : ORLG_NUM_ASSIGN_RULES)) return fail(ORLG_ERR_INVALID, "unknown assignment rule %d", assign);
+    if (assign < ORLG_ASSIGN_FIRST || assign >= (own_entry == 2 ? ORLG_ASSIGN_MOST_USED + 1 : (min_cut_entry || gn_entry) ? ORLG_ASSIGN_MIN_CUT + 1 : ORLG_NUM_ASSIGN_RULES)) return fail(ORLG_ERR_INVALID, "unknown assignment rule %d", assign);
     if (assign != ORLG_ASSIGN_FIRST) {
-        if (!cut_route && policy != ORLG_POLICY_SP_FF && policy != ORLG_POLICY_SAP_FF && policy != ORLG_POLICY_LLP_FF && policy != ORLG_POLICY_PATH_FF_EXTERNAL)
+        if (!cut_route && policy != ORLG_POLICY_SP_FF && policy != ORLG_POLICY_SAP_FF && policy != ORLG_POLICY_LLP_FF && policy != ORLG_POLICY_PATH_FF_EXTERNAL &&
+            !(gn_entry && policy == ORLG_POLICY_SAP_GN))
             return fail(ORLG_ERR_INVALID, "assignment rule %d needs a route (sp_ff, sap_ff, llp_ff or path_ff_external): policy %d names its own slot or block", assign, policy);
-        if (e->p.gn) return fail(ORLG_ERR_INVALID, "assignment rule %d on a handle with a gn_gate: the admission check knows the reference's first fit only", assign);
+        if (e->p.gn && !gn_entry) return fail(ORLG_ERR_INVALID, "assignment rule %d on a handle with a gn_gate: this entry runs no rule behind the admission check, orlg_step_rule_gn does", assign);
     }
     const bool ext = policy == ORLG_POLICY_EXTERNAL || policy == ORLG_POLICY_DEEPRMSA_EXTERNAL || policy == ORLG_POLICY_PATH_FF_EXTERNAL;
     if (ext && (!actions || n_steps != 1)) return fail(ORLG_ERR_INVALID, "external actions need an action array and n_steps == 1");
@@ -708,7 +714,7 @@ int orlg_step_min_cut(orlg_env *e, int32_t route, int32_t n_steps, const int32_t
     if (route != ORLG_POLICY_SP_FF && route != ORLG_POLICY_SAP_FF && route != ORLG_POLICY_LLP_FF && route != ORLG_POLICY_PATH_FF_EXTERNAL &&
         route != ORLG_ROUTE_FEWEST_CUTS)
         return fail(ORLG_ERR_INVALID, "the fewest-cuts window needs a route (sp_ff, sap_ff, llp_ff, path_ff_external or ORLG_ROUTE_FEWEST_CUTS): got %d", route);
-    if (e->p.gn) return fail(ORLG_ERR_INVALID, "the fewest-cuts window on a handle with a gn_gate: the admission check knows the reference's first fit only");
+    if (e->p.gn) return fail(ORLG_ERR_INVALID, "the fewest-cuts window on a handle with a gn_gate: this entry runs no rule behind the admission check, orlg_step_rule_gn does");
     const int32_t policy = route == ORLG_ROUTE_FEWEST_CUTS ? (int32_t)ORLG_POLICY_MIN_CUT : route;
     if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr, nullptr, nullptr, ORLG_ASSIGN_MIN_CUT, 1);
     return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, ORLG_ASSIGN_MIN_CUT, 1);
@@ -722,12 +728,39 @@ int orlg_step_window(orlg_env *e, int32_t route, int32_t rule, int32_t n_steps, 
         return fail(ORLG_ERR_INVALID, "orlg_step_window needs a route (sp_ff, sap_ff, llp_ff, path_ff_external or ORLG_ROUTE_BEST_WINDOW): got %d", route);
     if (!old_rule && rule != ORLG_RULE_MOST_USED)
         return fail(ORLG_ERR_INVALID, "orlg_step_window needs a rule (ORLG_ASSIGN_FIRST_FULL, LAST, BEST, EXACT or ORLG_RULE_MOST_USED): got %d", rule);
-    if (e->p.gn) return fail(ORLG_ERR_INVALID, "orlg_step_window on a handle with a gn_gate: the admission check knows the reference's first fit only");
+    if (e->p.gn) return fail(ORLG_ERR_INVALID, "orlg_step_window on a handle with a gn_gate: this entry runs no rule behind the admission check (orlg_step_rule_gn does, for the rules and routes other than MOST_USED and BEST_WINDOW)");
     if (old_route && old_rule) return orlg_step_assign(e, route, rule, n_steps, actions, auto_reset, io, diag);   // what that launches
     const int32_t policy = route == ORLG_ROUTE_BEST_WINDOW ? (int32_t)ORLG_POLICY_BEST_WINDOW : route;
     const int32_t assign = rule == ORLG_RULE_MOST_USED ? (int32_t)ORLG_ASSIGN_MOST_USED : rule;
     if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr, nullptr, nullptr, assign, 2);
     return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, assign, 2);
+}
+// a route and a rule behind the admission check: everything is checked here, rmsa_step then launches a GN x ASSIGN instantiation
+int orlg_step_rule_gn(orlg_env *e, int32_t route, int32_t rule, int32_t gn_mode, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
+                      const orlg_step_io *io, const struct orlg_step_diag *diag) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: the handle has no gn_gate (orlg_step_assign, orlg_step_min_cut serve it)");
+    if (route == ORLG_ROUTE_BEST_WINDOW || rule == ORLG_RULE_MOST_USED)
+        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: the rule MOST_USED and the route BEST_WINDOW are not served behind a gn_gate (route %d, rule %d)", route, rule);
+    if (route != ORLG_POLICY_SP_FF && route != ORLG_POLICY_SAP_FF && route != ORLG_POLICY_LLP_FF && route != ORLG_POLICY_PATH_FF_EXTERNAL &&
+        route != ORLG_ROUTE_FEWEST_CUTS)
+        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn needs a route (sp_ff, sap_ff, llp_ff, path_ff_external or ORLG_ROUTE_FEWEST_CUTS): got %d", route);
+    if (rule == ORLG_ASSIGN_FIRST)
+        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: rule ORLG_ASSIGN_FIRST is the reference's first fit, which orlg_step_gn runs behind the gate");
+    const bool old_rule = rule == ORLG_ASSIGN_FIRST_FULL || rule == ORLG_ASSIGN_LAST || rule == ORLG_ASSIGN_BEST || rule == ORLG_ASSIGN_EXACT;
+    if (!old_rule && rule != ORLG_RULE_FEWEST_CUTS)
+        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn needs a rule (ORLG_ASSIGN_FIRST_FULL, LAST, BEST, EXACT or ORLG_RULE_FEWEST_CUTS): got %d", rule);
+    if (gn_mode != ORLG_GN_MODE_CHECK && gn_mode != ORLG_GN_MODE_NEXT_PATH)
+        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: unknown gn_mode %d (ORLG_GN_MODE_CHECK or ORLG_GN_MODE_NEXT_PATH)", gn_mode);
+    if (gn_mode == ORLG_GN_MODE_NEXT_PATH && route != ORLG_POLICY_SAP_FF)
+        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: ORLG_GN_MODE_NEXT_PATH goes with the route sap_ff only: got route %d", route);
+    if (route == ORLG_ROUTE_FEWEST_CUTS && rule != ORLG_RULE_FEWEST_CUTS)
+        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: the route ORLG_ROUTE_FEWEST_CUTS ranks fewest-cuts windows, it needs the rule ORLG_RULE_FEWEST_CUTS: got %d", rule);
+    const int32_t policy = route == ORLG_ROUTE_FEWEST_CUTS ? (int32_t)ORLG_POLICY_MIN_CUT
+                           : gn_mode == ORLG_GN_MODE_NEXT_PATH ? (int32_t)ORLG_POLICY_SAP_GN : route;
+    const int32_t assign = rule == ORLG_RULE_FEWEST_CUTS ? (int32_t)ORLG_ASSIGN_MIN_CUT : rule;
+    if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr, nullptr, nullptr, assign, 3);
+    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, assign, 3);
 }
 
 int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
@@ -1096,6 +1129,35 @@ int orlg_gn_action_masks(orlg_env *e, uint8_t *path_ff, double *path_ff_gsnr_db,
                        reinterpret_cast<double *>(slots[3].dev), e->allow_rejection);
     HIP_TRY(hipGetLastError());
     return collect_outputs(e, slots, 4);
+}
+
+int orlg_gn_path_windows(orlg_env *e, int32_t rule, int16_t *slots_out, double *gsnr_db, uint8_t *admitted) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!slots_out && !gsnr_db && !admitted) return fail(ORLG_ERR_INVALID, "null argument: no slots, GSNR or admitted buffer");
+    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn path windows: the handle has no gn_gate");
+    if ((rule < ORLG_ASSIGN_FIRST || rule >= ORLG_NUM_ASSIGN_RULES) && rule != ORLG_RULE_FEWEST_CUTS)
+        return fail(ORLG_ERR_INVALID, "gn path windows: unknown rule %d (ORLG_ASSIGN_FIRST .. EXACT or ORLG_RULE_FEWEST_CUTS)", rule);
+    HIP_TRY(hipSetDevice(e->device));
+    const OrlgParams &p = e->p;
+    const size_t bk = (size_t)p.B * p.K;
+    OutSlot slots[3] = {{slots_out, bk * sizeof(int16_t)}, {gsnr_db, bk * sizeof(double)}, {admitted, bk}};
+    int rc = place_outputs(e, slots, 3);
+    if (rc) return rc;
+    orlg_gn_path_windows_kernel_t k = orlg_pick_gn_path_windows(e->W);
+    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
+    // as orlg_gn_action_masks: a wave holds its environment's occupancy row and the live descriptors of its release ring
+    const size_t per_wave = (size_t)((p.NW * 8 + 15) & ~15) + (size_t)((p.Q * 4 + 15) & ~15);
+    int wpb = e->waves_per_block;
+    while (wpb > 1 && (size_t)p.l_shared_bytes + per_wave * wpb > ORLG_LDS_BYTES) --wpb;
+    const size_t lds = (size_t)p.l_shared_bytes + per_wave * wpb;
+    if (lds > ORLG_LDS_BYTES) return fail(ORLG_ERR_INVALID, "gn path windows: a release queue of %d entries does not fit the LDS next to the tables", p.Q);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int nblocks = (p.B + wpb - 1) / wpb;
+    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;
+    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, rule == ORLG_RULE_FEWEST_CUTS ? (int)ORLG_ASSIGN_MIN_CUT : (int)rule,
+                       reinterpret_cast<int16_t *>(slots[0].dev), reinterpret_cast<double *>(slots[1].dev), reinterpret_cast<uint8_t *>(slots[2].dev));
+    HIP_TRY(hipGetLastError());
+    return collect_outputs(e, slots, 3);
 }
 
 int orlg_simple_matrix_obs_dim(orlg_env *e) { return e ? 2 * e->p.N + e->p.E * e->p.S : ORLG_ERR_INVALID; }

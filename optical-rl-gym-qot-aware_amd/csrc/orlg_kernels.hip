@@ -63,6 +63,9 @@
 // (OrlgParams::assign == ORLG_ASSIGN_MOST_USED, OrlgParams::policy == ORLG_POLICY_BEST_WINDOW): wave_window_assign (orlg_usage.h)
 // stands where wave_assign stands, and the environment's prefix sums of the slot usage lie in LDS BEHIND the workgroup's wave
 // regions (ORLG_USAGE_BYTES(W) per wave; the launch asks for them), so that no other launch's layout changes.
+// GN with ASSIGN (and CUT): orlg_step_rule_gn -- the rule's window, or the fewest-cuts window, goes through the check of
+// SEC(3) like any other proposal.  Its mode next-path arrives as the policy ORLG_POLICY_SAP_GN: route sap from the first path the
+// check has not refused yet, with sap_ff_gn's retry.  These instantiations live in orlg_inst_gnrules.hip; USAGE has none.
 template <bool GN>
 struct SapRetry {
     int from = 0, path = 0, slot = 0;
@@ -245,15 +248,22 @@ DEV void rmsa_body(const OrlgParams &p) {
             if constexpr (ASSIGN) {
                 KernargParams kq = kernarg_params();
                 const int given = policy == ORLG_POLICY_PATH_EXT ? uni(kq->actions[env]) : 0;
+                // GN (orlg_step_rule_gn): the rule's window goes through the check of SEC(3).  Mode next-path arrives as
+                // the device policy SAP_GN: route sap over the candidate paths from sap.from on -- the paths below it have been
+                // refused in this step -- which the rules see as a pair with fewer paths, numbered from 0
+                int route = policy, first = 0;
+                if constexpr (GN) {
+                    if (policy == ORLG_POLICY_SAP_GN) { route = ORLG_POLICY_SAP; first = sap.from; }
+                }
                 // (CUT: the fewest-cuts window, with a hop loop of its own, in the rules' place)
                 int got;
-                if constexpr (CUT) got = wave_cut_assign<W>(wv.occ, tb, base, K, S, req_br, lane, policy, given);
+                if constexpr (CUT) got = wave_cut_assign<W>(wv.occ, tb, base + first, K - first, S, req_br, lane, route, given);
                 else if constexpr (USAGE)
                     got = wave_window_assign<W>(wv.occ, reinterpret_cast<int32_t *>(smem + p.l_shared_bytes + (size_t)(blockDim.x >> 6) * p.l_wave_bytes +
                                                                                     (size_t)wib * ORLG_USAGE_BYTES(W)),
                                                 tb, base, K, E, S, req_br, lane, policy, kq->assign, given);
-                else got = wave_assign<W>(wv.occ, tb, base, K, S, req_br, lane, policy, kq->assign, given);
-                if (got >= 0) { a_path = got >> 10; a_slot = got & 1023; }
+                else got = wave_assign<W>(wv.occ, tb, base + first, K - first, S, req_br, lane, route, kq->assign, given);
+                if (got >= 0) { a_path = (got >> 10) + first; a_slot = got & 1023; }
             } else if (FF) {
                 const int kmax = policy == ORLG_POLICY_SP ? 1 : K;
                 const bool on = pp < kmax && pw < W;

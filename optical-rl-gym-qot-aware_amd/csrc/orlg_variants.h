@@ -75,6 +75,16 @@ inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
 #define ORLG_WAVE_USAGE_KEYS(X)                                                                                                                                   \
     X(orlg_rmsa_kernel, 1, false, false, false, true, false, true) X(orlg_rmsa_kernel, 2, false, false, false, true, false, true) X(orlg_rmsa_kernel, 0, false, false, false, true, false, true) \
     X(orlg_rmsa_kernel, 1, false, false, true, true, false, true) X(orlg_rmsa_kernel, 2, false, false, true, true, false, true) X(orlg_rmsa_kernel, 0, false, false, true, true, false, true)
+// X(kernel, STATS, DEFER, GN, CAUSE, ASSIGN[, CUT]): what orlg_step_rule_gn launches -- the ASSIGN keys and the CUT
+// keys again with GN: an assignment rule, or the fewest-cuts window, whose proposal goes through the admission check.  No USAGE
+// (refused).  Lists of their own, and a unit of its own (orlg_inst_gnrules.hip, one object per W, lookup orlg_gnrules_kernel_W<n>):
+// the orlg_inst_wave objects hold what they held.
+#define ORLG_WAVE_GN_ASSIGN_KEYS(X)                                                                                                    \
+    X(orlg_rmsa_kernel, 1, false, true, false, true) X(orlg_rmsa_kernel, 2, false, true, false, true) X(orlg_rmsa_kernel, 0, false, true, false, true) \
+    X(orlg_rmsa_kernel, 1, false, true, true, true) X(orlg_rmsa_kernel, 2, false, true, true, true) X(orlg_rmsa_kernel, 0, false, true, true, true)
+#define ORLG_WAVE_GN_CUT_KEYS(X)                                                                                                                   \
+    X(orlg_rmsa_kernel, 1, false, true, false, true, true) X(orlg_rmsa_kernel, 2, false, true, false, true, true) X(orlg_rmsa_kernel, 0, false, true, false, true, true) \
+    X(orlg_rmsa_kernel, 1, false, true, true, true, true) X(orlg_rmsa_kernel, 2, false, true, true, true, true) X(orlg_rmsa_kernel, 0, false, true, true, true, true)
 
 // X(STATS, HBMQ, DEFER, TRAFFIC, TRACE).  Per kind of handle: every statistics level, the same with the release queue left in HBM
 // (launches of very few steps), and full statistics with the link updates deferred (long launches).  The kinds: plain, with
@@ -148,6 +158,8 @@ inline constexpr OrlgWaveKey ORLG_WAVE_CAUSE_KEY_LIST[] = {ORLG_WAVE_CAUSE_KEYS(
 inline constexpr OrlgWaveKey ORLG_WAVE_ASSIGN_KEY_LIST[] = {ORLG_WAVE_ASSIGN_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgWaveKey ORLG_WAVE_CUT_KEY_LIST[] = {ORLG_WAVE_CUT_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgWaveKey ORLG_WAVE_USAGE_KEY_LIST[] = {ORLG_WAVE_USAGE_KEYS(ORLG_WAVE_KEY_ENTRY)};
+inline constexpr OrlgWaveKey ORLG_WAVE_GN_ASSIGN_KEY_LIST[] = {ORLG_WAVE_GN_ASSIGN_KEYS(ORLG_WAVE_KEY_ENTRY)};
+inline constexpr OrlgWaveKey ORLG_WAVE_GN_CUT_KEY_LIST[] = {ORLG_WAVE_GN_CUT_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_KEY_LIST[] = {ORLG_GROUP_KEYS(ORLG_GROUP_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_CAUSE_KEY_LIST[] = {ORLG_GROUP_CAUSE_KEYS(ORLG_GROUP_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_ASSIGN_KEY_LIST[] = {ORLG_GROUP_ASSIGN_KEYS(ORLG_GROUP_KEY_ENTRY)};
@@ -202,6 +214,7 @@ typedef void (*orlg_gn_action_masks_kernel_t)(const OrlgParams, uint8_t *, doubl
 typedef void (*orlg_fit_levels_kernel_t)(const OrlgParams, uint8_t *);                         // orlg_fit_levels_kernel
 typedef void (*orlg_min_cuts_kernel_t)(const OrlgParams, int16_t *, int16_t *);                // orlg_min_cuts_kernel
 typedef void (*orlg_usage_kernel_t)(const OrlgParams, uint8_t *, int32_t *, int16_t *);     // orlg_usage_kernel
+typedef void (*orlg_gn_path_windows_kernel_t)(const OrlgParams, int, int16_t *, double *, uint8_t *);   // orlg_gn_path_windows_kernel
 typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
 #define ORLG_FOR_EACH_W(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__) X(6, __VA_ARGS__) X(8, __VA_ARGS__)
 #define ORLG_FOR_EACH_PHY_W(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__)
@@ -214,6 +227,8 @@ typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
     orlg_fit_levels_kernel_t orlg_fit_levels_kernel_W##n() __attribute__((weak));                 \
     orlg_min_cuts_kernel_t orlg_min_cuts_kernel_W##n() __attribute__((weak));                     \
     orlg_usage_kernel_t orlg_usage_kernel_W##n() __attribute__((weak));                           \
+    orlg_rmsa_kernel_t orlg_gnrules_kernel_W##n(OrlgWaveKey) __attribute__((weak));   /* orlg_inst_gnrules.hip */ \
+    orlg_gn_path_windows_kernel_t orlg_gn_path_windows_kernel_W##n() __attribute__((weak));       \
     orlg_rmsa_kernel_t orlg_group_kernel_W##n(OrlgGroupKey) __attribute__((weak));
 #define ORLG_DECL_PHY_W(n, ...)                                                                   \
     orlg_phy_kernel_t orlg_phy_kernel_W##n(OrlgPhyKey) __attribute__((weak));                     \
@@ -227,6 +242,9 @@ ORLG_FOR_EACH_PHY_W(ORLG_DECL_PHY_W, )
 #define ORLG_PICK_CASE(n, lookup, ...) case n: return lookup##n ? lookup##n(__VA_ARGS__) : nullptr;
 #define ORLG_PICK(FOR_EACH_W, W, lookup, ...) switch (W) { FOR_EACH_W(ORLG_PICK_CASE, lookup, __VA_ARGS__) default: return nullptr; }
 static orlg_rmsa_kernel_t orlg_pick(int W, const OrlgWaveKey &key) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_wave_kernel_W, key) }
+// the GN x ASSIGN keys (ORLG_WAVE_GN_ASSIGN_KEYS, ORLG_WAVE_GN_CUT_KEYS): a lookup of their own -- orlg_pick answers for the keys it
+// always answered for, and with null for these
+static orlg_rmsa_kernel_t orlg_pick_gn_rules(int W, const OrlgWaveKey &key) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gnrules_kernel_W, key) }
 static orlg_rmsa_kernel_t orlg_pick(int W, const OrlgGroupKey &key) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_group_kernel_W, key) }
 static orlg_phy_kernel_t orlg_pick(int W, const OrlgPhyKey &key) {   // the TRACE instantiations are objects of their own
     if (key.TRACE) { ORLG_PICK(ORLG_FOR_EACH_PHY_W, W, orlg_phy_trace_kernel_W, key) }
@@ -239,3 +257,4 @@ static orlg_fit_levels_kernel_t orlg_pick_fit_levels(int W) { ORLG_PICK(ORLG_FOR
 static orlg_min_cuts_kernel_t orlg_pick_min_cuts(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_min_cuts_kernel_W, ) }
 static orlg_usage_kernel_t orlg_pick_usage(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_usage_kernel_W, ) }
 static orlg_gn_action_masks_kernel_t orlg_pick_gn_action_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_action_masks_kernel_W, ) }
+static orlg_gn_path_windows_kernel_t orlg_pick_gn_path_windows(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_path_windows_kernel_W, ) }

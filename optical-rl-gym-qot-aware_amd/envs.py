@@ -588,18 +588,48 @@ def assignment_slot(available, n, rule):
     raise ValueError(f"rule {rule!r}: expected one of {_lib.ASSIGN_RULES}")
 
 
-def assignment_heuristic(route, rule):
+def _gn_mode(route, gn):
+    """The ``gn=`` argument of the heuristics below, checked."""
+    if gn not in (None, "check", "next_path"):
+        raise ValueError(f"gn {gn!r}: expected None, 'check' or 'next_path'")
+    if gn == "next_path" and route != "sap":
+        raise ValueError(f"gn='next_path' goes on to the next candidate path: it needs route 'sap', got {route!r}")
+    return gn
+
+
+def _next_path_action(env, rule):
+    """What ``run("sap_<rule>", gn_rule="next_path")`` proposes for the pending request of a ``gn_gate=`` view, read from the
+    handle's query ``path_rule_windows(rule)``: the first path whose rule window the admission check admits; none admitted: the
+    first path that has a window, which the step then refuses as the device's step is refused; no window: the rejection."""
+    S, k = env.topology.graph["num_spectrum_resources"], env.topology.graph["k_paths"]
+    slots, _, admitted = env._batched.path_rule_windows(rule)
+    ok, has = np.flatnonzero(admitted[env._index]), np.flatnonzero(slots[env._index] < S)
+    if has.size == 0:
+        return [k, S]
+    idp = int(ok[0] if ok.size else has[0])
+    return [idp, int(slots[env._index, idp])]
+
+
+def assignment_heuristic(route, rule, gn=None):
     """A heuristic ``f(env) -> [path, slot]`` in the drop-in callback shape of ``shortest_available_path_first_fit``: route
     ``"sp"`` (path 0), ``"sap"`` (the first path that has a window) or ``"llp"`` (of the paths that have a window the one with
     the most free slots, strict ``>``; ``rmsa_env.py:854-937``) with assignment rule ``rule`` of ``ASSIGN_RULES`` on it.  Not in
     the reference beyond ``rule="first"``; what the device policies ``{sp,sap,llp}_{ff,ff_full,lf,bf,ef}`` propose, written on
-    the view's own ``get_available_slots`` / ``get_number_slots``."""
+    the view's own ``get_available_slots`` / ``get_number_slots``.
+
+    ``gn=`` (a ``gn_gate=`` view): ``"check"`` -- what ``run(name, gn_rule="check")`` proposes, which is the proposal
+    above (the view's step applies the check); ``"next_path"`` (route ``"sap"``, a rule other than ``"first"``) -- what
+    ``run(name, gn_rule="next_path")`` proposes, read from the handle's ``path_rule_windows(rule)``."""
     if route not in ("sp", "sap", "llp"):
         raise ValueError(f"route {route!r}: expected 'sp', 'sap' or 'llp'")
     if rule not in _lib.ASSIGN_RULES:
         raise ValueError(f"rule {rule!r}: expected one of {_lib.ASSIGN_RULES}")
+    if _gn_mode(route, gn) is not None and rule == "first":
+        raise ValueError("gn=: rule 'first' is the reference's first fit (shortest_available_path_first_fit_gn goes on to the next path)")
 
     def heuristic(env):
+        if gn == "next_path":
+            return _next_path_action(env, rule)
         S, k = env.topology.graph["num_spectrum_resources"], env.topology.graph["k_paths"]
         paths = env.k_shortest_paths[env.current_service.source, env.current_service.destination]
         best, action = 0, [k, S]
@@ -637,18 +667,22 @@ def _min_cut_slot(rows, n):
     return best
 
 
-def min_cut_heuristic(route):
+def min_cut_heuristic(route, gn=None):
     """A heuristic ``f(env) -> [path, slot]`` for ``RMSA-v0`` in the drop-in callback shape of
     ``shortest_available_path_first_fit``: the window with the fewest cuts on route ``"sp"`` (path 0), ``"sap"`` (the first path
     that has a window), ``"llp"`` (of the paths that have a window the one with the most free slots, strict ``>``) or
     ``"min_cut"`` (of all paths the one whose fewest-cuts window has the fewest cuts, ties to the lowest path).  Not in the
     reference for this environment (its ``calculate_r_cut`` belongs to the QoT-aware one); what the device policies
     ``sp_mc`` / ``sap_mc`` / ``llp_mc`` / ``min_cut`` propose, written on what the view exposes: the rows of
-    ``topology.graph["available_slots"]``, the link indices along a path's ``node_list`` and ``get_number_slots``."""
+    ``topology.graph["available_slots"]``, the link indices along a path's ``node_list`` and ``get_number_slots``.
+    ``gn=``: as :func:`assignment_heuristic` (``"next_path"`` reads ``path_rule_windows("min_cut")``)."""
     if route not in ("sp", "sap", "llp", "min_cut"):
         raise ValueError(f"route {route!r}: expected 'sp', 'sap', 'llp' or 'min_cut'")
+    _gn_mode(route, gn)
 
     def heuristic(env):
+        if gn == "next_path":
+            return _next_path_action(env, "min_cut")
         S, k = env.topology.graph["num_spectrum_resources"], env.topology.graph["k_paths"]
         paths = env.k_shortest_paths[env.current_service.source, env.current_service.destination]
         avail = env.topology.graph["available_slots"]

@@ -122,7 +122,7 @@ class _Evaluation:
 def evaluate_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, monitor_path: Optional[str] = None,
                                env_id: str = "RMSA-v0", info_keywords: Sequence[str] = RMSA_INFO_KEYWORDS,
                                chunk: int = 1000, monitor_dir: Optional[str] = None, monitor_name: Optional[str] = None,
-                               by_group: bool = False):
+                               by_group: bool = False, gn_rule=None):
     """Run ``n_eval_episodes`` episodes of ``policy`` on every env of a :class:`BatchedRMSAEnv` with the reference
     loop's semantics: ``env.reset()`` (episode counters only) before every episode, step until ``done``.  Returns
     (episode_rewards [episodes, B], episode_lengths [episodes, B], per-episode info arrays); optionally writes one
@@ -132,9 +132,11 @@ def evaluate_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, moni
     ``{monitor_dir}/logs_{load:g}_{episode_length}/{monitor_name}.monitor.csv`` (``monitor_name`` defaults to ``policy``).
     ``by_group=True`` adds a fourth return value (whatever the output paths): per group its load and, [episodes, G] each, the
     mean blocking rates with their standard error over the group's seeds, formed from ``reduce_counters(by_group=True)``.
-    Both need every group to be one load (``ValueError`` otherwise)."""
+    Both need every group to be one load (``ValueError`` otherwise).  ``gn_rule``: passed on to ``env.run`` (an assignment rule
+    behind the GN-model admission check of a ``gn_gate=`` handle)."""
     B = env.batch_size
     ev = _Evaluation(env, info_keywords, monitor_dir, by_group)
+    kw = {} if gn_rule is None else {"gn_rule": gn_rule}
     for _ in range(n_eval_episodes):
         env.reset(only_episode_counters=True)
         ep_r = np.zeros(B)
@@ -145,7 +147,7 @@ def evaluate_heuristic_batched(env, policy: str, n_eval_episodes: int = 10, moni
         left = env.episode_length - 1
         while left > 0:
             n = min(left, chunk)
-            out = env.run(policy, n, outputs=("reward", "done"))
+            out = env.run(policy, n, outputs=("reward", "done"), **kw)
             ep_r += out["reward"].sum(axis=0)
             ep_l += n
             left -= n
