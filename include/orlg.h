@@ -220,6 +220,37 @@ int orlg_set_gn_gate(orlg_env *env, const orlg_rmsa_gn_gate *gate);
 int orlg_step_gn(orlg_env *env, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
                  const orlg_step_io *io, double *gn_gsnr_db);
 
+/* ---- a gate that protects the running lightpaths (this project's; off by default).  In the GN model every service is
+ * an interferer of every other service on a shared link: a candidate that closes its own budget can still push a neighbour below
+ * the threshold of the neighbour's modulation.  With protection on, the check above runs as before and gives the same gn_gsnr_db;
+ * a candidate that passes it meets a second check before _provision_path.
+ * AFFECTED: the running services of the environment (the release queue's entries) whose path shares at least one link with the
+ * candidate's.  For each affected service i, calculate_osnr.py:9-56 is evaluated for i over the links of ITS path, with i's window,
+ * bandwidth n_i D, centre f0 + (s_i + n_i / 2) D and launch power density * n_i D as above; the interferers of a link of i are the
+ * other running services whose path contains the link, plus the candidate (calculate_osnr.py:33-45, one more term) where its path
+ * contains it.  i itself is in no list.  margin_i = GSNR_i - thresholds_db[SE_i - 1]; the step's NEIGHBOUR MARGIN is the minimum
+ * over all affected services (no early exit).  Admitted iff the candidate passes its own check AND the neighbour margin is >= 0;
+ * without an affected service the second condition holds.  A refusal by either check is the gate's refusal as described above (not
+ * accepted, the rejection's reward, nothing provisioned, no queue entry, act_path / act_slot the proposal) with cause
+ * ORLG_CAUSE_GN.  ORLG_POLICY_SAP_FF_GN goes on to the next path after a refusal by EITHER check, each candidate checked once; when
+ * the paths end the step is the refusal of the first candidate, with that candidate's gn_gsnr_db and neighbour margin (NaN if its
+ * own check refused it).
+ * A running lightpath may sit below its threshold without any newcomer: a release can move a neighbour's sum either way, and a
+ * snapshot of a handle that does not protect can be loaded.  Nothing is torn down then; every candidate that touches such a
+ * lightpath is refused while it lasts.
+ * Protection is configuration, not state: snapshots cross between protecting, gated and ungated handles.  Every step entry point
+ * applies it on a protecting handle (as orlg_step applies the gate); such a handle runs orlg_rmsa_kernel<W,STATS,false,true,CAUSE,
+ * false,false,false,true>.  orlg_gn_action_masks, orlg_step_rule_gn and orlg_gn_path_windows know the candidate's own check only:
+ * on a protecting handle they would describe a step the handle does not run and return ORLG_ERR_INVALID.
+ * orlg_set_gn_protect: ORLG_ERR_INVALID on a handle without a gate; orlg_set_gn_gate(env, NULL) clears it, a new gate keeps it. */
+int orlg_set_gn_protect(orlg_env *env, int32_t on);
+struct orlg_step_diag;
+/* orlg_step_diag plus one more per-step output: gn_neighbour_margin_db [n_steps][B] float64 = the neighbour margin in dB, NaN where
+ * the second check did not run (no own check ran, the own check refused, no running service shares a link; all NaN on a handle that
+ * does not protect).  Every pointer may be NULL; buffers as the other per-step outputs. */
+int orlg_step_gn_protect(orlg_env *env, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
+                         const orlg_step_io *io, const struct orlg_step_diag *diag, double *gn_neighbour_margin_db);
+
 /* ---- why a request was refused (not in the reference).  Both definitions look only at the occupancy the step met,
  * at `accepted` and at whether the GN-model admission check refused; they are the same for every policy and every action.
  * For the pending request, n = get_number_slots(p) of candidate path p (links l_1..l_h), free(l) = the free slots of link l:

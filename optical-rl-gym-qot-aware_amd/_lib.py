@@ -186,6 +186,9 @@ def _prototypes():
               # GN-model admission check inside the step
               "orlg_set_gn_gate": (None, [vp, P(RmsaGnGate)]),
               "orlg_step_gn": (None, [vp, i32, i32, vp, i32, P(StepIO), vp]),
+              # ... that also protects the running lightpaths: the switch, and the step with the neighbour margin
+              "orlg_set_gn_protect": (None, [vp, i32]),
+              "orlg_step_gn_protect": (None, [vp, i32, i32, vp, i32, P(StepIO), P(StepDiag), vp]),
               # valid-action masks that know the admission check
               "orlg_gn_action_masks": (None, [vp, vp, vp, vp, vp]),
               # blocking cause per step, fit level per candidate path

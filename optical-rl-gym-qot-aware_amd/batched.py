@@ -79,9 +79,16 @@ class BatchedRMSAEnv(BatchedHandle):
             gg.thresholds_db, gg.num_thresholds = self._keep_array(g["thresholds_db"], np.float64), len(g["thresholds_db"])
             try:
                 _lib.check(self.L.orlg_set_gn_gate(self.h, C.byref(gg)))
+                if self.gn_protect:
+                    _lib.check(self.L.orlg_set_gn_protect(self.h, 1))
             except Exception:
                 self.close()
                 raise
+
+    @property
+    def gn_protect(self):
+        """The gate also protects the running lightpaths (``rmsa_gn_gate_parameters(protect_running=True)``)."""
+        return bool(self.gn_gate and self.gn_gate.get("protect_running"))
 
     def launch_info(self):
         """Launch geometry of the step kernel (envs per workgroup, LDS bytes, resident workgroups per CU)."""
@@ -132,7 +139,16 @@ class BatchedRMSAEnv(BatchedHandle):
         (not accepted, ``act_path`` / ``act_slot`` the proposal, ``gn_gsnr_db`` the value compared, cause ``"gn"``).
         ``"next_path"`` (the ``sap_*`` names only): the candidate paths in order, the first one whose rule window is admitted is
         provisioned -- ``sap_ff_gn`` with the rule's window in the first fit's place.  ``None``: everything above, unchanged.  The
-        most-used rule and the ``any_*`` routes stay without a gate.  :meth:`path_rule_windows` is the matching query."""
+        most-used rule and the ``any_*`` routes stay without a gate.  :meth:`path_rule_windows` is the matching query.
+
+        A gate that protects the running lightpaths (``rmsa_gn_gate_parameters(protect_running=True)``, ``gn_protect``; not in the
+        reference): a candidate that passes its own check is provisioned only if no running service on a shared link
+        falls below the threshold of its modulation with the candidate lit.  ``"gn_neighbour_margin_db"`` in ``outputs`` -- the
+        smallest ``GSNR - threshold`` over those services, NaN where that check did not run (no own check, the own check refused,
+        no running service shares a link, or a handle that does not protect); it leaves through ``orlg_step_gn_protect``.  A
+        refusal by either check is the gate's refusal, cause ``"gn"``; ``sap_ff_gn`` goes on to the next path after either.
+        ``gn_rule=``, the ``_gn`` mask kinds and :meth:`path_rule_windows` know the candidate's own check only: on a protecting
+        handle they raise ``ValueError``."""
         if gn_rule is not None:
             return self._run_rule_gn(policy, n_steps, actions, auto_reset, outputs, out, cause_counts, gn_rule)
         return self._run(policy, n_steps, actions, auto_reset, outputs, out, cause_counts)
@@ -149,6 +165,9 @@ class BatchedRMSAEnv(BatchedHandle):
                              "with an assignment rule other than the reference's first fit)")
         if self.gn_gate is None:
             raise ValueError(f"gn_rule={gn_rule!r} needs a handle with a GN-model admission check (gn_gate=)")
+        if self.gn_protect:
+            raise ValueError(f"gn_rule={gn_rule!r}: the handle protects its running lightpaths (protect_running), and no assignment "
+                             "rule runs behind that second check yet")
         if gn_rule == "next_path" and not policy.startswith("sap_"):
             raise ValueError(f"gn_rule='next_path' goes on to the next candidate path: it needs a sap_* name, got {policy!r}")
         return self._run(policy, n_steps, actions, auto_reset, outputs, out, cause_counts, _lib.GN_RULE_MODES[gn_rule])
@@ -167,6 +186,10 @@ class BatchedRMSAEnv(BatchedHandle):
         if "gn_gsnr_db" in names:
             names = [n for n in names if n != "gn_gsnr_db"]
             gsnr = self._step_outputs(["gn_gsnr_db"], n_steps, out, {"gn_gsnr_db": "float64"}, {})
+        margin = None
+        if "gn_neighbour_margin_db" in names:
+            names = [n for n in names if n != "gn_neighbour_margin_db"]
+            margin = self._step_outputs(["gn_neighbour_margin_db"], n_steps, out, {"gn_neighbour_margin_db": "float64"}, {})
         diag = {}
         if "block_cause" in names:
             names = [n for n in names if n != "block_cause"]
@@ -190,7 +213,18 @@ class BatchedRMSAEnv(BatchedHandle):
                 actions = np.ascontiguousarray(actions, dtype=np.int32)
             _check_buffer("actions", actions, ashape, np.int32)
             ap = _ptr(actions)
-        if diag or rule or cut:   # (a name of WINDOW_POLICIES has a rule)
+        if margin is not None:
+            if rule or cut or gn_mode is not None:
+                raise ValueError(f"policy {policy!r}: gn_neighbour_margin_db leaves a launch of the reference's first fit only "
+                                 "(orlg_step_gn_protect); no assignment rule runs behind the check of the running lightpaths")
+            d = _lib.StepDiag(_ptr(diag.get("block_cause")), _ptr(diag.get("block_cause_counts")),
+                              None if gsnr is None else _ptr(gsnr["gn_gsnr_db"]))
+            _lib.check(self.L.orlg_step_gn_protect(self.h, pid, int(n_steps), ap, 1 if auto_reset else 0, C.byref(io), C.byref(d),
+                                                   _ptr(margin["gn_neighbour_margin_db"])))
+            res.update(diag)
+            res.update(gsnr or {})
+            res.update(margin)
+        elif diag or rule or cut:   # (a name of WINDOW_POLICIES has a rule)
             d = _lib.StepDiag(_ptr(diag.get("block_cause")), _ptr(diag.get("block_cause_counts")),
                               None if gsnr is None else _ptr(gsnr["gn_gsnr_db"]))
             if gn_mode is not None:
@@ -341,6 +375,9 @@ class BatchedRMSAEnv(BatchedHandle):
             raise ValueError(f"gsnr_out: kind {kind!r} has no GSNR rows, they go with {self.GN_MASK_KINDS}")
         if gn and self.gn_gate is None:
             raise ValueError(f"kind {kind!r} needs a handle with a GN-model admission check (gn_gate=)")
+        if gn and self.gn_protect:
+            raise ValueError(f"kind {kind!r}: the handle protects its running lightpaths (protect_running); this mask knows the "
+                             "candidate's own check only and would describe a step the handle does not run")
         if out is None:
             out = np.zeros(shape, dt)
         else:
@@ -440,6 +477,9 @@ class BatchedRMSAEnv(BatchedHandle):
             raise ValueError(f"rule {rule!r}: expected one of {tuple(_lib.GN_PATH_WINDOW_RULES)}")
         if self.gn_gate is None:
             raise ValueError("path_rule_windows needs a handle with a GN-model admission check (gn_gate=)")
+        if self.gn_protect:
+            raise ValueError("path_rule_windows: the handle protects its running lightpaths (protect_running); this query knows the "
+                             "candidate's own check only and would describe a step the handle does not run")
         shape = (self.batch_size, self.k_paths)
         res = []
         for name, buf, dt in (("slots_out", slots_out, np.int16), ("gsnr_out", gsnr_out, np.float64), ("admitted_out", admitted_out, np.uint8)):

@@ -21,9 +21,10 @@ struct orlg_env : OrlgHandle {
     int allow_rejection = 0;   // the action spaces carry the explicit rejection (orlg_set_allow_rejection): one more mask column
     std::vector<uint8_t> path_se;   // spectral efficiency of every path record (orlg_set_gn_gate checks the thresholds against it)
     double *gn_table = nullptr;     // the gate's table on the device (allocated with the first gate; OrlgParams::gn = it or nullptr)
+    bool gn_protect = false;        // the gate also protects the running lightpaths (orlg_set_gn_protect; configuration, not state)
 };
-enum { X_ACTIONS, X_GSNR, X_CAUSE, X_CAUSE_COUNTS };   // OrlgHandle::extra: external actions from / the gn_gsnr_db, block_cause and cause_counts outputs for host memory
-static_assert(X_CAUSE_COUNTS < ORLG_EXTRA_SLOTS, "OrlgHandle::extra");
+enum { X_ACTIONS, X_GSNR, X_CAUSE, X_CAUSE_COUNTS, X_MARGIN };   // OrlgHandle::extra: external actions from / the gn_gsnr_db, block_cause, cause_counts and gn_neighbour_margin_db outputs for host memory
+static_assert(X_MARGIN < ORLG_EXTRA_SLOTS, "OrlgHandle::extra");
 
 #define SYNC_CHECK(e) do { int rc_ = orlg_handle_sync_check(e); if (rc_) return rc_; } while (0)
 
@@ -219,9 +220,11 @@ static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
     const bool df = !gn && p.mode == ORLG_MODE_STEP && orlg_defer_link_stats(p.stats_level, p.n_steps, p.out_mask, ov);   // as launch_rmsa_group
     const OrlgWaveKey key = {ff ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel_ff)
                                 : p.mode == ORLG_MODE_STEP ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel) : ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel),
-                             p.stats_level, df, gn, cause, assign, assign && p.assign == ORLG_ASSIGN_MIN_CUT, assign && usage_launch(p)};
-    // (an assignment rule behind the check, orlg_step_rule_gn: the instantiations of orlg_inst_gnrules.hip, with a lookup of their own)
-    rmsa_kernel_t k = gn && assign ? orlg_pick_gn_rules(e->W, key) : orlg_pick(e->W, key);
+                             p.stats_level, df, gn, cause, assign, assign && p.assign == ORLG_ASSIGN_MIN_CUT, assign && usage_launch(p),
+                             gn && e->gn_protect};
+    // (an assignment rule behind the check, orlg_step_rule_gn: the instantiations of orlg_inst_gnrules.hip, with a lookup of their own;
+    // a handle that protects its running lightpaths: those of orlg_inst_gnprotect.hip -- orlg_step_rule_gn refuses on it)
+    rmsa_kernel_t k = key.PROTECT ? orlg_pick_gn_protect(e->W, key) : gn && assign ? orlg_pick_gn_rules(e->W, key) : orlg_pick(e->W, key);
     if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
     if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), e->lds_block_bytes)) return rc;
     const int wpb = e->waves_per_block;
@@ -601,10 +604,11 @@ static int extra_out(orlg_env *e, ExtraOut *o, void *user, size_t bytes, int slo
 // ORLG_ASSIGN_MIN_CUT, which only orlg_step_min_cut passes, with own_entry = 1 -- `policy` may then be the device's ORLG_POLICY_MIN_CUT;
 // own_entry = 2: orlg_step_window, which has checked its route and rule itself -- the device's ORLG_ASSIGN_MOST_USED and ORLG_POLICY_BEST_WINDOW;
 // own_entry = 3: orlg_step_rule_gn, which has checked route, rule, mode and the gate itself -- a rule up to ORLG_ASSIGN_MIN_CUT on a
-// gated handle, `policy` a route, the device's ORLG_POLICY_MIN_CUT, or ORLG_POLICY_SAP_GN = route sap that goes on to the next path)
+// gated handle, `policy` a route, the device's ORLG_POLICY_MIN_CUT, or ORLG_POLICY_SAP_GN = route sap that goes on to the next path;
+// margin: the output gn_neighbour_margin_db of orlg_step_gn_protect)
 static int rmsa_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
                      const orlg_step_io *io, double *gsnr, uint8_t *cause = nullptr, int32_t *counts = nullptr, int32_t assign = ORLG_ASSIGN_FIRST,
-                     int own_entry = 0) {
+                     int own_entry = 0, double *margin = nullptr) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     if (n_steps < 1) return fail(ORLG_ERR_INVALID, "n_steps must be >= 1");
     const bool min_cut_entry = own_entry == 1;
@@ -670,6 +674,12 @@ static int rmsa_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t
     p.o_cause_counts = static_cast<int32_t *>(xn.dev);
     if (cause || counts) p.out_mask |= ORLG_OUT_CAUSE_BIT;
     if (counts) HIP_TRY(hipMemsetAsync(xn.dev, 0, xn.bytes, e->stream));
+    // gn_neighbour_margin_db: written by a protecting handle's kernels; every other handle ran no second check -- all NaN
+    ExtraOut xm;
+    rc = extra_out(e, &xm, margin, cnt * sizeof(double), X_MARGIN);
+    if (rc) return rc;
+    p.o_margin = static_cast<double *>(xm.dev);
+    if (margin && !(p.gn && e->gn_protect)) HIP_TRY(hipMemsetAsync(xm.dev, 0xff, xm.bytes, e->stream));
     p.assign = assign;
     if (assign != ORLG_ASSIGN_FIRST) p.out_mask |= ORLG_OUT_ASSIGN_BIT;   // the launch runs an ASSIGN instantiation
     rc = launch_rmsa(e, p);
@@ -678,7 +688,7 @@ static int rmsa_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t
     bool any = false;
     rc = orlg_handle_collect(e, slots, ORLG_NUM_OUTS, cnt, p.outs, &any);
     if (rc) return rc;
-    for (const ExtraOut *x : {&xc, &xn})
+    for (const ExtraOut *x : {&xc, &xn, &xm})
         if (x->staged()) {
             HIP_TRY(hipMemcpyAsync(x->user, x->dev, x->bytes, hipMemcpyDeviceToHost, e->stream));
             any = true;
@@ -702,6 +712,11 @@ int orlg_step_diag(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *
                    const struct orlg_step_diag *diag) {
     if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr);
     return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts);
+}
+int orlg_step_gn_protect(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
+                         const struct orlg_step_diag *diag, double *gn_neighbour_margin_db) {
+    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag ? diag->gn_gsnr_db : nullptr, diag ? diag->block_cause : nullptr,
+                     diag ? diag->cause_counts : nullptr, ORLG_ASSIGN_FIRST, 0, gn_neighbour_margin_db);
 }
 int orlg_step_assign(orlg_env *e, int32_t policy, int32_t assign, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
                      const orlg_step_io *io, const struct orlg_step_diag *diag) {
@@ -740,6 +755,8 @@ int orlg_step_rule_gn(orlg_env *e, int32_t route, int32_t rule, int32_t gn_mode,
                       const orlg_step_io *io, const struct orlg_step_diag *diag) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     if (!e->p.gn) return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: the handle has no gn_gate (orlg_step_assign, orlg_step_min_cut serve it)");
+    if (e->gn_protect)
+        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: the handle protects its running lightpaths (orlg_set_gn_protect), and no assignment rule runs behind that second check yet: orlg_step_gn_protect runs the reference's first fit behind it");
     if (route == ORLG_ROUTE_BEST_WINDOW || rule == ORLG_RULE_MOST_USED)
         return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: the rule MOST_USED and the route BEST_WINDOW are not served behind a gn_gate (route %d, rule %d)", route, rule);
     if (route != ORLG_POLICY_SP_FF && route != ORLG_POLICY_SAP_FF && route != ORLG_POLICY_LLP_FF && route != ORLG_POLICY_PATH_FF_EXTERNAL &&
@@ -768,6 +785,7 @@ int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
     HIP_TRY(hipSetDevice(e->device));
     if (!g) {
         e->p.gn = nullptr;
+        e->gn_protect = false;   // (protection is a property of the gate: a new gate keeps it, no gate has none)
         return ORLG_OK;
     }
     if (e->group_mode == ORLG_KERNEL_GROUP)
@@ -810,6 +828,13 @@ int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
     HIP_TRY(hipStreamSynchronize(e->stream));   // (a launch in flight may be reading the table)
     HIP_TRY(hipMemcpy(e->gn_table, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     e->p.gn = e->gn_table;
+    return ORLG_OK;
+}
+
+int orlg_set_gn_protect(orlg_env *e, int32_t on) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn_protect: the handle has no gn_gate (orlg_set_gn_gate): protection is a property of the gate");
+    e->gn_protect = on != 0;
     return ORLG_OK;
 }
 
@@ -1105,6 +1130,8 @@ int orlg_gn_action_masks(orlg_env *e, uint8_t *path_ff, double *path_ff_gsnr_db,
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     if (!path_ff && !path_ff_gsnr_db && !deeprmsa && !deeprmsa_gsnr_db) return fail(ORLG_ERR_INVALID, "null argument: no mask or GSNR buffer");
     if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn action masks: the handle has no gn_gate");
+    if (e->gn_protect)
+        return fail(ORLG_ERR_INVALID, "gn action masks: the handle protects its running lightpaths (orlg_set_gn_protect); these masks know the candidate's own check only and would describe a step this handle does not run");
     HIP_TRY(hipSetDevice(e->device));
     const OrlgParams &p = e->p;
     const size_t B = (size_t)p.B, kj = (size_t)p.K * p.j;
@@ -1135,6 +1162,8 @@ int orlg_gn_path_windows(orlg_env *e, int32_t rule, int16_t *slots_out, double *
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     if (!slots_out && !gsnr_db && !admitted) return fail(ORLG_ERR_INVALID, "null argument: no slots, GSNR or admitted buffer");
     if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn path windows: the handle has no gn_gate");
+    if (e->gn_protect)
+        return fail(ORLG_ERR_INVALID, "gn path windows: the handle protects its running lightpaths (orlg_set_gn_protect); this query knows the candidate's own check only and would describe a step this handle does not run");
     if ((rule < ORLG_ASSIGN_FIRST || rule >= ORLG_NUM_ASSIGN_RULES) && rule != ORLG_RULE_FEWEST_CUTS)
         return fail(ORLG_ERR_INVALID, "gn path windows: unknown rule %d (ORLG_ASSIGN_FIRST .. EXACT or ORLG_RULE_FEWEST_CUTS)", rule);
     HIP_TRY(hipSetDevice(e->device));

@@ -169,6 +169,10 @@ struct OrlgParams {
     // ORLG_OUT_ASSIGN_BIT in out_mask; ORLG_ASSIGN_MIN_CUT (above): the fewest-cuts window, orlg_cut.h, the CUT instantiations.
     // (At the struct's end, as the cause pointers)
     int32_t assign;
+    // the neighbour margin of a protecting handle (orlg_set_gn_protect, orlg_rmsa_gn_protect.h): the per-step output
+    // gn_neighbour_margin_db [n_steps][B] of orlg_step_gn_protect, written by the PROTECT instantiations only; nullptr = not asked
+    // for.  (At the struct's end, as the fields above)
+    double *o_margin;
 };
 // out_mask of a launch that asks for a cause output: not one of outs[], but a per-step output like them -- what looks at
 // out_mask to choose a kernel (the deferred link statistics, the group kernel's HBMQ kind and lean body) keeps such a launch on

@@ -34,6 +34,7 @@
 #include "orlg_link_stats.h"   // and through it orlg_wave.h, orlg_rmsa_layout.h, orlg_spectrum.h
 #include "orlg_requests.h"     // mt_regenerate, the ring's three producers, ring_store, ring_visible, orlg_env_rates
 #include "orlg_rmsa_gn.h"      // rmsa_gn_gsnr: the GN-model admission check of the GN instantiations
+#include "orlg_rmsa_gn_protect.h"   // rmsa_gn_neighbour_margin: the check of the running lightpaths of the PROTECT instantiations
 #include "orlg_block_cause.h"  // wave_fit_levels: the classifier of the CAUSE instantiations
 #include "orlg_assign.h"       // wave_assign: the assignment rules of the ASSIGN instantiations
 #include "orlg_cut.h"          // wave_cut_assign: the fewest-cuts window of the CUT instantiations
@@ -66,10 +67,14 @@
 // GN with ASSIGN (and CUT): orlg_step_rule_gn -- the rule's window, or the fewest-cuts window, goes through the check of
 // SEC(3) like any other proposal.  Its mode next-path arrives as the policy ORLG_POLICY_SAP_GN: route sap from the first path the
 // check has not refused yet, with sap_ff_gn's retry.  These instantiations live in orlg_inst_gnrules.hip; USAGE has none.
+// PROTECT (with GN, without ASSIGN): the handle protects its running lightpaths (orlg_set_gn_protect) -- a candidate that
+// passes its own check is provisioned only if rmsa_gn_neighbour_margin (orlg_rmsa_gn_protect.h) is not negative: no running service on
+// a shared link falls below its threshold.  A refusal by it is the gate's refusal, sap_ff_gn's retry included; `margin` is what the
+// retry reports with the first candidate when the paths end.  These instantiations live in orlg_inst_gnprotect.hip.
 template <bool GN>
 struct SapRetry {
     int from = 0, path = 0, slot = 0;
-    double gsnr = 0.0;
+    double gsnr = 0.0, margin = 0.0;
     bool exhausted = false;
 };
 template <>
@@ -78,7 +83,7 @@ struct SapRetry<false> {
 };
 
 template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false, bool CUT = false,
-          bool USAGE = false>
+          bool USAGE = false, bool PROTECT = false>
 DEV void rmsa_body(const OrlgParams &p) {
     extern __shared__ __align__(16) unsigned char smem[];
 #ifdef ORLG_SHAPE_ASSUME
@@ -350,6 +355,7 @@ DEV void rmsa_body(const OrlgParams &p) {
             const double prev_compact = comp_cur;
             bool accepted = false;
             double gn_gsnr = __longlong_as_double(0x7ff8000000000000ll);   // GN: the GSNR the check compared, NaN = no check ran
+            [[maybe_unused]] double gn_margin = __longlong_as_double(0x7ff8000000000000ll);   // PROTECT: the neighbour margin, NaN = that check did not run
             if constexpr (GN) {   // sap_ff_gn: no further path has a fit, the step is the refusal of the first candidate
                 sap.exhausted = sap.from > 0 && a_path == K;
                 if (sap.exhausted) { a_path = sap.path; a_slot = sap.slot; }
@@ -367,18 +373,30 @@ DEV void rmsa_body(const OrlgParams &p) {
                 if constexpr (GN) {
                     if (sap.exhausted) {
                         gn_gsnr = sap.gsnr;
+                        if constexpr (PROTECT) gn_margin = sap.margin;
                         window_ok = false;
                     } else if (window_ok) {
                         const OrlgGnTable gn = ORLG_GPTR(const double, p.gn);
                         const OrlgPathRec *cand = tb.recs + (base + a_path);
                         gn_gsnr = rmsa_gn_gsnr(wv, tb, gn, E, Q, q_head, q_n, cand, a_slot, n);
                         window_ok = gn_gsnr >= gn[ORLG_GN_THR0 + (int)cand->se - 1];
+                        // PROTECT: the running services that share a link with the candidate, each with the candidate lit; no
+                        // such service: NaN, which refuses nothing
+                        if constexpr (PROTECT) {
+                            if (window_ok) {
+                                gn_margin = rmsa_gn_neighbour_margin(wv, tb, gn, E, Q, q_head, q_n, cand, a_slot, n);
+                                window_ok = !(gn_margin < 0.0);
+                            }
+                        }
                         // sap_ff_gn (QoT-aware shortest available path, first fit; not in the reference, include/orlg.h
                         // ORLG_POLICY_SAP_FF_GN): a refused window is followed by the first fit of the next path that has one --
                         // the step starts over at its policy, which nothing has changed yet, from the path behind this one.  Each
                         // candidate is checked once; when the paths end, the refusal shows the first candidate
                         if (policy == ORLG_POLICY_SAP_GN && !window_ok) {
-                            if (sap.from == 0) { sap.path = a_path; sap.slot = a_slot; sap.gsnr = gn_gsnr; }
+                            if (sap.from == 0) {
+                                sap.path = a_path; sap.slot = a_slot; sap.gsnr = gn_gsnr;
+                                if constexpr (PROTECT) sap.margin = gn_margin;
+                            }
                             sap.from = a_path + 1;
                             --t;
                             continue;
@@ -476,6 +494,10 @@ DEV void rmsa_body(const OrlgParams &p) {
             }
             if constexpr (GN) {
                 if (lane == 0 && p.o_gsnr) ORLG_GPTR(double, p.o_gsnr)[(size_t)t * p.B + env] = gn_gsnr;
+            }
+            if constexpr (PROTECT) {
+                KernargParams kq = kernarg_params();
+                if (lane == 0 && kq->o_margin) ORLG_GPTR(double, kq->o_margin)[(size_t)t * p.B + env] = gn_margin;
             }
             if constexpr (CAUSE) {
                 int cause = ORLG_CAUSE_ACCEPTED;
@@ -676,11 +698,13 @@ DEV void rmsa_body(const OrlgParams &p) {
     SEC_FLUSH;
 }
 
-template <int W, int STATS, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false, bool CUT = false, bool USAGE = false>
+template <int W, int STATS, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false, bool CUT = false, bool USAGE = false,
+          bool PROTECT = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel(const OrlgParams p) {
     static_assert(!CUT || ASSIGN, "the fewest-cuts window is an assignment rule");
     static_assert(!USAGE || (ASSIGN && !CUT), "most-used windows and the best-window route are assignment rules of their own");
-    rmsa_body<W, STATS, true, false, DEFER, GN, CAUSE, ASSIGN, CUT, USAGE>(p);
+    static_assert(!PROTECT || (GN && !ASSIGN), "protection is a property of the gate; no assignment rule runs behind it");
+    rmsa_body<W, STATS, true, false, DEFER, GN, CAUSE, ASSIGN, CUT, USAGE, PROTECT>(p);
 }
 template <int W, int STATS, bool DEFER = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel_ff(const OrlgParams p) {

@@ -10,5 +10,6 @@
 #include "orlg_osnr.hip"
 #include "orlg_inst_wave.hip"
 #include "orlg_inst_gnrules.hip"
+#include "orlg_inst_gnprotect.hip"
 #include "orlg_inst_group.hip"
 #include "orlg_inst_phy.hip"

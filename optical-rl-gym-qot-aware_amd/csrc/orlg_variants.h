@@ -14,7 +14,8 @@
 // bool ASSIGN = false, bool CUT = false>; the reset kernel has no DEFER, and only orlg_rmsa_kernel has GN (the GN-model admission
 // check, orlg_rmsa_gn.h), CAUSE (the blocking cause of every step, orlg_block_cause.h), ASSIGN (the spectrum-assignment rules beyond
 // the reference's first fit, orlg_assign.h), CUT (ASSIGN with the fewest-cuts window in the rules' place, orlg_cut.h) and, after it,
-// USAGE (ASSIGN with the rule MOST_USED and the route BEST_WINDOW, orlg_usage.h)
+// USAGE (ASSIGN with the rule MOST_USED and the route BEST_WINDOW, orlg_usage.h) and, last, PROTECT (GN with the check of the
+// running lightpaths, orlg_rmsa_gn_protect.h)
 #define ORLG_WAVE_KERNELS(X) X(orlg_rmsa_kernel) X(orlg_rmsa_kernel_ff) X(orlg_rmsa_reset_kernel)
 #define ORLG_WAVE_KERNEL(name) ORLG_IS_##name
 enum OrlgWaveKernel {
@@ -22,13 +23,13 @@ enum OrlgWaveKernel {
     ORLG_WAVE_KERNELS(X)
 #undef X
 };
-struct OrlgWaveKey { OrlgWaveKernel kernel; int STATS; bool DEFER; bool GN = false; bool CAUSE = false; bool ASSIGN = false; bool CUT = false; bool USAGE = false; };
+struct OrlgWaveKey { OrlgWaveKernel kernel; int STATS; bool DEFER; bool GN = false; bool CAUSE = false; bool ASSIGN = false; bool CUT = false; bool USAGE = false; bool PROTECT = false; };
 // orlg_rmsa_group_kernel (orlg_group_kernels.hip)
 struct OrlgGroupKey { int STATS; bool HBMQ, DEFER, TRAFFIC, TRACE; bool CAUSE = false; bool ASSIGN = false; bool CUT = false; bool USAGE = false; };
 // orlg_phy_kernel (orlg_phy_kernels.hip)
 struct OrlgPhyKey { bool DF, GN; int POL; bool CONT, TRACE; };
 
-inline bool operator==(const OrlgWaveKey &a, const OrlgWaveKey &b) { return a.kernel == b.kernel && a.STATS == b.STATS && a.DEFER == b.DEFER && a.GN == b.GN && a.CAUSE == b.CAUSE && a.ASSIGN == b.ASSIGN && a.CUT == b.CUT && a.USAGE == b.USAGE; }
+inline bool operator==(const OrlgWaveKey &a, const OrlgWaveKey &b) { return a.kernel == b.kernel && a.STATS == b.STATS && a.DEFER == b.DEFER && a.GN == b.GN && a.CAUSE == b.CAUSE && a.ASSIGN == b.ASSIGN && a.CUT == b.CUT && a.USAGE == b.USAGE && a.PROTECT == b.PROTECT; }
 inline bool operator==(const OrlgGroupKey &a, const OrlgGroupKey &b) {
     return a.STATS == b.STATS && a.HBMQ == b.HBMQ && a.DEFER == b.DEFER && a.TRAFFIC == b.TRAFFIC && a.TRACE == b.TRACE && a.CAUSE == b.CAUSE && a.ASSIGN == b.ASSIGN && a.CUT == b.CUT && a.USAGE == b.USAGE;
 }
@@ -85,6 +86,16 @@ inline bool operator==(const OrlgPhyKey &a, const OrlgPhyKey &b) {
 #define ORLG_WAVE_GN_CUT_KEYS(X)                                                                                                                   \
     X(orlg_rmsa_kernel, 1, false, true, false, true, true) X(orlg_rmsa_kernel, 2, false, true, false, true, true) X(orlg_rmsa_kernel, 0, false, true, false, true, true) \
     X(orlg_rmsa_kernel, 1, false, true, true, true, true) X(orlg_rmsa_kernel, 2, false, true, true, true, true) X(orlg_rmsa_kernel, 0, false, true, true, true, true)
+// X(kernel, STATS, DEFER, GN, CAUSE, ASSIGN, CUT, USAGE, PROTECT): what a handle that protects its running lightpaths launches
+// (orlg_set_gn_protect) -- the GN keys again with PROTECT, without and with the classifier.  Lists of their own, and a
+// unit of its own (orlg_inst_gnprotect.hip, one object per W, lookup orlg_gnprotect_kernel_W<n>): the orlg_inst_wave and
+// orlg_inst_gnrules objects hold what they held.
+#define ORLG_WAVE_GN_PROTECT_KEYS(X)                                                                                                              \
+    X(orlg_rmsa_kernel, 1, false, true, false, false, false, false, true) X(orlg_rmsa_kernel, 2, false, true, false, false, false, false, true) \
+    X(orlg_rmsa_kernel, 0, false, true, false, false, false, false, true)
+#define ORLG_WAVE_GN_PROTECT_CAUSE_KEYS(X)                                                                                                      \
+    X(orlg_rmsa_kernel, 1, false, true, true, false, false, false, true) X(orlg_rmsa_kernel, 2, false, true, true, false, false, false, true) \
+    X(orlg_rmsa_kernel, 0, false, true, true, false, false, false, true)
 
 // X(STATS, HBMQ, DEFER, TRAFFIC, TRACE).  Per kind of handle: every statistics level, the same with the release queue left in HBM
 // (launches of very few steps), and full statistics with the link updates deferred (long launches).  The kinds: plain, with
@@ -160,6 +171,8 @@ inline constexpr OrlgWaveKey ORLG_WAVE_CUT_KEY_LIST[] = {ORLG_WAVE_CUT_KEYS(ORLG
 inline constexpr OrlgWaveKey ORLG_WAVE_USAGE_KEY_LIST[] = {ORLG_WAVE_USAGE_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgWaveKey ORLG_WAVE_GN_ASSIGN_KEY_LIST[] = {ORLG_WAVE_GN_ASSIGN_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgWaveKey ORLG_WAVE_GN_CUT_KEY_LIST[] = {ORLG_WAVE_GN_CUT_KEYS(ORLG_WAVE_KEY_ENTRY)};
+inline constexpr OrlgWaveKey ORLG_WAVE_GN_PROTECT_KEY_LIST[] = {ORLG_WAVE_GN_PROTECT_KEYS(ORLG_WAVE_KEY_ENTRY)};
+inline constexpr OrlgWaveKey ORLG_WAVE_GN_PROTECT_CAUSE_KEY_LIST[] = {ORLG_WAVE_GN_PROTECT_CAUSE_KEYS(ORLG_WAVE_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_KEY_LIST[] = {ORLG_GROUP_KEYS(ORLG_GROUP_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_CAUSE_KEY_LIST[] = {ORLG_GROUP_CAUSE_KEYS(ORLG_GROUP_KEY_ENTRY)};
 inline constexpr OrlgGroupKey ORLG_GROUP_ASSIGN_KEY_LIST[] = {ORLG_GROUP_ASSIGN_KEYS(ORLG_GROUP_KEY_ENTRY)};
@@ -189,8 +202,8 @@ inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgWaveKey &k)
 #define X(name) #name,
     static const char *const names[] = {ORLG_WAVE_KERNELS(X)};
 #undef X
-    const OrlgArg args[] = {{k.STATS, 'i'}, {k.DEFER, 'd'}, {k.GN, 'd'}, {k.CAUSE, 'd'}, {k.ASSIGN, 'd'}, {k.CUT, 'd'}, {k.USAGE, 'd'}};
-    orlg_format_kernel(buf, cap, names[k.kernel], W, args, k.kernel == ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel) ? 1 : 7);
+    const OrlgArg args[] = {{k.STATS, 'i'}, {k.DEFER, 'd'}, {k.GN, 'd'}, {k.CAUSE, 'd'}, {k.ASSIGN, 'd'}, {k.CUT, 'd'}, {k.USAGE, 'd'}, {k.PROTECT, 'd'}};
+    orlg_format_kernel(buf, cap, names[k.kernel], W, args, k.kernel == ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel) ? 1 : 8);
 }
 inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgGroupKey &k) {
     const OrlgArg args[] = {{k.STATS, 'i'}, {k.HBMQ, 'd'}, {k.DEFER, 'd'}, {k.TRAFFIC, 'd'}, {k.TRACE, 'd'}, {k.CAUSE, 'd'}, {k.ASSIGN, 'd'}, {k.CUT, 'd'}, {k.USAGE, 'd'}};
@@ -229,6 +242,7 @@ typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
     orlg_usage_kernel_t orlg_usage_kernel_W##n() __attribute__((weak));                           \
     orlg_rmsa_kernel_t orlg_gnrules_kernel_W##n(OrlgWaveKey) __attribute__((weak));   /* orlg_inst_gnrules.hip */ \
     orlg_gn_path_windows_kernel_t orlg_gn_path_windows_kernel_W##n() __attribute__((weak));       \
+    orlg_rmsa_kernel_t orlg_gnprotect_kernel_W##n(OrlgWaveKey) __attribute__((weak));   /* orlg_inst_gnprotect.hip */ \
     orlg_rmsa_kernel_t orlg_group_kernel_W##n(OrlgGroupKey) __attribute__((weak));
 #define ORLG_DECL_PHY_W(n, ...)                                                                   \
     orlg_phy_kernel_t orlg_phy_kernel_W##n(OrlgPhyKey) __attribute__((weak));                     \
@@ -245,6 +259,8 @@ static orlg_rmsa_kernel_t orlg_pick(int W, const OrlgWaveKey &key) { ORLG_PICK(O
 // the GN x ASSIGN keys (ORLG_WAVE_GN_ASSIGN_KEYS, ORLG_WAVE_GN_CUT_KEYS): a lookup of their own -- orlg_pick answers for the keys it
 // always answered for, and with null for these
 static orlg_rmsa_kernel_t orlg_pick_gn_rules(int W, const OrlgWaveKey &key) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gnrules_kernel_W, key) }
+// the PROTECT keys (ORLG_WAVE_GN_PROTECT_KEYS, ORLG_WAVE_GN_PROTECT_CAUSE_KEYS): a lookup of their own, for the same reason
+static orlg_rmsa_kernel_t orlg_pick_gn_protect(int W, const OrlgWaveKey &key) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gnprotect_kernel_W, key) }
 static orlg_rmsa_kernel_t orlg_pick(int W, const OrlgGroupKey &key) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_group_kernel_W, key) }
 static orlg_phy_kernel_t orlg_pick(int W, const OrlgPhyKey &key) {   // the TRACE instantiations are objects of their own
     if (key.TRACE) { ORLG_PICK(ORLG_FOR_EACH_PHY_W, W, orlg_phy_trace_kernel_W, key) }

@@ -321,7 +321,9 @@ class RMSAEnv(_View):
                                           "avg_link_utilization") + self._gate_outputs())
 
     def _gate_outputs(self):
-        return ("gn_gsnr_db",) if self._batched.gn_gate is not None else ()
+        if self._batched.gn_gate is None:
+            return ()
+        return ("gn_gsnr_db", "gn_neighbour_margin_db") if self._batched.gn_protect else ("gn_gsnr_db",)
 
     def step(self, action):
         """``rmsa_env.py:222-341`` -> (observation, reward, done, info)"""
@@ -345,6 +347,8 @@ class RMSAEnv(_View):
                           float(r["avg_link_compactness"][0, 0]), float(r["avg_link_utilization"][0, 0]))
         if "gn_gsnr_db" in r:   # (a handle with a GN-model admission check: the GSNR it compared, NaN = no check ran)
             info["gn_gsnr_db"] = float(r["gn_gsnr_db"][0, 0])
+        if "gn_neighbour_margin_db" in r:   # (... that protects its running lightpaths: the neighbour margin, NaN = that check did not run)
+            info["gn_neighbour_margin_db"] = float(r["gn_neighbour_margin_db"][0, 0])
         reward = r["reward"][0, 0]
         reward = int(reward) if float(reward).is_integer() else float(reward)
         self._sync()

@@ -134,7 +134,7 @@ def gn_gate_parameters(topology, num_channels=268, *, launch_power_dbm=0.0, chan
 
 
 def rmsa_gn_gate_parameters(topology, *, launch_power_dbm_per_50ghz=0.0, frequency_start_hz=191.7e12, channel_width=12.5,
-                            max_span_length_km=80.0, attenuation_db_km=0.2, noise_figure_db=4.5, thresholds_db=None):
+                            max_span_length_km=80.0, attenuation_db_km=0.2, noise_figure_db=4.5, thresholds_db=None, protect_running=False):
     """Parameters of the GN-model admission check of ``BatchedRMSAEnv(..., gn_gate=...)`` / ``BatchedDeepRMSAEnv``
     (``include/orlg.h`` ``orlg_rmsa_gn_gate``): a plain dict of numbers / arrays.
 
@@ -142,14 +142,17 @@ def rmsa_gn_gate_parameters(topology, *, launch_power_dbm_per_50ghz=0.0, frequen
       ``[s, s + n)`` is ``n`` slots wide around ``frequency_start_hz + (s + n / 2) * width``;
     * launch power: a constant power spectral density, ``launch_power_dbm_per_50ghz`` dBm in every 50 GHz --
       ``1e-3 * 10 ** (dBm / 10) / 50e9`` W/Hz;
-    * spans, attenuation, noise figure and the default thresholds: the conventions of :func:`gn_gate_parameters`.
+    * spans, attenuation, noise figure and the default thresholds: the conventions of :func:`gn_gate_parameters`;
+    * ``protect_running=True`` adds the key ``"protect_running"``: the gate also refuses a candidate that would push a running
+      lightpath on a shared link below the threshold of its modulation (``orlg_set_gn_protect``).  Without it the
+      dict has exactly the eight keys above.
     """
     from .topology import FrozenTopology
     t = FrozenTopology.from_graph(topology)
     lengths = np.array([float(e[4]) for e in t.edges], np.float64)[np.argsort([int(e[2]) for e in t.edges])]
     nspans = (lengths // max_span_length_km).astype(np.int32) + 1
     thr = thresholds_db if thresholds_db is not None else [0.5 * (a + b) for a, b in TABLE_THRESHOLDS_DB]
-    return {
+    g = {
         "launch_power_density_w_hz": 1e-3 * 10 ** (launch_power_dbm_per_50ghz / 10.0) / 50e9,
         "frequency_start_hz": float(frequency_start_hz),
         "slot_width_hz": float(channel_width) * 1e9,
@@ -159,6 +162,9 @@ def rmsa_gn_gate_parameters(topology, *, launch_power_dbm_per_50ghz=0.0, frequen
         "link_span_length_km": lengths / nspans,
         "thresholds_db": np.asarray(sorted(thr), np.float64),
     }
+    if protect_running:
+        g["protect_running"] = True
+    return g
 
 
 RMSA_GN_GATE_SCALARS = ("launch_power_density_w_hz", "frequency_start_hz", "slot_width_hz", "attenuation_normalized", "noise_figure")
@@ -189,4 +195,6 @@ def check_rmsa_gn_gate(gate, topology, step_kernel="auto"):
     se_max = int(np.max(t.path_se))
     if se_max > thr.size:
         raise ValueError(f"gn_gate: a path has spectral efficiency {se_max}, thresholds_db has {thr.size} entries")
+    if gate.get("protect_running"):   # (carried only when asked for)
+        g["protect_running"] = True
     return g
