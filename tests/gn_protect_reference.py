@@ -207,16 +207,25 @@ def final_state(o):
 
 
 def run_case(case, seed=None, n_steps=N_STEPS, policy=None, gate_items=()):
-    """The protecting oracle of a case (seed, policy: the case's own by default), run once per process and shared: (per-step
-    arrays, final state, figures).  Read-only by agreement."""
-    return _run_case(case, CASES[case]["seed"] if seed is None else seed, n_steps, policy or CASES[case]["policy"], tuple(gate_items))
+    """The protecting oracle of a case -- a name of CASES or a (topology, kwargs) pair with its `policy`, as
+    gn_gate_reference.run_case takes one -- (seed, policy: the case's own by default; a pair's seed is its kwargs'), run once per
+    process and shared: (per-step arrays, final state, figures).  Read-only by agreement."""
+    if isinstance(case, str):
+        seed, policy = CASES[case]["seed"] if seed is None else seed, policy or CASES[case]["policy"]
+    else:
+        assert policy is not None, "a (topology, kwargs) case has no policy of its own"
+        seed = case[1]["seed"] if seed is None else seed
+    return _run_case(ref.cache_key(case), seed, n_steps, policy, tuple(gate_items))
 
 
 @functools.lru_cache(maxsize=None)
-def _run_case(case, seed, n_steps, policy, gate_items):
-    topo = load_topology(CASES[case]["topology"])
+def _run_case(key, seed, n_steps, policy, gate_items):
+    if isinstance(key, str):
+        topo, kw = load_topology(CASES[key]["topology"]), case_kwargs(key)
+    else:
+        topo, kw, _ = ref.resolve_case((key[0], dict(key[1])), policy)
     with device_log_in_oracle():
-        po = ProtectingOracle(topo, case_kwargs(case), case_gate(topo, **dict(gate_items)), seed=seed)
+        po = ProtectingOracle(topo, kw, case_gate(topo, **dict(gate_items)), seed=seed)
         tr = po.run(policy, n_steps)
     final, fig = final_state(po.o), po.figures()
     po.close()
@@ -225,6 +234,7 @@ def _run_case(case, seed, n_steps, policy, gate_items):
     return tr, final, fig
 
 
-def run_batch(case, n_steps=N_STEPS, policy=None, batch=B):
-    """run_case for the seeds case seed + 0 .. batch - 1"""
-    return [run_case(case, seed=CASES[case]["seed"] + i, n_steps=n_steps, policy=policy) for i in range(batch)]
+def run_batch(case, n_steps=N_STEPS, policy=None, batch=B, gate_items=()):
+    """run_case for the seeds case seed + 0 .. batch - 1 (a (topology, kwargs) pair's seed is its kwargs')"""
+    seed = CASES[case]["seed"] if isinstance(case, str) else case[1]["seed"]
+    return [run_case(case, seed=seed + i, n_steps=n_steps, policy=policy, gate_items=gate_items) for i in range(batch)]
