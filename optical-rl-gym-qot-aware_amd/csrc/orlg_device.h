@@ -21,6 +21,9 @@
 
 // One k-shortest-path record (16 B): Path.hops, Path.best_modulation.spectral_efficiency and the link
 // "index" of every hop (utils.py:27-36, rmsa_env.py:479-483).
+// Padding: link[h] for h >= hops repeats link[0] (orlg_path_records, orlg_host.hip, fills it so).  A byte past the path's end
+// thus names a link of the path itself, and a reader that ANDs the occupancy words of all ORLG_MAX_HOPS bytes gets the path's
+// word (group_path_word_rec, orlg_group_kernels.hip).  Every other reader stops at `hops` and must not depend on the padding.
 struct __attribute__((aligned(16))) OrlgPathRec {
     uint8_t hops, se;
     uint8_t link[ORLG_MAX_HOPS];

@@ -334,6 +334,11 @@
             const int kmax = (given || policy == ORLG_POLICY_SP || (!LEAN && policy == ORLG_POLICY_DEEP_SP)) ? 1 : K;
             const int ps = gl / W, w = gl - ps * W;
             int found = 0x7fffffff, found_key = 0x7fffffff;
+            // First fit starts below S - n (exclusive: rmsa_env.py:860-871).  Slots at and beyond S are stored as not free, so a free
+            // window of n slots lies inside [0, S) and starts below S - n exactly when it does not hold slot S - 1: the first-fit
+            // family looks for its windows with that one slot cleared, and no start needs masking afterwards.  (Slot S - 1 is in
+            // word (S - 1) >> 6, not always the last of the W words.)  The DeepRMSA family has no such limit: nothing cleared.
+            const u64 lastbit = (!deep && w == ((S - 1) >> 6)) ? 1ull << ((S - 1) & 63) : 0ull;
             for (int p0 = 0; p0 < kmax; p0 += PP) {
                 if (!llp && ballot(act && a_ok && found == 0x7fffffff) == 0ull) break;
                 const int pp = p0 + ps;
@@ -342,13 +347,9 @@
                 const u64 x = group_path_word_rec<W>(occ, tb.recs, base + path0 + pp, w, on, se_pp, hops_pp);
                 int n = 1;
                 if (on) n = tb.nslots[req_br * ORLG_NSLOT_STRIDE + se_pp];
-                u64 r = run_starts<W>(x, n, w);
+                u64 r = run_starts<W>(x & ~lastbit, n, w);
                 const u64 xprev = lane_prev_u64(x);
-                if (!deep) {
-                    // start slots below S - n (exclusive: rmsa_env.py:860-871)
-                    const int below = (S - n) - 64 * w;
-                    r &= below >= 64 ? ~0ull : (below <= 0 ? 0ull : ((1ull << below) - 1ull));
-                } else {
+                if (deep) {
                     // block starts: free slots whose predecessor is not free
                     r &= x & ~((x << 1) | (w > 0 ? xprev >> 63 : 0ull));
                     if (!LEAN && policy == ORLG_POLICY_DEEP_EXT) {

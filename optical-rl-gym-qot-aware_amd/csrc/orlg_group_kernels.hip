@@ -79,8 +79,10 @@ ORLG_SEG_REDUCE(seg_max, ORLG_OP_MAX)
 // path_word_rec (orlg_spectrum.h) with the hop words FOUR TO A WAIT: the record's link bytes are all in registers, so the reads of
 // a group of four hops are issued back to back and ANDed in after one round trip, where the other form waits for every hop's
 // word before it votes on the next (three waves per SIMD do not hide that chain here; the wave kernel, at four, keeps its own
-// form).  A hop past the path's end reads the word of the path's first link -- a valid address on every lane, link 0 on an
-// inactive one -- and a select puts ~0 in its place.  Inactive lanes return 0 with se = hops = 0, as there.
+// form).  No hop is tested against the path's end: every link byte of the record is read as it stands and its word ANDed in.
+// The host pads the bytes past the end with the path's first link (OrlgPathRec, orlg_device.h) and AND is idempotent, so a
+// hop past the end repeats a word the result already holds; its address is a link of the path, valid on every lane.  An
+// inactive lane keeps a zero record: it reads link 0, starts from acc = 0 and returns 0 with se = hops = 0, as there.
 template <int W>
 DEV u64 group_path_word_rec(const u64 *occ, const OrlgPathRec *recs, int gid, int w, bool active, int &se, int &hops_out) {
     uint4 r = make_uint4(0u, 0u, 0u, 0u);
@@ -89,7 +91,6 @@ DEV u64 group_path_word_rec(const u64 *occ, const OrlgPathRec *recs, int gid, in
     const int hops = (int)(r.x & 0xffu);
     se = (int)((r.x >> 8) & 0xffu);
     hops_out = hops;
-    const int first = __mul24((int)((r.x >> 16) & 0xffu), W) + w;
     u64 acc = active ? ~0ull : 0ull;
 #pragma unroll
     for (int h0 = 0; h0 < ORLG_MAX_HOPS; h0 += 4) {
@@ -100,11 +101,11 @@ DEV u64 group_path_word_rec(const u64 *occ, const OrlgPathRec *recs, int gid, in
             const int h = h0 + k;
             if (h < ORLG_MAX_HOPS) {
                 const int link = (int)((q[(h + 2) >> 2] >> (8 * ((h + 2) & 3))) & 0xffu);
-                v[k] = occ[h < hops ? __mul24(link, W) + w : first];
+                v[k] = occ[__mul24(link, W) + w];
             }
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) acc &= h0 + k < hops ? v[k] : ~0ull;
+        for (int k = 0; k < 4; ++k) acc &= v[k];
     }
     return acc;
 }

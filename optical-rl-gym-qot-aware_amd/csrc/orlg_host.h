@@ -232,7 +232,8 @@ struct OrlgBlob {
     }
 };
 // OrlgPathRec of every path of t from the CSR arrays; hops, CSR and link indices checked.  link_fmt words a link outside 0..E-1
-// (printf arguments: path, link).  The spectral efficiency is copied unchecked.
+// (printf arguments: path, link).  The spectral efficiency is copied unchecked.  The link bytes past a path's end are filled
+// with the path's first link: the padding rule stated at OrlgPathRec (orlg_device.h), which the group kernel's policy relies on.
 int orlg_path_records(const orlg_topology *t, int E, const char *link_fmt, std::vector<OrlgPathRec> *recs);
 
 // ---------------------------------------------------------------------------------------- kernels over the scalar records

@@ -182,6 +182,7 @@ int orlg_path_records(const orlg_topology *t, int E, const char *link_fmt, std::
             if (l < 0 || l >= E) return fail(ORLG_ERR_INVALID, link_fmt, g, l);
             r.link[i] = (uint8_t)l;
         }
+        for (int i = h; i < ORLG_MAX_HOPS; i++) r.link[i] = r.link[0];   // the padding rule of OrlgPathRec (orlg_device.h)
     }
     return ORLG_OK;
 }
