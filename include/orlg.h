@@ -486,6 +486,40 @@ int orlg_action_masks(orlg_env *env, uint8_t *path_ff, uint64_t *slots);
  * NULL, or a handle without a gate, is ORLG_ERR_INVALID.  Buffers as orlg_action_masks. */
 int orlg_gn_action_masks(orlg_env *env, uint8_t *path_ff, double *path_ff_gsnr_db, uint8_t *deeprmsa, double *deeprmsa_gsnr_db);
 
+/* ---- the running services of every environment, and their GN-model audit (this project's).  Every gate entry above
+ * asks whether a CANDIDATE should be lit; these two say how the lightpaths that are already running are doing.  The state they read
+ * is the state between launches, which holds no service that is due at the pending request's arrival.
+ * RUNNING SERVICES of an environment: the live entries of its release ring -- n = clamp(n_running, 0, Q) of them (Q =
+ * orlg_queue_capacity) at ring slots (head + rank) % Q in ascending release time; RANK is that index.  An entry is decoded as the
+ * step decodes it: its path record, its first slot, num_slots = get_number_slots(bit rate, the path's spectral efficiency).
+ * orlg_get_running_services: count [B] = n, head [B] = the ring slot of rank 0; path_gid [B][Q] int32 (the global index of the path
+ * record, as in orlg_query_path_mask), slot and num_slots [B][Q] int16, bit_rate [B][Q] int32 (the rate itself, not its index),
+ * release_time [B][Q] float64 -- each in rank order, entries past count -1 / NaN.  Any pointer may be NULL, not all. */
+int orlg_queue_capacity(orlg_env *env);
+int orlg_get_running_services(orlg_env *env, int32_t *count, int32_t *head, int32_t *path_gid, int16_t *slot, int16_t *num_slots,
+                              int32_t *bit_rate, double *release_time);
+/* The audit.  For the running service of rank i, GSNR_i is calculate_osnr.py:9-56 for a service with window [s_i, s_i + n_i),
+ * bandwidth n_i D, centre f0 + (s_i + n_i / 2) D and launch power density * n_i D over the links of ITS path; the interferers of a
+ * link are the OTHER running services whose path holds that link; i itself is in no list.  This is the victim evaluation of
+ * "AFFECTED" above without a candidate's term.  margin_i = GSNR_i - thresholds_db[SE_i - 1];
+ * osnr_ase_db_i = 10 log10(1 / sum over spans of P_ASE / P), snr_nli_db_i = 10 log10(1 / sum over spans of P_NLI / P): linear,
+ * 1 / GSNR = 1 / ase + 1 / nli.
+ * summary [B]: n_running = n; n_below = #{i : margin_i < 0}; min_margin_db = the smallest margin, NaN when n = 0; worst_rank = the
+ * lowest rank that attains it, -1 when n = 0 (margin_db[worst_rank] has the bits of min_margin_db).  gsnr_db, margin_db, osnr_ase_db,
+ * snr_nli_db: [B][Q] float64 in rank order, NaN past n.  Any output pointer may be NULL, not all.
+ * gate: NULL = the handle's own gate; otherwise a gate for this call alone, under the rules of orlg_set_gn_gate (except that the
+ * handle's step kernel does not matter), which leaves the handle's configuration untouched -- margins at another launch power, or
+ * the audit of traffic an ungated handle built.  ORLG_ERR_INVALID: gate == NULL on a handle without a gate.
+ * Reads state and writes only the caller's buffers; served on gated, protecting and ungated handles, after either step kernel, with
+ * traces, continuous bit rates and per-environment traffic.  It describes no step, so a protecting handle serves it too.  Nothing
+ * is torn down or re-routed.  Buffers as orlg_action_masks. */
+typedef struct orlg_gn_audit_summary {
+    int32_t n_running, n_below, worst_rank, pad;
+    double min_margin_db;
+} orlg_gn_audit_summary;
+int orlg_gn_audit(orlg_env *env, const orlg_rmsa_gn_gate *gate, orlg_gn_audit_summary *summary, double *gsnr_db, double *margin_db,
+                  double *osnr_ase_db, double *snr_nli_db);
+
 /* SimpleMatrixObservation.observation() (rmsa_env.py:940-971) for every env: [B][2N + E*S] uint8 */
 int orlg_simple_matrix_observation(orlg_env *env, uint8_t *out);
 int orlg_simple_matrix_obs_dim(orlg_env *env);

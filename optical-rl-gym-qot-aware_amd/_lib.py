@@ -138,6 +138,15 @@ class RmsaGnGate(C.Structure):   # include/orlg.h orlg_rmsa_gn_gate
                 ("link_span_length_km", C.c_void_p), ("thresholds_db", C.c_void_p), ("num_thresholds", C.c_int32)]
 
 
+class GnAuditSummary(C.Structure):   # include/orlg.h orlg_gn_audit_summary
+    _fields_ = [("n_running", C.c_int32), ("n_below", C.c_int32), ("worst_rank", C.c_int32), ("pad", C.c_int32),
+                ("min_margin_db", C.c_double)]
+
+
+# the same record as a numpy dtype: the [B] summaries of orlg_gn_audit
+GN_AUDIT_SUMMARY_DTYPE = [("n_running", "<i4"), ("n_below", "<i4"), ("worst_rank", "<i4"), ("pad", "<i4"), ("min_margin_db", "<f8")]
+
+
 class PhyStepIO(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("act_path", "n_channels", "channels", "accepted", "done", "request",
                                          "arrival", "holding", "number_cuts_total", "rss_total_metric",
@@ -205,7 +214,11 @@ def _prototypes():
               "orlg_path_most_used": (None, [vp, vp, vp]),
               # assignment rules behind the GN-model admission check: the step, every path's rule window and its GSNR
               "orlg_step_rule_gn": (None, [vp, i32, i32, i32, i32, vp, i32, P(StepIO), P(StepDiag)]),
-              "orlg_gn_path_windows": (None, [vp, i32, vp, vp, vp])})
+              "orlg_gn_path_windows": (None, [vp, i32, vp, vp, vp]),
+              # the running services of every environment and their GN-model audit
+              "orlg_queue_capacity": (None, [vp]),
+              "orlg_get_running_services": (None, [vp, vp, vp, vp, vp, vp, vp, vp]),
+              "orlg_gn_audit": (None, [vp, P(RmsaGnGate), vp, vp, vp, vp, vp])})
     # QoT-aware only
     t.update({"orlg_phy_step": (None, [vp, i32, i32, vp, vp, i32, P(PhyStepIO)]), "orlg_phy_node_vectors": (None, [vp]),
               "orlg_phy_get_episode_stats": (None, [vp, vp]), "orlg_phy_channel_masks": (None, [vp, vp]),

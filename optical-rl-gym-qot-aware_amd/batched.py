@@ -491,6 +491,108 @@ class BatchedRMSAEnv(BatchedHandle):
         _lib.check(self.L.orlg_gn_path_windows(self.h, _lib.GN_PATH_WINDOW_RULES[rule], _ptr(res[0]), _ptr(res[1]), _ptr(res[2])))
         return res[0], res[1], res[2]
 
+    # ------------------------------------------------------------------ the running services and their GN-model audit
+    RUNNING_SERVICE_FIELDS = (("count", np.int32, False), ("head", np.int32, False), ("path_gid", np.int32, True),
+                              ("slot", np.int16, True), ("num_slots", np.int16, True), ("bit_rate", np.int32, True),
+                              ("release_time", np.float64, True))   # (name, dtype, [B, Q] rather than [B])
+    AUDIT_SERVICE_FIELDS = ("gsnr_db", "margin_db", "osnr_ase_db", "snr_nli_db")
+
+    @property
+    def queue_capacity(self):
+        """Slots of an environment's release ring (``orlg_queue_capacity``): the row length of the per-service arrays below."""
+        return int(self.L.orlg_queue_capacity(self.h))
+
+    def _rank_buffers(self, fields, out, what):
+        """one buffer per (name, dtype, per service) of `fields`: the caller's (``out[name]``, checked) or a new numpy array"""
+        unknown = set(out or ()) - {f[0] for f in fields}
+        if unknown:
+            raise ValueError(f"{what}: out= has no buffer named {sorted(unknown)}")
+        B, Q = self.batch_size, self.queue_capacity
+        res = {}
+        for name, dt, wide in fields:
+            shape = (B, Q) if wide else (B,)
+            buf = (out or {}).get(name)
+            res[name] = np.zeros(shape, dt) if buf is None else _check_buffer(f"out[{name!r}]", buf, shape, dt)
+        return res
+
+    def running_services(self, out=None):
+        """The running services of every environment (``orlg_get_running_services``): a dict -- ``count`` [B] int32,
+        the live entries of the release ring; ``head`` [B] int32, the ring slot of rank 0; and [B, Q] each, in rank order (ascending
+        release time), ``path_gid`` int32 (the global index of the path record), ``slot`` and ``num_slots`` int16, ``bit_rate`` int32
+        and ``release_time`` float64, with -1 / NaN past ``count``.  ``Q`` is :attr:`queue_capacity`.  Reads state only; ``out``: a
+        dict of preallocated buffers by these names (numpy arrays or torch tensors, as ``out`` in :meth:`action_masks`)."""
+        res = self._rank_buffers(self.RUNNING_SERVICE_FIELDS, out, "running_services")
+        _lib.check(self.L.orlg_get_running_services(self.h, *(_ptr(res[f[0]]) for f in self.RUNNING_SERVICE_FIELDS)))
+        return res
+
+    def _gn_gate_struct(self, g):
+        """(orlg_rmsa_gn_gate, the arrays it points to) of a checked gate dict; the library copies what it needs"""
+        gg = _lib.RmsaGnGate()
+        for name in _osnr.RMSA_GN_GATE_SCALARS:
+            setattr(gg, name, float(g[name]))
+        keep = [np.ascontiguousarray(g["link_num_spans"], np.int32), np.ascontiguousarray(g["link_span_length_km"], np.float64),
+                np.ascontiguousarray(g["thresholds_db"], np.float64)]
+        gg.link_num_spans, gg.link_span_length_km, gg.thresholds_db = (a.ctypes.data_as(C.c_void_p) for a in keep)
+        gg.num_thresholds = len(keep[2])
+        return gg, keep
+
+    def qot_audit(self, gate=None, services=False, by_group=False, out=None):
+        """The GN-model audit of every running lightpath (``orlg_gn_audit``; not in the reference): for every running
+        service its GSNR against the OTHER running services of its environment over the links of its own path -- the victim
+        evaluation of ``protect_running`` without a candidate -- and its margin to the threshold of its modulation.  A dict:
+
+        ``n_running`` [B] int32, ``n_below`` [B] int32 (services with a margin below zero), ``min_margin_db`` [B] float64 (NaN where
+        nothing runs) and ``worst_rank`` [B] int32 (the lowest rank that attains it, -1 where nothing runs);
+        ``services=True`` adds ``gsnr_db``, ``margin_db``, ``osnr_ase_db`` and ``snr_nli_db``, [B, Q] float64 in the rank order of
+        :meth:`running_services`, NaN past ``n_running`` (linear: 1 / GSNR = 1 / ase + 1 / nli);
+        ``by_group=True`` adds ``by_group``: ``services``, ``below`` [G] int64 and ``min_margin_db`` [G] float64 (NaN for a group in
+        which nothing runs), reduced on the host from the [B] arrays over the groups of a sweep handle.
+
+        ``gate``: what :func:`rmsa_gn_gate_parameters` returns, for this call alone -- margins at another launch power, or the
+        audit of traffic an ungated handle built; ``protect_running`` is ignored there, and the handle's own gate stays.  ``None``
+        is the handle's gate; a handle without one raises ``ValueError``.  Served on gated, protecting and ungated handles, after
+        either step kernel.  Reads state only.  ``out``: a dict of preallocated buffers -- the four [B, Q] names (numpy arrays or
+        torch tensors; device tensors are written in place; naming one implies it is returned) and ``summary``, [B, 24] uint8, the
+        ``orlg_gn_audit_summary`` records as the library writes them (the four [B] arrays are then views of it)."""
+        if gate is None and self.gn_gate is None:
+            raise ValueError("qot_audit: the handle has no GN-model admission check (gn_gate=); give the audit a gate= of its own")
+        g = None if gate is None else _osnr.check_rmsa_gn_gate(gate, self.topology)
+        out = dict(out or {})
+        unknown = set(out) - set(self.AUDIT_SERVICE_FIELDS) - {"summary"}
+        if unknown:
+            raise ValueError(f"qot_audit: out= has no buffer named {sorted(unknown)}")
+        B = self.batch_size
+        summary = out.pop("summary", None)
+        if summary is None:
+            summary = np.zeros((B, 24), np.uint8)
+        else:
+            _check_buffer("out['summary']", summary, (B, 24), np.uint8)
+        names = [n for n in self.AUDIT_SERVICE_FIELDS if services or n in out]
+        res = self._rank_buffers([(n, np.float64, True) for n in names], out, "qot_audit")
+        gg, keep = (None, None) if g is None else self._gn_gate_struct(g)
+        _lib.check(self.L.orlg_gn_audit(self.h, None if gg is None else C.byref(gg), _ptr(summary),
+                                        *(_ptr(res.get(n)) for n in self.AUDIT_SERVICE_FIELDS)))
+        del keep
+        if hasattr(summary, "data_ptr"):   # a torch tensor: views of the records, on its device
+            import torch
+            i32 = summary[:, :16].view(torch.int32)
+            head = {"n_running": i32[:, 0], "n_below": i32[:, 1], "worst_rank": i32[:, 2],
+                    "min_margin_db": summary[:, 16:].view(torch.float64)[:, 0]}
+        else:
+            rec = summary.view(_lib.GN_AUDIT_SUMMARY_DTYPE)[:, 0]
+            head = {n: rec[n] for n in ("n_running", "n_below", "worst_rank", "min_margin_db")}
+        if by_group:
+            to_np = lambda a: a.cpu().numpy() if hasattr(a, "data_ptr") else a
+            n, below, worst = (to_np(head[k]) for k in ("n_running", "n_below", "min_margin_db"))
+            G = self.num_groups
+            low = np.full(G, np.inf)
+            np.fmin.at(low, self.groups, worst)   # (fmin: an environment in which nothing runs has NaN and does not count)
+            running = np.bincount(self.groups, weights=n, minlength=G).astype(np.int64)
+            head["by_group"] = {"services": running, "below": np.bincount(self.groups, weights=below, minlength=G).astype(np.int64),
+                                "min_margin_db": np.where(low == np.inf, np.nan, low)}
+        head.update(res)
+        return head
+
     def simple_matrix_observation(self, out=None):
         """SimpleMatrixObservation.observation() for every env: [B, 2N + E*S] uint8 (``rmsa_env.py:940-971``)."""
         dim = self.L.orlg_simple_matrix_obs_dim(self.h)

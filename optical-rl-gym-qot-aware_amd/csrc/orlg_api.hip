@@ -22,6 +22,7 @@ struct orlg_env : OrlgHandle {
     std::vector<uint8_t> path_se;   // spectral efficiency of every path record (orlg_set_gn_gate checks the thresholds against it)
     double *gn_table = nullptr;     // the gate's table on the device (allocated with the first gate; OrlgParams::gn = it or nullptr)
     bool gn_protect = false;        // the gate also protects the running lightpaths (orlg_set_gn_protect; configuration, not state)
+    double *audit_table = nullptr;  // the table of a gate given with orlg_gn_audit (allocated with the first such call; never OrlgParams::gn)
 };
 enum { X_ACTIONS, X_GSNR, X_CAUSE, X_CAUSE_COUNTS, X_MARGIN };   // OrlgHandle::extra: external actions from / the gn_gsnr_db, block_cause, cause_counts and gn_neighbour_margin_db outputs for host memory
 static_assert(X_MARGIN < ORLG_EXTRA_SLOTS, "OrlgHandle::extra");
@@ -780,16 +781,9 @@ int orlg_step_rule_gn(orlg_env *e, int32_t route, int32_t rule, int32_t gn_mode,
     return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, assign, 3);
 }
 
-int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    HIP_TRY(hipSetDevice(e->device));
-    if (!g) {
-        e->p.gn = nullptr;
-        e->gn_protect = false;   // (protection is a property of the gate: a new gate keeps it, no gate has none)
-        return ORLG_OK;
-    }
-    if (e->group_mode == ORLG_KERNEL_GROUP)
-        return fail(ORLG_ERR_INVALID, "gn_gate: the admission check is served by the wave-per-environment kernel, the handle was created with step_kernel GROUP");
+// the rules of a gate and its table (ORLG_GN_*, orlg_device.h) for this handle's topology: what orlg_set_gn_gate installs and what
+// orlg_gn_audit builds for a gate given with the call
+static int gn_gate_table(const orlg_env *e, const orlg_rmsa_gn_gate *g, std::vector<double> &tab) {
     const int E = e->p.E;
     if (!g->link_num_spans || !g->link_span_length_km || !g->thresholds_db) return fail(ORLG_ERR_INVALID, "null argument");
     const struct { const char *name; double v; } scalars[] = {
@@ -807,7 +801,7 @@ int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
         if (e->path_se[gid] > 6)
             return fail(ORLG_ERR_INVALID, "gn_gate: path %zu has spectral efficiency %d, the modulation factors of the GN model end at 6", gid, e->path_se[gid]);
     }
-    std::vector<double> tab(ORLG_GN_LINK0 + 4 * (size_t)E, 0.0);
+    tab.assign(ORLG_GN_LINK0 + 4 * (size_t)E, 0.0);
     const double att = g->attenuation_normalized;
     tab[ORLG_GN_DENSITY] = g->launch_power_density_w_hz; tab[ORLG_GN_F0] = g->frequency_start_hz; tab[ORLG_GN_SLOT] = g->slot_width_hz;
     tab[ORLG_GN_ATT] = att; tab[ORLG_GN_NF] = g->noise_figure; tab[ORLG_GN_LEFF_A] = 1 / (2 * att);
@@ -823,6 +817,21 @@ int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
         double *row = &tab[ORLG_GN_LINK0 + 4 * (size_t)l];
         row[0] = l_eff; row[1] = l_eff / (len * 1e3); row[2] = e1; row[3] = (double)g->link_num_spans[l];
     }
+    return ORLG_OK;
+}
+
+int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    HIP_TRY(hipSetDevice(e->device));
+    if (!g) {
+        e->p.gn = nullptr;
+        e->gn_protect = false;   // (protection is a property of the gate: a new gate keeps it, no gate has none)
+        return ORLG_OK;
+    }
+    if (e->group_mode == ORLG_KERNEL_GROUP)
+        return fail(ORLG_ERR_INVALID, "gn_gate: the admission check is served by the wave-per-environment kernel, the handle was created with step_kernel GROUP");
+    std::vector<double> tab;
+    if (int rc = gn_gate_table(e, g, tab)) return rc;
     if (!e->gn_table)
         if (int rc = orlg_handle_alloc(e, &e->gn_table, tab.size())) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));   // (a launch in flight may be reading the table)
@@ -1187,6 +1196,72 @@ int orlg_gn_path_windows(orlg_env *e, int32_t rule, int16_t *slots_out, double *
                        reinterpret_cast<int16_t *>(slots[0].dev), reinterpret_cast<double *>(slots[1].dev), reinterpret_cast<uint8_t *>(slots[2].dev));
     HIP_TRY(hipGetLastError());
     return collect_outputs(e, slots, 3);
+}
+
+// ---- the running services and their GN-model audit (orlg_gn_audit_kernels.hip)
+int orlg_queue_capacity(orlg_env *e) { return e ? e->p.Q : ORLG_ERR_INVALID; }
+
+int orlg_get_running_services(orlg_env *e, int32_t *count, int32_t *head, int32_t *path_gid, int16_t *slot, int16_t *num_slots,
+                              int32_t *bit_rate, double *release_time) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!count && !head && !path_gid && !slot && !num_slots && !bit_rate && !release_time)
+        return fail(ORLG_ERR_INVALID, "null argument: no buffer of the running services");
+    HIP_TRY(hipSetDevice(e->device));
+    const OrlgParams &p = e->p;
+    const size_t B = (size_t)p.B, bq = B * p.Q;
+    OutSlot slots[7] = {{count, B * 4}, {head, B * 4}, {path_gid, bq * 4}, {slot, bq * 2}, {num_slots, bq * 2}, {bit_rate, bq * 4},
+                        {release_time, bq * 8}};
+    int rc = place_outputs(e, slots, 7);
+    if (rc) return rc;
+    size_t nblocks = (bq + 255) / 256;
+    if (nblocks > (size_t)8 * e->num_cu) nblocks = (size_t)8 * e->num_cu;
+    hipLaunchKernelGGL(orlg_running_services_kernel_lookup(), dim3((unsigned)nblocks), dim3(256), 0, e->stream, p,
+                       reinterpret_cast<int32_t *>(slots[0].dev), reinterpret_cast<int32_t *>(slots[1].dev),
+                       reinterpret_cast<int32_t *>(slots[2].dev), reinterpret_cast<int16_t *>(slots[3].dev),
+                       reinterpret_cast<int16_t *>(slots[4].dev), reinterpret_cast<int32_t *>(slots[5].dev),
+                       reinterpret_cast<double *>(slots[6].dev));
+    HIP_TRY(hipGetLastError());
+    return collect_outputs(e, slots, 7);
+}
+
+int orlg_gn_audit(orlg_env *e, const orlg_rmsa_gn_gate *gate, orlg_gn_audit_summary *summary, double *gsnr_db, double *margin_db,
+                  double *osnr_ase_db, double *snr_nli_db) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!summary && !gsnr_db && !margin_db && !osnr_ase_db && !snr_nli_db)
+        return fail(ORLG_ERR_INVALID, "null argument: no summary or per-service buffer");
+    if (!gate && !e->p.gn) return fail(ORLG_ERR_INVALID, "gn audit: the handle has no gn_gate and none was given with the call");
+    HIP_TRY(hipSetDevice(e->device));
+    const OrlgParams &p = e->p;
+    const double *table = p.gn;
+    if (gate) {   // a table of this call's own: the handle's configuration stays what it is
+        std::vector<double> tab;
+        if (int rc = gn_gate_table(e, gate, tab)) return rc;
+        if (!e->audit_table)
+            if (int rc = orlg_handle_alloc(e, &e->audit_table, tab.size())) return rc;
+        HIP_TRY(hipStreamSynchronize(e->stream));   // (an audit in flight may be reading the table)
+        HIP_TRY(hipMemcpy(e->audit_table, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+        table = e->audit_table;
+    }
+    const size_t B = (size_t)p.B, bq = B * p.Q * sizeof(double);
+    OutSlot slots[5] = {{summary, B * sizeof(orlg_gn_audit_summary)}, {gsnr_db, bq}, {margin_db, bq}, {osnr_ase_db, bq}, {snr_nli_db, bq}};
+    int rc = place_outputs(e, slots, 5);
+    if (rc) return rc;
+    // a wave holds the live descriptors of its environment's release ring (up to Q): as many waves per workgroup as the LDS takes
+    // next to the tables
+    const size_t per_wave = (size_t)((p.Q * 4 + 15) & ~15);
+    int wpb = e->waves_per_block;
+    while (wpb > 1 && (size_t)p.l_shared_bytes + per_wave * wpb > ORLG_LDS_BYTES) --wpb;
+    const size_t lds = (size_t)p.l_shared_bytes + per_wave * wpb;
+    if (lds > ORLG_LDS_BYTES) return fail(ORLG_ERR_INVALID, "gn audit: a release queue of %d entries does not fit the LDS next to the tables", p.Q);
+    orlg_gn_audit_kernel_t k = orlg_gn_audit_kernel_lookup();
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int nblocks = (p.B + wpb - 1) / wpb;
+    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;   // as orlg_gn_action_masks: each wave strides over its environments
+    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, table, reinterpret_cast<orlg_gn_audit_summary *>(slots[0].dev),
+                       reinterpret_cast<double *>(slots[1].dev), reinterpret_cast<double *>(slots[2].dev),
+                       reinterpret_cast<double *>(slots[3].dev), reinterpret_cast<double *>(slots[4].dev));
+    HIP_TRY(hipGetLastError());
+    return collect_outputs(e, slots, 5);
 }
 
 int orlg_simple_matrix_obs_dim(orlg_env *e) { return e ? 2 * e->p.N + e->p.E * e->p.S : ORLG_ERR_INVALID; }

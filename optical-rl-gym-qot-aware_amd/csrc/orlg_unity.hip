@@ -11,5 +11,6 @@
 #include "orlg_inst_wave.hip"
 #include "orlg_inst_gnrules.hip"
 #include "orlg_inst_gnprotect.hip"
+#include "orlg_gn_audit_kernels.hip"
 #include "orlg_inst_group.hip"
 #include "orlg_inst_phy.hip"

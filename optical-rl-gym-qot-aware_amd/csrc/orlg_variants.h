@@ -229,6 +229,11 @@ typedef void (*orlg_min_cuts_kernel_t)(const OrlgParams, int16_t *, int16_t *); 
 typedef void (*orlg_usage_kernel_t)(const OrlgParams, uint8_t *, int32_t *, int16_t *);     // orlg_usage_kernel
 typedef void (*orlg_gn_path_windows_kernel_t)(const OrlgParams, int, int16_t *, double *, uint8_t *);   // orlg_gn_path_windows_kernel
 typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
+// orlg_gn_audit_kernels.hip: the two kernels of the audit know no word count -- one object, one lookup each, no W
+typedef void (*orlg_gn_audit_kernel_t)(const OrlgParams, const double *, orlg_gn_audit_summary *, double *, double *, double *, double *);
+typedef void (*orlg_running_services_kernel_t)(const OrlgParams, int32_t *, int32_t *, int32_t *, int16_t *, int16_t *, int32_t *, double *);
+orlg_gn_audit_kernel_t orlg_gn_audit_kernel_lookup();
+orlg_running_services_kernel_t orlg_running_services_kernel_lookup();
 #define ORLG_FOR_EACH_W(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__) X(6, __VA_ARGS__) X(8, __VA_ARGS__)
 #define ORLG_FOR_EACH_PHY_W(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__)
 #define ORLG_DECL_W(n, ...)                                                                       \

@@ -299,6 +299,21 @@ class RMSAEnv(_View):
             m[k, S] = True
         return m
 
+    def qot_audit(self, gate=None):
+        """The GN-model audit of this environment's running lightpaths (``BatchedRMSAEnv.qot_audit``; not in the reference): a dict
+        -- ``n_running``, ``n_below``, ``worst_rank`` (ints), ``min_margin_db`` (float, NaN when nothing runs) and ``services``, one
+        dict per running service in ascending release time: ``path_gid``, ``slot``, ``num_slots``, ``bit_rate``, ``release_time``,
+        ``gsnr_db``, ``margin_db``, ``osnr_ase_db``, ``snr_nli_db``.  ``gate``: as there."""
+        b, i = self._batched, self._index
+        a = b.qot_audit(gate=gate, services=True)
+        run = b.running_services()
+        n = int(a["n_running"][i])
+        names = ("path_gid", "slot", "num_slots", "bit_rate", "release_time")
+        return {"n_running": n, "n_below": int(a["n_below"][i]), "worst_rank": int(a["worst_rank"][i]),
+                "min_margin_db": float(a["min_margin_db"][i]),
+                "services": [dict({k: run[k][i, r].item() for k in names}, **{k: float(a[k][i, r]) for k in b.AUDIT_SERVICE_FIELDS})
+                             for r in range(n)]}
+
     # ------------------------------------------------------------------ gym surface
     def reset(self, only_episode_counters: bool = True):
         """``rmsa_env.py:343-457``"""
