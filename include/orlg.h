@@ -241,7 +241,8 @@ int orlg_step_gn(orlg_env *env, int32_t policy, int32_t n_steps, const int32_t *
  * Protection is configuration, not state: snapshots cross between protecting, gated and ungated handles.  Every step entry point
  * applies it on a protecting handle (as orlg_step applies the gate); such a handle runs orlg_rmsa_kernel<W,STATS,false,true,CAUSE,
  * false,false,false,true>.  orlg_gn_action_masks, orlg_step_rule_gn and orlg_gn_path_windows know the candidate's own check only:
- * on a protecting handle they would describe a step the handle does not run and return ORLG_ERR_INVALID.
+ * on a protecting handle they would describe a step the handle does not run and return ORLG_ERR_INVALID.  The masks and the rule
+ * windows that know both checks are orlg_gn_admission_masks and orlg_gn_admission_windows below, on any handle with a gate.
  * orlg_set_gn_protect: ORLG_ERR_INVALID on a handle without a gate; orlg_set_gn_gate(env, NULL) clears it, a new gate keeps it. */
 int orlg_set_gn_protect(orlg_env *env, int32_t on);
 struct orlg_step_diag;
@@ -485,6 +486,26 @@ int orlg_action_masks(orlg_env *env, uint8_t *path_ff, uint64_t *slots);
  * The explicit rejection's column (orlg_set_allow_rejection) is always 1 and has no GSNR column.  Any pointer may be NULL; all
  * NULL, or a handle without a gate, is ORLG_ERR_INVALID.  Buffers as orlg_action_masks. */
 int orlg_gn_action_masks(orlg_env *env, uint8_t *path_ff, double *path_ff_gsnr_db, uint8_t *deeprmsa, double *deeprmsa_gsnr_db);
+
+/* The masks and the rule windows that know BOTH halves of the admission check (this project's): they describe the step
+ * THIS handle runs, on any handle with a gate.  A bit is 1 iff the window exists, its own GSNR meets thresholds_db[SE - 1] and, on a
+ * handle that protects its running lightpaths (orlg_set_gn_protect), the NEIGHBOUR MARGIN of the candidate is not below zero --
+ * !(margin < 0.0), the step's own predicate.
+ * orlg_gn_admission_masks: shapes, columns and buffers of orlg_gn_action_masks, plus path_ff_margin_db [B][k] and deeprmsa_margin_db
+ * [B][k*j] float64 -- the candidate's neighbour margin in dB, NaN where the second check would not run (no window, the own check
+ * refuses, no running service shares a link, or the handle does not protect).  Row a of deeprmsa is the outcome of
+ * orlg_step_gn_protect with ORLG_POLICY_DEEPRMSA_EXTERNAL and action a, row p of path_ff with ORLG_POLICY_PATH_FF_EXTERNAL and action
+ * p: the rows have the bits of that step's gn_gsnr_db and gn_neighbour_margin_db.  The rejection's column is always 1 and has no
+ * GSNR or margin column.
+ * orlg_gn_admission_windows: rule, slots, gsnr_db and admitted as orlg_gn_path_windows, plus margin_db [B][k]; row p is the outcome of
+ * orlg_step_gn_protect with ORLG_POLICY_EXTERNAL and action [p, slots[p]].
+ * On a gated handle that does not protect, masks, admitted, slots and GSNR are byte-identical to orlg_gn_action_masks /
+ * orlg_gn_path_windows and every margin is NaN.  Any pointer may be NULL, not all.  ORLG_ERR_INVALID: a handle without a gate, an
+ * unknown rule, all pointers NULL, or a release queue that does not fit the LDS next to the tables.  They read state and write only
+ * the caller's buffers.  Buffers as orlg_action_masks. */
+int orlg_gn_admission_masks(orlg_env *env, uint8_t *path_ff, double *path_ff_gsnr_db, double *path_ff_margin_db, uint8_t *deeprmsa,
+                            double *deeprmsa_gsnr_db, double *deeprmsa_margin_db);
+int orlg_gn_admission_windows(orlg_env *env, int32_t rule, int16_t *slots, double *gsnr_db, double *margin_db, uint8_t *admitted);
 
 /* ---- the running services of every environment, and their GN-model audit (this project's).  Every gate entry above
  * asks whether a CANDIDATE should be lit; these two say how the lightpaths that are already running are doing.  The state they read

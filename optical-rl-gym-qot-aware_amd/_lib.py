@@ -218,7 +218,10 @@ def _prototypes():
               # the running services of every environment and their GN-model audit
               "orlg_queue_capacity": (None, [vp]),
               "orlg_get_running_services": (None, [vp, vp, vp, vp, vp, vp, vp, vp]),
-              "orlg_gn_audit": (None, [vp, P(RmsaGnGate), vp, vp, vp, vp, vp])})
+              "orlg_gn_audit": (None, [vp, P(RmsaGnGate), vp, vp, vp, vp, vp]),
+              # the masks and rule windows that know both halves of the admission check (a protecting handle's too)
+              "orlg_gn_admission_masks": (None, [vp, vp, vp, vp, vp, vp, vp]),
+              "orlg_gn_admission_windows": (None, [vp, i32, vp, vp, vp, vp])})
     # QoT-aware only
     t.update({"orlg_phy_step": (None, [vp, i32, i32, vp, vp, i32, P(PhyStepIO)]), "orlg_phy_node_vectors": (None, [vp]),
               "orlg_phy_get_episode_stats": (None, [vp, vp]), "orlg_phy_channel_masks": (None, [vp, vp]),

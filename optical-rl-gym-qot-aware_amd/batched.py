@@ -377,7 +377,8 @@ class BatchedRMSAEnv(BatchedHandle):
             raise ValueError(f"kind {kind!r} needs a handle with a GN-model admission check (gn_gate=)")
         if gn and self.gn_protect:
             raise ValueError(f"kind {kind!r}: the handle protects its running lightpaths (protect_running); this mask knows the "
-                             "candidate's own check only and would describe a step the handle does not run")
+                             "candidate's own check only and would describe a step the handle does not run: "
+                             f"admission_masks({kind[:-3]!r}) knows both checks")
         if out is None:
             out = np.zeros(shape, dt)
         else:
@@ -479,7 +480,8 @@ class BatchedRMSAEnv(BatchedHandle):
             raise ValueError("path_rule_windows needs a handle with a GN-model admission check (gn_gate=)")
         if self.gn_protect:
             raise ValueError("path_rule_windows: the handle protects its running lightpaths (protect_running); this query knows the "
-                             "candidate's own check only and would describe a step the handle does not run")
+                             "candidate's own check only and would describe a step the handle does not run: "
+                             "admission_windows(rule) knows both checks")
         shape = (self.batch_size, self.k_paths)
         res = []
         for name, buf, dt in (("slots_out", slots_out, np.int16), ("gsnr_out", gsnr_out, np.float64), ("admitted_out", admitted_out, np.uint8)):
@@ -490,6 +492,81 @@ class BatchedRMSAEnv(BatchedHandle):
             res.append(buf)
         _lib.check(self.L.orlg_gn_path_windows(self.h, _lib.GN_PATH_WINDOW_RULES[rule], _ptr(res[0]), _ptr(res[1]), _ptr(res[2])))
         return res[0], res[1], res[2]
+
+    # ------------------------------------------------------------------ masks and rule windows that know both halves of the check
+    ADMISSION_MASK_KINDS = ("path_ff", "deeprmsa")
+
+    def _float_rows(self, name, buf, shape):
+        """a float64 row buffer of a query: None / False = not asked for, True = a new array, else the caller's, checked"""
+        if buf is None or buf is False:
+            return None
+        if buf is True:
+            return np.zeros(shape, np.float64)
+        _check_buffer(name, buf, shape, np.float64)
+        if not hasattr(buf, "data_ptr") and not buf.flags["WRITEABLE"]:
+            raise ValueError(f"{name}: read-only array")
+        return buf
+
+    def admission_masks(self, kind, out=None, gsnr_out=None, margin_out=None):
+        """Valid actions of every env's pending request under BOTH halves of the GN-model admission check
+        (``orlg_gn_admission_masks``; a handle with ``gn_gate=`` only): ``mask[a] = 1`` iff the step THIS handle runs
+        would accept the service -- the window exists, its own GSNR meets the threshold of the path's modulation and, on a handle
+        that protects its running lightpaths (``protect_running``), no running service that shares a link falls below its own
+        threshold (the neighbour margin is not below zero).  ``kind``: ``"path_ff"`` [B, k + reject] uint8, the outcome of
+        ``run("path_ff_external", actions=p)``, or ``"deeprmsa"`` [B, k*j + reject], the outcome of ``run("deeprmsa_external",
+        actions=a)``; the explicit rejection's column is always 1.  ``gsnr_out`` / ``margin_out``: a float64 buffer [B, k] / [B, k*j]
+        or ``True`` for a new array -- the bits of that step's ``gn_gsnr_db`` (NaN = no window) and ``gn_neighbour_margin_db`` (NaN =
+        the second check would not run: no window, the own check refuses, no running service shares a link, or the handle does not
+        protect).  Returns ``mask``, or a tuple ``(mask[, gsnr][, margin])`` with the rows that were asked for.  On a gated handle
+        that does not protect the mask and the GSNR are those of ``action_masks(kind + "_gn")``.  Reads state only; the buffers as
+        ``out`` in :meth:`action_masks`."""
+        if kind not in self.ADMISSION_MASK_KINDS:
+            raise ValueError(f"kind {kind!r}: expected one of {self.ADMISSION_MASK_KINDS}")
+        if self.gn_gate is None:
+            raise ValueError("admission_masks needs a handle with a GN-model admission check (gn_gate=)")
+        shape, dt = self.action_mask_shape(kind)
+        rows = (self.batch_size, self.k_paths * (self.j if kind == "deeprmsa" else 1))
+        if out is None:
+            out = np.zeros(shape, dt)
+        else:
+            _check_buffer("out", out, shape, dt)
+            if not hasattr(out, "data_ptr") and not out.flags["WRITEABLE"]:
+                raise ValueError("out: read-only array")
+        gsnr = self._float_rows("gsnr_out", gsnr_out, rows)
+        margin = self._float_rows("margin_out", margin_out, rows)
+        ptrs = (_ptr(out), None if gsnr is None else _ptr(gsnr), None if margin is None else _ptr(margin))
+        if kind == "path_ff":
+            _lib.check(self.L.orlg_gn_admission_masks(self.h, *ptrs, None, None, None))
+        else:
+            _lib.check(self.L.orlg_gn_admission_masks(self.h, None, None, None, *ptrs))
+        res = (out,) + tuple(r for r in (gsnr, margin) if r is not None)
+        return out if len(res) == 1 else res
+
+    def admission_windows(self, rule, slots_out=None, gsnr_out=None, margin_out=None, admitted_out=None):
+        """The window an assignment rule proposes on every candidate path of every env's pending request, and what BOTH halves of
+        the GN-model admission check say to it (``orlg_gn_admission_windows``; a handle with ``gn_gate=`` only):
+        ``(slots, gsnr, margin, admitted)`` -- slots, gsnr and admitted as :meth:`path_rule_windows`, margin [B, k] float64 the
+        candidate's neighbour margin in dB (NaN as in :meth:`admission_masks`).  ``rule``: one of ``_lib.GN_PATH_WINDOW_RULES``.
+        Row ``p`` is the outcome of ``run("external", actions=[p, slots[p]])`` on this handle, with the bits of its ``gn_gsnr_db``
+        and ``gn_neighbour_margin_db``.  On a gated handle that does not protect slots, gsnr and admitted are those of
+        :meth:`path_rule_windows` and every margin is NaN.  Reads state only; the buffers as ``out`` in :meth:`action_masks`."""
+        if rule not in _lib.GN_PATH_WINDOW_RULES:
+            raise ValueError(f"rule {rule!r}: expected one of {tuple(_lib.GN_PATH_WINDOW_RULES)}")
+        if self.gn_gate is None:
+            raise ValueError("admission_windows needs a handle with a GN-model admission check (gn_gate=)")
+        shape = (self.batch_size, self.k_paths)
+        res = []
+        for name, buf, dt in (("slots_out", slots_out, np.int16), ("gsnr_out", gsnr_out, np.float64), ("margin_out", margin_out, np.float64),
+                              ("admitted_out", admitted_out, np.uint8)):
+            if buf is None:
+                buf = np.zeros(shape, dt)
+            else:
+                _check_buffer(name, buf, shape, dt)
+                if not hasattr(buf, "data_ptr") and not buf.flags["WRITEABLE"]:
+                    raise ValueError(f"{name}: read-only array")
+            res.append(buf)
+        _lib.check(self.L.orlg_gn_admission_windows(self.h, _lib.GN_PATH_WINDOW_RULES[rule], *(_ptr(b) for b in res)))
+        return tuple(res)
 
     # ------------------------------------------------------------------ the running services and their GN-model audit
     RUNNING_SERVICE_FIELDS = (("count", np.int32, False), ("head", np.int32, False), ("path_gid", np.int32, True),

@@ -1140,7 +1140,7 @@ int orlg_gn_action_masks(orlg_env *e, uint8_t *path_ff, double *path_ff_gsnr_db,
     if (!path_ff && !path_ff_gsnr_db && !deeprmsa && !deeprmsa_gsnr_db) return fail(ORLG_ERR_INVALID, "null argument: no mask or GSNR buffer");
     if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn action masks: the handle has no gn_gate");
     if (e->gn_protect)
-        return fail(ORLG_ERR_INVALID, "gn action masks: the handle protects its running lightpaths (orlg_set_gn_protect); these masks know the candidate's own check only and would describe a step this handle does not run");
+        return fail(ORLG_ERR_INVALID, "gn action masks: the handle protects its running lightpaths (orlg_set_gn_protect); these masks know the candidate's own check only and would describe a step this handle does not run: orlg_gn_admission_masks knows both checks");
     HIP_TRY(hipSetDevice(e->device));
     const OrlgParams &p = e->p;
     const size_t B = (size_t)p.B, kj = (size_t)p.K * p.j;
@@ -1172,7 +1172,7 @@ int orlg_gn_path_windows(orlg_env *e, int32_t rule, int16_t *slots_out, double *
     if (!slots_out && !gsnr_db && !admitted) return fail(ORLG_ERR_INVALID, "null argument: no slots, GSNR or admitted buffer");
     if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn path windows: the handle has no gn_gate");
     if (e->gn_protect)
-        return fail(ORLG_ERR_INVALID, "gn path windows: the handle protects its running lightpaths (orlg_set_gn_protect); this query knows the candidate's own check only and would describe a step this handle does not run");
+        return fail(ORLG_ERR_INVALID, "gn path windows: the handle protects its running lightpaths (orlg_set_gn_protect); this query knows the candidate's own check only and would describe a step this handle does not run: orlg_gn_admission_windows knows both checks");
     if ((rule < ORLG_ASSIGN_FIRST || rule >= ORLG_NUM_ASSIGN_RULES) && rule != ORLG_RULE_FEWEST_CUTS)
         return fail(ORLG_ERR_INVALID, "gn path windows: unknown rule %d (ORLG_ASSIGN_FIRST .. EXACT or ORLG_RULE_FEWEST_CUTS)", rule);
     HIP_TRY(hipSetDevice(e->device));
@@ -1196,6 +1196,75 @@ int orlg_gn_path_windows(orlg_env *e, int32_t rule, int16_t *slots_out, double *
                        reinterpret_cast<int16_t *>(slots[0].dev), reinterpret_cast<double *>(slots[1].dev), reinterpret_cast<uint8_t *>(slots[2].dev));
     HIP_TRY(hipGetLastError());
     return collect_outputs(e, slots, 3);
+}
+
+// ---- the masks and rule windows that know both halves of the check (orlg_gn_admission_kernels.hip)
+// as orlg_gn_action_masks: a wave holds its environment's occupancy row and the live descriptors of its release ring (up to Q) -- as
+// many waves per workgroup as the LDS takes next to the tables.  0: the queue does not fit
+static size_t gn_admission_lds(const orlg_env *e, int &wpb) {
+    const OrlgParams &p = e->p;
+    const size_t per_wave = (size_t)((p.NW * 8 + 15) & ~15) + (size_t)((p.Q * 4 + 15) & ~15);
+    wpb = e->waves_per_block;
+    while (wpb > 1 && (size_t)p.l_shared_bytes + per_wave * wpb > ORLG_LDS_BYTES) --wpb;
+    const size_t lds = (size_t)p.l_shared_bytes + per_wave * wpb;
+    return lds > ORLG_LDS_BYTES ? 0 : lds;
+}
+
+int orlg_gn_admission_masks(orlg_env *e, uint8_t *path_ff, double *path_ff_gsnr_db, double *path_ff_margin_db, uint8_t *deeprmsa,
+                            double *deeprmsa_gsnr_db, double *deeprmsa_margin_db) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!path_ff && !path_ff_gsnr_db && !path_ff_margin_db && !deeprmsa && !deeprmsa_gsnr_db && !deeprmsa_margin_db)
+        return fail(ORLG_ERR_INVALID, "null argument: no mask, GSNR or margin buffer");
+    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn admission masks: the handle has no gn_gate");
+    HIP_TRY(hipSetDevice(e->device));
+    const OrlgParams &p = e->p;
+    const size_t B = (size_t)p.B, kj = (size_t)p.K * p.j;
+    OutSlot slots[6] = {{path_ff, B * (p.K + e->allow_rejection)}, {path_ff_gsnr_db, B * p.K * sizeof(double)},
+                        {path_ff_margin_db, B * p.K * sizeof(double)}, {deeprmsa, B * (kj + e->allow_rejection)},
+                        {deeprmsa_gsnr_db, B * kj * sizeof(double)}, {deeprmsa_margin_db, B * kj * sizeof(double)}};
+    int rc = place_outputs(e, slots, 6);
+    if (rc) return rc;
+    orlg_gn_admission_masks_kernel_t k = orlg_pick_gn_admission_masks(e->W);
+    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
+    int wpb;
+    const size_t lds = gn_admission_lds(e, wpb);
+    if (!lds) return fail(ORLG_ERR_INVALID, "gn admission masks: a release queue of %d entries does not fit the LDS next to the tables", p.Q);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int nblocks = (p.B + wpb - 1) / wpb;
+    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;   // as orlg_action_masks: each wave strides over its environments
+    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, reinterpret_cast<uint8_t *>(slots[0].dev),
+                       reinterpret_cast<double *>(slots[1].dev), reinterpret_cast<double *>(slots[2].dev),
+                       reinterpret_cast<uint8_t *>(slots[3].dev), reinterpret_cast<double *>(slots[4].dev),
+                       reinterpret_cast<double *>(slots[5].dev), e->allow_rejection, e->gn_protect ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    return collect_outputs(e, slots, 6);
+}
+
+int orlg_gn_admission_windows(orlg_env *e, int32_t rule, int16_t *slots_out, double *gsnr_db, double *margin_db, uint8_t *admitted) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!slots_out && !gsnr_db && !margin_db && !admitted) return fail(ORLG_ERR_INVALID, "null argument: no slots, GSNR, margin or admitted buffer");
+    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn admission windows: the handle has no gn_gate");
+    if ((rule < ORLG_ASSIGN_FIRST || rule >= ORLG_NUM_ASSIGN_RULES) && rule != ORLG_RULE_FEWEST_CUTS)
+        return fail(ORLG_ERR_INVALID, "gn admission windows: unknown rule %d (ORLG_ASSIGN_FIRST .. EXACT or ORLG_RULE_FEWEST_CUTS)", rule);
+    HIP_TRY(hipSetDevice(e->device));
+    const OrlgParams &p = e->p;
+    const size_t bk = (size_t)p.B * p.K;
+    OutSlot slots[4] = {{slots_out, bk * sizeof(int16_t)}, {gsnr_db, bk * sizeof(double)}, {margin_db, bk * sizeof(double)}, {admitted, bk}};
+    int rc = place_outputs(e, slots, 4);
+    if (rc) return rc;
+    orlg_gn_admission_windows_kernel_t k = orlg_pick_gn_admission_windows(e->W);
+    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
+    int wpb;
+    const size_t lds = gn_admission_lds(e, wpb);
+    if (!lds) return fail(ORLG_ERR_INVALID, "gn admission windows: a release queue of %d entries does not fit the LDS next to the tables", p.Q);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int nblocks = (p.B + wpb - 1) / wpb;
+    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;
+    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, rule == ORLG_RULE_FEWEST_CUTS ? (int)ORLG_ASSIGN_MIN_CUT : (int)rule,
+                       reinterpret_cast<int16_t *>(slots[0].dev), reinterpret_cast<double *>(slots[1].dev),
+                       reinterpret_cast<double *>(slots[2].dev), reinterpret_cast<uint8_t *>(slots[3].dev), e->gn_protect ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    return collect_outputs(e, slots, 4);
 }
 
 // ---- the running services and their GN-model audit (orlg_gn_audit_kernels.hip)

@@ -228,6 +228,9 @@ typedef void (*orlg_fit_levels_kernel_t)(const OrlgParams, uint8_t *);          
 typedef void (*orlg_min_cuts_kernel_t)(const OrlgParams, int16_t *, int16_t *);                // orlg_min_cuts_kernel
 typedef void (*orlg_usage_kernel_t)(const OrlgParams, uint8_t *, int32_t *, int16_t *);     // orlg_usage_kernel
 typedef void (*orlg_gn_path_windows_kernel_t)(const OrlgParams, int, int16_t *, double *, uint8_t *);   // orlg_gn_path_windows_kernel
+// orlg_gn_admission_kernels.hip: masks / rule windows that know both halves of the GN-model admission check
+typedef void (*orlg_gn_admission_masks_kernel_t)(const OrlgParams, uint8_t *, double *, double *, uint8_t *, double *, double *, int, int);
+typedef void (*orlg_gn_admission_windows_kernel_t)(const OrlgParams, int, int16_t *, double *, double *, uint8_t *, int);
 typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
 // orlg_gn_audit_kernels.hip: the two kernels of the audit know no word count -- one object, one lookup each, no W
 typedef void (*orlg_gn_audit_kernel_t)(const OrlgParams, const double *, orlg_gn_audit_summary *, double *, double *, double *, double *);
@@ -248,6 +251,8 @@ orlg_running_services_kernel_t orlg_running_services_kernel_lookup();
     orlg_rmsa_kernel_t orlg_gnrules_kernel_W##n(OrlgWaveKey) __attribute__((weak));   /* orlg_inst_gnrules.hip */ \
     orlg_gn_path_windows_kernel_t orlg_gn_path_windows_kernel_W##n() __attribute__((weak));       \
     orlg_rmsa_kernel_t orlg_gnprotect_kernel_W##n(OrlgWaveKey) __attribute__((weak));   /* orlg_inst_gnprotect.hip */ \
+    orlg_gn_admission_masks_kernel_t orlg_gn_admission_masks_kernel_W##n() __attribute__((weak));   /* orlg_inst_gnadmit.hip */ \
+    orlg_gn_admission_windows_kernel_t orlg_gn_admission_windows_kernel_W##n() __attribute__((weak)); \
     orlg_rmsa_kernel_t orlg_group_kernel_W##n(OrlgGroupKey) __attribute__((weak));
 #define ORLG_DECL_PHY_W(n, ...)                                                                   \
     orlg_phy_kernel_t orlg_phy_kernel_W##n(OrlgPhyKey) __attribute__((weak));                     \
@@ -279,3 +284,5 @@ static orlg_min_cuts_kernel_t orlg_pick_min_cuts(int W) { ORLG_PICK(ORLG_FOR_EAC
 static orlg_usage_kernel_t orlg_pick_usage(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_usage_kernel_W, ) }
 static orlg_gn_action_masks_kernel_t orlg_pick_gn_action_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_action_masks_kernel_W, ) }
 static orlg_gn_path_windows_kernel_t orlg_pick_gn_path_windows(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_path_windows_kernel_W, ) }
+static orlg_gn_admission_masks_kernel_t orlg_pick_gn_admission_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_admission_masks_kernel_W, ) }
+static orlg_gn_admission_windows_kernel_t orlg_pick_gn_admission_windows(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_admission_windows_kernel_W, ) }

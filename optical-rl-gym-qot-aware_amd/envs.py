@@ -445,7 +445,10 @@ class DeepRMSAEnv(RMSAEnv):
     def action_masks(self, gn=False):
         """Valid actions of ``Discrete(k*j + reject)`` for the pending request: bool [k*j + reject], True where ``step(a)``
         would accept the service (the method maskable-PPO implementations look for).  ``gn=True`` (a ``gn_gate=`` environment):
-        the mask that knows the GN-model admission check, ``BatchedRMSAEnv.action_masks("deeprmsa_gn")``."""
+        the mask that knows the GN-model admission check, ``BatchedRMSAEnv.action_masks("deeprmsa_gn")`` -- and, where the gate
+        protects the running lightpaths, both halves of it: ``BatchedRMSAEnv.admission_masks("deeprmsa")``."""
+        if gn and self._batched.gn_protect:
+            return self._batched.admission_masks("deeprmsa")[self._index].astype(bool)
         return self._batched.action_masks("deeprmsa_gn" if gn else "deeprmsa")[self._index].astype(bool)
 
 
@@ -517,7 +520,8 @@ class PathOnlyFirstFitAction:
 
     def action_masks(self, gn=False):
         """Valid paths for the pending request: bool [k + reject], True where ``action(p)`` finds a slot.  ``gn=True`` (a
-        ``gn_gate=`` environment): ... and the GN-model admission check admits that window (``"path_ff_gn"``).  With
+        ``gn_gate=`` environment): ... and the GN-model admission check admits that window (``"path_ff_gn"``; where the gate
+        protects the running lightpaths, both halves of the check: ``BatchedRMSAEnv.admission_masks("path_ff")``).  With
         ``assign=`` another rule: the paths that have a window, ``path_fit_levels() >= 3`` (no mask kernel of its own)."""
         if self.assign != "first":
             if gn:
@@ -526,6 +530,8 @@ class PathOnlyFirstFitAction:
             m = np.ones(e.k_paths + e.reject_action, bool)
             m[:e.k_paths] = e._batched.path_fit_levels()[e._index] >= 3
             return m
+        if gn and self._inner._batched.gn_protect:
+            return self._inner._batched.admission_masks("path_ff")[self._inner._index].astype(bool)
         return self._inner._batched.action_masks("path_ff_gn" if gn else "path_ff")[self._inner._index].astype(bool)
 
     def step(self, action):
