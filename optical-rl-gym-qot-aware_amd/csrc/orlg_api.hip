@@ -5,6 +5,7 @@
 #include "orlg_host.h"
 #include "orlg_group_plan.h"
 #include "orlg_wave.h"   // valid_mask, ORLG_INF_BITS for the helper kernels; the step kernels are instantiated in orlg_inst_*.hip
+#include "orlg_graph_log.h"   // ORLG_GLOG_MAX_Q: the queue capacity the lean body's packed log is sized for
 
 // ---------------------------------------------------------------------------------------- handle
 struct orlg_env : OrlgHandle {
@@ -385,6 +386,7 @@ static int rmsa_create(const orlg_topology *t, const orlg_rmsa_config *c, int32_
     Q = ((Q + 15) / 16) * 16;   // 16 slots = one row of the four-environments-per-wave kernel, 128 bytes of times
     if (Q < 64) Q = 64;
     if (Q > 4096) return fail(ORLG_ERR_INVALID, "queue_capacity %d too large for LDS (max 4096)", Q);
+    static_assert(4096 <= ORLG_GLOG_MAX_Q, "the lean body's graph log packs the bit rates of a full queue (orlg_graph_log.h)");
     p.Q = Q;
     {
         char msg[192];

@@ -8,7 +8,9 @@
 //
 // LEAN compiles out what a first-fit launch without per-step outputs and with discrete bit rates never runs: the external,
 // path-only, DeepRMSA and load-balancing policies, the validation of an external action, the per-step outputs (`done`
-// included) and the continuous bit-rate refill.  Everything else is the same operations on the same values.
+// included) and the continuous bit-rate refill.  Everything else is the same operations on the same values -- the graph statistics
+// of an accepted provision too, but later: LEAN logs what _update_network_stats consumes and works the log off in batches
+// (orlg_graph_log.h, group_graph_replay).
     static_assert(!DEFER || (STATS >= 2 && !HBMQ), "the deferred link statistics belong to long launches with full statistics");
     static_assert(!(TRACE && TRAFFIC), "a trace handle has no arrival rates");
     static_assert(!LEAN || DEFER, "the lean body belongs to the long launches");
@@ -139,8 +141,13 @@
     int sum_span = gs->sum_span, sum_gaps = gs->sum_gaps;
     int eproc = (int)gs->c[2];
     wave_sync();
+    // LEAN: the graph statistics are logged per accepted provision and worked off in batches (orlg_graph_log.h, group_graph_replay):
+    // entry k of the row's environment on lane k of the row, lg_cnt of them.  g_thr, g_comp, g_lu and comp_cur are then names
+    // nothing reads: between two replays the three doubles rest in the scalars record, and the body has no use for the compactness
+    [[maybe_unused]] OrlgGraphEntry lg = {0.0, 0u, 0u, 0u};
+    [[maybe_unused]] int lg_cnt = 0;
     double comp_cur = 1.0;
-    if (NET) comp_cur = network_compactness(sum_span, sum_sh, sum_gaps, E);
+    if (NET && !LEAN) comp_cur = network_compactness(sum_span, sum_sh, sum_gaps, E);
     if (DEFER)   // the summaries of all E links, from the occupancy just loaded
         group_link_stats<W, true, false, true, 2>(lane, occ, nullptr, lint, tb, S, E, nullptr, E, 0.0, sum_span, sum_gaps, comp_cur,
                                                   0, 0.0, g_thr, g_comp, g_lu, nullptr, nullptr, lsum);
@@ -430,10 +437,22 @@
         }
         SEC(4);  // statistics at provision
         if (NET)
-            group_link_stats<W, FULL, true, DEFER, DEFER ? 1 : 0, true>(lane, occ, lst, lint, tb, S, E, rec->link, accepted ? hops : 0,
-                                                                          current_time, sum_span, sum_gaps, comp_cur, sum_sh,
-                                                                          (double)sum_bitrate_running, g_thr, g_comp, g_lu, llog,
-                                                                          &need_replay, lsum, a_slot, n);
+            group_link_stats<W, FULL, !LEAN, DEFER, DEFER ? 1 : 0, true>(lane, occ, lst, lint, tb, S, E, rec->link, accepted ? hops : 0,
+                                                                           current_time, sum_span, sum_gaps, comp_cur, sum_sh,
+                                                                           (double)sum_bitrate_running, g_thr, g_comp, g_lu, llog,
+                                                                           &need_replay, lsum, a_slot, n);
+        if constexpr (LEAN) {
+            // _update_network_stats (rmsa_env.py:537-560) of an accepted row, logged: what it consumes, as the pass above left it
+            const bool logs = accepted && hops > 0;
+            OrlgGraphEntry ne;
+            orlg_glog_pack(ne, current_time, sum_bitrate_running, sum_span, sum_sh, sum_gaps);
+            if (logs && gl == lg_cnt) lg = ne;
+            lg_cnt += logs ? 1 : 0;
+            if (ballot(lg_cnt >= ORLG_GLOG_CAP) != 0ull) {   // a row's log is full: every row works its log off
+                SEC(15);  // graph replay
+                group_graph_replay(lane, lg, lg_cnt, p.scal + env, E);
+            }
+        }
         SEC(5);  // queue insert
         {
             // ---- _add_release (optical_network_env.py:178-189): the new entry goes behind every entry that is not later, and the
@@ -735,6 +754,11 @@
 
     SEC(14);  // link replay
     if (DEFER) group_link_replay(lane, lst, lint, tb, S, E, llog);   // (the state that leaves carries no pending updates)
+    if constexpr (LEAN) {
+        // ... and no pending graph statistics: the next chunk of the quad may go to another wave
+        SEC(15);  // graph replay
+        if (ballot(lg_cnt > 0) != 0ull) group_graph_replay(lane, lg, lg_cnt, p.scal + env, E);
+    }
     // ------------------------------------------------------------------ LDS -> HBM
     SEC(13);  // state store
     wave_sync();
@@ -782,7 +806,7 @@
         if (gl == 8) {
             go->current_time = current_time;
             go->req_arrival = req_arrival; go->req_holding = req_holding;
-            go->g_throughput = g_thr; go->g_compactness = g_comp; go->g_last_update = g_lu;
+            if (!LEAN) { go->g_throughput = g_thr; go->g_compactness = g_comp; go->g_last_update = g_lu; }   // (LEAN: group_graph_replay's)
             go->sum_bitrate_running = sum_bitrate_running;
             go->episodes_done = episodes_done;
             go->sum_slots_hops = sum_sh; go->n_running = n_running;

@@ -28,6 +28,7 @@
 #include "orlg_assign.h"       // assign_word_key: the assignment rules of the ASSIGN instantiations
 #include "orlg_cut.h"          // cut_word_key: the fewest-cuts window of the CUT instantiations
 #include "orlg_usage.h"        // usage_prefix, window_word_key: the rule MOST_USED and the route BEST_WINDOW of the USAGE instantiations
+#include "orlg_graph_log.h"    // OrlgGraphEntry, orlg_glog_*: the lean body's logged graph statistics (group_graph_replay below)
 
 #define ORLG_GL 16  // lanes per environment (one DPP row)
 #define ORLG_GE 4   // environments per wave
@@ -362,6 +363,49 @@ DEV void group_release_links(const int lane, u64 *occ, u64 *lsum, int32_t *lint,
 
 DEV void group_link_replay(const int lane, double *lst, int32_t *lint, const Tab &tb, int S, int E, const uint4 *llog) {
     link_replay<ORLG_GL>(lane, lst, lint, tb, S, E, llog);
+}
+
+// The logged graph statistics of the lean body (orlg_graph_log.h), worked off: lane k of a row holds entry k of the row's
+// environment, `cnt` of them (the same number on the row's lanes; the lanes from `cnt` on hold stale entries nobody reads).
+// Every lane evaluates its own entry -- the compactness, the reciprocal of its time, the time difference to the entry before it
+// (the previous lane's time; g_last_update for entry 0) and the two products: the part of _update_network_stats that does not depend on
+// the running averages.  The chain then runs DOWN THE ROW, for all four rows at once: in iteration k lane k takes the two averages
+// as lane k - 1 left them (row_shr:1; lane 0 starts from the stored ones), applies its own entry and hands the result on, so
+// the terms stay where they were evaluated and only two doubles move per link of the chain.  A lane without an entry (a row with
+// fewer entries than the longest, nmax) or whose time fails the guard hands on what it received; after nmax iterations lane
+// nmax - 1 of every row holds the row's result.  The other lanes execute the same instructions on values nobody reads.  Between
+// two replays the three doubles rest in the environment's scalars record (HBM; a few accesses per launch): no register of the
+// step loop holds them.  Rows past the batch's end never log (their steps are not accepted).  The DPP reads stand outside any
+// condition.
+static_assert(255 * 64 * ORLG_MAX_W <= ORLG_GLOG_MAX_ES, "a link is a byte, a link's bitmap ORLG_MAX_W words: the log's E S fields");
+DEV void group_graph_replay(const int lane, const OrlgGraphEntry &lg, int &cnt, OrlgEnvScalars *gs, int E) {
+    const int gl = lane & 15;
+    // what other lanes of this wave stored in an earlier replay: the stores only have to be complete (same CU)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const bool head = gl == 0 && cnt > 0;
+    double x_thr = 0.0, x_comp = 0.0, g_lu = 0.0;
+    if (head) { x_thr = gs->g_throughput; x_comp = gs->g_compactness; g_lu = gs->g_last_update; }
+    const double before = ORLG_DPP_F64(lane_prev_i32, lg.now);
+    const double lu = gl == 0 ? g_lu : before;   // g_last_update as the lane's entry meets it: every update ends with g_lu = now
+    const OrlgGraphTerm t = orlg_glog_eval(lg, lu, E);
+    const bool upd = gl < cnt && t.now > 0;
+    const int c0 = __builtin_amdgcn_readlane(cnt, 0), c1 = __builtin_amdgcn_readlane(cnt, 16);
+    const int c2 = __builtin_amdgcn_readlane(cnt, 32), c3 = __builtin_amdgcn_readlane(cnt, 48);
+    const int m01 = c0 > c1 ? c0 : c1, m23 = c2 > c3 ? c2 : c3;
+    const int nmax = m01 > m23 ? m01 : m23;
+    double o_thr = 0.0, o_comp = 0.0;
+    for (int k = 0; k < nmax; ++k) {
+        const double n_thr = orlg_glog_chain(x_thr, lu, t.c_thr, t.now, t.ynow);
+        const double n_comp = orlg_glog_chain(x_comp, lu, t.c_comp, t.now, t.ynow);
+        o_thr = upd ? n_thr : x_thr;
+        o_comp = upd ? n_comp : x_comp;
+        x_thr = ORLG_DPP_F64(lane_prev_i32, o_thr);
+        x_comp = ORLG_DPP_F64(lane_prev_i32, o_comp);
+    }
+    if (gl == nmax - 1 && cnt > 0) { gs->g_throughput = o_thr; gs->g_compactness = o_comp; }
+    if (gl == cnt - 1) gs->g_last_update = lg.now;   // (g_last_update = now also where the guard fails)
+    cnt = 0;
 }
 
 // set (release) or clear (provision) the window [s, s+n) on every link of a row's path; hops = 0: the row does not take part

@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "optical-rl-gym-qot-aware_amd")
 LIB = os.path.join(PKG, "liborlg_sections.so")
 NAMES = ["idle/ticket", "state load", "policy", "validate+provision", "stats@provision", "queue insert", "outputs",
-         "next arrival", "refill", "release scan", "release apply", "stats@release", "done/reset", "state store", "link replay", ""]
+         "next arrival", "refill", "release scan", "release apply", "stats@release", "done/reset", "state store", "link replay", "graph replay"]
 
 
 def main():
@@ -75,7 +75,7 @@ def main():
     env.synchronize()
     L.orlg_debug_sections(out, 1)
     tot = sum(out)
-    res = {NAMES[i]: round(100.0 * out[i] / tot, 2) for i in range(15)}
+    res = {NAMES[i]: round(100.0 * out[i] / tot, 2) for i in range(16)}
     res["cycles_per_env_step"] = tot / (args.batch * args.steps)
     print(json.dumps({"stats": args.stats, "batch": args.batch, "percent_of_wave_cycles": res}))
 
