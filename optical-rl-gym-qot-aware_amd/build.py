@@ -6,7 +6,8 @@ hipcc cross-compiles without a GPU.  -ffp-contract=off is REQUIRED: the fp64 sta
 arrival process must perform exactly the reference's IEEE operations (no fused multiply-add).
 
 The library is a set of translation units compiled in parallel into csrc/build/*.o and linked: the host side
-(orlg_host.hip: what the APIs share; orlg_api.hip, orlg_phy_api.hip, orlg_osnr.hip: the three APIs) and one object per
+(orlg_host.hip: what the APIs share; orlg_api.hip, orlg_api_step.hip, orlg_api_query.hip: the RMSA API -- handle and getters, the step,
+the queries; orlg_phy_api.hip, orlg_osnr.hip: the other two APIs) and one object per
 (kernel family, words per link W) from orlg_inst_{wave,gnrules,gnprotect,gnadmit,group,phy}.hip -- orlg_inst_phy.hip twice, with -DORLG_INST_TRACE=0 and 1;
 orlg_gn_audit_kernels.hip, whose kernels know no word count, is one object.
 Which instantiations a family has is written once, in csrc/orlg_variants.h.  An object is rebuilt when any file its depfile names
@@ -30,8 +31,9 @@ PHY_W = (1, 2, 3, 4, 5)
 
 def units():
     """(object name, source, extra defines)"""
-    u = [("orlg_host", "orlg_host.hip", []), ("orlg_api", "orlg_api.hip", []), ("orlg_phy_api", "orlg_phy_api.hip", []),
-         ("orlg_osnr", "orlg_osnr.hip", [])]
+    # the host side: what the APIs share, the RMSA API's three units (csrc/orlg_rmsa_host.h says what lives where), the other two APIs
+    u = [("orlg_host", "orlg_host.hip", []), ("orlg_api", "orlg_api.hip", []), ("orlg_api_step", "orlg_api_step.hip", []),
+         ("orlg_api_query", "orlg_api_query.hip", []), ("orlg_phy_api", "orlg_phy_api.hip", []), ("orlg_osnr", "orlg_osnr.hip", [])]
     # the largest objects first: the pool then finishes with the small ones
     for w in sorted(WAVE_W, reverse=True):
         u.append((f"orlg_inst_wave_w{w}", "orlg_inst_wave.hip", [f"-DORLG_INST_W={w}"]))

@@ -1,34 +1,13 @@
-// orlg_api.hip -- host side of liborlg.so: the C ABI declared in include/orlg.h.
-// Owns the device state of B environments, builds the read-only tables and launches the kernels of orlg_kernels.hip, orlg_group_kernels.hip, orlg_query_kernels.hip and orlg_mask_kernels.hip; what it has
-// in common with the QoT-aware API is the handle core of orlg_host.h.  No CPU compute path exists: every entry point that touches
-// environments needs a HIP device.
-#include "orlg_host.h"
-#include "orlg_group_plan.h"
+// orlg_api.hip -- host side of liborlg.so: the C ABI declared in include/orlg.h, first of its three units (orlg_rmsa_host.h says what
+// lives where).  Owns the device state of B environments and builds the read-only tables: create, reset, reseed, the getters and
+// reductions, checkpoint / resume, the debug exports; the kernels of orlg_kernels.hip and orlg_group_kernels.hip are launched by
+// orlg_api_step.hip, those of orlg_query_kernels.hip and orlg_mask_kernels.hip by orlg_api_query.hip.  What the three have in common
+// with the QoT-aware API is the handle core of orlg_host.h.  No CPU compute path exists: every entry point that touches environments
+// needs a HIP device.
+#include "orlg_rmsa_host.h"
+#include "orlg_step_call.h"   // orlg_debug_step_call
 #include "orlg_wave.h"   // valid_mask, ORLG_INF_BITS for the helper kernels; the step kernels are instantiated in orlg_inst_*.hip
 #include "orlg_graph_log.h"   // ORLG_GLOG_MAX_Q: the queue capacity the lean body's packed log is sized for
-
-// ---------------------------------------------------------------------------------------- handle
-struct orlg_env : OrlgHandle {
-    OrlgParams p = {};
-    int resident_blocks = 0;   // workgroups of the step kernel the device keeps resident (grid size of the work queue)
-    // four-environments-per-wave step kernel: group_mode = ORLG_KERNEL_* (AUTO falls back to WAVE when the shape does not fit the
-    // kernel's LDS budget); the LDS layout of each kind of instantiation (orlg_group_plan.h) and its resident workgroups
-    int group_mode = 0;
-    OrlgGroupLayout group[3] = {};                          // by OrlgGroupKind
-    int group_usage_resident[ORLG_GROUP_WAVES + 1] = {};    // ... of the USAGE instantiations, which take more LDS (launch_rmsa_group)
-    int group_resident[3][ORLG_GROUP_WAVES + 1] = {};       // ... by waves per workgroup (0 = not asked yet)
-    uint4 *llog = nullptr;          // DEFER: the log of link updates [B][E][ORLG_LLOG_CAP] (allocated with the first such launch)
-    uint32_t *progress = nullptr;   // chunked tickets: chunks completed per quad in the current launch (allocated with the first such launch)
-    int allow_rejection = 0;   // the action spaces carry the explicit rejection (orlg_set_allow_rejection): one more mask column
-    std::vector<uint8_t> path_se;   // spectral efficiency of every path record (orlg_set_gn_gate checks the thresholds against it)
-    double *gn_table = nullptr;     // the gate's table on the device (allocated with the first gate; OrlgParams::gn = it or nullptr)
-    bool gn_protect = false;        // the gate also protects the running lightpaths (orlg_set_gn_protect; configuration, not state)
-    double *audit_table = nullptr;  // the table of a gate given with orlg_gn_audit (allocated with the first such call; never OrlgParams::gn)
-};
-enum { X_ACTIONS, X_GSNR, X_CAUSE, X_CAUSE_COUNTS, X_MARGIN };   // OrlgHandle::extra: external actions from / the gn_gsnr_db, block_cause, cause_counts and gn_neighbour_margin_db outputs for host memory
-static_assert(X_MARGIN < ORLG_EXTRA_SLOTS, "OrlgHandle::extra");
-
-#define SYNC_CHECK(e) do { int rc_ = orlg_handle_sync_check(e); if (rc_) return rc_; } while (0)
 
 // ---------------------------------------------------------------------------------------- small kernels
 // reset(only_episode_counters=False) state: every slot free, empty queue, zero counters and statistics;
@@ -130,142 +109,6 @@ __global__ void orlg_overflow_kernel(const OrlgEnvScalars *scal, int B, int *out
     if (any) atomicOr(out, 1);
 }
 
-// ---------------------------------------------------------------------------------------- launches
-// the kernels live in per-W objects (orlg_inst_wave.hip / orlg_inst_group.hip), found by key: orlg_pick (orlg_variants.h)
-typedef orlg_rmsa_kernel_t rmsa_kernel_t;
-typedef orlg_masks_kernel_t masks_kernel_t;
-
-// the tooling environment of a launch
-static OrlgGroupOverrides group_overrides() {
-    const char *wpb = getenv("ORLG_GROUP_WPB"), *chunks = getenv("ORLG_GROUP_CHUNKS");
-    return {getenv("ORLG_NO_DEFER") != nullptr, getenv("ORLG_NO_CHUNKS") != nullptr, getenv("ORLG_NO_LEAN") != nullptr,
-            wpb ? atoi(wpb) : 0, chunks ? atoi(chunks) : 0};
-}
-
-// the step kernel with four environments per wave: first-fit policies and external (path, slot) actions.  What is launched is
-// decided in orlg_group_plan.h; here it is done
-// a launch of orlg_step_window under the rule MOST_USED or the route BEST_WINDOW: the USAGE instantiations (orlg_usage.h)
-static bool usage_launch(const OrlgParams &p) {
-    return (p.out_mask & ORLG_OUT_ASSIGN_BIT) != 0 && (p.assign == ORLG_ASSIGN_MOST_USED || p.policy == ORLG_POLICY_BEST_WINDOW);
-}
-
-static int launch_rmsa_group(orlg_env *e, const OrlgParams &p, const OrlgGroupOverrides &ov) {
-    OrlgGroupChoice c = orlg_group_choose(e->group, {p.B, p.n_steps, p.stats_level, p.policy, p.out_mask, p.br_width}, ov, e->num_cu);
-    const OrlgGroupLayout &l = e->group[c.kind];
-    const bool df = c.kind == ORLG_GROUP_DEFER;
-    const bool trace = p.tr_arrival != nullptr;   // a request trace: the instantiations that replay it
-    const bool traffic = !trace && p.rates != nullptr;   // per-environment rates: the instantiations that read them
-    const bool cause = (p.out_mask & ORLG_OUT_CAUSE_BIT) != 0;   // the blocking cause: the plain kind with the classifier (the plan chose it)
-    const bool assign = (p.out_mask & ORLG_OUT_ASSIGN_BIT) != 0;   // an assignment rule: the plain kind with the rules (the plan chose it)
-    const bool cut = assign && p.assign == ORLG_ASSIGN_MIN_CUT;   // ... the fewest-cuts window: the CUT instantiations
-    const bool usage = usage_launch(p);   // ... MOST_USED / BEST_WINDOW: the USAGE instantiations, with their prefix sums behind the wave regions
-    const OrlgGroupKey key = {p.stats_level, c.kind == ORLG_GROUP_HBMQ, df, traffic, trace, cause, assign, cut, usage};
-    rmsa_kernel_t k = orlg_pick(e->W, key);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    if (usage) {
-        c.wpb = orlg_group_usage_wpb(l, c.wpb, e->W);
-        if (c.wpb < 1)
-            return fail(ORLG_ERR_INVALID, "step_kernel \"group\": one wave's four environments (%d B) and their slot-usage prefix sums (%d B) do not "
-                                          "fit the LDS next to the tables (%d B); use step_kernel \"wave\" or \"auto\" for this policy",
-                        l.wave_bytes, 4 * ORLG_USAGE_BYTES(e->W), l.shared_bytes);
-        c.lds_bytes = orlg_group_lds(l.shared_bytes, c.wpb, l.wave_bytes + 4 * ORLG_USAGE_BYTES(e->W));
-    }
-    if (df && !e->llog)
-        if (int rc = orlg_handle_alloc(e, &e->llog, (size_t)p.B * p.E * ORLG_LLOG_CAP)) return rc;
-    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), usage ? c.lds_bytes : orlg_group_lds(l.shared_bytes, l.wpb_max, l.wave_bytes))) return rc;
-    int *resident = usage ? &e->group_usage_resident[c.wpb] : &e->group_resident[c.kind][c.wpb];
-    if (int rc = orlg_handle_resident(e, reinterpret_cast<const void *>(k), ORLG_WAVE * c.wpb, c.lds_bytes, resident)) return rc;
-    const OrlgGroupTickets t = orlg_group_tickets(c, p.B, p.n_steps, *resident, ov);
-    if (t.n_chunks > 1) {
-        if (!e->progress)
-            if (int rc = orlg_handle_alloc(e, &e->progress, (size_t)p.B / 4 + 1)) return rc;
-        HIP_TRY(hipMemsetAsync(e->progress, 0, (size_t)t.n_quads * sizeof(uint32_t), e->stream));
-    }
-    OrlgParams q = p;
-    q.llog = df ? e->llog : nullptr;
-    q.g_lstat = l.lstat; q.g_lint = l.lint; q.g_qtime = l.qtime; q.g_qdesc = l.qdesc; q.g_wave_bytes = l.wave_bytes;
-    q.g_lean = c.lean;
-    q.ticket_base = e->ticket_base; q.ticket_stride = c.ticket_stride;
-    q.n_chunks = t.n_chunks; q.chunk_steps = t.chunk_steps; q.progress = t.n_chunks > 1 ? e->progress : nullptr;
-    e->ticket_base += t.ticket_advance;
-    hipLaunchKernelGGL(k, dim3(t.nblocks), dim3(ORLG_WAVE * c.wpb), c.lds_bytes, e->stream, q);
-    HIP_TRY(hipGetLastError());
-    orlg_handle_launched(e, key, t.nblocks, ORLG_WAVE * c.wpb, c.lds_bytes, t.n_chunks, c.lean ? "lean" : "full");
-    return ORLG_OK;
-}
-
-static bool group_kernel_serves(const orlg_env *e, const OrlgParams &p) {
-    if (e->group_mode == ORLG_KERNEL_WAVE || p.mode != ORLG_MODE_STEP || p.gn) return false;   // (a gated handle: the wave kernel's GN instantiations)
-    if (e->group_mode == ORLG_KERNEL_GROUP) return true;
-    // (a USAGE launch whose prefix sums the LDS does not hold next to one wave's environments: the wave kernel)
-    if (usage_launch(p) && orlg_group_usage_wpb(e->group[ORLG_GROUP_PLAIN], 1, e->W) < 1) return false;
-    // AUTO: this kernel once the batch exceeds what the wave-per-environment kernel keeps resident (4096 environments on
-    // MI355X) -- long launches (B = 65 536: 1140 vs 630 M env-steps/s) and launches of one step alike (B = 32 768, DeepRMSA
-    // shape: 0.145 vs 0.161 ms per step + observation); at or below it the wave-per-environment kernel has the shorter step
-    // (B = 4096: 630 vs 440 M).
-    return p.B > e->resident_blocks * e->waves_per_block;
-}
-
-// the plain wave-per-environment step kernel
-static rmsa_kernel_t step_kernel(int W, int stats) { return orlg_pick(W, OrlgWaveKey{ORLG_WAVE_KERNEL(orlg_rmsa_kernel), stats, false}); }
-
-static int launch_rmsa(orlg_env *e, const OrlgParams &p) {
-    // a step of a handle with a GN-model admission check: the general kernel's GN instantiation, whatever the policy and the length
-    const bool gn = p.mode == ORLG_MODE_STEP && p.gn != nullptr;
-    // a launch that asks for the blocking cause: the general kernel's CAUSE instantiation, with or without the check
-    const bool cause = p.mode == ORLG_MODE_STEP && (p.out_mask & ORLG_OUT_CAUSE_BIT) != 0;
-    // a launch under an assignment rule other than the reference's first fit: the general kernel's ASSIGN instantiation (behind a gate:
-    // orlg_step_rule_gn alone, every other entry refuses)
-    const bool assign = p.mode == ORLG_MODE_STEP && (p.out_mask & ORLG_OUT_ASSIGN_BIT) != 0;
-    const bool ff = !gn && !cause && !assign && p.mode == ORLG_MODE_STEP && p.K <= 8 && (p.policy == ORLG_POLICY_SP || p.policy == ORLG_POLICY_SAP);
-    const OrlgGroupOverrides ov = group_overrides();
-    const bool df = !gn && p.mode == ORLG_MODE_STEP && orlg_defer_link_stats(p.stats_level, p.n_steps, p.out_mask, ov);   // as launch_rmsa_group
-    const OrlgWaveKey key = {ff ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel_ff)
-                                : p.mode == ORLG_MODE_STEP ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel) : ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel),
-                             p.stats_level, df, gn, cause, assign, assign && p.assign == ORLG_ASSIGN_MIN_CUT, assign && usage_launch(p),
-                             gn && e->gn_protect};
-    // (an assignment rule behind the check, orlg_step_rule_gn: the instantiations of orlg_inst_gnrules.hip, with a lookup of their own;
-    // a handle that protects its running lightpaths: those of orlg_inst_gnprotect.hip -- orlg_step_rule_gn refuses on it)
-    rmsa_kernel_t k = key.PROTECT ? orlg_pick_gn_protect(e->W, key) : gn && assign ? orlg_pick_gn_rules(e->W, key) : orlg_pick(e->W, key);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), e->lds_block_bytes)) return rc;
-    const int wpb = e->waves_per_block;
-    if (e->resident_blocks <= 0) {
-        const void *ks = reinterpret_cast<const void *>(step_kernel(e->W, p.stats_level));  // the grid is sized for the step kernel (any grid is correct)
-        int rc = orlg_kernel_lds(ks, e->lds_block_bytes);
-        if (!rc) rc = orlg_handle_resident(e, ks, ORLG_WAVE * wpb, e->lds_block_bytes, &e->resident_blocks);
-        if (rc) return rc;
-    }
-    if (group_kernel_serves(e, p)) return launch_rmsa_group(e, p, ov);
-    // (a USAGE launch: the waves' prefix sums of the slot usage lie behind the wave regions, asked for here and by no other launch;
-    // where the handle's workgroup fills the LDS, such a launch runs with as many waves per workgroup as still fit)
-    int wpu = wpb;
-    size_t lds = e->lds_block_bytes;
-    if (key.USAGE) {
-        const size_t per_wave = (size_t)p.l_wave_bytes + ORLG_USAGE_BYTES(e->W);
-        while (wpu > 1 && (size_t)p.l_shared_bytes + wpu * per_wave > ORLG_LDS_BYTES) --wpu;
-        lds = (size_t)p.l_shared_bytes + wpu * per_wave;
-        if (lds > ORLG_LDS_BYTES)
-            return fail(ORLG_ERR_INVALID, "tables, one environment and its slot-usage prefix sums (%zu B) exceed the 160 KiB LDS", lds);
-        if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), lds)) return rc;
-    }
-    int nblocks = (p.B + wpu - 1) / wpu;
-    if (nblocks > e->resident_blocks) nblocks = e->resident_blocks;
-    if (df && !e->llog) {
-        int rc = orlg_handle_alloc(e, &e->llog, (size_t)p.B * p.E * ORLG_LLOG_CAP);
-        if (rc) return rc;
-    }
-    OrlgParams q = p;
-    q.llog = df ? e->llog : nullptr;
-    q.ticket_base = e->ticket_base;
-    q.ticket_stride = (p.mode != ORLG_MODE_STEP || p.n_steps <= 16) ? 1u : 0u;
-    if (!q.ticket_stride) e->ticket_base += (uint32_t)p.B;  // waves * 1 static environment + (B - waves) tickets + one failing draw per wave
-    dim3 grid(nblocks), block(ORLG_WAVE * wpu);
-    hipLaunchKernelGGL(k, grid, block, lds, e->stream, q);
-    HIP_TRY(hipGetLastError());
-    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * wpu, lds);
-    return ORLG_OK;
-}
 
 // copy `bytes` from a device buffer to a caller pointer (host or device) and wait
 static int copy_out(orlg_env *e, void *dst, const void *src, size_t bytes) {
@@ -532,20 +375,6 @@ static int rmsa_create(const orlg_topology *t, const orlg_rmsa_config *c, int32_
     return ORLG_OK;
 }
 
-/* launch geometry of the step kernel: out[0] waves (envs) per workgroup, out[1] LDS bytes per workgroup,
- * out[2] workgroups resident per CU according to hipOccupancyMaxActiveBlocksPerMultiprocessor, out[3] W */
-int orlg_launch_info(orlg_env *e, int32_t *out) {
-    if (!e || !out) return fail(ORLG_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(e->device));
-    rmsa_kernel_t k = step_kernel(e->W, e->p.stats_level);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)e->lds_block_bytes));
-    int nb = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(k), ORLG_WAVE * e->waves_per_block,
-                                                         e->lds_block_bytes));
-    out[0] = e->waves_per_block; out[1] = (int32_t)e->lds_block_bytes; out[2] = nb; out[3] = e->W;
-    return ORLG_OK;
-}
 
 int orlg_last_kernel(orlg_env *e, char *buf, int32_t cap) { return orlg_handle_last_kernel(e, buf, cap); }
 int orlg_set_stream(orlg_env *e, void *hip_stream) { return orlg_handle_set_stream(e, hip_stream); }
@@ -578,275 +407,6 @@ int orlg_reset(orlg_env *e, int32_t only_episode_counters) {
 
 int orlg_reseed(orlg_env *e, const uint64_t *seeds, uint64_t base_seed) {
     return orlg_handle_reseed(e, e ? e->p.mt : nullptr, e ? e->p.scal : nullptr, e ? e->p.B : 0, seeds, base_seed);
-}
-
-// io slot ids
-enum { IO_PATH, IO_SLOT, IO_ACC, IO_DONE, IO_REWARD, IO_REQ, IO_ARR, IO_HOLD, IO_COMP, IO_CDIFF };
-
-}  // extern "C"
-// An output of a launch that is not one of orlg_step_io's (block_cause, cause_counts): device memory is written in place,
-// host memory through the handle's buffer `slot` (as orlg_handle_place does for the others); null = not asked for
-struct ExtraOut {
-    void *user = nullptr, *dev = nullptr;
-    size_t bytes = 0;
-    bool staged() const { return user && dev != user; }
-};
-static int extra_out(orlg_env *e, ExtraOut *o, void *user, size_t bytes, int slot) {
-    o->user = user; o->bytes = bytes; o->dev = nullptr;
-    if (!user) return ORLG_OK;
-    o->dev = orlg_is_device_ptr(user) ? user : nullptr;
-    if (!o->dev) {
-        int rc = orlg_scratch_grow(&e->extra[slot], bytes);
-        if (rc) return rc;
-        o->dev = e->extra[slot].ptr;
-    }
-    return ORLG_OK;
-}
-// orlg_step, orlg_step_gn, orlg_step_diag, orlg_step_assign and orlg_step_min_cut (gsnr, cause, counts: the outputs beyond
-// orlg_step_io, nullptr = not asked for; assign: ORLG_ASSIGN_*, 0 = the reference's first fit, or the device's own
-// ORLG_ASSIGN_MIN_CUT, which only orlg_step_min_cut passes, with own_entry = 1 -- `policy` may then be the device's ORLG_POLICY_MIN_CUT;
-// own_entry = 2: orlg_step_window, which has checked its route and rule itself -- the device's ORLG_ASSIGN_MOST_USED and ORLG_POLICY_BEST_WINDOW;
-// own_entry = 3: orlg_step_rule_gn, which has checked route, rule, mode and the gate itself -- a rule up to ORLG_ASSIGN_MIN_CUT on a
-// gated handle, `policy` a route, the device's ORLG_POLICY_MIN_CUT, or ORLG_POLICY_SAP_GN = route sap that goes on to the next path;
-// margin: the output gn_neighbour_margin_db of orlg_step_gn_protect)
-static int rmsa_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
-                     const orlg_step_io *io, double *gsnr, uint8_t *cause = nullptr, int32_t *counts = nullptr, int32_t assign = ORLG_ASSIGN_FIRST,
-                     int own_entry = 0, double *margin = nullptr) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (n_steps < 1) return fail(ORLG_ERR_INVALID, "n_steps must be >= 1");
-    const bool min_cut_entry = own_entry == 1;
-    const bool gn_entry = own_entry == 3;
-    const bool cut_route = ((min_cut_entry || gn_entry) && policy == ORLG_POLICY_MIN_CUT) || (own_entry == 2 && policy == ORLG_POLICY_BEST_WINDOW);
-    if (!cut_route && (policy < ORLG_POLICY_EXTERNAL || policy > ORLG_POLICY_SAP_FF_GN)) return fail(ORLG_ERR_INVALID, "unknown policy %d", policy);
-    if (policy == ORLG_POLICY_SAP_FF_GN && !e->p.gn)
-        return fail(ORLG_ERR_INVALID, "policy %d (sap_ff_gn) asks the GN-model admission check: the handle has no gn_gate", policy);
-    // an assignment rule other than the reference's first fit: the policy is a route, the handle has no gate -- before anything is launched
-    // (the public rules; ORLG_ASSIGN_MIN_CUT comes from orlg_step_min_cut alone and is an unknown rule to every other caller)
-    if (assign < ORLG_ASSIGN_FIRST || assign >= (own_entry == 2 ? ORLG_ASSIGN_MOST_USED + 1 : (min_cut_entry || gn_entry) ? ORLG_ASSIGN_MIN_CUT + 1 : ORLG_NUM_ASSIGN_RULES)) return fail(ORLG_ERR_INVALID, "unknown assignment rule %d", assign);
-    if (assign != ORLG_ASSIGN_FIRST) {
-        if (!cut_route && policy != ORLG_POLICY_SP_FF && policy != ORLG_POLICY_SAP_FF && policy != ORLG_POLICY_LLP_FF && policy != ORLG_POLICY_PATH_FF_EXTERNAL &&
-            !(gn_entry && policy == ORLG_POLICY_SAP_GN))
-            return fail(ORLG_ERR_INVALID, "assignment rule %d needs a route (sp_ff, sap_ff, llp_ff or path_ff_external): policy %d names its own slot or block", assign, policy);
-        if (e->p.gn && !gn_entry) return fail(ORLG_ERR_INVALID, "assignment rule %d on a handle with a gn_gate: this entry runs no rule behind the admission check, orlg_step_rule_gn does", assign);
-    }
-    const bool ext = policy == ORLG_POLICY_EXTERNAL || policy == ORLG_POLICY_DEEPRMSA_EXTERNAL || policy == ORLG_POLICY_PATH_FF_EXTERNAL;
-    if (ext && (!actions || n_steps != 1)) return fail(ORLG_ERR_INVALID, "external actions need an action array and n_steps == 1");
-    {
-        int rc0 = orlg_trace_admit(&e->trace, n_steps);   // before anything is launched or copied
-        if (rc0) return rc0;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    OrlgParams p = e->p;
-    p.mode = ORLG_MODE_STEP; p.n_steps = n_steps; p.policy = policy; p.auto_reset = auto_reset;
-    if (ext) {
-        size_t n = (size_t)p.B * (policy == ORLG_POLICY_EXTERNAL ? 2 : 1);
-        if (const void *da = orlg_device_alias(actions)) {   // device memory, or pinned host memory read over the bus
-            p.actions = static_cast<const int32_t *>(da);
-        } else {
-            int rc = orlg_scratch_grow(&e->extra[X_ACTIONS], n * sizeof(int32_t));
-            if (rc) return rc;
-            p.actions = static_cast<const int32_t *>(e->extra[X_ACTIONS].ptr);
-            HIP_TRY(hipMemcpyAsync(e->extra[X_ACTIONS].ptr, actions, n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-        }
-    }
-    // outputs: write straight into device pointers, stage host pointers
-    const size_t cnt = (size_t)n_steps * p.B;
-    const OrlgOut slots[ORLG_NUM_OUTS] = {
-        {io ? io->act_path : nullptr, 4},   {io ? io->act_slot : nullptr, 4},  {io ? io->accepted : nullptr, 1},
-        {io ? io->done : nullptr, 1},       {io ? io->reward : nullptr, 8},    {io ? io->request : nullptr, 16},
-        {io ? io->arrival : nullptr, 8},    {io ? io->holding : nullptr, 8},   {io ? io->network_compactness : nullptr, 8},
-        {io ? io->network_compactness_difference : nullptr, 8},
-        {io ? io->avg_link_compactness : nullptr, 8},   {io ? io->avg_link_utilization : nullptr, 8}};
-    int rc = orlg_handle_place(e, slots, ORLG_NUM_OUTS, cnt, p.outs, &p.out_mask);
-    if (rc) return rc;
-    // gn_gsnr_db: device memory (or pinned host memory) is written in place, pageable host memory through a buffer of the handle
-    const bool gsnr_staged = gsnr && !orlg_device_alias(gsnr);
-    p.o_gsnr = gsnr ? static_cast<double *>(orlg_device_alias(gsnr)) : nullptr;
-    if (gsnr_staged) {
-        rc = orlg_scratch_grow(&e->extra[X_GSNR], cnt * sizeof(double));
-        if (rc) return rc;
-        p.o_gsnr = static_cast<double *>(e->extra[X_GSNR].ptr);
-    }
-    if (gsnr && !p.gn) HIP_TRY(hipMemsetAsync(p.o_gsnr, 0xff, cnt * sizeof(double), e->stream));   // no gate, no check: all NaN
-    // block_cause / cause_counts: the launch runs a CAUSE instantiation (ORLG_OUT_CAUSE_BIT); the counts are zeroed on the stream
-    ExtraOut xc, xn;
-    rc = extra_out(e, &xc, cause, cnt, X_CAUSE);
-    if (!rc) rc = extra_out(e, &xn, counts, (size_t)p.B * ORLG_NUM_CAUSES * sizeof(int32_t), X_CAUSE_COUNTS);
-    if (rc) return rc;
-    p.o_cause = static_cast<uint8_t *>(xc.dev);
-    p.o_cause_counts = static_cast<int32_t *>(xn.dev);
-    if (cause || counts) p.out_mask |= ORLG_OUT_CAUSE_BIT;
-    if (counts) HIP_TRY(hipMemsetAsync(xn.dev, 0, xn.bytes, e->stream));
-    // gn_neighbour_margin_db: written by a protecting handle's kernels; every other handle ran no second check -- all NaN
-    ExtraOut xm;
-    rc = extra_out(e, &xm, margin, cnt * sizeof(double), X_MARGIN);
-    if (rc) return rc;
-    p.o_margin = static_cast<double *>(xm.dev);
-    if (margin && !(p.gn && e->gn_protect)) HIP_TRY(hipMemsetAsync(xm.dev, 0xff, xm.bytes, e->stream));
-    p.assign = assign;
-    if (assign != ORLG_ASSIGN_FIRST) p.out_mask |= ORLG_OUT_ASSIGN_BIT;   // the launch runs an ASSIGN instantiation
-    rc = launch_rmsa(e, p);
-    if (rc) return rc;
-    if (e->trace.length > 0) e->trace.position += n_steps;
-    bool any = false;
-    rc = orlg_handle_collect(e, slots, ORLG_NUM_OUTS, cnt, p.outs, &any);
-    if (rc) return rc;
-    for (const ExtraOut *x : {&xc, &xn, &xm})
-        if (x->staged()) {
-            HIP_TRY(hipMemcpyAsync(x->user, x->dev, x->bytes, hipMemcpyDeviceToHost, e->stream));
-            any = true;
-        }
-    if (gsnr_staged) {
-        HIP_TRY(hipMemcpyAsync(gsnr, p.o_gsnr, cnt * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-        any = true;
-    }
-    if (any) SYNC_CHECK(e);
-    return ORLG_OK;
-}
-extern "C" {
-int orlg_step(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io) {
-    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr);
-}
-int orlg_step_gn(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
-                 double *gn_gsnr_db) {
-    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, gn_gsnr_db);
-}
-int orlg_step_diag(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
-                   const struct orlg_step_diag *diag) {
-    if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr);
-    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts);
-}
-int orlg_step_gn_protect(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
-                         const struct orlg_step_diag *diag, double *gn_neighbour_margin_db) {
-    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag ? diag->gn_gsnr_db : nullptr, diag ? diag->block_cause : nullptr,
-                     diag ? diag->cause_counts : nullptr, ORLG_ASSIGN_FIRST, 0, gn_neighbour_margin_db);
-}
-int orlg_step_assign(orlg_env *e, int32_t policy, int32_t assign, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
-                     const orlg_step_io *io, const struct orlg_step_diag *diag) {
-    if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr, nullptr, nullptr, assign);
-    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, assign);
-}
-int orlg_step_min_cut(orlg_env *e, int32_t route, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
-                      const struct orlg_step_diag *diag) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (route != ORLG_POLICY_SP_FF && route != ORLG_POLICY_SAP_FF && route != ORLG_POLICY_LLP_FF && route != ORLG_POLICY_PATH_FF_EXTERNAL &&
-        route != ORLG_ROUTE_FEWEST_CUTS)
-        return fail(ORLG_ERR_INVALID, "the fewest-cuts window needs a route (sp_ff, sap_ff, llp_ff, path_ff_external or ORLG_ROUTE_FEWEST_CUTS): got %d", route);
-    if (e->p.gn) return fail(ORLG_ERR_INVALID, "the fewest-cuts window on a handle with a gn_gate: this entry runs no rule behind the admission check, orlg_step_rule_gn does");
-    const int32_t policy = route == ORLG_ROUTE_FEWEST_CUTS ? (int32_t)ORLG_POLICY_MIN_CUT : route;
-    if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr, nullptr, nullptr, ORLG_ASSIGN_MIN_CUT, 1);
-    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, ORLG_ASSIGN_MIN_CUT, 1);
-}
-int orlg_step_window(orlg_env *e, int32_t route, int32_t rule, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
-                     const struct orlg_step_diag *diag) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    const bool old_route = route == ORLG_POLICY_SP_FF || route == ORLG_POLICY_SAP_FF || route == ORLG_POLICY_LLP_FF || route == ORLG_POLICY_PATH_FF_EXTERNAL;
-    const bool old_rule = rule == ORLG_ASSIGN_FIRST_FULL || rule == ORLG_ASSIGN_LAST || rule == ORLG_ASSIGN_BEST || rule == ORLG_ASSIGN_EXACT;
-    if (!old_route && route != ORLG_ROUTE_BEST_WINDOW)
-        return fail(ORLG_ERR_INVALID, "orlg_step_window needs a route (sp_ff, sap_ff, llp_ff, path_ff_external or ORLG_ROUTE_BEST_WINDOW): got %d", route);
-    if (!old_rule && rule != ORLG_RULE_MOST_USED)
-        return fail(ORLG_ERR_INVALID, "orlg_step_window needs a rule (ORLG_ASSIGN_FIRST_FULL, LAST, BEST, EXACT or ORLG_RULE_MOST_USED): got %d", rule);
-    if (e->p.gn) return fail(ORLG_ERR_INVALID, "orlg_step_window on a handle with a gn_gate: this entry runs no rule behind the admission check (orlg_step_rule_gn does, for the rules and routes other than MOST_USED and BEST_WINDOW)");
-    if (old_route && old_rule) return orlg_step_assign(e, route, rule, n_steps, actions, auto_reset, io, diag);   // what that launches
-    const int32_t policy = route == ORLG_ROUTE_BEST_WINDOW ? (int32_t)ORLG_POLICY_BEST_WINDOW : route;
-    const int32_t assign = rule == ORLG_RULE_MOST_USED ? (int32_t)ORLG_ASSIGN_MOST_USED : rule;
-    if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr, nullptr, nullptr, assign, 2);
-    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, assign, 2);
-}
-// a route and a rule behind the admission check: everything is checked here, rmsa_step then launches a GN x ASSIGN instantiation
-int orlg_step_rule_gn(orlg_env *e, int32_t route, int32_t rule, int32_t gn_mode, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
-                      const orlg_step_io *io, const struct orlg_step_diag *diag) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: the handle has no gn_gate (orlg_step_assign, orlg_step_min_cut serve it)");
-    if (e->gn_protect)
-        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: the handle protects its running lightpaths (orlg_set_gn_protect), and no assignment rule runs behind that second check yet: orlg_step_gn_protect runs the reference's first fit behind it");
-    if (route == ORLG_ROUTE_BEST_WINDOW || rule == ORLG_RULE_MOST_USED)
-        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: the rule MOST_USED and the route BEST_WINDOW are not served behind a gn_gate (route %d, rule %d)", route, rule);
-    if (route != ORLG_POLICY_SP_FF && route != ORLG_POLICY_SAP_FF && route != ORLG_POLICY_LLP_FF && route != ORLG_POLICY_PATH_FF_EXTERNAL &&
-        route != ORLG_ROUTE_FEWEST_CUTS)
-        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn needs a route (sp_ff, sap_ff, llp_ff, path_ff_external or ORLG_ROUTE_FEWEST_CUTS): got %d", route);
-    if (rule == ORLG_ASSIGN_FIRST)
-        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: rule ORLG_ASSIGN_FIRST is the reference's first fit, which orlg_step_gn runs behind the gate");
-    const bool old_rule = rule == ORLG_ASSIGN_FIRST_FULL || rule == ORLG_ASSIGN_LAST || rule == ORLG_ASSIGN_BEST || rule == ORLG_ASSIGN_EXACT;
-    if (!old_rule && rule != ORLG_RULE_FEWEST_CUTS)
-        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn needs a rule (ORLG_ASSIGN_FIRST_FULL, LAST, BEST, EXACT or ORLG_RULE_FEWEST_CUTS): got %d", rule);
-    if (gn_mode != ORLG_GN_MODE_CHECK && gn_mode != ORLG_GN_MODE_NEXT_PATH)
-        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: unknown gn_mode %d (ORLG_GN_MODE_CHECK or ORLG_GN_MODE_NEXT_PATH)", gn_mode);
-    if (gn_mode == ORLG_GN_MODE_NEXT_PATH && route != ORLG_POLICY_SAP_FF)
-        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: ORLG_GN_MODE_NEXT_PATH goes with the route sap_ff only: got route %d", route);
-    if (route == ORLG_ROUTE_FEWEST_CUTS && rule != ORLG_RULE_FEWEST_CUTS)
-        return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: the route ORLG_ROUTE_FEWEST_CUTS ranks fewest-cuts windows, it needs the rule ORLG_RULE_FEWEST_CUTS: got %d", rule);
-    const int32_t policy = route == ORLG_ROUTE_FEWEST_CUTS ? (int32_t)ORLG_POLICY_MIN_CUT
-                           : gn_mode == ORLG_GN_MODE_NEXT_PATH ? (int32_t)ORLG_POLICY_SAP_GN : route;
-    const int32_t assign = rule == ORLG_RULE_FEWEST_CUTS ? (int32_t)ORLG_ASSIGN_MIN_CUT : rule;
-    if (!diag) return rmsa_step(e, policy, n_steps, actions, auto_reset, io, nullptr, nullptr, nullptr, assign, 3);
-    return rmsa_step(e, policy, n_steps, actions, auto_reset, io, diag->gn_gsnr_db, diag->block_cause, diag->cause_counts, assign, 3);
-}
-
-// the rules of a gate and its table (ORLG_GN_*, orlg_device.h) for this handle's topology: what orlg_set_gn_gate installs and what
-// orlg_gn_audit builds for a gate given with the call
-static int gn_gate_table(const orlg_env *e, const orlg_rmsa_gn_gate *g, std::vector<double> &tab) {
-    const int E = e->p.E;
-    if (!g->link_num_spans || !g->link_span_length_km || !g->thresholds_db) return fail(ORLG_ERR_INVALID, "null argument");
-    const struct { const char *name; double v; } scalars[] = {
-        {"launch_power_density_w_hz", g->launch_power_density_w_hz}, {"frequency_start_hz", g->frequency_start_hz},
-        {"slot_width_hz", g->slot_width_hz}, {"attenuation_normalized", g->attenuation_normalized}, {"noise_figure", g->noise_figure}};
-    for (const auto &sc : scalars)
-        if (!std::isfinite(sc.v) || !(sc.v > 0)) return fail(ORLG_ERR_INVALID, "gn_gate: %s must be finite and positive", sc.name);
-    if (g->num_thresholds < 1 || g->num_thresholds > ORLG_GN_LINK0 - ORLG_GN_THR0)
-        return fail(ORLG_ERR_INVALID, "gn_gate: num_thresholds %d not in 1..%d", g->num_thresholds, ORLG_GN_LINK0 - ORLG_GN_THR0);
-    for (int i = 0; i < g->num_thresholds; i++)
-        if (!std::isfinite(g->thresholds_db[i])) return fail(ORLG_ERR_INVALID, "gn_gate: thresholds_db[%d] is not finite", i);
-    for (size_t gid = 0; gid < e->path_se.size(); gid++) {
-        if (e->path_se[gid] > g->num_thresholds)
-            return fail(ORLG_ERR_INVALID, "gn_gate: path %zu has spectral efficiency %d, thresholds_db has %d entries", gid, e->path_se[gid], g->num_thresholds);
-        if (e->path_se[gid] > 6)
-            return fail(ORLG_ERR_INVALID, "gn_gate: path %zu has spectral efficiency %d, the modulation factors of the GN model end at 6", gid, e->path_se[gid]);
-    }
-    tab.assign(ORLG_GN_LINK0 + 4 * (size_t)E, 0.0);
-    const double att = g->attenuation_normalized;
-    tab[ORLG_GN_DENSITY] = g->launch_power_density_w_hz; tab[ORLG_GN_F0] = g->frequency_start_hz; tab[ORLG_GN_SLOT] = g->slot_width_hz;
-    tab[ORLG_GN_ATT] = att; tab[ORLG_GN_NF] = g->noise_figure; tab[ORLG_GN_LEFF_A] = 1 / (2 * att);
-    for (int i = 0; i < g->num_thresholds; i++) tab[ORLG_GN_THR0 + i] = g->thresholds_db[i];
-    for (int l = 0; l < E; l++) {
-        const double len = g->link_span_length_km[l];
-        if (g->link_num_spans[l] < 1) return fail(ORLG_ERR_INVALID, "gn_gate: link_num_spans[%d] = %d", l, g->link_num_spans[l]);
-        if (!std::isfinite(len) || !(len > 0)) return fail(ORLG_ERR_INVALID, "gn_gate: link_span_length_km[%d] must be finite and positive", l);
-        // per span, as calculate_osnr.py:24-26, 50 writes them
-        const double l_eff = (1 - std::exp(-2 * att * len * 1e3)) / (2 * att);
-        const double e1 = std::exp(2 * att * len * 1e3) - 1;
-        if (!std::isfinite(e1)) return fail(ORLG_ERR_INVALID, "gn_gate: the loss of a span of link %d overflows", l);
-        double *row = &tab[ORLG_GN_LINK0 + 4 * (size_t)l];
-        row[0] = l_eff; row[1] = l_eff / (len * 1e3); row[2] = e1; row[3] = (double)g->link_num_spans[l];
-    }
-    return ORLG_OK;
-}
-
-int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    HIP_TRY(hipSetDevice(e->device));
-    if (!g) {
-        e->p.gn = nullptr;
-        e->gn_protect = false;   // (protection is a property of the gate: a new gate keeps it, no gate has none)
-        return ORLG_OK;
-    }
-    if (e->group_mode == ORLG_KERNEL_GROUP)
-        return fail(ORLG_ERR_INVALID, "gn_gate: the admission check is served by the wave-per-environment kernel, the handle was created with step_kernel GROUP");
-    std::vector<double> tab;
-    if (int rc = gn_gate_table(e, g, tab)) return rc;
-    if (!e->gn_table)
-        if (int rc = orlg_handle_alloc(e, &e->gn_table, tab.size())) return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));   // (a launch in flight may be reading the table)
-    HIP_TRY(hipMemcpy(e->gn_table, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-    e->p.gn = e->gn_table;
-    return ORLG_OK;
-}
-
-int orlg_set_gn_protect(orlg_env *e, int32_t on) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn_protect: the handle has no gn_gate (orlg_set_gn_gate): protection is a property of the gate");
-    e->gn_protect = on != 0;
-    return ORLG_OK;
 }
 
 int orlg_get_requests(orlg_env *e, orlg_request *out) {
@@ -925,414 +485,6 @@ int orlg_get_episodes_done(orlg_env *e, int64_t *out) {
     size_t bytes = (size_t)e->p.B * 8;
     int rc = extract(e, EX_EPISODES, bytes);
     return rc ? rc : copy_out(e, out, e->staging.bytes(), bytes);
-}
-
-static int query_masks(orlg_env *e, int32_t env_index, int gid0, int count, uint64_t *masks, int32_t *nslots) {
-    if (!e || !masks || !nslots) return fail(ORLG_ERR_INVALID, "null argument");
-    if (env_index < 0 || env_index >= e->p.B) return fail(ORLG_ERR_INVALID, "env_index out of range");
-    HIP_TRY(hipSetDevice(e->device));
-    size_t mbytes = (size_t)count * e->W * 8, nbytes = (size_t)count * 4;
-    int rc = orlg_handle_staging(e, mbytes + nbytes + 64);
-    if (rc) return rc;
-    masks_kernel_t k = orlg_pick_masks(e->W);
-    u64 *dm = reinterpret_cast<u64 *>(e->staging.bytes());
-    int32_t *dn = reinterpret_cast<int32_t *>(e->staging.bytes() + ((mbytes + 15) & ~(size_t)15));
-    size_t lds = (size_t)e->p.l_shared_bytes + (size_t)e->p.NW * 8;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k, dim3(1), dim3(ORLG_WAVE), lds, e->stream, e->p, env_index, gid0, count, dm, dn);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(masks, dm, mbytes, hipMemcpyDefault, e->stream));
-    HIP_TRY(hipMemcpyAsync(nslots, dn, nbytes, hipMemcpyDefault, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ORLG_OK;
-}
-
-int orlg_query_path_masks(orlg_env *e, int32_t env_index, uint64_t *masks, int32_t *nslots) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    return query_masks(e, env_index, -1, e->p.K, masks, nslots);
-}
-
-int orlg_query_path_mask(orlg_env *e, int32_t env_index, int32_t path_gid, uint64_t *mask, int32_t *nslots) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (path_gid < 0 || path_gid >= e->num_paths) return fail(ORLG_ERR_INVALID, "path_gid out of range");
-    return query_masks(e, env_index, path_gid, 1, mask, nslots);
-}
-
-int orlg_deeprmsa_obs_dim(orlg_env *e) { return e ? e->p.obs_dim : ORLG_ERR_INVALID; }
-// A caller's output buffer of one launch: device memory -- or pinned host memory, which the kernel then writes over the bus,
-// asynchronously like a device buffer (no staging copy, no wait: the caller synchronises the stream or an event) -- is written
-// in place; pageable host memory gets a slice of the handle's staging buffer and is copied after the launch.
-struct OutSlot {
-    void *user;
-    size_t bytes, off;
-    void *dev;
-    bool staged;
-};
-static int place_outputs(orlg_env *e, OutSlot *slots, int n) {
-    size_t need = 0;
-    for (int i = 0; i < n; ++i) {
-        OutSlot &s = slots[i];
-        s.dev = s.user ? orlg_device_alias(s.user) : nullptr;
-        s.staged = s.user && !s.dev;
-        s.off = need;
-        if (s.staged) need += (s.bytes + 15) & ~(size_t)15;
-    }
-    if (need) {
-        int rc = orlg_handle_staging(e, need);
-        if (rc) return rc;
-    }
-    for (int i = 0; i < n; ++i)
-        if (slots[i].staged) slots[i].dev = e->staging.bytes() + slots[i].off;
-    return ORLG_OK;
-}
-static int collect_outputs(orlg_env *e, const OutSlot *slots, int n) {
-    bool any = false;
-    for (int i = 0; i < n; ++i)
-        if (slots[i].staged) {
-            HIP_TRY(hipMemcpyAsync(slots[i].user, slots[i].dev, slots[i].bytes, hipMemcpyDefault, e->stream));
-            any = true;
-        }
-    if (any) HIP_TRY(hipStreamSynchronize(e->stream));
-    return ORLG_OK;
-}
-
-int orlg_set_allow_rejection(orlg_env *e, int32_t allow_rejection) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    e->allow_rejection = allow_rejection ? 1 : 0;
-    return ORLG_OK;
-}
-int orlg_deeprmsa_mask_dim(orlg_env *e) { return e ? e->p.K * e->p.j + e->allow_rejection : ORLG_ERR_INVALID; }
-
-// observation and / or DeepRMSA mask out of ONE launch of orlg_deeprmsa_obs_kernel (mask == nullptr: the kernel writes exactly
-// what it wrote before the mask existed; out == nullptr: the mask alone, the row stays on chip)
-static int deeprmsa_observation(orlg_env *e, void *out, bool f32, uint8_t *mask) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!out && !mask) return fail(ORLG_ERR_INVALID, "null argument: neither an observation nor a mask buffer");
-    HIP_TRY(hipSetDevice(e->device));
-    OrlgParams p = e->p;
-    const int mask_dim = p.K * p.j + e->allow_rejection;
-    OutSlot slots[2] = {{out, (size_t)p.B * p.obs_dim * (f32 ? 4 : 8)}, {mask, (size_t)p.B * mask_dim}};
-    int rc = place_outputs(e, slots, 2);
-    if (rc) return rc;
-    p.obs_f32 = f32 ? 1 : 0;
-    p.o_obs = reinterpret_cast<double *>(slots[0].dev);
-    orlg_obs_kernel_t k = orlg_pick_obs(e->W);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    const int wpb = e->waves_per_block;
-    size_t lds = (size_t)p.l_shared_bytes + (size_t)(((p.NW * 8 + 15) & ~15) + ((p.obs_dim * 8 + 15) & ~15)) * wpb;
-    if (lds > ORLG_LDS_BYTES) return fail(ORLG_ERR_INVALID, "observation of %d values does not fit the LDS next to the tables", p.obs_dim);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int nblocks = (p.B + wpb - 1) / wpb;
-    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;   // a few workgroups per CU, each wave striding over its environments
-    dim3 grid(nblocks), block(ORLG_WAVE * wpb);
-    hipLaunchKernelGGL(k, grid, block, lds, e->stream, p, reinterpret_cast<uint8_t *>(slots[1].dev), mask_dim);
-    HIP_TRY(hipGetLastError());
-    return collect_outputs(e, slots, 2);
-}
-int orlg_deeprmsa_observation(orlg_env *e, double *out) {
-    if (!out) return fail(ORLG_ERR_INVALID, "null argument");
-    return deeprmsa_observation(e, out, false, nullptr);
-}
-int orlg_deeprmsa_observation_f32(orlg_env *e, float *out) {
-    if (!out) return fail(ORLG_ERR_INVALID, "null argument");
-    return deeprmsa_observation(e, out, true, nullptr);
-}
-int orlg_deeprmsa_observation_masked(orlg_env *e, void *obs, int32_t obs_f32, uint8_t *mask) {
-    return deeprmsa_observation(e, obs, obs_f32 != 0, mask);
-}
-
-int orlg_action_masks(orlg_env *e, uint8_t *path_ff, uint64_t *slot_masks) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!path_ff && !slot_masks) return fail(ORLG_ERR_INVALID, "null argument: neither a path_ff nor a slots buffer");
-    HIP_TRY(hipSetDevice(e->device));
-    const OrlgParams &p = e->p;
-    const int ff_dim = p.K + e->allow_rejection;
-    OutSlot slots[2] = {{path_ff, (size_t)p.B * ff_dim}, {slot_masks, (size_t)p.B * p.K * e->W * 8}};
-    int rc = place_outputs(e, slots, 2);
-    if (rc) return rc;
-    orlg_action_masks_kernel_t k = orlg_pick_action_masks(e->W);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    const int wpb = e->waves_per_block;
-    const size_t lds = (size_t)p.l_shared_bytes + (size_t)((p.NW * 8 + 15) & ~15) * wpb;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int nblocks = (p.B + wpb - 1) / wpb;
-    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;   // as the observation: each wave strides over its environments
-    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, reinterpret_cast<uint8_t *>(slots[0].dev), ff_dim,
-                       reinterpret_cast<u64 *>(slots[1].dev));
-    HIP_TRY(hipGetLastError());
-    return collect_outputs(e, slots, 2);
-}
-
-int orlg_path_fit_levels(orlg_env *e, uint8_t *levels) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!levels) return fail(ORLG_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(e->device));
-    const OrlgParams &p = e->p;
-    OutSlot slots[1] = {{levels, (size_t)p.B * p.K}};
-    int rc = place_outputs(e, slots, 1);
-    if (rc) return rc;
-    orlg_fit_levels_kernel_t k = orlg_pick_fit_levels(e->W);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    const int wpb = e->waves_per_block;
-    const size_t lds = (size_t)p.l_shared_bytes + (size_t)((p.NW * 8 + 15) & ~15) * wpb;   // as orlg_action_masks: tables + one occupancy row per wave
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int nblocks = (p.B + wpb - 1) / wpb;
-    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;
-    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, reinterpret_cast<uint8_t *>(slots[0].dev));
-    HIP_TRY(hipGetLastError());
-    return collect_outputs(e, slots, 1);
-}
-
-int orlg_path_min_cuts(orlg_env *e, int16_t *cuts, int16_t *slots_out) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!cuts && !slots_out) return fail(ORLG_ERR_INVALID, "null argument: neither a cuts nor a slots buffer");
-    HIP_TRY(hipSetDevice(e->device));
-    const OrlgParams &p = e->p;
-    OutSlot slots[2] = {{cuts, (size_t)p.B * p.K * sizeof(int16_t)}, {slots_out, (size_t)p.B * p.K * sizeof(int16_t)}};
-    int rc = place_outputs(e, slots, 2);
-    if (rc) return rc;
-    orlg_min_cuts_kernel_t k = orlg_pick_min_cuts(e->W);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    const int wpb = e->waves_per_block;
-    const size_t lds = (size_t)p.l_shared_bytes + (size_t)((p.NW * 8 + 15) & ~15) * wpb;   // as orlg_path_fit_levels
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int nblocks = (p.B + wpb - 1) / wpb;
-    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;
-    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, reinterpret_cast<int16_t *>(slots[0].dev),
-                       reinterpret_cast<int16_t *>(slots[1].dev));
-    HIP_TRY(hipGetLastError());
-    return collect_outputs(e, slots, 2);
-}
-
-// orlg_slot_usage and orlg_path_most_used: one kernel (orlg_usage_kernel), a null array is not written
-static int usage_query(orlg_env *e, uint8_t *slot_usage, int32_t *usage, int16_t *slots_out) {
-    HIP_TRY(hipSetDevice(e->device));
-    const OrlgParams &p = e->p;
-    OutSlot slots[3] = {{slot_usage, (size_t)p.B * p.S}, {usage, (size_t)p.B * p.K * sizeof(int32_t)}, {slots_out, (size_t)p.B * p.K * sizeof(int16_t)}};
-    int rc = place_outputs(e, slots, 3);
-    if (rc) return rc;
-    orlg_usage_kernel_t k = orlg_pick_usage(e->W);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    const size_t per_wave = (size_t)((p.NW * 8 + 15) & ~15) + ORLG_USAGE_BYTES(e->W);   // an occupancy row and its prefix sums
-    int wpb = e->waves_per_block;
-    while (wpb > 1 && (size_t)p.l_shared_bytes + per_wave * wpb > ORLG_LDS_BYTES) --wpb;
-    const size_t lds = (size_t)p.l_shared_bytes + per_wave * wpb;
-    if (lds > ORLG_LDS_BYTES) return fail(ORLG_ERR_INVALID, "tables, one occupancy row and its slot-usage prefix sums (%zu B) exceed the 160 KiB LDS", lds);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int nblocks = (p.B + wpb - 1) / wpb;
-    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;
-    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, static_cast<uint8_t *>(slots[0].dev),
-                       reinterpret_cast<int32_t *>(slots[1].dev), reinterpret_cast<int16_t *>(slots[2].dev));
-    HIP_TRY(hipGetLastError());
-    return collect_outputs(e, slots, 3);
-}
-int orlg_slot_usage(orlg_env *e, uint8_t *usage) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!usage) return fail(ORLG_ERR_INVALID, "null argument: usage");
-    return usage_query(e, usage, nullptr, nullptr);
-}
-int orlg_path_most_used(orlg_env *e, int32_t *usage, int16_t *slots_out) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!usage && !slots_out) return fail(ORLG_ERR_INVALID, "null argument: neither a usage nor a slots buffer");
-    return usage_query(e, nullptr, usage, slots_out);
-}
-
-int orlg_gn_action_masks(orlg_env *e, uint8_t *path_ff, double *path_ff_gsnr_db, uint8_t *deeprmsa, double *deeprmsa_gsnr_db) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!path_ff && !path_ff_gsnr_db && !deeprmsa && !deeprmsa_gsnr_db) return fail(ORLG_ERR_INVALID, "null argument: no mask or GSNR buffer");
-    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn action masks: the handle has no gn_gate");
-    if (e->gn_protect)
-        return fail(ORLG_ERR_INVALID, "gn action masks: the handle protects its running lightpaths (orlg_set_gn_protect); these masks know the candidate's own check only and would describe a step this handle does not run: orlg_gn_admission_masks knows both checks");
-    HIP_TRY(hipSetDevice(e->device));
-    const OrlgParams &p = e->p;
-    const size_t B = (size_t)p.B, kj = (size_t)p.K * p.j;
-    OutSlot slots[4] = {{path_ff, B * (p.K + e->allow_rejection)}, {path_ff_gsnr_db, B * p.K * sizeof(double)},
-                        {deeprmsa, B * (kj + e->allow_rejection)}, {deeprmsa_gsnr_db, B * kj * sizeof(double)}};
-    int rc = place_outputs(e, slots, 4);
-    if (rc) return rc;
-    orlg_gn_action_masks_kernel_t k = orlg_pick_gn_action_masks(e->W);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    // a wave holds its environment's occupancy row and the live descriptors of its release ring (up to Q): as many waves per
-    // workgroup as the LDS takes next to the tables
-    const size_t per_wave = (size_t)((p.NW * 8 + 15) & ~15) + (size_t)((p.Q * 4 + 15) & ~15);
-    int wpb = e->waves_per_block;
-    while (wpb > 1 && (size_t)p.l_shared_bytes + per_wave * wpb > ORLG_LDS_BYTES) --wpb;
-    const size_t lds = (size_t)p.l_shared_bytes + per_wave * wpb;
-    if (lds > ORLG_LDS_BYTES) return fail(ORLG_ERR_INVALID, "gn action masks: a release queue of %d entries does not fit the LDS next to the tables", p.Q);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int nblocks = (p.B + wpb - 1) / wpb;
-    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;   // as orlg_action_masks: each wave strides over its environments
-    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, reinterpret_cast<uint8_t *>(slots[0].dev),
-                       reinterpret_cast<double *>(slots[1].dev), reinterpret_cast<uint8_t *>(slots[2].dev),
-                       reinterpret_cast<double *>(slots[3].dev), e->allow_rejection);
-    HIP_TRY(hipGetLastError());
-    return collect_outputs(e, slots, 4);
-}
-
-int orlg_gn_path_windows(orlg_env *e, int32_t rule, int16_t *slots_out, double *gsnr_db, uint8_t *admitted) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!slots_out && !gsnr_db && !admitted) return fail(ORLG_ERR_INVALID, "null argument: no slots, GSNR or admitted buffer");
-    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn path windows: the handle has no gn_gate");
-    if (e->gn_protect)
-        return fail(ORLG_ERR_INVALID, "gn path windows: the handle protects its running lightpaths (orlg_set_gn_protect); this query knows the candidate's own check only and would describe a step this handle does not run: orlg_gn_admission_windows knows both checks");
-    if ((rule < ORLG_ASSIGN_FIRST || rule >= ORLG_NUM_ASSIGN_RULES) && rule != ORLG_RULE_FEWEST_CUTS)
-        return fail(ORLG_ERR_INVALID, "gn path windows: unknown rule %d (ORLG_ASSIGN_FIRST .. EXACT or ORLG_RULE_FEWEST_CUTS)", rule);
-    HIP_TRY(hipSetDevice(e->device));
-    const OrlgParams &p = e->p;
-    const size_t bk = (size_t)p.B * p.K;
-    OutSlot slots[3] = {{slots_out, bk * sizeof(int16_t)}, {gsnr_db, bk * sizeof(double)}, {admitted, bk}};
-    int rc = place_outputs(e, slots, 3);
-    if (rc) return rc;
-    orlg_gn_path_windows_kernel_t k = orlg_pick_gn_path_windows(e->W);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    // as orlg_gn_action_masks: a wave holds its environment's occupancy row and the live descriptors of its release ring
-    const size_t per_wave = (size_t)((p.NW * 8 + 15) & ~15) + (size_t)((p.Q * 4 + 15) & ~15);
-    int wpb = e->waves_per_block;
-    while (wpb > 1 && (size_t)p.l_shared_bytes + per_wave * wpb > ORLG_LDS_BYTES) --wpb;
-    const size_t lds = (size_t)p.l_shared_bytes + per_wave * wpb;
-    if (lds > ORLG_LDS_BYTES) return fail(ORLG_ERR_INVALID, "gn path windows: a release queue of %d entries does not fit the LDS next to the tables", p.Q);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int nblocks = (p.B + wpb - 1) / wpb;
-    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;
-    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, rule == ORLG_RULE_FEWEST_CUTS ? (int)ORLG_ASSIGN_MIN_CUT : (int)rule,
-                       reinterpret_cast<int16_t *>(slots[0].dev), reinterpret_cast<double *>(slots[1].dev), reinterpret_cast<uint8_t *>(slots[2].dev));
-    HIP_TRY(hipGetLastError());
-    return collect_outputs(e, slots, 3);
-}
-
-// ---- the masks and rule windows that know both halves of the check (orlg_gn_admission_kernels.hip)
-// as orlg_gn_action_masks: a wave holds its environment's occupancy row and the live descriptors of its release ring (up to Q) -- as
-// many waves per workgroup as the LDS takes next to the tables.  0: the queue does not fit
-static size_t gn_admission_lds(const orlg_env *e, int &wpb) {
-    const OrlgParams &p = e->p;
-    const size_t per_wave = (size_t)((p.NW * 8 + 15) & ~15) + (size_t)((p.Q * 4 + 15) & ~15);
-    wpb = e->waves_per_block;
-    while (wpb > 1 && (size_t)p.l_shared_bytes + per_wave * wpb > ORLG_LDS_BYTES) --wpb;
-    const size_t lds = (size_t)p.l_shared_bytes + per_wave * wpb;
-    return lds > ORLG_LDS_BYTES ? 0 : lds;
-}
-
-int orlg_gn_admission_masks(orlg_env *e, uint8_t *path_ff, double *path_ff_gsnr_db, double *path_ff_margin_db, uint8_t *deeprmsa,
-                            double *deeprmsa_gsnr_db, double *deeprmsa_margin_db) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!path_ff && !path_ff_gsnr_db && !path_ff_margin_db && !deeprmsa && !deeprmsa_gsnr_db && !deeprmsa_margin_db)
-        return fail(ORLG_ERR_INVALID, "null argument: no mask, GSNR or margin buffer");
-    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn admission masks: the handle has no gn_gate");
-    HIP_TRY(hipSetDevice(e->device));
-    const OrlgParams &p = e->p;
-    const size_t B = (size_t)p.B, kj = (size_t)p.K * p.j;
-    OutSlot slots[6] = {{path_ff, B * (p.K + e->allow_rejection)}, {path_ff_gsnr_db, B * p.K * sizeof(double)},
-                        {path_ff_margin_db, B * p.K * sizeof(double)}, {deeprmsa, B * (kj + e->allow_rejection)},
-                        {deeprmsa_gsnr_db, B * kj * sizeof(double)}, {deeprmsa_margin_db, B * kj * sizeof(double)}};
-    int rc = place_outputs(e, slots, 6);
-    if (rc) return rc;
-    orlg_gn_admission_masks_kernel_t k = orlg_pick_gn_admission_masks(e->W);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    int wpb;
-    const size_t lds = gn_admission_lds(e, wpb);
-    if (!lds) return fail(ORLG_ERR_INVALID, "gn admission masks: a release queue of %d entries does not fit the LDS next to the tables", p.Q);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int nblocks = (p.B + wpb - 1) / wpb;
-    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;   // as orlg_action_masks: each wave strides over its environments
-    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, reinterpret_cast<uint8_t *>(slots[0].dev),
-                       reinterpret_cast<double *>(slots[1].dev), reinterpret_cast<double *>(slots[2].dev),
-                       reinterpret_cast<uint8_t *>(slots[3].dev), reinterpret_cast<double *>(slots[4].dev),
-                       reinterpret_cast<double *>(slots[5].dev), e->allow_rejection, e->gn_protect ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    return collect_outputs(e, slots, 6);
-}
-
-int orlg_gn_admission_windows(orlg_env *e, int32_t rule, int16_t *slots_out, double *gsnr_db, double *margin_db, uint8_t *admitted) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!slots_out && !gsnr_db && !margin_db && !admitted) return fail(ORLG_ERR_INVALID, "null argument: no slots, GSNR, margin or admitted buffer");
-    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn admission windows: the handle has no gn_gate");
-    if ((rule < ORLG_ASSIGN_FIRST || rule >= ORLG_NUM_ASSIGN_RULES) && rule != ORLG_RULE_FEWEST_CUTS)
-        return fail(ORLG_ERR_INVALID, "gn admission windows: unknown rule %d (ORLG_ASSIGN_FIRST .. EXACT or ORLG_RULE_FEWEST_CUTS)", rule);
-    HIP_TRY(hipSetDevice(e->device));
-    const OrlgParams &p = e->p;
-    const size_t bk = (size_t)p.B * p.K;
-    OutSlot slots[4] = {{slots_out, bk * sizeof(int16_t)}, {gsnr_db, bk * sizeof(double)}, {margin_db, bk * sizeof(double)}, {admitted, bk}};
-    int rc = place_outputs(e, slots, 4);
-    if (rc) return rc;
-    orlg_gn_admission_windows_kernel_t k = orlg_pick_gn_admission_windows(e->W);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    int wpb;
-    const size_t lds = gn_admission_lds(e, wpb);
-    if (!lds) return fail(ORLG_ERR_INVALID, "gn admission windows: a release queue of %d entries does not fit the LDS next to the tables", p.Q);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int nblocks = (p.B + wpb - 1) / wpb;
-    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;
-    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, rule == ORLG_RULE_FEWEST_CUTS ? (int)ORLG_ASSIGN_MIN_CUT : (int)rule,
-                       reinterpret_cast<int16_t *>(slots[0].dev), reinterpret_cast<double *>(slots[1].dev),
-                       reinterpret_cast<double *>(slots[2].dev), reinterpret_cast<uint8_t *>(slots[3].dev), e->gn_protect ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    return collect_outputs(e, slots, 4);
-}
-
-// ---- the running services and their GN-model audit (orlg_gn_audit_kernels.hip)
-int orlg_queue_capacity(orlg_env *e) { return e ? e->p.Q : ORLG_ERR_INVALID; }
-
-int orlg_get_running_services(orlg_env *e, int32_t *count, int32_t *head, int32_t *path_gid, int16_t *slot, int16_t *num_slots,
-                              int32_t *bit_rate, double *release_time) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!count && !head && !path_gid && !slot && !num_slots && !bit_rate && !release_time)
-        return fail(ORLG_ERR_INVALID, "null argument: no buffer of the running services");
-    HIP_TRY(hipSetDevice(e->device));
-    const OrlgParams &p = e->p;
-    const size_t B = (size_t)p.B, bq = B * p.Q;
-    OutSlot slots[7] = {{count, B * 4}, {head, B * 4}, {path_gid, bq * 4}, {slot, bq * 2}, {num_slots, bq * 2}, {bit_rate, bq * 4},
-                        {release_time, bq * 8}};
-    int rc = place_outputs(e, slots, 7);
-    if (rc) return rc;
-    size_t nblocks = (bq + 255) / 256;
-    if (nblocks > (size_t)8 * e->num_cu) nblocks = (size_t)8 * e->num_cu;
-    hipLaunchKernelGGL(orlg_running_services_kernel_lookup(), dim3((unsigned)nblocks), dim3(256), 0, e->stream, p,
-                       reinterpret_cast<int32_t *>(slots[0].dev), reinterpret_cast<int32_t *>(slots[1].dev),
-                       reinterpret_cast<int32_t *>(slots[2].dev), reinterpret_cast<int16_t *>(slots[3].dev),
-                       reinterpret_cast<int16_t *>(slots[4].dev), reinterpret_cast<int32_t *>(slots[5].dev),
-                       reinterpret_cast<double *>(slots[6].dev));
-    HIP_TRY(hipGetLastError());
-    return collect_outputs(e, slots, 7);
-}
-
-int orlg_gn_audit(orlg_env *e, const orlg_rmsa_gn_gate *gate, orlg_gn_audit_summary *summary, double *gsnr_db, double *margin_db,
-                  double *osnr_ase_db, double *snr_nli_db) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
-    if (!summary && !gsnr_db && !margin_db && !osnr_ase_db && !snr_nli_db)
-        return fail(ORLG_ERR_INVALID, "null argument: no summary or per-service buffer");
-    if (!gate && !e->p.gn) return fail(ORLG_ERR_INVALID, "gn audit: the handle has no gn_gate and none was given with the call");
-    HIP_TRY(hipSetDevice(e->device));
-    const OrlgParams &p = e->p;
-    const double *table = p.gn;
-    if (gate) {   // a table of this call's own: the handle's configuration stays what it is
-        std::vector<double> tab;
-        if (int rc = gn_gate_table(e, gate, tab)) return rc;
-        if (!e->audit_table)
-            if (int rc = orlg_handle_alloc(e, &e->audit_table, tab.size())) return rc;
-        HIP_TRY(hipStreamSynchronize(e->stream));   // (an audit in flight may be reading the table)
-        HIP_TRY(hipMemcpy(e->audit_table, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-        table = e->audit_table;
-    }
-    const size_t B = (size_t)p.B, bq = B * p.Q * sizeof(double);
-    OutSlot slots[5] = {{summary, B * sizeof(orlg_gn_audit_summary)}, {gsnr_db, bq}, {margin_db, bq}, {osnr_ase_db, bq}, {snr_nli_db, bq}};
-    int rc = place_outputs(e, slots, 5);
-    if (rc) return rc;
-    // a wave holds the live descriptors of its environment's release ring (up to Q): as many waves per workgroup as the LDS takes
-    // next to the tables
-    const size_t per_wave = (size_t)((p.Q * 4 + 15) & ~15);
-    int wpb = e->waves_per_block;
-    while (wpb > 1 && (size_t)p.l_shared_bytes + per_wave * wpb > ORLG_LDS_BYTES) --wpb;
-    const size_t lds = (size_t)p.l_shared_bytes + per_wave * wpb;
-    if (lds > ORLG_LDS_BYTES) return fail(ORLG_ERR_INVALID, "gn audit: a release queue of %d entries does not fit the LDS next to the tables", p.Q);
-    orlg_gn_audit_kernel_t k = orlg_gn_audit_kernel_lookup();
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int nblocks = (p.B + wpb - 1) / wpb;
-    if (nblocks > 4 * e->num_cu) nblocks = 4 * e->num_cu;   // as orlg_gn_action_masks: each wave strides over its environments
-    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), lds, e->stream, p, table, reinterpret_cast<orlg_gn_audit_summary *>(slots[0].dev),
-                       reinterpret_cast<double *>(slots[1].dev), reinterpret_cast<double *>(slots[2].dev),
-                       reinterpret_cast<double *>(slots[3].dev), reinterpret_cast<double *>(slots[4].dev));
-    HIP_TRY(hipGetLastError());
-    return collect_outputs(e, slots, 5);
 }
 
 int orlg_simple_matrix_obs_dim(orlg_env *e) { return e ? 2 * e->p.N + e->p.E * e->p.S : ORLG_ERR_INVALID; }
@@ -1456,6 +608,15 @@ extern "C" int orlg_debug_group_plan(const int32_t *in, int32_t n_in, int32_t *o
     ORLG_GROUP_PLAN_OUT(X)
 #undef X
     return i;
+}
+// what orlg_step_call.h makes of a call of a step entry, without a device or a handle (tests/test_step_calls.py): in[] = entry kind,
+// policy or route, rule, gn_mode, n_steps, the handle has a gate, the gate protects; out[] = policy, assign.  Returns the code
+extern "C" int orlg_debug_step_call(const int32_t *in, int32_t n_in, int32_t *out) {
+    if (!in || !out || n_in != 7) return fail(ORLG_ERR_INVALID, "orlg_debug_step_call: %d inputs", n_in);
+    OrlgStepCall call = {};
+    const int rc = orlg_step_call({in[0], in[1], in[2], in[3], in[4], in[5] != 0, in[6] != 0}, &call);
+    out[0] = call.policy; out[1] = call.assign;
+    return rc;
 }
 #ifdef ORLG_SECTIONS
 #include "orlg_sections.h"   // orlg_sections[]

@@ -1,5 +1,5 @@
 // orlg_device.h -- device-side data layout shared by the kernels (through orlg_wave.h) and the host API
-// (orlg_host.h, orlg_api.hip).  Names follow the reference's domain: links, slots, paths, services, release queue.
+// (orlg_host.h, the RMSA API's units orlg_api*.hip behind orlg_rmsa_host.h).  Names follow the reference's domain: links, slots, paths, services, release queue.
 #pragma once
 #include <hip/hip_vector_types.h>   // uint4
 #include <stdint.h>

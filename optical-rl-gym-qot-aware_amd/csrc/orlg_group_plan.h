@@ -1,7 +1,7 @@
 // orlg_group_plan.h -- what the host decides about a launch of the four-environments-per-wave step kernel (orlg_group_kernels.hip):
 // the LDS layout of a wave's region for each of the kernel's three kinds of instantiation, and from them the kind, the workgroup, the
 // grid and the tickets of one launch.  Arithmetic only -- no HIP call, no environment variable, no handle -- so all of it runs
-// without a device (orlg_debug_group_plan); rmsa_create and launch_rmsa_group (orlg_api.hip) do what it says.
+// without a device (orlg_debug_group_plan); rmsa_create (orlg_api.hip) and launch_rmsa_group (orlg_api_step.hip) do what it says.
 #pragma once
 #include <cmath>
 #include <cstddef>

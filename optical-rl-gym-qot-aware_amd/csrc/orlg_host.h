@@ -1,5 +1,5 @@
-// orlg_host.h -- the host side that the translation units of liborlg.so share (orlg_host.hip defines it; orlg_api.hip,
-// orlg_phy_api.hip and orlg_osnr.hip use it): errors, the handle core of both C APIs with the functions that work on it, the
+// orlg_host.h -- the host side that the translation units of liborlg.so share (orlg_host.hip defines it; the RMSA API's
+// units through orlg_rmsa_host.h, orlg_phy_api.hip and orlg_osnr.hip use it): errors, the handle core of both C APIs with the functions that work on it, the
 // helper kernels that differ only in the scalar record, and what a launch of a step kernel does around the launch itself.  The
 // kernel instantiations, their keys and names: orlg_variants.h.
 #pragma once

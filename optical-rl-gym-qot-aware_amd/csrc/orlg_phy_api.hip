@@ -1,6 +1,6 @@
 // orlg_phy_api.hip -- host side of the QoT-aware (PhyRMSA) path: orlg_phy_* entry points of include/orlg.h.
 // Its own translation unit; the step kernel is instantiated per word count in orlg_inst_phy.hip.  What it has in common with the
-// RMSA API (orlg_api.hip) is the handle core of orlg_host.h.
+// RMSA API (orlg_api.hip, orlg_api_step.hip, orlg_api_query.hip) is the handle core of orlg_host.h.
 #include "orlg_host.h"
 #include "orlg_lds.h"
 #include "orlg_phy_layout.h"

@@ -5,7 +5,7 @@
 // LDS; apply_window: a slot window set or cleared on every link of a path in the wave's bitmap (it lives here and not in
 // orlg_spectrum.h because it takes a Wave, and the QoT-aware kernels include orlg_spectrum.h); KernargParams / kernarg_params:
 // the opaque re-read of OrlgParams from the kernarg segment.  The byte offsets themselves are OrlgParams' (orlg_device.h), computed
-// by the host (orlg_api.hip).
+// by the host (rmsa_create, orlg_api.hip).
 //
 // Reference: optical_rl_gym/envs/rmsa_env.py _provision_path :462-513 and _release_path :515-535 (apply_window: the slot
 // window of a service on the links of its path).

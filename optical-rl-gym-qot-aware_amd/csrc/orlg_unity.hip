@@ -6,6 +6,8 @@
 #endif
 #include "orlg_host.hip"
 #include "orlg_api.hip"
+#include "orlg_api_step.hip"
+#include "orlg_api_query.hip"
 #include "orlg_phy_api.hip"
 #include "orlg_osnr.hip"
 #include "orlg_inst_wave.hip"

@@ -67,7 +67,7 @@ def _none_named(deps, *patterns):
 def test_family_boundaries_hold():
     build.build(verbose=False)
     # the wave-per-environment step kernel is parsed by its own objects only
-    for pattern in ("orlg_inst_phy*_w*", "orlg_inst_group_w*", "orlg_api", "orlg_phy_api", "orlg_osnr"):
+    for pattern in ("orlg_inst_phy*_w*", "orlg_inst_group_w*", "orlg_api", "orlg_api_step", "orlg_api_query", "orlg_phy_api", "orlg_osnr"):
         assert _none_named(_dep_names(pattern), "orlg_kernels.hip") == {}
     assert len(_dep_names("orlg_inst_phy*_w*")) == 10 and len(_dep_names("orlg_inst_group_w*")) == 7
     # the QoT-aware family takes path_word from orlg_spectrum.h and nothing of the RMSA path's layout or statistics
