@@ -622,8 +622,8 @@ extern "C" int orlg_debug_step_call(const int32_t *in, int32_t n_in, int32_t *ou
 #include "orlg_sections.h"   // orlg_sections[]
 extern "C" int orlg_debug_sections(unsigned long long *out, int reset) {
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(orlg_sections), 16 * 8));
-    if (reset) { unsigned long long z[16] = {0}; HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(orlg_sections), z, 16 * 8)); }
+    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(orlg_sections), ORLG_NSEC * 8));
+    if (reset) { unsigned long long z[ORLG_NSEC] = {0}; HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(orlg_sections), z, ORLG_NSEC * 8)); }
     return ORLG_OK;
 }
 #endif

@@ -349,11 +349,29 @@
             for (int p0 = 0; p0 < kmax; p0 += PP) {
                 if (!llp && ballot(act && a_ok && found == 0x7fffffff) == 0ull) break;
                 const int pp = p0 + ps;
-                const bool on = ps < PP && pp < kmax && a_ok;
+                bool on = ps < PP && pp < kmax && a_ok;
                 int se_pp, hops_pp;
-                const u64 x = group_path_word_rec<W>(occ, tb.recs, base + path0 + pp, w, on, se_pp, hops_pp);
                 int n = 1;
-                if (on) n = tb.nslots[req_br * ORLG_NSLOT_STRIDE + se_pp];
+                // the pass's path record (an inactive lane keeps a zero record, group_path_word_rec's): the pass below is written ONCE,
+                // from the record -- with the pass in both arms of the branch the lean body carried three scratch reloads into
+                // the step loop
+                uint4 rq = make_uint4(0u, 0u, 0u, 0u);
+                if (LEAN && p0 > 0) {
+                    // A first-fit pass after the first (LEAN: first fit, and the links' summaries exist): only the rows that have no
+                    // window yet look on, and only at the paths whose links all have a free run of n (group_path_candidate, which
+                    // also loads the record and the slot count); a pass that no row of the batch has such a path for would find
+                    // nothing and is left out.  Left out, not the last: with three passes the last one may hold the window the
+                    // middle one cannot.  Rows past the batch's end do not vote.  (The full body of the DEFER instantiations could
+                    // run the same test -- lsum is there -- but it costs that body spilled registers, and no long launch runs it)
+                    SEC(16);  // longest-run test
+                    on = group_path_candidate<W>(lane, lsum, tb, base + path0 + pp, base, w, on && found == 0x7fffffff, req_br, rq, n);
+                    SEC(2);
+                    if (ballot(act && on) == 0ull) continue;
+                } else if (on) {
+                    rq = *reinterpret_cast<const uint4 *>(tb.recs + (base + path0 + pp));
+                }
+                const u64 x = group_path_word_of<W>(occ, rq, w, on, se_pp, hops_pp);
+                if (!(LEAN && p0 > 0) && on) n = tb.nslots[req_br * ORLG_NSLOT_STRIDE + se_pp];
                 u64 r = run_starts<W>(x & ~lastbit, n, w);
                 const u64 xprev = lane_prev_u64(x);
                 if (deep) {

@@ -84,10 +84,10 @@ ORLG_SEG_REDUCE(seg_max, ORLG_OP_MAX)
 // The host pads the bytes past the end with the path's first link (OrlgPathRec, orlg_device.h) and AND is idempotent, so a
 // hop past the end repeats a word the result already holds; its address is a link of the path, valid on every lane.  An
 // inactive lane keeps a zero record: it reads link 0, starts from acc = 0 and returns 0 with se = hops = 0, as there.
+// group_path_word_of: the same from a record the caller holds in registers (the later first-fit passes of the lean body
+// load it for group_path_candidate below and hand it on); an inactive lane passes a record whose first word is zero.
 template <int W>
-DEV u64 group_path_word_rec(const u64 *occ, const OrlgPathRec *recs, int gid, int w, bool active, int &se, int &hops_out) {
-    uint4 r = make_uint4(0u, 0u, 0u, 0u);
-    if (active) r = *reinterpret_cast<const uint4 *>(recs + gid);
+DEV u64 group_path_word_of(const u64 *occ, const uint4 r, int w, bool active, int &se, int &hops_out) {
     const uint32_t q[4] = {r.x, r.y, r.z, r.w};
     const int hops = (int)(r.x & 0xffu);
     se = (int)((r.x >> 8) & 0xffu);
@@ -110,6 +110,12 @@ DEV u64 group_path_word_rec(const u64 *occ, const OrlgPathRec *recs, int gid, in
     }
     return acc;
 }
+template <int W>
+DEV u64 group_path_word_rec(const u64 *occ, const OrlgPathRec *recs, int gid, int w, bool active, int &se, int &hops_out) {
+    uint4 r = make_uint4(0u, 0u, 0u, 0u);
+    if (active) r = *reinterpret_cast<const uint4 *>(recs + gid);
+    return group_path_word_of<W>(occ, r, w, active, se, hops_out);
+}
 
 // A link's summary (DEFER instantiation, LDS only): every integer _update_link_stats consumes, 10 bits each -- free slots, free
 // runs, used runs, first used slot (lmin), end of the last used run (lmax), longest free run, slot 0 free, slot S - 1 free.  With
@@ -118,6 +124,49 @@ DEV u64 group_path_word_rec(const u64 *occ, const OrlgPathRec *recs, int gid, in
 DEV u64 lsum_pack(int freec, int F, int U, int lmin, int lmax, int ml, bool ff, bool lf) {
     return (u64)((uint32_t)freec | ((uint32_t)F << 10) | ((uint32_t)U << 20)) |
            ((u64)((uint32_t)(lmin & 0x3ff) | ((uint32_t)lmax << 10) | ((uint32_t)ml << 20) | ((uint32_t)ff << 30) | ((uint32_t)lf << 31)) << 32);
+}
+
+// The longest-run test of a first-fit pass after the first (the lean body of the DEFER instantiations).  A
+// path can hold a window of n slots only if every one of its links has a free run of n, and a link's summary holds its longest
+// free run ml -- exact after every provision (the statistics pass recomputes it), every release (max(ml, L + n + R)) and every
+// state load.  The pass's own layout: lane (ps, w) of path record gid tests hops w, w + W, w + 2 W, ... -- a byte of the record
+// and the high half of that link's summary per hop -- and the path's W lanes learn the outcome from one row vote.
+// Straight-line code, two LDS round trips: the record and the lane's link bytes, then the slot count and the summaries.  So
+// nothing is tested against the path's end or against `on`, knowingly: a byte past the path's end repeats the path's first link
+// (OrlgPathRec, orlg_device.h), whose outcome the vote holds already; a hop index past the record's last byte is clamped to that
+// byte (a link of the path, or the padding); and a lane that is not on reads record gid0, which every lane may read (the
+// first candidate of the row's request), and does not vote.
+// Returns the lane's `on` for the pass: on, and no link of its path rules the window out.  rec: the path's record for
+// group_path_word_of (its first word zero where the result is false); n: the path's slot count, 1 where the result is false
+// (run_starts' doubling loop runs to the largest n of the wave: a lane that does not look must not lengthen it).  The vote stands outside every
+// condition (row_ballot).
+template <int W>
+DEV bool group_path_candidate(const int lane, const u64 *lsum, const Tab &tb, int gid, int gid0, int w, bool on, int br, uint4 &rec, int &n) {
+    constexpr int NH = (ORLG_MAX_HOPS + W - 1) / W;   // hops per lane at most
+    const uint32_t *sum_hi = reinterpret_cast<const uint32_t *>(lsum) + 1;
+    const OrlgPathRec *pr = tb.recs + (on ? gid : gid0);
+    uint4 r = *reinterpret_cast<const uint4 *>(pr);
+    int lk[NH];
+#pragma unroll
+    for (int j = 0; j < NH; ++j) {
+        int h = w + j * W;
+        if ((j + 1) * W > ORLG_MAX_HOPS) h = h < ORLG_MAX_HOPS - 1 ? h : ORLG_MAX_HOPS - 1;   // (the last group only)
+        lk[j] = (int)pr->link[h];
+    }
+    n = tb.nslots[br * ORLG_NSLOT_STRIDE + (int)((r.x >> 8) & 0xffu)];
+    uint32_t ml = 0x3ffu;   // the shortest of the longest runs of the lane's hops
+#pragma unroll
+    for (int j = 0; j < NH; ++j) {
+        const uint32_t m = (sum_hi[2 * lk[j]] >> 20) & 0x3ffu;
+        ml = m < ml ? m : ml;
+    }
+    const uint32_t bad = row_ballot(on && (int)ml < n, lane);
+    const uint32_t mine = ((1u << W) - 1u) << ((lane & 15) - w);   // the lanes of this lane's path
+    const bool ok = on && (bad & mine) == 0u;
+    r.x = ok ? r.x : 0u;
+    n = ok ? n : 1;   // (a lane that is not on must not lengthen run_starts for the others)
+    rec = r;
+    return ok;
 }
 
 // link statistics of up to ORLG_MAX_HOPS links per row: link_stats_update (orlg_link_stats.h) with 16 / W links per row and

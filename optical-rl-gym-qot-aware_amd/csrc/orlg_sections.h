@@ -5,17 +5,19 @@
 #pragma once
 #include "orlg_wave.h"
 
+// section ids 0 .. ORLG_NSEC - 1 (tools/section_profile.py names them); one lane of a wave per id
+#define ORLG_NSEC 20
 #ifdef ORLG_SECTIONS
-__device__ unsigned long long orlg_sections[16];
-#define SEC_DECL_G __shared__ unsigned long long sec_acc[16][16]; long long sec_t0 = 0; int sec_cur = 0; \
-    if (lane < 16) sec_acc[wib][lane] = 0ull; wave_sync(); sec_t0 = __builtin_readcyclecounter();
-#define SEC_DECL __shared__ unsigned long long sec_acc[ORLG_MAX_WAVES_PER_BLOCK][16]; long long sec_t0 = 0; int sec_cur = 0; \
-    if (lane < 16) sec_acc[wib][lane] = 0ull; wave_sync(); sec_t0 = __builtin_readcyclecounter();
+__device__ unsigned long long orlg_sections[ORLG_NSEC];
+#define SEC_DECL_G __shared__ unsigned long long sec_acc[16][ORLG_NSEC]; long long sec_t0 = 0; int sec_cur = 0; \
+    if (lane < ORLG_NSEC) sec_acc[wib][lane] = 0ull; wave_sync(); sec_t0 = __builtin_readcyclecounter();
+#define SEC_DECL __shared__ unsigned long long sec_acc[ORLG_MAX_WAVES_PER_BLOCK][ORLG_NSEC]; long long sec_t0 = 0; int sec_cur = 0; \
+    if (lane < ORLG_NSEC) sec_acc[wib][lane] = 0ull; wave_sync(); sec_t0 = __builtin_readcyclecounter();
 #define SEC(i) do { const long long sec_n = __builtin_readcyclecounter(); if (lane == 0) sec_acc[wib][sec_cur] += (unsigned long long)(sec_n - sec_t0); \
     sec_t0 = sec_n; sec_cur = (i); } while (0)
-#define SEC_FLUSH do { SEC(0); wave_sync(); if (lane < 16) atomicAdd(&orlg_sections[lane], sec_acc[wib][lane]); } while (0)
+#define SEC_FLUSH do { SEC(0); wave_sync(); if (lane < ORLG_NSEC) atomicAdd(&orlg_sections[lane], sec_acc[wib][lane]); } while (0)
 // device functions that time their own sub-sections take the kernel's accumulators along
-#define SEC_PARAMS , unsigned long long (*sec_acc)[16], long long &sec_t0, int &sec_cur, int wib
+#define SEC_PARAMS , unsigned long long (*sec_acc)[ORLG_NSEC], long long &sec_t0, int &sec_cur, int wib
 #define SEC_ARGS , sec_acc, sec_t0, sec_cur, wib
 #else
 #define SEC_PARAMS

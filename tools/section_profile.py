@@ -7,7 +7,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "optical-rl-gym-qot-aware_amd")
 LIB = os.path.join(PKG, "liborlg_sections.so")
 NAMES = ["idle/ticket", "state load", "policy", "validate+provision", "stats@provision", "queue insert", "outputs",
-         "next arrival", "refill", "release scan", "release apply", "stats@release", "done/reset", "state store", "link replay", "graph replay"]
+         "next arrival", "refill", "release scan", "release apply", "stats@release", "done/reset", "state store", "link replay", "graph replay",
+         "policy: longest-run test"]
+NSEC = 20   # ORLG_NSEC (csrc/orlg_sections.h)
 
 
 def main():
@@ -46,7 +48,7 @@ def main():
                  "defrag: grooming scan", "defrag: candidate scan", "state store", "defrag: candidate rounds", "defrag: candidate ranks"]
         env.run(args.phy, 3000, auto_reset=True)
         L = _lib.load()
-        out = (C.c_ulonglong * 16)()
+        out = (C.c_ulonglong * NSEC)()
         L.orlg_debug_sections(out, 1)
         if args.metrics:
             import torch
@@ -67,7 +69,7 @@ def main():
                          mean_service_holding_time=25, episode_length=1000, seed=10, stats_level=args.stats)
     env.run("sap_ff", 500, auto_reset=True)
     L = _lib.load()
-    out = (C.c_ulonglong * 16)()
+    out = (C.c_ulonglong * NSEC)()
     L.orlg_debug_sections(out, 1)
     chunk = args.chunk or args.steps
     for _ in range(args.steps // chunk):
@@ -75,7 +77,7 @@ def main():
     env.synchronize()
     L.orlg_debug_sections(out, 1)
     tot = sum(out)
-    res = {NAMES[i]: round(100.0 * out[i] / tot, 2) for i in range(16)}
+    res = {NAMES[i]: round(100.0 * out[i] / tot, 2) for i in range(len(NAMES))}
     res["cycles_per_env_step"] = tot / (args.batch * args.steps)
     print(json.dumps({"stats": args.stats, "batch": args.batch, "percent_of_wave_cycles": res}))
 
