@@ -9,6 +9,7 @@
 // Reference: optical_rl_gym/envs/rmsa_env.py is_path_free :721-734, get_available_slots :745-756, get_available_blocks :774-804,
 // the first-fit loops of the heuristics :860-871, :908-913.
 #pragma once
+#include "orlg_run_schedule.h"
 #include "orlg_wave.h"
 
 // ---------------------------------------------------------------------------------------- first fit
@@ -137,21 +138,35 @@ DEV u64 path_word_rec(const u64 *occ, const OrlgPathRec *recs, int gid, int w, b
 // of a row (w = the lane's word; `x` = 0 on lanes that hold nothing).  r_m = AND of x >> 0 .. x >> (m - 1) is doubled:
 // r_{m+k} = r_m & (r_m >> k) for k <= m; k <= 31, so that a shift is two 32-bit funnel shifts (v_alignbit_b32) fed by the next
 // word's low half (one DPP read).  n may differ between the rows (and between the paths inside a row): the loop runs to the
-// longest, a finished lane shifts by k = 0, which leaves it as it is -- no predication.
+// longest, a finished lane shifts by k = 0, which leaves it as it is -- no predication.  The schedule is orlg_run_schedule.h's: the
+// slots covered so far are one number for the wave (have_u and the round's step ku depend on no lane: scalar registers), a lane
+// carries only what it has left (rem), n >= 1.  `keep` (nothing beyond the path's last word) is a mask in a register, not a
+// condition -- the empty asm keeps the compiler from turning it back into a select -- so that the DPP read, which gives 0 past
+// the row's end, folds into the AND (v_and_b32_dpp).  Eight vector instructions a round: v_min (k), v_and_dpp, 2 x v_alignbit,
+// 2 x v_and, v_sub (rem), v_cmp (the ballot).  The ballot and the DPP read stand outside every condition.
+//
+// The loop's shape is part of its cost.  The exit test is a ballot of rem > 0 (which is k > 0: ku >= 1) at the END of a round,
+// behind one test before the first: the compiler then closes the round with v_cmp + s_cbranch_vccnz, one taken branch, and
+// keeps have_u scalar.  `for (;;) { ...; if (ballot(k > 0) == 0) break; ... }` became a round of three branches around a
+// scalar select of the exit condition, and `while (ballot(rem > 0))` put have_u into a vector register (profiles/README.md,
+// round 17: the shape is worth more than the three instructions).
 template <int W>
 DEV u64 run_starts(u64 x, int n, int w) {
     uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
-    const uint32_t keep = w == W - 1 ? 0u : ~0u;  // nothing beyond the last word
-    int have = 1;
-    for (;;) {
-        int k = n - have;
-        k = k < have ? k : have;
-        k = k < 31 ? k : 31;
-        if (ballot(k > 0) == 0ull) break;
-        const uint32_t nlo = (uint32_t)lane_next_i32((int)lo) & keep;
-        const uint32_t slo = __builtin_amdgcn_alignbit(hi, lo, (uint32_t)k), shi = __builtin_amdgcn_alignbit(nlo, hi, (uint32_t)k);
-        lo &= slo; hi &= shi;
-        have += k;
+    uint32_t keep = w == W - 1 ? 0u : ~0u;  // nothing beyond the last word
+    asm volatile("" : "+v"(keep));
+    int rem = orlg_run_rem0(n);
+    int have_u = 1;
+    if (ballot(rem > 0) != 0ull) {   // (none: every lane wants one slot, r_1 = x)
+        do {
+            const int ku = orlg_run_ku(have_u);
+            const int k = orlg_run_k(rem, ku);
+            const uint32_t nlo = (uint32_t)lane_next_i32((int)lo) & keep;
+            const uint32_t slo = __builtin_amdgcn_alignbit(hi, lo, (uint32_t)k), shi = __builtin_amdgcn_alignbit(nlo, hi, (uint32_t)k);
+            lo &= slo; hi &= shi;
+            rem -= k;
+            have_u += ku;
+        } while (ballot(rem > 0) != 0ull);
     }
     return ((u64)hi << 32) | lo;
 }
