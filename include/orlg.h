@@ -507,6 +507,25 @@ int orlg_gn_admission_masks(orlg_env *env, uint8_t *path_ff, double *path_ff_gsn
                             double *deeprmsa_gsnr_db, double *deeprmsa_margin_db);
 int orlg_gn_admission_windows(orlg_env *env, int32_t rule, int16_t *slots, double *gsnr_db, double *margin_db, uint8_t *admitted);
 
+/* The admission check over the WHOLE spectrum (this project's): for the pending request of every environment, every
+ * path p < k and every start slot s < S, on any handle with a gate.  n = get_number_slots(p), thr = thresholds_db[SE(p) - 1],
+ * window(p, s) = the "slots" bit of orlg_action_masks (s + n <= S and [s, s + n) free on every hop, the start S - n included).
+ * mask: [B][k][W] uint64 or NULL, bit s % 64 of word s / 64, W = orlg_words_per_link -- window && gsnr >= thr && !(margin < 0.0): the
+ *   step's own predicate, the outcome of orlg_step_gn_protect with ORLG_POLICY_EXTERNAL and action [p, s] on this handle.
+ * gsnr_db: [B][k][S] float64 or NULL -- the GSNR the step would compare for [s, s + n) on p, NaN where window is 0.
+ * margin_db: [B][k][S] float64 or NULL -- the candidate's neighbour margin (orlg_set_gn_protect), NaN where that check would not run:
+ *   no window, the own check refuses, no running service shares a link, or the handle does not protect.
+ * best_slot: [B][k] int16 or NULL -- the lowest start among the admitted windows of p with the largest WORST MARGIN
+ *   w = gsnr - thr, or min(gsnr - thr, margin) where the margin is not NaN; S where p has no admitted window.
+ * best_margin_db: [B][k] float64 or NULL -- that w, NaN where p has none.
+ * The start slots sit on lanes and sum the interferers in ring order, the step by a wave reduction: the GSNR agrees with the step's
+ * gn_gsnr_db to ~1e-15 relative, and a window whose gsnr - thr comes out within 1e-9 dB of zero is evaluated by the step's own
+ * routine, so that the bit is the step's; the margin has the bits of the step's gn_neighbour_margin_db.
+ * Any pointer may be NULL, not all.  ORLG_ERR_INVALID: a handle without a gate, all pointers NULL, or a release queue that does not
+ * fit the LDS next to the tables.  Runs on the handle's stream, reads state and writes only the caller's buffers.  Buffers as
+ * orlg_gn_admission_masks. */
+int orlg_gn_admission_slots(orlg_env *env, uint64_t *mask, double *gsnr_db, double *margin_db, int16_t *best_slot, double *best_margin_db);
+
 /* ---- the running services of every environment, and their GN-model audit (this project's).  Every gate entry above
  * asks whether a CANDIDATE should be lit; these two say how the lightpaths that are already running are doing.  The state they read
  * is the state between launches, which holds no service that is due at the pending request's arrival.

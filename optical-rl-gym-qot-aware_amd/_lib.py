@@ -221,7 +221,9 @@ def _prototypes():
               "orlg_gn_audit": (None, [vp, P(RmsaGnGate), vp, vp, vp, vp, vp]),
               # the masks and rule windows that know both halves of the admission check (a protecting handle's too)
               "orlg_gn_admission_masks": (None, [vp, vp, vp, vp, vp, vp, vp]),
-              "orlg_gn_admission_windows": (None, [vp, i32, vp, vp, vp, vp])})
+              "orlg_gn_admission_windows": (None, [vp, i32, vp, vp, vp, vp]),
+              # ... over every start slot of every path: mask words, GSNR and margin rows, the window with the largest worst margin
+              "orlg_gn_admission_slots": (None, [vp, vp, vp, vp, vp, vp])})
     # QoT-aware only
     t.update({"orlg_phy_step": (None, [vp, i32, i32, vp, vp, i32, P(PhyStepIO)]), "orlg_phy_node_vectors": (None, [vp]),
               "orlg_phy_get_episode_stats": (None, [vp, vp]), "orlg_phy_channel_masks": (None, [vp, vp]),

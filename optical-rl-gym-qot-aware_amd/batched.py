@@ -568,6 +568,54 @@ class BatchedRMSAEnv(BatchedHandle):
         _lib.check(self.L.orlg_gn_admission_windows(self.h, _lib.GN_PATH_WINDOW_RULES[rule], *(_ptr(b) for b in res)))
         return tuple(res)
 
+    # ------------------------------------------------------------------ the check over every start slot of every path
+    def _checked_out(self, name, buf, shape, dt):
+        """an output buffer of a query: None = a new array, else the caller's, checked"""
+        if buf is None:
+            return np.zeros(shape, dt)
+        _check_buffer(name, buf, shape, dt)
+        if not hasattr(buf, "data_ptr") and not buf.flags["WRITEABLE"]:
+            raise ValueError(f"{name}: read-only array")
+        return buf
+
+    def admission_slot_masks(self, out=None, gsnr_out=None, margin_out=None):
+        """The GN-model admission check over the whole spectrum (``orlg_gn_admission_slots``; a handle with
+        ``gn_gate=`` only): ``mask`` [B, k, W] uint64, laid out as ``action_masks("slots")`` -- bit ``s`` of path ``p`` is 1 iff
+        ``run("external", actions=[p, s])`` on THIS handle would accept the pending request: the window ``[s, s + n)`` is free on
+        every hop, its own GSNR meets the threshold of the path's modulation and, on a handle that protects its running lightpaths
+        (``protect_running``), the neighbour margin is not below zero.  ``gsnr_out`` / ``margin_out``: a float64 buffer [B, k, S] or
+        ``True`` for a new array -- the GSNR in dB the step would compare for that window (NaN = no free window) and the
+        candidate's neighbour margin in dB (NaN = the second check would not run: no window, the own check refuses, no running
+        service shares a link, or the handle does not protect).  Returns ``mask``, or a tuple ``(mask[, gsnr][, margin])`` with the
+        rows that were asked for.  The GSNR agrees with the step's ``gn_gsnr_db`` to ~1e-15 relative (start slots on lanes sum the
+        interferers in ring order), the bit is the step's decision, the margin has the bits of ``gn_neighbour_margin_db``.  Reads
+        state only; the buffers as ``out`` in :meth:`action_masks`."""
+        if self.gn_gate is None:
+            raise ValueError("admission_slot_masks needs a handle with a GN-model admission check (gn_gate=)")
+        B, k, S = self.batch_size, self.k_paths, self.num_spectrum_resources
+        out = self._checked_out("out", out, (B, k, self.words_per_link), np.uint64)
+        gsnr = self._float_rows("gsnr_out", gsnr_out, (B, k, S))
+        margin = self._float_rows("margin_out", margin_out, (B, k, S))
+        _lib.check(self.L.orlg_gn_admission_slots(self.h, _ptr(out), None if gsnr is None else _ptr(gsnr),
+                                                  None if margin is None else _ptr(margin), None, None))
+        res = (out,) + tuple(r for r in (gsnr, margin) if r is not None)
+        return out if len(res) == 1 else res
+
+    def max_margin_windows(self, slots_out=None, margin_out=None):
+        """Of all windows of every candidate path that the admission check of THIS handle admits, the one that leaves the most
+        margin (``orlg_gn_admission_slots``; a handle with ``gn_gate=`` only): ``(slots, margin)`` -- [B, k] int16, the
+        lowest start among the admitted windows with the largest worst margin (``S`` = the path has no admitted window), and
+        [B, k] float64, that margin in dB (NaN = none): ``gsnr - threshold`` of the window itself or, where it is smaller, the
+        neighbour margin of a protecting handle.  ``run("external", actions=[p, slots[p]])`` accepts wherever ``slots[p] < S``.
+        Reads state only; the buffers as ``out`` in :meth:`action_masks`."""
+        if self.gn_gate is None:
+            raise ValueError("max_margin_windows needs a handle with a GN-model admission check (gn_gate=)")
+        shape = (self.batch_size, self.k_paths)
+        slots = self._checked_out("slots_out", slots_out, shape, np.int16)
+        margin = self._checked_out("margin_out", margin_out, shape, np.float64)
+        _lib.check(self.L.orlg_gn_admission_slots(self.h, None, None, None, _ptr(slots), _ptr(margin)))
+        return slots, margin
+
     # ------------------------------------------------------------------ the running services and their GN-model audit
     RUNNING_SERVICE_FIELDS = (("count", np.int32, False), ("head", np.int32, False), ("path_gid", np.int32, True),
                               ("slot", np.int16, True), ("num_slots", np.int16, True), ("bit_rate", np.int32, True),

@@ -1,7 +1,8 @@
 // orlg_api_query.hip -- the entry points of the RMSA C API (include/orlg.h) that read the state of the batch with a kernel: the path
 // masks of one environment, and for the whole batch the DeepRMSA observation, the action masks, fit levels, cuts and slot usage, the
-// masks and rule windows that know the GN-model admission check, the running services and their audit.  Each keeps its argument
-// checks, its slot table, its LDS bytes per wave and its argument list; the launch is launch_wave_query.
+// masks and rule windows that know the GN-model admission check, that check over every start slot of every path, the running
+// services and their audit.  Each keeps its argument checks, its slot table, its LDS bytes per wave and its argument list; the
+// launch is launch_wave_query.
 #include "orlg_rmsa_host.h"
 
 typedef orlg_masks_kernel_t masks_kernel_t;
@@ -57,8 +58,9 @@ static int collect_outputs(orlg_env *e, const OutSlot *slots, int n) {
 // The fit: rmsa_create chose waves_per_block with l_shared_bytes + waves_per_block * l_wave_bytes <= ORLG_LDS_BYTES, and
 // l_wave_bytes holds the occupancy row, 12 * Q bytes of release queue and the 2496 bytes of generator state.  A query that asks per
 // wave for no more than that -- the row and up16(4 * Q) of descriptors, the descriptors alone, the row and its 256 * W <= 2048 bytes
-// of prefix sums -- therefore fits with the handle's waves_per_block, whatever the shape.  The DeepRMSA observation alone can ask for
-// more (obs_dim * 8 grows with N, K and j), and is refused here.
+// of prefix sums, the row and twice up16(4 * Q) (descriptors and compacted offsets) -- therefore fits with the handle's
+// waves_per_block, whatever the shape.  The DeepRMSA observation alone can ask for more (obs_dim * 8 grows with N, K and j), and is
+// refused here.
 template <typename... Params, typename... Args>
 static int launch_wave_query(orlg_env *e, void (*k)(Params...), size_t per_wave, OutSlot *slots, int n, const Args &...args) {
     if (int rc = place_outputs(e, slots, n)) return rc;
@@ -264,6 +266,21 @@ int orlg_gn_admission_windows(orlg_env *e, int32_t rule, int16_t *slots_out, dou
     OutSlot slots[4] = {{slots_out, bk * sizeof(int16_t)}, {gsnr_db, bk * sizeof(double)}, {margin_db, bk * sizeof(double)}, {admitted, bk}};
     return launch_wave_query(e, orlg_pick_gn_admission_windows(e->W), occ_row_bytes(p) + ring_desc_bytes(p), slots, 4, p, query_rule(rule),
                              slots[0].dev, slots[1].dev, slots[2].dev, slots[3].dev, e->gn_protect ? 1 : 0);
+}
+
+// ---- the check over every start slot of every path (orlg_gn_slots_kernels.hip)
+int orlg_gn_admission_slots(orlg_env *e, uint64_t *mask, double *gsnr_db, double *margin_db, int16_t *best_slot, double *best_margin_db) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!mask && !gsnr_db && !margin_db && !best_slot && !best_margin_db)
+        return fail(ORLG_ERR_INVALID, "null argument: no mask, GSNR, margin or best-window buffer");
+    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn admission slots: the handle has no gn_gate");
+    HIP_TRY(hipSetDevice(e->device));
+    const OrlgParams &p = e->p;
+    const size_t bk = (size_t)p.B * p.K, bks = bk * p.S * sizeof(double);
+    OutSlot slots[5] = {{mask, bk * e->W * 8}, {gsnr_db, bks}, {margin_db, bks}, {best_slot, bk * sizeof(int16_t)}, {best_margin_db, bk * sizeof(double)}};
+    // a wave holds its environment's occupancy row, the live descriptors and the compacted offsets of the services that meet a path
+    return launch_wave_query(e, orlg_pick_gn_slots(e->W), occ_row_bytes(p) + 2 * ring_desc_bytes(p), slots, 5, p, slots[0].dev, slots[1].dev,
+                             slots[2].dev, slots[3].dev, slots[4].dev, e->gn_protect ? 1 : 0);
 }
 
 // ---- the running services and their GN-model audit (orlg_gn_audit_kernels.hip)

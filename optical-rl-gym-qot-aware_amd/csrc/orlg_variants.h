@@ -261,6 +261,12 @@ ORLG_FOR_EACH_W(ORLG_DECL_W, )
 ORLG_FOR_EACH_PHY_W(ORLG_DECL_PHY_W, )
 #undef ORLG_DECL_W
 #undef ORLG_DECL_PHY_W
+// orlg_gn_slots_kernels.hip: the admission check over every start slot of every path -- a unit of its own (orlg_inst_gnslots.hip,
+// one object per W) with a declaration list of its own: the lists above stay what they are
+typedef void (*orlg_gn_slots_kernel_t)(const OrlgParams, uint64_t *, double *, double *, int16_t *, double *, int);
+#define ORLG_DECL_GN_SLOTS_W(n, ...) orlg_gn_slots_kernel_t orlg_gn_slots_kernel_W##n() __attribute__((weak));
+ORLG_FOR_EACH_W(ORLG_DECL_GN_SLOTS_W, )
+#undef ORLG_DECL_GN_SLOTS_W
 
 // the lookup `lookup`<W> called with the arguments after it, as a function body: null when the library holds no such W
 #define ORLG_PICK_CASE(n, lookup, ...) case n: return lookup##n ? lookup##n(__VA_ARGS__) : nullptr;
@@ -286,3 +292,4 @@ static orlg_gn_action_masks_kernel_t orlg_pick_gn_action_masks(int W) { ORLG_PIC
 static orlg_gn_path_windows_kernel_t orlg_pick_gn_path_windows(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_path_windows_kernel_W, ) }
 static orlg_gn_admission_masks_kernel_t orlg_pick_gn_admission_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_admission_masks_kernel_W, ) }
 static orlg_gn_admission_windows_kernel_t orlg_pick_gn_admission_windows(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_admission_windows_kernel_W, ) }
+static orlg_gn_slots_kernel_t orlg_pick_gn_slots(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_slots_kernel_W, ) }

@@ -287,14 +287,27 @@ class RMSAEnv(_View):
         """Valid actions of ``MultiDiscrete(path, slot)`` for the pending request: bool [k + reject, S + reject], True where
         ``step([p, s])`` would provision the service (``rmsa_env.py:233-260``).  With ``allow_rejection`` the extra row and
         column belong to the explicit rejection ``[k, S]``: only their corner is True.  "The window is free": a GN-model
-        admission check (``gn_gate=``) may still refuse it, and ``gn=True`` is refused -- a slot matrix that knows the gate
-        would be ``k S`` GSNR evaluations per environment."""
+        admission check (``gn_gate=``) may still refuse it, and ``gn=True`` is refused here; the slot matrix that knows the gate
+        is :meth:`admission_slot_masks`."""
         if gn:
             raise ValueError("action_masks(gn=True): there is no slot matrix that knows the GN-model admission check (k * S GSNR "
                              "evaluations per environment); the gated masks are DeepRMSAEnv's and PathOnlyFirstFitAction's")
         k, S, r = self.k_paths, self.num_spectrum_resources, self.reject_action
         m = np.zeros((k + r, S + r), bool)
         m[:k, :S] = self._slot_bits()
+        if r:
+            m[k, S] = True
+        return m
+
+    def admission_slot_masks(self):
+        """:meth:`action_masks` under the GN-model admission check of this environment (``gn_gate=``, with ``protect_running`` both
+        halves; ``BatchedRMSAEnv.admission_slot_masks``, not in the reference): bool [k + reject, S + reject], True where
+        ``step([p, s])`` would be accepted -- the window is free, its GSNR meets the threshold of the path's modulation and no
+        running lightpath that shares a link falls below its own.  The rejection's corner as in :meth:`action_masks`."""
+        k, S, r = self.k_paths, self.num_spectrum_resources, self.reject_action
+        words = self._batched.admission_slot_masks()[self._index]
+        m = np.zeros((k + r, S + r), bool)
+        m[:k, :S] = np.unpackbits(words.view(np.uint8), axis=-1, bitorder="little")[:, :S].astype(bool)
         if r:
             m[k, S] = True
         return m
@@ -581,6 +594,31 @@ def shortest_available_path_first_fit_gn(env: RMSAEnv) -> Tuple[int, int]:
         if env.is_path_free(path, s, n):
             return (idp, s)
     return (k, S)
+
+
+MAX_MARGIN_ROUTES = ("sap", "any")
+
+
+def max_margin_heuristic(route):
+    """A callback ``f(env) -> (path, slot)`` for a ``gn_gate=`` environment (not in the reference): of the windows the
+    admission check admits, the one that leaves the most margin (``BatchedRMSAEnv.max_margin_windows``).  ``route``: ``"sap"`` -- the
+    first candidate path that has an admitted window, at its best window; ``"any"`` -- the path whose best window has the largest
+    margin, the lowest index on ties.  ``(k, S)``, the rejection, if no path has an admitted window."""
+    if route not in MAX_MARGIN_ROUTES:
+        raise ValueError(f"route {route!r}: expected one of {MAX_MARGIN_ROUTES}")
+
+    def heuristic(env):
+        S, k = env.topology.graph["num_spectrum_resources"], env.topology.graph["k_paths"]
+        slots, margin = env._batched.max_margin_windows()
+        slots, margin = slots[env._index], margin[env._index]
+        has = np.flatnonzero(slots < S)
+        if has.size == 0:
+            return (k, S)
+        idp = int(has[0]) if route == "sap" else int(has[np.argmax(margin[has])])
+        return (idp, int(slots[idp]))
+
+    heuristic.__name__ = f"{route}_max_margin"
+    return heuristic
 
 
 def assignment_slot(available, n, rule):
