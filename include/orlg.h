@@ -629,7 +629,8 @@ typedef struct orlg_phy_config {
     int32_t num_bit_rates;
     int32_t k_table;          /* k-path columns of the tables (>= topology k_paths) */
     int32_t num_table_rows;
-    int32_t queue_capacity;   /* running services per env, multiple of 64; 0 = from the load */
+    int32_t queue_capacity;   /* running services per env, multiple of 64; 0 = from the load: mean + 8 sigma + 32, at most what a
+                               * full network holds (links x channels x largest level's capacity / smallest bit rate), at most 8192 */
     int32_t grooming;         /* env.grooming (phy_rmsa_env.py:57): bmfa / bmfa_rss consult the virtual layer only when set;
                                * sapff / bmff / sapbm always do (:1256, 1321, 1678) */
     int32_t channel_state_capacity; /* entries per channel_state[src, dst, k-path] list (8..64); 0 = from the load */
@@ -745,7 +746,9 @@ int orlg_phy_get_occupancy(orlg_phy_env *env, uint64_t *out);
 int orlg_phy_reduce_counters(orlg_phy_env *env, int64_t *out /* [16] as orlg_reduce_counters */);
 /* as orlg_reseed */
 int orlg_phy_reseed(orlg_phy_env *env, const uint64_t *seeds, uint64_t base_seed);
-/* checkpoint / resume, as orlg_save_state */
+/* checkpoint / resume, as orlg_save_state.  A state carries the channel count of the handle that saved it: handles of the same
+ * word count and capacities have states of the same size, and orlg_phy_load_state refuses one of another channel count
+ * (ORLG_ERR_INVALID, nothing copied). */
 int64_t orlg_phy_state_size(orlg_phy_env *env);
 int orlg_phy_save_state(orlg_phy_env *env, void *buffer);
 int orlg_phy_load_state(orlg_phy_env *env, const void *buffer);

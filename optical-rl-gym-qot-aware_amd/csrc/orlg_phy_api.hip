@@ -33,6 +33,7 @@ __global__ void orlg_phy_clear_kernel(OrlgPhyParams p, int W, int keep_rng) {
         s.ring_pos = keep_rng ? p.scal[i].ring_pos : 0;
         s.ring_cnt = keep_rng ? p.scal[i].ring_cnt : 0;
         if (p.tr_arrival) { s.mt_idx = 0; s.ring_pos = 0; s.ring_cnt = 0; }   // a trace handle rewinds (as orlg_clear_state_kernel)
+        s.pad[0] = p.C;   // the shape stamp of a saved state (orlg_phy_load_state)
         p.scal[i] = s;
     }
 }
@@ -258,13 +259,24 @@ static int phy_create(const orlg_topology *t, const orlg_phy_config *c, int32_t 
         }
         p.cs_len = pw2;
     }
-    // release queue: at most Poisson(load) services in progress, and never more than the channel-links can hold
+    // release queue: at most Poisson(load) services in progress, and never more than a full network can hold.  Services on the
+    // virtual layer share channels, so the spectrum bounds them only through the capacity of a lit channel: a channel-link carries
+    // at most (largest level x 100 Gb/s) / (smallest bit rate) services -- every service takes at least one link of at least one
+    // channel, and a lit channel of a path holds no more than its level allows (phy_rmsa_env.py:600-602).  The default never
+    // exceeds the 8192 slots a queue can have; a network that needs more reports ORLG_ERR_QUEUE_FULL.
     int Q = c->queue_capacity;
     if (Q <= 0) {
         double load = arrival_lambda / holding_lambda;
         double q = load + 8.0 * std::sqrt(load) + 32.0;
-        double cap = (double)E * C / 2.0 + 64.0;
+        int max_level = 1;   // (the rows in use hold 1..31, checked above)
+        for (size_t i = 0, n = (size_t)c->num_table_rows * C * c->k_table; i < n; i++)
+            if (c->modulation_level[i] > max_level && c->modulation_level[i] <= 31) max_level = c->modulation_level[i];
+        int min_rate = c->bit_rates ? c->bit_rates[0] : 0;
+        for (int b = 1; c->bit_rates && b < NBR; b++) min_rate = c->bit_rates[b] < min_rate ? c->bit_rates[b] : min_rate;
+        // (a smallest bit rate of 0 -- continuous, lower bound 0 -- bounds nothing)
+        double cap = min_rate > 0 ? (double)E * C * std::ceil(100.0 * max_level / min_rate) + 64.0 : 8192.0;
         Q = (int)(q < cap ? q : cap);
+        if (Q > 8192) Q = 8192;
         if (trace) {   // the trace's own bound, unclamped: services on the virtual layer share channels, the spectrum does not bound them
             Q = trace_state.peak + 1;
             if (Q > 8192)
@@ -731,8 +743,24 @@ int orlg_phy_save_state(orlg_phy_env *e, void *buffer) {
     return orlg_handle_state_save(e, phy_state_parts(e), buffer);
 }
 int orlg_phy_load_state(orlg_phy_env *e, const void *buffer) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null argument");
-    return orlg_handle_load(e, phy_state_parts(e), buffer, e->p.scal, e->p.B);
+    if (!e || !buffer) return fail(ORLG_ERR_INVALID, "null argument");
+    // Two handles of the same word count, queue and list capacities save states of the same size whatever their channel counts
+    // (65 and 128 channels are two words each), and the bits of the last word's channels that do not exist read as occupied
+    // channels in the wider handle.  Every environment's scalars carry the channel count of the handle that cleared them: a
+    // state of another count is refused before anything is copied (0: saved before the stamp existed, taken as it is).
+    const std::vector<OrlgStatePart> parts = phy_state_parts(e);
+    size_t off = 0;
+    for (const OrlgStatePart &sp : parts) {
+        if (sp.ptr == e->p.scal) break;
+        off += sp.bytes;
+    }
+    std::vector<OrlgPhyScalars> scal((size_t)e->p.B);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpy(scal.data(), static_cast<const unsigned char *>(buffer) + off, scal.size() * sizeof(OrlgPhyScalars), hipMemcpyDefault));
+    for (int i = 0; i < e->p.B; i++)
+        if (scal[i].pad[0] != 0 && scal[i].pad[0] != e->p.C)
+            return fail(ORLG_ERR_INVALID, "snapshot of a handle with %d channels, this handle has %d", scal[i].pad[0], e->p.C);
+    return orlg_handle_load(e, parts, buffer, e->p.scal, e->p.B);
 }
 int orlg_phy_load_state_checked(orlg_phy_env *e, const void *buffer, int64_t bytes) {
     if (!e || !buffer) return fail(ORLG_ERR_INVALID, "null argument");

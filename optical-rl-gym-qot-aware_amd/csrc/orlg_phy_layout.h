@@ -56,7 +56,8 @@ struct __attribute__((aligned(16))) OrlgPhyScalars {
     int32_t n_running, req_src, req_dst, req_br, req_sid, mt_idx, new_service, q_overflow;
     int32_t next_seq, counted_moves, counted_moves_groom, counted_defrag_cycles;  // phy_rmsa_env.py:110-112
     int32_t ring_pos, ring_cnt;                  // pre-generated arrivals: next entry, entries left (OrlgPhyParams::ring_*)
-    int32_t pad[4];
+    int32_t pad[4];                              // pad[0]: the handle's channel count, stamped by the host when it clears the
+                                                 // state (orlg_phy_api.hip); the step kernel never writes the padding
 };
 static_assert(sizeof(OrlgPhyScalars) == 224, "OrlgPhyScalars layout");
 

@@ -333,6 +333,73 @@ def phy_matches_reference(z, tr, i, n):
         assert np.array_equal(dc[:, 1], z["num_moves_groom"][:n]) and np.array_equal(dc[:, 2], z["num_defrag_cycle"][:n])
 
 
+# ---------------------------------------------------------------------------------------- against a QoT-aware reference trace
+# (fixtures of run_phy_trace, tests/golden/make_golden.py: the float64 shares of a continuous handle included)
+PHY_TRACE_COUNTERS = ("services_processed", "services_accepted", "episode_services_processed", "episode_services_accepted",
+                      "bit_rate_requested", "bit_rate_provisioned")
+
+
+def channel_caps(topo, tables, tr, i):
+    """ch_cap of the trace: the table's level of every chosen channel on the chosen k-path (the tuple's field 3)."""
+    pairs, mod, _ = tables
+    rows = topo.pair_table_rows(pairs)
+    n = topo.num_nodes
+    caps = np.zeros(tr["channels"].shape[:1] + (12,), np.int16)
+    for t in range(caps.shape[0]):
+        a = int(tr["act_path"][t, i])
+        idp = a - 20 if a >= 20 else a
+        r = rows[int(tr["request"][t, i, 1]) * n + int(tr["request"][t, i, 2])]
+        for q in range(int(tr["n_channels"][t, i])):
+            caps[t, q] = mod[r, int(tr["channels"][t, i, q]), idp]
+    return caps
+
+
+def check_trace(topo, tables, tr, i, z, lo, hi):
+    """steps lo..hi-1 of env i's per-step outputs against the reference's trace"""
+    s = slice(lo, hi)
+    assert np.array_equal(tr["request"][:, i, 1], z["src_id"][s]) and np.array_equal(tr["request"][:, i, 2], z["dst_id"][s]), i
+    assert np.array_equal(tr["request"][:, i, 3], z["bit_rate"][s]), i
+    assert np.array_equal(tr["request"][:, i, 0], z["service_id"][s]), i
+    np.testing.assert_allclose(tr["arrival"][:, i], z["arrival"][s], rtol=1e-12, atol=0)
+    np.testing.assert_allclose(tr["holding"][:, i], z["holding"][s], rtol=1e-12, atol=0)
+    assert np.array_equal(tr["act_path"][:, i], z["act_path"][s]), i
+    assert np.array_equal(tr["n_channels"][:, i], z["n_channels"][s]), i
+    assert np.array_equal(tr["channels"][:, i, :12], z["channels"][s]), i
+    if "channels_used_f64" in tr:   # a continuous handle: the float64 shares, bit for bit
+        for f, g in (("channels_used_f64", "ch_used"), ("channels_free_f64", "ch_free")):
+            bad = np.argwhere(tr[f][:, i, :12] != z[g][s])
+            assert bad.size == 0, (f, i, bad[:3], tr[f][:, i, :12][tuple(bad[:3].T)], z[g][s][tuple(bad[:3].T)])
+    else:   # discrete bit rates: whole 100 Gb/s units (the handle has no output for the free share)
+        assert np.array_equal(tr["channels_used"][:, i, :12].astype(np.float64), z["ch_used"][s]), i
+    if "defrag_counters" in tr:
+        dc = tr["defrag_counters"][:, i].astype(np.int64)
+        assert np.array_equal(dc[:, 0] / 2 + dc[:, 1], z["num_moves"][s]), i
+        assert np.array_equal(dc[:, 1], z["num_moves_groom"][s]) and np.array_equal(dc[:, 2], z["num_defrag_cycle"][s]), i
+    assert np.array_equal(channel_caps(topo, tables, tr, i)[:, :12], z["ch_cap"][s]), i
+    assert np.array_equal(tr["accepted"][:, i], z["accepted"][s]) and np.array_equal(tr["done"][:, i], z["done"][s]), i
+    virtual = (tr["act_path"][:, i] >= 20) & (tr["accepted"][:, i] == 1)
+    assert np.array_equal(virtual, z["virtual"][s]), i
+    assert np.array_equal(tr["number_cuts_total"][:, i], z["number_cuts_total"][s]), i
+    assert np.array_equal(tr["rss_total_metric"][:, i], z["rss_total_metric"][s]), i
+
+
+def check_state(env, i, z, t):
+    """env i after step t (0-based) against the reference's record of that step"""
+    cnt = env.counters()
+    for name in PHY_TRACE_COUNTERS:
+        assert cnt[name][i] == z[name][t], (name, i, t)
+    np.testing.assert_allclose(env.current_time()[i], z["current_time"][t], rtol=1e-12, atol=0)
+    assert env.num_running()[i] == z["n_running"][t], i
+    if not z["done"][t]:   # (the info ratios of a step that ended an episode are gone after the reset)
+        info, st = env.info(), env.episode_stats()
+        assert info["total_path_length"][i] == z["total_path_length"][t], i
+        np.testing.assert_allclose(info["avrage_gsnr"][i], z["avrage_gsnr"][t], rtol=1e-15)
+        assert info["average_path_index"][i] == z["average_path_index"][t], i
+        assert info["path_index"][i] == z["path_index"][t] and info["physical_paths"][i] == z["physical_paths"][t], i
+        # NumPy-2 uint8 wrap of the reference's accumulator: reproduced on the host (as tests/test_gpu_phy.py)
+        assert (st["total_modulation_level"][i] % 256) / (st["channels_accepted"][i] + 1) == z["average_mod_level"][t], i
+
+
 # ---------------------------------------------------------------------------------------- instantiation names
 def kernel_name(family, W_or_S, stats, *, hbmq=False, defer=False, traffic=False, trace=False, ff=False, gn=False):
     """The name last_kernel() starts with, as orlg_kernel_name (csrc/orlg_variants.h) spells it: trailing `false` flags left out.

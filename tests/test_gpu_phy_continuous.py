@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, load_phy_tables, load_topology
-from gpu_support import PHY_CONTINUOUS_OUTS as OUTS, phy_env as make_env, same_bytes, snapshot
+from gpu_support import PHY_CONTINUOUS_OUTS as OUTS, check_state, check_trace, phy_env as make_env, same_bytes, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -14,69 +14,11 @@ CASES = ["cont_us14_s20_sapff", "cont_us14_s21_bmff", "cont_us14_s22_sapbm", "co
          "cont_us14_s24_bmfa", "cont_us14_s25_bmfa_groom", "cont_us14_s26_bmfa_rss_groom",
          "cont_us14_s27_sapbm_100_600", "cont_us14_s28_faff_rss_100_600",
          "cont_us14_s29_sapff_100_600_load20000", "cont_jpn12_s30_bmff"]
-COUNTERS = ("services_processed", "services_accepted", "episode_services_processed", "episode_services_accepted",
-            "bit_rate_requested", "bit_rate_provisioned")
-
-
-def channel_caps(topo, tables, tr, i):
-    """ch_cap of the trace: the table's level of every chosen channel on the chosen k-path (the tuple's field 3)."""
-    pairs, mod, _ = tables
-    rows = topo.pair_table_rows(pairs)
-    n = topo.num_nodes
-    caps = np.zeros(tr["channels"].shape[:1] + (12,), np.int16)
-    for t in range(caps.shape[0]):
-        a = int(tr["act_path"][t, i])
-        idp = a - 20 if a >= 20 else a
-        r = rows[int(tr["request"][t, i, 1]) * n + int(tr["request"][t, i, 2])]
-        for q in range(int(tr["n_channels"][t, i])):
-            caps[t, q] = mod[r, int(tr["channels"][t, i, q]), idp]
-    return caps
-
-
 def same_state(a, b, envs):
     """Two handles hold the same simulation (the saved state also carries never-written, uninitialised slots)."""
     same_bytes(snapshot(a, save_state=False), snapshot(b, save_state=False), "state")
     for i in envs:
         assert a.channel_state(i) == b.channel_state(i), i
-
-
-def check_trace(topo, tables, tr, i, z, lo, hi):
-    """steps lo..hi-1 of env i's per-step outputs against the reference's trace"""
-    s = slice(lo, hi)
-    assert np.array_equal(tr["request"][:, i, 1], z["src_id"][s]) and np.array_equal(tr["request"][:, i, 2], z["dst_id"][s]), i
-    assert np.array_equal(tr["request"][:, i, 3], z["bit_rate"][s]), i
-    assert np.array_equal(tr["request"][:, i, 0], z["service_id"][s]), i
-    np.testing.assert_allclose(tr["arrival"][:, i], z["arrival"][s], rtol=1e-12, atol=0)
-    np.testing.assert_allclose(tr["holding"][:, i], z["holding"][s], rtol=1e-12, atol=0)
-    assert np.array_equal(tr["act_path"][:, i], z["act_path"][s]), i
-    assert np.array_equal(tr["n_channels"][:, i], z["n_channels"][s]), i
-    assert np.array_equal(tr["channels"][:, i, :12], z["channels"][s]), i
-    for f, g in (("channels_used_f64", "ch_used"), ("channels_free_f64", "ch_free")):
-        bad = np.argwhere(tr[f][:, i, :12] != z[g][s])
-        assert bad.size == 0, (f, i, bad[:3], tr[f][:, i, :12][tuple(bad[:3].T)], z[g][s][tuple(bad[:3].T)])
-    assert np.array_equal(channel_caps(topo, tables, tr, i)[:, :12], z["ch_cap"][s]), i
-    assert np.array_equal(tr["accepted"][:, i], z["accepted"][s]) and np.array_equal(tr["done"][:, i], z["done"][s]), i
-    virtual = (tr["act_path"][:, i] >= 20) & (tr["accepted"][:, i] == 1)
-    assert np.array_equal(virtual, z["virtual"][s]), i
-    assert np.array_equal(tr["number_cuts_total"][:, i], z["number_cuts_total"][s]), i
-    assert np.array_equal(tr["rss_total_metric"][:, i], z["rss_total_metric"][s]), i
-
-
-def check_state(env, i, z, t):
-    """env i after step t (0-based) against the reference's record of that step"""
-    cnt = env.counters()
-    for name in COUNTERS:
-        assert cnt[name][i] == z[name][t], (name, i, t)
-    np.testing.assert_allclose(env.current_time()[i], z["current_time"][t], rtol=1e-12, atol=0)
-    assert env.num_running()[i] == z["n_running"][t], i
-    if not z["done"][t]:   # (the info ratios of a step that ended an episode are gone after the reset)
-        info, st = env.info(), env.episode_stats()
-        assert info["total_path_length"][i] == z["total_path_length"][t], i
-        np.testing.assert_allclose(info["avrage_gsnr"][i], z["avrage_gsnr"][t], rtol=1e-15)
-        assert info["average_path_index"][i] == z["average_path_index"][t], i
-        assert info["path_index"][i] == z["path_index"][t] and info["physical_paths"][i] == z["physical_paths"][t], i
-        # NumPy-2 uint8 wrap of the reference's accumulator: reproduced on the host (as tests/test_gpu_phy.py)
-        assert (st["total_modulation_level"][i] % 256) / (st["channels_accepted"][i] + 1) == z["average_mod_level"][t], i
 
 
 @pytest.mark.parametrize("case", CASES)
