@@ -525,6 +525,30 @@ int orlg_gn_admission_windows(orlg_env *env, int32_t rule, int16_t *slots, doubl
  * fit the LDS next to the tables.  Runs on the handle's stream, reads state and writes only the caller's buffers.  Buffers as
  * orlg_gn_admission_masks. */
 int orlg_gn_admission_slots(orlg_env *env, uint64_t *mask, double *gsnr_db, double *margin_db, int16_t *best_slot, double *best_margin_db);
+/* ---- max-margin assignment inside the step (this project's).  orlg_step_diag under a policy that takes, on a handle with
+ * a gn_gate (protecting or not), the admitted window with the largest worst margin w -- best_slot / best_margin_db of
+ * orlg_gn_admission_slots, evaluated inside the step for the pending request after the due services are released, bit for bit.
+ * `route`:
+ *     ORLG_POLICY_SAP_FF            the first path in order that has an admitted window, at its best_slot; later paths are not evaluated
+ *     ORLG_ROUTE_BEST_WINDOW        the path with the largest best_margin (strictly greater: ties go to the lowest index), at its best_slot
+ *     ORLG_POLICY_PATH_FF_EXTERNAL  actions [B] name the path (n_steps == 1), the proposal is its best_slot; a path out of range gives the
+ *                                   rejection (k, S)
+ * Some path in the route's scope has a free window but none is admitted: the proposal is the lowest free start (S - n included) of the
+ * first such path, which the step's check refuses -- a gate refusal, cause ORLG_CAUSE_GN, with act_path, act_slot, gn_gsnr_db and
+ * gn_neighbour_margin_db of that candidate.  No free window in scope: the rejection (k, S) with NaN, classified as under orlg_step_diag.
+ * The proposal goes through the step's own check like any other, so gn_gsnr_db (diag) has the step routine's bits, and an admitted
+ * proposal is accepted.  window_margin_db [n_steps][B] float64, or NULL: the w found for the proposed window, NaN for a fallback or a
+ * rejection.  diag may be NULL.  orlg_step_max_margin_protect is the same call with one more per-step output, gn_neighbour_margin_db
+ * [n_steps][B] as under orlg_step_gn_protect (NaN on a handle that does not protect), as that entry adds it to orlg_step_diag.
+ * ORLG_ERR_INVALID, before anything is launched: a null handle or one
+ * without a gn_gate, any other route, n_steps < 1, ORLG_POLICY_PATH_FF_EXTERNAL without actions, a release queue whose Q compacted ring
+ * offsets do not fit the LDS next to one environment.  n_steps steps are ONE launch of orlg_rmsa_mm_kernel<W, STATS[, CAUSE]>, the
+ * wave-per-environment kernel with the whole-spectrum policy section, at every batch size. */
+int orlg_step_max_margin(orlg_env *env, int32_t route, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
+                         const struct orlg_step_diag *diag, double *window_margin_db /* [n_steps][B] or NULL */);
+int orlg_step_max_margin_protect(orlg_env *env, int32_t route, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
+                                 const orlg_step_io *io, const struct orlg_step_diag *diag, double *window_margin_db,
+                                 double *gn_neighbour_margin_db);
 
 /* ---- the running services of every environment, and their GN-model audit (this project's).  Every gate entry above
  * asks whether a CANDIDATE should be lit; these two say how the lightpaths that are already running are doing.  The state they read

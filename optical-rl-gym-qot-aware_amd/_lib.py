@@ -46,6 +46,10 @@ WINDOW_POLICIES = {"sp_mu": (POLICIES["sp_ff"], RULE_MOST_USED), "sap_mu": (POLI
 RULE_FEWEST_CUTS = 102
 GN_RULE_MODES = {"check": 0, "next_path": 1}
 GN_PATH_WINDOW_RULES = {"first": 0, "first_full": 1, "last": 2, "best": 3, "exact": 4, "min_cut": RULE_FEWEST_CUTS}
+# include/orlg.h orlg_step_max_margin: the admitted window with the largest worst margin, found inside the step (a
+# handle with gn_gate= only).  The names, and the route each one is to that entry.  Tables of their own, as CUT_POLICIES
+MAX_MARGIN_POLICIES = ("sap_mm", "any_mm", "path_mm_external")
+MAX_MARGIN_ROUTES = {"sap_mm": POLICIES["sap_ff"], "any_mm": ROUTE_BEST_WINDOW, "path_mm_external": POLICIES["path_ff_external"]}
 
 
 def policy_ids(policy):
@@ -223,7 +227,9 @@ def _prototypes():
               "orlg_gn_admission_masks": (None, [vp, vp, vp, vp, vp, vp, vp]),
               "orlg_gn_admission_windows": (None, [vp, i32, vp, vp, vp, vp]),
               # ... over every start slot of every path: mask words, GSNR and margin rows, the window with the largest worst margin
-              "orlg_gn_admission_slots": (None, [vp, vp, vp, vp, vp, vp])})
+              "orlg_gn_admission_slots": (None, [vp, vp, vp, vp, vp, vp]),
+              "orlg_step_max_margin": (None, [vp, i32, i32, vp, i32, P(StepIO), P(StepDiag), vp]),
+              "orlg_step_max_margin_protect": (None, [vp, i32, i32, vp, i32, P(StepIO), P(StepDiag), vp, vp])})
     # QoT-aware only
     t.update({"orlg_phy_step": (None, [vp, i32, i32, vp, vp, i32, P(PhyStepIO)]), "orlg_phy_node_vectors": (None, [vp]),
               "orlg_phy_get_episode_stats": (None, [vp, vp]), "orlg_phy_channel_masks": (None, [vp, vp]),

@@ -148,10 +148,68 @@ class BatchedRMSAEnv(BatchedHandle):
         no running service shares a link, or a handle that does not protect); it leaves through ``orlg_step_gn_protect``.  A
         refusal by either check is the gate's refusal, cause ``"gn"``; ``sap_ff_gn`` goes on to the next path after either.
         ``gn_rule=``, the ``_gn`` mask kinds and :meth:`path_rule_windows` know the candidate's own check only: on a protecting
-        handle they raise ``ValueError``."""
+        handle they raise ``ValueError``.
+
+        Max-margin assignment inside the step (``orlg_step_max_margin``; not in the reference): the names of
+        ``_lib.MAX_MARGIN_POLICIES`` on a handle with ``gn_gate=``, protecting or not -- ``sap_mm`` (the first path in order that has
+        an admitted window, at the admitted window whose worst margin ``w = min(GSNR - threshold, neighbour margin)`` is the
+        largest, ties to the lowest start), ``any_mm`` (of all k paths the one whose such window has the largest ``w``, ties to the
+        lowest path) and ``path_mm_external`` (``actions`` [B] names the path).  Where a path in scope has a free window but none is
+        admitted, the lowest free start of the first such path is proposed and refused: a gate refusal, cause ``"gn"``.
+        ``"gn_window_margin_db"`` in ``outputs`` (these names only) -- the ``w`` of the proposed window, NaN for such a fallback or
+        a rejection.  ``n_steps`` steps are one launch; :meth:`max_margin_windows` is the matching query, bit for bit.  Without a
+        gate, or with ``gn_rule=``: ``ValueError``."""
+        if policy in _lib.MAX_MARGIN_POLICIES:
+            return self._run_max_margin(policy, n_steps, actions, auto_reset, outputs, out, cause_counts, gn_rule)
+        if "gn_window_margin_db" in _output_names(outputs, out):
+            raise ValueError(f"policy {policy!r}: gn_window_margin_db is an output of the names of _lib.MAX_MARGIN_POLICIES only")
         if gn_rule is not None:
             return self._run_rule_gn(policy, n_steps, actions, auto_reset, outputs, out, cause_counts, gn_rule)
         return self._run(policy, n_steps, actions, auto_reset, outputs, out, cause_counts)
+
+    def _run_max_margin(self, policy, n_steps, actions, auto_reset, outputs, out, cause_counts, gn_rule):
+        """``run(<a name of MAX_MARGIN_POLICIES>)``: the refusals before the library is called, then ``orlg_step_max_margin_protect``."""
+        if gn_rule is not None:
+            raise ValueError(f"policy {policy!r} with gn_rule=: a max-margin policy names its own window, no assignment rule runs with it")
+        if self.gn_gate is None:
+            raise ValueError(f"policy {policy!r} needs a handle with a GN-model admission check (gn_gate=): the margin is the check's")
+        if int(n_steps) < 1:
+            raise ValueError(f"n_steps {n_steps}: expected >= 1")
+        B = self.batch_size
+        route = _lib.MAX_MARGIN_ROUTES[policy]
+        ap = None
+        if policy == "path_mm_external":
+            if actions is None:
+                raise ValueError(f"policy {policy!r} needs an actions array")
+            if int(n_steps) != 1:
+                raise ValueError(f"policy {policy!r}: the actions name one path per environment, n_steps must be 1")
+            if not hasattr(actions, "data_ptr"):
+                actions = np.asarray(actions)
+                if actions.dtype.kind not in "iu":
+                    raise TypeError(f"actions: dtype {actions.dtype}, expected an integer type")
+                actions = np.ascontiguousarray(actions, dtype=np.int32)
+            _check_buffer("actions", actions, (B,), np.int32)
+            ap = _ptr(actions)
+        io = _lib.StepIO()
+        names = _output_names(outputs, out)
+        extra = {}
+        for name, dtype in (("gn_gsnr_db", "float64"), ("gn_neighbour_margin_db", "float64"), ("gn_window_margin_db", "float64"),
+                            ("block_cause", "uint8")):
+            if name in names:
+                names = [n for n in names if n != name]
+                extra.update(self._step_outputs([name], n_steps, out, {name: dtype}, {}))
+        if cause_counts is not None and cause_counts is not False:
+            if cause_counts is True:
+                cause_counts = np.zeros((B, _lib.NUM_CAUSES), np.int32)
+            else:
+                _check_buffer("out[cause_counts]", cause_counts, (B, _lib.NUM_CAUSES), np.int32)
+            extra["block_cause_counts"] = cause_counts
+        res = self._step_outputs(names, n_steps, out, _lib.STEP_IO_DTYPES, _STEP_IO_SHAPES, io)
+        d = _lib.StepDiag(_ptr(extra.get("block_cause")), _ptr(extra.get("block_cause_counts")), _ptr(extra.get("gn_gsnr_db")))
+        _lib.check(self.L.orlg_step_max_margin_protect(self.h, route, int(n_steps), ap, 1 if auto_reset else 0, C.byref(io), C.byref(d),
+                                                       _ptr(extra.get("gn_window_margin_db")), _ptr(extra.get("gn_neighbour_margin_db"))))
+        res.update(extra)
+        return res
 
     def _run_rule_gn(self, policy, n_steps, actions, auto_reset, outputs, out, cause_counts, gn_rule):
         """``run(..., gn_rule=)``: every refusal before the library is called."""

@@ -140,6 +140,47 @@ int launch_rmsa(orlg_env *e, const OrlgParams &p) {
     return ORLG_OK;
 }
 
+// ---- the gated step kernel under a max-margin policy (orlg_rmsa_mm_kernel, orlg_inst_gnmm.hip)
+// Its workgroup: the handle's wave regions and, behind them, up16(4 Q) bytes per wave for the compacted services of the path under
+// evaluation; where the handle's workgroup fills the LDS, as many waves as still fit.  Refused where one wave does not.
+struct MmLaunch {
+    double *window_margin = nullptr;   // device memory the kernel writes gn_window_margin_db to, nullptr = not asked for
+    int wpu = 0;
+    size_t lds = 0;
+};
+static int mm_geometry(const orlg_env *e, MmLaunch *m) {
+    const size_t per_wave = (size_t)e->p.l_wave_bytes + (((size_t)e->p.Q * 4 + 15) & ~(size_t)15);
+    int wpu = e->waves_per_block;
+    while (wpu > 1 && (size_t)e->p.l_shared_bytes + wpu * per_wave > ORLG_LDS_BYTES) --wpu;
+    m->wpu = wpu;
+    m->lds = (size_t)e->p.l_shared_bytes + wpu * per_wave;
+    if (m->lds > ORLG_LDS_BYTES)
+        return fail(ORLG_ERR_INVALID, "orlg_step_max_margin: tables, one environment and the ring of its %d compacted services (%zu B) exceed the 160 KiB LDS",
+                    e->p.Q, m->lds);
+    return ORLG_OK;
+}
+static int launch_rmsa_mm(orlg_env *e, const OrlgParams &p, const MmLaunch &m) {
+    const bool cause = (p.out_mask & ORLG_OUT_CAUSE_BIT) != 0;
+    const OrlgMmKey key = {p.stats_level, cause};
+    orlg_rmsa_mm_kernel_t k = orlg_pick_gn_mm(e->W, key);
+    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
+    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), m.lds)) return rc;
+    int *resident = &e->mm_resident[p.stats_level][cause ? 1 : 0];
+    if (int rc = orlg_handle_resident(e, reinterpret_cast<const void *>(k), ORLG_WAVE * m.wpu, m.lds, resident)) return rc;
+    int nblocks = (p.B + m.wpu - 1) / m.wpu;
+    if (nblocks > *resident) nblocks = *resident;
+    OrlgParams q = p;
+    q.llog = nullptr;
+    q.ticket_base = e->ticket_base;
+    q.ticket_stride = p.n_steps <= 16 ? 1u : 0u;
+    if (!q.ticket_stride) e->ticket_base += (uint32_t)p.B;
+    const OrlgMmArgs a = {m.window_margin, e->gn_protect ? 1 : 0, 0};
+    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * m.wpu), m.lds, e->stream, q, a);
+    HIP_TRY(hipGetLastError());
+    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * m.wpu, m.lds);
+    return ORLG_OK;
+}
+
 extern "C" {
 /* launch geometry of the step kernel: out[0] waves (envs) per workgroup, out[1] LDS bytes per workgroup,
  * out[2] workgroups resident per CU according to hipOccupancyMaxActiveBlocksPerMultiprocessor, out[3] W */
@@ -159,12 +200,13 @@ int orlg_launch_info(orlg_env *e, int32_t *out) {
 
 // ---------------------------------------------------------------------------------------- the step
 // the outputs of a step beyond orlg_step_io (nullptr = not asked for): gn_gsnr_db, block_cause and cause_counts of orlg_step_diag,
-// gn_neighbour_margin_db of orlg_step_gn_protect
+// gn_neighbour_margin_db of orlg_step_gn_protect, gn_window_margin_db of orlg_step_max_margin
 struct StepExtras {
     double *gsnr = nullptr;
     uint8_t *cause = nullptr;
     int32_t *counts = nullptr;
     double *margin = nullptr;
+    double *wmargin = nullptr;
 };
 static StepExtras step_extras(const struct orlg_step_diag *diag, double *margin = nullptr) {
     StepExtras x;
@@ -193,9 +235,10 @@ static int place_extra(orlg_env *e, ExtraOut *o) {
     return ORLG_OK;
 }
 
-// one launch of n_steps steps of a call that orlg_step_call has resolved: the live part of every step entry
+// one launch of n_steps steps of a call that orlg_step_call has resolved: the live part of every step entry.  mm: the call is
+// orlg_step_max_margin's (orlg_step_mm_call resolved it, mm_geometry found its workgroup) and launches orlg_rmsa_mm_kernel
 static int rmsa_step(orlg_env *e, const OrlgStepCall &call, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
-                     const orlg_step_io *io, const StepExtras &x) {
+                     const orlg_step_io *io, const StepExtras &x, MmLaunch *mm = nullptr) {
     const int32_t policy = call.policy;
     const bool ext = policy == ORLG_POLICY_EXTERNAL || policy == ORLG_POLICY_DEEPRMSA_EXTERNAL || policy == ORLG_POLICY_PATH_FF_EXTERNAL;
     if (ext && (!actions || n_steps != 1)) return fail(ORLG_ERR_INVALID, "external actions need an action array and n_steps == 1");
@@ -224,9 +267,9 @@ static int rmsa_step(orlg_env *e, const OrlgStepCall &call, int32_t n_steps, con
         {io ? io->avg_link_compactness : nullptr, 8},   {io ? io->avg_link_utilization : nullptr, 8}};
     int rc = orlg_handle_place(e, slots, ORLG_NUM_OUTS, cnt, p.outs, &p.out_mask);
     if (rc) return rc;
-    ExtraOut extra[4] = {{x.gsnr, cnt * sizeof(double), X_GSNR, true}, {x.cause, cnt, X_CAUSE, false},
+    ExtraOut extra[5] = {{x.gsnr, cnt * sizeof(double), X_GSNR, true}, {x.cause, cnt, X_CAUSE, false},
                          {x.counts, (size_t)p.B * ORLG_NUM_CAUSES * sizeof(int32_t), X_CAUSE_COUNTS, false},
-                         {x.margin, cnt * sizeof(double), X_MARGIN, false}};
+                         {x.margin, cnt * sizeof(double), X_MARGIN, false}, {x.wmargin, cnt * sizeof(double), X_WINDOW_MARGIN, false}};
     for (ExtraOut &o : extra)
         if ((rc = place_extra(e, &o))) return rc;
     p.o_gsnr = static_cast<double *>(extra[0].dev);
@@ -241,7 +284,8 @@ static int rmsa_step(orlg_env *e, const OrlgStepCall &call, int32_t n_steps, con
     if (x.margin && !(p.gn && e->gn_protect)) HIP_TRY(hipMemsetAsync(p.o_margin, 0xff, extra[3].bytes, e->stream));
     p.assign = call.assign;
     if (call.assign != ORLG_ASSIGN_FIRST) p.out_mask |= ORLG_OUT_ASSIGN_BIT;   // the launch runs an ASSIGN instantiation
-    rc = launch_rmsa(e, p);
+    if (mm) mm->window_margin = static_cast<double *>(extra[4].dev);
+    rc = mm ? launch_rmsa_mm(e, p, *mm) : launch_rmsa(e, p);
     if (rc) return rc;
     if (e->trace.length > 0) e->trace.position += n_steps;
     bool any = false;
@@ -296,6 +340,22 @@ int orlg_step_window(orlg_env *e, int32_t route, int32_t rule, int32_t n_steps, 
 int orlg_step_rule_gn(orlg_env *e, int32_t route, int32_t rule, int32_t gn_mode, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
                       const orlg_step_io *io, const struct orlg_step_diag *diag) {
     return step_entry(e, ORLG_ENTRY_RULE_GN, route, rule, gn_mode, n_steps, actions, auto_reset, io, step_extras(diag));
+}
+// a max-margin policy behind the gate: resolved by orlg_step_mm_call, one launch of orlg_rmsa_mm_kernel
+int orlg_step_max_margin_protect(orlg_env *e, int32_t route, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
+                                 const struct orlg_step_diag *diag, double *window_margin_db, double *gn_neighbour_margin_db) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    OrlgStepCall call;
+    if (int rc = orlg_step_mm_call({route, n_steps, e->p.gn != nullptr, actions != nullptr}, &call)) return rc;
+    MmLaunch mm;
+    if (int rc = mm_geometry(e, &mm)) return rc;
+    StepExtras x = step_extras(diag, gn_neighbour_margin_db);
+    x.wmargin = window_margin_db;
+    return rmsa_step(e, call, n_steps, actions, auto_reset, io, x, &mm);
+}
+int orlg_step_max_margin(orlg_env *e, int32_t route, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
+                         const struct orlg_step_diag *diag, double *window_margin_db) {
+    return orlg_step_max_margin_protect(e, route, n_steps, actions, auto_reset, io, diag, window_margin_db, nullptr);
 }
 }  // extern "C"
 

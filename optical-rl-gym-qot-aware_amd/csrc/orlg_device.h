@@ -177,6 +177,13 @@ struct OrlgParams {
     // for.  (At the struct's end, as the fields above)
     double *o_margin;
 };
+// what a launch of orlg_rmsa_mm_kernel (orlg_step_max_margin, orlg_gn_max_margin.h) gets beside OrlgParams -- a kernel argument of its
+// own: OrlgParams, and with it the kernarg segment of every other kernel, stays what it is
+struct OrlgMmArgs {
+    double *o_window_margin;   // [n_steps][B] the w of the proposed window, NaN for a fallback or a rejection; nullptr = not asked for
+    int32_t protect;           // the handle protects its running lightpaths (wave-uniform)
+    int32_t pad;
+};
 // out_mask of a launch that asks for a cause output: not one of outs[], but a per-step output like them -- what looks at
 // out_mask to choose a kernel (the deferred link statistics, the group kernel's HBMQ kind and lean body) keeps such a launch on
 // the plain instantiations, the only ones that exist with the classifier

@@ -39,6 +39,7 @@
 #include "orlg_assign.h"       // wave_assign: the assignment rules of the ASSIGN instantiations
 #include "orlg_cut.h"          // wave_cut_assign: the fewest-cuts window of the CUT instantiations
 #include "orlg_usage.h"        // wave_window_assign: the rule MOST_USED and the route BEST_WINDOW of the USAGE instantiations
+#include "orlg_gn_max_margin.h"   // wave_max_margin: the whole-spectrum policy section of the MM instantiations
 #include "orlg_sections.h"
 
 // ---------------------------------------------------------------------------------------- the step kernel
@@ -71,6 +72,12 @@
 // passes its own check is provisioned only if rmsa_gn_neighbour_margin (orlg_rmsa_gn_protect.h) is not negative: no running service on
 // a shared link falls below its threshold.  A refusal by it is the gate's refusal, sap_ff_gn's retry included; `margin` is what the
 // retry reports with the first candidate when the paths end.  These instantiations live in orlg_inst_gnprotect.hip.
+// MM (with GN, without ASSIGN and PROTECT): the launch is orlg_step_max_margin's -- wave_max_margin (orlg_gn_max_margin.h)
+// stands where the first-fit policy section stands: the admission check over every free start of the paths in scope, then the window
+// with the largest worst margin, or the fallback the check refuses.  The wave's Q compacted ranks lie in LDS BEHIND the workgroup's wave
+// regions, as USAGE's prefix sums do.  Protection is a runtime argument here (OrlgMmArgs::protect), and the second check of SEC(3) runs
+// under it.  The kernel has a name of its own, orlg_rmsa_mm_kernel (the section's registers are the query's, not the step's), and its
+// instantiations a unit of their own, orlg_inst_gnmm.hip.
 template <bool GN>
 struct SapRetry {
     int from = 0, path = 0, slot = 0;
@@ -83,8 +90,8 @@ struct SapRetry<false> {
 };
 
 template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false, bool CUT = false,
-          bool USAGE = false, bool PROTECT = false>
-DEV void rmsa_body(const OrlgParams &p) {
+          bool USAGE = false, bool PROTECT = false, bool MM = false>
+DEV void rmsa_body(const OrlgParams &p, [[maybe_unused]] const OrlgMmArgs *mm = nullptr) {
     extern __shared__ __align__(16) unsigned char smem[];
 #ifdef ORLG_SHAPE_ASSUME
     ORLG_SHAPE_ASSUME  // experiment (tools/shape_experiment.py): shape and layout fields as compile-time constants
@@ -250,7 +257,15 @@ DEV void rmsa_body(const OrlgParams &p) {
 
             int a_path = K, a_slot = S;  // rejection (rmsa_env.py:871,913)
             const int policy = p.policy;
-            if constexpr (ASSIGN) {
+            [[maybe_unused]] double mm_w = __longlong_as_double(0x7ff8000000000000ll);   // MM: the w of the proposed window
+            if constexpr (MM) {
+                const int given = policy == ORLG_POLICY_PATH_EXT ? uni(kernarg_params()->actions[env]) : 0;
+                uint32_t *cidx = reinterpret_cast<uint32_t *>(smem + p.l_shared_bytes + (size_t)(blockDim.x >> 6) * p.l_wave_bytes +
+                                                              (size_t)wib * ((Q * 4 + 15) & ~15));
+                const int got = wave_max_margin<W>(wv, tb, ORLG_GPTR(const double, p.gn), E, Q, q_head, q_n, cidx, base, K, S, req_br, policy, given,
+                                                   mm->protect, mm_w);
+                if (got >= 0) { a_path = got >> 10; a_slot = got & 1023; }
+            } else if constexpr (ASSIGN) {
                 KernargParams kq = kernarg_params();
                 const int given = policy == ORLG_POLICY_PATH_EXT ? uni(kq->actions[env]) : 0;
                 // GN (orlg_step_rule_gn): the rule's window goes through the check of SEC(3).  Mode next-path arrives as
@@ -364,7 +379,7 @@ DEV void rmsa_body(const OrlgParams &p) {
                 const int n = __builtin_amdgcn_readlane(my_n, a_path);
                 // the device policies only propose windows they found free; agent actions are checked (is_path_free)
                 bool window_ok = true;
-                if (!FF && !ASSIGN && (policy == ORLG_POLICY_EXT || policy == ORLG_POLICY_PATH_EXT || policy == ORLG_POLICY_DEEP_EXT)) {
+                if (!FF && !ASSIGN && !MM && (policy == ORLG_POLICY_EXT || policy == ORLG_POLICY_PATH_EXT || policy == ORLG_POLICY_DEEP_EXT)) {
                     u64 x[W];
 #pragma unroll
                     for (int w = 0; w < W; ++w) x[w] = readlane64(acc, a_path * LS + w);
@@ -384,6 +399,12 @@ DEV void rmsa_body(const OrlgParams &p) {
                         // such service: NaN, which refuses nothing
                         if constexpr (PROTECT) {
                             if (window_ok) {
+                                gn_margin = rmsa_gn_neighbour_margin(wv, tb, gn, E, Q, q_head, q_n, cand, a_slot, n);
+                                window_ok = !(gn_margin < 0.0);
+                            }
+                        }
+                        if constexpr (MM) {   // (the same check under the launch's runtime flag)
+                            if (window_ok && mm->protect) {
                                 gn_margin = rmsa_gn_neighbour_margin(wv, tb, gn, E, Q, q_head, q_n, cand, a_slot, n);
                                 window_ok = !(gn_margin < 0.0);
                             }
@@ -498,6 +519,11 @@ DEV void rmsa_body(const OrlgParams &p) {
             if constexpr (PROTECT) {
                 KernargParams kq = kernarg_params();
                 if (lane == 0 && kq->o_margin) ORLG_GPTR(double, kq->o_margin)[(size_t)t * p.B + env] = gn_margin;
+            }
+            if constexpr (MM) {   // (o_margin: a handle that does not protect ran no second check -- the host has filled the output)
+                KernargParams kq = kernarg_params();
+                if (lane == 0 && mm->protect && kq->o_margin) ORLG_GPTR(double, kq->o_margin)[(size_t)t * p.B + env] = gn_margin;
+                if (lane == 0 && mm->o_window_margin) ORLG_GPTR(double, mm->o_window_margin)[(size_t)t * p.B + env] = mm_w;
             }
             if constexpr (CAUSE) {
                 int cause = ORLG_CAUSE_ACCEPTED;
@@ -705,6 +731,12 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_r
     static_assert(!USAGE || (ASSIGN && !CUT), "most-used windows and the best-window route are assignment rules of their own");
     static_assert(!PROTECT || (GN && !ASSIGN), "protection is a property of the gate; no assignment rule runs behind it");
     rmsa_body<W, STATS, true, false, DEFER, GN, CAUSE, ASSIGN, CUT, USAGE, PROTECT>(p);
+}
+// the gated step kernel under a max-margin policy (orlg_step_max_margin): the launch bounds of orlg_gn_slots_kernel -- eight waves per
+// workgroup, two per SIMD -- for the registers of the whole-spectrum section
+template <int W, int STATS, bool CAUSE = false>
+__global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK) void orlg_rmsa_mm_kernel(const OrlgParams p, const OrlgMmArgs m) {
+    rmsa_body<W, STATS, true, false, false, true, CAUSE, false, false, false, false, true>(p, &m);
 }
 template <int W, int STATS, bool DEFER = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel_ff(const OrlgParams p) {

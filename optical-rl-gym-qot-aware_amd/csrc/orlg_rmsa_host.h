@@ -28,9 +28,10 @@ struct orlg_env : OrlgHandle {
     double *gn_table = nullptr;     // the gate's table on the device (allocated with the first gate; OrlgParams::gn = it or nullptr)
     bool gn_protect = false;        // the gate also protects the running lightpaths (orlg_set_gn_protect; configuration, not state)
     double *audit_table = nullptr;  // the table of a gate given with orlg_gn_audit (allocated with the first such call; never OrlgParams::gn)
+    int mm_resident[3][2] = {};     // workgroups of orlg_rmsa_mm_kernel the device keeps resident, by statistics level and CAUSE (0 = not asked yet)
 };
-enum { X_ACTIONS, X_GSNR, X_CAUSE, X_CAUSE_COUNTS, X_MARGIN };   // OrlgHandle::extra: external actions from / the gn_gsnr_db, block_cause, cause_counts and gn_neighbour_margin_db outputs for host memory
-static_assert(X_MARGIN < ORLG_EXTRA_SLOTS, "OrlgHandle::extra");
+enum { X_ACTIONS, X_GSNR, X_CAUSE, X_CAUSE_COUNTS, X_MARGIN, X_WINDOW_MARGIN };   // OrlgHandle::extra: external actions from / the gn_gsnr_db, block_cause, cause_counts, gn_neighbour_margin_db and gn_window_margin_db outputs for host memory
+static_assert(X_WINDOW_MARGIN < ORLG_EXTRA_SLOTS, "OrlgHandle::extra");
 
 #define SYNC_CHECK(e) do { int rc_ = orlg_handle_sync_check(e); if (rc_) return rc_; } while (0)
 

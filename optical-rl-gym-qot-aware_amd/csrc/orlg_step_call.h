@@ -36,6 +36,21 @@ static inline int32_t orlg_device_assign(int32_t rule) {
     return rule == ORLG_RULE_MOST_USED ? (int32_t)ORLG_ASSIGN_MOST_USED : rule == ORLG_RULE_FEWEST_CUTS ? (int32_t)ORLG_ASSIGN_MIN_CUT : rule;
 }
 
+// orlg_step_max_margin: a call of its own beside the entries above -- no OrlgStepEntry, and the policies they accept stay
+// what they were.  route: the caller's; actions: the caller gave an action array.  The launch's own refusal, a ring of compacted
+// services that does not fit the LDS, needs the handle's layout and is orlg_api_step.hip's.
+struct OrlgStepMmAsk { int32_t route, n_steps; bool gated, actions; };
+static inline int orlg_step_mm_call(const OrlgStepMmAsk &a, OrlgStepCall *call) {
+    if (!a.gated) return orlg_fail(ORLG_ERR_INVALID, "orlg_step_max_margin: the handle has no gn_gate (the margin is the admission check's)");
+    if (a.route != ORLG_POLICY_SAP_FF && a.route != ORLG_ROUTE_BEST_WINDOW && a.route != ORLG_POLICY_PATH_FF_EXTERNAL)
+        return orlg_fail(ORLG_ERR_INVALID, "orlg_step_max_margin needs a route (ORLG_POLICY_SAP_FF, ORLG_ROUTE_BEST_WINDOW or ORLG_POLICY_PATH_FF_EXTERNAL): got %d", a.route);
+    if (a.n_steps < 1) return orlg_fail(ORLG_ERR_INVALID, "n_steps must be >= 1");
+    if (a.route == ORLG_POLICY_PATH_FF_EXTERNAL && !a.actions)
+        return orlg_fail(ORLG_ERR_INVALID, "orlg_step_max_margin: the route ORLG_POLICY_PATH_FF_EXTERNAL needs an action array");
+    *call = {orlg_device_policy(a.route), ORLG_ASSIGN_FIRST};
+    return ORLG_OK;
+}
+
 static inline int orlg_step_call(const OrlgStepAsk &a, OrlgStepCall *call) {
     const int32_t route = a.policy, rule = a.rule;
     const char *const steps = "n_steps must be >= 1";

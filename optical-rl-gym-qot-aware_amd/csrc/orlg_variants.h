@@ -267,6 +267,24 @@ typedef void (*orlg_gn_slots_kernel_t)(const OrlgParams, uint64_t *, double *, d
 #define ORLG_DECL_GN_SLOTS_W(n, ...) orlg_gn_slots_kernel_t orlg_gn_slots_kernel_W##n() __attribute__((weak));
 ORLG_FOR_EACH_W(ORLG_DECL_GN_SLOTS_W, )
 #undef ORLG_DECL_GN_SLOTS_W
+// orlg_rmsa_mm_kernel (orlg_kernels.hip): the gated step kernel under a max-margin policy (orlg_step_max_margin) --
+// template <int W, int STATS, bool CAUSE = false>, a kernel name, a key, a key list, a unit (orlg_inst_gnmm.hip, one object per W) and a
+// declaration list of its own: the lists above stay what they are.  X(STATS[, CAUSE]): per statistics level, without and with the
+// classifier; protection is a runtime argument of the launch (OrlgMmArgs), no key
+struct OrlgMmKey { int STATS; bool CAUSE = false; };
+inline bool operator==(const OrlgMmKey &a, const OrlgMmKey &b) { return a.STATS == b.STATS && a.CAUSE == b.CAUSE; }
+#define ORLG_WAVE_GN_MM_KEYS(X) X(1) X(2) X(0) X(1, true) X(2, true) X(0, true)
+#define ORLG_MM_KEY_ENTRY(...) OrlgMmKey{__VA_ARGS__},
+inline constexpr OrlgMmKey ORLG_WAVE_GN_MM_KEY_LIST[] = {ORLG_WAVE_GN_MM_KEYS(ORLG_MM_KEY_ENTRY)};
+inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgMmKey &k) {
+    const OrlgArg args[] = {{k.STATS, 'i'}, {k.CAUSE, 'd'}};
+    orlg_format_kernel(buf, cap, "orlg_rmsa_mm_kernel", W, args, 2);
+}
+struct OrlgMmArgs;
+typedef void (*orlg_rmsa_mm_kernel_t)(const OrlgParams, const OrlgMmArgs);
+#define ORLG_DECL_GN_MM_W(n, ...) orlg_rmsa_mm_kernel_t orlg_gnmm_kernel_W##n(OrlgMmKey) __attribute__((weak));
+ORLG_FOR_EACH_W(ORLG_DECL_GN_MM_W, )
+#undef ORLG_DECL_GN_MM_W
 
 // the lookup `lookup`<W> called with the arguments after it, as a function body: null when the library holds no such W
 #define ORLG_PICK_CASE(n, lookup, ...) case n: return lookup##n ? lookup##n(__VA_ARGS__) : nullptr;
@@ -293,3 +311,4 @@ static orlg_gn_path_windows_kernel_t orlg_pick_gn_path_windows(int W) { ORLG_PIC
 static orlg_gn_admission_masks_kernel_t orlg_pick_gn_admission_masks(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_admission_masks_kernel_W, ) }
 static orlg_gn_admission_windows_kernel_t orlg_pick_gn_admission_windows(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_admission_windows_kernel_W, ) }
 static orlg_gn_slots_kernel_t orlg_pick_gn_slots(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_slots_kernel_W, ) }
+static orlg_rmsa_mm_kernel_t orlg_pick_gn_mm(int W, const OrlgMmKey &key) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gnmm_kernel_W, key) }
