@@ -115,6 +115,15 @@
     // without return -- 336 bytes of LDS per environment decide how many waves a CU keeps resident.  Every access
     // is an atomic, so that the updates of one address arrive at L2 in program order.
     int32_t *ghist = p.hist + (size_t)env * 4 * NBR;
+    // DEFER: the same addresses formed where they are used, from a wave-uniform base (the quad's first environment: scalar
+    // registers) and the row's 32-bit byte offset -- as per-lane 64-bit pointers they are loop invariants the step loop has no
+    // registers for, and a reload from scratch is a load: the wave waits for everything it has in flight
+    [[maybe_unused]] char *hist_q = reinterpret_cast<char *>(p.hist + (size_t)env0 * 4 * NBR);
+    [[maybe_unused]] const uint32_t hist_row = (uint32_t)((env - env0) * 4 * NBR) * 4u;
+    // (histogram `which`, entry i; the other instantiations keep the statements they had, so that they stay the code they were)
+    [[maybe_unused]] auto hist_at = [&](int which, int i) -> int32_t * {
+        return reinterpret_cast<int32_t *>(hist_q + (hist_row + (uint32_t)(which * NBR + i) * 4u));
+    };
     if (NET) quad_copy(wbase + p.g_lint, p.lint + (size_t)env0 * p.lint_stride, nact * p.lint_stride * 4, lane);
     if (nact < ORLG_GE) {   // the batch's last quad only
         wave_sync();
@@ -446,12 +455,20 @@
         // ---- _provision_path (rmsa_env.py:462-513)
         // (with network statistics the statistics pass below clears the window as it reads the links' words)
         if (!NET) group_apply_window<W>(lane, occ, rec->link, accepted ? hops : 0, a_slot, n, false);
+        // DEFER: the step's one wait for vector memory, where it is free -- the ring prefetch and the previous step's last log stores
+        // and histogram atomics were issued at least a policy pass ago, and from here on the step issues stores and atomics
+        // without return only, which nothing in it waits for
+        if constexpr (DEFER) vm_drain();
         if (accepted) {
             sum_sh += n * hops;
             n_running += 1;
             sum_bitrate_running += br_val;
             cnt += (cidx == 1 || cidx == 3) ? 1 : ((cidx == 5 || cidx == 7) ? br_val : 0);
-            if (gl == 0) { atomicAdd(ghist + NBR + req_br, 1); atomicAdd(ghist + 3 * NBR + req_br, 1); }
+            if constexpr (DEFER) {
+                if (gl == 0) { atomicAdd(hist_at(1, req_br), 1); atomicAdd(hist_at(3, req_br), 1); }
+            } else {
+                if (gl == 0) { atomicAdd(ghist + NBR + req_br, 1); atomicAdd(ghist + 3 * NBR + req_br, 1); }
+            }
         }
         SEC(4);  // statistics at provision
         if (NET)
@@ -469,6 +486,7 @@
             if (ballot(lg_cnt >= ORLG_GLOG_CAP) != 0ull) {   // a row's log is full: every row works its log off
                 SEC(15);  // graph replay
                 group_graph_replay(lane, lg, lg_cnt, p.scal + env, E);
+                vm_drain();   // a cold block ends drained: the hot path it rejoins then needs no wait for this block's loads
             }
         }
         SEC(5);  // queue insert
@@ -581,6 +599,7 @@
                                                                  p.ring_ht + (size_t)env_s * ORLG_RING, p.ring_req + (size_t)env_s * ORLG_RING,
                                                                  &idx_s, p.tr_len, env_s);
                     ring_visible();
+                    if constexpr (DEFER) vm_drain();   // (a cold block ends drained)
                     if ((lane & 48) == src_lane) { ring_cnt = got; ring_pos = 0; mt_idx = idx_s; dry = false; }
                     continue;
                 }
@@ -616,6 +635,7 @@
                 o_mt[lane] = m0; o_mt[lane + 64] = m1;
                 if (lane < 156 - 128) o_mt[lane + 128] = m2;
                 ring_visible();
+                if constexpr (DEFER) vm_drain();   // (a cold block ends drained)
                 if ((lane & 48) == src_lane) { ring_cnt = got; ring_pos = 0; mt_idx = idx_s; dry = false; }
             }
             SEC(7);
@@ -624,6 +644,7 @@
             if (!pf_ok) {
                 const size_t ro = (size_t)env * ORLG_RING + ring_pos;
                 r_iat = p.ring_iat[ro]; r_ht = p.ring_ht[ro]; rq = p.ring_req[ro];
+                if constexpr (DEFER) vm_drain();   // (a cold block ends drained; these three are read at once anyway)
             }
             if (act) {
                 const double at = TRACE ? r_iat : current_time + r_iat;   // (a trace's ring holds the arrival time itself)
@@ -637,7 +658,11 @@
                 req_arrival = at; req_holding = r_ht;
                 const int bv = tb.bit_rates[req_br];
                 cnt += (cidx == 0 || cidx == 2) ? 1 : ((cidx == 4 || cidx == 6) ? bv : 0);
-                if (gl == 0) { atomicAdd(ghist + req_br, 1); atomicAdd(ghist + 2 * NBR + req_br, 1); }
+                if constexpr (DEFER) {
+                    if (gl == 0) { atomicAdd(hist_at(0, req_br), 1); atomicAdd(hist_at(2, req_br), 1); }
+                } else {
+                    if (gl == 0) { atomicAdd(ghist + req_br, 1); atomicAdd(ghist + 2 * NBR + req_br, 1); }
+                }
             }
 
             // ---- release every service with release time <= now, in time order (rmsa_env.py:689-695): the ring's head
@@ -734,6 +759,7 @@
                 if (DEFER && ballot(need_replay) != 0ull) {   // (a link's log never grows past ORLG_LLOG_FLUSH + 1 entries)
                     SEC(14);  // link replay
                     group_link_replay(lane, lst, lint, tb, S, E, llog);
+                    vm_drain();   // (a cold block ends drained: without it the release loop's head waits on every pass)
                     need_replay = false;
                     SEC(11);
                 }
@@ -744,6 +770,7 @@
         if (DEFER && ballot(need_replay) != 0ull) {   // a link's log is filling up: every row works its logs off
             SEC(14);  // link replay
             group_link_replay(lane, lst, lint, tb, S, E, llog);
+            vm_drain();   // (a cold block ends drained)
             need_replay = false;
         }
         // ============================================================== done / episode reset
@@ -755,7 +782,11 @@
             if (ballot(done && p.auto_reset)) {
                 // reset(only_episode_counters=True) with a pending service (rmsa_env.py:343-389)
                 if (done && p.auto_reset) {
-                    for (int i = gl; i < NBR; i += ORLG_GL) { atomicExch(ghist + 2 * NBR + i, 0); atomicExch(ghist + 3 * NBR + i, 0); }
+                    if constexpr (DEFER) {
+                        for (int i = gl; i < NBR; i += ORLG_GL) { atomicExch(hist_at(2, i), 0); atomicExch(hist_at(3, i), 0); }
+                    } else {
+                        for (int i = gl; i < NBR; i += ORLG_GL) { atomicExch(ghist + 2 * NBR + i, 0); atomicExch(ghist + 3 * NBR + i, 0); }
+                    }
                     eproc = 1;
                     episodes_done += 1;
                     const int bv = tb.bit_rates[req_br];
@@ -764,7 +795,11 @@
                     if (cidx == 6) cnt = bv;
                 }
                 wave_sync();
-                if (done && p.auto_reset && gl == 0) atomicExch(ghist + 2 * NBR + req_br, 1);
+                if constexpr (DEFER) {
+                    if (done && p.auto_reset && gl == 0) atomicExch(hist_at(2, req_br), 1);
+                } else {
+                    if (done && p.auto_reset && gl == 0) atomicExch(ghist + 2 * NBR + req_br, 1);
+                }
                 wave_sync();
             }
         }

@@ -255,5 +255,8 @@ DEV void link_stats_update(Wave &wv, const Tab &tb, int S, int E, const uint8_t 
         if (graph_now && lane == 0) wv.wsc->g_lu = now;
         wave_sync();
     }
-    if (DEFER && ballot(need_replay) != 0ull) link_replay<64>(lane, wv.lst, wv.lint, tb, S, E, llog);
+    if (DEFER && ballot(need_replay) != 0ull) {
+        link_replay<64>(lane, wv.lst, wv.lint, tb, S, E, llog);
+        vm_drain();   // the cold block ends drained: the step it rejoins then does not wait for its own log stores
+    }
 }

@@ -32,6 +32,11 @@ DEV void wave_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+// An explicit `s_waitcnt vmcnt(0)` (gfx9 encoding: expcnt and lgkmcnt left at their maxima): the wave waits here for its
+// outstanding loads, stores and atomics without return -- one in-order counter.  It orders nothing and nothing depends on it;
+// it is a statement about WHERE the wave waits.  The compiler's wait-count pass reads the builtin (inline assembly it does not
+// read) and then knows the counter is zero on the paths that pass here, so it places no wait of its own for them further on.
+DEV void vm_drain() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 DEV int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 DEV u64 readlane64(u64 v, int l) {
     uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
