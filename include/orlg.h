@@ -584,6 +584,51 @@ typedef struct orlg_gn_audit_summary {
 int orlg_gn_audit(orlg_env *env, const orlg_rmsa_gn_gate *gate, orlg_gn_audit_summary *summary, double *gsnr_db, double *margin_db,
                   double *osnr_ase_db, double *snr_nli_db);
 
+/* ---- adaptive modulation behind the gate (this project's): the spectral efficiency a service runs at chosen from the
+ * GSNR, inside the step.  Every entry above runs a service at its path's reach-table spectral efficiency and compares the GSNR with
+ * that one threshold.  A gate in mode ORLG_GN_MODULATION_ADAPTIVE reads thresholds_db as the reference's modulation_level table reads
+ * its GSNR: M = num_thresholds levels, level m in 1..M = spectral efficiency m, n_m = get_number_slots at m slots.
+ * CANDIDATE (p, m) of the pending request: the reference's first fit of n_m on path p (the smallest s in [0, S - n_m) free on every
+ * link); its CHECK is orlg_set_gn_gate's for a service on [s, s + n_m) -- bandwidth n_m D, centre f0 + (s + n_m / 2) D, power density
+ * n_m D -- admitted iff GSNR_dB >= thresholds_db[m - 1].  n_m does not fall with m: a level without a window ends the path.
+ * Every running service interferes with the level it was provisioned at (n_i and phi_mod of that level); the level is kept with the
+ * service in the release ring (3 bits of the path field, so an adaptive handle has fewer than 2048 path records), 0 = the path's
+ * own: a state without adaptive services is a valid adaptive state, and the blob of orlg_save_state keeps its size.
+ * orlg_set_gn_modulation: needs a gate.  ORLG_ERR_INVALID: no gate, an unknown mode, ADAPTIVE with num_thresholds > 6 (the modulation
+ * factors of the GN model end there), with 2048 or more path records, or on a handle that protects its running lightpaths; PATH on a
+ * handle whose state holds a service with a level.  On an adaptive handle orlg_set_gn_gate(NULL) and orlg_set_gn_protect(1) are
+ * refused, as are orlg_step_rule_gn, orlg_step_max_margin*, orlg_gn_action_masks, orlg_gn_path_windows, orlg_gn_admission_*, and
+ * block_cause / cause_counts (ORLG_ERR_INVALID); orlg_step, orlg_step_gn and orlg_step_diag without those two outputs propose and
+ * check at the path's own spectral efficiency as before, and only their decode of the running services knows the stored level.
+ * orlg_gn_audit audits every service at the threshold of ITS level; orlg_get_running_services_se adds se [B][Q] int16, the spectral
+ * efficiency every service runs at (-1 past count), to orlg_get_running_services.  orlg_load_state into a handle that is not adaptive
+ * refuses a snapshot in which a descriptor names no path record of the handle -- what a stored level looks like there
+ * (ORLG_ERR_INVALID, nothing copied).
+ * orlg_step_modulation, `policy`:
+ *     ORLG_AM_SP_FF          path 0 only, levels M down to 1: the first admitted candidate is provisioned
+ *     ORLG_AM_SAP_FF         the paths in order, each with levels M down to 1: the first admitted candidate of the first path that
+ *                            has one is provisioned
+ *     ORLG_AM_PATH_EXTERNAL  actions [B] name the path (n_steps == 1), the levels as above
+ *     ORLG_AM_EXTERNAL       actions [B][3] = (path, slot, se) (n_steps == 1): orlg_step's ORLG_POLICY_EXTERNAL with n = n_se; an se
+ *                            outside 1..M is an action out of range -- a rejection, no check
+ * Candidates were checked and none was admitted: the gate's refusal -- nothing is provisioned, act_path / act_slot / gn_gsnr_db /
+ * gn_se are those of the FIRST candidate checked.  No candidate has a window: the policy's rejection, (k, S), NaN, gn_se 0.
+ * gn_gsnr_db [n_steps][B] float64 and gn_se [n_steps][B] uint8 (the level of the candidate shown, 0 = no check ran), or NULL.
+ * n_steps steps are ONE launch of orlg_rmsa_am_kernel<W, STATS>, which every other step of an adaptive handle launches too. */
+#define ORLG_GN_MODULATION_PATH 0
+#define ORLG_GN_MODULATION_ADAPTIVE 1
+enum { ORLG_AM_SP_FF = 200, ORLG_AM_SAP_FF = 201, ORLG_AM_PATH_EXTERNAL = 202, ORLG_AM_EXTERNAL = 203 };
+int orlg_set_gn_modulation(orlg_env *env, int32_t mode);
+int orlg_step_modulation(orlg_env *env, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
+                         double *gn_gsnr_db /* [n_steps][B] or NULL */, uint8_t *gn_se /* [n_steps][B] or NULL */);
+/* Every level of every candidate path of every env's pending request, with no early exit (one launch): slot [B][k][M] int16 (S = no
+ * window), gsnr_db [B][k][M] float64 (NaN), admitted [B][k][M] uint8 -- entry [p][m - 1] is the outcome of ORLG_AM_EXTERNAL with the
+ * action (p, slot, m), with the bits of its gn_gsnr_db; best_se [B][k] uint8: the level ORLG_AM_PATH_EXTERNAL provisions on path p,
+ * 0 = none.  An adaptive handle only.  Any pointer may be NULL, not all.  Reads state only; buffers as orlg_action_masks. */
+int orlg_gn_modulation_windows(orlg_env *env, int16_t *slot, double *gsnr_db, uint8_t *admitted, uint8_t *best_se);
+int orlg_get_running_services_se(orlg_env *env, int32_t *count, int32_t *head, int32_t *path_gid, int16_t *slot, int16_t *num_slots,
+                                 int32_t *bit_rate, double *release_time, int16_t *se);
+
 /* SimpleMatrixObservation.observation() (rmsa_env.py:940-971) for every env: [B][2N + E*S] uint8 */
 int orlg_simple_matrix_observation(orlg_env *env, uint8_t *out);
 int orlg_simple_matrix_obs_dim(orlg_env *env);

@@ -1,8 +1,8 @@
 from . import _lib, envs, trace, traffic
-from ._lib import ASSIGN_RULES, BLOCK_CAUSES, CUT_POLICIES, FIT_LEVELS, MAX_MARGIN_POLICIES, WINDOW_POLICIES, OrlgError
+from ._lib import ADAPTIVE_POLICIES, ASSIGN_RULES, BLOCK_CAUSES, CUT_POLICIES, FIT_LEVELS, MAX_MARGIN_POLICIES, WINDOW_POLICIES, OrlgError
 from .batched import DEFAULT_BIT_RATES, BatchedDeepRMSAEnv, BatchedRMSAEnv
 from .envs import (DeepRMSAEnv, PathOnlyFirstFitAction, RMSAEnv, SimpleMatrixObservation, assignment_heuristic,
-                   min_cut_heuristic, window_heuristic, max_margin_heuristic,
+                   min_cut_heuristic, window_heuristic, max_margin_heuristic, adaptive_modulation_heuristic,
                    deeprmsa_shortest_available_path_first_fit,
                    deeprmsa_shortest_path_first_fit, evaluate_heuristic, least_loaded_path_first_fit,
                    random_policy, shortest_available_path_first_fit, shortest_available_path_first_fit_gn,
@@ -24,4 +24,4 @@ __all__ = ["ENV_IDS", "env_class", "make", "register_with_gym", "FrozenTopology"
            "shortest_available_path_first_fit_gn",
            "least_loaded_path_first_fit", "deeprmsa_shortest_path_first_fit",
            "deeprmsa_shortest_available_path_first_fit", "random_policy", "evaluate_heuristic",
-           "traffic", "make_sweep", "BLOCK_CAUSES", "FIT_LEVELS", "ASSIGN_RULES", "assignment_heuristic", "CUT_POLICIES", "min_cut_heuristic", "max_margin_heuristic", "MAX_MARGIN_POLICIES", "WINDOW_POLICIES", "window_heuristic", "write_monitor_tree", "trace", "RequestTrace", "TraceError", "record_trace"]
+           "traffic", "make_sweep", "BLOCK_CAUSES", "FIT_LEVELS", "ASSIGN_RULES", "assignment_heuristic", "CUT_POLICIES", "min_cut_heuristic", "max_margin_heuristic", "adaptive_modulation_heuristic", "MAX_MARGIN_POLICIES", "ADAPTIVE_POLICIES", "WINDOW_POLICIES", "window_heuristic", "write_monitor_tree", "trace", "RequestTrace", "TraceError", "record_trace"]

@@ -50,6 +50,14 @@ GN_PATH_WINDOW_RULES = {"first": 0, "first_full": 1, "last": 2, "best": 3, "exac
 # handle with gn_gate= only).  The names, and the route each one is to that entry.  Tables of their own, as CUT_POLICIES
 MAX_MARGIN_POLICIES = ("sap_mm", "any_mm", "path_mm_external")
 MAX_MARGIN_ROUTES = {"sap_mm": POLICIES["sap_ff"], "any_mm": ROUTE_BEST_WINDOW, "path_mm_external": POLICIES["path_ff_external"]}
+# include/orlg.h orlg_set_gn_modulation / orlg_step_modulation: a gate that chooses the spectral efficiency a service runs at from the
+# GSNR (a handle with gn_gate=rmsa_gn_gate_parameters(..., modulation="adaptive") only).  The gate's modes, the policy names
+# that walk the levels and the value each one is to that entry.  Tables of their own, as CUT_POLICIES
+GN_MODULATION_MODES = {"path": 0, "adaptive": 1}
+ADAPTIVE_POLICIES = ("sp_ff_am", "sap_ff_am", "path_am_external", "external_am")
+ADAPTIVE_POLICY_IDS = {"sp_ff_am": 200, "sap_ff_am": 201, "path_am_external": 202, "external_am": 203}
+MAX_MODULATION_LEVELS = 6     # the modulation factors of the GN model end at spectral efficiency 6
+MAX_ADAPTIVE_PATHS = 2048     # a service's level takes 3 bits of its descriptor's 14-bit path field
 
 
 def policy_ids(policy):
@@ -229,7 +237,13 @@ def _prototypes():
               # ... over every start slot of every path: mask words, GSNR and margin rows, the window with the largest worst margin
               "orlg_gn_admission_slots": (None, [vp, vp, vp, vp, vp, vp]),
               "orlg_step_max_margin": (None, [vp, i32, i32, vp, i32, P(StepIO), P(StepDiag), vp]),
-              "orlg_step_max_margin_protect": (None, [vp, i32, i32, vp, i32, P(StepIO), P(StepDiag), vp, vp])})
+              "orlg_step_max_margin_protect": (None, [vp, i32, i32, vp, i32, P(StepIO), P(StepDiag), vp, vp]),
+              # a gate that chooses the modulation from the GSNR: the mode, the step that walks the levels, every level of every path,
+              # the running services with the spectral efficiency each one runs at
+              "orlg_set_gn_modulation": (None, [vp, i32]),
+              "orlg_step_modulation": (None, [vp, i32, i32, vp, i32, P(StepIO), vp, vp]),
+              "orlg_gn_modulation_windows": (None, [vp, vp, vp, vp, vp]),
+              "orlg_get_running_services_se": (None, [vp, vp, vp, vp, vp, vp, vp, vp, vp])})
     # QoT-aware only
     t.update({"orlg_phy_step": (None, [vp, i32, i32, vp, vp, i32, P(PhyStepIO)]), "orlg_phy_node_vectors": (None, [vp]),
               "orlg_phy_get_episode_stats": (None, [vp, vp]), "orlg_phy_channel_masks": (None, [vp, vp]),

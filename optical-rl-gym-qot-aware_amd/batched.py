@@ -81,6 +81,8 @@ class BatchedRMSAEnv(BatchedHandle):
                 _lib.check(self.L.orlg_set_gn_gate(self.h, C.byref(gg)))
                 if self.gn_protect:
                     _lib.check(self.L.orlg_set_gn_protect(self.h, 1))
+                if self.gn_adaptive:
+                    _lib.check(self.L.orlg_set_gn_modulation(self.h, _lib.GN_MODULATION_MODES["adaptive"]))
             except Exception:
                 self.close()
                 raise
@@ -89,6 +91,23 @@ class BatchedRMSAEnv(BatchedHandle):
     def gn_protect(self):
         """The gate also protects the running lightpaths (``rmsa_gn_gate_parameters(protect_running=True)``)."""
         return bool(self.gn_gate and self.gn_gate.get("protect_running"))
+
+    @property
+    def gn_adaptive(self):
+        """The gate chooses the spectral efficiency a service runs at from the GSNR
+        (``rmsa_gn_gate_parameters(modulation="adaptive")``)."""
+        gate = getattr(self, "gn_gate", None)
+        return bool(gate and gate.get("modulation") == "adaptive")
+
+    @property
+    def modulation_levels(self):
+        """``M``: the levels an adaptive gate chooses among (its ``num_thresholds``), 0 on every other handle."""
+        return len(self.gn_gate["thresholds_db"]) if self.gn_adaptive else 0
+
+    def _refuse_adaptive(self, what, why):
+        """``ValueError`` on a handle whose gate chooses the modulation, before the library is called: what DESIGN 2.33 leaves for later"""
+        if self.gn_adaptive:
+            raise ValueError(f"{what}: the handle's gate chooses the modulation (modulation='adaptive'); {why}")
 
     def launch_info(self):
         """Launch geometry of the step kernel (envs per workgroup, LDS bytes, resident workgroups per CU)."""
@@ -158,7 +177,31 @@ class BatchedRMSAEnv(BatchedHandle):
         admitted, the lowest free start of the first such path is proposed and refused: a gate refusal, cause ``"gn"``.
         ``"gn_window_margin_db"`` in ``outputs`` (these names only) -- the ``w`` of the proposed window, NaN for such a fallback or
         a rejection.  ``n_steps`` steps are one launch; :meth:`max_margin_windows` is the matching query, bit for bit.  Without a
-        gate, or with ``gn_rule=``: ``ValueError``."""
+        gate, or with ``gn_rule=``: ``ValueError``.
+
+        Adaptive modulation behind the gate (``orlg_step_modulation``; not in the reference): the names of
+        ``_lib.ADAPTIVE_POLICIES`` on a handle with ``gn_gate=rmsa_gn_gate_parameters(..., modulation="adaptive")``.  A level ``m`` in
+        ``1..M`` (``M`` = the gate's thresholds) is the spectral efficiency a service runs at: ``n_m`` slots, admitted iff the GSNR of
+        the first fit of ``n_m`` meets ``thresholds_db[m - 1]``.  ``sp_ff_am`` (path 0, levels ``M`` down to 1, the first admitted
+        candidate), ``sap_ff_am`` (the paths in order, each with its levels), ``path_am_external`` (``actions`` [B] name the path)
+        and ``external_am`` (``actions`` [B, 3] = (path, slot, se); an ``se`` outside ``1..M`` is an action out of range).
+        Candidates were checked and none admitted: the gate's refusal, with ``act_path`` / ``act_slot`` / ``gn_gsnr_db`` / ``gn_se``
+        of the FIRST candidate checked.  ``"gn_se"`` in ``outputs`` (these names only) -- [n_steps, B] uint8, the level of the
+        candidate shown, 0 where no check ran.  Every other policy keeps proposing at the path's own spectral efficiency on such a
+        handle; ``gn_rule=``, the ``_mm`` names and ``block_cause`` / ``cause_counts`` raise ``ValueError`` there.
+        :meth:`modulation_windows` is the matching query."""
+        if policy in _lib.ADAPTIVE_POLICIES:
+            return self._run_modulation(policy, n_steps, actions, auto_reset, outputs, out, cause_counts, gn_rule)
+        if "gn_se" in _output_names(outputs, out):
+            raise ValueError(f"policy {policy!r}: gn_se is an output of the names of _lib.ADAPTIVE_POLICIES only")
+        if self.gn_adaptive:
+            later = "no such launch runs behind an adaptive gate yet"
+            if policy in _lib.MAX_MARGIN_POLICIES:
+                self._refuse_adaptive(f"policy {policy!r}", later)
+            if gn_rule is not None:
+                self._refuse_adaptive(f"gn_rule={gn_rule!r}", later)
+            if "block_cause" in _output_names(outputs, out) or (cause_counts is not None and cause_counts is not False):
+                self._refuse_adaptive("block_cause / cause_counts", "its step kernel holds no classifier yet")
         if policy in _lib.MAX_MARGIN_POLICIES:
             return self._run_max_margin(policy, n_steps, actions, auto_reset, outputs, out, cause_counts, gn_rule)
         if "gn_window_margin_db" in _output_names(outputs, out):
@@ -166,6 +209,65 @@ class BatchedRMSAEnv(BatchedHandle):
         if gn_rule is not None:
             return self._run_rule_gn(policy, n_steps, actions, auto_reset, outputs, out, cause_counts, gn_rule)
         return self._run(policy, n_steps, actions, auto_reset, outputs, out, cause_counts)
+
+    def _run_modulation(self, policy, n_steps, actions, auto_reset, outputs, out, cause_counts, gn_rule):
+        """``run(<a name of ADAPTIVE_POLICIES>)``: the refusals before the library is called, then ``orlg_step_modulation``."""
+        if gn_rule is not None:
+            raise ValueError(f"policy {policy!r} with gn_rule=: the policy walks the levels of the reference's first fit, no assignment rule runs with it")
+        if not self.gn_adaptive:
+            raise ValueError(f"policy {policy!r} needs a handle whose gate chooses the modulation "
+                             "(gn_gate=rmsa_gn_gate_parameters(..., modulation='adaptive'))")
+        names = _output_names(outputs, out)
+        if "block_cause" in names or (cause_counts is not None and cause_counts is not False):
+            raise ValueError(f"policy {policy!r}: block_cause / cause_counts are not served with the names of _lib.ADAPTIVE_POLICIES yet")
+        for name in ("gn_neighbour_margin_db", "gn_window_margin_db"):
+            if name in names:
+                raise ValueError(f"policy {policy!r}: {name} is not an output of the names of _lib.ADAPTIVE_POLICIES")
+        if int(n_steps) < 1:
+            raise ValueError(f"n_steps {n_steps}: expected >= 1")
+        B = self.batch_size
+        ap = None
+        if policy in ("path_am_external", "external_am"):
+            if actions is None:
+                raise ValueError(f"policy {policy!r} needs an actions array")
+            if int(n_steps) != 1:
+                raise ValueError(f"policy {policy!r}: the actions name one candidate per environment, n_steps must be 1")
+            if not hasattr(actions, "data_ptr"):
+                actions = np.asarray(actions)
+                if actions.dtype.kind not in "iu":
+                    raise TypeError(f"actions: dtype {actions.dtype}, expected an integer type")
+                actions = np.ascontiguousarray(actions, dtype=np.int32)
+            _check_buffer("actions", actions, (B, 3) if policy == "external_am" else (B,), np.int32)
+            ap = _ptr(actions)
+        io = _lib.StepIO()
+        extra = {}
+        for name, dtype in (("gn_gsnr_db", "float64"), ("gn_se", "uint8")):
+            if name in names:
+                names = [n for n in names if n != name]
+                extra.update(self._step_outputs([name], n_steps, out, {name: dtype}, {}))
+        res = self._step_outputs(names, n_steps, out, _lib.STEP_IO_DTYPES, _STEP_IO_SHAPES, io)
+        _lib.check(self.L.orlg_step_modulation(self.h, _lib.ADAPTIVE_POLICY_IDS[policy], int(n_steps), ap, 1 if auto_reset else 0,
+                                               C.byref(io), _ptr(extra.get("gn_gsnr_db")), _ptr(extra.get("gn_se"))))
+        res.update(extra)
+        return res
+
+    def modulation_windows(self, slot_out=None, gsnr_out=None, admitted_out=None, best_se_out=None):
+        """Every level of every candidate path of every env's pending request behind a gate that chooses the modulation
+        (``orlg_gn_modulation_windows``; one launch, no early exit): ``(slot, gsnr_db, admitted, best_se)`` -- [B, k, M]
+        int16 the first fit of ``n_m`` on the path (``S`` = no window), [B, k, M] float64 its GSNR in dB (NaN), [B, k, M] uint8 1 iff
+        it meets ``thresholds_db[m - 1]``, and [B, k] uint8 the level ``path_am_external`` provisions on the path (0 = none).  Entry
+        ``[p, m - 1]`` is the outcome of ``run("external_am", actions=[p, slot, m])``, with the bits of its ``gn_gsnr_db``: the
+        agent's mask and feature for ``external_am`` / ``path_am_external``.  Reads state only; the buffers as ``out`` in
+        :meth:`action_masks`."""
+        if not self.gn_adaptive:
+            raise ValueError("modulation_windows needs a handle whose gate chooses the modulation "
+                             "(gn_gate=rmsa_gn_gate_parameters(..., modulation='adaptive'))")
+        B, k, M = self.batch_size, self.k_paths, self.modulation_levels
+        res = [self._checked_out(name, buf, shape, dt) for name, buf, shape, dt in (
+            ("slot_out", slot_out, (B, k, M), np.int16), ("gsnr_out", gsnr_out, (B, k, M), np.float64),
+            ("admitted_out", admitted_out, (B, k, M), np.uint8), ("best_se_out", best_se_out, (B, k), np.uint8))]
+        _lib.check(self.L.orlg_gn_modulation_windows(self.h, *(_ptr(b) for b in res)))
+        return tuple(res)
 
     def _run_max_margin(self, policy, n_steps, actions, auto_reset, outputs, out, cause_counts, gn_rule):
         """``run(<a name of MAX_MARGIN_POLICIES>)``: the refusals before the library is called, then ``orlg_step_max_margin_protect``."""
@@ -433,6 +535,9 @@ class BatchedRMSAEnv(BatchedHandle):
             raise ValueError(f"gsnr_out: kind {kind!r} has no GSNR rows, they go with {self.GN_MASK_KINDS}")
         if gn and self.gn_gate is None:
             raise ValueError(f"kind {kind!r} needs a handle with a GN-model admission check (gn_gate=)")
+        if gn:
+            self._refuse_adaptive(f"kind {kind!r}", "this mask describes a step at the path's own spectral efficiency against services "
+                                  "without levels: modulation_windows() is the query of such a handle")
         if gn and self.gn_protect:
             raise ValueError(f"kind {kind!r}: the handle protects its running lightpaths (protect_running); this mask knows the "
                              "candidate's own check only and would describe a step the handle does not run: "
@@ -536,6 +641,7 @@ class BatchedRMSAEnv(BatchedHandle):
             raise ValueError(f"rule {rule!r}: expected one of {tuple(_lib.GN_PATH_WINDOW_RULES)}")
         if self.gn_gate is None:
             raise ValueError("path_rule_windows needs a handle with a GN-model admission check (gn_gate=)")
+        self._refuse_adaptive("path_rule_windows", "no assignment rule runs behind an adaptive gate yet: modulation_windows() is the query of such a handle")
         if self.gn_protect:
             raise ValueError("path_rule_windows: the handle protects its running lightpaths (protect_running); this query knows the "
                              "candidate's own check only and would describe a step the handle does not run: "
@@ -582,6 +688,7 @@ class BatchedRMSAEnv(BatchedHandle):
             raise ValueError(f"kind {kind!r}: expected one of {self.ADMISSION_MASK_KINDS}")
         if self.gn_gate is None:
             raise ValueError("admission_masks needs a handle with a GN-model admission check (gn_gate=)")
+        self._refuse_adaptive("admission_masks", "modulation_windows() is the query of such a handle")
         shape, dt = self.action_mask_shape(kind)
         rows = (self.batch_size, self.k_paths * (self.j if kind == "deeprmsa" else 1))
         if out is None:
@@ -612,6 +719,7 @@ class BatchedRMSAEnv(BatchedHandle):
             raise ValueError(f"rule {rule!r}: expected one of {tuple(_lib.GN_PATH_WINDOW_RULES)}")
         if self.gn_gate is None:
             raise ValueError("admission_windows needs a handle with a GN-model admission check (gn_gate=)")
+        self._refuse_adaptive("admission_windows", "modulation_windows() is the query of such a handle")
         shape = (self.batch_size, self.k_paths)
         res = []
         for name, buf, dt in (("slots_out", slots_out, np.int16), ("gsnr_out", gsnr_out, np.float64), ("margin_out", margin_out, np.float64),
@@ -650,6 +758,7 @@ class BatchedRMSAEnv(BatchedHandle):
         state only; the buffers as ``out`` in :meth:`action_masks`."""
         if self.gn_gate is None:
             raise ValueError("admission_slot_masks needs a handle with a GN-model admission check (gn_gate=)")
+        self._refuse_adaptive("admission_slot_masks", "modulation_windows() is the query of such a handle")
         B, k, S = self.batch_size, self.k_paths, self.num_spectrum_resources
         out = self._checked_out("out", out, (B, k, self.words_per_link), np.uint64)
         gsnr = self._float_rows("gsnr_out", gsnr_out, (B, k, S))
@@ -668,6 +777,7 @@ class BatchedRMSAEnv(BatchedHandle):
         Reads state only; the buffers as ``out`` in :meth:`action_masks`."""
         if self.gn_gate is None:
             raise ValueError("max_margin_windows needs a handle with a GN-model admission check (gn_gate=)")
+        self._refuse_adaptive("max_margin_windows", "modulation_windows() is the query of such a handle")
         shape = (self.batch_size, self.k_paths)
         slots = self._checked_out("slots_out", slots_out, shape, np.int16)
         margin = self._checked_out("margin_out", margin_out, shape, np.float64)
@@ -677,7 +787,7 @@ class BatchedRMSAEnv(BatchedHandle):
     # ------------------------------------------------------------------ the running services and their GN-model audit
     RUNNING_SERVICE_FIELDS = (("count", np.int32, False), ("head", np.int32, False), ("path_gid", np.int32, True),
                               ("slot", np.int16, True), ("num_slots", np.int16, True), ("bit_rate", np.int32, True),
-                              ("release_time", np.float64, True))   # (name, dtype, [B, Q] rather than [B])
+                              ("release_time", np.float64, True), ("se", np.int16, True))   # (name, dtype, [B, Q] rather than [B])
     AUDIT_SERVICE_FIELDS = ("gsnr_db", "margin_db", "osnr_ase_db", "snr_nli_db")
 
     @property
@@ -702,10 +812,11 @@ class BatchedRMSAEnv(BatchedHandle):
         """The running services of every environment (``orlg_get_running_services``): a dict -- ``count`` [B] int32,
         the live entries of the release ring; ``head`` [B] int32, the ring slot of rank 0; and [B, Q] each, in rank order (ascending
         release time), ``path_gid`` int32 (the global index of the path record), ``slot`` and ``num_slots`` int16, ``bit_rate`` int32
-        and ``release_time`` float64, with -1 / NaN past ``count``.  ``Q`` is :attr:`queue_capacity`.  Reads state only; ``out``: a
+        and ``release_time`` float64, with -1 / NaN past ``count``; ``se`` int16, the spectral efficiency the service runs at -- its
+        path's own, or the level an adaptive gate provisioned it at.  ``Q`` is :attr:`queue_capacity`.  Reads state only; ``out``: a
         dict of preallocated buffers by these names (numpy arrays or torch tensors, as ``out`` in :meth:`action_masks`)."""
         res = self._rank_buffers(self.RUNNING_SERVICE_FIELDS, out, "running_services")
-        _lib.check(self.L.orlg_get_running_services(self.h, *(_ptr(res[f[0]]) for f in self.RUNNING_SERVICE_FIELDS)))
+        _lib.check(self.L.orlg_get_running_services_se(self.h, *(_ptr(res[f[0]]) for f in self.RUNNING_SERVICE_FIELDS)))
         return res
 
     def _gn_gate_struct(self, g):

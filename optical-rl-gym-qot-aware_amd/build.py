@@ -8,7 +8,7 @@ arrival process must perform exactly the reference's IEEE operations (no fused m
 The library is a set of translation units compiled in parallel into csrc/build/*.o and linked: the host side
 (orlg_host.hip: what the APIs share; orlg_api.hip, orlg_api_step.hip, orlg_api_query.hip: the RMSA API -- handle and getters, the step,
 the queries; orlg_phy_api.hip, orlg_osnr.hip: the other two APIs) and one object per
-(kernel family, words per link W) from orlg_inst_{wave,gnrules,gnprotect,gnadmit,gnslots,gnmm,group,phy}.hip -- orlg_inst_phy.hip twice, with -DORLG_INST_TRACE=0 and 1;
+(kernel family, words per link W) from orlg_inst_{wave,gnrules,gnprotect,gnadmit,gnslots,gnmm,gnam,group,phy}.hip -- orlg_inst_phy.hip twice, with -DORLG_INST_TRACE=0 and 1;
 orlg_gn_audit_kernels.hip, whose kernels know no word count, is one object.
 Which instantiations a family has is written once, in csrc/orlg_variants.h.  An object is rebuilt when any file its depfile names
 (or the flags) changed, so an edit of one kernel family recompiles that family only.
@@ -47,6 +47,8 @@ def units():
         u.append((f"orlg_inst_gnslots_w{w}", "orlg_inst_gnslots.hip", [f"-DORLG_INST_W={w}"]))
     for w in sorted(WAVE_W, reverse=True):   # the gated step kernel under a max-margin policy (orlg_step_max_margin)
         u.append((f"orlg_inst_gnmm_w{w}", "orlg_inst_gnmm.hip", [f"-DORLG_INST_W={w}"]))
+    for w in sorted(WAVE_W, reverse=True):   # the gated step kernel of a gate that chooses the modulation, and its query (orlg_step_modulation)
+        u.append((f"orlg_inst_gnam_w{w}", "orlg_inst_gnam.hip", [f"-DORLG_INST_W={w}"]))
     u.append(("orlg_gn_audit", "orlg_gn_audit_kernels.hip", []))   # the audit of the running lightpaths: no word count, one object
     for w in sorted(PHY_W, reverse=True):
         u.append((f"orlg_inst_phy_w{w}", "orlg_inst_phy.hip", [f"-DORLG_INST_W={w}", "-DORLG_INST_TRACE=0"]))

@@ -5,6 +5,7 @@
 // with the QoT-aware API is the handle core of orlg_host.h.  No CPU compute path exists: every entry point that touches environments
 // needs a HIP device.
 #include "orlg_rmsa_host.h"
+#include "orlg_qdesc.h"
 #include "orlg_step_call.h"   // orlg_debug_step_call
 #include "orlg_wave.h"   // valid_mask, ORLG_INF_BITS for the helper kernels; the step kernels are instantiated in orlg_inst_*.hip
 #include "orlg_graph_log.h"   // ORLG_GLOG_MAX_Q: the queue capacity the lean body's packed log is sized for
@@ -566,9 +567,31 @@ int orlg_save_state(orlg_env *e, void *buffer) {
     return orlg_handle_state_save(e, rmsa_state_parts(e), buffer);
 }
 int orlg_load_state(orlg_env *e, const void *buffer) {
-    if (!e) return fail(ORLG_ERR_INVALID, "null argument");
+    if (!e || !buffer) return fail(ORLG_ERR_INVALID, "null argument");
+    // a snapshot of a handle whose gate chooses the modulation may hold services with a level (orlg_qdesc.h): a handle that is not
+    // adaptive would read the level as part of the path record -- refused before anything is copied
+    if (!e->p.gn_adaptive) {
+        HIP_TRY(hipSetDevice(e->device));
+        const std::vector<OrlgStatePart> parts = rmsa_state_parts(e);
+        size_t off = 0;
+        for (const OrlgStatePart &sp : parts) {
+            if (sp.ptr == e->p.qdesc) break;
+            off += sp.bytes;
+        }
+        const int has = rmsa_state_has_levels(e, static_cast<const unsigned char *>(buffer) + off);
+        if (has < 0) return has;
+        if (has)
+            return fail(ORLG_ERR_INVALID, "load_state: a running service of the snapshot names no path record of this handle (%d records): the state of a gate that chooses the modulation (orlg_set_gn_modulation) loads into such a handle only", e->num_paths);
+    }
     return orlg_handle_load(e, rmsa_state_parts(e), buffer, e->p.scal, e->p.B);
 }
+}
+int rmsa_state_has_levels(orlg_env *e, const void *qdesc) {
+    std::vector<uint32_t> d((size_t)e->p.B * e->p.Q);
+    HIP_TRY(hipMemcpy(d.data(), qdesc, d.size() * sizeof(uint32_t), hipMemcpyDefault));
+    for (uint32_t v : d)   // (an empty slot holds 0)
+        if (orlg_qdesc_gid(v, false) >= e->num_paths) return 1;
+    return 0;
 }
 
 

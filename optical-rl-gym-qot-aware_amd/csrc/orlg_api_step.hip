@@ -3,6 +3,7 @@
 // refuses it: orlg_step_call.h), the orlg_step* entries, and the GN-model gate a step checks against with its setters.
 #include "orlg_rmsa_host.h"
 #include "orlg_step_call.h"
+#include "orlg_qdesc.h"
 
 // ---------------------------------------------------------------------------------------- launches
 // the kernels live in per-W objects (orlg_inst_wave.hip / orlg_inst_group.hip), found by key: orlg_pick (orlg_variants.h)
@@ -82,7 +83,11 @@ static bool group_kernel_serves(const orlg_env *e, const OrlgParams &p) {
 // the plain wave-per-environment step kernel
 static rmsa_kernel_t step_kernel(int W, int stats) { return orlg_pick(W, OrlgWaveKey{ORLG_WAVE_KERNEL(orlg_rmsa_kernel), stats, false}); }
 
+static int launch_rmsa_am(orlg_env *e, const OrlgParams &p, uint8_t *o_se);
+
 int launch_rmsa(orlg_env *e, const OrlgParams &p) {
+    // a step of a handle whose gate chooses the modulation: orlg_rmsa_am_kernel, whatever the policy -- its decode knows the levels
+    if (p.mode == ORLG_MODE_STEP && p.gn && p.gn_adaptive) return launch_rmsa_am(e, p, nullptr);
     // a step of a handle with a GN-model admission check: the general kernel's GN instantiation, whatever the policy and the length
     const bool gn = p.mode == ORLG_MODE_STEP && p.gn != nullptr;
     // a launch that asks for the blocking cause: the general kernel's CAUSE instantiation, with or without the check
@@ -181,6 +186,30 @@ static int launch_rmsa_mm(orlg_env *e, const OrlgParams &p, const MmLaunch &m) {
     return ORLG_OK;
 }
 
+// ---- the gated step kernel of a handle whose gate chooses the modulation (orlg_rmsa_am_kernel, orlg_inst_gnam.hip): the
+// handle's own workgroup -- it needs no LDS beyond the wave regions
+static int launch_rmsa_am(orlg_env *e, const OrlgParams &p, uint8_t *o_se) {
+    const OrlgAmKey key = {p.stats_level};
+    orlg_rmsa_am_kernel_t k = orlg_pick_gn_am(e->W, key);
+    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
+    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), e->lds_block_bytes)) return rc;
+    const int wpb = e->waves_per_block;
+    int *resident = &e->am_resident[p.stats_level];
+    if (int rc = orlg_handle_resident(e, reinterpret_cast<const void *>(k), ORLG_WAVE * wpb, e->lds_block_bytes, resident)) return rc;
+    int nblocks = (p.B + wpb - 1) / wpb;
+    if (nblocks > *resident) nblocks = *resident;
+    OrlgParams q = p;
+    q.llog = nullptr;
+    q.ticket_base = e->ticket_base;
+    q.ticket_stride = p.n_steps <= 16 ? 1u : 0u;
+    if (!q.ticket_stride) e->ticket_base += (uint32_t)p.B;
+    const OrlgAmArgs a = {o_se};
+    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), e->lds_block_bytes, e->stream, q, a);
+    HIP_TRY(hipGetLastError());
+    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * wpb, e->lds_block_bytes);
+    return ORLG_OK;
+}
+
 extern "C" {
 /* launch geometry of the step kernel: out[0] waves (envs) per workgroup, out[1] LDS bytes per workgroup,
  * out[2] workgroups resident per CU according to hipOccupancyMaxActiveBlocksPerMultiprocessor, out[3] W */
@@ -207,6 +236,7 @@ struct StepExtras {
     int32_t *counts = nullptr;
     double *margin = nullptr;
     double *wmargin = nullptr;
+    uint8_t *se = nullptr;   // gn_se of orlg_step_modulation
 };
 static StepExtras step_extras(const struct orlg_step_diag *diag, double *margin = nullptr) {
     StepExtras x;
@@ -237,17 +267,19 @@ static int place_extra(orlg_env *e, ExtraOut *o) {
 
 // one launch of n_steps steps of a call that orlg_step_call has resolved: the live part of every step entry.  mm: the call is
 // orlg_step_max_margin's (orlg_step_mm_call resolved it, mm_geometry found its workgroup) and launches orlg_rmsa_mm_kernel
+// am: the call is orlg_step_modulation's (call.policy is the device's ORLG_POLICY_*_AM) and launches orlg_rmsa_am_kernel with gn_se
 static int rmsa_step(orlg_env *e, const OrlgStepCall &call, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
-                     const orlg_step_io *io, const StepExtras &x, MmLaunch *mm = nullptr) {
+                     const orlg_step_io *io, const StepExtras &x, MmLaunch *mm = nullptr, bool am = false) {
     const int32_t policy = call.policy;
-    const bool ext = policy == ORLG_POLICY_EXTERNAL || policy == ORLG_POLICY_DEEPRMSA_EXTERNAL || policy == ORLG_POLICY_PATH_FF_EXTERNAL;
+    const bool ext = am ? policy == ORLG_POLICY_PATH_AM_EXT || policy == ORLG_POLICY_EXT_AM
+                        : policy == ORLG_POLICY_EXTERNAL || policy == ORLG_POLICY_DEEPRMSA_EXTERNAL || policy == ORLG_POLICY_PATH_FF_EXTERNAL;
     if (ext && (!actions || n_steps != 1)) return fail(ORLG_ERR_INVALID, "external actions need an action array and n_steps == 1");
     if (int rc = orlg_trace_admit(&e->trace, n_steps)) return rc;   // before anything is launched or copied
     HIP_TRY(hipSetDevice(e->device));
     OrlgParams p = e->p;
     p.mode = ORLG_MODE_STEP; p.n_steps = n_steps; p.policy = policy; p.auto_reset = auto_reset;
     if (ext) {
-        size_t n = (size_t)p.B * (policy == ORLG_POLICY_EXTERNAL ? 2 : 1);
+        size_t n = (size_t)p.B * (am ? (policy == ORLG_POLICY_EXT_AM ? 3 : 1) : policy == ORLG_POLICY_EXTERNAL ? 2 : 1);
         if (const void *da = orlg_device_alias(actions)) {   // device memory, or pinned host memory read over the bus
             p.actions = static_cast<const int32_t *>(da);
         } else {
@@ -267,9 +299,10 @@ static int rmsa_step(orlg_env *e, const OrlgStepCall &call, int32_t n_steps, con
         {io ? io->avg_link_compactness : nullptr, 8},   {io ? io->avg_link_utilization : nullptr, 8}};
     int rc = orlg_handle_place(e, slots, ORLG_NUM_OUTS, cnt, p.outs, &p.out_mask);
     if (rc) return rc;
-    ExtraOut extra[5] = {{x.gsnr, cnt * sizeof(double), X_GSNR, true}, {x.cause, cnt, X_CAUSE, false},
+    ExtraOut extra[6] = {{x.gsnr, cnt * sizeof(double), X_GSNR, true}, {x.cause, cnt, X_CAUSE, false},
                          {x.counts, (size_t)p.B * ORLG_NUM_CAUSES * sizeof(int32_t), X_CAUSE_COUNTS, false},
-                         {x.margin, cnt * sizeof(double), X_MARGIN, false}, {x.wmargin, cnt * sizeof(double), X_WINDOW_MARGIN, false}};
+                         {x.margin, cnt * sizeof(double), X_MARGIN, false}, {x.wmargin, cnt * sizeof(double), X_WINDOW_MARGIN, false},
+                         {x.se, cnt, X_SE, false}};
     for (ExtraOut &o : extra)
         if ((rc = place_extra(e, &o))) return rc;
     p.o_gsnr = static_cast<double *>(extra[0].dev);
@@ -285,7 +318,7 @@ static int rmsa_step(orlg_env *e, const OrlgStepCall &call, int32_t n_steps, con
     p.assign = call.assign;
     if (call.assign != ORLG_ASSIGN_FIRST) p.out_mask |= ORLG_OUT_ASSIGN_BIT;   // the launch runs an ASSIGN instantiation
     if (mm) mm->window_margin = static_cast<double *>(extra[4].dev);
-    rc = mm ? launch_rmsa_mm(e, p, *mm) : launch_rmsa(e, p);
+    rc = mm ? launch_rmsa_mm(e, p, *mm) : am ? launch_rmsa_am(e, p, static_cast<uint8_t *>(extra[5].dev)) : launch_rmsa(e, p);
     if (rc) return rc;
     if (e->trace.length > 0) e->trace.position += n_steps;
     bool any = false;
@@ -305,6 +338,13 @@ static int step_entry(orlg_env *e, OrlgStepEntry entry, int32_t policy, int32_t 
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     OrlgStepCall call;
     if (int rc = orlg_step_call({entry, policy, rule, gn_mode, n_steps, e->p.gn != nullptr, e->gn_protect}, &call)) return rc;
+    // a handle whose gate chooses the modulation: what its one kernel does not hold is refused
+    if (e->p.gn_adaptive) {
+        if (entry == ORLG_ENTRY_RULE_GN)
+            return fail(ORLG_ERR_INVALID, "orlg_step_rule_gn: the handle's gate chooses the modulation (orlg_set_gn_modulation), and no assignment rule runs behind it yet");
+        if (x.cause || x.counts)
+            return fail(ORLG_ERR_INVALID, "block_cause / cause_counts: the handle's gate chooses the modulation (orlg_set_gn_modulation), and its step kernel holds no classifier yet");
+    }
     return rmsa_step(e, call, n_steps, actions, auto_reset, io, x);
 }
 extern "C" {
@@ -345,6 +385,8 @@ int orlg_step_rule_gn(orlg_env *e, int32_t route, int32_t rule, int32_t gn_mode,
 int orlg_step_max_margin_protect(orlg_env *e, int32_t route, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
                                  const struct orlg_step_diag *diag, double *window_margin_db, double *gn_neighbour_margin_db) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (e->p.gn_adaptive)
+        return fail(ORLG_ERR_INVALID, "orlg_step_max_margin: the handle's gate chooses the modulation (orlg_set_gn_modulation), and no max-margin policy runs behind it yet");
     OrlgStepCall call;
     if (int rc = orlg_step_mm_call({route, n_steps, e->p.gn != nullptr, actions != nullptr}, &call)) return rc;
     MmLaunch mm;
@@ -356,6 +398,21 @@ int orlg_step_max_margin_protect(orlg_env *e, int32_t route, int32_t n_steps, co
 int orlg_step_max_margin(orlg_env *e, int32_t route, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
                          const struct orlg_step_diag *diag, double *window_margin_db) {
     return orlg_step_max_margin_protect(e, route, n_steps, actions, auto_reset, io, diag, window_margin_db, nullptr);
+}
+// a policy that walks the levels behind a gate that chooses the modulation: one launch of orlg_rmsa_am_kernel
+int orlg_step_modulation(orlg_env *e, int32_t policy, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
+                         double *gn_gsnr_db, uint8_t *gn_se) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!e->p.gn || !e->p.gn_adaptive)
+        return fail(ORLG_ERR_INVALID, "orlg_step_modulation: the handle's gate does not choose the modulation (orlg_set_gn_modulation with ORLG_GN_MODULATION_ADAPTIVE on a handle with a gn_gate)");
+    if (policy < ORLG_AM_SP_FF || policy > ORLG_AM_EXTERNAL)
+        return fail(ORLG_ERR_INVALID, "orlg_step_modulation needs a policy ORLG_AM_SP_FF .. ORLG_AM_EXTERNAL: got %d", policy);
+    if (n_steps < 1) return fail(ORLG_ERR_INVALID, "n_steps must be >= 1");
+    const OrlgStepCall call = {(int32_t)ORLG_POLICY_SP_AM + (policy - ORLG_AM_SP_FF), ORLG_ASSIGN_FIRST};
+    StepExtras x;
+    x.gsnr = gn_gsnr_db;
+    x.se = gn_se;
+    return rmsa_step(e, call, n_steps, actions, auto_reset, io, x, nullptr, true);
 }
 }  // extern "C"
 
@@ -402,12 +459,16 @@ int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     HIP_TRY(hipSetDevice(e->device));
     if (!g) {
+        if (e->p.gn_adaptive)
+            return fail(ORLG_ERR_INVALID, "gn_gate: the handle's gate chooses the modulation (orlg_set_gn_modulation): its running services carry levels that no handle without a gate can read");
         e->p.gn = nullptr;
         e->gn_protect = false;   // (protection is a property of the gate: a new gate keeps it, no gate has none)
         return ORLG_OK;
     }
     if (e->group_mode == ORLG_KERNEL_GROUP)
         return fail(ORLG_ERR_INVALID, "gn_gate: the admission check is served by the wave-per-environment kernel, the handle was created with step_kernel GROUP");
+    if (e->p.gn_adaptive && g->num_thresholds != e->p.gn_adaptive)
+        return fail(ORLG_ERR_INVALID, "gn_gate: the handle's gate chooses among %d levels (orlg_set_gn_modulation), the new gate has %d thresholds", e->p.gn_adaptive, g->num_thresholds);
     std::vector<double> tab;
     if (int rc = gn_gate_table(e, g, tab)) return rc;
     if (!e->gn_table)
@@ -415,13 +476,43 @@ int orlg_set_gn_gate(orlg_env *e, const orlg_rmsa_gn_gate *g) {
     HIP_TRY(hipStreamSynchronize(e->stream));   // (a launch in flight may be reading the table)
     HIP_TRY(hipMemcpy(e->gn_table, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     e->p.gn = e->gn_table;
+    e->gn_num_thresholds = g->num_thresholds;
     return ORLG_OK;
 }
 
 int orlg_set_gn_protect(orlg_env *e, int32_t on) {
     if (!e) return fail(ORLG_ERR_INVALID, "null handle");
     if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn_protect: the handle has no gn_gate (orlg_set_gn_gate): protection is a property of the gate");
+    if (on && e->p.gn_adaptive)
+        return fail(ORLG_ERR_INVALID, "gn_protect: the handle's gate chooses the modulation (orlg_set_gn_modulation), and the running lightpaths are not protected behind it yet");
     e->gn_protect = on != 0;
+    return ORLG_OK;
+}
+
+int orlg_set_gn_modulation(orlg_env *e, int32_t mode) {
+    if (!e) return fail(ORLG_ERR_INVALID, "null handle");
+    if (!e->p.gn) return fail(ORLG_ERR_INVALID, "gn_modulation: the handle has no gn_gate (orlg_set_gn_gate): the mode is a property of the gate");
+    if (mode != ORLG_GN_MODULATION_PATH && mode != ORLG_GN_MODULATION_ADAPTIVE)
+        return fail(ORLG_ERR_INVALID, "gn_modulation: unknown mode %d (ORLG_GN_MODULATION_PATH or ORLG_GN_MODULATION_ADAPTIVE)", mode);
+    HIP_TRY(hipSetDevice(e->device));
+    if (mode == ORLG_GN_MODULATION_PATH) {
+        if (e->p.gn_adaptive) {   // (the levels its services carry would read as path records)
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            const int has = rmsa_state_has_levels(e, e->p.qdesc);
+            if (has < 0) return has;
+            if (has) return fail(ORLG_ERR_INVALID, "gn_modulation: the state holds a service that runs at a level of its own; a gate that does not choose the modulation cannot read it");
+        }
+        e->p.gn_adaptive = 0;
+        return ORLG_OK;
+    }
+    if (e->gn_protect)
+        return fail(ORLG_ERR_INVALID, "gn_modulation: the handle protects its running lightpaths (orlg_set_gn_protect), and the modulation is not chosen behind that second check yet");
+    if (e->num_paths >= ORLG_QDESC_AM_PATHS)
+        return fail(ORLG_ERR_INVALID, "gn_modulation: %d path records; a service's level takes 3 bits of the descriptor's path field, which leaves room for %d", e->num_paths, ORLG_QDESC_AM_PATHS - 1);
+    const int M = e->gn_num_thresholds;
+    if (M < 1 || M > ORLG_QDESC_MAX_LEVEL)
+        return fail(ORLG_ERR_INVALID, "gn_modulation: the gate has %d thresholds; the levels are spectral efficiencies 1..%d, where the modulation factors of the GN model end", M, ORLG_QDESC_MAX_LEVEL);
+    e->p.gn_adaptive = M;
     return ORLG_OK;
 }
 

@@ -156,7 +156,11 @@ struct OrlgParams {
     // ring's first array holds absolute arrival times (refill_requests_trace_as)
     const double *tr_arrival, *tr_holding;
     const uint32_t *tr_req;
-    int32_t tr_len, pad_tr;
+    int32_t tr_len;
+    // the gate chooses the modulation from the GSNR (orlg_set_gn_modulation): M = the gate's num_thresholds, 0 = every
+    // service runs at its path's own spectral efficiency.  Set: the descriptors of qdesc carry a level (orlg_qdesc.h).  (It took the
+    // place of a padding word: every other field lies in the kernarg segment where it lay)
+    int32_t gn_adaptive;
     // GN-model admission check of the wave-per-environment kernel (orlg_set_gn_gate, orlg_rmsa_gn.h): the gate's table in HBM
     // (ORLG_GN_* below), nullptr = no gate; o_gsnr: the per-step output gn_gsnr_db [n_steps][B] of orlg_step_gn, nullptr = not asked for
     const double *gn;
@@ -183,6 +187,13 @@ struct OrlgMmArgs {
     double *o_window_margin;   // [n_steps][B] the w of the proposed window, NaN for a fallback or a rejection; nullptr = not asked for
     int32_t protect;           // the handle protects its running lightpaths (wave-uniform)
     int32_t pad;
+};
+// device-side only (orlg_step_modulation, orlg_rmsa_gn_am.h; the AM instantiations alone read them): the policies that walk the levels
+// of a path -- path 0 / the paths in order / the agent's path -- and the agent's (path, slot, level)
+enum { ORLG_POLICY_SP_AM = 10, ORLG_POLICY_SAP_AM = 11, ORLG_POLICY_PATH_AM_EXT = 12, ORLG_POLICY_EXT_AM = 13 };
+// what a launch of orlg_rmsa_am_kernel gets beside OrlgParams -- a kernel argument of its own, as OrlgMmArgs
+struct OrlgAmArgs {
+    uint8_t *o_se;   // [n_steps][B] gn_se: the level of the candidate the step shows, 0 = no check ran; nullptr = not asked for
 };
 // out_mask of a launch that asks for a cause output: not one of outs[], but a per-step output like them -- what looks at
 // out_mask to choose a kernel (the deferred link statistics, the group kernel's HBMQ kind and lean body) keeps such a launch on

@@ -40,6 +40,7 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK) void orlg_gn_a
     const OrlgGnTable gn = ORLG_GPTR(const double, table);
     const bool wide = p.E > 64;
     const bool services = gsnr || margin || ase || nli;
+    const bool adaptive = p.gn_adaptive != 0;   // the descriptors carry the level their service runs at (orlg_qdesc.h)
     const double nan = ORLG_AUDIT_NAN, inf = __longlong_as_double((long long)ORLG_INF_BITS);
     for (int env = blockIdx.x * (int)(blockDim.x >> 6) + wib; env < p.B; env += n_waves) {
         int q_head, q_n;
@@ -55,14 +56,15 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK) void orlg_gn_a
         wave_sync();
         const bool resident = q_n <= 64;
         OrlgGnAuditEntry mine = {};
-        if (resident && q_n > 0) mine = rmsa_gn_audit_decode(tb, gn, wv.qdesc[lane < q_n ? lane : 0], wide);
+        if (resident && q_n > 0) mine = rmsa_gn_audit_decode(tb, gn, wv.qdesc[lane < q_n ? lane : 0], wide, adaptive);
         const size_t row = (size_t)env * Q;
         double c_g = nan, c_m = nan, c_a = nan, c_n = nan;   // lane r: the values of rank (v & ~63) + r
         double my_min = inf;                                // ... the smallest margin of the ranks this lane took, its lowest rank
         int my_rank = 0x7fffffff, my_below = 0;
         for (int v = 0; v < q_n; ++v) {
-            const OrlgGnAuditValue r = rmsa_gn_audit_victim(wv, tb, gn, wide, q_n, v, resident, mine);
-            const int se = (int)tb.recs[wv.qdesc[v] & 0x3fffu].se;
+            const OrlgGnAuditValue r = rmsa_gn_audit_victim(wv, tb, gn, wide, q_n, v, resident, mine, adaptive);
+            // (every service is audited at the threshold of the level it runs at)
+            const int se = orlg_qdesc_se(orlg_qdesc_level(wv.qdesc[v], adaptive), (int)tb.recs[orlg_qdesc_gid(wv.qdesc[v], adaptive)].se);
             const double m = r.gsnr_db - gn[ORLG_GN_THR0 + se - 1];
             if (lane == (v & 63)) {
                 c_g = r.gsnr_db; c_m = m; c_a = r.ase_db; c_n = r.nli_db;
@@ -106,9 +108,10 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK) void orlg_gn_a
 
 // the running services of every environment, decoded as the step decodes them: count, head [B]; the rest [B][Q] in rank order, -1 /
 // NaN past count; any of them may be nullptr.  One thread per (environment, rank); the tables are read where they lie in HBM.
+// se: the spectral efficiency the service runs at -- the level an adaptive handle stored with it (orlg_qdesc.h), else its path's own.
 __global__ __launch_bounds__(256) void orlg_running_services_kernel(const OrlgParams p, int32_t *count, int32_t *head, int32_t *path_gid,
                                                                     int16_t *slot, int16_t *num_slots, int32_t *bit_rate,
-                                                                    double *release_time) {
+                                                                    double *release_time, int16_t *se) {
     const OrlgPathRec *recs = reinterpret_cast<const OrlgPathRec *>(p.tables + p.t_recs);
     const uint16_t *nslots = reinterpret_cast<const uint16_t *>(p.tables + p.t_nslots);
     const int32_t *bit_rates = reinterpret_cast<const int32_t *>(p.tables + p.t_bitrates);
@@ -125,15 +128,17 @@ __global__ __launch_bounds__(256) void orlg_running_services_kernel(const OrlgPa
             if (head) head[env] = h;
         }
         int32_t gid = -1, br = -1;
-        int16_t s = -1, ns = -1;
+        int16_t s = -1, ns = -1, lv = -1;
         double t = ORLG_AUDIT_NAN;
         if (rank < n) {
             int pos = h + rank;
             pos -= pos >= Q ? Q : 0;
             const uint32_t d = p.qdesc[(size_t)env * Q + pos];
-            gid = (int32_t)(d & 0x3fffu);
+            const bool adaptive = p.gn_adaptive != 0;
+            gid = (int32_t)orlg_qdesc_gid(d, adaptive);
             s = (int16_t)((d >> 14) & 0x3ffu);
-            ns = (int16_t)nslots[(d >> 24) * ORLG_NSLOT_STRIDE + recs[gid].se];
+            lv = (int16_t)orlg_qdesc_se(orlg_qdesc_level(d, adaptive), (int)recs[gid].se);
+            ns = (int16_t)nslots[(d >> 24) * ORLG_NSLOT_STRIDE + lv];
             br = bit_rates[d >> 24];
             t = p.qtime[(size_t)env * Q + pos];
         }
@@ -142,6 +147,7 @@ __global__ __launch_bounds__(256) void orlg_running_services_kernel(const OrlgPa
         if (num_slots) num_slots[i] = ns;
         if (bit_rate) bit_rate[i] = br;
         if (release_time) release_time[i] = t;
+        if (se) se[i] = lv;
     }
 }
 

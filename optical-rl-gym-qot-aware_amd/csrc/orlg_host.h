@@ -137,7 +137,7 @@ struct OrlgScratch {
     unsigned char *bytes() const { return static_cast<unsigned char *>(ptr); }
 };
 #define ORLG_IO_SLOTS 16      // >= ORLG_NUM_OUTS, ORLG_PHY_NUM_OUTS
-#define ORLG_EXTRA_SLOTS 6   // a variant's own buffers of that kind (staged actions, the float64 shares)
+#define ORLG_EXTRA_SLOTS 7   // a variant's own buffers of that kind (staged actions, the float64 shares)
 
 // What orlg_env and orlg_phy_env have in common: the device, the stream, the launch geometry of the step kernel, every device
 // allocation, the sticky error word, traffic and trace.  It owns what it holds: deleting a handle waits for its stream and frees

@@ -40,6 +40,7 @@
 #include "orlg_cut.h"          // wave_cut_assign: the fewest-cuts window of the CUT instantiations
 #include "orlg_usage.h"        // wave_window_assign: the rule MOST_USED and the route BEST_WINDOW of the USAGE instantiations
 #include "orlg_gn_max_margin.h"   // wave_max_margin: the whole-spectrum policy section of the MM instantiations
+#include "orlg_rmsa_gn_am.h"      // am_path_levels, rmsa_gn_gsnr_am: the level walk and the level-aware check of the AM instantiations
 #include "orlg_sections.h"
 
 // ---------------------------------------------------------------------------------------- the step kernel
@@ -78,6 +79,13 @@
 // regions, as USAGE's prefix sums do.  Protection is a runtime argument here (OrlgMmArgs::protect), and the second check of SEC(3) runs
 // under it.  The kernel has a name of its own, orlg_rmsa_mm_kernel (the section's registers are the query's, not the step's), and its
 // instantiations a unit of their own, orlg_inst_gnmm.hip.
+// AM (with GN, without ASSIGN, PROTECT, MM and CAUSE): the handle's gate chooses the modulation from the GSNR (orlg_set_gn_modulation,
+// DESIGN 2.33) -- every launch of such a handle runs these instantiations, because every reader of a descriptor must know the level it
+// may carry (orlg_qdesc.h): the release, and the check's decode of the running services (rmsa_gn_gsnr_am in rmsa_gn_gsnr's place).
+// The policies ORLG_POLICY_SP_AM .. EXT_AM (orlg_step_modulation) walk the levels of a path in the policy section, checks included
+// (am_path_levels); SEC(3) then provisions what was admitted or shows the first candidate that was checked.  Every other policy
+// proposes and is checked as on a plain gated handle, at the path's own spectral efficiency (level 0).  The kernel has a name of its
+// own, orlg_rmsa_am_kernel, and its instantiations a unit of their own, orlg_inst_gnam.hip.
 template <bool GN>
 struct SapRetry {
     int from = 0, path = 0, slot = 0;
@@ -90,8 +98,8 @@ struct SapRetry<false> {
 };
 
 template <int W, int STATS, bool STEPK, bool FF = false, bool DEFER = false, bool GN = false, bool CAUSE = false, bool ASSIGN = false, bool CUT = false,
-          bool USAGE = false, bool PROTECT = false, bool MM = false>
-DEV void rmsa_body(const OrlgParams &p, [[maybe_unused]] const OrlgMmArgs *mm = nullptr) {
+          bool USAGE = false, bool PROTECT = false, bool MM = false, bool AM = false>
+DEV void rmsa_body(const OrlgParams &p, [[maybe_unused]] const OrlgMmArgs *mm = nullptr, [[maybe_unused]] const OrlgAmArgs *am = nullptr) {
     extern __shared__ __align__(16) unsigned char smem[];
 #ifdef ORLG_SHAPE_ASSUME
     ORLG_SHAPE_ASSUME  // experiment (tools/shape_experiment.py): shape and layout fields as compile-time constants
@@ -258,6 +266,59 @@ DEV void rmsa_body(const OrlgParams &p, [[maybe_unused]] const OrlgMmArgs *mm = 
             int a_path = K, a_slot = S;  // rejection (rmsa_env.py:871,913)
             const int policy = p.policy;
             [[maybe_unused]] double mm_w = __longlong_as_double(0x7ff8000000000000ll);   // MM: the w of the proposed window
+            // AM: the level of the candidate the step shows (0: the path's own, no level chosen), the policy section ran the checks
+            // itself, and then what they said: admitted, and the GSNR compared (NaN = no candidate had a window)
+            [[maybe_unused]] int am_se = 0;
+            [[maybe_unused]] bool am_checked = false, am_ok = false;
+            [[maybe_unused]] double am_gsnr = __longlong_as_double(0x7ff8000000000000ll);
+            [[maybe_unused]] OrlgAmEntry am_first = {};   // AM: the ring's first 64 entries as interferers, decoded once per step
+            if constexpr (AM) {
+                if (q_n > 0) am_first = am_ring_entry(wv, tb, ORLG_GPTR(const double, p.gn), E, Q, q_head, q_n, 0);
+            }
+            if constexpr (AM) {
+                if (policy == ORLG_POLICY_EXT_AM) {
+                    // the agent's (path, slot, level): `external` with n = n_level; a level outside 1..M is an action out of range
+                    const int32_t *acts = kernarg_params()->actions;
+                    a_path = uni(acts[3 * env]);
+                    a_slot = uni(acts[3 * env + 1]);
+                    const int lv = uni(acts[3 * env + 2]);
+                    am_checked = true;
+                    if (lv >= 1 && lv <= p.gn_adaptive && a_path >= 0 && a_path < K && a_slot >= 0 && a_slot < S) {
+                        u64 x[W];
+#pragma unroll
+                        for (int w = 0; w < W; ++w) x[w] = readlane64(acc, a_path * LS + w);
+                        const int n = uni((int)tb.nslots[req_br * ORLG_NSLOT_STRIDE + lv]);
+                        if (window_free<W>(x, a_slot, n, S)) {
+                            const OrlgGnTable gn = ORLG_GPTR(const double, p.gn);
+                            am_se = lv;
+                            am_gsnr = rmsa_gn_gsnr_am(wv, tb, gn, E, Q, q_head, q_n, tb.recs + (base + a_path), a_slot, n, am_first);
+                            am_ok = uni((int)(am_gsnr >= gn[ORLG_GN_THR0 + lv - 1])) != 0;
+                        }
+                    }
+                } else if (policy >= ORLG_POLICY_SP_AM) {
+                    // sp_ff_am / sap_ff_am / path_am_external: the paths in scope in order, each with its levels M down to 1; the first
+                    // admitted candidate is the proposal, else the first candidate that was checked, else the rejection
+                    int lo = 0, hi = policy == ORLG_POLICY_SP_AM ? 1 : K;
+                    if (policy == ORLG_POLICY_PATH_AM_EXT) {
+                        lo = uni(kernarg_params()->actions[env]);
+                        hi = lo >= 0 && lo < K ? lo + 1 : lo;
+                    }
+                    am_checked = true;
+                    const OrlgGnTable gn = ORLG_GPTR(const double, p.gn);
+                    for (int idp = lo; idp < hi; ++idp) {
+                        u64 x[W];
+#pragma unroll
+                        for (int w = 0; w < W; ++w) x[w] = readlane64(acc, idp * LS + w);
+                        const OrlgAmPath r = am_path_levels<W>(wv, tb, gn, E, Q, q_head, q_n, am_first, tb.recs + (base + idp), x, req_br,
+                                                               p.gn_adaptive, S);
+                        if (r.se) {
+                            a_path = idp; a_slot = r.slot; am_se = r.se; am_gsnr = r.gsnr; am_ok = true;
+                            break;
+                        }
+                        if (r.f_se && !am_se) { a_path = idp; a_slot = r.f_slot; am_se = r.f_se; am_gsnr = r.f_gsnr; }
+                    }
+                }
+            }
             if constexpr (MM) {
                 const int given = policy == ORLG_POLICY_PATH_EXT ? uni(kernarg_params()->actions[env]) : 0;
                 uint32_t *cidx = reinterpret_cast<uint32_t *>(smem + p.l_shared_bytes + (size_t)(blockDim.x >> 6) * p.l_wave_bytes +
@@ -284,6 +345,7 @@ DEV void rmsa_body(const OrlgParams &p, [[maybe_unused]] const OrlgMmArgs *mm = 
                                                 tb, base, K, E, S, req_br, lane, policy, kq->assign, given);
                 else got = wave_assign<W>(wv.occ, tb, base + first, K - first, S, req_br, lane, route, kq->assign, given);
                 if (got >= 0) { a_path = (got >> 10) + first; a_slot = got & 1023; }
+            } else if (AM && am_checked) {   // (the section above has proposed)
             } else if (FF) {
                 const int kmax = policy == ORLG_POLICY_SP ? 1 : K;
                 const bool on = pp < kmax && pw < W;
@@ -376,7 +438,10 @@ DEV void rmsa_body(const OrlgParams &p, [[maybe_unused]] const OrlgMmArgs *mm = 
                 if (sap.exhausted) { a_path = sap.path; a_slot = sap.slot; }
             }
             if (a_path >= 0 && a_path < K && a_slot >= 0 && a_slot < S) {
-                const int n = __builtin_amdgcn_readlane(my_n, a_path);
+                int n = __builtin_amdgcn_readlane(my_n, a_path);
+                if constexpr (AM) {   // (a candidate at a level of its own)
+                    if (am_se) n = uni((int)tb.nslots[req_br * ORLG_NSLOT_STRIDE + am_se]);
+                }
                 // the device policies only propose windows they found free; agent actions are checked (is_path_free)
                 bool window_ok = true;
                 if (!FF && !ASSIGN && !MM && (policy == ORLG_POLICY_EXT || policy == ORLG_POLICY_PATH_EXT || policy == ORLG_POLICY_DEEP_EXT)) {
@@ -390,10 +455,14 @@ DEV void rmsa_body(const OrlgParams &p, [[maybe_unused]] const OrlgMmArgs *mm = 
                         gn_gsnr = sap.gsnr;
                         if constexpr (PROTECT) gn_margin = sap.margin;
                         window_ok = false;
+                    } else if (AM && am_checked) {   // the level walk has checked: its verdict and the GSNR it compared
+                        gn_gsnr = am_gsnr;
+                        window_ok = am_ok;
                     } else if (window_ok) {
                         const OrlgGnTable gn = ORLG_GPTR(const double, p.gn);
                         const OrlgPathRec *cand = tb.recs + (base + a_path);
-                        gn_gsnr = rmsa_gn_gsnr(wv, tb, gn, E, Q, q_head, q_n, cand, a_slot, n);
+                        if constexpr (AM) gn_gsnr = rmsa_gn_gsnr_am(wv, tb, gn, E, Q, q_head, q_n, cand, a_slot, n, am_first);
+                        else gn_gsnr = rmsa_gn_gsnr(wv, tb, gn, E, Q, q_head, q_n, cand, a_slot, n);
                         window_ok = gn_gsnr >= gn[ORLG_GN_THR0 + (int)cand->se - 1];
                         // PROTECT: the running services that share a link with the candidate, each with the candidate lit; no
                         // such service: NaN, which refuses nothing
@@ -476,7 +545,8 @@ DEV void rmsa_body(const OrlgParams &p, [[maybe_unused]] const OrlgMmArgs *mm = 
                         pr -= pr >= Q ? Q : 0;
                         if (lane == 0) {
                             wv.qtime[pr] = rel;
-                            wv.qdesc[pr] = (uint32_t)gid | ((uint32_t)a_slot << 14) | ((uint32_t)req_br << 24);
+                            if constexpr (AM) wv.qdesc[pr] = orlg_qdesc_make(gid, am_se, a_slot, req_br);
+                            else wv.qdesc[pr] = (uint32_t)gid | ((uint32_t)a_slot << 14) | ((uint32_t)req_br << 24);
                         }
                         q_n += 1;
                         if (r == 0) next_rel = rel;
@@ -534,6 +604,9 @@ DEV void rmsa_body(const OrlgParams &p, [[maybe_unused]] const OrlgMmArgs *mm = 
                 KernargParams kq = kernarg_params();
                 if (lane == 0 && kq->o_cause) ORLG_GPTR(uint8_t, kq->o_cause)[(size_t)t * p.B + env] = (uint8_t)cause;
                 cause_cnt += lane == cause ? 1 : 0;
+            }
+            if constexpr (AM) {   // gn_se: the level of the candidate whose GSNR the step shows, 0 where no check ran or none chose a level
+                if (lane == 0 && am->o_se) am->o_se[(size_t)t * p.B + env] = (uint8_t)(gn_gsnr == gn_gsnr ? am_se : 0);
             }
             if constexpr (GN) sap.from = 0;
             new_service = 0;
@@ -625,9 +698,13 @@ DEV void rmsa_body(const OrlgParams &p, [[maybe_unused]] const OrlgMmArgs *mm = 
                 SEC(10);  // release apply
                 // ---- _release_path (rmsa_env.py:515-535)
                 const uint32_t d = (uint32_t)uni((int)wv.qdesc[q_head]);
-                const int gid = (int)(d & 0x3fff), s0 = (int)((d >> 14) & 0x3ff), bri2 = (int)(d >> 24);
+                int gid = (int)(d & 0x3fff);
+                const int s0 = (int)((d >> 14) & 0x3ff), bri2 = (int)(d >> 24);
+                if constexpr (AM) gid = orlg_qdesc_gid(d, true);
                 const OrlgPathRec *rec = tb.recs + gid;
-                const int hops = rec->hops, se = rec->se;
+                const int hops = rec->hops;
+                int se = rec->se;
+                if constexpr (AM) se = orlg_qdesc_se(orlg_qdesc_level(d, true), se);   // (the slots it took were its level's)
                 const int n = tb.nslots[bri2 * ORLG_NSLOT_STRIDE + se];
                 if (lane == 0) {
                     wv.qtime[q_head] = __longlong_as_double((long long)ORLG_INF_BITS);
@@ -737,6 +814,13 @@ __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_r
 template <int W, int STATS, bool CAUSE = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK) void orlg_rmsa_mm_kernel(const OrlgParams p, const OrlgMmArgs m) {
     rmsa_body<W, STATS, true, false, false, true, CAUSE, false, false, false, false, true>(p, &m);
+}
+// the gated step kernel of a handle whose gate chooses the modulation (orlg_set_gn_modulation): eight waves per workgroup, two per
+// SIMD, as orlg_rmsa_mm_kernel -- the level walk keeps the ring's first 64 entries decoded (14 registers) next to the step's own state,
+// and the plain gated kernels already spill at 128 registers
+template <int W, int STATS>
+__global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK) void orlg_rmsa_am_kernel(const OrlgParams p, const OrlgAmArgs a) {
+    rmsa_body<W, STATS, true, false, false, true, false, false, false, false, false, false, true>(p, nullptr, &a);
 }
 template <int W, int STATS, bool DEFER = false>
 __global__ __launch_bounds__(ORLG_WAVE *ORLG_MAX_WAVES_PER_BLOCK, 4) void orlg_rmsa_kernel_ff(const OrlgParams p) {

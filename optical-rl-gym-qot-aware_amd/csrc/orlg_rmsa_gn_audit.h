@@ -9,6 +9,7 @@
 // 14-step link mask, bandwidth, centre and phi_mod -- is a value (OrlgGnAuditEntry) the caller may keep in registers across the
 // whole victim loop where the ring fits one chunk of 64 lanes, and re-decodes per chunk only above that.
 #pragma once
+#include "orlg_qdesc.h"             // a descriptor of an adaptive handle carries the level its service runs at
 #include "orlg_rmsa_gn_protect.h"   // rmsa_gn_link_mask, rmsa_gn_phi_mod
 
 // one ring entry as an interferer: bandwidth, centre frequency, phi_mod of its modulation, the links of its path
@@ -22,11 +23,12 @@ struct OrlgGnAuditValue {
     double gsnr_db, ase_db, nli_db;
 };
 
-// entry `d` decoded as the step decodes it (orlg_rmsa_gn.h)
-DEV OrlgGnAuditEntry rmsa_gn_audit_decode(const Tab &tb, OrlgGnTable gn, uint32_t d, bool wide) {
+// entry `d` decoded as the step decodes it (orlg_rmsa_gn.h; adaptive: the handle's mode, OrlgParams::gn_adaptive != 0 -- orlg_qdesc.h)
+DEV OrlgGnAuditEntry rmsa_gn_audit_decode(const Tab &tb, OrlgGnTable gn, uint32_t d, bool wide, bool adaptive) {
     const double f0 = gn[ORLG_GN_F0], slot = gn[ORLG_GN_SLOT];
-    const OrlgPathRec ri = tb.recs[d & 0x3fffu];
-    const int s_i = (int)((d >> 14) & 0x3ffu), n_i = (int)tb.nslots[(d >> 24) * ORLG_NSLOT_STRIDE + ri.se];
+    const OrlgPathRec ri = tb.recs[orlg_qdesc_gid(d, adaptive)];
+    const int se_i = orlg_qdesc_se(orlg_qdesc_level(d, adaptive), (int)ri.se);
+    const int s_i = (int)((d >> 14) & 0x3ffu), n_i = (int)tb.nslots[(d >> 24) * ORLG_NSLOT_STRIDE + se_i];
     u64 m0, m1, m2, m3;
     // (a constant `wide` per call: with the flag left to its unrolled loop the compiler keeps two of the words in scratch)
     if (wide) rmsa_gn_link_mask(ri, true, m0, m1, m2, m3);
@@ -35,7 +37,7 @@ DEV OrlgGnAuditEntry rmsa_gn_audit_decode(const Tab &tb, OrlgGnTable gn, uint32_
     e.m0 = m0; e.m1 = m1; e.m2 = m2; e.m3 = m3;
     e.sb = (double)n_i * slot;
     e.sf = f0 + ((double)s_i + 0.5 * (double)n_i) * slot;
-    e.pm = rmsa_gn_phi_mod((int)ri.se);
+    e.pm = rmsa_gn_phi_mod(se_i);
     return e;
 }
 
@@ -44,14 +46,15 @@ DEV OrlgGnAuditEntry rmsa_gn_audit_decode(const Tab &tb, OrlgGnTable gn, uint32_
 // (rmsa_gn_victim_gsnr's shape and order); the ASE and NLI shares ride along in the span loop.  `resident`: q_n <= 64 and `mine` is
 // the decode of entry `lane` (any value on the lanes past q_n); otherwise every chunk is decoded here.  Wave-uniform result.
 DEV OrlgGnAuditValue rmsa_gn_audit_victim(const Wave &wv, const Tab &tb, OrlgGnTable gn, bool wide, int q_n, int v, bool resident,
-                                          const OrlgGnAuditEntry &mine) {
+                                          const OrlgGnAuditEntry &mine, bool adaptive) {
     const double beta_2 = -21.3e-27, gamma = 1.3e-3, h_plank = 6.626e-34, pi = 3.141592653589793;
     const int lane = wv.lane;
     const double density = gn[ORLG_GN_DENSITY], f0 = gn[ORLG_GN_F0], slot = gn[ORLG_GN_SLOT], att = gn[ORLG_GN_ATT];
     const double nf = gn[ORLG_GN_NF], l_eff_a = gn[ORLG_GN_LEFF_A];
     const uint32_t dv = wv.qdesc[v];
-    const OrlgPathRec *rec = tb.recs + (dv & 0x3fffu);
-    const int s = (int)((dv >> 14) & 0x3ffu), n = (int)tb.nslots[(dv >> 24) * ORLG_NSLOT_STRIDE + rec->se];
+    const OrlgPathRec *rec = tb.recs + orlg_qdesc_gid(dv, adaptive);
+    const int se_v = orlg_qdesc_se(orlg_qdesc_level(dv, adaptive), (int)rec->se);
+    const int s = (int)((dv >> 14) & 0x3ffu), n = (int)tb.nslots[(dv >> 24) * ORLG_NSLOT_STRIDE + se_v];
     const int hops = rec->hops;
     const int my_link = (int)rec->link[lane < hops ? lane : 0];   // lane h = hop h of the victim
     const double lk_leff = gn[ORLG_GN_LINK0 + 4 * my_link], lk_ratio = gn[ORLG_GN_LINK0 + 4 * my_link + 1];
@@ -62,7 +65,7 @@ DEV OrlgGnAuditValue rmsa_gn_audit_victim(const Wave &wv, const Tab &tb, OrlgGnT
     for (int j0 = 0; j0 < q_n; j0 += 64) {
         const bool valid = j0 + lane < q_n && j0 + lane != v;
         OrlgGnAuditEntry e = mine;
-        if (!resident) e = rmsa_gn_audit_decode(tb, gn, wv.qdesc[j0 + lane < q_n ? j0 + lane : 0], wide);
+        if (!resident) e = rmsa_gn_audit_decode(tb, gn, wv.qdesc[j0 + lane < q_n ? j0 + lane : 0], wide, adaptive);
         const double df = valid ? e.sf - fc : slot;   // (windows on a shared link are disjoint: df != 0 where it is used)
         const double A = asinh(pi * pi * fabs(beta_2) * l_eff_a * e.sb * (df + (e.sb / 2))) -
                          asinh(pi * pi * fabs(beta_2) * l_eff_a * e.sb * (df - (e.sb / 2)));

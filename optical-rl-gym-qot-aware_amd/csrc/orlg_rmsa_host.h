@@ -2,7 +2,7 @@
 // buffers and the two functions that cross units.
 //   orlg_api.hip        the helper kernels, create, reset, reseed, the getters and reductions, checkpoint / resume, the debug exports
 //   orlg_api_step.hip   launch_rmsa and the group kernel's launch, rmsa_step and the orlg_step* entries, orlg_launch_info, the gate:
-//                       gn_gate_table, orlg_set_gn_gate, orlg_set_gn_protect
+//                       gn_gate_table, orlg_set_gn_gate, orlg_set_gn_protect, orlg_set_gn_modulation with orlg_step_modulation
 //   orlg_api_query.hip  what reads the state with a kernel of orlg_query_kernels.hip, orlg_mask_kernels.hip or the orlg_gn_*_kernels:
 //                       path masks, the DeepRMSA observation, action masks, fit levels, cuts, usage, the GN masks and windows, the
 //                       running services and their audit -- with the output slots of a query and the queries' one launch
@@ -29,9 +29,11 @@ struct orlg_env : OrlgHandle {
     bool gn_protect = false;        // the gate also protects the running lightpaths (orlg_set_gn_protect; configuration, not state)
     double *audit_table = nullptr;  // the table of a gate given with orlg_gn_audit (allocated with the first such call; never OrlgParams::gn)
     int mm_resident[3][2] = {};     // workgroups of orlg_rmsa_mm_kernel the device keeps resident, by statistics level and CAUSE (0 = not asked yet)
+    int gn_num_thresholds = 0;      // num_thresholds of the gate in force: the levels a gate that chooses the modulation has (orlg_set_gn_modulation)
+    int am_resident[3] = {};       // ... of orlg_rmsa_am_kernel, by statistics level (the gate's mode itself is OrlgParams::gn_adaptive)
 };
-enum { X_ACTIONS, X_GSNR, X_CAUSE, X_CAUSE_COUNTS, X_MARGIN, X_WINDOW_MARGIN };   // OrlgHandle::extra: external actions from / the gn_gsnr_db, block_cause, cause_counts, gn_neighbour_margin_db and gn_window_margin_db outputs for host memory
-static_assert(X_WINDOW_MARGIN < ORLG_EXTRA_SLOTS, "OrlgHandle::extra");
+enum { X_ACTIONS, X_GSNR, X_CAUSE, X_CAUSE_COUNTS, X_MARGIN, X_WINDOW_MARGIN, X_SE };   // OrlgHandle::extra: external actions from / the gn_gsnr_db, block_cause, cause_counts, gn_neighbour_margin_db and gn_window_margin_db outputs for host memory
+static_assert(X_SE < ORLG_EXTRA_SLOTS, "OrlgHandle::extra");   // (X_SE: the gn_se output of orlg_step_modulation)
 
 #define SYNC_CHECK(e) do { int rc_ = orlg_handle_sync_check(e); if (rc_) return rc_; } while (0)
 
@@ -41,3 +43,7 @@ int launch_rmsa(orlg_env *e, const OrlgParams &p);
 // the rules of a gate and its table (ORLG_GN_*, orlg_device.h) for this handle's topology: what orlg_set_gn_gate installs and what
 // orlg_gn_audit builds for a gate given with the call
 int gn_gate_table(const orlg_env *e, const orlg_rmsa_gn_gate *g, std::vector<double> &tab);
+// 1 where a descriptor of `qdesc` (B * Q words, host or device memory: a state blob's part or the handle's own array) names no path
+// record of the handle -- what the level of an adaptive handle's service looks like to a handle that is not (orlg_qdesc.h); 0 where
+// none does; a negative error code
+int rmsa_state_has_levels(orlg_env *e, const void *qdesc);

@@ -16,6 +16,7 @@
 #include "orlg_inst_gnadmit.hip"
 #include "orlg_inst_gnslots.hip"
 #include "orlg_inst_gnmm.hip"
+#include "orlg_inst_gnam.hip"
 #include "orlg_gn_audit_kernels.hip"
 #include "orlg_inst_group.hip"
 #include "orlg_inst_phy.hip"

@@ -234,7 +234,7 @@ typedef void (*orlg_gn_admission_windows_kernel_t)(const OrlgParams, int, int16_
 typedef void (*orlg_phy_kernel_t)(const OrlgPhyParams);
 // orlg_gn_audit_kernels.hip: the two kernels of the audit know no word count -- one object, one lookup each, no W
 typedef void (*orlg_gn_audit_kernel_t)(const OrlgParams, const double *, orlg_gn_audit_summary *, double *, double *, double *, double *);
-typedef void (*orlg_running_services_kernel_t)(const OrlgParams, int32_t *, int32_t *, int32_t *, int16_t *, int16_t *, int32_t *, double *);
+typedef void (*orlg_running_services_kernel_t)(const OrlgParams, int32_t *, int32_t *, int32_t *, int16_t *, int16_t *, int32_t *, double *, int16_t *);
 orlg_gn_audit_kernel_t orlg_gn_audit_kernel_lookup();
 orlg_running_services_kernel_t orlg_running_services_kernel_lookup();
 #define ORLG_FOR_EACH_W(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__) X(6, __VA_ARGS__) X(8, __VA_ARGS__)
@@ -285,6 +285,27 @@ typedef void (*orlg_rmsa_mm_kernel_t)(const OrlgParams, const OrlgMmArgs);
 #define ORLG_DECL_GN_MM_W(n, ...) orlg_rmsa_mm_kernel_t orlg_gnmm_kernel_W##n(OrlgMmKey) __attribute__((weak));
 ORLG_FOR_EACH_W(ORLG_DECL_GN_MM_W, )
 #undef ORLG_DECL_GN_MM_W
+// orlg_rmsa_am_kernel (orlg_kernels.hip): the gated step kernel of a handle whose gate chooses the modulation from the GSNR
+// (orlg_set_gn_modulation) -- template <int W, int STATS>, a kernel name, a key, a key list, a unit (orlg_inst_gnam.hip,
+// one object per W, which also holds the modulation query orlg_gn_modulation_kernel) and a declaration list of its own, behind the
+// ones above: they stay what they are.  X(STATS): per statistics level
+struct OrlgAmKey { int STATS; };
+inline bool operator==(const OrlgAmKey &a, const OrlgAmKey &b) { return a.STATS == b.STATS; }
+#define ORLG_WAVE_GN_AM_KEYS(X) X(1) X(2) X(0)
+#define ORLG_AM_KEY_ENTRY(...) OrlgAmKey{__VA_ARGS__},
+inline constexpr OrlgAmKey ORLG_WAVE_GN_AM_KEY_LIST[] = {ORLG_WAVE_GN_AM_KEYS(ORLG_AM_KEY_ENTRY)};
+inline void orlg_kernel_name(char *buf, size_t cap, int W, const OrlgAmKey &k) {
+    const OrlgArg args[] = {{k.STATS, 'i'}};
+    orlg_format_kernel(buf, cap, "orlg_rmsa_am_kernel", W, args, 1);
+}
+struct OrlgAmArgs;
+typedef void (*orlg_rmsa_am_kernel_t)(const OrlgParams, const OrlgAmArgs);
+typedef void (*orlg_gn_modulation_kernel_t)(const OrlgParams, int16_t *, double *, uint8_t *, uint8_t *);   // orlg_gn_modulation_kernel
+#define ORLG_DECL_GN_AM_W(n, ...)                                                    \
+    orlg_rmsa_am_kernel_t orlg_gnam_kernel_W##n(OrlgAmKey) __attribute__((weak)); \
+    orlg_gn_modulation_kernel_t orlg_gn_modulation_kernel_W##n() __attribute__((weak));
+ORLG_FOR_EACH_W(ORLG_DECL_GN_AM_W, )
+#undef ORLG_DECL_GN_AM_W
 
 // the lookup `lookup`<W> called with the arguments after it, as a function body: null when the library holds no such W
 #define ORLG_PICK_CASE(n, lookup, ...) case n: return lookup##n ? lookup##n(__VA_ARGS__) : nullptr;
@@ -312,3 +333,5 @@ static orlg_gn_admission_masks_kernel_t orlg_pick_gn_admission_masks(int W) { OR
 static orlg_gn_admission_windows_kernel_t orlg_pick_gn_admission_windows(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_admission_windows_kernel_W, ) }
 static orlg_gn_slots_kernel_t orlg_pick_gn_slots(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_slots_kernel_W, ) }
 static orlg_rmsa_mm_kernel_t orlg_pick_gn_mm(int W, const OrlgMmKey &key) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gnmm_kernel_W, key) }
+static orlg_rmsa_am_kernel_t orlg_pick_gn_am(int W, const OrlgAmKey &key) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gnam_kernel_W, key) }
+static orlg_gn_modulation_kernel_t orlg_pick_gn_modulation(int W) { ORLG_PICK(ORLG_FOR_EACH_W, W, orlg_gn_modulation_kernel_W, ) }

@@ -241,10 +241,11 @@ class RMSAEnv(_View):
         return np.unpackbits(m.view(np.uint8), bitorder="little")[:self.num_spectrum_resources].astype(np.int64)
 
     # ------------------------------------------------------------------ reference query surface
-    def get_number_slots(self, path: Path) -> int:
-        """``rmsa_env.py:708-719`` (plain arithmetic on the pending request)."""
-        return math.ceil(self.current_service.bit_rate /
-                         (path.best_modulation.spectral_efficiency * self.channel_width)) + 1
+    def get_number_slots(self, path: Path, se=None) -> int:
+        """``rmsa_env.py:708-719`` (plain arithmetic on the pending request).  ``se``: a spectral efficiency in the place of the
+        path's own -- the level of a candidate behind a gate that chooses the modulation (not in the reference)."""
+        se = path.best_modulation.spectral_efficiency if se is None else int(se)
+        return math.ceil(self.current_service.bit_rate / (se * self.channel_width)) + 1
 
     def is_path_free(self, path: Path, initial_slot: int, number_slots: int) -> bool:
         """``rmsa_env.py:721-734``"""
@@ -341,8 +342,18 @@ class RMSAEnv(_View):
         """(path, initial_slot) as RMSAEnv.step sees them"""
         return int(action[0]), int(action[1])
 
+    @staticmethod
+    def _action_level(action):
+        """the se of a (path, slot, se) action, None for every other action (DeepRMSA's and the path-only space's are one integer)"""
+        return int(action[2]) if np.ndim(action) == 1 and len(action) == 3 else None
+
     def _device_step(self, action):
         path, initial_slot = int(action[0]), int(action[1])
+        if self._action_level(action) is not None:   # (path, slot, se) behind a gate that chooses the modulation (DESIGN 2.33): the device checks the rest
+            return self._batched.run("external_am", 1, actions=np.array([[path, initial_slot, int(action[2])]], np.int32),
+                                     outputs=("accepted", "done", "reward", "network_compactness",
+                                              "network_compactness_difference", "avg_link_compactness",
+                                              "avg_link_utilization", "gn_gsnr_db", "gn_se"))
         return self._batched.run("external", 1, actions=np.array([[path, initial_slot]], np.int32),
                                  outputs=("accepted", "done", "reward", "network_compactness",
                                           "network_compactness_difference", "avg_link_compactness",
@@ -368,13 +379,16 @@ class RMSAEnv(_View):
         if served.accepted:
             self.actions_taken[path, initial_slot] += 1
             if self.bit_rate_selection == "discrete":
-                self.slots_provisioned_histogram[self.get_number_slots(candidates[path])] += 2
+                se = self._action_level(action)   # (a level of its own: the slots it took are the level's)
+                self.slots_provisioned_histogram[self.get_number_slots(candidates[path], se)] += 2
         else:
             self.actions_taken[self.k_paths, self.num_spectrum_resources] += 1
         info = self._info(float(r["network_compactness"][0, 0]), float(r["network_compactness_difference"][0, 0]),
                           float(r["avg_link_compactness"][0, 0]), float(r["avg_link_utilization"][0, 0]))
         if "gn_gsnr_db" in r:   # (a handle with a GN-model admission check: the GSNR it compared, NaN = no check ran)
             info["gn_gsnr_db"] = float(r["gn_gsnr_db"][0, 0])
+        if "gn_se" in r:   # (... that chooses the modulation: the level of the candidate it checked, 0 = no check ran)
+            info["gn_se"] = int(r["gn_se"][0, 0])
         if "gn_neighbour_margin_db" in r:   # (... that protects its running lightpaths: the neighbour margin, NaN = that check did not run)
             info["gn_neighbour_margin_db"] = float(r["gn_neighbour_margin_db"][0, 0])
         reward = r["reward"][0, 0]
@@ -594,6 +608,34 @@ def shortest_available_path_first_fit_gn(env: RMSAEnv) -> Tuple[int, int]:
         if env.is_path_free(path, s, n):
             return (idp, s)
     return (k, S)
+
+
+def adaptive_modulation_heuristic(route):
+    """A callback ``f(env) -> (path, slot, se)`` for an environment whose gate chooses the modulation
+    (``gn_gate=rmsa_gn_gate_parameters(..., modulation="adaptive")``; not in the reference): what the device policies
+    ``"sp_ff_am"`` (``route="sp"``) and ``"sap_ff_am"`` (``"sap"``) propose, read from ``BatchedRMSAEnv.modulation_windows``.  The
+    paths in scope in order, each with its levels ``M`` down to 1: the first admitted candidate; if none is admitted, the first
+    candidate that has a window -- the step then refuses it; if none has one, ``(k, S, 0)``, the rejection."""
+    if route not in ("sp", "sap"):
+        raise ValueError(f"route {route!r}: expected 'sp' or 'sap'")
+
+    def heuristic(env):
+        S, k = env.topology.graph["num_spectrum_resources"], env.topology.graph["k_paths"]
+        slot, _, admitted, _ = env._batched.modulation_windows()
+        slot, admitted = slot[env._index], admitted[env._index]
+        first = None
+        for idp in range(1 if route == "sp" else k):
+            for m in range(slot.shape[1], 0, -1):
+                if slot[idp, m - 1] >= S:
+                    break
+                if admitted[idp, m - 1]:
+                    return (idp, int(slot[idp, m - 1]), m)
+                if first is None:
+                    first = (idp, int(slot[idp, m - 1]), m)
+        return first if first is not None else (k, S, 0)
+
+    heuristic.__name__ = f"{route}_adaptive_modulation"
+    return heuristic
 
 
 MAX_MARGIN_ROUTES = ("sap", "any")

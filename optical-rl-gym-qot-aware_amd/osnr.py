@@ -134,7 +134,8 @@ def gn_gate_parameters(topology, num_channels=268, *, launch_power_dbm=0.0, chan
 
 
 def rmsa_gn_gate_parameters(topology, *, launch_power_dbm_per_50ghz=0.0, frequency_start_hz=191.7e12, channel_width=12.5,
-                            max_span_length_km=80.0, attenuation_db_km=0.2, noise_figure_db=4.5, thresholds_db=None, protect_running=False):
+                            max_span_length_km=80.0, attenuation_db_km=0.2, noise_figure_db=4.5, thresholds_db=None, protect_running=False,
+                            modulation="path"):
     """Parameters of the GN-model admission check of ``BatchedRMSAEnv(..., gn_gate=...)`` / ``BatchedDeepRMSAEnv``
     (``include/orlg.h`` ``orlg_rmsa_gn_gate``): a plain dict of numbers / arrays.
 
@@ -146,7 +147,13 @@ def rmsa_gn_gate_parameters(topology, *, launch_power_dbm_per_50ghz=0.0, frequen
     * ``protect_running=True`` adds the key ``"protect_running"``: the gate also refuses a candidate that would push a running
       lightpath on a shared link below the threshold of its modulation (``orlg_set_gn_protect``).  Without it the
       dict has exactly the eight keys above.
+    * ``modulation="adaptive"`` adds the key ``"modulation"``: the gate reads ``thresholds_db`` as the reference's ``modulation_level``
+      table reads a GSNR -- level ``m`` = spectral efficiency ``m`` needs ``thresholds_db[m - 1]`` -- and the policies of
+      ``ADAPTIVE_POLICIES`` run a service at the highest level its GSNR meets (``orlg_set_gn_modulation``).  The
+      default ``"path"``: every service runs at its path's reach-table spectral efficiency, and the dict has no such key.
     """
+    if modulation not in ("path", "adaptive"):
+        raise ValueError(f"modulation {modulation!r}: expected 'path' or 'adaptive'")
     from .topology import FrozenTopology
     t = FrozenTopology.from_graph(topology)
     lengths = np.array([float(e[4]) for e in t.edges], np.float64)[np.argsort([int(e[2]) for e in t.edges])]
@@ -164,6 +171,8 @@ def rmsa_gn_gate_parameters(topology, *, launch_power_dbm_per_50ghz=0.0, frequen
     }
     if protect_running:
         g["protect_running"] = True
+    if modulation == "adaptive":
+        g["modulation"] = "adaptive"
     return g
 
 
@@ -197,4 +206,19 @@ def check_rmsa_gn_gate(gate, topology, step_kernel="auto"):
         raise ValueError(f"gn_gate: a path has spectral efficiency {se_max}, thresholds_db has {thr.size} entries")
     if gate.get("protect_running"):   # (carried only when asked for)
         g["protect_running"] = True
+    mode = gate.get("modulation", "path")
+    if mode not in ("path", "adaptive"):
+        raise ValueError(f"gn_gate: modulation {mode!r}: expected 'path' or 'adaptive'")
+    if mode == "adaptive":   # the rules of orlg_set_gn_modulation
+        from ._lib import MAX_ADAPTIVE_PATHS, MAX_MODULATION_LEVELS
+        if g.get("protect_running"):
+            raise ValueError("gn_gate: modulation='adaptive' with protect_running: the modulation is not chosen behind the check of the "
+                             "running lightpaths yet")
+        if thr.size > MAX_MODULATION_LEVELS:
+            raise ValueError(f"gn_gate: modulation='adaptive' with {thr.size} thresholds: the levels are spectral efficiencies "
+                             f"1..{MAX_MODULATION_LEVELS}, where the modulation factors of the GN model end")
+        if t.num_paths >= MAX_ADAPTIVE_PATHS:
+            raise ValueError(f"gn_gate: modulation='adaptive' on a topology with {t.num_paths} path records: a service's level takes 3 "
+                             f"bits of its descriptor's path field, which leaves room for {MAX_ADAPTIVE_PATHS - 1}")
+        g["modulation"] = "adaptive"
     return g

@@ -1,0 +1,234 @@
+"""Adaptive modulation behind the GN gate (``include/orlg.h`` ``orlg_set_gn_modulation``, ``orlg_step_modulation``,
+``orlg_gn_modulation_windows``) without a GPU: the symbols, the unit and the names of its kernels, every refusal before
+the library is called, the descriptor's decode, and -- from the reference alone, every case of ``test_gpu_gn_modulation.py`` stepped by
+its own choices -- what those cases exercise."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import gn_gate_reference as ref
+import gn_modulation_reference as am
+from conftest import ROOT, load_topology, oracle_env_from_kwargs
+from gpu_support import device_log_in_oracle
+from optical_rl_gym_amd import BatchedDeepRMSAEnv, BatchedRMSAEnv, _lib, rmsa_gn_gate_parameters
+
+NEW = ("orlg_set_gn_modulation", "orlg_step_modulation", "orlg_gn_modulation_windows", "orlg_get_running_services_se")
+
+
+# ---------------------------------------------------------------------------------------- the entry points and their unit
+def test_prototypes_exports_and_abi():
+    import optical_rl_gym_amd as orlg
+    header = open(os.path.join(ROOT, "include", "orlg.h")).read()
+    declared = set(re.findall(r"\b(orlg_[a-z_0-9]+)\s*\(", header))
+    for name in NEW:
+        assert name in declared and name in _lib.PROTOTYPES and name in _lib.EXPORTED_SYMBOLS
+    assert "#define ORLG_ABI_VERSION 3" in header
+    assert orlg.ADAPTIVE_POLICIES is _lib.ADAPTIVE_POLICIES == ("sp_ff_am", "sap_ff_am", "path_am_external", "external_am")
+    assert not set(_lib.ADAPTIVE_POLICIES) & (set(_lib.POLICIES) | set(_lib.ASSIGN_POLICIES) | set(_lib.CUT_POLICIES) |
+                                              set(_lib.WINDOW_POLICIES) | set(_lib.MAX_MARGIN_POLICIES))
+    for name, value in _lib.ADAPTIVE_POLICY_IDS.items():
+        c_name = {"sp_ff_am": "ORLG_AM_SP_FF", "sap_ff_am": "ORLG_AM_SAP_FF", "path_am_external": "ORLG_AM_PATH_EXTERNAL",
+                  "external_am": "ORLG_AM_EXTERNAL"}[name]
+        assert re.search(r"\b%s = %d\b" % (c_name, value), header), name
+    L = _lib.load()   # (a fresh library: the loader rebuilds a stale one)
+    assert L.orlg_abi_version() == 3
+    assert L.orlg_set_gn_modulation(None, 1) == -1 and b"null handle" in L.orlg_last_error()
+    assert L.orlg_step_modulation(None, 201, 1, None, 0, None, None, None) == -1
+    assert L.orlg_gn_modulation_windows(None, None, None, None, None) == -1
+    assert L.orlg_get_running_services_se(None, None, None, None, None, None, None, None, None) == -1
+    # the existing step entries accept no new policy value
+    out = (C.c_int32 * 2)()
+    for policy in (10, 11, 12, 13, 200, 201, 202, 203):
+        assert L.orlg_debug_step_call((C.c_int32 * 7)(0, policy, 0, 0, 1, 1, 0), 7, out) == -1 and b"unknown policy" in L.orlg_last_error()
+
+
+def test_the_kernels_are_a_unit_of_their_own():
+    from optical_rl_gym_amd import build
+    units = build.units()
+    mine = [(n, s, x) for n, s, x in units if s == "orlg_inst_gnam.hip"]
+    assert [n for n, _, _ in mine] == [f"orlg_inst_gnam_w{w}" for w in sorted(build.WAVE_W, reverse=True)]
+    assert all(x == [f"-DORLG_INST_W={n.rsplit('w', 1)[1]}"] for n, _, x in mine)
+    assert len({n for n, _, _ in units}) == len(units)
+    for other in ("orlg_inst_wave.hip", "orlg_inst_gnrules.hip", "orlg_inst_gnprotect.hip", "orlg_inst_gnadmit.hip", "orlg_inst_gnslots.hip",
+                  "orlg_inst_gnmm.hip", "orlg_inst_group.hip"):
+        text = open(os.path.join(build.CSRC, other)).read()
+        assert "am_kernel" not in text and "GN_AM" not in text and "modulation" not in text, other
+    for new in ("orlg_qdesc.h", "orlg_rmsa_gn_am.h", "orlg_gn_modulation_kernels.hip", "orlg_inst_gnam.hip"):
+        assert "asm" not in open(os.path.join(build.CSRC, new)).read(), new   # no inline assembly
+    variants = open(os.path.join(build.CSRC, "orlg_variants.h")).read()
+    assert "ORLG_WAVE_GN_AM_KEYS(X) X(1) X(2) X(0)" in variants and "orlg_pick_gn_am" in variants
+    assert variants.index("ORLG_WAVE_GN_AM_KEYS") > variants.index("ORLG_WAVE_GN_MM_KEYS")   # behind the existing lists
+    # the level-aware decode is written once: its readers name the header's functions, none masks a descriptor's path field itself
+    for user in ("orlg_rmsa_gn_am.h", "orlg_gn_modulation_kernels.hip"):
+        text = open(os.path.join(build.CSRC, user)).read()
+        assert "0x7ffu" not in text and "0x3fff" not in text and ">> 11" not in text, user
+    assert "orlg_qdesc_gid" in open(os.path.join(build.CSRC, "orlg_rmsa_gn_am.h")).read()
+    assert "orlg_qdesc_gid" in open(os.path.join(build.CSRC, "orlg_gn_audit_kernels.hip")).read()
+    assert "orlg_qdesc_gid" in open(os.path.join(build.CSRC, "orlg_rmsa_gn_audit.h")).read()
+
+
+def test_the_descriptor_keeps_its_level():
+    """orlg_qdesc.h restated: 11 bits of path record, 3 of level, 10 of slot, 8 of rate; level 0 reads as the plain layout"""
+    make = lambda gid, level, slot, rate: gid | level << 11 | slot << 14 | rate << 24
+    for gid, level, slot, rate in ((0, 0, 0, 0), (2047, 6, 1023, 255), (454, 3, 319, 20), (454, 0, 319, 20)):
+        d = make(gid, level, slot, rate)
+        assert d < 1 << 32
+        assert (d & 0x7ff, (d >> 11) & 7, (d >> 14) & 0x3ff, d >> 24) == (gid, level, slot, rate)
+        if level == 0:
+            assert d & 0x3fff == gid   # a state without levels reads the same on every handle
+        else:
+            assert d & 0x3fff >= 2048   # ... and a level names no path record of a handle that may be adaptive
+
+
+# ---------------------------------------------------------------------------------------- the gate's mode, before the library is loaded
+def test_gate_parameters_and_their_refusals(nsfnet):
+    plain = rmsa_gn_gate_parameters(nsfnet)
+    assert "modulation" not in plain and len(plain) == 8
+    g = rmsa_gn_gate_parameters(nsfnet, modulation="adaptive")
+    assert g["modulation"] == "adaptive" and len(g) == 9
+    with pytest.raises(ValueError, match="modulation"):
+        rmsa_gn_gate_parameters(nsfnet, modulation="best")
+    from optical_rl_gym_amd.osnr import check_rmsa_gn_gate
+    assert check_rmsa_gn_gate(g, nsfnet)["modulation"] == "adaptive" and "modulation" not in check_rmsa_gn_gate(plain, nsfnet)
+    with pytest.raises(ValueError, match="modulation"):
+        check_rmsa_gn_gate(dict(plain, modulation="best"), nsfnet)
+    with pytest.raises(ValueError, match="protect_running"):
+        check_rmsa_gn_gate(dict(g, protect_running=True), nsfnet)
+    with pytest.raises(ValueError, match="7 thresholds"):
+        check_rmsa_gn_gate(dict(g, thresholds_db=np.arange(7.0)), nsfnet)
+    with pytest.raises(ValueError, match="group"):
+        check_rmsa_gn_gate(g, nsfnet, "group")
+    big = am.expanded(nsfnet, 6)   # 2730 path records
+    assert big.num_paths >= _lib.MAX_ADAPTIVE_PATHS
+    with pytest.raises(ValueError, match="path records"):
+        check_rmsa_gn_gate(rmsa_gn_gate_parameters(big, modulation="adaptive"), big)
+    for cls in (BatchedRMSAEnv, BatchedDeepRMSAEnv):   # refused by the constructor before the library is touched
+        with pytest.raises(ValueError, match="protect_running"):
+            cls(nsfnet, 2, gn_gate=dict(g, protect_running=True), seed=1)
+        with pytest.raises(ValueError, match="group"):
+            cls(nsfnet, 2, gn_gate=g, step_kernel="group", seed=1)
+
+
+class _NoLibrary:
+    """Stands where the loaded library would: any call through it fails the test."""
+
+    def __getattr__(self, name):
+        raise AssertionError(f"the library was called ({name}) although the arguments are wrong")
+
+
+NB, K, S, W = 3, 5, 320, 5
+
+
+def _shell(gn_gate, cls=BatchedRMSAEnv):
+    env = cls.__new__(cls)
+    env.L, env.h = _NoLibrary(), None
+    env.batch_size, env.k_paths, env.j, env.reject_action, env.words_per_link, env.num_spectrum_resources = NB, K, 1, 0, W, S
+    env.gn_gate = gn_gate
+    return env
+
+
+@pytest.mark.parametrize("cls", [BatchedRMSAEnv, BatchedDeepRMSAEnv])
+def test_refused_before_the_library_is_called(cls, nsfnet):
+    plain, adaptive = rmsa_gn_gate_parameters(nsfnet), rmsa_gn_gate_parameters(nsfnet, modulation="adaptive")
+    path_acts, ext_acts = np.zeros(NB, np.int32), np.zeros((NB, 3), np.int32)
+    for name in _lib.ADAPTIVE_POLICIES:
+        acts = ext_acts if name == "external_am" else path_acts if name == "path_am_external" else None
+        for gate in (None, plain):   # the names need the mode
+            with pytest.raises(ValueError, match="adaptive"):
+                _shell(gate, cls).run(name, 1, actions=acts)
+        env = _shell(adaptive, cls)
+        assert env.gn_adaptive and env.modulation_levels == 6 and not env.gn_protect
+        with pytest.raises(ValueError, match="gn_rule"):
+            env.run(name, 1, actions=acts, gn_rule="check")
+        with pytest.raises(ValueError, match="block_cause"):
+            env.run(name, 1, actions=acts, outputs=("block_cause",))
+        with pytest.raises(ValueError, match="block_cause"):
+            env.run(name, 1, actions=acts, cause_counts=True)
+        with pytest.raises(ValueError, match="gn_window_margin_db"):
+            env.run(name, 1, actions=acts, outputs=("gn_window_margin_db",))
+        with pytest.raises(ValueError, match="n_steps"):
+            env.run(name, 0, actions=acts)
+    env = _shell(adaptive, cls)
+    with pytest.raises(ValueError, match="actions"):
+        env.run("external_am", 1)
+    with pytest.raises(ValueError, match="n_steps must be 1"):
+        env.run("path_am_external", 2, actions=path_acts)
+    with pytest.raises(ValueError):
+        env.run("external_am", 1, actions=np.zeros((NB, 2), np.int32))   # (path, slot) without the level
+    with pytest.raises(TypeError):
+        env.run("external_am", 1, actions=np.zeros((NB, 3)))
+    # what an adaptive handle does not serve yet
+    for name in _lib.MAX_MARGIN_POLICIES:
+        with pytest.raises(ValueError, match="modulation='adaptive'"):
+            env.run(name, 1, actions=path_acts if name.endswith("external") else None)
+    with pytest.raises(ValueError, match="modulation='adaptive'"):
+        env.run("sap_lf", 1, gn_rule="check")
+    with pytest.raises(ValueError, match="modulation='adaptive'"):
+        env.run("sap_ff", 1, outputs=("block_cause",))
+    with pytest.raises(ValueError, match="modulation='adaptive'"):
+        env.run("sap_ff", 1, cause_counts=True)
+    for kind in BatchedRMSAEnv.GN_MASK_KINDS:
+        with pytest.raises(ValueError, match="modulation='adaptive'"):
+            env.action_masks(kind)
+    for call in (lambda: env.path_rule_windows("first"), lambda: env.admission_masks("path_ff"), lambda: env.admission_windows("first"),
+                 env.admission_slot_masks, env.max_margin_windows):
+        with pytest.raises(ValueError, match="modulation='adaptive'"):
+            call()
+    # gn_se and the query belong to the mode
+    with pytest.raises(ValueError, match="ADAPTIVE_POLICIES"):
+        env.run("sap_ff", 1, outputs=("gn_se",))
+    for gate in (None, plain):
+        with pytest.raises(ValueError, match="adaptive"):
+            _shell(gate, cls).modulation_windows()
+    with pytest.raises(ValueError):
+        env.modulation_windows(slot_out=np.zeros((NB, K, 5), np.int16))
+
+
+def test_the_views_know_the_level():
+    from optical_rl_gym_amd import adaptive_modulation_heuristic
+    with pytest.raises(ValueError, match="route"):
+        adaptive_modulation_heuristic("llp")
+    assert adaptive_modulation_heuristic("sap").__name__ == "sap_adaptive_modulation"
+
+
+# ---------------------------------------------------------------------------------------- what the GPU cases exercise, from the reference alone
+@pytest.mark.parametrize("case", list(am.CASES))
+def test_the_case_exercises_the_levels(case):
+    fig = [am.run_case(case, i)[2] for i in range(am.B)]
+    accepted, other = sum(f["accepted"] for f in fig), sum(f["other_level"] for f in fig)
+    closest = min(f["closest"] for f in fig)
+    print(case, "accepted", accepted, "at another level", other, "refused after", max(f["refused_after"] for f in fig), "levels; most running",
+          max(f["max_running"] for f in fig), "closest", closest, "mean checks", np.mean([f["mean_checks"] for f in fig]), "max checks",
+          max(f["max_checks"] for f in fig))
+    assert other >= 0.05 * accepted > 0                      # at least 5 % of the accepted services take a level other than their path's
+    assert max(f["refused_after"] for f in fig) >= 2          # a gate refusal after several levels
+    assert closest > 1e-6                                     # no compared GSNR within 1e-6 dB of its threshold
+    assert min(f["min_admitted_margin"] for f in fig) >= 0
+    topo = load_topology(am.CASES[case]["topology"])
+    assert max(f["max_checks"] for f in fig) <= topo.k_paths * 6
+    if "l150" in case and "nsfnet" in case:
+        assert max(f["max_running"] for f in fig) > 64        # more than one chunk of interferers
+    if "ring34" in case:
+        assert max(f["link_ranges"] for f in fig) == 4        # link masks of four words
+
+
+def test_thresholds_nobody_misses_give_the_ungated_oracle(nsfnet):
+    """With all thresholds at -100 dB the adaptive reference is sap_ff on a topology whose every path has spectral efficiency M"""
+    kw = ref.case_kwargs("nsfnet_s320_l150_sapff")
+    gate = am.case_gate(nsfnet, 6.0, thresholds_db=[-100.0] * 6)
+    with device_log_in_oracle():
+        ao = am.AdaptiveOracle(nsfnet, kw, gate, seed=11)
+        got = ao.run_route("sap", 300)
+        ao_final = ao.final()
+        ao.close()
+        o = oracle_env_from_kwargs(am.expanded(nsfnet, 6, only_se=6), kw, seed=11)
+        want = o.run("sap_ff", 300, reset_on_done=True)
+        for f in ("act_path", "act_slot", "accepted"):
+            assert np.array_equal(got[f], want[f]), f
+        assert (got["gn_se"][got["accepted"] == 1] == 6).all()
+        assert np.array_equal(ao_final["available_slots"], o.available_slots()) and ao_final["counters"] == o.counters()
+        assert ao_final["current_time"] == o.current_time()
+        o.close()
