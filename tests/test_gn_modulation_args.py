@@ -1,7 +1,7 @@
 """Adaptive modulation behind the GN gate (``include/orlg.h`` ``orlg_set_gn_modulation``, ``orlg_step_modulation``,
 ``orlg_gn_modulation_windows``) without a GPU: the symbols, the unit and the names of its kernels, every refusal before
 the library is called, the descriptor's decode, and -- from the reference alone, every case of ``test_gpu_gn_modulation.py`` stepped by
-its own choices -- what those cases exercise."""
+its own choices -- what those cases exercise, and what the shapes of ``test_gpu_gn_modulation_shapes.py`` reach."""
 import ctypes as C
 import os
 import re
@@ -232,3 +232,128 @@ def test_thresholds_nobody_misses_give_the_ungated_oracle(nsfnet):
         assert np.array_equal(ao_final["available_slots"], o.available_slots()) and ao_final["counters"] == o.counters()
         assert ao_final["current_time"] == o.current_time()
         o.close()
+
+
+# ---------------------------------------------------------------------------------------- what the shapes of test_gpu_gn_modulation_shapes.py reach
+STATS_CASES = ("nsfnet_s128_l25_6dbm", "nsfnet_s320_l150_0dbm")
+
+
+def _figures(shape, n_envs, **kw):
+    fig = [am.run_shape(shape, i, **kw)[2] for i in range(n_envs)]
+    print(shape, "accepted", [f["accepted"] for f in fig], "at another level", [f["other_level"] for f in fig], "refusals",
+          [f["rejects"] for f in fig], "peak", [f["max_running"] for f in fig], "closest", min(f["closest"] for f in fig), "max checks",
+          max(f["max_checks"] for f in fig), "released", [f["released"] for f in fig])
+    assert min(f["closest"] for f in fig) > 1e-6   # no compared GSNR within 1e-6 dB of its threshold
+    return fig
+
+
+@pytest.mark.parametrize("case", STATS_CASES + ("mixed",))
+def test_the_statistics_cases_release_services_at_another_level(case):
+    """sum_sh, the link statistics and the compactness of a release take the slots of the LEVEL: in every environment a service whose
+    level is not its path's own is released before the last step, so a release that took the path's own would show"""
+    for i in range(am.B):
+        fig = (am.run_mixed(i) if case == "mixed" else am.run_case(case, i))[2]
+        assert fig["released_other"] >= 1 and fig["closest"] > 1e-6, (case, i, fig)
+
+
+def test_the_mixed_plan_interleaves_releases_with_and_without_a_level():
+    for i in range(am.B):
+        tr, _, fig, services = am.run_mixed(i)
+        assert 1 <= fig["released_other"] < fig["released"], (i, fig)
+
+
+@pytest.mark.parametrize("M", [3, 1])
+def test_fewer_levels(M, nsfnet):
+    topo = am.clipped(nsfnet, M)
+    assert int(topo.path_se.max()) == M and np.array_equal(topo.path_se, np.minimum(nsfnet.path_se, M))
+    assert np.array_equal(topo.path_links, nsfnet.path_links) and np.array_equal(topo.path_hops, nsfnet.path_hops)
+    gate = am.shape_gate(topo, 6.0, M)
+    assert len(gate["thresholds_db"]) == M and np.array_equal(gate["thresholds_db"], am.case_gate(nsfnet, 6.0)["thresholds_db"][:M])
+    from optical_rl_gym_amd.osnr import check_rmsa_gn_gate
+    assert len(check_rmsa_gn_gate(gate, topo)["thresholds_db"]) == M
+    if M == 3:
+        # the unclipped topology is refused; the message names the highest spectral efficiency of a path (NSFNET's paths end at 5)
+        assert int(nsfnet.path_se.max()) == 5
+        with pytest.raises(ValueError, match="a path has spectral efficiency 5, thresholds_db has 3 entries"):
+            check_rmsa_gn_gate(am.shape_gate(nsfnet, 6.0, M), nsfnet)
+    hot, cold = _figures("m%d_6dbm" % M, am.B), _figures("m%d_0dbm" % M, am.B)
+    f0 = hot[0]
+    assert (f0["accepted"], f0["rejects"]) == ((96, 34) if M == 3 else (69, 4))   # the figures of seed 21
+    if M == 3:
+        assert (f0["other_level"], f0["max_checks"]) == (11, 12)
+        assert all(f["other_level"] >= 1 and f["refused_after"] >= 2 for f in hot)
+    else:
+        assert all(f["other_level"] == 0 and f["max_checks"] <= nsfnet.k_paths for f in hot)   # the walk has one level
+    assert all(f["rejects"] >= 1 and f["accepted"] >= 1 for f in hot)
+    assert all(f["rejects"] == 0 for f in cold)   # 0 dBm: the all-admitted arm
+
+
+def test_three_chunks_of_interferers():
+    c = am.SHAPES["chunks3"]
+    fig = _figures("chunks3", c["B"])
+    assert all(f["max_running"] > 128 for f in fig)   # a third chunk of 64 in every environment
+    assert all(f["rejects"] >= 1 and f["max_checks"] >= 2 for f in fig)
+    f0 = fig[0]
+    assert (f0["max_running"], f0["rejects"], f0["max_checks"]) == (147, 25, 10) and abs(f0["closest"] - 2.7e-4) < 1e-5   # seed 11
+    for i, f in enumerate(fig):   # the step of the peak has more than 128 running: where the query is compared
+        assert f["peak_step"] < c["n"] and f["max_running"] > 128
+
+
+def test_the_ring_laps():
+    c = am.SHAPES["lap"]
+    fig = _figures("lap", am.B)
+    peak = max(f["max_running"] for f in fig)
+    Q = am.ring_capacity(peak, c["queue_margin"])
+    assert (peak, Q) == (23, 64) and fig[0]["max_running"] == 19
+    assert all(f["released"] >= 2 * Q for f in fig)   # the head passes Q twice in every environment
+    assert all(f["max_running"] < Q for f in fig)
+
+
+@pytest.mark.parametrize("shape", list(am.MANY))
+def test_the_many_path_shapes_reach_the_high_paths(shape, tmp_path):
+    from gpu_support import MANY_PATHS, many_paths_topology
+    topo = many_paths_topology(shape, tmp_path)
+    c = MANY_PATHS[shape]
+    assert topo.k_paths == c["k"] > 8 and topo.num_paths < _lib.MAX_ADAPTIVE_PATHS
+    assert topo.num_paths == {"g3x3_k9_s64": 324, "g4x4_k16_s200": 1920, "g3x4_k10_s384": 660}[shape]
+    fig = _figures(shape, am.B, topo=topo)
+    high = 0
+    for i in range(am.B):
+        tr = am.run_shape(shape, i, topo=topo)[0]
+        acc = tr["accepted"].astype(bool)
+        high += int((tr["act_path"][acc] >= 8).sum())
+    print(shape, "accepted on paths >= 8:", high)
+    assert high >= 10
+    assert sum(f["other_level"] for f in fig) >= 1 and sum(f["rejects"] for f in fig) >= 1
+
+
+def test_too_many_path_records_are_refused(tmp_path):
+    from gpu_support import many_paths_topology
+    from optical_rl_gym_amd.osnr import check_rmsa_gn_gate
+    topo = many_paths_topology(am.MANY_REFUSED, tmp_path)
+    assert topo.num_paths == 2520
+    with pytest.raises(ValueError, match="path records"):
+        check_rmsa_gn_gate(am.case_gate(topo, 6.0), topo)
+
+
+def test_the_query_cases_at_the_other_word_counts():
+    """ring34 (link masks of four words), one and eight words per link: after the warm-up the query sees levels with and without a
+    window, admitted and refused"""
+    for case in ("ring34_s100_l60_6dbm", "nsfnet_s64_l12_6dbm", "nsfnet_s512_l100_6dbm"):
+        for i in (0, 1):
+            fig = am.run_case(case, i, n_steps=110)[2]
+            assert fig["rejects"] >= 1 and fig["other_level"] >= 1 and fig["closest"] > 1e-6, (case, i, fig)
+
+
+def test_the_sweep_and_the_deeprmsa_handle():
+    c = am.SWEEP
+    for i in range(len(c["loads"]) * c["seeds_per_load"]):
+        fig = am.run_sweep(i)[2]
+        assert fig["closest"] > 1e-6 and fig["other_level"] >= 1 and fig["rejects"] >= 1, (i, fig)
+    low, high = (sum(am.run_sweep(g * c["seeds_per_load"] + r)[2]["max_running"] for r in range(c["seeds_per_load"])) for g in (0, 1))
+    assert high > low   # the environments do run their own loads
+    for i in range(am.DEEP["B"]):
+        tr, own, _, fig, _ = am.run_deep(i)
+        assert fig["closest"] > 1e-6 and fig["other_level"] >= 1 and fig["rejects"] >= 1, (i, fig)
+        assert set(np.unique(tr["reward"])) == {-1.0, 1.0} and np.array_equal(tr["reward"], np.where(tr["accepted"] == 1, 1.0, -1.0))
+        assert own["accepted"].any() and (own["gn_se"] == 0).all()
