@@ -678,54 +678,86 @@
                     // disjoint occupancy words, summaries, span-cache entries and link logs at one `current_time`, and what joins
                     // them are integer sums, so the order between them leaves no trace.  Lanes 0..7 of the row take A's hops, lanes
                     // 8..15 B's.  Anything else -- a shared link, a longer path, a third due service -- waits for the next pass.
-                    const bool up = gl >= 8;
+                    //
+                    // Four passes of ten have no due B in any row, so the wave votes once and such a pass
+                    // takes the PLAIN prelude: every lane of a row serves A, its place in the row is its hop, one entry leaves the
+                    // ring -- no link masks, no trade between the halves.  A's descriptor is in a register when the pass begins,
+                    // so A's 16-byte record is asked for first, next to B's ring entry, and waits for no compare; the plain
+                    // prelude takes hops, se and the lane's link from that register copy.  The preludes hand ONE
+                    // group_release_links its arguments, the lane's link among them.
                     // (slots outside the ring's live part were never written: B is read only where it exists)
+                    const uint32_t d_a = rel_now ? next_desc : 0u;   // (the head's descriptor came with its time)
+                    const uint4 rec_a = *reinterpret_cast<const uint4 *>(tb.recs + (int)(d_a & 0x3fff));
                     double b_rel = INF;
                     uint32_t b_desc = 0u;
                     if (rel_now && q_n >= 2) {
                         const int qb = q_head + 1 == Q ? 0 : q_head + 1;
                         b_rel = qtime[qb]; b_desc = qdesc[qb];
                     }
-                    const bool b_due = b_rel <= current_time;
-                    // the lane's service: its descriptor, path record, window and hop count
-                    const bool mine = up ? b_due : rel_now;
-                    const uint32_t d_a = rel_now ? next_desc : 0u;   // (the head's descriptor came with its time)
-                    const uint32_t d = up ? b_desc : d_a;            // (a B that is not due is a real entry: `mine` keeps its lanes off)
-                    const int gid2 = (int)(d & 0x3fff), s0 = (int)((d >> 14) & 0x3ff), bri2 = (int)(d >> 24);
-                    const OrlgPathRec *rec2 = tb.recs + gid2;
-                    const int hops2 = mine ? (int)rec2->hops : 0;
-                    const int n2 = tb.nslots[bri2 * ORLG_NSLOT_STRIDE + rec2->se];
-                    const int br2 = mine ? tb.bit_rates[bri2] : 0;
-                    const int hop = gl & 7;
-                    // the links of each half as bits (link mod 64): exact up to 64 links, beyond them a false conflict costs one
-                    // pass and nothing else
-                    const u64 lbits = half_row_or_u64(hop < hops2 ? 1ull << (rec2->link[hop] & 63) : 0ull);
-                    const u64 obits = ((u64)(uint32_t)row_swap8_i32((int)(uint32_t)(lbits >> 32)) << 32) | (uint32_t)row_swap8_i32((int)(uint32_t)lbits);
-                    const int hops_o = row_swap8_i32(hops2), n_o = row_swap8_i32(n2), br_o = row_swap8_i32(br2);   // the other half's
-                    const bool pair = b_due && hops2 <= 8 && hops_o <= 8 && (lbits & obits) == 0ull;
-                    // A alone: the whole row is A's, as before (lanes 8..15 matter to a path of more than 8 hops only)
-                    const bool a_up = up && !pair;
-                    const int hops_a = up ? hops_o : hops2, n_a = up ? n_o : n2, br_a = up ? br_o : br2;
-                    const int hops_b = up ? hops2 : hops_o, n_b = up ? n2 : n_o, br_b = up ? br2 : br_o;
+                    const bool b_due = b_rel <= current_time;   // (false in a row that releases nothing: idle rows do not vote)
+                    const int bri_a = (int)(d_a >> 24);
+                    // what the pass does, per lane: hop `r_hop` of `r_hops` over `r_link`, window [r_s, r_s + r_n); per row: the
+                    // entries that leave the ring and what leaves the running sums with them
+                    int r_link, r_hop, r_hops, r_s, r_n, pops, br_out, sh_out;
+                    if (ballot(b_due) == 0ull) {
+                        // ---- no row has a due B: A alone on the whole row (lanes 8..15 matter to a path of more than 8 hops only)
+                        r_hops = rel_now ? (int)(rec_a.x & 0xffu) : 0;
+                        r_n = tb.nslots[bri_a * ORLG_NSLOT_STRIDE + (int)((rec_a.x >> 8) & 0xffu)];
+                        br_out = tb.bit_rates[bri_a];
+                        r_link = group_rec_byte(rec_a, (gl + 2) & 15);   // (lanes 14, 15: no hop of any path, never used)
+                        r_hop = gl;
+                        r_s = (int)((d_a >> 14) & 0x3ff);
+                        pops = 1;
+                        sh_out = r_n * r_hops;
+                    } else {
+                        // ---- some row may release two: lanes 0..7 of a row take A's hops, lanes 8..15 B's
+                        const bool up = gl >= 8;
+                        // the lane's service: its descriptor, path record, window and hop count (the record byte by byte: both
+                        // records in registers and a select between them measured slower)
+                        const bool mine = up ? b_due : rel_now;
+                        const uint32_t d = up ? b_desc : d_a;   // (a B that is not due is a real entry: `mine` keeps its lanes off)
+                        const int s0 = (int)((d >> 14) & 0x3ff), bri2 = (int)(d >> 24);
+                        const int hop = gl & 7;
+                        const OrlgPathRec *rec2 = tb.recs + (int)(d & 0x3fff);
+                        const int hops2 = mine ? (int)rec2->hops : 0;
+                        const int n2 = tb.nslots[bri2 * ORLG_NSLOT_STRIDE + rec2->se];
+                        const int br2 = mine ? tb.bit_rates[bri2] : 0;
+                        const int link2 = (int)rec2->link[hop];
+                        // the links of each half as bits (link mod 64): exact up to 64 links, beyond them a false conflict costs
+                        // one pass and nothing else
+                        const u64 lbits = half_row_or_u64(hop < hops2 ? 1ull << (link2 & 63) : 0ull);
+                        const u64 obits = ((u64)(uint32_t)row_swap8_i32((int)(uint32_t)(lbits >> 32)) << 32) | (uint32_t)row_swap8_i32((int)(uint32_t)lbits);
+                        const int hops_o = row_swap8_i32(hops2), n_o = row_swap8_i32(n2), br_o = row_swap8_i32(br2);   // the other half's
+                        const bool pair = b_due && hops2 <= 8 && hops_o <= 8 && (lbits & obits) == 0ull;
+                        // A alone: the whole row is A's, its upper lanes take A's link from the register copy
+                        const bool a_up = up && !pair;
+                        const int hops_a = up ? hops_o : hops2, n_a = up ? n_o : n2, br_a = up ? br_o : br2;
+                        const int hops_b = up ? hops2 : hops_o, n_b = up ? n2 : n_o, br_b = up ? br2 : br_o;
+                        r_link = a_up ? group_rec_byte(rec_a, (gl + 2) & 15) : link2;
+                        r_hop = pair ? hop : gl;
+                        r_hops = a_up ? hops_a : hops2;
+                        r_s = a_up ? (int)((d_a >> 14) & 0x3ff) : s0;
+                        r_n = a_up ? n_a : n2;
+                        pops = pair ? 2 : 1;
+                        br_out = br_a + (pair ? br_b : 0);
+                        sh_out = n_a * hops_a + (pair ? n_b * hops_b : 0);
+                    }
                     if (rel_now) {
                         // (the ring in LDS leaves a popped slot as it is: the state store writes the (+inf, 0) of the slots that left)
-                        const int pops = pair ? 2 : 1;
                         q_head += pops;
                         q_head -= q_head >= Q ? Q : 0;
                         q_pops += pops;
                         q_n -= pops;
                         n_running -= pops;
-                        sum_bitrate_running -= br_a + (pair ? br_b : 0);
-                        sum_sh -= n_a * hops_a + (pair ? n_b * hops_b : 0);
+                        sum_bitrate_running -= br_out;
+                        sum_sh -= sh_out;
                         released = true;
                         next_rel = q_n > 0 ? qtime[q_head] : INF;   // the next entry
                         next_desc = q_n > 0 ? qdesc[q_head] : 0u;
                     }
                     // the window and its links' statistics in one pass, lane = hop (group_release_links; ends with a wave_sync)
-                    const uint8_t *links2 = a_up ? (tb.recs + (int)(d_a & 0x3fff))->link : rec2->link;
-                    group_release_links<W>(lane, occ, lsum, lint, S, links2, pair ? hop : gl, a_up ? hops_a : hops2,
-                                           a_up ? (int)((d_a >> 14) & 0x3ff) : s0, a_up ? n_a : n2, current_time, sum_span, sum_gaps, llog,
-                                           need_replay);
+                    group_release_links<W>(lane, occ, lsum, lint, S, r_link, r_hop, r_hops, r_s, r_n, current_time, sum_span, sum_gaps,
+                                           llog, need_replay);
                     SEC(11);  // statistics at release: the log replays only
                 } else {
                     // ---- _release_path (rmsa_env.py:515-535)

@@ -117,6 +117,13 @@ DEV u64 group_path_word_rec(const u64 *occ, const OrlgPathRec *recs, int gid, in
     return group_path_word_of<W>(occ, r, w, active, se, hops_out);
 }
 
+// Byte i (0 .. 15, lane-variable) of a path record held in registers: hops, se, link[0 .. 13] (OrlgPathRec).  Two selects pick the
+// record's half, one 64-bit shift the byte.
+DEV int group_rec_byte(const uint4 r, int i) {
+    const u64 half = ((u64)((i & 8) ? r.w : r.y) << 32) | ((i & 8) ? r.z : r.x);
+    return (int)((half >> (8 * (i & 7))) & 0xffull);
+}
+
 // A link's summary (DEFER instantiation, LDS only): every integer _update_link_stats consumes, 10 bits each -- free slots, free
 // runs, used runs, first used slot (lmin), end of the last used run (lmax), longest free run, slot 0 free, slot S - 1 free.  With
 // no used slot lmin / lmax are group_link_stats' 0x7fff / 0 and lmin keeps only its low 10 bits: a summary is read at a release
@@ -324,16 +331,16 @@ DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, 
 // the words next to and under the window at once (independent LDS reads), ORs the window into the one or two words it covers,
 // looks further out only where a bordering free run reaches a word's end, then logs the update and refreshes the span cache
 // exactly as group_link_stats would (the same values, so the same bits).
-// The lane's hop is its own: hop `hop` of a path of `hops` (none: hops = 0), with that path's window.  A row that releases one
+// The lane's hop is its own: hop `hop` of a path of `hops` (none: hops = 0) over link `link` (the caller holds the path's record in
+// registers; read only where hop < hops), with that path's window.  A row that releases one
 // service has hop = the lane's place in the row; a row that releases two link-disjoint services at once (orlg_group_body.h) gives
 // its lower eight lanes the first one's hops and its upper eight the second one's, and the row sums below cover both.
 template <int W>
-DEV void group_release_links(const int lane, u64 *occ, u64 *lsum, int32_t *lint, int S, const uint8_t *links, int hop, int hops, int s,
+DEV void group_release_links(const int lane, u64 *occ, u64 *lsum, int32_t *lint, int S, const int link, int hop, int hops, int s,
                              int n, double now, int &sum_span, int &sum_gaps, uint4 *llog, bool &need_replay) {
     static_assert(ORLG_MAX_HOPS <= ORLG_GL, "one lane per hop");
     int dspan = 0, dgaps = 0;
     if (hop < hops) {
-        const int link = (int)links[hop];
         u64 *lw = occ + __mul24(link, W);
         const int e = s + n;
         // the words that hold slot s - 1, slot s + n, and the window's first / last slot: independent reads (coinciding ones too)

@@ -8,7 +8,10 @@ nothing due).  A model of iteration counts, not a measurement of the kernel.
 
   one    the head only (the kernel before the paired release)
   two    the head and the entry behind it where that is due too, both paths have at most 8 hops and they share no link
-  four   up to four consecutive due entries of at most 4 hops each that share no link pairwise"""
+  four   up to four consecutive due entries of at most 4 hops each that share no link pairwise
+
+Under rule `two` it also counts the passes in which no row of the quad has a due entry behind its head (two_passes_b_free_share, and
+those that are a quad-step's first pass per quad-step): the passes that need none of the pair's machinery."""
 import argparse
 import bisect
 import json
@@ -41,14 +44,37 @@ def passes(due, width, max_hops):
     return n
 
 
+def due_behind_head(due):
+    """Rule `two`, pass by pass: whether the entry behind the head is due when the pass begins (what the row votes with)."""
+    out, i = [], 0
+    while i < len(due):
+        out.append(i + 1 < len(due))
+        pair = i + 1 < len(due) and max(len(due[i]), len(due[i + 1])) <= 8 and not (due[i] & due[i + 1])
+        i += 2 if pair else 1
+    return out
+
+
+def b_free_share(votes):
+    """votes[seed][step] = due_behind_head of that row and step.  The passes of a quad-step run to its slowest row; a pass is
+    B-free where no row that still releases has a due entry behind its head.  Returns (passes, B-free passes, B-free FIRST
+    passes) over whole quads of seeds."""
+    n = nb = nb_first = 0
+    for q in range(0, len(votes), 4):
+        for rows in zip(*votes[q:q + 4]):
+            for j in range(max(len(r) for r in rows)):
+                free = not any(r[j] for r in rows if j < len(r))
+                n, nb, nb_first = n + 1, nb + free, nb_first + (free and j == 0)
+    return n, nb, nb_first
+
+
 def replay(topo, tr, warmup):
-    """Per step from `warmup` on: the passes of each rule, and the step's consecutive due pairs as (pairs, link-disjoint pairs);
-    the longest released path."""
+    """Per step from `warmup` on: the passes of each rule, the step's consecutive due pairs as (pairs, link-disjoint pairs) and
+    its votes under rule `two` (due_behind_head); the longest released path."""
     N = topo.num_nodes
     arrival, holding, accepted = np.asarray(tr["arrival"]), np.asarray(tr["holding"]), np.asarray(tr["accepted"]) != 0
     gid = topo.pair_path_base[np.asarray(tr["src"]) * N + np.asarray(tr["dst"])] + np.asarray(tr["act_path"])
     ring, sets = [], []   # release times in time order (ties in insert order), and each entry's links
-    rows, pairs, longest = [], [], 0
+    rows, pairs, votes, longest = [], [], [], 0
     for t in range(len(accepted)):
         if accepted[t]:
             k = bisect.bisect_right(ring, arrival[t] + holding[t])
@@ -61,8 +87,9 @@ def replay(topo, tr, warmup):
         if t >= warmup:
             rows.append([passes(due, w, h) for _, w, h in RULES])
             pairs.append((max(len(due) - 1, 0), sum(1 for a, b in zip(due, due[1:]) if not (a & b))))
+            votes.append(due_behind_head(due))
             longest = max([longest] + [len(d) for d in due])
-    return np.array(rows), np.array(pairs), longest
+    return np.array(rows), np.array(pairs), votes, longest
 
 
 def main():
@@ -76,16 +103,17 @@ def main():
     topo = load_topology("nsfnet_chen_5-paths_6-modulations")
     n_seeds = args.seeds[1] - args.seeds[0] + 1
     assert n_seeds % 4 == 0, "whole quads of seeds"
-    rows, pairs, longest = [], [], 0
+    rows, pairs, votes, longest = [], [], [], 0
     for seed in range(args.seeds[0], args.seeds[1] + 1):
         kw = dict(num_spectrum_resources=320, load=args.load, mean_service_holding_time=25, episode_length=1000, seed=seed)
         o = oracle_env_from_kwargs(topo, kw, seed=seed)
         tr = o.run("sap_ff", args.warmup + args.steps, reset_on_done=True)
         o.close()
-        r, p, h = replay(topo, tr, args.warmup)
-        rows.append(r); pairs.append(p); longest = max(longest, h)
+        r, p, v, h = replay(topo, tr, args.warmup)
+        rows.append(r); pairs.append(p); votes.append(v); longest = max(longest, h)
     rows, pairs = np.stack(rows), np.concatenate(pairs)                       # [seed, step, rule], [seed x step, 2]
     quads = rows.reshape(n_seeds // 4, 4, rows.shape[1], len(RULES)).max(axis=1)   # the loop runs to the slowest of a wave's four rows
+    n_pass, n_free, n_free_first = b_free_share(votes)
     names = [r[0] for r in RULES]
     rnd = lambda v: dict(zip(names, (round(float(x), 3) for x in v)))
     out = {"workload": f"RMSA NSFNET-320 load {args.load:g} sap_ff, seeds {args.seeds[0]}..{args.seeds[1]}, {args.steps} steps each "
@@ -96,6 +124,8 @@ def main():
            "iterations_per_quad_step": rnd(quads.mean(axis=(0, 1))),
            "p_quad_step_ge_2": rnd((quads >= 2).mean(axis=(0, 1))),
            "p_quad_step_ge_3": rnd((quads >= 3).mean(axis=(0, 1))),
+           "two_passes_b_free_share": round(n_free / max(1, n_pass), 3),
+           "two_passes_b_free_first_per_quad_step": round(n_free_first / quads.shape[1] / quads.shape[0], 3),
            "due_consecutive_pairs_link_disjoint": round(float(pairs[:, 1].sum() / max(1, pairs[:, 0].sum())), 3),
            "longest_released_path_hops": int(longest)}
     print(json.dumps(out, indent=1))
