@@ -34,21 +34,16 @@ def units():
     # the host side: what the APIs share, the RMSA API's three units (csrc/orlg_rmsa_host.h says what lives where), the other two APIs
     u = [("orlg_host", "orlg_host.hip", []), ("orlg_api", "orlg_api.hip", []), ("orlg_api_step", "orlg_api_step.hip", []),
          ("orlg_api_query", "orlg_api_query.hip", []), ("orlg_phy_api", "orlg_phy_api.hip", []), ("orlg_osnr", "orlg_osnr.hip", [])]
-    # the largest objects first: the pool then finishes with the small ones
-    for w in sorted(WAVE_W, reverse=True):
-        u.append((f"orlg_inst_wave_w{w}", "orlg_inst_wave.hip", [f"-DORLG_INST_W={w}"]))
-    for w in sorted(WAVE_W, reverse=True):   # the gated step kernel under an assignment rule, and its query (orlg_step_rule_gn)
-        u.append((f"orlg_inst_gnrules_w{w}", "orlg_inst_gnrules.hip", [f"-DORLG_INST_W={w}"]))
-    for w in sorted(WAVE_W, reverse=True):   # the gated step kernel that protects the running lightpaths (orlg_set_gn_protect)
-        u.append((f"orlg_inst_gnprotect_w{w}", "orlg_inst_gnprotect.hip", [f"-DORLG_INST_W={w}"]))
-    for w in sorted(WAVE_W, reverse=True):   # the masks and rule windows that know both halves of the check (orlg_gn_admission_masks)
-        u.append((f"orlg_inst_gnadmit_w{w}", "orlg_inst_gnadmit.hip", [f"-DORLG_INST_W={w}"]))
-    for w in sorted(WAVE_W, reverse=True):   # the check over every start slot of every path (orlg_gn_admission_slots)
-        u.append((f"orlg_inst_gnslots_w{w}", "orlg_inst_gnslots.hip", [f"-DORLG_INST_W={w}"]))
-    for w in sorted(WAVE_W, reverse=True):   # the gated step kernel under a max-margin policy (orlg_step_max_margin)
-        u.append((f"orlg_inst_gnmm_w{w}", "orlg_inst_gnmm.hip", [f"-DORLG_INST_W={w}"]))
-    for w in sorted(WAVE_W, reverse=True):   # the gated step kernel of a gate that chooses the modulation, and its query (orlg_step_modulation)
-        u.append((f"orlg_inst_gnam_w{w}", "orlg_inst_gnam.hip", [f"-DORLG_INST_W={w}"]))
+    # one object per (wave-kernel family, W), the largest W first: the pool then finishes with the small ones
+    for family in ("wave",        # the step, reset and query kernels of a handle without extras
+                   "gnrules",     # the gated step kernel under an assignment rule, and its query (orlg_step_rule_gn)
+                   "gnprotect",   # the gated step kernel that protects the running lightpaths (orlg_set_gn_protect)
+                   "gnadmit",     # the masks and rule windows that know both halves of the check (orlg_gn_admission_masks)
+                   "gnslots",     # the check over every start slot of every path (orlg_gn_admission_slots)
+                   "gnmm",        # the gated step kernel under a max-margin policy (orlg_step_max_margin)
+                   "gnam"):       # the gated step kernel of a gate that chooses the modulation, and its query (orlg_step_modulation)
+        for w in sorted(WAVE_W, reverse=True):
+            u.append((f"orlg_inst_{family}_w{w}", f"orlg_inst_{family}.hip", [f"-DORLG_INST_W={w}"]))
     u.append(("orlg_gn_audit", "orlg_gn_audit_kernels.hip", []))   # the audit of the running lightpaths: no word count, one object
     for w in sorted(PHY_W, reverse=True):
         u.append((f"orlg_inst_phy_w{w}", "orlg_inst_phy.hip", [f"-DORLG_INST_W={w}", "-DORLG_INST_TRACE=0"]))

@@ -632,6 +632,33 @@ extern "C" int orlg_debug_group_plan(const int32_t *in, int32_t n_in, int32_t *o
 #undef X
     return i;
 }
+// what orlg_wave_plan.h makes of a launch of the wave-per-environment kernels, without a device or a handle (tests/test_wave_plan.py):
+// in[] in ORLG_WAVE_PLAN_IN order -- the ask of orlg_wave_choose, then the arguments of orlg_wave_extra_lds, then B and the resident
+// workgroups; out[] in ORLG_WAVE_PLAN_OUT order -- the family, the key (kernel = -1 and STATS, CAUSE for the MM and AM keys), the
+// workgroup and, where a wave fits, its grid and tickets
+#define ORLG_WAVE_PLAN_IN(X) X(mode) X(policy) X(K) X(stats_level) X(n_steps) X(out_mask) X(assign) X(gated) X(adaptive) X(protect) \
+    X(max_margin) X(no_defer) X(shared_bytes) X(wave_bytes) X(extra_per_wave) X(wpb) X(B) X(resident)
+#define ORLG_WAVE_PLAN_OUT(X) X(c, family) X(k, kernel) X(k, STATS) X(k, DEFER) X(k, GN) X(k, CAUSE) X(k, ASSIGN) X(k, CUT) X(k, USAGE) \
+    X(k, PROTECT) X(s, wpu) X(s, lds) X(g, nblocks) X(g, ticket_stride) X(g, ticket_advance)
+extern "C" int orlg_debug_wave_plan(const int32_t *in, int32_t n_in, int32_t *out, int32_t n_out) {
+#define X(f) int32_t f;
+    struct { ORLG_WAVE_PLAN_IN(X) } v;
+#undef X
+    if (!in || !out || n_in != (int32_t)(sizeof(v) / sizeof(int32_t))) return fail(ORLG_ERR_INVALID, "orlg_debug_wave_plan: %d inputs", n_in);
+    memcpy(&v, in, sizeof(v));
+    if (v.wpb < 1 || v.resident < 1 || v.n_steps < 1) return fail(ORLG_ERR_INVALID, "orlg_debug_wave_plan: no workgroup to plan for");
+    const OrlgWaveChoice c = orlg_wave_choose({v.mode, v.policy, v.K, v.stats_level, v.n_steps, v.out_mask, v.assign, v.gated != 0, v.adaptive != 0,
+                                               v.protect != 0, v.max_margin != 0, v.no_defer != 0});
+    struct { int kernel, STATS; bool DEFER, GN, CAUSE, ASSIGN, CUT, USAGE, PROTECT; } k = {-1, c.mm.STATS, false, false, c.family == ORLG_WAVE_MM && c.mm.CAUSE};
+    if (c.family == ORLG_WAVE_PLAIN) k = {c.key.kernel, c.key.STATS, c.key.DEFER, c.key.GN, c.key.CAUSE, c.key.ASSIGN, c.key.CUT, c.key.USAGE, c.key.PROTECT};
+    const OrlgWaveShape s = orlg_wave_extra_lds(v.shared_bytes, v.wave_bytes, v.extra_per_wave, v.wpb);
+    const OrlgWaveGrid g = s.wpu ? orlg_wave_grid(v.B, s.wpu, v.resident, v.mode, v.n_steps) : OrlgWaveGrid{};
+    int i = 0;
+#define X(s, f) if (i < n_out) out[i] = (int32_t)s.f; i++;
+    ORLG_WAVE_PLAN_OUT(X)
+#undef X
+    return i;
+}
 // what orlg_step_call.h makes of a call of a step entry, without a device or a handle (tests/test_step_calls.py): in[] = entry kind,
 // policy or route, rule, gn_mode, n_steps, the handle has a gate, the gate protects; out[] = policy, assign.  Returns the code
 extern "C" int orlg_debug_step_call(const int32_t *in, int32_t n_in, int32_t *out) {

@@ -1,5 +1,5 @@
 // orlg_api_step.hip -- the step of the RMSA C API (include/orlg.h): the launch of the step kernels (launch_rmsa, which create and reset
-// use as well, and the group kernel's launch_rmsa_group), one launch of a resolved call (rmsa_step; what a call resolves to and what
+// use as well: the wave kernels' one launch_wave and the group kernel's launch_rmsa_group), one launch of a resolved call (rmsa_step; what a call resolves to and what
 // refuses it: orlg_step_call.h), the orlg_step* entries, and the GN-model gate a step checks against with its setters.
 #include "orlg_rmsa_host.h"
 #include "orlg_step_call.h"
@@ -16,7 +16,7 @@ static OrlgGroupOverrides group_overrides() {
             wpb ? atoi(wpb) : 0, chunks ? atoi(chunks) : 0};
 }
 
-// the step kernel with four environments per wave: first-fit policies and external (path, slot) actions.  What is launched is
+// ---- the step kernel with four environments per wave: first-fit policies and external (path, slot) actions.  What is launched is
 // decided in orlg_group_plan.h; here it is done
 // a launch of orlg_step_window under the rule MOST_USED or the route BEST_WINDOW: the USAGE instantiations (orlg_usage.h)
 static bool usage_launch(const OrlgParams &p) {
@@ -80,133 +80,110 @@ static bool group_kernel_serves(const orlg_env *e, const OrlgParams &p) {
     return p.B > e->resident_blocks * e->waves_per_block;
 }
 
+// ---- the wave-per-environment step kernels: what is launched is decided in orlg_wave_plan.h; here it is done
 // the plain wave-per-environment step kernel
 static rmsa_kernel_t step_kernel(int W, int stats) { return orlg_pick(W, OrlgWaveKey{ORLG_WAVE_KERNEL(orlg_rmsa_kernel), stats, false}); }
 
-static int launch_rmsa_am(orlg_env *e, const OrlgParams &p, uint8_t *o_se);
-
-int launch_rmsa(orlg_env *e, const OrlgParams &p) {
-    // a step of a handle whose gate chooses the modulation: orlg_rmsa_am_kernel, whatever the policy -- its decode knows the levels
-    if (p.mode == ORLG_MODE_STEP && p.gn && p.gn_adaptive) return launch_rmsa_am(e, p, nullptr);
-    // a step of a handle with a GN-model admission check: the general kernel's GN instantiation, whatever the policy and the length
-    const bool gn = p.mode == ORLG_MODE_STEP && p.gn != nullptr;
-    // a launch that asks for the blocking cause: the general kernel's CAUSE instantiation, with or without the check
-    const bool cause = p.mode == ORLG_MODE_STEP && (p.out_mask & ORLG_OUT_CAUSE_BIT) != 0;
-    // a launch under an assignment rule other than the reference's first fit: the general kernel's ASSIGN instantiation (behind a gate:
-    // orlg_step_rule_gn alone, every other entry refuses)
-    const bool assign = p.mode == ORLG_MODE_STEP && (p.out_mask & ORLG_OUT_ASSIGN_BIT) != 0;
-    const bool ff = !gn && !cause && !assign && p.mode == ORLG_MODE_STEP && p.K <= 8 && (p.policy == ORLG_POLICY_SP || p.policy == ORLG_POLICY_SAP);
-    const OrlgGroupOverrides ov = group_overrides();
-    const bool df = !gn && p.mode == ORLG_MODE_STEP && orlg_defer_link_stats(p.stats_level, p.n_steps, p.out_mask, ov);   // as launch_rmsa_group
-    const OrlgWaveKey key = {ff ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel_ff)
-                                : p.mode == ORLG_MODE_STEP ? ORLG_WAVE_KERNEL(orlg_rmsa_kernel) : ORLG_WAVE_KERNEL(orlg_rmsa_reset_kernel),
-                             p.stats_level, df, gn, cause, assign, assign && p.assign == ORLG_ASSIGN_MIN_CUT, assign && usage_launch(p),
-                             gn && e->gn_protect};
-    // (an assignment rule behind the check, orlg_step_rule_gn: the instantiations of orlg_inst_gnrules.hip, with a lookup of their own;
-    // a handle that protects its running lightpaths: those of orlg_inst_gnprotect.hip -- orlg_step_rule_gn refuses on it)
-    rmsa_kernel_t k = key.PROTECT ? orlg_pick_gn_protect(e->W, key) : gn && assign ? orlg_pick_gn_rules(e->W, key) : orlg_pick(e->W, key);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), e->lds_block_bytes)) return rc;
-    const int wpb = e->waves_per_block;
-    if (e->resident_blocks <= 0) {
-        const void *ks = reinterpret_cast<const void *>(step_kernel(e->W, p.stats_level));  // the grid is sized for the step kernel (any grid is correct)
-        int rc = orlg_kernel_lds(ks, e->lds_block_bytes);
-        if (!rc) rc = orlg_handle_resident(e, ks, ORLG_WAVE * wpb, e->lds_block_bytes, &e->resident_blocks);
-        if (rc) return rc;
-    }
-    if (group_kernel_serves(e, p)) return launch_rmsa_group(e, p, ov);
-    // (a USAGE launch: the waves' prefix sums of the slot usage lie behind the wave regions, asked for here and by no other launch;
-    // where the handle's workgroup fills the LDS, such a launch runs with as many waves per workgroup as still fit)
-    int wpu = wpb;
-    size_t lds = e->lds_block_bytes;
-    if (key.USAGE) {
-        const size_t per_wave = (size_t)p.l_wave_bytes + ORLG_USAGE_BYTES(e->W);
-        while (wpu > 1 && (size_t)p.l_shared_bytes + wpu * per_wave > ORLG_LDS_BYTES) --wpu;
-        lds = (size_t)p.l_shared_bytes + wpu * per_wave;
-        if (lds > ORLG_LDS_BYTES)
-            return fail(ORLG_ERR_INVALID, "tables, one environment and its slot-usage prefix sums (%zu B) exceed the 160 KiB LDS", lds);
-        if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), lds)) return rc;
-    }
-    int nblocks = (p.B + wpu - 1) / wpu;
-    if (nblocks > e->resident_blocks) nblocks = e->resident_blocks;
-    if (df && !e->llog) {
-        int rc = orlg_handle_alloc(e, &e->llog, (size_t)p.B * p.E * ORLG_LLOG_CAP);
-        if (rc) return rc;
-    }
-    OrlgParams q = p;
-    q.llog = df ? e->llog : nullptr;
-    q.ticket_base = e->ticket_base;
-    q.ticket_stride = (p.mode != ORLG_MODE_STEP || p.n_steps <= 16) ? 1u : 0u;
-    if (!q.ticket_stride) e->ticket_base += (uint32_t)p.B;  // waves * 1 static environment + (B - waves) tickets + one failing draw per wave
-    dim3 grid(nblocks), block(ORLG_WAVE * wpu);
-    hipLaunchKernelGGL(k, grid, block, lds, e->stream, q);
-    HIP_TRY(hipGetLastError());
-    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * wpu, lds);
-    return ORLG_OK;
-}
-
-// ---- the gated step kernel under a max-margin policy (orlg_rmsa_mm_kernel, orlg_inst_gnmm.hip)
-// Its workgroup: the handle's wave regions and, behind them, up16(4 Q) bytes per wave for the compacted services of the path under
-// evaluation; where the handle's workgroup fills the LDS, as many waves as still fit.  Refused where one wave does not.
-struct MmLaunch {
-    double *window_margin = nullptr;   // device memory the kernel writes gn_window_margin_db to, nullptr = not asked for
+// What a step entry resolved beyond the call (rmsa_step): the family its launch runs -- orlg_step_max_margin's calls are MM, every other
+// entry leaves the plan to find it (a handle whose gate chooses the modulation: AM) -- with the workgroup of an MM launch (mm_geometry)
+// and where the kernel's second argument points: gn_window_margin_db (OrlgMmArgs), gn_se (OrlgAmArgs); nullptr = not asked for
+struct WaveFamily {
+    OrlgWaveFamily family = ORLG_WAVE_PLAIN;
+    OrlgWaveShape mm = {};
+    double *window_margin = nullptr;
+    uint8_t *se = nullptr;
+};
+// one launch: the kernel and the name it reports, the kernel's second argument (nullptr: it has none), the workgroup, where the
+// resident workgroups of this kernel and shape are kept, and the log of a DEFER instantiation (nullptr for any other)
+struct WaveLaunch {
+    const void *kernel = nullptr;
+    char name[96] = "";
+    const void *arg2 = nullptr;
     int wpu = 0;
     size_t lds = 0;
+    int *resident = nullptr;
+    uint4 *llog = nullptr;
 };
-static int mm_geometry(const orlg_env *e, MmLaunch *m) {
-    const size_t per_wave = (size_t)e->p.l_wave_bytes + (((size_t)e->p.Q * 4 + 15) & ~(size_t)15);
-    int wpu = e->waves_per_block;
-    while (wpu > 1 && (size_t)e->p.l_shared_bytes + wpu * per_wave > ORLG_LDS_BYTES) --wpu;
-    m->wpu = wpu;
-    m->lds = (size_t)e->p.l_shared_bytes + wpu * per_wave;
-    if (m->lds > ORLG_LDS_BYTES)
-        return fail(ORLG_ERR_INVALID, "orlg_step_max_margin: tables, one environment and the ring of its %d compacted services (%zu B) exceed the 160 KiB LDS",
-                    e->p.Q, m->lds);
+template <typename Key>
+static int wave_kernel(const orlg_env *e, const Key &key, WaveLaunch *w) {
+    w->kernel = reinterpret_cast<const void *>(orlg_pick(e->W, key));
+    if (!w->kernel) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
+    orlg_kernel_name(w->name, sizeof(w->name), e->W, key);
     return ORLG_OK;
 }
-static int launch_rmsa_mm(orlg_env *e, const OrlgParams &p, const MmLaunch &m) {
-    const bool cause = (p.out_mask & ORLG_OUT_CAUSE_BIT) != 0;
-    const OrlgMmKey key = {p.stats_level, cause};
-    orlg_rmsa_mm_kernel_t k = orlg_pick_gn_mm(e->W, key);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), m.lds)) return rc;
-    int *resident = &e->mm_resident[p.stats_level][cause ? 1 : 0];
-    if (int rc = orlg_handle_resident(e, reinterpret_cast<const void *>(k), ORLG_WAVE * m.wpu, m.lds, resident)) return rc;
-    int nblocks = (p.B + m.wpu - 1) / m.wpu;
-    if (nblocks > *resident) nblocks = *resident;
+static int launch_wave(orlg_env *e, const OrlgParams &p, const WaveLaunch &w) {
+    if (int rc = orlg_kernel_lds(w.kernel, w.lds)) return rc;
+    if (int rc = orlg_handle_resident(e, w.kernel, ORLG_WAVE * w.wpu, w.lds, w.resident)) return rc;
+    const OrlgWaveGrid g = orlg_wave_grid(p.B, w.wpu, *w.resident, p.mode, p.n_steps);
     OrlgParams q = p;
-    q.llog = nullptr;
+    q.llog = w.llog;
     q.ticket_base = e->ticket_base;
-    q.ticket_stride = p.n_steps <= 16 ? 1u : 0u;
-    if (!q.ticket_stride) e->ticket_base += (uint32_t)p.B;
-    const OrlgMmArgs a = {m.window_margin, e->gn_protect ? 1 : 0, 0};
-    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * m.wpu), m.lds, e->stream, q, a);
+    q.ticket_stride = g.ticket_stride;
+    e->ticket_base += g.ticket_advance;
+    void *args[] = {&q, const_cast<void *>(w.arg2)};
+    (void)hipLaunchKernel(w.kernel, dim3(g.nblocks), dim3(ORLG_WAVE * w.wpu), args, w.lds, e->stream);
     HIP_TRY(hipGetLastError());
-    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * m.wpu, m.lds);
+    orlg_handle_note_launch(e, w.name, g.nblocks, ORLG_WAVE * w.wpu, w.lds, 0, nullptr);
     return ORLG_OK;
 }
 
-// ---- the gated step kernel of a handle whose gate chooses the modulation (orlg_rmsa_am_kernel, orlg_inst_gnam.hip): the
-// handle's own workgroup -- it needs no LDS beyond the wave regions
-static int launch_rmsa_am(orlg_env *e, const OrlgParams &p, uint8_t *o_se) {
-    const OrlgAmKey key = {p.stats_level};
-    orlg_rmsa_am_kernel_t k = orlg_pick_gn_am(e->W, key);
-    if (!k) return fail(ORLG_ERR_INVALID, "no kernel for W=%d", e->W);
-    if (int rc = orlg_kernel_lds(reinterpret_cast<const void *>(k), e->lds_block_bytes)) return rc;
-    const int wpb = e->waves_per_block;
-    int *resident = &e->am_resident[p.stats_level];
-    if (int rc = orlg_handle_resident(e, reinterpret_cast<const void *>(k), ORLG_WAVE * wpb, e->lds_block_bytes, resident)) return rc;
-    int nblocks = (p.B + wpb - 1) / wpb;
-    if (nblocks > *resident) nblocks = *resident;
-    OrlgParams q = p;
-    q.llog = nullptr;
-    q.ticket_base = e->ticket_base;
-    q.ticket_stride = p.n_steps <= 16 ? 1u : 0u;
-    if (!q.ticket_stride) e->ticket_base += (uint32_t)p.B;
-    const OrlgAmArgs a = {o_se};
-    hipLaunchKernelGGL(k, dim3(nblocks), dim3(ORLG_WAVE * wpb), e->lds_block_bytes, e->stream, q, a);
-    HIP_TRY(hipGetLastError());
-    orlg_handle_launched(e, key, nblocks, ORLG_WAVE * wpb, e->lds_block_bytes);
+static int launch_rmsa_family(orlg_env *e, const OrlgParams &p, const WaveFamily &f) {
+    const OrlgGroupOverrides ov = group_overrides();
+    const OrlgWaveChoice c = orlg_wave_choose({p.mode, p.policy, p.K, p.stats_level, p.n_steps, (int)p.out_mask, p.assign, p.gn != nullptr,
+                                               p.gn_adaptive != 0, e->gn_protect, f.family == ORLG_WAVE_MM, ov.no_defer});
+    WaveLaunch w;
+    w.wpu = e->waves_per_block;
+    w.lds = e->lds_block_bytes;
+    // orlg_rmsa_mm_kernel and orlg_rmsa_am_kernel: a second kernel argument, and the resident workgroups of their own kernel and shape
+    if (c.family == ORLG_WAVE_MM) {
+        if (int rc = wave_kernel(e, c.mm, &w)) return rc;
+        const OrlgMmArgs a = {f.window_margin, e->gn_protect ? 1 : 0, 0};
+        w.arg2 = &a; w.wpu = f.mm.wpu; w.lds = f.mm.lds;
+        w.resident = &e->mm_resident[p.stats_level][c.mm.CAUSE ? 1 : 0];
+        return launch_wave(e, p, w);
+    }
+    if (c.family == ORLG_WAVE_AM) {   // (the handle's own workgroup: it needs no LDS beyond the wave regions)
+        if (int rc = wave_kernel(e, c.am, &w)) return rc;
+        const OrlgAmArgs a = {f.se};
+        w.arg2 = &a;
+        w.resident = &e->am_resident[p.stats_level];
+        return launch_wave(e, p, w);
+    }
+    if (int rc = wave_kernel(e, c.key, &w)) return rc;
+    // Every launch of this family sizes its grid from resident_blocks, asked once for the plain step kernel at the handle's workgroup --
+    // a GN, CAUSE or ASSIGN launch too, and a USAGE launch of fewer waves per workgroup (any grid is correct; other code reads the value)
+    if (e->resident_blocks <= 0) {
+        const void *ks = reinterpret_cast<const void *>(step_kernel(e->W, p.stats_level));
+        int rc = orlg_kernel_lds(ks, e->lds_block_bytes);
+        if (!rc) rc = orlg_handle_resident(e, ks, ORLG_WAVE * w.wpu, e->lds_block_bytes, &e->resident_blocks);
+        if (rc) return rc;
+    }
+    w.resident = &e->resident_blocks;
+    if (group_kernel_serves(e, p)) return launch_rmsa_group(e, p, ov);   // (after the key is picked: a W without kernels is refused first)
+    // (a USAGE launch: the waves' prefix sums of the slot usage lie behind the wave regions, asked for here and by no other launch;
+    // where the handle's workgroup fills the LDS, such a launch runs with as many waves per workgroup as still fit)
+    if (c.key.USAGE) {
+        const OrlgWaveShape u = orlg_wave_extra_lds(p.l_shared_bytes, p.l_wave_bytes, ORLG_USAGE_BYTES(e->W), w.wpu);
+        if (!u.wpu)
+            return fail(ORLG_ERR_INVALID, "tables, one environment and its slot-usage prefix sums (%zu B) exceed the 160 KiB LDS", u.lds);
+        w.wpu = u.wpu; w.lds = u.lds;
+    }
+    if (c.key.DEFER) {
+        if (!e->llog)
+            if (int rc = orlg_handle_alloc(e, &e->llog, (size_t)p.B * p.E * ORLG_LLOG_CAP)) return rc;
+        w.llog = e->llog;
+    }
+    return launch_wave(e, p, w);
+}
+int launch_rmsa(orlg_env *e, const OrlgParams &p) { return launch_rmsa_family(e, p, {}); }
+
+// the workgroup of orlg_rmsa_mm_kernel (orlg_inst_gnmm.hip): the handle's wave regions and, behind them, up16(4 Q) bytes
+// per wave for the compacted services of the path under evaluation.  Refused where one wave does not fit
+static int mm_geometry(const orlg_env *e, OrlgWaveShape *m) {
+    *m = orlg_wave_extra_lds(e->p.l_shared_bytes, e->p.l_wave_bytes, ((size_t)e->p.Q * 4 + 15) & ~(size_t)15, e->waves_per_block);
+    if (!m->wpu)
+        return fail(ORLG_ERR_INVALID, "orlg_step_max_margin: tables, one environment and the ring of its %d compacted services (%zu B) exceed the 160 KiB LDS",
+                    e->p.Q, m->lds);
     return ORLG_OK;
 }
 
@@ -265,12 +242,13 @@ static int place_extra(orlg_env *e, ExtraOut *o) {
     return ORLG_OK;
 }
 
-// one launch of n_steps steps of a call that orlg_step_call has resolved: the live part of every step entry.  mm: the call is
-// orlg_step_max_margin's (orlg_step_mm_call resolved it, mm_geometry found its workgroup) and launches orlg_rmsa_mm_kernel
-// am: the call is orlg_step_modulation's (call.policy is the device's ORLG_POLICY_*_AM) and launches orlg_rmsa_am_kernel with gn_se
+// one launch of n_steps steps of a call that orlg_step_call has resolved: the live part of every step entry.  fam.family MM: the call
+// is orlg_step_max_margin's (orlg_step_mm_call resolved it, mm_geometry found its workgroup) and launches orlg_rmsa_mm_kernel; AM: the
+// call is orlg_step_modulation's (call.policy is the device's ORLG_POLICY_*_AM) and launches orlg_rmsa_am_kernel with gn_se
 static int rmsa_step(orlg_env *e, const OrlgStepCall &call, int32_t n_steps, const int32_t *actions, int32_t auto_reset,
-                     const orlg_step_io *io, const StepExtras &x, MmLaunch *mm = nullptr, bool am = false) {
+                     const orlg_step_io *io, const StepExtras &x, WaveFamily fam = {}) {
     const int32_t policy = call.policy;
+    const bool am = fam.family == ORLG_WAVE_AM;
     const bool ext = am ? policy == ORLG_POLICY_PATH_AM_EXT || policy == ORLG_POLICY_EXT_AM
                         : policy == ORLG_POLICY_EXTERNAL || policy == ORLG_POLICY_DEEPRMSA_EXTERNAL || policy == ORLG_POLICY_PATH_FF_EXTERNAL;
     if (ext && (!actions || n_steps != 1)) return fail(ORLG_ERR_INVALID, "external actions need an action array and n_steps == 1");
@@ -317,8 +295,9 @@ static int rmsa_step(orlg_env *e, const OrlgStepCall &call, int32_t n_steps, con
     if (x.margin && !(p.gn && e->gn_protect)) HIP_TRY(hipMemsetAsync(p.o_margin, 0xff, extra[3].bytes, e->stream));
     p.assign = call.assign;
     if (call.assign != ORLG_ASSIGN_FIRST) p.out_mask |= ORLG_OUT_ASSIGN_BIT;   // the launch runs an ASSIGN instantiation
-    if (mm) mm->window_margin = static_cast<double *>(extra[4].dev);
-    rc = mm ? launch_rmsa_mm(e, p, *mm) : am ? launch_rmsa_am(e, p, static_cast<uint8_t *>(extra[5].dev)) : launch_rmsa(e, p);
+    fam.window_margin = static_cast<double *>(extra[4].dev);
+    fam.se = static_cast<uint8_t *>(extra[5].dev);
+    rc = launch_rmsa_family(e, p, fam);
     if (rc) return rc;
     if (e->trace.length > 0) e->trace.position += n_steps;
     bool any = false;
@@ -389,11 +368,12 @@ int orlg_step_max_margin_protect(orlg_env *e, int32_t route, int32_t n_steps, co
         return fail(ORLG_ERR_INVALID, "orlg_step_max_margin: the handle's gate chooses the modulation (orlg_set_gn_modulation), and no max-margin policy runs behind it yet");
     OrlgStepCall call;
     if (int rc = orlg_step_mm_call({route, n_steps, e->p.gn != nullptr, actions != nullptr}, &call)) return rc;
-    MmLaunch mm;
-    if (int rc = mm_geometry(e, &mm)) return rc;
+    WaveFamily mm;
+    mm.family = ORLG_WAVE_MM;
+    if (int rc = mm_geometry(e, &mm.mm)) return rc;
     StepExtras x = step_extras(diag, gn_neighbour_margin_db);
     x.wmargin = window_margin_db;
-    return rmsa_step(e, call, n_steps, actions, auto_reset, io, x, &mm);
+    return rmsa_step(e, call, n_steps, actions, auto_reset, io, x, mm);
 }
 int orlg_step_max_margin(orlg_env *e, int32_t route, int32_t n_steps, const int32_t *actions, int32_t auto_reset, const orlg_step_io *io,
                          const struct orlg_step_diag *diag, double *window_margin_db) {
@@ -412,7 +392,9 @@ int orlg_step_modulation(orlg_env *e, int32_t policy, int32_t n_steps, const int
     StepExtras x;
     x.gsnr = gn_gsnr_db;
     x.se = gn_se;
-    return rmsa_step(e, call, n_steps, actions, auto_reset, io, x, nullptr, true);
+    WaveFamily am;
+    am.family = ORLG_WAVE_AM;
+    return rmsa_step(e, call, n_steps, actions, auto_reset, io, x, am);
 }
 }  // extern "C"
 

@@ -1,6 +1,6 @@
 // orlg_gn_audit_kernels.hip -- the GN-model audit of every running lightpath of every environment, and the list of the running
 // services it audits (include/orlg.h orlg_gn_audit, orlg_get_running_services).  A unit of its own and ONE object:
-// nothing here depends on the word count W (no occupancy row is read), so the orlg_inst_* objects hold what they held.
+// nothing here depends on the word count W (no occupancy row is read), so it needs no orlg_inst_* object per W.
 //
 // orlg_gn_audit_kernel has the shape of orlg_gn_action_masks_kernel: tables staged once per workgroup, one wave per environment at
 // a time, the grid sized to the device and striding over the batch, the LIVE descriptors of the release ring copied to LDS in rank

@@ -10,6 +10,7 @@
 #pragma once
 #include "orlg_host.h"
 #include "orlg_group_plan.h"
+#include "orlg_wave_plan.h"
 
 // ---------------------------------------------------------------------------------------- handle
 struct orlg_env : OrlgHandle {

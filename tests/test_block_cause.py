@@ -116,20 +116,14 @@ def test_new_symbols_in_a_fresh_library():
     assert FIT_LEVELS == ("capacity", "contiguity", "alignment", "last_window", "fit")
 
 
-def test_cause_key_lists_resolve_to_their_kernels(tmp_path):
+def test_cause_key_lists_resolve_to_their_kernels():
+    from host_programs import variant_names
     from optical_rl_gym_amd import build
-    if build.needs_build():
-        build.build(verbose=False)
-    exe = str(tmp_path / "variant_names_cause")
-    lib = build.LIB
-    subprocess.run([build._hipcc(), "-std=c++17", "-O1", "-Wall", "-Wno-unused-function", "-I", build.CSRC,
-                    "-x", "c++", os.path.join(ROOT, "tests", "variant_names_cause.cpp"), "-x", "none", lib,
-                    "-Wl,-rpath," + os.path.dirname(lib), "-ldl", "-o", exe], check=True)
-    run = subprocess.run([exe], capture_output=True, text=True)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout[-4000:] + run.stderr[-2000:]
-    # per word count: 3 statistics levels x {no gate, GN} wave keys, 3 x {plain, traffic, trace} group keys, the query kernel
-    assert run.stdout.strip().splitlines()[-1] == "checked %d" % ((6 + 9 + 1) * len(build.WAVE_W))
+    counts = variant_names().counts
+    # per word count: 3 statistics levels x {no gate, GN} wave keys, 3 x {plain, traffic, trace} group keys; the query kernel is one
+    # of the single-kernel lookups the program walks
+    assert (counts["ORLG_WAVE_CAUSE_KEYS"], counts["ORLG_GROUP_CAUSE_KEYS"]) == (6 * len(build.WAVE_W), 9 * len(build.WAVE_W))
+    assert counts["ORLG_WAVE_QUERIES"] == 12 * len(build.WAVE_W) + 2   # (orlg_fit_levels_kernel among them)
 
 
 # ---------------------------------------------------------------------------------------- refusals before the library is called

@@ -18,6 +18,8 @@ pytestmark = pytest.mark.skipif(shutil.which(build._hipcc()) is None, reason="ne
 
 # the text of a function body, included inside orlg_rmsa_group_kernel and orlg_rmsa_group_body: says so in its first lines
 NOT_AT_FILE_SCOPE = {"orlg_group_body.h"}
+# what a header needs on the command line: the instantiation units' shared header is compiled for one word count
+DEFINES = {"orlg_inst.h": ["-DORLG_INST_W=5"]}
 
 
 def _included_files():
@@ -33,7 +35,8 @@ def _parse_alone(header, tmp):
     src = os.path.join(tmp, os.path.basename(header) + ".hip")
     with open(src, "w") as f:
         f.write('#include "%s"\n' % os.path.basename(header))
-    run = subprocess.run([build._hipcc()] + build.FLAGS + ["--cuda-device-only", "-fsyntax-only", "-I", build.CSRC, src],
+    run = subprocess.run([build._hipcc()] + build.FLAGS + DEFINES.get(os.path.basename(header), []) +
+                         ["--cuda-device-only", "-fsyntax-only", "-I", build.CSRC, src],
                          capture_output=True, text=True)
     return os.path.basename(header), run.returncode, run.stderr
 

@@ -53,21 +53,19 @@ def test_the_kernels_are_a_unit_of_their_own():
         assert "gn_slots_path<W" in text and "gn_slots_finish<W>" in text and "asinh" not in text, user
     variants = open(os.path.join(build.CSRC, "orlg_variants.h")).read()
     assert "ORLG_WAVE_GN_MM_KEYS(X) X(1) X(2) X(0) X(1, true) X(2, true) X(0, true)" in variants
-    assert "orlg_gnmm_kernel_W##n(OrlgMmKey) __attribute__((weak))" in variants and "orlg_pick_gn_mm" in variants
+    # the unit exports its lookup per word count, and for no other
+    exported = subprocess.run(["nm", "-D", "--defined-only", build.LIB], capture_output=True, text=True, check=True).stdout
+    assert sorted(re.findall(r"orlg_gnmm_kernel_W(\d)9OrlgMmKey", exported)) == sorted(str(w) for w in build.WAVE_W)
 
 
-def test_reported_names_are_the_kernels(tmp_path):
+def test_reported_names_are_the_kernels():
+    """through tests/variant_names.cpp: orlg_pick(W, OrlgMmKey) returns, per key, the kernel of that name with the parameters
+    (OrlgParams, OrlgMmArgs) -- the kernel the unit's own lookup returns -- and the list ends with <W,0,true>"""
+    from host_programs import variant_names
     from optical_rl_gym_amd import build
-    if build.needs_build():
-        build.build(verbose=False)
-    exe, lib = str(tmp_path / "mm_variant_names"), build.LIB
-    subprocess.run([build._hipcc(), "-std=c++17", "-O1", "-Wall", "-Wno-unused-function", "-I", build.CSRC, "-x", "c++",
-                    os.path.join(ROOT, "tests", "mm_variant_names.cpp"), "-x", "none", lib, "-Wl,-rpath," + os.path.dirname(lib), "-ldl",
-                    "-o", exe], check=True)
-    run = subprocess.run([exe], capture_output=True, text=True)
-    assert run.returncode == 0, run.stdout[-4000:] + run.stderr[-2000:]
-    lines = run.stdout.strip().splitlines()
-    assert lines[-1] == "checked %d" % (6 * len(build.WAVE_W)) and "W=5 orlg_rmsa_mm_kernel<5,0,true>" in lines
+    run = variant_names()
+    assert run.counts["ORLG_WAVE_GN_MM_KEYS"] == 6 * len(build.WAVE_W)
+    assert any(line.startswith("W=5 orlg_rmsa_mm_kernel<5,0,true> ") for line in run.lines)
 
 
 def test_the_existing_entries_keep_their_domain():

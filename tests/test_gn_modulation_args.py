@@ -59,7 +59,13 @@ def test_the_kernels_are_a_unit_of_their_own():
     for new in ("orlg_qdesc.h", "orlg_rmsa_gn_am.h", "orlg_gn_modulation_kernels.hip", "orlg_inst_gnam.hip"):
         assert "asm" not in open(os.path.join(build.CSRC, new)).read(), new   # no inline assembly
     variants = open(os.path.join(build.CSRC, "orlg_variants.h")).read()
-    assert "ORLG_WAVE_GN_AM_KEYS(X) X(1) X(2) X(0)" in variants and "orlg_pick_gn_am" in variants
+    assert "ORLG_WAVE_GN_AM_KEYS(X) X(1) X(2) X(0)" in variants
+    # ... and orlg_pick(W, OrlgAmKey) returns, per key, the kernel of that name with the parameters (OrlgParams, OrlgAmArgs), the one
+    # the unit's own lookup returns (tests/variant_names.cpp); the list ends with <W,0>
+    from host_programs import variant_names
+    run = variant_names()
+    assert run.counts["ORLG_WAVE_GN_AM_KEYS"] == 3 * len(build.WAVE_W)
+    assert any(line.startswith("W=5 ") and line.endswith(" orlg_rmsa_am_kernel<5,0>") for line in run.lines)
     assert variants.index("ORLG_WAVE_GN_AM_KEYS") > variants.index("ORLG_WAVE_GN_MM_KEYS")   # behind the existing lists
     # the level-aware decode is written once: its readers name the header's functions, none masks a descriptor's path field itself
     for user in ("orlg_rmsa_gn_am.h", "orlg_gn_modulation_kernels.hip"):

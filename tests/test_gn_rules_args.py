@@ -175,20 +175,12 @@ def test_a_null_handle_answers_first():
 
 
 # ---------------------------------------------------------------------------------------- the key lists and their objects
-def test_gn_rule_key_lists_resolve_to_their_kernels(tmp_path):
+def test_gn_rule_key_lists_resolve_to_their_kernels():
+    from host_programs import variant_names
     from optical_rl_gym_amd import build
-    if build.needs_build():
-        build.build(verbose=False)
-    exe = str(tmp_path / "variant_names_gn_rules")
-    lib = build.LIB
-    subprocess.run([build._hipcc(), "-std=c++17", "-O1", "-Wall", "-Wno-unused-function", "-I", build.CSRC,
-                    "-x", "c++", os.path.join(ROOT, "tests", "variant_names_gn_rules.cpp"), "-x", "none", lib,
-                    "-Wl,-rpath," + os.path.dirname(lib), "-ldl", "-o", exe], check=True)
-    run = subprocess.run([exe], capture_output=True, text=True)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout[-4000:] + run.stderr[-2000:]
+    counts = variant_names().counts
     # per word count: 3 statistics levels x {no cause, CAUSE} x {a rule, the fewest-cuts window}
-    assert run.stdout.strip().splitlines()[-1] == "checked %d" % (12 * len(build.WAVE_W))
+    assert (counts["ORLG_WAVE_GN_ASSIGN_KEYS"], counts["ORLG_WAVE_GN_CUT_KEYS"]) == (6 * len(build.WAVE_W), 6 * len(build.WAVE_W))
 
 
 def test_the_new_instantiations_are_objects_of_their_own():

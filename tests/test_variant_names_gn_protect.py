@@ -1,25 +1,17 @@
 """The kernels of a handle that protects its running lightpaths (``csrc/orlg_variants.h`` ``ORLG_WAVE_GN_PROTECT_KEY_LIST``,
-``ORLG_WAVE_GN_PROTECT_CAUSE_KEY_LIST``): every new key has a kernel and a distinct name at every word count, and every
-old key answers as before.  Device-free: ``variant_names_gn_protect.cpp`` is a plain host program linked with the built library."""
-import os
-import subprocess
+``ORLG_WAVE_GN_PROTECT_CAUSE_KEY_LIST``): every such key has a kernel and a distinct name at every word count, its unit
+answers it and no other unit does, and every other key of the family answers as before.  Device-free: ``tests/variant_names.cpp``
+walks them (``host_programs.variant_names``)."""
+from host_programs import variant_names
 
-from conftest import ROOT
-
-OLD_WAVE_KEYS = 11 + 3 + 6 + 6 + 6 + 6 + 6 + 6   # the older lists of csrc/orlg_variants.h, in its order
+OLD_WAVE_KEYS = 11 + 3 + 6 + 6 + 6 + 6 + 6 + 6   # the lists of the other two units of csrc/orlg_variants.h, in its order
 NEW_KEYS = 3 + 3
 
 
-def test_protecting_names_are_the_protecting_kernels(tmp_path):
+def test_protecting_names_are_the_protecting_kernels():
     from optical_rl_gym_amd import build
-    if build.needs_build():
-        build.build(verbose=False)
-    exe = str(tmp_path / "variant_names_gn_protect")
-    lib = build.LIB
-    subprocess.run([build._hipcc(), "-std=c++17", "-O1", "-Wall", "-Wno-unused-function", "-I", build.CSRC,
-                    "-x", "c++", os.path.join(ROOT, "tests", "variant_names_gn_protect.cpp"), "-x", "none", lib,
-                    "-Wl,-rpath," + os.path.dirname(lib), "-ldl", "-o", exe], check=True)
-    run = subprocess.run([exe], capture_output=True, text=True)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout[-4000:] + run.stderr[-2000:]
-    assert run.stdout.strip().splitlines()[-1] == "checked %d" % ((OLD_WAVE_KEYS + NEW_KEYS) * len(build.WAVE_W))
+    counts = variant_names().counts
+    n = len(build.WAVE_W)
+    assert (counts["ORLG_WAVE_GN_PROTECT_KEYS"], counts["ORLG_WAVE_GN_PROTECT_CAUSE_KEYS"]) == (3 * n, 3 * n)
+    wave = [c for name, c in counts.items() if name.startswith("ORLG_WAVE_") and name not in ("ORLG_WAVE_GN_MM_KEYS", "ORLG_WAVE_GN_AM_KEYS", "ORLG_WAVE_QUERIES")]
+    assert sum(wave) == (OLD_WAVE_KEYS + NEW_KEYS) * n
