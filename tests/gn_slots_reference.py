@@ -48,7 +48,14 @@ BATCHES = {
     K32: dict(B=2, n=40, warmup=30, protect=True, handle={}),
     TRI: dict(B=2, n=4, warmup=130, protect=True, handle={}),
     "gated:nsfnet_s320_l150_sapff": dict(B=2, n=20, warmup=100, protect=False, handle={}),
+    # the word counts no other batch has -- one, three, four and six words per link -- on the shapes of gpu_support.MANY_PATHS (k > 8:
+    # the path's words W lanes apart): 60 steps of the shape's own policy, then 40 with the query
+    "g3x3_k9_s64": dict(B=2, n=40, warmup=60, protect=True, handle={}),
+    "g4x4_k21_s192": dict(B=2, n=40, warmup=60, protect=True, handle={}),
+    "g4x4_k16_s200": dict(B=2, n=40, warmup=60, protect=True, handle={}),
+    "g3x4_k10_s384": dict(B=2, n=40, warmup=60, protect=True, handle={}),
 }
+WORDS = ("g3x3_k9_s64", "g4x4_k21_s192", "g4x4_k16_s200", "g3x4_k10_s384")   # W = 1, 3, 4, 6: there for their shape, outside COUNTED
 COUNTED = ("nsfnet_s100_l20_spff", "jpn12_s320_l150_sapff", "ring34_s320_l300_llpff", "ring36_s512_l500_sapff")   # every kind of window
 SEEDS = {}   # batch -> the first seed of the batch where it had to move off the case's own to meet a condition (none had to)
 

@@ -1,6 +1,7 @@
 """Max-margin assignment inside the step (``include/orlg.h`` ``orlg_step_max_margin``) without a GPU: the symbol, the
 unit and the names of its kernels, every refusal before the library is called, the proposal rules on hand-made rows, and -- from the
-reference alone, every batch of ``test_gpu_gn_max_margin.py`` stepped by its own max-margin choices -- what those batches exercise."""
+reference alone, every batch of ``test_gpu_gn_max_margin.py`` and every shape of ``test_gpu_gn_max_margin_shapes.py`` stepped by its own
+max-margin choices -- what those batches and shapes exercise, so that no comparison on the device passes with its target idle."""
 import ctypes as C
 import os
 import re
@@ -186,3 +187,75 @@ def test_what_a_batch_exercises(batch, route, tmp_path):
         if route == "sap":
             assert c["later_path"] >= mm.MIN_COUNT, c
         assert c["neighbour_decided"] >= mm.MIN_COUNT, c   # (the counted batches all protect)
+    if batch in sl.WORDS:   # there for their word count: a fallback, best windows that are not the first free one, and under the route
+        # that looks at every path a proposal on a path from 8 up (sap_mm proposes there 0 .. 2 times per batch; path_mm_external is
+        # given such paths by the device test: below)
+        assert c["fallback"] >= 1 and c["best_not_first"] >= mm.MIN_COUNT, c
+        if route == "any":
+            assert c["high_path"] >= 1, c
+
+
+def test_the_word_count_batches_are_given_high_paths(tmp_path):
+    """path_mm_external in test_gpu_gn_max_margin.py draws its paths from default_rng(32): at every new word count some of them lie at
+    8 or above (k = 9 has one such path: about one draw in nine)"""
+    from gpu_support import MANY_PATHS
+    assert [MANY_PATHS[b]["W"] for b in sl.WORDS] == [1, 3, 4, 6]
+    for batch in sl.WORDS:
+        c, k = sl.BATCHES[batch], MANY_PATHS[batch]["k"]
+        assert (c["B"], c["n"], c["warmup"], c["protect"]) == (2, 40, 60, True) and batch not in mm.COUNTED
+        given = np.random.default_rng(32).integers(0, k, size=(c["n"], c["B"]))
+        assert (given >= 8).sum() >= 1, batch
+
+
+# ---------------------------------------------------------------------------------------- what the shapes of test_gpu_gn_max_margin_shapes.py reach
+@pytest.mark.parametrize("W", sorted(mm.WORD_CASES))
+def test_what_a_word_count_case_reaches(W, tmp_path):
+    """the first SHAPE_B environments of the batch, SHAPE_N steps of sap_mm: admitted proposals and a fallback (the classifier's "gn")
+    at every word count; at one and two words also rejections (k, S), whose cause the classifier takes from the fit levels"""
+    batch = mm.WORD_CASES[W]
+    topo, kw, _ = sl.batch_case(batch, tmp_path)
+    assert (kw["num_spectrum_resources"] + 63) // 64 == W and sorted(mm.WORD_CASES) == [1, 2, 3, 4, 5, 6, 8]
+    steps = [s for i in range(mm.SHAPE_B) for s in mm.word_case_run(W, i, tmp_path)]
+    kinds = [s[0] for s in steps]
+    print(batch, {k: kinds.count(k) for k in ("admitted", "fallback", "rejection")}, "most running", max(s[2] for s in steps))
+    assert len(steps) == mm.SHAPE_B * mm.SHAPE_N and kinds.count("admitted") >= mm.MIN_COUNT and kinds.count("fallback") >= 1
+    if W <= 2:
+        assert kinds.count("rejection") >= 1
+
+
+def test_what_the_chunks_case_reaches(tmp_path):
+    """every environment has more than 192 services in progress (four chunks of the ring) and more than 128 that share a link with one
+    path (three chunks of the compacted list) at the first step the device evaluates -- whatever the max-margin steps then choose;
+    nothing overflows a ring of 256"""
+    c, kw = mm.CHUNKS, mm.chunks_kwargs()
+    topo = sl.tri_topology(tmp_path)
+    for i in range(c["B"]):
+        (kind, _, running, sharing, pops), = mm.own_run(topo, kw, kw["seed"] + i, c["policy"], c["warmup"], (("sap", 1),))
+        print("chunks", i, kind, "running", running, "sharing a link with one path", sharing, "released", pops)
+        assert 192 < running < c["queue_capacity"] - sum(n for _, n in c["plan"]) and sharing > 128, (i, running, sharing)
+
+
+def test_what_the_lapping_ring_reaches(tmp_path):
+    """every environment releases at least 2 Q services, the ring's live entries wrap at Q at ten or more evaluated steps, and the ring
+    never fills"""
+    c = mm.LAP
+    Q = c["queue_capacity"]
+    for i in range(c["B"]):
+        steps = mm.lap_run(i, tmp_path)
+        wrapped = sum(1 for _, _, running, _, pops in steps if pops % Q + running > Q)
+        print("lap", i, "released before the last step", steps[-1][4], "steps with a wrapped ring", wrapped, "most running", max(s[2] for s in steps))
+        assert len(steps) == c["n"] and steps[-1][4] >= 2 * Q and wrapped >= mm.MIN_COUNT and max(s[2] for s in steps) < Q - 1, i
+
+
+def test_the_plan_of_the_launch_of_fewer_waves():
+    """NSFNET with 320 slots and a ring of 1024 (tests/test_wave_plan.py GEOMETRY): the handle's eight waves per workgroup become six, 14
+    environments three workgroups; at the ring's cap of 4096 slots the handle has two waves and the launch keeps both"""
+    from gpu_support import wave_plan
+    c = mm.FEWER
+    wave_bytes = lambda Q: 6112 + 12 * Q
+    up16 = lambda n: (n + 15) & ~15
+    Q = c["queue_capacity"]
+    p = wave_plan(gated=1, protect=1, max_margin=1, n_steps=c["n"], wave_bytes=wave_bytes(Q), extra_per_wave=up16(4 * Q), wpb=8, B=c["B"])
+    assert (p["family"], p["wpu"], p["nblocks"], p["lds"]) == ("MM", 6, 3, 14320 + 6 * (wave_bytes(Q) + 4 * Q)) and c["B"] % 6
+    p = wave_plan(gated=1, protect=1, max_margin=1, wave_bytes=wave_bytes(4096), extra_per_wave=up16(4 * 4096), wpb=2, B=c["B"])
+    assert p["wpu"] == 2

@@ -258,6 +258,14 @@ def test_batch_is_meaningful(batch, tmp_path):
         high_adm = sum(int(tr["mask"][:, 8:].sum()) for tr, _ in runs)
         high_ref = sum(int((tr["window"][:, 8:] & ~tr["mask"][:, 8:]).sum()) for tr, _ in runs)
         assert high_adm >= sl.MIN_COUNT and high_ref >= sl.MIN_COUNT, (high_adm, high_ref)
+    if batch in sl.WORDS:   # one, three, four and six words per link with k > 8: windows admitted and refused on the paths from 8 up, and
+        # best windows in the last word of the row (the end of the select chains over the chunks)
+        S = runs[0][0]["window"].shape[-1]
+        last = 64 * ((S + 63) // 64 - 1)
+        high_adm = sum(int(tr["mask"][:, 8:].sum()) for tr, _ in runs)
+        high_ref = sum(int((tr["window"][:, 8:] & ~tr["mask"][:, 8:]).sum()) for tr, _ in runs)
+        best_last = sum(int(((tr["best_slot"] >= last) & (tr["best_slot"] < S)).sum()) for tr, _ in runs)
+        assert (S + 63) // 64 in (1, 3, 4, 6) and min(high_adm, high_ref, best_last, fig["best_not_first"]) >= sl.MIN_COUNT, (high_adm, high_ref, best_last, fig)
     if batch == sl.TRI:   # more than 64 services share a link with one path, more than 64 run
         assert max(int(tr["affected"].max()) for tr, _ in runs) > 64 and fig["max_running"] > 64 and fig["admitted_checked"] >= sl.MIN_COUNT, fig
     if not c["protect"]:
