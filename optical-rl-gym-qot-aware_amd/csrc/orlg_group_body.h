@@ -18,6 +18,15 @@
     static_assert(!ASSIGN || (!HBMQ && !DEFER), "the assignment rules belong to the plain kind");
     static_assert(!CUT || ASSIGN, "the fewest-cuts window is an assignment rule");
     static_assert(!USAGE || (ASSIGN && !CUT), "most-used windows and the best-window route are assignment rules of their own");
+    // LEAN keeps two of the step's books on the lanes, because nothing in a lean launch reads them before a ticket ends (DESIGN 2.5,
+    // round 20; orlg_group_plan.h gives the lean body to handles of at most 2 * ORLG_GL bit rates only):
+    // LANE_HIST: lane gl of a row counts the arrivals (h_req) and the accepted provisions (h_acc) with the bit-rate indices gl (low
+    // 16 bits) and gl + 16 (high 16 bits) since the last flush; the four histograms and the eight counters follow from them in
+    // books_flush -- at an episode's end, when the ticket's state leaves, and every ORLG_LEAN_FLUSH_STEPS steps of a ticket, so that no
+    // field overflows.  Between flushes the counters rest in the scalars record, as the graph log's three doubles do
+    // LANE_SUMS: sum_span and sum_gaps are lane partials (group_link_stats, PART): lane 0 of the row starts with the state's
+    // value, every lane adds its own links' differences, and the row sum is formed where orlg_glog_pack and the state store read it
+    constexpr bool LANE_HIST = LEAN, LANE_SUMS = LEAN;
     extern __shared__ __align__(16) unsigned char smem[];
     stage_tables(smem, p);
     const int lane = threadIdx.x & 63;
@@ -141,15 +150,59 @@
     const OrlgEnvScalars *gs = p.scal + env;
     double current_time = gs->current_time, req_arrival = gs->req_arrival, req_holding = gs->req_holding;
     double g_thr = gs->g_throughput, g_comp = gs->g_compactness, g_lu = gs->g_last_update;
-    long long cnt = gs->c[gl & 7];  // counter gl & 7 (lanes 8..15 mirror lanes 0..7)
+    [[maybe_unused]] long long cnt = gs->c[gl & 7];  // counter gl & 7 (lanes 8..15 mirror lanes 0..7); LANE_HIST: not read, the counters stay in the record
     long long sum_bitrate_running = gs->sum_bitrate_running, episodes_done = gs->episodes_done;
     int sum_sh = gs->sum_slots_hops, n_running = gs->n_running;
     int req_src = gs->req_src, req_dst = gs->req_dst, req_br = gs->req_br, req_sid = gs->req_sid;
     int mt_idx = gs->mt_idx, new_service = gs->new_service, q_overflow = gs->q_overflow;
     int ring_pos = gs->ring_pos, ring_cnt = gs->ring_cnt;
     int sum_span = gs->sum_span, sum_gaps = gs->sum_gaps;
+    if (LANE_SUMS && gl != 0) { sum_span = 0; sum_gaps = 0; }   // (lane partials: the state's sums on the row's first lane)
     int eproc = (int)gs->c[2];
     wave_sync();
+    // LANE_HIST: the accumulators, and the flush of the rows `rows` -- the histograms take atomics without return, as everywhere (the
+    // updates of one address stay in program order); the counters are row sums of the accumulators (services) and of accumulator x
+    // bit rate, added to the record by the row's first eight lanes.  `episode`: the flush of an episode's end, which leaves the
+    // episode counters as reset(only_episode_counters=True) with a pending service does (below).  Cold: a few times per environment
+    // and launch.  Its addresses are formed where they are used, from the quad's wave-uniform bases and the row's place in the quad
+    // (cold_row): every one of them is a loop invariant, and the compiler keeps a hoisted invariant in a register or in scratch
+    // across the whole step loop -- the empty asm makes the row's place a value it cannot hoist, and hist_q, hist_row and hist_at
+    // have no use in this body
+    // (lane_one: what the lane adds for a request of bit-rate index br -- 1 in the field of br on the lane of br, 0 elsewhere; br_one:
+    // that of the pending request, which counts at its arrival and, a step later, where it is accepted)
+    [[maybe_unused]] uint32_t h_req = 0u, h_acc = 0u;
+    [[maybe_unused]] auto lane_one = [&](int br) -> uint32_t { return (br & (ORLG_GL - 1)) == gl ? 1u << (br & ORLG_GL) : 0u; };
+    [[maybe_unused]] uint32_t br_one = lane_one(req_br);
+    [[maybe_unused]] auto cold_row = [&]() -> uint32_t {
+        uint32_t r = (uint32_t)(env - env0);
+        asm volatile("" : "+v"(r));
+        return r;
+    };
+    [[maybe_unused]] auto hist_lean = [&](uint32_t row, int which, int i) -> int32_t * {
+        return reinterpret_cast<int32_t *>(reinterpret_cast<char *>(p.hist + (size_t)env0 * 4 * NBR) + ((row * 4u + (uint32_t)which) * (uint32_t)NBR + (uint32_t)i) * 4u);
+    };
+    [[maybe_unused]] auto books_flush = [&](const bool rows, const bool episode) {
+        const int gh = gl + ORLG_GL;
+        const int rate_lo = gl < NBR ? tb.bit_rates[gl] : 0, rate_hi = gh < NBR ? tb.bit_rates[gh] : 0;
+        const int req_lo = (int)(h_req & 0xffffu), req_hi = (int)(h_req >> 16), acc_lo = (int)(h_acc & 0xffffu), acc_hi = (int)(h_acc >> 16);
+        const long long n_req = row_add_i32(req_lo + req_hi), n_acc = row_add_i32(acc_lo + acc_hi);
+        const long long b_req = row_add_i64((long long)req_lo * rate_lo + (long long)req_hi * rate_hi);
+        const long long b_acc = row_add_i64((long long)acc_lo * rate_lo + (long long)acc_hi * rate_hi);
+        if (rows) {
+            const uint32_t row = cold_row();
+            if (gl < NBR && req_lo) { atomicAdd(hist_lean(row, 0, gl), req_lo); atomicAdd(hist_lean(row, 2, gl), req_lo); }
+            if (gh < NBR && req_hi) { atomicAdd(hist_lean(row, 0, gh), req_hi); atomicAdd(hist_lean(row, 2, gh), req_hi); }
+            if (gl < NBR && acc_lo) { atomicAdd(hist_lean(row, 1, gl), acc_lo); atomicAdd(hist_lean(row, 3, gl), acc_lo); }
+            if (gh < NBR && acc_hi) { atomicAdd(hist_lean(row, 1, gh), acc_hi); atomicAdd(hist_lean(row, 3, gh), acc_hi); }
+            if (gl < 8) {
+                int64_t *c = reinterpret_cast<OrlgEnvScalars *>(reinterpret_cast<char *>(p.scal + env0) + row * (uint32_t)sizeof(OrlgEnvScalars))->c + gl;
+                long long v = *c + ((gl & 4) ? ((gl & 1) ? b_acc : b_req) : ((gl & 1) ? n_acc : n_req));
+                if (episode) v = gl == 2 ? 1 : (gl == 6 ? tb.bit_rates[req_br] : ((gl == 3 || gl == 7) ? 0 : v));
+                *c = v;
+            }
+            h_req = 0u; h_acc = 0u;
+        }
+    };
     // LEAN: the graph statistics are logged per accepted provision and worked off in batches (orlg_graph_log.h, group_graph_replay):
     // entry k of the row's environment on lane k of the row, lg_cnt of them.  g_thr, g_comp, g_lu and comp_cur are then names
     // nothing reads: between two replays the three doubles rest in the scalars record, and the body has no use for the compactness
@@ -463,16 +516,20 @@
             sum_sh += n * hops;
             n_running += 1;
             sum_bitrate_running += br_val;
-            cnt += (cidx == 1 || cidx == 3) ? 1 : ((cidx == 5 || cidx == 7) ? br_val : 0);
-            if constexpr (DEFER) {
-                if (gl == 0) { atomicAdd(hist_at(1, req_br), 1); atomicAdd(hist_at(3, req_br), 1); }
+            if constexpr (LANE_HIST) {
+                h_acc += br_one;
             } else {
-                if (gl == 0) { atomicAdd(ghist + NBR + req_br, 1); atomicAdd(ghist + 3 * NBR + req_br, 1); }
+                cnt += (cidx == 1 || cidx == 3) ? 1 : ((cidx == 5 || cidx == 7) ? br_val : 0);
+                if constexpr (DEFER) {
+                    if (gl == 0) { atomicAdd(hist_at(1, req_br), 1); atomicAdd(hist_at(3, req_br), 1); }
+                } else {
+                    if (gl == 0) { atomicAdd(ghist + NBR + req_br, 1); atomicAdd(ghist + 3 * NBR + req_br, 1); }
+                }
             }
         }
         SEC(4);  // statistics at provision
         if (NET)
-            group_link_stats<W, FULL, !LEAN, DEFER, DEFER ? 1 : 0, true>(lane, occ, lst, lint, tb, S, E, rec->link, accepted ? hops : 0,
+            group_link_stats<W, FULL, !LEAN, DEFER, DEFER ? 1 : 0, true, LANE_SUMS>(lane, occ, lst, lint, tb, S, E, rec->link, accepted ? hops : 0,
                                                                            current_time, sum_span, sum_gaps, comp_cur, sum_sh,
                                                                            (double)sum_bitrate_running, g_thr, g_comp, g_lu, llog,
                                                                            &need_replay, lsum, a_slot, n);
@@ -480,7 +537,9 @@
             // _update_network_stats (rmsa_env.py:537-560) of an accepted row, logged: what it consumes, as the pass above left it
             const bool logs = accepted && hops > 0;
             OrlgGraphEntry ne;
-            orlg_glog_pack(ne, current_time, sum_bitrate_running, sum_span, sum_sh, sum_gaps);
+            // (LANE_SUMS: the step's one join of the two partial sums over the row)
+            orlg_glog_pack(ne, current_time, sum_bitrate_running, LANE_SUMS ? row_add_i32(sum_span) : sum_span, sum_sh,
+                           LANE_SUMS ? row_add_i32(sum_gaps) : sum_gaps);
             if (logs && gl == lg_cnt) lg = ne;
             lg_cnt += logs ? 1 : 0;
             if (ballot(lg_cnt >= ORLG_GLOG_CAP) != 0ull) {   // a row's log is full: every row works its log off
@@ -656,12 +715,17 @@
                 new_service = 1;
                 eproc += 1;
                 req_arrival = at; req_holding = r_ht;
-                const int bv = tb.bit_rates[req_br];
-                cnt += (cidx == 0 || cidx == 2) ? 1 : ((cidx == 4 || cidx == 6) ? bv : 0);
-                if constexpr (DEFER) {
-                    if (gl == 0) { atomicAdd(hist_at(0, req_br), 1); atomicAdd(hist_at(2, req_br), 1); }
+                if constexpr (LANE_HIST) {
+                    br_one = lane_one(req_br);
+                    h_req += br_one;
                 } else {
-                    if (gl == 0) { atomicAdd(ghist + req_br, 1); atomicAdd(ghist + 2 * NBR + req_br, 1); }
+                    const int bv = tb.bit_rates[req_br];
+                    cnt += (cidx == 0 || cidx == 2) ? 1 : ((cidx == 4 || cidx == 6) ? bv : 0);
+                    if constexpr (DEFER) {
+                        if (gl == 0) { atomicAdd(hist_at(0, req_br), 1); atomicAdd(hist_at(2, req_br), 1); }
+                    } else {
+                        if (gl == 0) { atomicAdd(ghist + req_br, 1); atomicAdd(ghist + 2 * NBR + req_br, 1); }
+                    }
                 }
             }
 
@@ -756,7 +820,7 @@
                         next_desc = q_n > 0 ? qdesc[q_head] : 0u;
                     }
                     // the window and its links' statistics in one pass, lane = hop (group_release_links; ends with a wave_sync)
-                    group_release_links<W>(lane, occ, lsum, lint, S, r_link, r_hop, r_hops, r_s, r_n, current_time, sum_span, sum_gaps,
+                    group_release_links<W, LANE_SUMS>(lane, occ, lsum, lint, S, r_link, r_hop, r_hops, r_s, r_n, current_time, sum_span, sum_gaps,
                                            llog, need_replay);
                     SEC(11);  // statistics at release: the log replays only
                 } else {
@@ -813,26 +877,45 @@
                 ORLG_GPTR(uint8_t, tb.outs[ORLG_OUT_DONE])[(size_t)(t0 + t) * p.B + env] = done ? 1 : 0;
             if (ballot(done && p.auto_reset)) {
                 // reset(only_episode_counters=True) with a pending service (rmsa_env.py:343-389)
+                // (LANE_HIST: what the lanes hold of the episode that ends goes to the histograms before they are zeroed, and the
+                // flush leaves the episode counters as the statements below leave `cnt`)
+                if constexpr (LANE_HIST) books_flush(done && p.auto_reset, true);
                 if (done && p.auto_reset) {
-                    if constexpr (DEFER) {
+                    if constexpr (LANE_HIST) {
+                        const uint32_t row = cold_row();
+                        for (int i = gl; i < NBR; i += ORLG_GL) { atomicExch(hist_lean(row, 2, i), 0); atomicExch(hist_lean(row, 3, i), 0); }
+                    } else if constexpr (DEFER) {
                         for (int i = gl; i < NBR; i += ORLG_GL) { atomicExch(hist_at(2, i), 0); atomicExch(hist_at(3, i), 0); }
                     } else {
                         for (int i = gl; i < NBR; i += ORLG_GL) { atomicExch(ghist + 2 * NBR + i, 0); atomicExch(ghist + 3 * NBR + i, 0); }
                     }
                     eproc = 1;
                     episodes_done += 1;
-                    const int bv = tb.bit_rates[req_br];
-                    if (cidx == 2) cnt = 1;
-                    if (cidx == 3 || cidx == 7) cnt = 0;
-                    if (cidx == 6) cnt = bv;
+                    if constexpr (!LANE_HIST) {
+                        const int bv = tb.bit_rates[req_br];
+                        if (cidx == 2) cnt = 1;
+                        if (cidx == 3 || cidx == 7) cnt = 0;
+                        if (cidx == 6) cnt = bv;
+                    }
                 }
                 wave_sync();
-                if constexpr (DEFER) {
+                if constexpr (LANE_HIST) {
+                    if (done && p.auto_reset && gl == 0) atomicExch(hist_lean(cold_row(), 2, req_br), 1);
+                } else if constexpr (DEFER) {
                     if (done && p.auto_reset && gl == 0) atomicExch(hist_at(2, req_br), 1);
                 } else {
                     if (done && p.auto_reset && gl == 0) atomicExch(ghist + 2 * NBR + req_br, 1);
                 }
                 wave_sync();
+                if constexpr (LANE_HIST) vm_drain();   // (a cold block ends drained: the flush loaded the counters)
+            }
+        }
+        if constexpr (LANE_HIST) {
+            // a field of the accumulators grows by at most one a step: a ticket of very many steps flushes in time (wave-uniform)
+            static_assert(ORLG_LEAN_FLUSH_STEPS < 0x10000 && (ORLG_LEAN_FLUSH_STEPS & (ORLG_LEAN_FLUSH_STEPS - 1)) == 0, "16-bit fields");
+            if ((t & (ORLG_LEAN_FLUSH_STEPS - 1)) == ORLG_LEAN_FLUSH_STEPS - 1) {
+                books_flush(act, false);
+                vm_drain();
             }
         }
     }
@@ -844,6 +927,10 @@
         SEC(15);  // graph replay
         if (ballot(lg_cnt > 0) != 0ull) group_graph_replay(lane, lg, lg_cnt, p.scal + env, E);
     }
+    // ... and nothing on the lanes: the histograms and the counters complete, the two sums joined (the atomics and the stores are
+    // covered by the wait and the release below, as the state's are)
+    if constexpr (LANE_HIST) books_flush(act, false);
+    [[maybe_unused]] const int span_row = LANE_SUMS ? row_add_i32(sum_span) : sum_span, gaps_row = LANE_SUMS ? row_add_i32(sum_gaps) : sum_gaps;
     // ------------------------------------------------------------------ LDS -> HBM
     SEC(13);  // state store
     wave_sync();
@@ -887,7 +974,9 @@
             }
         }
         OrlgEnvScalars *go = p.scal + env;
-        if (gl < 8) go->c[gl] = cnt;
+        if constexpr (!LANE_HIST) {   // (LANE_HIST: the record has them, books_flush)
+            if (gl < 8) go->c[gl] = cnt;
+        }
         if (gl == 8) {
             go->current_time = current_time;
             go->req_arrival = req_arrival; go->req_holding = req_holding;
@@ -898,7 +987,7 @@
             go->req_src = req_src; go->req_dst = req_dst; go->req_br = req_br; go->req_sid = req_sid;
             go->mt_idx = mt_idx; go->new_service = new_service; go->q_overflow = q_overflow;
             go->ring_pos = ring_pos; go->ring_cnt = ring_cnt;
-            go->sum_span = sum_span; go->sum_gaps = sum_gaps; go->q_head = q_headc;
+            go->sum_span = span_row; go->sum_gaps = gaps_row; go->q_head = q_headc;
             if (q_overflow) *p.err_flag = 1;   // reported by the next entry point that waits for the stream
         }
     }

@@ -32,8 +32,15 @@
 
 #define ORLG_GL 16  // lanes per environment (one DPP row)
 #define ORLG_GE 4   // environments per wave
+#define ORLG_LEAN_FLUSH_STEPS 0x8000   // the lean body's packed bit-rate counts (orlg_group_body.h, LANE_HIST) go to memory at least this often
 
 DEV int row_add_i32(int v) { v += dpp_xor1(v); v += dpp_xor2(v); v += dpp_half_mirror(v); v += dpp_row_mirror(v); return v; }
+// ... of 64-bit terms (the lean body's flushes: cold)
+#define ORLG_DPP_I64(fn, x) (long long)(((u64)(uint32_t)fn((int)((u64)(x) >> 32)) << 32) | (uint32_t)fn((int)(uint32_t)(x)))
+DEV long long row_add_i64(long long v) {
+    v += ORLG_DPP_I64(dpp_xor1, v); v += ORLG_DPP_I64(dpp_xor2, v); v += ORLG_DPP_I64(dpp_half_mirror, v); v += ORLG_DPP_I64(dpp_row_mirror, v);
+    return v;
+}
 // the value of the lane eight places away in the row (row_ror:8): a row's two halves trade places
 DEV int row_swap8_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false); }
 // OR over the eight lanes of a half row, on every lane of it
@@ -191,7 +198,9 @@ DEV bool group_path_candidate(const int lane, const u64 *lsum, const Tab &tb, in
 // group_apply_window's: a link's word w on one lane, and a path never repeats a link, so no word is touched twice in a launch of
 // the pass): the word is cleared in the register it was read into, stored back where the window reaches it, and everything
 // after -- the neighbours' DPP reads included -- sees the cleared words.  No write pass of its own, no second read.
-template <int W, bool LINKF, bool GRAPH, bool DEFER = false, int SUM = 0, bool APPLY = false>
+// PART: sum_span and sum_gaps are LANE PARTIALS of the row's two sums (the lean body, orlg_group_body.h): a link lane adds its own
+// link's differences to its own registers and the pass joins nothing over the row -- integer sums, formed where they are read.
+template <int W, bool LINKF, bool GRAPH, bool DEFER = false, int SUM = 0, bool APPLY = false, bool PART = false>
 DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, const Tab &tb, int S, int E, const uint8_t *links,
                           int nlinks, double now, int &sum_span, int &sum_gaps, double &comp_cur, int sum_sh, double cur_thr,
                           double &g_thr, double &g_comp, double &g_lu, uint4 *llog = nullptr, bool *need_replay = nullptr,
@@ -290,8 +299,13 @@ DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, 
             dspan = nspan - (old & 0xffff);
             dgaps = ngaps - (old >> 16);
         }
-        sum_span += row_add_i32(dspan);
-        sum_gaps += row_add_i32(dgaps);
+        if constexpr (PART) {
+            sum_span += dspan;
+            sum_gaps += dgaps;
+        } else {
+            sum_span += row_add_i32(dspan);
+            sum_gaps += row_add_i32(dgaps);
+        }
         if (LINKF && !DEFER && link_lane && now > 0) {
             double *l_util = lst, *l_ef = lst + E, *l_c = lst + 2 * E, *l_lu = lst + 3 * E;
             const double last_update = l_lu[link];
@@ -335,7 +349,8 @@ DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, 
 // registers; read only where hop < hops), with that path's window.  A row that releases one
 // service has hop = the lane's place in the row; a row that releases two link-disjoint services at once (orlg_group_body.h) gives
 // its lower eight lanes the first one's hops and its upper eight the second one's, and the row sums below cover both.
-template <int W>
+// PART: sum_span and sum_gaps are lane partials, as in group_link_stats: every hop lane adds its own link's differences.
+template <int W, bool PART = false>
 DEV void group_release_links(const int lane, u64 *occ, u64 *lsum, int32_t *lint, int S, const int link, int hop, int hops, int s,
                              int n, double now, int &sum_span, int &sum_gaps, uint4 *llog, bool &need_replay) {
     static_assert(ORLG_MAX_HOPS <= ORLG_GL, "one lane per hop");
@@ -412,8 +427,13 @@ DEV void group_release_links(const int lane, u64 *occ, u64 *lsum, int32_t *lint,
         dspan = nspan - (old & 0xffff);
         dgaps = ngaps - (old >> 16);
     }
-    sum_span += row_add_i32(dspan);
-    sum_gaps += row_add_i32(dgaps);
+    if constexpr (PART) {
+        sum_span += dspan;
+        sum_gaps += dgaps;
+    } else {
+        sum_span += row_add_i32(dspan);
+        sum_gaps += row_add_i32(dgaps);
+    }
     wave_sync();
 }
 

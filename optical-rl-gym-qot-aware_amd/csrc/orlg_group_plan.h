@@ -48,7 +48,10 @@ static inline int orlg_group_usage_wpb(const OrlgGroupLayout &l, int wpb, int W)
     return wpb;
 }
 
-struct OrlgGroupLaunch { int B, n_steps, stats_level, policy, out_mask, br_width; };
+// the lean body keeps its bit-rate histograms on the sixteen lanes of an environment's row, two bit rates per lane (orlg_group_body.h, LANE_HIST)
+enum { ORLG_LEAN_MAX_BIT_RATES = 32 };
+// (n_bit_rates: the handle's; 0 = not said, which orlg_debug_group_plan's callers rely on)
+struct OrlgGroupLaunch { int B, n_steps, stats_level, policy, out_mask, br_width, n_bit_rates = 0; };
 // the tooling environment: ORLG_NO_DEFER, ORLG_NO_CHUNKS, ORLG_NO_LEAN set; ORLG_GROUP_WPB, ORLG_GROUP_CHUNKS (0 = not set)
 struct OrlgGroupOverrides { bool no_defer, no_chunks, no_lean; int wpb, chunks; };
 struct OrlgGroupChoice { OrlgGroupKind kind; int wpb; size_t lds_bytes; bool lean; uint32_t ticket_stride; bool long_rounds; };
@@ -91,8 +94,9 @@ static inline OrlgGroupChoice orlg_group_choose(const OrlgGroupLayout *layouts, 
     if (ov.wpb >= 1 && ov.wpb <= wpb_max) c.wpb = ov.wpb;   // tooling override: waves per workgroup
     c.lds_bytes = orlg_group_lds(layouts[c.kind].shared_bytes, c.wpb, layouts[c.kind].wave_bytes);
     // the lean body of the DEFER instantiations (orlg_rmsa_group_body): first fit over the first path or all of them, no per-step
-    // output at all, discrete bit rates -- what a heuristic's evaluation or a load sweep launches
-    c.lean = df && (a.policy == ORLG_POLICY_SP || a.policy == ORLG_POLICY_SAP) && a.out_mask == 0 && a.br_width == 0 && !ov.no_lean;
+    // output at all, discrete bit rates, no more of them than a row's lanes count -- what a heuristic's evaluation or a load sweep launches
+    c.lean = df && (a.policy == ORLG_POLICY_SP || a.policy == ORLG_POLICY_SAP) && a.out_mask == 0 && a.br_width == 0 && !ov.no_lean &&
+             a.n_bit_rates <= ORLG_LEAN_MAX_BIT_RATES;
     c.ticket_stride = a.n_steps <= 16 ? 1u : 0u;
     return c;
 }
