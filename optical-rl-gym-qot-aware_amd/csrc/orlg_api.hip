@@ -276,6 +276,9 @@ static int rmsa_create(const orlg_topology *t, const orlg_rmsa_config *c, int32_
                 ns[(size_t)b * ORLG_NSLOT_STRIDE + se] = (uint16_t)(n > 65535 ? 65535 : n);
             }
         p.t_nslots = blob.put(ns.data(), ns.size() * 2);
+        e->min_slots = 65535;
+        for (int b = 0; b < NBR; b++)
+            for (int se = 1; se < ORLG_NSLOT_STRIDE; se++) e->min_slots = std::min(e->min_slots, (int)ns[(size_t)b * ORLG_NSLOT_STRIDE + se]);
         p.t_bitrates = blob.put(c->bit_rates, (size_t)NBR * 4);
         {
             std::vector<double> zc((size_t)NBR, 0.0);   // (continuous: no cumulative weights, the table stays in place)

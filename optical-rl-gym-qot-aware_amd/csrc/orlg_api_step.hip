@@ -24,7 +24,7 @@ static bool usage_launch(const OrlgParams &p) {
 }
 
 static int launch_rmsa_group(orlg_env *e, const OrlgParams &p, const OrlgGroupOverrides &ov) {
-    OrlgGroupChoice c = orlg_group_choose(e->group, {p.B, p.n_steps, p.stats_level, p.policy, p.out_mask, p.br_width, p.NBR}, ov, e->num_cu);
+    OrlgGroupChoice c = orlg_group_choose(e->group, {p.B, p.n_steps, p.stats_level, p.policy, p.out_mask, p.br_width, p.NBR, e->min_slots}, ov, e->num_cu);
     const OrlgGroupLayout &l = e->group[c.kind];
     const bool df = c.kind == ORLG_GROUP_DEFER;
     const bool trace = p.tr_arrival != nullptr;   // a request trace: the instantiations that replay it

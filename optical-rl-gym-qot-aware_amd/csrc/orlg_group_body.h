@@ -529,7 +529,7 @@
         }
         SEC(4);  // statistics at provision
         if (NET)
-            group_link_stats<W, FULL, !LEAN, DEFER, DEFER ? 1 : 0, true, LANE_SUMS>(lane, occ, lst, lint, tb, S, E, rec->link, accepted ? hops : 0,
+            group_link_stats<W, FULL, !LEAN, DEFER, DEFER ? 1 : 0, true, LANE_SUMS, LEAN>(lane, occ, lst, lint, tb, S, E, rec->link, accepted ? hops : 0,
                                                                            current_time, sum_span, sum_gaps, comp_cur, sum_sh,
                                                                            (double)sum_bitrate_running, g_thr, g_comp, g_lu, llog,
                                                                            &need_replay, lsum, a_slot, n);

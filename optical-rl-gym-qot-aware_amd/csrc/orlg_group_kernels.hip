@@ -29,6 +29,7 @@
 #include "orlg_cut.h"          // cut_word_key: the fewest-cuts window of the CUT instantiations
 #include "orlg_usage.h"        // usage_prefix, window_word_key: the rule MOST_USED and the route BEST_WINDOW of the USAGE instantiations
 #include "orlg_graph_log.h"    // OrlgGraphEntry, orlg_glog_*: the lean body's logged graph statistics (group_graph_replay below)
+#include "orlg_link_summary.h" // lsum_pack, lsum_unpack, orlg_lsum_provision: a link's summary of the DEFER instantiations
 
 #define ORLG_GL 16  // lanes per environment (one DPP row)
 #define ORLG_GE 4   // environments per wave
@@ -131,15 +132,6 @@ DEV int group_rec_byte(const uint4 r, int i) {
     return (int)((half >> (8 * (i & 7))) & 0xffull);
 }
 
-// A link's summary (DEFER instantiation, LDS only): every integer _update_link_stats consumes, 10 bits each -- free slots, free
-// runs, used runs, first used slot (lmin), end of the last used run (lmax), longest free run, slot 0 free, slot S - 1 free.  With
-// no used slot lmin / lmax are group_link_stats' 0x7fff / 0 and lmin keeps only its low 10 bits: a summary is read at a release
-// only, when the link holds the window (at least one used slot).
-DEV u64 lsum_pack(int freec, int F, int U, int lmin, int lmax, int ml, bool ff, bool lf) {
-    return (u64)((uint32_t)freec | ((uint32_t)F << 10) | ((uint32_t)U << 20)) |
-           ((u64)((uint32_t)(lmin & 0x3ff) | ((uint32_t)lmax << 10) | ((uint32_t)ml << 20) | ((uint32_t)ff << 30) | ((uint32_t)lf << 31)) << 32);
-}
-
 // The longest-run test of a first-fit pass after the first (the lean body of the DEFER instantiations).  A
 // path can hold a window of n slots only if every one of its links has a free run of n, and a link's summary holds its longest
 // free run ml -- exact after every provision (the statistics pass recomputes it), every release (max(ml, L + n + R)) and every
@@ -200,7 +192,16 @@ DEV bool group_path_candidate(const int lane, const u64 *lsum, const Tab &tb, in
 // after -- the neighbours' DPP reads included -- sees the cleared words.  No write pass of its own, no second read.
 // PART: sum_span and sum_gaps are LANE PARTIALS of the row's two sums (the lean body, orlg_group_body.h): a link lane adds its own
 // link's differences to its own registers and the pass joins nothing over the row -- integer sums, formed where they are read.
-template <int W, bool LINKF, bool GRAPH, bool DEFER = false, int SUM = 0, bool APPLY = false, bool PART = false>
+// FROMSUM (the lean body's pass at a provision): the window was WHOLLY FREE on every link of the pass (a first fit's window on an
+// accepted row) and the link's summary is exact, so the rescan produces the longest free run alone -- the one integer that does
+// not follow from the summary (65 % of the updates cut a longest run: DESIGN 2.5, rounds 4 and 15).  A word lane reads its word,
+// clears the window, hands `prev` on and runs the lead / e chain, fstarts and the run loop for seg_max(ml); the used runs, the
+// popcounts, the first / last used slot, slot S - 1 and their three segment reductions are not computed.  The link lane reads
+// the old summary and the two words that hold slot win_s - 1 and slot win_s + win_n -- with the pass's first reads, on every
+// lane and outside every condition: the indices are words of the lane's link whatever the lane's window says, and a lane that
+// is not on reads link 0 -- and orlg_lsum_provision (orlg_link_summary.h) gives the other seven.  The same values as the rescan,
+// so the same bits in the summary, the log entry, the span cache and the two sums.
+template <int W, bool LINKF, bool GRAPH, bool DEFER = false, int SUM = 0, bool APPLY = false, bool PART = false, bool FROMSUM = false>
 DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, const Tab &tb, int S, int E, const uint8_t *links,
                           int nlinks, double now, int &sum_span, int &sum_gaps, double &comp_cur, int sum_sh, double cur_thr,
                           double &g_thr, double &g_comp, double &g_lu, uint4 *llog = nullptr, bool *need_replay = nullptr,
@@ -208,6 +209,7 @@ DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, 
     static_assert(W <= 8, "at least two links per row");
     static_assert(!APPLY || SUM != 2, "the summary rebuild changes no occupancy");
     static_assert(SUM == 0 || (LINKF && DEFER && (SUM == 1 || !GRAPH)), "summaries belong to the deferred instantiation");
+    static_assert(!FROMSUM || (SUM == 1 && APPLY), "the statistics follow from the summary where the pass clears a free window");
     constexpr int NS = ORLG_GL / W;  // links per row and pass
     const int gl = lane & 15;
     const int sl = gl / W, w = gl - sl * W;
@@ -223,6 +225,12 @@ DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, 
         // the link's words sit on consecutive lanes: the neighbours' words arrive by DPP instead of further LDS reads
         u64 x = 0ull;
         if (on) x = occ[__mul24(link, W) + w];
+        [[maybe_unused]] u64 old_sum = 0ull, x_below = 0ull, x_above = 0ull;
+        if constexpr (FROMSUM) {
+            old_sum = lsum[link];
+            x_below = occ[__mul24(link, W) + orlg_lsum_word_below(S, win_s)];
+            x_above = occ[__mul24(link, W) + orlg_lsum_word_above(S, win_s + win_n)];
+        }
         if (APPLY && on) {
             const u64 m = window_mask(win_s, win_n, w);
             x &= ~m;
@@ -243,23 +251,28 @@ DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, 
                 e = nlead == 64 ? 64 + ne : nlead;
             }
         }
-        const bool first_free = x & 1ull;                                                     // meaningful on w == 0
-        // slot S - 1 sits in word (S - 1) >> 6 -- not always the last of the W words (S = 400 runs on the 8-word layout)
-        const uint32_t last_free_bit = w == ((S - 1) >> 6) ? (uint32_t)((x >> ((S - 1) & 63)) & 1ull) : 0u;
-        // ... on the link's first lane: slot S - 1 sits in the link's last word or in the one before it (W = ceil(S / 64), 8 for 7)
-        uint32_t lf = last_free_bit;
-        if (W > 1) lf |= (uint32_t)lane_ahead_i32<(W > 1 ? W - 1 : 1)>((int)last_free_bit);
-        if (W > 2) lf |= (uint32_t)lane_ahead_i32<(W > 2 ? W - 2 : 1)>((int)last_free_bit);
-        const bool last_free = lf != 0u;
+        bool first_free = false, last_free = false;
+        if constexpr (!FROMSUM) {
+            first_free = x & 1ull;                                                            // meaningful on w == 0
+            // slot S - 1 sits in word (S - 1) >> 6 -- not always the last of the W words (S = 400 runs on the 8-word layout)
+            const uint32_t last_free_bit = w == ((S - 1) >> 6) ? (uint32_t)((x >> ((S - 1) & 63)) & 1ull) : 0u;
+            // ... on the link's first lane: slot S - 1 sits in the link's last word or in the one before it (W = ceil(S / 64), 8 for 7)
+            uint32_t lf = last_free_bit;
+            if (W > 1) lf |= (uint32_t)lane_ahead_i32<(W > 1 ? W - 1 : 1)>((int)last_free_bit);
+            if (W > 2) lf |= (uint32_t)lane_ahead_i32<(W > 2 ? W - 2 : 1)>((int)last_free_bit);
+            last_free = lf != 0u;
+        }
         if (on) {
-            u64 u = ~x & valid_mask(S, w);
             u64 carry_f = w > 0 ? (prev >> 63) : 0ull;
-            u64 carry_u = w > 0 ? ((~prev) >> 63) : 0ull;
             u64 fstarts = x & ~((x << 1) | carry_f);
-            u64 ustarts = u & ~((u << 1) | carry_u);
-            packed = (uint32_t)(popc64(x) | (popc64(fstarts) << 10) | (popc64(ustarts) << 20));  // free slots, free runs, used runs
-            ilo = u ? (uint32_t)(0x7fff - (64 * w + ctz64(u))) : 0u;
-            hi = u ? (uint32_t)(64 * w + 64 - clz64(u)) : 0u;
+            if constexpr (!FROMSUM) {
+                u64 u = ~x & valid_mask(S, w);
+                u64 carry_u = w > 0 ? ((~prev) >> 63) : 0ull;
+                u64 ustarts = u & ~((u << 1) | carry_u);
+                packed = (uint32_t)(popc64(x) | (popc64(fstarts) << 10) | (popc64(ustarts) << 20));  // free slots, free runs, used runs
+                ilo = u ? (uint32_t)(0x7fff - (64 * w + ctz64(u))) : 0u;
+                hi = u ? (uint32_t)(64 * w + 64 - clz64(u)) : 0u;
+            }
             if (LINKF) {
                 u64 st = fstarts;
                 while (st) {
@@ -270,10 +283,19 @@ DEV void group_link_stats(const int lane, u64 *occ, double *lst, int32_t *lint, 
                 }
             }
         }
-        packed = seg_add<W>(packed);
-        const int lmin = 0x7fff - (int)seg_max<W>(ilo), lmax = (int)seg_max<W>(hi);
-        if (LINKF) ml = seg_max<W>(ml);
-        const int freec = (int)(packed & 0x3ff), F = (int)((packed >> 10) & 0x3ff), U = (int)(packed >> 20);
+        int freec, F, U, lmin, lmax;
+        if constexpr (FROMSUM) {
+            ml = seg_max<W>(ml);
+            const int win_e = win_s + win_n;
+            const OrlgLinkSummary r = orlg_lsum_provision(lsum_unpack(old_sum), S, win_s, win_n, orlg_lsum_free_below(x_below, S, win_s),
+                                                          orlg_lsum_free_above(x_above, S, win_e), (int)ml);
+            freec = r.freec, F = r.F, U = r.U, lmin = r.lmin, lmax = r.lmax, first_free = r.ff, last_free = r.lf;
+        } else {
+            packed = seg_add<W>(packed);
+            lmin = 0x7fff - (int)seg_max<W>(ilo), lmax = (int)seg_max<W>(hi);
+            if (LINKF) ml = seg_max<W>(ml);
+            freec = (int)(packed & 0x3ff), F = (int)((packed >> 10) & 0x3ff), U = (int)(packed >> 20);
+        }
         const bool link_lane = on && w == 0;  // one lane per link carries on
         if (SUM != 0 && link_lane) lsum[link] = lsum_pack(freec, F, U, lmin, lmax, (int)ml, first_free, last_free);
         if (SUM == 2) { wave_sync(); continue; }

@@ -50,8 +50,10 @@ static inline int orlg_group_usage_wpb(const OrlgGroupLayout &l, int wpb, int W)
 
 // the lean body keeps its bit-rate histograms on the sixteen lanes of an environment's row, two bit rates per lane (orlg_group_body.h, LANE_HIST)
 enum { ORLG_LEAN_MAX_BIT_RATES = 32 };
-// (n_bit_rates: the handle's; 0 = not said, which orlg_debug_group_plan's callers rely on)
-struct OrlgGroupLaunch { int B, n_steps, stats_level, policy, out_mask, br_width, n_bit_rates = 0; };
+// (n_bit_rates: the handle's; 0 = not said, which orlg_debug_group_plan's callers rely on.  min_slots: the smallest window the
+// handle's slots table holds, 1 = not said: the lean body's pass at a provision takes the links' statistics from their summaries
+// (group_link_stats, FROMSUM), which holds for a window of at least one slot -- the table's 0 for a negative bit rate is none)
+struct OrlgGroupLaunch { int B, n_steps, stats_level, policy, out_mask, br_width, n_bit_rates = 0, min_slots = 1; };
 // the tooling environment: ORLG_NO_DEFER, ORLG_NO_CHUNKS, ORLG_NO_LEAN set; ORLG_GROUP_WPB, ORLG_GROUP_CHUNKS (0 = not set)
 struct OrlgGroupOverrides { bool no_defer, no_chunks, no_lean; int wpb, chunks; };
 struct OrlgGroupChoice { OrlgGroupKind kind; int wpb; size_t lds_bytes; bool lean; uint32_t ticket_stride; bool long_rounds; };
@@ -96,7 +98,7 @@ static inline OrlgGroupChoice orlg_group_choose(const OrlgGroupLayout *layouts, 
     // the lean body of the DEFER instantiations (orlg_rmsa_group_body): first fit over the first path or all of them, no per-step
     // output at all, discrete bit rates, no more of them than a row's lanes count -- what a heuristic's evaluation or a load sweep launches
     c.lean = df && (a.policy == ORLG_POLICY_SP || a.policy == ORLG_POLICY_SAP) && a.out_mask == 0 && a.br_width == 0 && !ov.no_lean &&
-             a.n_bit_rates <= ORLG_LEAN_MAX_BIT_RATES;
+             a.n_bit_rates <= ORLG_LEAN_MAX_BIT_RATES && a.min_slots >= 1;
     c.ticket_stride = a.n_steps <= 16 ? 1u : 0u;
     return c;
 }
